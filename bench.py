@@ -13,15 +13,20 @@ replica and the ranks meet in ONE exchange step per optimiser step (default: an 
 masks and two all-reduces of the small gradients; "weak" scaling: views per step = N).
 value = views (fwd+bwd) per second over the whole job.
 
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP-event timed inside the timed region) and
-`cpu_baseline` (the CPU oracle, N=1 only).  At N > 1 the line also carries `rccl_ranks` (ranks a real all-reduce reached), `per_rank_ms_per_step`,
-`exchange`, `launch` and `rccl_microbench` (the step's collectives alone at the step's sizes).
+A plain run sets up, warms up (W untimed steps), times exactly K steps with nothing else on the device, writes the outputs of the last
+timed step when `--dump-outputs DIR` is given, and prints ONE JSON line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (wall time of one timed step) and the workload in `config`.  At N > 1 the line also carries `rccl_ranks` (ranks a real
+all-reduce reached), `per_rank_ms_per_step`, `exchange` and `launch`.
 
-The process that measures the contract line measures nothing else.  At N = 1 it then runs SURVEY 8d's literal config-3 schedule (1.5M -> 2.0M
-Gaussians by five extend() appends, the reference's learning rates) in a SECOND process and puts it into `config.growth_schedule` beside the
-stationary line; `--extras` adds the secondary legs (views_cycle, math_modes, other_host_path, graphed, joint_pose_step, C++ hosts) the same way;
-`--no-extras` runs neither.  A THIRD process (round 6) measures the reference's unmodified host on the drop-in boundary (`dropin_host`,
-`config.dropin_host`).  The legs themselves live in bench_legs.py; this file is the contract line.
+`--full` measures everything beside the headline as well: `roofline` (the two longest kernels of an instrumented warm-up pass, HIP-event timed
+inside the timed region), `cpu_baseline` (the CPU oracle, N=1 only), `value_long` (the same step over a >= 1 s window) and, at N > 1,
+`rccl_microbench` (the step's collectives alone at the step's sizes) and a per-kernel roofline.  At N = 1 it then runs SURVEY 8d's literal
+config-3 schedule (1.5M -> 2.0M Gaussians by five extend() appends, the reference's learning rates) in a SECOND process and puts it into
+`config.growth_schedule` beside the stationary line, and a THIRD process measures the reference's unmodified host on the drop-in boundary
+(`dropin_host`, `config.dropin_host`); `--no-extras` runs neither.  `--extras` adds the secondary legs (views_cycle, math_modes,
+other_host_path, graphed, joint_pose_step, C++ hosts) the same way.  The legs themselves live in bench_legs.py; this file is the contract line.
+
+`--dump-outputs DIR` writes what the timed path handed its caller after the last timed step as `DIR/<name>.npy` (dump_outputs()).
 """
 import argparse
 import json
@@ -199,11 +204,19 @@ def main():
                          "results are bit-identical to the insertion order (tests/test_morton_order_gpu.py).  insertion: the rows as generated")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="the contract line only: no second process at all (neither the growth-schedule leg nor --extras)")
-    ap.add_argument("--extras", action="store_true", help="after the contract measurements, run the secondary legs (views_cycle, math_modes, other_host_path, graphed, "
+    ap.add_argument("--extras", action="store_true", help="with --full: after the contract measurements, run the secondary legs (views_cycle, math_modes, other_host_path, graphed, "
                                                           "joint_pose_step, cpp hosts) in a SECOND process and merge its results into the line")
     ap.add_argument("--leg", default=None, choices=["growth_schedule", "extras", "dropin"], help=argparse.SUPPRESS)   # child mode: one leg process
-    ap.add_argument("--profile-all", action="store_true", help="HIP-event time every kernel inside the timed region (adds overhead)")
+    ap.add_argument("--profile-all", action="store_true", help="HIP-event time every kernel inside the timed region (adds overhead; --full)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: roofline, cpu_baseline, value_long, the N > 1 per-kernel pass and "
+                                                        "collectives alone, and the growth_schedule / dropin_host legs (off: set up, warm up, time, print)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step handed its caller "
+                                                                        "(loss terms, visibility mask, updated parameters) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if (args.profile_all or args.extras) and not args.full:
+        ap.error("--profile-all and --extras are --full measurements: add --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))   # `python bench.py --gpus N`, the shape of the driver's N = 1 command: spawn the N ranks ourselves
@@ -290,10 +303,11 @@ def main():
         tcw = torch.from_numpy(cam.world_view_transform[3, :3].copy())
 
     graphed = dict(gs=None)
+    last = {}   # what the latest step handed back to its caller (--dump-outputs)
 
     def step():
         if graphed["gs"] is not None:
-            graphed["gs"].step()
+            last["terms"] = graphed["gs"].step()
             return None
         if args.mode == "slam":
             slam["it"] += 1
@@ -307,8 +321,10 @@ def main():
                 slam["warm"] = True
         if args.mode in ("train", "slam"):
             if host["mode"] == "fused":
-                return trainer.training_step_fused(model, cam, gt, bg, adam_in_backward=not args.split_adam)[1]
-            return trainer.training_step(model, cam, gt, bg)[1]
+                last["terms"], v = trainer.training_step_fused(model, cam, gt, bg, adam_in_backward=not args.split_adam)
+                return v
+            last["loss"], v = trainer.training_step(model, cam, gt, bg)
+            return v
         return trainer.render_fwd_bwd(model, cam, dL, bg)
 
     def sync_all():
@@ -333,14 +349,15 @@ def main():
             step()
         torch.cuda.synchronize()
     _trace("model on the device; warm-up")
-    # ---- warm-up (untimed); the last warm-up steps double as the per-kernel breakdown pass
-    nprof = min(3, args.warmup)
+    # ---- warm-up (untimed); with --full the last warm-up steps double as the per-kernel breakdown pass
+    nprof = min(3, args.warmup) if args.full else 0
     for _ in range(args.warmup - nprof):
         step()
     torch.cuda.synchronize()
-    _lib.profile_reset()
-    _lib.profile_enable(True)
     vis = None
+    if args.full:
+        _lib.profile_reset()
+        _lib.profile_enable(True)
     for _ in range(nprof):
         vis = step()
     breakdown = _lib.profile_collect() if nprof else {}
@@ -355,19 +372,20 @@ def main():
             step()
 
     _trace("timed region")
-    # ---- timed region: exactly K steps, dominant kernel bracketed by HIP events on its launch stream
+    # ---- timed region: exactly K steps (--full: the two candidate kernels bracketed by HIP events on their launch stream)
     dist_on = trainer._dist_on() and args.mode == "train" and args.host == "fused"
     if dist_on:
         trainer.DIST_TIMING = {}
-    _lib.profile_reset()
-    _lib.profile_enable(True, only=None if args.profile_all else candidates)
+    if args.full:
+        _lib.profile_reset()
+        _lib.profile_enable(True, only=None if args.profile_all else candidates)
     sync_all()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         vis = step()
     sync_all()
     t1 = time.perf_counter()
-    timed = _lib.profile_collect()
+    timed = _lib.profile_collect() if args.full else {}
     _lib.profile_enable(False)
     exchange = None
     if dist_on:
@@ -391,8 +409,14 @@ def main():
                                        "Gaussians in a one-rank group, where the collectives are copies",
                         "exposed_fraction_upper_bound": round(tail / max(comp + tail, 1e-9), 4), "bytes_sent_per_rank_per_step": None if sent is None else int(sent),
                         "world": n}
+    if graphed["gs"] is not None:
+        assert graphed["gs"].check() == 0, "a timed step did not fit its capacity buffers"
+        last["visible"] = graphed["gs"].visible
+        graphed["gs"] = None
+    if args.dump_outputs and rank == 0:   # before anything else runs a step: the outputs of the LAST timed step
+        dump_outputs(args.dump_outputs, model, args.mode, dict(last, visible=last.get("visible", vis)))
     timed_all = None
-    if dist_on and not args.profile_all:
+    if dist_on and args.full and not args.profile_all:
         # the N > 1 compute leg gets a per-kernel roofline of its own (sh_grad_from_rgb, the split Adam, preprocess_bwd without Adam): a short
         # fully instrumented pass AFTER the timed region
         _lib.profile_reset()
@@ -402,169 +426,167 @@ def main():
         sync_all()
         timed_all = _lib.profile_collect()
         _lib.profile_enable(False)
-    if graphed["gs"] is not None:
-        assert graphed["gs"].check() == 0, "a timed step did not fit its capacity buffers"
-        graphed["gs"] = None
     dt = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     if world > 1:
         torch.distributed.all_reduce(dt, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(dt.item())
 
-    _trace(f"timed region done: {1e3 * (t1 - t0) / args.steps:.3f} ms/step; unit counts")
-    # ---- unit counts of this workload (one extra forward, untimed), taken RIGHT AFTER the timed steps: the secondary legs below train the map
-    # further, and the counts (live instances above all) drift with it — the roofline and the replayed counters must describe the timed region
-    with torch.no_grad():
-        from gaussian_lic_amd.rasterizer import render
-        image, _, _, visible, radii = render(cam, model, bg)
-    torch.cuda.synchronize()
-    # R and B of the last forward are returned by the C-ABI; re-run through the functional API to read them
-    from gaussian_lic_amd import rasterizer as rz
-    rs = rz.GaussianRasterizationSettings(H, W, float(cam.tanfovx), float(cam.tanfovy), float(cam.limx_neg), float(cam.limx_pos),
-                                          float(cam.limy_neg), float(cam.limy_pos), bg, 1.0, cam.d_world_view_transform,
-                                          cam.d_full_proj_transform, 3, cam.d_camera_center)
-    with torch.no_grad():
-        e = torch.empty(0, device=dev)
-        Rn, Bn = rz.rasterize_gaussians(bg, model.get_xyz(), e, model.get_opacity(), model.get_scaling(), model.get_rotation(), 1.0, e,
-                                        rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, H, W, rs.limx_neg, rs.limx_pos,
-                                        rs.limy_neg, rs.limy_pos, model.get_features_dc(), model.get_features_rest(), 3, rs.campos,
-                                        False, False, False)[:2]
+    _trace(f"timed region done: {1e3 * (t1 - t0) / args.steps:.3f} ms/step" + ("; unit counts" if args.full else ""))
     P = model.P
-    stats = dict(P=P, V=int(visible.sum().item()), R=int(Rn), B=int(Bn), N=W * H, T=((W + 15) // 16) * ((H + 15) // 16), K=16, strict=strict_mode,
-                 nv=world, Vu=int(vis.sum().item()) if (vis is not None and torch.is_tensor(vis)) else int(visible.sum().item()))   # (N > 1: `vis` of the last step is the OR over the views)
-    try:   # instances / buckets in front of their tile's last contributor: what the blend kernels really process
+    stats, roofline, cpu = {}, None, None
+    if args.full:
+        # ---- unit counts of this workload (one extra forward, untimed), taken RIGHT AFTER the timed steps: the secondary legs below train the map
+        # further, and the counts (live instances above all) drift with it — the roofline and the replayed counters must describe the timed region
         with torch.no_grad():
-            fwd = rz.rasterize_gaussians(bg, model.get_xyz(), e, model.get_opacity(), model.get_scaling(), model.get_rotation(), 1.0, e,
-                                         rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, H, W, rs.limx_neg, rs.limx_pos,
-                                         rs.limy_neg, rs.limy_pos, model.get_features_dc(), model.get_features_rest(), 3, rs.campos, False, False, False)
-            dbg = rz.debug_export(rs, P, 15, fwd[0], fwd[1], fwd[5], fwd[6], fwd[7], fwd[8], what=("ranges", "max_contrib"))
-        n_t = (dbg["ranges"][:, 1] - dbg["ranges"][:, 0]).long()
-        live_b = (dbg["max_contrib"].long() + 63) // 64
-        stats["B32"] = int(((n_t + 31) // 32).sum().item())   # the reference's 32-entry buckets (SURVEY 8d's B)
-        stats["B_live"] = int(live_b.sum().item())
-        stats["R_live"] = int(torch.minimum(n_t, 64 * live_b).sum().item())
-        del fwd, dbg
-    except Exception:
-        pass
-
-
-    # ---- the same K steps through the other host path (reported next to `value`, not part of it)
-    def timed_loop(fn, n):
-        for _ in range(3):
-            fn()
-        sync_all()
-        o0 = time.perf_counter()
-        for _ in range(n):
-            fn()
-        sync_all()
-        odt = torch.tensor([time.perf_counter() - o0], dtype=torch.float64, device=dev)
-        if world > 1:
-            torch.distributed.all_reduce(odt, op=torch.distributed.ReduceOp.MAX)
-        return float(odt.item())
-
-    # ---- the same step over a window of at least one second (the driver's --steps 20 is a 50 ms window): reported beside `value`
-    _trace("roofline / cpu_baseline")
-    # ---- roofline of the dominant kernel (and, beside it, of the runner-up among the two that were timed)
-    fused_adam = args.mode in ("train", "slam") and args.host == "fused" and world == 1
-    pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    pmc, pmc_units_ok = None, False
-    if os.path.exists(pmc_path):
-        try:
-            pmc = json.load(open(pmc_path))
-            # the counters are replayed only when they were collected on THIS workload: same scene, and the unit counts the kernels' work
-            # depends on (visible Gaussians, instances, live instances / buckets) within 2 % of this run's — otherwise traffic is null
-            pu = pmc.get("units") or {}
-            pmc_units_ok = (pmc.get("workload") == f"{args.scene}-{P}-{W}x{H}" and strict_mode == bool(pmc.get("strict", True)) and
-                            pmc.get("map_order", "insertion") == args.map_order and
-                            all(k in pu and stats.get(k) and abs(pu[k] - stats[k]) <= 0.02 * stats[k] for k in ("V", "R", "R_live", "B_live")))
+            from gaussian_lic_amd.rasterizer import render
+            image, _, _, visible, radii = render(cam, model, bg)
+        torch.cuda.synchronize()
+        # R and B of the last forward are returned by the C-ABI; re-run through the functional API to read them
+        from gaussian_lic_amd import rasterizer as rz
+        rs = rz.GaussianRasterizationSettings(H, W, float(cam.tanfovx), float(cam.tanfovy), float(cam.limx_neg), float(cam.limx_pos),
+                                              float(cam.limy_neg), float(cam.limy_pos), bg, 1.0, cam.d_world_view_transform,
+                                              cam.d_full_proj_transform, 3, cam.d_camera_center)
+        with torch.no_grad():
+            e = torch.empty(0, device=dev)
+            Rn, Bn = rz.rasterize_gaussians(bg, model.get_xyz(), e, model.get_opacity(), model.get_scaling(), model.get_rotation(), 1.0, e,
+                                            rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, H, W, rs.limx_neg, rs.limx_pos,
+                                            rs.limy_neg, rs.limy_pos, model.get_features_dc(), model.get_features_rest(), 3, rs.campos,
+                                            False, False, False)[:2]
+        stats = dict(P=P, V=int(visible.sum().item()), R=int(Rn), B=int(Bn), N=W * H, T=((W + 15) // 16) * ((H + 15) // 16), K=16, strict=strict_mode,
+                     nv=world, Vu=int(vis.sum().item()) if (vis is not None and torch.is_tensor(vis)) else int(visible.sum().item()))   # (N > 1: `vis` of the last step is the OR over the views)
+        try:   # instances / buckets in front of their tile's last contributor: what the blend kernels really process
+            with torch.no_grad():
+                fwd = rz.rasterize_gaussians(bg, model.get_xyz(), e, model.get_opacity(), model.get_scaling(), model.get_rotation(), 1.0, e,
+                                             rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, H, W, rs.limx_neg, rs.limx_pos,
+                                             rs.limy_neg, rs.limy_pos, model.get_features_dc(), model.get_features_rest(), 3, rs.campos, False, False, False)
+                dbg = rz.debug_export(rs, P, 15, fwd[0], fwd[1], fwd[5], fwd[6], fwd[7], fwd[8], what=("ranges", "max_contrib"))
+            n_t = (dbg["ranges"][:, 1] - dbg["ranges"][:, 0]).long()
+            live_b = (dbg["max_contrib"].long() + 63) // 64
+            stats["B32"] = int(((n_t + 31) // 32).sum().item())   # the reference's 32-entry buckets (SURVEY 8d's B)
+            stats["B_live"] = int(live_b.sum().item())
+            stats["R_live"] = int(torch.minimum(n_t, 64 * live_b).sum().item())
+            del fwd, dbg
         except Exception:
-            pmc = None
-    units_now = {k: stats.get(k) for k in ("P", "V", "R", "R_live", "B_live")}
+            pass
 
-    def hbm_roofline(kname):
-        """`bound` is "hbm" for every kernel of this path (integer / fp32 streaming work, no MFMA): achieved = ALGORITHMIC bytes of a launch / its
-        average duration by HIP events inside the timed region, frac = achieved / 8 TB/s.  For the two blend kernels that fraction is small because
-        they are bound by VALU issue and latency, not by bytes: a model of that sits beside it as `valu_model`, never as `frac`."""
-        k_ms, k_n = timed.get(kname, (0.0, 0))
-        avg_ms = k_ms / max(k_n, 1)
-        abytes = algorithmic_bytes("preprocess_bwd+adam" if (kname == "preprocess_bwd" and fused_adam) else kname, stats)
-        if kname == "adam" and dist_on and trainer.exchange_mode() == "rank1":
-            abytes = algorithmic_bytes("adam_small", stats)   # rank-1 exchange: features_dc / features_rest are updated inside sh_grad_from_rgb
-        if kname == "adam" and k_n > args.steps:
-            abytes /= round(k_n / args.steps)   # N > 1: the optimiser runs once per exchanged segment; the formula is per STEP, the time per launch
-        achieved = abytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        # HBM traffic and VALU instruction counts cannot be measured from inside this process (PMC counters need rocprofv3 around it): they are
-        # REPLAYED from the committed profile of the same workload and labelled with the file they come from; null when the workload differs.
-        traffic, traffic_src = None, None
-        scan_on = strict_mode and os.environ.get("GSLIC_BWD_SCAN", "1") != "0"
-        if pmc is not None and pmc_units_ok:
-            pu = pmc.get("units") or {}
-            for key in (f"{kname}_scan_kernel" if scan_on else None, f"{kname}_tail_kernel", f"{kname}_kernel", kname):
-                hit = [v for n, v in pmc.get("kernels", {}).items() if key and n.split("<")[0].strip() == key]
-                if hit and traffic is None:
-                    traffic = hit[0]["hbm_bytes_per_launch"]
-                    traffic_src = (f"profiles/pmc_traffic.json@{pmc.get('tag', 'untagged')} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, calibrated on a "
-                                   f"1 GiB copy; collected at V={pu.get('V')} R={pu.get('R')} R_live={pu.get('R_live')} B_live={pu.get('B_live')})")
-        r = dict(bound="hbm", kernel=kname, achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s",
-                 frac=round(achieved / HBM_PEAK_GBS, 5), traffic=traffic, traffic_source=traffic_src, algorithmic_bytes_per_launch=abytes,
-                 avg_launch_ms=round(avg_ms, 4), launches_timed=int(k_n), ms_in_timed_region=round(k_ms, 3),
-                 timing="HIP events around every launch of the kernel inside the timed region", units=units_now)
-        if kname in ("render_fwd", "render_bwd"):
-            cpi = VALU_CYCLES_PER_INST["render_bwd" if (kname == "render_bwd" and scan_on) else ("render_bwd_pipeline" if kname == "render_bwd" else "render_fwd")]
-            r["valu_model"] = dict(modelled_issue_cycles_per_inst=cpi, shader_clock_ghz=SHADER_CLOCK_GHZ, simds=1024,
-                                   note="NOT the roofline fraction.  VALU instructions per launch (rocprofv3 SQ_INSTS_VALU of the same workload) x modelled issue "
-                                        "cycles per instruction (instruction mix of the inner loop x tools/ubench/issue_rate) / (launch duration x 1024 SIMDs x "
-                                        "clock): an upper bound on how issue-bound the kernel is — it counts the set-up code's instructions too, and timed by "
-                                        "elimination (profiles/r04y_bwd_scan_by_elimination.log) the row-scan backward's inner loops are 37 % of its time")
+
+        # ---- the same K steps through the other host path (reported next to `value`, not part of it)
+        def timed_loop(fn, n):
+            for _ in range(3):
+                fn()
+            sync_all()
+            o0 = time.perf_counter()
+            for _ in range(n):
+                fn()
+            sync_all()
+            odt = torch.tensor([time.perf_counter() - o0], dtype=torch.float64, device=dev)
+            if world > 1:
+                torch.distributed.all_reduce(odt, op=torch.distributed.ReduceOp.MAX)
+            return float(odt.item())
+
+        # ---- the same step over a window of at least one second (the driver's --steps 20 is a 50 ms window): reported beside `value`
+        _trace("roofline / cpu_baseline")
+        # ---- roofline of the dominant kernel (and, beside it, of the runner-up among the two that were timed)
+        fused_adam = args.mode in ("train", "slam") and args.host == "fused" and world == 1
+        pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        pmc, pmc_units_ok = None, False
+        if os.path.exists(pmc_path):
             try:
-                import ast
-                import glob
-                sq_files = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_sq_counters.txt")))   # the newest tag sorts last
-                for line in (open(sq_files[-1]) if sq_files else []):
-                    name, _, rest = line.partition(" {")
-                    if name.split("<")[0].strip() in (f"{kname}_kernel", f"{kname}_tail_kernel", f"{kname}_scan_kernel" if scan_on else "-") and pmc_units_ok:
-                        c = ast.literal_eval("{" + rest.strip())
-                        insts = c["SQ_INSTS_VALU"] * 32.0   # the extract averages per shader engine; 32 engines
-                        cycles = 1024.0 * avg_ms * 1e-3 * SHADER_CLOCK_GHZ * 1e9
-                        r["valu_model"].update(valu_insts_per_launch=insts, counters_source="profiles/" + os.path.basename(sq_files[-1]),
-                                               simd_cycles_per_valu_inst=round(cycles / insts, 2) if insts else None,
-                                               issue_frac_modelled=round(insts * cpi / cycles, 4) if cycles else None)
+                pmc = json.load(open(pmc_path))
+                # the counters are replayed only when they were collected on THIS workload: same scene, and the unit counts the kernels' work
+                # depends on (visible Gaussians, instances, live instances / buckets) within 2 % of this run's — otherwise traffic is null
+                pu = pmc.get("units") or {}
+                pmc_units_ok = (pmc.get("workload") == f"{args.scene}-{P}-{W}x{H}" and strict_mode == bool(pmc.get("strict", True)) and
+                                pmc.get("map_order", "insertion") == args.map_order and
+                                all(k in pu and stats.get(k) and abs(pu[k] - stats[k]) <= 0.02 * stats[k] for k in ("V", "R", "R_live", "B_live")))
             except Exception:
-                pass
-        return r
+                pmc = None
+        units_now = {k: stats.get(k) for k in ("P", "V", "R", "R_live", "B_live")}
 
-    tie = False
-    if len(candidates) > 1 and all(k in timed for k in candidates):
-        t_a, t_b = timed[candidates[0]][0], timed[candidates[1]][0]
-        dominant = max(candidates, key=lambda k: timed[k][0])
-        # Within 5 % of each other the order is run-to-run noise (same box, same script: preprocess_bwd 434.8 us by HIP events and 452.7 under
-        # rocprofv3, render_bwd 440.4 / 442.6: profiles/r06z_*): the tie goes to the kernel that moves more bytes — the one the HBM roofline binds —
-        # and the other sits beside it as `runner_up` with its own time, bytes and fraction.
-        if abs(t_a - t_b) <= 0.05 * max(t_a, t_b):
-            tie = True
-            fa = args.mode in ("train", "slam") and args.host == "fused" and world == 1
-            ab = {k: algorithmic_bytes("preprocess_bwd+adam" if (k == "preprocess_bwd" and fa) else k, stats) for k in candidates}
-            dominant = max(candidates, key=lambda k: ab[k])
-    roofline = hbm_roofline(dominant)
-    others = [k for k in candidates if k != dominant]
-    if others:
-        ru = hbm_roofline(others[0])
-        roofline["runner_up"] = {k: ru[k] for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch",
-                                                     "avg_launch_ms", "launches_timed", "ms_in_timed_region")}
-        roofline["dominant_rule"] = ("the longer of the two longest kernels over the K timed steps (HIP events around both)" if not tie else
-                                     "the two longest kernels are within 5 % of each other over the K timed steps (HIP events around both; their order is "
-                                     "run-to-run noise): named is the one that moves more algorithmic bytes, the other is `runner_up`")
-    # the whole step against the HBM peak on SURVEY 8d's A_view (the survey's figure of merit): algorithmic bytes of one view / ms_per_step
-    av = a_view_bytes(stats)
-    step_ms = 1e3 * elapsed / args.steps
-    roofline["step"] = dict(algorithmic_bytes=av["A_view"], parts={k: v for k, v in av.items() if k != "A_view"},
-                            achieved_TBps=round(av["A_view"] * world / (step_ms * 1e-3) / 1e12, 3) if step_ms > 0 else None,
-                            frac=round(av["A_view"] * world / (step_ms * 1e-3) / 1e9 / (HBM_PEAK_GBS * world), 4) if step_ms > 0 else None,
-                            note="SURVEY.md 8d A_view at this run's P, V, R, B32, N, T (per view; N > 1: per GPU) / ms_per_step / 8 TB/s")
+        def hbm_roofline(kname):
+            """`bound` is "hbm" for every kernel of this path (integer / fp32 streaming work, no MFMA): achieved = ALGORITHMIC bytes of a launch / its
+            average duration by HIP events inside the timed region, frac = achieved / 8 TB/s.  For the two blend kernels that fraction is small because
+            they are bound by VALU issue and latency, not by bytes: a model of that sits beside it as `valu_model`, never as `frac`."""
+            k_ms, k_n = timed.get(kname, (0.0, 0))
+            avg_ms = k_ms / max(k_n, 1)
+            abytes = algorithmic_bytes("preprocess_bwd+adam" if (kname == "preprocess_bwd" and fused_adam) else kname, stats)
+            if kname == "adam" and dist_on and trainer.exchange_mode() == "rank1":
+                abytes = algorithmic_bytes("adam_small", stats)   # rank-1 exchange: features_dc / features_rest are updated inside sh_grad_from_rgb
+            if kname == "adam" and k_n > args.steps:
+                abytes /= round(k_n / args.steps)   # N > 1: the optimiser runs once per exchanged segment; the formula is per STEP, the time per launch
+            achieved = abytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            # HBM traffic and VALU instruction counts cannot be measured from inside this process (PMC counters need rocprofv3 around it): they are
+            # REPLAYED from the committed profile of the same workload and labelled with the file they come from; null when the workload differs.
+            traffic, traffic_src = None, None
+            scan_on = strict_mode and os.environ.get("GSLIC_BWD_SCAN", "1") != "0"
+            if pmc is not None and pmc_units_ok:
+                pu = pmc.get("units") or {}
+                for key in (f"{kname}_scan_kernel" if scan_on else None, f"{kname}_tail_kernel", f"{kname}_kernel", kname):
+                    hit = [v for n, v in pmc.get("kernels", {}).items() if key and n.split("<")[0].strip() == key]
+                    if hit and traffic is None:
+                        traffic = hit[0]["hbm_bytes_per_launch"]
+                        traffic_src = (f"profiles/pmc_traffic.json@{pmc.get('tag', 'untagged')} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, calibrated on a "
+                                       f"1 GiB copy; collected at V={pu.get('V')} R={pu.get('R')} R_live={pu.get('R_live')} B_live={pu.get('B_live')})")
+            r = dict(bound="hbm", kernel=kname, achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s",
+                     frac=round(achieved / HBM_PEAK_GBS, 5), traffic=traffic, traffic_source=traffic_src, algorithmic_bytes_per_launch=abytes,
+                     avg_launch_ms=round(avg_ms, 4), launches_timed=int(k_n), ms_in_timed_region=round(k_ms, 3),
+                     timing="HIP events around every launch of the kernel inside the timed region", units=units_now)
+            if kname in ("render_fwd", "render_bwd"):
+                cpi = VALU_CYCLES_PER_INST["render_bwd" if (kname == "render_bwd" and scan_on) else ("render_bwd_pipeline" if kname == "render_bwd" else "render_fwd")]
+                r["valu_model"] = dict(modelled_issue_cycles_per_inst=cpi, shader_clock_ghz=SHADER_CLOCK_GHZ, simds=1024,
+                                       note="NOT the roofline fraction.  VALU instructions per launch (rocprofv3 SQ_INSTS_VALU of the same workload) x modelled issue "
+                                            "cycles per instruction (instruction mix of the inner loop x tools/ubench/issue_rate) / (launch duration x 1024 SIMDs x "
+                                            "clock): an upper bound on how issue-bound the kernel is — it counts the set-up code's instructions too, and timed by "
+                                            "elimination (profiles/r04y_bwd_scan_by_elimination.log) the row-scan backward's inner loops are 37 % of its time")
+                try:
+                    import ast
+                    import glob
+                    sq_files = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_sq_counters.txt")))   # the newest tag sorts last
+                    for line in (open(sq_files[-1]) if sq_files else []):
+                        name, _, rest = line.partition(" {")
+                        if name.split("<")[0].strip() in (f"{kname}_kernel", f"{kname}_tail_kernel", f"{kname}_scan_kernel" if scan_on else "-") and pmc_units_ok:
+                            c = ast.literal_eval("{" + rest.strip())
+                            insts = c["SQ_INSTS_VALU"] * 32.0   # the extract averages per shader engine; 32 engines
+                            cycles = 1024.0 * avg_ms * 1e-3 * SHADER_CLOCK_GHZ * 1e9
+                            r["valu_model"].update(valu_insts_per_launch=insts, counters_source="profiles/" + os.path.basename(sq_files[-1]),
+                                                   simd_cycles_per_valu_inst=round(cycles / insts, 2) if insts else None,
+                                                   issue_frac_modelled=round(insts * cpi / cycles, 4) if cycles else None)
+                except Exception:
+                    pass
+            return r
 
-    # ---- CPU baseline: the oracle (C port of the reference kernels, OpenMP) on a 1/16-scale sample of the same workload
-    cpu = None
-    if world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(args)
+        tie = False
+        if len(candidates) > 1 and all(k in timed for k in candidates):
+            t_a, t_b = timed[candidates[0]][0], timed[candidates[1]][0]
+            dominant = max(candidates, key=lambda k: timed[k][0])
+            # Within 5 % of each other the order is run-to-run noise (same box, same script: preprocess_bwd 434.8 us by HIP events and 452.7 under
+            # rocprofv3, render_bwd 440.4 / 442.6: profiles/r06z_*): the tie goes to the kernel that moves more bytes — the one the HBM roofline binds —
+            # and the other sits beside it as `runner_up` with its own time, bytes and fraction.
+            if abs(t_a - t_b) <= 0.05 * max(t_a, t_b):
+                tie = True
+                fa = args.mode in ("train", "slam") and args.host == "fused" and world == 1
+                ab = {k: algorithmic_bytes("preprocess_bwd+adam" if (k == "preprocess_bwd" and fa) else k, stats) for k in candidates}
+                dominant = max(candidates, key=lambda k: ab[k])
+        roofline = hbm_roofline(dominant)
+        others = [k for k in candidates if k != dominant]
+        if others:
+            ru = hbm_roofline(others[0])
+            roofline["runner_up"] = {k: ru[k] for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch",
+                                                         "avg_launch_ms", "launches_timed", "ms_in_timed_region")}
+            roofline["dominant_rule"] = ("the longer of the two longest kernels over the K timed steps (HIP events around both)" if not tie else
+                                         "the two longest kernels are within 5 % of each other over the K timed steps (HIP events around both; their order is "
+                                         "run-to-run noise): named is the one that moves more algorithmic bytes, the other is `runner_up`")
+        # the whole step against the HBM peak on SURVEY 8d's A_view (the survey's figure of merit): algorithmic bytes of one view / ms_per_step
+        av = a_view_bytes(stats)
+        step_ms = 1e3 * elapsed / args.steps
+        roofline["step"] = dict(algorithmic_bytes=av["A_view"], parts={k: v for k, v in av.items() if k != "A_view"},
+                                achieved_TBps=round(av["A_view"] * world / (step_ms * 1e-3) / 1e12, 3) if step_ms > 0 else None,
+                                frac=round(av["A_view"] * world / (step_ms * 1e-3) / 1e9 / (HBM_PEAK_GBS * world), 4) if step_ms > 0 else None,
+                                note="SURVEY.md 8d A_view at this run's P, V, R, B32, N, T (per view; N > 1: per GPU) / ms_per_step / 8 TB/s")
+
+        # ---- CPU baseline: the oracle (C port of the reference kernels, OpenMP) on a 1/16-scale sample of the same workload
+        if world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(args)
 
     views = args.steps * world
     if (P, W, H) == (2_000_000, 1920, 1080) and args.scene == "random":
@@ -584,7 +606,7 @@ def main():
         else f"rendered views/sec (fwd+bwd) at {W}x{H}, {P} Gaussians",
         "value": round(views / elapsed, 3), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
+        "dtype": "f32", "data": "synthetic", "full": bool(args.full),
         "config": {"workload": f"{config_label}: {P} Gaussians ({'PLY map' if args.ply else args.scene + ' scene, seed 0'}), {W}x{H}, SH degree 3, "
                                + ("render fwd + 0.8*L1+0.2*(1-fused-SSIM) + bwd + sparse Adam per view"
                                   if args.mode in ("train", "slam") else "bare render fwd+bwd per view")
@@ -600,9 +622,11 @@ def main():
                                      "single": "ONE all-reduce of the [P x 59] slab + the visibility mask as P more floats"}[trainer.exchange_mode()] + ")"),
                    "mode": args.mode, "host": args.host if args.mode != "render" else "dropin", "parallelism": f"dp{world}" if world > 1 else "single",
                    "math": "strict" if strict_mode else "fast", "map_order": args.map_order,
-                   # how the forward grouped the instances by tile in the instrumented warm-up pass (GSLIC_BINNING / gslic_set_binning_mode; auto follows the row order)
-                   "binning": ("atomic" if "tile_bin" in breakdown else "radix") + " (" + os.environ.get("GSLIC_BINNING", "auto") + ")",
-                   "visible": stats["V"], "instances_R": stats["R"], "buckets_B": stats["B"], "instances_live": stats.get("R_live"),
+                   # how the forward grouped the instances by tile in the instrumented warm-up pass (without --full: in the last timed step)
+                   # (GSLIC_BINNING / gslic_set_binning_mode; auto follows the row order)
+                   "binning": (("atomic" if "tile_bin" in breakdown else "radix") if args.full else _lib.binning_path()[0])
+                              + " (" + os.environ.get("GSLIC_BINNING", "auto") + ")",
+                   "visible": stats.get("V"), "instances_R": stats.get("R"), "buckets_B": stats.get("B"), "instances_live": stats.get("R_live"),
                    "buckets_live": stats.get("B_live")},
         "roofline": roofline,
         "cpu_baseline": cpu,
@@ -620,17 +644,17 @@ def main():
                                                     "ms_per_call": round(slam["ms"] / max(slam["calls"], 1), 3)},
         # per-kernel time of the fully INSTRUMENTED warm-up pass (a HIP-event pair around every launch: the events' own overhead makes the
         # sum exceed ms_per_step; used to pick the dominant kernel, not to price the step)
-        "kernel_ms_per_step_instrumented": {k: round(v[0] / max(nprof, 1), 4) for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1][0])},
+        "kernel_ms_per_step_instrumented": {k: round(v[0] / max(nprof, 1), 4) for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1][0])} if args.full else None,
         "kernel_ms_per_launch_timed": None if not args.profile_all else {k: round(v[0] / max(v[1], 1), 4) for k, v in sorted(timed.items(), key=lambda kv: -kv[1][0])},
         "kernel_roofline": (kernel_table(timed, stats, fused_adam, rank1=dist_on and trainer.exchange_mode() == "rank1") if args.profile_all else
                             (kernel_table(timed_all, stats, False, rank1=trainer.exchange_mode() == "rank1") if timed_all else None)),
     }
 
-    # ---- the contract measurements are complete at this point; this process adds the same step over a >= 1 s window (`value_long`) and, at N > 1,
-    # per-rank times and the collectives alone.  Every other leg runs in a process of its own AFTER this one has released the GPU.
-    _trace("value_long")
+    # ---- the contract measurements are complete at this point; with --full this process adds the same step over a >= 1 s window (`value_long`)
+    # and, at N > 1, the collectives alone.  Every other leg runs in a process of its own AFTER this one has released the GPU.
     value_long = None
-    if args.mode != "slam":
+    if args.full and args.mode != "slam":
+        _trace("value_long")
         n_long = int(min(4000, max(args.steps, np.ceil(1.2 * args.steps / max(elapsed, 1e-6)))))
         sec = timed_loop(step, n_long)
         value_long = {"value": round(n_long * world / sec, 3), "unit": "views/s", "ms_per_step": round(1e3 * sec / n_long, 3), "steps": n_long,
@@ -651,11 +675,12 @@ def main():
                          "self_launched": os.environ.get("GSLIC_BENCH_SELF_LAUNCHED") == "1",
                          "prime_steps": prime_steps, "gc": "gc.collect() + gc.freeze() before the warm-up: the one-off 36-75 ms stall of rounds 4-5 at the ~79th step of a "
                                                            "process group was a generation-2 pass of Python's garbage collector (profiles/r06g_dist_stall.log), not the runtime"}
-        try:
-            from bench_legs import collectives_alone
-            out["rccl_microbench"] = collectives_alone(model.P, world, rank, dev, backend)
-        except Exception as ex:
-            out["rccl_microbench"] = {"error": str(ex)[:300]}
+        if args.full:
+            try:
+                from bench_legs import collectives_alone
+                out["rccl_microbench"] = collectives_alone(model.P, world, rank, dev, backend)
+            except Exception as ex:
+                out["rccl_microbench"] = {"error": str(ex)[:300]}
 
     if rank != 0:
         if torch.distributed.is_initialized():
@@ -666,7 +691,7 @@ def main():
         faulthandler.cancel_dump_traceback_later()
     except Exception:
         pass
-    if world == 1 and not args.no_extras and not trainer._dist_on() and args.mode == "train" and args.host == "fused" and not args.graph and not args.split_adam:
+    if args.full and world == 1 and not args.no_extras and not trainer._dist_on() and args.mode == "train" and args.host == "fused" and not args.graph and not args.split_adam:
         # release the device, then the legs, each in its own process with a budget
         try:
             del model, gt, dL, image, visible, radii, vis
@@ -720,6 +745,43 @@ def kernel_table(timed, stats, fused_adam, rank1=False):
         gbs = ab / (avg * 1e-3) / 1e9 if avg > 0 else 0.0
         out[k] = {"avg_launch_ms": round(avg, 4), "launches": int(n), "algorithmic_bytes": ab, "achieved_GBps": round(gbs, 1), "frac_of_hbm_peak": round(gbs / HBM_PEAK_GBS, 4)}
     return out
+
+
+DUMP_ROWS = 1 << 17            # per-Gaussian rows --dump-outputs keeps (60 floats a row: 31.5 MB); a fixed, seeded sample when the map has more
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, model, mode, last):
+    """--dump-outputs DIR: what the timed path handed its caller after the last timed step, as DIR/<name>.npy, so that two builds of the
+    project can be compared output for output (every input of a run is seeded: the same arguments give the same inputs).  Per-Gaussian arrays
+    are in the caller's row order (the order the map was created in, whatever order the library keeps its rows in) and, when the map has more
+    than DUMP_ROWS rows, on a fixed sample of DUMP_ROWS of them (numpy default_rng(0), sorted):
+      rows                  float64 [S]  the sampled rows
+      visible               float32 [S]  1.0 where the step saw the Gaussian (radii > 0)
+      loss_terms            float32 [2]  mean L1 and mean SSIM of the step (fused host)      loss  float32 [1]  the loss (--host dropin)
+      xyz, features_dc, features_rest, opacity, scaling, rotation   float32 [S, ...]  the raw parameters after the step's Adam update
+    --mode render hands back the visibility mask only (its gradients are dropped), and the parameters it leaves unchanged are not written."""
+    os.makedirs(out_dir, exist_ok=True)
+    P = model.P
+    rows = np.arange(P) if P <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(P, DUMP_ROWS, replace=False))
+    idx = torch.from_numpy(rows).to(model.device)
+    order = model.original_order()   # storage row of every original row (None: the rows are stored in the original order)
+    if order is not None:
+        idx = order[idx]
+    arrays = {"rows": rows.astype(np.float64)}
+    for key, name in (("terms", "loss_terms"), ("loss", "loss")):
+        if last.get(key) is not None:
+            arrays[name] = last[key].detach().float().reshape(-1).cpu().numpy()
+    if last.get("visible") is not None:
+        arrays["visible"] = last["visible"].reshape(-1)[:P][idx].float().cpu().numpy()
+    if mode in ("train", "slam"):
+        for name in model.NAMES:
+            arrays[name] = getattr(model, name).detach()[idx].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES_MAX, f"--dump-outputs: {total} bytes over the {DUMP_BYTES_MAX} byte budget"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def _cpu_step(orc, sc, cam, gt, state, lrs):

@@ -2,7 +2,9 @@
 together with ply_driver.cpp, which replays saveMap's call sequence (src/gaussian.cpp:306-397).  Runs wherever /root/reference is
 mounted:    python oracle/ref_build/make_ply_golden.py
 The binary goes to oracle/_ref/ (git-ignored); the few-KB .ply files are committed and gaussian-lic_amd/io_ply.save_map must
-reproduce them byte for byte (tests/test_io_eval.py)."""
+reproduce them byte for byte (tests/test_io_eval.py).  The models the files were written from are committed beside them
+(tests/golden/savemap_inputs.npz): the scene generator's float32 arithmetic on the host is not bit-identical across CPUs, so the test
+reads them instead of regenerating them."""
 import os
 import subprocess
 import sys
@@ -17,6 +19,8 @@ REF_SRC = "/root/reference/src"
 OUT = os.path.join(os.path.dirname(HERE), "_ref")
 BIN = os.path.join(OUT, "ply_writer")
 CASES = [("savemap_64_d3", 64, 3, 0, 7), ("savemap_40_d0", 40, 0, 0, 8), ("savemap_50_d3_skybox10", 50, 3, 10, 9)]  # name, P, degree, skybox rows, seed
+INPUTS = "savemap_inputs.npz"   # per case "<name>.<parameter>": the model each .ply was written from
+FIELDS = ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation")
 
 
 def build():
@@ -38,8 +42,10 @@ def main():
         return 0
     build()
     gdir = os.path.join(ROOT, "tests", "golden")
+    inputs = {}
     for name, P, deg, sky, seed in CASES:
         raw = model_for(P, deg, seed)
+        inputs.update({f"{name}.{k}": raw[k].numpy() for k in FIELDS})
         s = slice(sky, None)
         # what saveMap hands to tinyply (gaussian.cpp:309-316): rows from skybox_points_num on, features transposed to [P,3,K] and flattened
         arrs = dict(xyz=raw["xyz"][s], f_dc=raw["features_dc"][s].transpose(1, 2).flatten(1), f_rest=raw["features_rest"][s].transpose(1, 2).flatten(1),
@@ -55,6 +61,7 @@ def main():
             out = os.path.join(gdir, name + ".ply")
             subprocess.run([BIN, out, str(n), str(M)] + paths, check=True)
         print(name, os.path.getsize(out), "bytes")
+    np.savez(os.path.join(gdir, INPUTS), **inputs)
     return 0
 
 

@@ -66,7 +66,7 @@ def test_bench_under_torchrun_one_rank():
     env = dict(os.environ)
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", GSLIC_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--gaussians", "100000",
+           "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "2", "--gaussians", "100000",
            "--width", "640", "--height", "360", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -86,7 +86,7 @@ def test_bench_gpus_2_launches_itself():
     import torch
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "GSLIC_FORCE_DIST")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", GSLIC_DIST_PRIME_STEPS="3")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--gaussians", "100000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "2", "--gaussians", "100000",
            "--width", "640", "--height", "360", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

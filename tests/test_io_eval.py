@@ -56,14 +56,17 @@ def test_eval_ssim_and_psnr_match_oracle(oracle32):
 
 def test_ply_equals_reference_tinyply_golden(tmp_path):
     """save_map byte-for-byte against files written by the REFERENCE's own tinyply with saveMap's call sequence
-    (tests/golden/savemap_*.ply from oracle/ref_build/make_ply_golden.py: src/tinyply.cpp compiled in place + ply_driver.cpp)."""
+    (tests/golden/savemap_*.ply from oracle/ref_build/make_ply_golden.py: src/tinyply.cpp compiled in place + ply_driver.cpp), from the
+    models stored beside them (savemap_inputs.npz)."""
     import os
     import gaussian_lic_amd  # noqa: F401
     from gaussian_lic_amd import io_ply
-    from oracle.ref_build.make_ply_golden import CASES, model_for
+    from oracle.ref_build.make_ply_golden import CASES, FIELDS, INPUTS
     gdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    stored = np.load(os.path.join(gdir, INPUTS))
     for name, P, deg, sky, seed in CASES:
-        raw = model_for(P, deg, seed)
+        raw = {k: torch.from_numpy(stored[f"{name}.{k}"]) for k in FIELDS}
+        assert raw["xyz"].shape[0] == P and raw["features_rest"].shape[1] == (deg + 1) ** 2 - 1, name
         m = _M()
         for k in ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation"):
             setattr(m, k, raw[k])

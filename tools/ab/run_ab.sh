@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 N=${1:-2}
 for r in $(seq $N); do
   for v in A B; do
-    GSLIC_HIP_LIB=$GRAFT_REPO_ROOT/tools/ab/libgslic_hip_$v.so timeout 300 python bench.py --steps 100 --no-cpu-baseline --no-extras --profile-all 2>/dev/null | python -c "
+    GSLIC_HIP_LIB=$PWD/tools/ab/libgslic_hip_$v.so timeout 300 python bench.py --full --steps 100 --no-cpu-baseline --no-extras --profile-all 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -10,7 +10,7 @@ for r in $(seq $N); do
   for spec in "$@"; do
     IFS='|' read -r label lib envs <<< "$spec"
     if [ "$lib" = "-" ] || [ -z "$lib" ]; then libenv=""; else libenv="GSLIC_HIP_LIB=$GRAFT_REPO_ROOT/$lib"; fi
-    env $libenv $envs timeout 300 python bench.py --steps 100 --no-cpu-baseline --no-extras ${BENCH_PROFILE---profile-all} ${BENCH_ARGS:-} 2>/dev/null | python -c "
+    env $libenv $envs timeout 300 python bench.py --full --steps 100 --no-cpu-baseline --no-extras ${BENCH_PROFILE---profile-all} ${BENCH_ARGS:-} 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_parity_gpu.py tests/test_vs_reference_kernels_gpu.py tests/test_fused_gpu.py -m gpu -x -q 2>&1 | tail -n 5
 for cfg in "$@"; do
   if [ "$cfg" = "-" ]; then envs=""; else envs="$cfg"; fi
-  env $envs timeout 300 python bench.py --steps 100 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+  env $envs timeout 300 python bench.py --full --steps 100 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -16,7 +16,7 @@ cat $OUT/${TAG}_ab.log
 BENCH_PROFILE="" bash tools/ab/run_multi.sh 2 "base-16B-rows|tools/ab/libgslic_hip_base.so|" "split-rows|-|" > $OUT/${TAG}_ab_unprofiled.log 2>&1
 cat $OUT/${TAG}_ab_unprofiled.log
 export GSLIC_CPP_HOST_DIR=/tmp/cpp_host
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 2> $OUT/${TAG}_bench_stderr.log | tail -1 > $OUT/${TAG}_bench_line_driver_command.json
+timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 2> $OUT/${TAG}_bench_stderr.log | tail -1 > $OUT/${TAG}_bench_line_driver_command.json
 python - <<PY
 import json
 d = json.load(open("$OUT/${TAG}_bench_line_driver_command.json"))

@@ -10,7 +10,7 @@ timeout 900 python tests/fuzz_vs_reference.py 300 6001 > $OUT/${TAG}_fuzz_300_fo
 tail -2 $OUT/${TAG}_fuzz_300_forced_paths.txt
 timeout 900 python tests/fuzz_vs_reference.py --poses 300 6002 > $OUT/${TAG}_fuzz_poses_300_forced_paths.txt 2>&1; echo "rc $?" >> $OUT/${TAG}_fuzz_poses_300_forced_paths.txt
 tail -2 $OUT/${TAG}_fuzz_poses_300_forced_paths.txt
-timeout 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 2> $OUT/${TAG}_bench_stderr.log | tail -1 > $OUT/${TAG}_bench_line_driver_command.json
+timeout 400 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 2> $OUT/${TAG}_bench_stderr.log | tail -1 > $OUT/${TAG}_bench_line_driver_command.json
 python - <<PY
 import json
 d = json.load(open("$OUT/${TAG}_bench_line_driver_command.json"))

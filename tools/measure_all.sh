@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="timeout 600 python $R/bench.py"
+B="timeout 600 python $R/bench.py --full"
 X="--no-cpu-baseline --no-extras --steps 100"
 # a saveMap-format PLY of the LiDAR-seeded scene (io_ply.save_map: byte-identical to the reference's tinyply output), for the --ply leg
 python - <<PY
@@ -38,11 +38,11 @@ PY
 # per-kernel durations
 # (the default step counts, so that the trace's average of the dominant kernel and the HIP-event average bench.py prints for it come from the
 # SAME process: the line is kept next to the stats)
-timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -o $TAG -- python $R/bench.py --no-cpu-baseline --no-extras > /tmp/prof_$TAG.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG -o $TAG -- python $R/bench.py --full --no-cpu-baseline --no-extras > /tmp/prof_$TAG.log 2>&1
 grep "^{" /tmp/prof_$TAG.log | tail -1 > $OUT/${TAG}_bench_line_under_rocprof.json
 python $R/tools/rocpd_summary.py $(find /tmp/prof_$TAG -name "*.db" | head -1) $OUT/${TAG}_train_2M_1080p_kernel_stats > /dev/null
 # the same step through the reference's operator API + LibTorch autograd (what an unmodified reference host runs): where its extra time goes
-timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_dropin_$TAG -o $TAG -- python $R/bench.py --host dropin --steps 20 --warmup 4 --no-cpu-baseline --no-extras > /tmp/prof_dropin_$TAG.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_dropin_$TAG -o $TAG -- python $R/bench.py --full --host dropin --steps 20 --warmup 4 --no-cpu-baseline --no-extras > /tmp/prof_dropin_$TAG.log 2>&1
 python $R/tools/rocpd_summary.py $(find /tmp/prof_dropin_$TAG -name "*.db" | head -1) $OUT/${TAG}_dropin_kernel_stats > /dev/null
 python $R/tools/rocpd_timeline.py $(find /tmp/prof_dropin_$TAG -name "*.db" | head -1) preprocess_kernel 12 > $OUT/${TAG}_dropin_timeline.txt 2>&1
 python $R/tools/rocpd_timeline.py $(find /tmp/prof_$TAG -name "*.db" | head -1) preprocess_kernel 12 > $OUT/${TAG}_fused_timeline.txt 2>&1

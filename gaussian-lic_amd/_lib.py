@@ -42,6 +42,7 @@ EXPORTS = [
     "gslic_l1_ssim_loss_backward", "gslic_set_math_mode", "gslic_set_binning_mode", "gslic_rasterize_forward_capacity", "gslic_rasterize_backward_rgb",
     "gslic_rasterize_backward_rgb_rows", "gslic_sh_grad_from_rgb", "gslic_sh_grad_from_rgb_adam", "gslic_rasterize_backward_rgb_payload",
     "gslic_sh_grad_from_rgb_adam_all", "gslic_get_binning_path", "gslic_scratch_round_up",
+    "gslic_rasterize_forward_depth", "gslic_rasterize_backward_depth",
 ]
 
 _lib = None
@@ -79,6 +80,11 @@ def lib():
         [ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp])
     L.gslic_rasterize_backward.argtypes = (
         [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp] + [vp] * 10 + [f32, vp])
+    L.gslic_rasterize_forward_depth.argtypes = (
+        [ctypes.POINTER(RasterParams)] + [ALLOC_FN, vp] * 4 + [vp] * 12 + [vp, vp, vp, vp] +
+        [ctypes.POINTER(i32), ctypes.POINTER(i32), vp])
+    L.gslic_rasterize_backward_depth.argtypes = (
+        [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp, vp] + [vp] * 10 + [f32, vp])
     L.gslic_rasterize_backward_adam.argtypes = (
         [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp] + [vp] * 6 + [f32, ctypes.POINTER(AdamFused), vp])
     L.gslic_rasterize_backward_camera.argtypes = (

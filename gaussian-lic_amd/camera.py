@@ -52,6 +52,31 @@ class Camera:
         self.tanfovx = np.float32(np.tan(np.float32(self.FoVx * np.float32(0.5))))
         self.tanfovy = np.float32(np.tan(np.float32(self.FoVy * np.float32(0.5))))
 
+    def project_depth(self, points_world):
+        """Sparse depth image [H,W] of a LiDAR point cloud (torch [N,3] world points, any device) for depth supervision: camera-frame z
+        (p_c = R_cw p + t_cw in float32), pixel (floor(x fx / z + cx), floor(y fy / z + cy)) as gaussian.cpp:548-565 assigns them, the
+        NEAREST point where several land on one pixel, 0 where none does.  Points with z <= 0 and pixels outside the image are dropped.
+        torch ops only: runs where the points are."""
+        import torch
+        pts = points_world.to(torch.float32)
+        dev = pts.device
+        W, H = self.image_width, self.image_height
+        R_cw = torch.from_numpy(np.ascontiguousarray(self.R_wc.T.astype(np.float32))).to(dev)
+        t_cw = torch.from_numpy((-self.R_wc.T @ self.t_wc).astype(np.float32)).to(dev)
+        # one product and one add per term, in a fixed order (no reduction kernel deciding the rounding): identical on CPU and GPU
+        pc = pts[:, 0:1] * R_cw[:, 0] + pts[:, 1:2] * R_cw[:, 1] + pts[:, 2:3] * R_cw[:, 2] + t_cw
+        z = pc[:, 2]
+        front = z > 0
+        zs = torch.where(front, z, torch.ones_like(z))
+        x = torch.floor((pc[:, 0] * float(self.fx)) / zs + float(self.cx))
+        y = torch.floor((pc[:, 1] * float(self.fy)) / zs + float(self.cy))
+        keep = front & (x >= 0) & (x < W) & (y >= 0) & (y < H)
+        idx = (y[keep].to(torch.int64) * W + x[keep].to(torch.int64))
+        depth = torch.full((H * W,), float("inf"), dtype=torch.float32, device=dev)
+        depth.scatter_reduce_(0, idx, z[keep], reduce="amin", include_self=True)
+        depth = torch.where(torch.isinf(depth), torch.zeros_like(depth), depth)
+        return depth.view(H, W)
+
     # ---- camera pose as an optimisation variable (the "cam" of the north-star; the reference has no counterpart: rasterizer.cpp:171-182) --------
     def pose_gradient(self, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos):
         """Chains the three camera gradients of gslic_rasterize_backward_camera (element order of the inputs: float[16] with (r, c) at [4c + r])

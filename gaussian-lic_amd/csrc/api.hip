@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include <atomic>
 #include <chrono>
+#include <mutex>
 
 #include <stdarg.h>
 #include <stdio.h>
@@ -100,7 +101,9 @@ GeomState GeomState::carve(const void* base, size_t P, size_t* bytes)
     if (bytes) *bytes = c.used(base) + 256;
     return g;
 }
-ImageState ImageState::carve(const void* base, size_t T, size_t* bytes)
+// depth = true (gslic_rasterize_forward_depth / gslic_rasterize_backward_depth): the depth arrays are carved BEHIND every other array, so the
+// layout without them is an exact prefix — the colour-only backward works on a depth forward's buffers unchanged
+ImageState ImageState::carve(const void* base, size_t T, size_t* bytes, bool depth)
 {
     Carver c(base);
     ImageState g;
@@ -108,10 +111,11 @@ ImageState ImageState::carve(const void* base, size_t T, size_t* bytes)
     g.bucket_offsets = c.take<uint32_t>(T);
     g.max_contrib = c.take<uint32_t>(T);
     g.pix_final = c.take<float4>(T * GS_TILE_PIX);
+    g.pix_depth = depth ? c.take<float>(T * GS_TILE_PIX) : nullptr;
     if (bytes) *bytes = c.used(base) + 256;
     return g;
 }
-BinningState BinningState::carve(const void* base, size_t R, int end_bit, bool no_color, size_t* bytes)
+BinningState BinningState::carve(const void* base, size_t R, int end_bit, bool no_color, size_t* bytes, bool depth)
 {
     Carver c(base);
     BinningState g;
@@ -127,16 +131,18 @@ BinningState BinningState::carve(const void* base, size_t R, int end_bit, bool n
     // (36 R bytes of partial rows, unused until the backward: room for the four 4 R arrays — contiguous: they are also the 16 R bytes of binned())
     uint32_t* const ls = no_color ? c.take<uint32_t>(4 * R) : reinterpret_cast<uint32_t*>(g.partials);
     for (int i = 0; i < 4; i++) g.lsort[i] = ls + (size_t)i * R;
+    g.partials_z = depth ? c.take<float>(R) : nullptr;
     if (bytes) *bytes = c.used(base) + 256;
     return g;
 }
-SampleState SampleState::carve(const void* base, size_t B, size_t* bytes)
+SampleState SampleState::carve(const void* base, size_t B, size_t* bytes, bool depth)
 {
     Carver c(base);
     SampleState g;
     g.bucket_to_tile = c.take<uint32_t>(B);
     g.ckpt = c.take<float4>(B * GS_TILE_PIX);
     g.hit = c.take<uint64_t>(B * GS_TILE_PIX);
+    g.ckpt_depth = depth ? c.take<float>(B * GS_TILE_PIX) : nullptr;
     if (bytes) *bytes = c.used(base) + 256;
     return g;
 }
@@ -417,13 +423,34 @@ static void binning_feedback(bool permuted, bool used_bin, uint32_t atomics, uin
     st.since_probe = 0;
 }
 
+// Host-side note of which forwards rendered depth (key: the address of their geometry flags; every forward into a buffer updates it).  The device
+// flag flags[GS_FLAG_DEPTH] stays the source of truth; the note lets a depth backward on buffers of a known forward skip the device read and its
+// stream synchronise (an unknown buffer — the note keeps the last 64 — is checked on the device).
+static std::mutex g_depth_note_mu;
+static struct { const void* flags; bool depth; } g_depth_note[64];
+static unsigned g_depth_note_next = 0;
+static void note_depth(const void* flags, bool depth)
+{
+    std::lock_guard<std::mutex> lk(g_depth_note_mu);
+    for (auto& e : g_depth_note)
+        if (e.flags == flags) { e.depth = depth; return; }
+    g_depth_note[g_depth_note_next++ & 63u] = {flags, depth};
+}
+static int known_depth(const void* flags)   // 1: a depth forward, 0: a colour-only forward, -1: unknown
+{
+    std::lock_guard<std::mutex> lk(g_depth_note_mu);
+    for (auto& e : g_depth_note)
+        if (e.flags == flags) return e.depth ? 1 : 0;
+    return -1;
+}
+
 static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn geom_alloc, void* geom_ctx, gslic_alloc_fn binning_alloc,
                             void* binning_ctx, gslic_alloc_fn img_alloc, void* img_ctx, gslic_alloc_fn sample_alloc,
                             void* sample_ctx, const ForwardCapacity* cap, const float* background, const float* means3D, const float* dc, const float* shs,
                             const float* colors_precomp, const float* opacities, const float* scales, const float* rotations,
                             const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
                             float* out_color, float* out_final_T, int32_t* radii, int32_t* num_rendered, int32_t* num_buckets,
-                            void* stream)
+                            void* stream, float* out_depth = nullptr, bool depth = false)
 {
     (void)background;
     GS_TRY(check_params(prm));
@@ -432,6 +459,9 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
     *num_buckets = 0;
     const int P = prm->P;
     if (P == 0) return GSLIC_OK;  // rasterize_points.cu:110
+    if (depth && prm->no_color)
+        return set_error(GSLIC_ERR_INVALID_ARG, "depth forward: no_color = 1 (the depth is blended with the colour and needs its checkpoints)");
+    if (depth && !out_depth) return set_error(GSLIC_ERR_INVALID_ARG, "depth forward: out_depth is NULL");
     if (colors_precomp || cov3D_precomp)
         return set_error(GSLIC_ERR_UNSUPPORTED, "colors_precomp / cov3D_precomp are not supported (the reference host always passes empty tensors)");
     if (!cap && (!geom_alloc || !binning_alloc || !img_alloc || (!prm->no_color && !sample_alloc)))
@@ -446,7 +476,7 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
 
     size_t geom_bytes, img_bytes;
     GeomState::carve(nullptr, (size_t)P, &geom_bytes);
-    ImageState::carve(nullptr, (size_t)T, &img_bytes);
+    ImageState::carve(nullptr, (size_t)T, &img_bytes, depth);
     if (cap && (cap->geom_bytes < geom_bytes || cap->img_bytes < img_bytes || !cap->geom || !cap->img || !cap->binning ||
                 (!no_color && !cap->sample) || !cap->status_out))
         return set_error(GSLIC_ERR_INVALID_ARG, "capacity mode: geometry / image buffer too small (need %zu / %zu bytes) or a NULL buffer", geom_bytes, img_bytes);
@@ -455,7 +485,7 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
     GeomState geom = GeomState::carve(align256(geom_base), (size_t)P, nullptr);
     char* img_base = cap ? cap->img : img_alloc(img_ctx, img_bytes);
     if (!img_base) return set_error(GSLIC_ERR_ALLOC, "image allocator returned NULL for %zu bytes", img_bytes);
-    ImageState img = ImageState::carve(align256(img_base), (size_t)T, nullptr);
+    ImageState img = ImageState::carve(align256(img_base), (size_t)T, nullptr, depth);
 
     GS_HIP(hipMemsetAsync(geom.flags, 0, geom.zero_bytes, s));
     PreprocessArgs pa;
@@ -492,10 +522,10 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
     }
 
     size_t bin_bytes;
-    BinningState::carve(nullptr, (size_t)R, end_bit, no_color, &bin_bytes);
+    BinningState::carve(nullptr, (size_t)R, end_bit, no_color, &bin_bytes, depth);
     char* bin_base = cap ? cap->binning : binning_alloc(binning_ctx, bin_bytes);
     if (!bin_base) return set_error(GSLIC_ERR_ALLOC, "binning allocator returned NULL for %zu bytes", bin_bytes);
-    BinningState bin = BinningState::carve(align256(bin_base), (size_t)R, end_bit, no_color, nullptr);
+    BinningState bin = BinningState::carve(align256(bin_base), (size_t)R, end_bit, no_color, nullptr, depth);
 
     // How the instances get grouped by tile (same lists either way, bit for bit): block-aggregated atomics on the tiles' cursors (tile_bin.hip) when
     // the map's row order keeps a block's instances on few tiles, the stable radix sort on the tile id otherwise (and above GS_TILE_BIN_MAX_T tiles).
@@ -561,10 +591,10 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
             binning_feedback(prm->tie_rank != nullptr, use_bin, bin_sample[0], bin_sample[1]);
         }
         size_t smp_bytes;
-        SampleState::carve(nullptr, (size_t)B, &smp_bytes);
+        SampleState::carve(nullptr, (size_t)B, &smp_bytes, depth);
         char* smp_base = cap ? cap->sample : sample_alloc(sample_ctx, smp_bytes);
         if (!smp_base) return set_error(GSLIC_ERR_ALLOC, "sample allocator returned NULL for %zu bytes", smp_bytes);
-        smp = SampleState::carve(align256(smp_base), (size_t)B, nullptr);
+        smp = SampleState::carve(align256(smp_base), (size_t)B, nullptr, depth);
     }
 
     RenderFwdArgs ra;
@@ -572,7 +602,9 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
     ra.ranges = img.ranges; ra.point_list = bin.point_list(); ra.rec = geom.rec; ra.bucket_offsets = img.bucket_offsets;
     ra.bucket_to_tile = smp.bucket_to_tile; ra.ckpt = smp.ckpt; ra.hit = smp.hit; ra.pix_final = img.pix_final; ra.max_contrib = img.max_contrib;
     ra.out_color = out_color; ra.out_final_T = out_final_T; ra.capB = B; ra.status = geom.flags; ra.tail4_from = T;   // (launch_render_fwd decides)
+    ra.out_depth = depth ? out_depth : nullptr; ra.ckpt_depth = smp.ckpt_depth; ra.pix_depth = img.pix_depth;   // (NULL without depth)
     GS_TRY(launch_render_fwd(ra, s));
+    note_depth(geom.flags, depth);
     DEBUG_SYNC(prm, s);
     if (cap) {
         hipLaunchKernelGGL(forward_status_kernel, dim3(1), dim3(1), 0, s, (const uint32_t*)(geom.point_offsets + (P - 1)),
@@ -625,6 +657,19 @@ int gslic_rasterize_forward(const gslic_raster_params* prm, gslic_alloc_fn geom_
                                   cam_pos, out_color, out_final_T, radii, num_rendered, num_buckets, stream);
 }
 
+int gslic_rasterize_forward_depth(const gslic_raster_params* prm, gslic_alloc_fn geom_alloc, void* geom_ctx, gslic_alloc_fn binning_alloc,
+                                  void* binning_ctx, gslic_alloc_fn img_alloc, void* img_ctx, gslic_alloc_fn sample_alloc,
+                                  void* sample_ctx, const float* background, const float* means3D, const float* dc, const float* shs,
+                                  const float* colors_precomp, const float* opacities, const float* scales, const float* rotations,
+                                  const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                                  float* out_color, float* out_final_T, float* out_depth, int32_t* radii, int32_t* num_rendered,
+                                  int32_t* num_buckets, void* stream)
+{
+    return rasterize_forward_impl(prm, geom_alloc, geom_ctx, binning_alloc, binning_ctx, img_alloc, img_ctx, sample_alloc, sample_ctx, nullptr,
+                                  background, means3D, dc, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
+                                  cam_pos, out_color, out_final_T, radii, num_rendered, num_buckets, stream, out_depth, true);
+}
+
 int gslic_rasterize_forward_capacity(const gslic_raster_params* prm, char* geom_buffer, size_t geom_bytes, char* binning_buffer,
                                      size_t binning_bytes, char* img_buffer, size_t img_bytes, char* sample_buffer, size_t sample_bytes,
                                      const float* background, const float* means3D, const float* dc, const float* shs,
@@ -647,7 +692,7 @@ static int rasterize_backward_impl(const gslic_raster_params* prm, int32_t R, in
                              float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale,
                              float* dL_drot, float lambda_erank, const gslic_adam_fused* adam, float* const dL_dcam[3], void* stream,
                              float* dL_drgb = nullptr, int32_t row_begin = 0, int32_t row_end = -1, bool skip_blend = false, uint8_t* vis_out = nullptr,
-                             float* campos_out = nullptr)
+                             float* campos_out = nullptr, const float* dL_ddepth = nullptr)
 {
     (void)background; (void)dc;
     GS_TRY(check_params(prm));
@@ -681,16 +726,31 @@ static int rasterize_backward_impl(const gslic_raster_params* prm, int32_t R, in
     hipStream_t s = (hipStream_t)stream;
     int gx, gy;
     const int T = tile_grid(prm->width, prm->height, gx, gy);
+    const bool depth = dL_ddepth != nullptr;
     GeomState geom = GeomState::carve(align256(geom_buffer), (size_t)P, nullptr);
-    ImageState img = ImageState::carve(align256(img_buffer), (size_t)T, nullptr);
-    BinningState bin = BinningState::carve(align256(binning_buffer), (size_t)R, sort_end_bit(T), false, nullptr);
-    SampleState smp = SampleState::carve(align256(sample_buffer), (size_t)B, nullptr);
+    if (depth) {
+        // the depth arrays exist only behind a depth forward's buffers.  Known buffers: the host note; else the flag its render kernel set (one
+        // 4-byte read, the stream waits for it)
+        int known = known_depth(geom.flags);
+        if (known < 0) {
+            uint32_t depth_flag = 0u;
+            GS_HIP(hipMemcpyAsync(&depth_flag, geom.flags + GS_FLAG_DEPTH, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            GS_HIP(hipStreamSynchronize(s));
+            known = depth_flag == 1u ? 1 : 0;
+        }
+        if (known != 1)
+            return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: these buffers come from a forward that rendered no depth (use gslic_rasterize_forward_depth)");
+    }
+    ImageState img = ImageState::carve(align256(img_buffer), (size_t)T, nullptr, depth);
+    BinningState bin = BinningState::carve(align256(binning_buffer), (size_t)R, sort_end_bit(T), false, nullptr, depth);
+    SampleState smp = SampleState::carve(align256(sample_buffer), (size_t)B, nullptr, depth);
 
     RenderBwdArgs rb;
     rb.W = prm->width; rb.H = prm->height; rb.gx = gx; rb.B = B;
     rb.ranges = img.ranges; rb.point_list = bin.point_list(); rb.inst_slot = bin.inst_slot(); rb.rec = geom.rec;
     rb.bucket_offsets = img.bucket_offsets; rb.bucket_to_tile = smp.bucket_to_tile; rb.ckpt = smp.ckpt; rb.hit = smp.hit; rb.pix_final = img.pix_final;
     rb.max_contrib = img.max_contrib; rb.dL_dpix = dL_dpix; rb.partials = bin.partials; rb.dead = bin.dead; rb.status = geom.flags; rb.T = T;
+    rb.dL_ddepth = dL_ddepth; rb.ckpt_depth = smp.ckpt_depth; rb.pix_depth = img.pix_depth; rb.partials_z = bin.partials_z;   // (NULL without depth)
     if (!skip_blend) GS_TRY(launch_render_bwd(rb, s));   // (a chunked per-Gaussian backward runs the blend backward with its first chunk only)
     DEBUG_SYNC(prm, s);
 
@@ -713,6 +773,7 @@ static int rasterize_backward_impl(const gslic_raster_params* prm, int32_t R, in
     }
     pb.status = geom.flags;
     pb.cam_partials = nullptr; pb.cam_out = nullptr;
+    pb.partials_z = depth ? bin.partials_z : nullptr;
     pb.vis_out = vis_out; pb.campos_out = campos_out;
     if (dL_dcam) {
         // scratch of the geometry buffer: the per-wave partial rows (128 B per wave; the generic 256-thread path writes 4 rows per block even
@@ -742,6 +803,24 @@ int gslic_rasterize_backward(const gslic_raster_params* prm, int32_t R, int32_t 
                                    projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, dL_dmean2D,
                                    dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot,
                                    lambda_erank, nullptr, nullptr, stream);
+}
+
+int gslic_rasterize_backward_depth(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
+                                   const float* dc, const float* shs, const float* colors_precomp, const float* scales,
+                                   const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                   const float* cam_pos, const int32_t* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                                   char* sample_buffer, const float* dL_dpix, const float* dL_ddepth, float* dL_dmean2D, float* dL_dconic,
+                                   float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh,
+                                   float* dL_dscale, float* dL_drot, float lambda_erank, void* stream)
+{
+    GS_TRY(check_params(prm));
+    if (prm->P == 0) return GSLIC_OK;
+    if (prm->no_color) return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no_color = 1 (no depth forward renders without colour)");
+    if (!dL_ddepth) return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: dL_ddepth is NULL (gslic_rasterize_backward is the colour-only backward)");
+    return rasterize_backward_impl(prm, R, B, background, means3D, dc, shs, colors_precomp, scales, rotations, cov3D_precomp, viewmatrix,
+                                   projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, dL_dmean2D,
+                                   dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot,
+                                   lambda_erank, nullptr, nullptr, stream, nullptr, 0, -1, false, nullptr, nullptr, dL_ddepth);
 }
 
 int gslic_rasterize_backward_rgb(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,

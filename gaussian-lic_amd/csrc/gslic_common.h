@@ -74,6 +74,7 @@ void prof_begin(int id, hipStream_t s);
 void prof_end(int id, hipStream_t s);
 extern bool g_prof_on;
 #define GS_FLAG_HITBITS 4   // index into GeomState::flags: set by a forward that recorded SampleState::hit
+#define GS_FLAG_DEPTH 12    // index into GeomState::flags: set by a depth forward (the depth arrays of the img / sample / binning blocks exist)
 #define GS_FLAG_BIN_ATOMICS 10   // index into GeomState::flags: [10] global atomics of a SAMPLE of the binning kernel's workgroups (their distinct tiles), [11] the
                                  // instances of those workgroups: what grouping by tile without a sort costs on this map's row order — api.hip picks the path by it
 #define GS_FLAG_LONG 9      // index into GeomState::flags: number of tiles whose instance list is longer than the one-wave depth sort takes (radix_sort.hip)
@@ -227,7 +228,8 @@ struct ImageState {
     uint32_t* bucket_offsets; // [T] inclusive scan of ceil(n_t / GS_BUCKET)
     uint32_t* max_contrib;    // [T]
     float4* pix_final;        // [T*256] tile-major {C.r,C.g,C.b, n_contrib bits}
-    static ImageState carve(const void* base, size_t T, size_t* bytes);
+    float* pix_depth;         // [T*256] tile-major final depth D: depth forwards only, carved behind everything else (NULL otherwise)
+    static ImageState carve(const void* base, size_t T, size_t* bytes, bool depth = false);
 };
 struct BinningState {
     // Emission order -> lists, on either grouping path (api.hip: binning_choice).  pp = plan.passes & 1 names the side the lists do NOT go to.
@@ -246,18 +248,21 @@ struct BinningState {
     float* partials;          // [9R] per emission slot: the instance's 9 partial gradients (36-byte rows), only when !no_color
     uint8_t* dead;            // [R] per emission slot: 1 = the instance lies in a bucket behind its tile's last contributor (its partial row is
                               // NOT written and must not be read: all nine gradients are exactly zero); zeroed by finalize_ranges_kernel / tile_bin_kernel
+    float* partials_z;        // [R] per emission slot: dL/dz of the instance (depth backward; the dead flags cover it too): depth forwards only,
+                              // carved behind everything else (NULL otherwise)
     SortPlan plan;
     uint32_t* point_list() const { return gauss[(plan.passes & 1) ^ 1]; }    // (written by the per-tile depth sort)
     uint32_t* inst_slot() const { return slots[(plan.passes & 1) ^ 1]; }
     uint4* binned() const { return reinterpret_cast<uint4*>(lsort[0]); }       // [R] 16-byte rows of the atomic binning (TileBinArgs): the four lsort arrays
-    static BinningState carve(const void* base, size_t R, int end_bit, bool no_color, size_t* bytes);
+    static BinningState carve(const void* base, size_t R, int end_bit, bool no_color, size_t* bytes, bool depth = false);
 };
 struct SampleState {
     uint32_t* bucket_to_tile; // [B]
     float4* ckpt;             // [B*256] {T, C.r, C.g, C.b} at the start of each bucket, per pixel
     uint64_t* hit;            // [B*256] per bucket and pixel (tile-major element order, like ckpt): bit j = the pixel blended entry j of the
                               // bucket — written by the strict forward, read by the strict backward (its blend / skip decisions)
-    static SampleState carve(const void* base, size_t B, size_t* bytes);
+    float* ckpt_depth;        // [B*256] depth D at the start of each bucket, per pixel: depth forwards only, carved last (NULL otherwise)
+    static SampleState carve(const void* base, size_t B, size_t* bytes, bool depth = false);
 };
 
 }  // namespace gslic

@@ -53,6 +53,10 @@ struct RenderFwdArgs {
     uint32_t capB;             // checkpoint buckets available in bucket_to_tile / ckpt
     uint32_t* status;          // device status words: [2] |= 2 when the buckets did not fit; a non-zero [2] on entry aborts the kernel
     int tail4_from;            // set by launch_render_fwd: tiles from this index on are blended by FOUR waves (one quadrant each); >= gx * gy: none
+    // depth forward (gslic_rasterize_forward_depth; all NULL otherwise): D = sum T alpha z over the colour's contributors
+    float* out_depth;          // [H,W]
+    float* ckpt_depth;         // [B*256] D at the start of each bucket, per pixel (SampleState::ckpt_depth)
+    float* pix_depth;          // [T*256] tile-major final D (ImageState::pix_depth)
 };
 int launch_render_fwd(const RenderFwdArgs& a, hipStream_t s);
 
@@ -75,6 +79,11 @@ struct RenderBwdArgs {
     int T;                     // tiles: bucket_offsets[T - 1] is the real bucket count (B may be a capacity)
     int xcd_lg;                // log2 of the run of consecutive buckets one XCD takes (launch_render_bwd); < 0: bucket = blockIdx.x
     int skip_if_bits;          // pipeline kernel only: leave when the forward recorded decision masks (the row-scan kernel has done the work)
+    // depth backward (gslic_rasterize_backward_depth; all NULL otherwise)
+    const float* dL_ddepth;    // [H,W]
+    const float* ckpt_depth;   // [B*256]
+    const float* pix_depth;    // [T*256]
+    float* partials_z;         // [R] dL/dz (view-space depth) per instance, written where `partials` is
 };
 int launch_render_bwd(const RenderBwdArgs& a, hipStream_t s);
 int launch_render_bwd_scan(const RenderBwdArgs& b, unsigned grid, hipStream_t s);   // render_bwd_scan.hip: strict arithmetic, needs SampleState::hit
@@ -109,6 +118,7 @@ struct PreprocessBwdArgs {
     float* campos_out;    // optional [3]: a copy of campos next to it (the payload's camera centre)
     float* cam_partials;  // optional [ceil(P/64)][32]: per-wave sums of the 27 camera-gradient terms (NULL: not computed)
     float* cam_out;       // [35] = dL_dviewmatrix[16] | dL_dprojmatrix[16] | dL_dcampos[3]
+    const float* partials_z;  // optional [R] (depth backward): dL/dz per instance, gathered like `partials`; dL_dmean3D += sum * (V[2], V[6], V[10])
 };
 int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s);
 

@@ -745,8 +745,43 @@ __global__ __launch_bounds__(256) void cam_reduce_kernel(size_t rows, const floa
     }
 }
 
+// Depth backward (gslic_rasterize_backward_depth), behind preprocess_bwd_kernel: dL/dz of every visible Gaussian = the sum of its instances' partials_z
+// (render_bwd's tenth per-instance sum), gathered like the nine partials (ascending emission slot, dead instances skipped: exact zeros), then
+//   dL_dmean3D += dL/dz (V[2], V[6], V[10])      (z = V[2] x + V[6] y + V[10] z + V[14]: row 2 of the view matrix, element [4c + r]).
+// A kernel of its own so that the per-Gaussian chain above stays the colour-only kernel instruction for instruction — the chain's contraction
+// choices move with any change to its code (the note above GS_PBWD_STRICT_CHAIN), and a zero depth gradient must leave dL_dmean3D as it is.  The
+// depth's share of dL/dopacity needs nothing here: it is inside the opacity partials already (the blend backward's fourth channel).
+__global__ __launch_bounds__(256) void depth_mean3d_kernel(int row_begin, int row_end, const int32_t* __restrict__ radii,
+                                                           const uint32_t* __restrict__ gauss_start, const uint32_t* __restrict__ tiles_touched,
+                                                           const uint8_t* __restrict__ dead, const float* __restrict__ partials_z,
+                                                           const float* __restrict__ V, const uint32_t* __restrict__ status, float* __restrict__ dL_dmean3D)
+{
+    if (status[2] != 0u) return;   // capacity overflow in the forward: preprocess_bwd_kernel wrote nothing either
+    const int idx = row_begin + (int)(blockIdx.x * 256u + threadIdx.x);
+    if (idx >= row_end || radii[idx] <= 0) return;   // invisible: the chain wrote exact zeros and there is no instance
+    const uint32_t u0 = gauss_start[idx], u1 = u0 + tiles_touched[idx];
+    float dz = 0.f;
+    constexpr int UP = 4;   // four instances in flight per trip (masked adds: the same summation order as one at a time)
+    for (uint32_t u = u0; u < u1; u += UP) {
+        bool live[UP];
+        float q[UP];
+#pragma unroll
+        for (int j = 0; j < UP; j++) live[j] = (u + j < u1) && dead[u + j] == 0;
+#pragma unroll
+        for (int j = 0; j < UP; j++) q[j] = live[j] ? partials_z[u + j] : 0.f;
+#pragma unroll
+        for (int j = 0; j < UP; j++)
+            if (live[j]) dz += q[j];
+    }
+    dL_dmean3D[3 * idx] += dz * V[2];
+    dL_dmean3D[3 * idx + 1] += dz * V[6];
+    dL_dmean3D[3 * idx + 2] += dz * V[10];
+}
+
 int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s)
 {
+    if (a.partials_z && (a.cam_partials || a.adam.on || a.dL_drgb || !a.dL_dmean3D))
+        return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no camera gradient, fused Adam or dL_drgb output, and dL_dmean3D is required");
     const bool cam = a.cam_partials != nullptr;
     const int nrows = a.row_end - a.row_begin;
     if (nrows <= 0) return GSLIC_OK;
@@ -760,6 +795,9 @@ int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s)
         if (cam) GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_kernel<false, 256, true>), dim3(div_up(nrows, 256)), dim3(256), 0, s, a);
         else GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_kernel<false, 256, false>), dim3(div_up(nrows, 256)), dim3(256), 0, s, a);
     }
+    if (a.partials_z)
+        GS_LAUNCH(K_PREPROCESS_BWD, depth_mean3d_kernel, dim3(div_up(nrows, 256)), dim3(256), 0, s, a.row_begin, a.row_end, a.radii, a.gauss_start,
+                  a.tiles_touched, a.dead, a.partials_z, a.view, a.status, a.dL_dmean3D);
     if (cam) {
         const size_t rows = (a.M == 15 && a.shs && (a.dL_dsh || a.adam.on || a.dL_drgb)) ? (size_t)div_up(a.P, 64) : (size_t)div_up(a.P, 256) * 4;
         GS_LAUNCH(K_PREPROCESS_BWD, cam_reduce_kernel, dim3(27), dim3(256), 0, s, rows, (const float*)a.cam_partials, a.cam_out);

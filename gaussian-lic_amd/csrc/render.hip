@@ -70,8 +70,12 @@ __device__ __forceinline__ float strip_max_p2(float hA, float hC, float nB, floa
 #ifndef GS_FWD_WAVES
 #define GS_FWD_WAVES 7   // (8: 64 VGPRs, 12 spilled — 0.349 ms either way, profiles/r06n_occupancy_others_ab.log)
 #endif
-template <bool STRICT, int SPLIT>
-__global__ __launch_bounds__(64, SPLIT >= 2 ? GS_FWD_WAVES : 5) void render_fwd_kernel(RenderFwdArgs a)
+#ifndef GS_FWD_WAVES_DEPTH
+#define GS_FWD_WAVES_DEPTH 6   // the depth instantiations: one accumulator more per pixel; at 7 waves (72 VGPRs) the strict one spilled 10 registers
+#endif
+// DEPTH (gslic_rasterize_forward_depth): the body also blends the view-space depth (render_fwd_body.inc); false is the colour-only kernel
+template <bool STRICT, int SPLIT, bool DEPTH>
+__global__ __launch_bounds__(64, SPLIT >= 2 ? (DEPTH ? GS_FWD_WAVES_DEPTH : GS_FWD_WAVES) : 5) void render_fwd_kernel(RenderFwdArgs a)
 {
     __shared__ float4 s_rec[3 * GS_BUCKET];
     // 1-D grid in groups of 8 * SPLIT workgroups: workgroup b of a group works on tile 8 * group + b % 8, quadrants (b / 8) * QN...:
@@ -95,8 +99,8 @@ __global__ __launch_bounds__(64, SPLIT >= 2 ? GS_FWD_WAVES : 5) void render_fwd_
 // eight, so a workgroup's XCD — blockIdx % 8 — is its tile's in both parts).  No workgroup of the grid is empty: a first version that launched four
 // per tile everywhere and let two of them leave ran the two-wave tiles on HALF the machine (the dispatcher's workgroup -> CU pattern is periodic:
 // 0.35 -> 0.52 ms).
-template <bool STRICT>
-__global__ __launch_bounds__(64, GS_FWD_WAVES) void render_fwd_tail_kernel(RenderFwdArgs a)
+template <bool STRICT, bool DEPTH>
+__global__ __launch_bounds__(64, DEPTH ? GS_FWD_WAVES_DEPTH : GS_FWD_WAVES) void render_fwd_tail_kernel(RenderFwdArgs a)
 {
     __shared__ float4 s_rec[3 * GS_BUCKET];
     const uint32_t n2 = 2u * (uint32_t)a.tail4_from;
@@ -164,6 +168,7 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 struct BwdLane {
     v2f d0, hAC, col_rg;          // centre relative to the tile origin; log2(e)-scaled conic diagonal {-1/2 A, -1/2 C}; colour r, g
     float nB, lop, colb;          // log2(e)-scaled -B; log2(opacity); colour b
+    float z;                      // DEPTH: view-space depth, the fourth channel of the dot product
 };
 
 // DST <- shift(SRC) with lane 0 <- INJ.  The DPP's destination is the register that held the injected value, so two steps per trip
@@ -175,7 +180,7 @@ struct BwdLane {
     asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"                           \
                  "v_mov_b32_dpp %1, %3 wave_shr:1 row_mask:0xf bank_mask:0xf"                                           \
                  : "+v"(IT), "+v"(IA) : "v"(ST), "v"(SA))
-#define GS_BW_PREFETCH(USE_BITS, NT, NA, NR, NH)                                                                     \
+#define GS_BW_PREFETCH(USE_BITS, NT, NA, NR, NH, NG)                                                                 \
     do { /* entry (step + 1) - lane of the arrays, clamped to [0, ninj]: entry 0 until the lane's first pixel arrives (its state is still */ \
          /* T = A = 0, see above), the all-zero entry ninj once the last pixel has passed; lane 0's {T, A} is the next injection */          \
         uint32_t oc_;                                                                                                \
@@ -184,12 +189,13 @@ struct BwdLane {
         const float2 bt_ = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(smem) + BW_OFF_BT + oc_);   \
         const float2 ta_ = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(smem) + BW_OFF_TA + oc_);   \
         if (USE_BITS) NH = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(smem) + BW_OFF_HM + oc_);    \
+        if (DEPTH) NG = reinterpret_cast<const float2*>(reinterpret_cast<const char*>(smem) + BW_OFF_GD + oc_)->x;  \
         NR = make_float4(rg_.x, rg_.y, bt_.x, bt_.y);                                                                \
         NT = ta_.x; NA = ta_.y;                                                                                      \
         asm volatile("v_add_u32 %0, %0, %1" : "+v"(off) : "v"(keight)); /* (left to the compiler: three adds and a copy per two steps) */ \
         __builtin_amdgcn_sched_barrier(0); /* keep the LDS reads at the top of the step: a whole step passes before they are used */ \
     } while (0)
-#define GS_BW_BODY(USE_BITS, T_, A_, GR, GH)                                                                         \
+#define GS_BW_BODY(USE_BITS, T_, A_, GR, GH, GD)                                                                     \
     do {                                                                                                             \
         const float4 gr = GR;                                                                                        \
         const uint32_t TAG = __float_as_uint(gr.w);                                                                  \
@@ -216,6 +222,8 @@ struct BwdLane {
         float cg = L.col_rg.x * gr.x;                                                                                \
         cg = __builtin_fmaf(L.col_rg.y, gr.y, cg);                                                                   \
         cg = __builtin_fmaf(L.colb, gr.z, cg); /* c . dL/dpixel */                                                   \
+        if (DEPTH) { cg = __builtin_fmaf(L.z, GD, cg); /* + z dL/ddepth: the fourth channel */                       \
+                     acc_z = __builtin_fmaf(Ta, GD, acc_z); }                                                        \
         acc_rg = GS_PK_FMA(GS_SPLAT(Ta), ((v2f){gr.x, gr.y}), acc_rg); acc_b = __builtin_fmaf(Ta, gr.z, acc_b);      \
         A_ = __builtin_fmaf(Ta, cg, A_);                                                                             \
         const float dLda = __builtin_fmaf(rinv, A_, T_ * cg);                                                        \
@@ -228,7 +236,10 @@ struct BwdLane {
         acc_op += w; /* divided by the opacity at the end */                                                         \
     } while (0)
 
-template <bool BITS>
+// DEPTH (gslic_rasterize_backward_depth): dL/ddepth joins dL/dpixel as a fourth channel — c . g + z g_D per pair, A seeded with
+// (checkpoint D - final D) g_D as well, and a tenth per-instance sum dL/dz = sum T alpha g_D written to partials_z.  A fifth float2 array in LDS
+// carries the pixels' g_D (its .y is unused).
+template <bool BITS, bool DEPTH>
 __global__ __launch_bounds__(64) void render_bwd_kernel(RenderBwdArgs a)
 {
     // Three float2 arrays of 256 + 1 entries in injection order — {dL/dpixel.r, .g}, {dL/dpixel.b, tag}, {T, A} at the start of this bucket
@@ -236,12 +247,13 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(RenderBwdArgs a)
     // (what the pipeline takes in while the last pixels drain); no slack entries in front or behind.  6168 bytes per wave: 26 workgroups per CU
     // (the 7.5 KB of the unclamped layout allowed 21).
     constexpr int NENT = GS_TILE_PIX + 1;
-    constexpr uint32_t BW_OFF_BT = NENT * 8u, BW_OFF_TA = 2u * NENT * 8u, BW_OFF_HM = 3u * NENT * 8u;
-    __shared__ float2 smem[(BITS ? 4 : 3) * NENT];   // BITS: + the pixels' recorded 64-bit decision masks (8224 bytes per wave: 19 per CU)
+    constexpr uint32_t BW_OFF_BT = NENT * 8u, BW_OFF_TA = 2u * NENT * 8u, BW_OFF_HM = 3u * NENT * 8u, BW_OFF_GD = (BITS ? 4u : 3u) * NENT * 8u;
+    __shared__ float2 smem[((BITS ? 4 : 3) + (DEPTH ? 1 : 0)) * NENT];   // BITS: + the pixels' recorded 64-bit decision masks (8224 bytes per wave: 19 per CU)
     float2* const s_rg = smem;
     float2* const s_bt = smem + NENT;
     float2* const s_ta = smem + 2 * NENT;
     uint2* const s_hm = reinterpret_cast<uint2*>(smem + 3 * NENT);   // (BITS only)
+    float2* const s_gd = smem + (BITS ? 4 : 3) * NENT;                // (DEPTH only) {dL/ddepth, -}
     const int lane = threadIdx.x;
     // Workgroup i runs on XCD i % 8 (eight private L2s).  The buckets of a tile are consecutive and all read the tile's pix_final, dL_dpixel
     // and the forward's per-tile data: runs of 2^xcd_lg consecutive buckets go to the same XCD, back to back, so that only the first
@@ -275,7 +287,7 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(RenderBwdArgs a)
     const size_t plane = (size_t)a.H * a.W;
     // ---- the tile's 256 pixels, four per lane, fetched at once
     float4 ck[4], pf[4];
-    float fg[4][3];
+    float fg[4][3], ckd[4], pfd[4], fgd[4];
     bool inside[4];
     uint2 hm[4];
 #pragma unroll
@@ -290,16 +302,19 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(RenderBwdArgs a)
         const int px = tx0 + tile_pix_x(pidx), py = ty0 + tile_pix_y(pidx);
         inside[c] = px < a.W && py < a.H;
         fg[c][0] = fg[c][1] = fg[c][2] = 0.f;
+        ckd[c] = pfd[c] = fgd[c] = 0.f;
+        if constexpr (DEPTH) { ckd[c] = a.ckpt_depth[(size_t)bucket * GS_TILE_PIX + pidx]; pfd[c] = a.pix_depth[(size_t)tile * GS_TILE_PIX + pidx]; }
         if (inside[c]) {
             const size_t pid = (size_t)py * a.W + px;
             fg[c][0] = a.dL_dpix[pid]; fg[c][1] = a.dL_dpix[plane + pid]; fg[c][2] = a.dL_dpix[2 * plane + pid];
+            if constexpr (DEPTH) fgd[c] = a.dL_ddepth[pid];
         }
     }
     // ---- this lane's Gaussian
     const float LOG2E = 1.4426950408889634f;
     BwdLane L;
     L.d0 = L.hAC = L.col_rg = (v2f){0.f, 0.f};
-    L.nB = L.colb = 0.f;
+    L.nB = L.colb = L.z = 0.f;
     L.lop = -__builtin_inff();  // a lane without a Gaussian: alpha = exp2(-inf) = 0, contributes nothing whatever the decision bits say
     float rop = 0.f;            // 1 / opacity
     if (valid) {
@@ -311,6 +326,7 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(RenderBwdArgs a)
         L.lop = __builtin_amdgcn_logf(r1.y);
         rop = r1.y > 0.f ? 1.0f / r1.y : 0.f;
         L.col_rg.x = r1.z; L.col_rg.y = r1.w; L.colb = r2.x;
+        if constexpr (DEPTH) L.z = r2.y;
     }
 
     // ---- injection order.  A pixel injected at position i with rel_i Gaussians of this bucket still in front of its last contributor
@@ -360,6 +376,7 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(RenderBwdArgs a)
             float A0 = (ck[c].y - pf[c].x) * fg[c][0];  // ar = checkpoint colour - final colour (backward.cu:522-523), dotted with dL/dpixel
             A0 = __builtin_fmaf(ck[c].z - pf[c].y, fg[c][1], A0);
             A0 = __builtin_fmaf(ck[c].w - pf[c].z, fg[c][2], A0);
+            if constexpr (DEPTH) { A0 = __builtin_fmaf(ckd[c] - pfd[c], fgd[c], A0); s_gd[pos[c]] = make_float2(fgd[c], 0.f); }
             s_rg[pos[c]] = make_float2(fg[c][0], fg[c][1]);
             s_bt[pos[c]] = make_float2(fg[c][2], __uint_as_float((rel[c] << 16) | ((uint32_t)tile_pix_y((int)pidx) << 8) | ((uint32_t)tile_pix_x((int)pidx) << 4)));
             if constexpr (BITS) s_hm[pos[c]] = hm[c];
@@ -369,6 +386,7 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(RenderBwdArgs a)
     if (lane == 0) {   // the drain entry (tag 0, mask 0: no pair blends; T = A = 0 injected)
         s_rg[ninj] = s_bt[ninj] = s_ta[ninj] = make_float2(0.f, 0.f);
         if constexpr (BITS) s_hm[ninj] = make_uint2(0u, 0u);
+        if constexpr (DEPTH) s_gd[ninj] = make_float2(0.f, 0.f);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -381,26 +399,27 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(RenderBwdArgs a)
     uint32_t klo = lane >= 32 ? 0u : 0xffffffffu;   // ... the low (all ones) or the high (all zeros) dword of the pixel's mask
     asm volatile("" : "+v"(c099), "+v"(c255), "+v"(ninf), "+v"(kneg), "+v"(kcmp), "+v"(kbit), "+v"(klo));
     v2f acc_S = {0.f, 0.f}, acc_cxy = {0.f, 0.f}, acc_rg = {0.f, 0.f};
-    float acc_cw = 0, acc_op = 0, acc_b = 0;
+    float acc_cw = 0, acc_op = 0, acc_b = 0, acc_z = 0;
     // {T, A}: the state travelling through the lanes (set 1) and the injection fetched one step ahead (set 2); a step shifts set 1
     // into set 2 (whose lane 0 holds the injection), so the sets swap roles every step: two steps per trip, no register copies.  The
     // records alternate between Ra and Rb the same way.
     float T1 = 0.f, A1 = 0.f, T2, A2;
     float4 Ra, Rb;
     uint2 Ha = make_uint2(0u, 0u), Hb = make_uint2(0u, 0u);
+    float Ga = 0.f, Gb = 0.f;   // DEPTH: the held pixel's dL/ddepth, fetched with its record
     int off = -8 * lane, kzero_i = 0, khi = 8 * (int)ninj, keight = 8;   // byte offset of entry (0 - lane); the clamp bounds; all in VGPRs
     asm volatile("" : "+v"(off), "+v"(kzero_i), "+v"(khi), "+v"(keight));
     // Two steps per trip, an even number of steps: one step more than needed is harmless — every lane then holds a pixel at or behind its
     // last contributor in this bucket (or the all-zero drain entry), which blends nothing — and the trip needs no exit test in its middle.
 #define GS_BW_LOOP(USE_BITS)                                                                                         \
-    GS_BW_PREFETCH(USE_BITS, T2, A2, Ra, Ha);                                                                        \
+    GS_BW_PREFETCH(USE_BITS, T2, A2, Ra, Ha, Ga);                                                                    \
     for (uint32_t sidx = 0; sidx < nsteps; sidx += 2) {                                                              \
         GS_BW_SHIFT_INJ(T2, A2, T1, A1); /* set 2 = state */                                                         \
-        GS_BW_PREFETCH(USE_BITS, T1, A1, Rb, Hb);                                                                    \
-        GS_BW_BODY(USE_BITS, T2, A2, Ra, Ha);                                                                        \
+        GS_BW_PREFETCH(USE_BITS, T1, A1, Rb, Hb, Gb);                                                                \
+        GS_BW_BODY(USE_BITS, T2, A2, Ra, Ha, Ga);                                                                    \
         GS_BW_SHIFT_INJ(T1, A1, T2, A2); /* set 1 = state */                                                         \
-        GS_BW_PREFETCH(USE_BITS, T2, A2, Ra, Ha);                                                                    \
-        GS_BW_BODY(USE_BITS, T1, A1, Rb, Hb);                                                                        \
+        GS_BW_PREFETCH(USE_BITS, T2, A2, Ra, Ha, Ga);                                                                \
+        GS_BW_BODY(USE_BITS, T1, A1, Rb, Hb, Gb);                                                                    \
     }
     if (use_bits) { GS_BW_LOOP(true) } else { GS_BW_LOOP(false) }
 #undef GS_BW_LOOP
@@ -417,6 +436,7 @@ __global__ __launch_bounds__(64) void render_bwd_kernel(RenderBwdArgs a)
         *reinterpret_cast<gs_v4f_u*>(o) = (gs_v4f_u){gx, gy, -0.5f * acc_cxy.x, -0.5f * acc_cxy.y};
         *reinterpret_cast<gs_v4f_u*>(o + 4) = (gs_v4f_u){-0.5f * acc_cw, acc_op * rop, acc_rg.x, acc_rg.y};
         o[8] = acc_b;
+        if constexpr (DEPTH) a.partials_z[slot] = acc_z;
     }
 }
 
@@ -441,7 +461,8 @@ static bool forward_known_strict(const void* hit)
     return false;
 }
 
-int launch_render_fwd(const RenderFwdArgs& a, hipStream_t s)
+template <bool DEPTH>
+static int launch_render_fwd_t(const RenderFwdArgs& a, hipStream_t s)
 {
     if (!a.no_color && a.hit) note_forward(a.hit, g_strict_math != 0);
     // waves per tile: two halve the serial chain of a tile's wave, at the price of both fetching the tile's records — which the XCD-aware
@@ -462,20 +483,25 @@ int launch_render_fwd(const RenderFwdArgs& a, hipStream_t s)
         if (!tail4_env && tail_tiles > 896u) tail_tiles = 896u;
         b.tail4_from = (int)(T - tail_tiles) & ~7;   // whole groups of eight tiles
         const unsigned grid = 2u * (unsigned)b.tail4_from + 32u * ((T - (unsigned)b.tail4_from + 7u) / 8u);
-        if (g_strict_math) GS_LAUNCH(K_RENDER_FWD, (render_fwd_tail_kernel<true>), dim3(grid), dim3(64), 0, s, b);
-        else GS_LAUNCH(K_RENDER_FWD, (render_fwd_tail_kernel<false>), dim3(grid), dim3(64), 0, s, b);
+        if (g_strict_math) GS_LAUNCH(K_RENDER_FWD, (render_fwd_tail_kernel<true, DEPTH>), dim3(grid), dim3(64), 0, s, b);
+        else GS_LAUNCH(K_RENDER_FWD, (render_fwd_tail_kernel<false, DEPTH>), dim3(grid), dim3(64), 0, s, b);
         return GSLIC_OK;
     }
-    if (g_strict_math && split == 1) GS_LAUNCH(K_RENDER_FWD, (render_fwd_kernel<true, 1>), dim3(groups * 8u), dim3(64), 0, s, a);
-    else if (g_strict_math && split == 4) GS_LAUNCH(K_RENDER_FWD, (render_fwd_kernel<true, 4>), dim3(groups * 32u), dim3(64), 0, s, a);
-    else if (g_strict_math) GS_LAUNCH(K_RENDER_FWD, (render_fwd_kernel<true, 2>), dim3(groups * 16u), dim3(64), 0, s, a);   // per-pixel arithmetic does not depend on the split
-    else if (split == 1) GS_LAUNCH(K_RENDER_FWD, (render_fwd_kernel<false, 1>), dim3(groups * 8u), dim3(64), 0, s, a);
-    else if (split == 4) GS_LAUNCH(K_RENDER_FWD, (render_fwd_kernel<false, 4>), dim3(groups * 32u), dim3(64), 0, s, a);
-    else GS_LAUNCH(K_RENDER_FWD, (render_fwd_kernel<false, 2>), dim3(groups * 16u), dim3(64), 0, s, a);
+    if (g_strict_math && split == 1) GS_LAUNCH(K_RENDER_FWD, (render_fwd_kernel<true, 1, DEPTH>), dim3(groups * 8u), dim3(64), 0, s, a);
+    else if (g_strict_math && split == 4) GS_LAUNCH(K_RENDER_FWD, (render_fwd_kernel<true, 4, DEPTH>), dim3(groups * 32u), dim3(64), 0, s, a);
+    else if (g_strict_math) GS_LAUNCH(K_RENDER_FWD, (render_fwd_kernel<true, 2, DEPTH>), dim3(groups * 16u), dim3(64), 0, s, a);   // per-pixel arithmetic does not depend on the split
+    else if (split == 1) GS_LAUNCH(K_RENDER_FWD, (render_fwd_kernel<false, 1, DEPTH>), dim3(groups * 8u), dim3(64), 0, s, a);
+    else if (split == 4) GS_LAUNCH(K_RENDER_FWD, (render_fwd_kernel<false, 4, DEPTH>), dim3(groups * 32u), dim3(64), 0, s, a);
+    else GS_LAUNCH(K_RENDER_FWD, (render_fwd_kernel<false, 2, DEPTH>), dim3(groups * 16u), dim3(64), 0, s, a);
     return GSLIC_OK;
+}
+int launch_render_fwd(const RenderFwdArgs& a, hipStream_t s)
+{
+    return a.out_depth ? launch_render_fwd_t<true>(a, s) : launch_render_fwd_t<false>(a, s);
 }
 int launch_render_bwd(const RenderBwdArgs& a, hipStream_t s)
 {
+    const bool depth = a.dL_ddepth != nullptr;
     if (a.B <= 0) return GSLIC_OK;
     // GSLIC_BWD_XCD_RUN = run length of consecutive buckets per XCD (a power of two; 0 = plain blockIdx order)
     static const int xcd_lg = [] {
@@ -495,12 +521,17 @@ int launch_render_bwd(const RenderBwdArgs& a, hipStream_t s)
     if (g_strict_math && use_scan) {
         // the row-scan kernel works from the decision masks of a strict forward; when the forward recorded none (the mode was switched in
         // between) every one of its workgroups leaves at once and the pipeline kernel behind it re-derives the decisions instead
-        launch_render_bwd_scan(b, grid, s);
+        launch_render_bwd_scan(b, grid, s);   // (depth: its DEPTH instantiation, chosen from b.dL_ddepth)
         if (forward_known_strict(a.hit)) return GSLIC_OK;
         b.skip_if_bits = 1;
     }
-    if (g_strict_math) GS_LAUNCH(K_RENDER_BWD, render_bwd_kernel<true>, dim3(grid), dim3(64), 0, s, b);
-    else GS_LAUNCH(K_RENDER_BWD, render_bwd_kernel<false>, dim3(grid), dim3(64), 0, s, b);
+    if (depth) {
+        if (g_strict_math) GS_LAUNCH(K_RENDER_BWD, (render_bwd_kernel<true, true>), dim3(grid), dim3(64), 0, s, b);
+        else GS_LAUNCH(K_RENDER_BWD, (render_bwd_kernel<false, true>), dim3(grid), dim3(64), 0, s, b);
+        return GSLIC_OK;
+    }
+    if (g_strict_math) GS_LAUNCH(K_RENDER_BWD, (render_bwd_kernel<true, false>), dim3(grid), dim3(64), 0, s, b);
+    else GS_LAUNCH(K_RENDER_BWD, (render_bwd_kernel<false, false>), dim3(grid), dim3(64), 0, s, b);
     return GSLIC_OK;
 }
 

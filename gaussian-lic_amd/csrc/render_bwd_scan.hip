@@ -130,6 +130,7 @@ struct ScanEntry {     // one list entry of the bucket, as the pipeline's BwdLan
     float hA, hC, nB;  // log2(e)-scaled conic: -1/2 A, -1/2 C, -B
     float lop;         // log2(opacity); -inf for an empty slot (alpha = exp2(-inf) = 0)
     float cr, cg, cb;  // colour
+    float z;           // DEPTH: view-space depth
 };
 
 constexpr int SC_HALF = 32 + 1;            // pixel records of a half quadrant (8x4 pixels) + its all-zero record
@@ -140,7 +141,7 @@ struct ScanLds {
     float4 ent[64 * SC_ENT_F4];       // the bucket's 64 entries (stride 12 floats)
     float acc[64 * 9];                // their nine sums, accumulated over the four quadrants
     uint32_t list[2 * 64];            // compacted entry indices of the two half quadrants being worked on
-    float2 ta[SC_NENT], rg[SC_NENT], bx[SC_NENT], py[SC_NENT];   // pixel records in compacted order: {T, A} {g.r, g.g} {g.b, px} {py, -}
+    float2 ta[SC_NENT], rg[SC_NENT], bx[SC_NENT], py[SC_NENT];   // pixel records in compacted order: {T, A} {g.r, g.g} {g.b, px} {py, dL/ddepth (DEPTH)}
     uint2 hm[SC_NENT];                // ... and the pixel's decision mask
 };
 
@@ -148,26 +149,27 @@ struct ScanLds {
 // lane = (entry slot, pixel row).  A specialisation per group count: the chunk loop carries no per-group branch, and every group's entry and
 // its nine sums stay in registers.  The block is a HALF quadrant (8x4 pixels): its entry set is smaller than the quadrant's (23 against 28 of
 // 64 on the 2M / 1080p scene) and fills its groups of sixteen better — 16 % fewer steps than whole quadrants (tools/bwd_hitmask_model.py).
-template <int NG>
-__device__ __forceinline__ void block_pass(ScanLds& S, const int lane, const int rb, const int lb, const int npx_, const int ne, float c099)
+// DEPTH: dL/ddepth is a fourth channel of the per-pair dot product (c . g + z g_D), and a tenth sum per entry, dL/dz = sum T alpha g_D, goes to accz.
+template <int NG, bool DEPTH>
+__device__ __forceinline__ void block_pass(ScanLds& S, float* accz, const int lane, const int rb, const int lb, const int npx_, const int ne, float c099)
 {
     const int npx = rb + npx_;
     const int slot_i = lane & 15, row = lane >> 4;
     ScanEntry E[NG];
     uint32_t ent[NG], kbit[NG], klo[NG];
     v2f_s acc_S[NG], acc_cxy[NG], acc_rg[NG];
-    float acc_cw[NG], acc_op[NG], acc_b[NG];
+    float acc_cw[NG], acc_op[NG], acc_b[NG], acc_z[NG];
 #pragma unroll
     for (int g = 0; g < NG; g++) {
         acc_S[g] = acc_cxy[g] = acc_rg[g] = (v2f_s){0.f, 0.f};
-        acc_cw[g] = acc_op[g] = acc_b[g] = 0.f;
-        E[g] = {0.f, 0.f, 0.f, 0.f, 0.f, -__builtin_inff(), 0.f, 0.f, 0.f};   // an empty slot: alpha = exp2(-inf) = 0 whatever the masks say
+        acc_cw[g] = acc_op[g] = acc_b[g] = acc_z[g] = 0.f;
+        E[g] = {0.f, 0.f, 0.f, 0.f, 0.f, -__builtin_inff(), 0.f, 0.f, 0.f, 0.f};   // an empty slot: alpha = exp2(-inf) = 0 whatever the masks say
         ent[g] = 0u; kbit[g] = 0u; klo[g] = 0u;
         const int k = 16 * g + slot_i;
         if (k < ne) {
             const uint32_t e = S.list[lb + k];
             const float4 e0 = S.ent[SC_ENT_F4 * e], e1 = S.ent[SC_ENT_F4 * e + 1], e2 = S.ent[SC_ENT_F4 * e + 2];
-            E[g] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x};
+            E[g] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, DEPTH ? e2.w : 0.f};
             ent[g] = e; kbit[g] = e & 31u; klo[g] = e < 32u ? 0xffffffffu : 0u;
         }
     }
@@ -178,7 +180,7 @@ __device__ __forceinline__ void block_pass(ScanLds& S, const int lane, const int
         const float2 ta = S.ta[idx], rg = S.rg[idx], bx = S.bx[idx], pyv = S.py[idx];
         const uint2 hm = S.hm[idx];
         float Tin = ta.x, Ain = ta.y;
-        const float pxf = bx.y, pyf = pyv.x;
+        const float pxf = bx.y, pyf = pyv.x, gD = pyv.y;
 #pragma unroll
         for (int g = 0; g < NG; g++) {
             const float dx = E[g].d0x - pxf, dy = E[g].d0y - pyf;
@@ -202,11 +204,13 @@ __device__ __forceinline__ void block_pass(ScanLds& S, const int lane, const int
             float cgd = E[g].cr * rg.x;
             cgd = __builtin_fmaf(E[g].cg, rg.y, cgd);
             cgd = __builtin_fmaf(E[g].cb, bx.x, cgd);              // c . dL/dpixel
+            if constexpr (DEPTH) cgd = __builtin_fmaf(E[g].z, gD, cgd);   // + z dL/ddepth
             const float Ap = Ain + row_scan_add(Ta * cgd);         // A behind this entry (the pipeline's A_ after its own contribution)
             const float dLda = __builtin_fmaf(rinv, Ap, Ti * cgd);
             const float w = ah * dLda;                             // opacity * G * dL/dalpha = G * dL/dG
             acc_rg[g] = __builtin_elementwise_fma((v2f_s){Ta, Ta}, (v2f_s){rg.x, rg.y}, acc_rg[g]);
             acc_b[g] = __builtin_fmaf(Ta, bx.x, acc_b[g]);
+            if constexpr (DEPTH) acc_z[g] = __builtin_fmaf(Ta, gD, acc_z[g]);
             const v2f_s d = {dx, dy};
             const v2f_s wd = (v2f_s){w, w} * d;
             acc_S[g] += wd;
@@ -229,6 +233,12 @@ __device__ __forceinline__ void block_pass(ScanLds& S, const int lane, const int
 #pragma unroll
             for (int k = 0; k < 9; k++) S.acc[9 * ent[g] + k] += v[k];
         }
+        if constexpr (DEPTH) {
+            float vz = acc_z[g];
+            vz += __shfl_xor(vz, 16, 64);
+            vz += __shfl_xor(vz, 32, 64);
+            if (row == 0 && 16 * g + slot_i < ne) accz[ent[g]] += vz;
+        }
     }
 }
 
@@ -236,9 +246,16 @@ __device__ __forceinline__ void block_pass(ScanLds& S, const int lane, const int
 #define GS_SCAN_WAVES 4   // waves per SIMD the register allocation aims at (124 VGPRs, no spills).  5 (96 VGPRs, 34 spilled, all but three reloads outside the
                           // chunk loops) was measured: 0.449 -> 0.592 ms (profiles/r04w_bwd_scan_five_waves_ab.log)
 #endif
-__global__ __launch_bounds__(64, GS_SCAN_WAVES) void render_bwd_scan_kernel(RenderBwdArgs a)
+#ifndef GS_SCAN_WAVES_DEPTH
+#define GS_SCAN_WAVES_DEPTH GS_SCAN_WAVES   // the depth instantiation (two more registers per entry group)
+#endif
+// DEPTH (gslic_rasterize_backward_depth): see block_pass; the pixels' dL/ddepth rides in the spare .y of S.py, the entries' z in the spare .w of
+// their third float4, the tenth sums in accz; A is seeded with (checkpoint D - final D) g_D as well
+template <bool DEPTH>
+__global__ __launch_bounds__(64, DEPTH ? GS_SCAN_WAVES_DEPTH : GS_SCAN_WAVES) void render_bwd_scan_kernel(RenderBwdArgs a)
 {
     __shared__ ScanLds S;
+    __shared__ float s_accz[DEPTH ? 64 : 1];
     const int lane = threadIdx.x;
     uint32_t bucket = blockIdx.x;
     if (a.xcd_lg >= 0) {   // runs of 2^xcd_lg consecutive buckets per XCD (launch_render_bwd)
@@ -265,7 +282,7 @@ __global__ __launch_bounds__(64, GS_SCAN_WAVES) void render_bwd_scan_kernel(Rend
     // ---- lane = entry: stage the bucket's entries
     const float LOG2E = 1.4426950408889634f;
     {
-    ScanEntry L = {0.f, 0.f, 0.f, 0.f, 0.f, -__builtin_inff(), 0.f, 0.f, 0.f};
+    ScanEntry L = {0.f, 0.f, 0.f, 0.f, 0.f, -__builtin_inff(), 0.f, 0.f, 0.f, 0.f};
     float rop = 0.f;
     if (valid && !((GS_SCAN_SKIP & 32) && a.T > -1)) {
         const uint32_t g = a.point_list[range.x + kit];
@@ -276,12 +293,14 @@ __global__ __launch_bounds__(64, GS_SCAN_WAVES) void render_bwd_scan_kernel(Rend
         L.lop = __builtin_amdgcn_logf(r1.y);
         rop = r1.y > 0.f ? 1.0f / r1.y : 0.f;
         L.cr = r1.z; L.cg = r1.w; L.cb = r2.x;
+        if constexpr (DEPTH) L.z = r2.y;
     }
     S.ent[SC_ENT_F4 * lane] = make_float4(L.d0x, L.d0y, L.hA, L.hC);
     S.ent[SC_ENT_F4 * lane + 1] = make_float4(L.nB, L.lop, L.cr, L.cg);
-    S.ent[SC_ENT_F4 * lane + 2] = make_float4(L.cb, rop, __uint_as_float(slot), 0.f);   // (.y, .z: what the lane needs again at the very end)
+    S.ent[SC_ENT_F4 * lane + 2] = make_float4(L.cb, rop, __uint_as_float(slot), DEPTH ? L.z : 0.f);   // (.y, .z: what the lane needs again at the very end)
 #pragma unroll
     for (int k = 0; k < 9; k++) S.acc[9 * lane + k] = 0.f;
+    if constexpr (DEPTH) s_accz[lane] = 0.f;
     }
 
     float c099 = 0.99f;
@@ -290,7 +309,7 @@ __global__ __launch_bounds__(64, GS_SCAN_WAVES) void render_bwd_scan_kernel(Rend
     // One quadrant's per-pixel inputs.  All four loads of a lane are issued together (the checkpoint of a pixel that turns out inactive is
     // stale memory and is never used), and quadrant q + 1's are in flight while quadrant q is worked on: a bucket otherwise spends eight
     // dependent round trips to memory here with four waves per SIMD to hide them.
-    struct PixIn { uint64_t hm; float4 pf, ck; float g0, g1, g2; };
+    struct PixIn { uint64_t hm; float4 pf, ck; float g0, g1, g2, ckd, pfd, gd; };
     auto load_pix = [&](int q) {
         PixIn r;
         const int pidx = q * 64 + lane;
@@ -299,9 +318,12 @@ __global__ __launch_bounds__(64, GS_SCAN_WAVES) void render_bwd_scan_kernel(Rend
         r.ck = a.ckpt[(size_t)bucket * GS_TILE_PIX + pidx];
         const int px = tx0 + tile_pix_x(pidx), py = ty0 + tile_pix_y(pidx);
         r.g0 = r.g1 = r.g2 = 0.f;
+        r.ckd = r.pfd = r.gd = 0.f;
+        if constexpr (DEPTH) { r.ckd = a.ckpt_depth[(size_t)bucket * GS_TILE_PIX + pidx]; r.pfd = a.pix_depth[(size_t)tile * GS_TILE_PIX + pidx]; }
         if (px < a.W && py < a.H) {
             const size_t pid = (size_t)py * a.W + px;
             r.g0 = a.dL_dpix[pid]; r.g1 = a.dL_dpix[plane + pid]; r.g2 = a.dL_dpix[2 * plane + pid];
+            if constexpr (DEPTH) r.gd = a.dL_ddepth[pid];
         }
         return r;
     };
@@ -345,12 +367,13 @@ __global__ __launch_bounds__(64, GS_SCAN_WAVES) void render_bwd_scan_kernel(Rend
             float A0 = (ck.y - pf.x) * g0;   // ar = checkpoint colour - final colour (backward.cu:522-523), dotted with dL/dpixel
             A0 = __builtin_fmaf(ck.z - pf.y, g1, A0);
             A0 = __builtin_fmaf(ck.w - pf.z, g2, A0);
+            if constexpr (DEPTH) A0 = __builtin_fmaf(cur.ckd - cur.pfd, cur.gd, A0);   // + (checkpoint D - final D) dL/ddepth
             // position among the active pixels of this lane's half (mbcnt_lo counts the set bits below a lane of the lower half, mbcnt_hi of the upper)
             const uint32_t pos = half ? (uint32_t)SC_HALF + __builtin_amdgcn_mbcnt_hi(balh[1], 0u) : __builtin_amdgcn_mbcnt_lo(balh[0], 0u);
             S.ta[pos] = make_float2(ck.x, A0);
             S.rg[pos] = make_float2(g0, g1);
             S.bx[pos] = make_float2(g2, (float)lx);
-            S.py[pos] = make_float2((float)ly, 0.f);
+            S.py[pos] = make_float2((float)ly, DEPTH ? cur.gd : 0.f);
             S.hm[pos] = make_uint2(mlo, mhi);
         }
         if ((lane & 31) == 0) {   // the all-zero record of each half: what a row without a pixel (last chunk) works on — nothing blends, every product is an exact zero
@@ -371,10 +394,10 @@ __global__ __launch_bounds__(64, GS_SCAN_WAVES) void render_bwd_scan_kernel(Rend
             if (npx == 0 || ((GS_SCAN_SKIP & 1) && a.T > -1)) continue;
             const int ne = h ? __popc(S_lo[1]) + __popc(S_hi[1]) : __popc(S_lo[0]) + __popc(S_hi[0]);
             switch ((ne + 15) >> 4) {
-            case 1: block_pass<1>(S, lane, h * SC_HALF, 64 * h, npx, ne, c099); break;
-            case 2: block_pass<2>(S, lane, h * SC_HALF, 64 * h, npx, ne, c099); break;
-            case 3: block_pass<3>(S, lane, h * SC_HALF, 64 * h, npx, ne, c099); break;
-            default: block_pass<4>(S, lane, h * SC_HALF, 64 * h, npx, ne, c099); break;
+            case 1: block_pass<1, DEPTH>(S, s_accz, lane, h * SC_HALF, 64 * h, npx, ne, c099); break;
+            case 2: block_pass<2, DEPTH>(S, s_accz, lane, h * SC_HALF, 64 * h, npx, ne, c099); break;
+            case 3: block_pass<3, DEPTH>(S, s_accz, lane, h * SC_HALF, 64 * h, npx, ne, c099); break;
+            default: block_pass<4, DEPTH>(S, s_accz, lane, h * SC_HALF, 64 * h, npx, ne, c099); break;
             }
         }
     }
@@ -403,12 +426,14 @@ __global__ __launch_bounds__(64, GS_SCAN_WAVES) void render_bwd_scan_kernel(Rend
         *reinterpret_cast<gs_v4f_u*>(o) = (gs_v4f_u){gx, gy, -0.5f * cxx, -0.5f * cxy};
         *reinterpret_cast<gs_v4f_u*>(o + 4) = (gs_v4f_u){-0.5f * cyy, op * rop, cr, cg};
         o[8] = cb;
+        if constexpr (DEPTH) a.partials_z[slot] = s_accz[lane];
     }
 }
 
 int launch_render_bwd_scan(const RenderBwdArgs& b, unsigned grid, hipStream_t s)
 {
-    GS_LAUNCH(K_RENDER_BWD, render_bwd_scan_kernel, dim3(grid), dim3(64), 0, s, b);
+    if (b.dL_ddepth) GS_LAUNCH(K_RENDER_BWD, render_bwd_scan_kernel<true>, dim3(grid), dim3(64), 0, s, b);
+    else GS_LAUNCH(K_RENDER_BWD, render_bwd_scan_kernel<false>, dim3(grid), dim3(64), 0, s, b);
     return GSLIC_OK;
 }
 

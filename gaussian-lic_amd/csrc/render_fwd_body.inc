@@ -1,12 +1,15 @@
 // render_fwd_body.inc — the body of the forward blend, included textually by the kernels of render.hip (a function taking the tile and the quadrant
-// as arguments compiles to a slower loop: 0.347 -> 0.355 ms, round 6).  The includer defines, in the enclosing scope: STRICT (bool constant),
-// GS_BODY_SPLIT (waves per tile: 1, 2 or 4), `a` (RenderFwdArgs), `s_rec` (the wave's 3 * GS_BUCKET float4 of LDS), `tile` and `q0` (first quadrant).
+// as arguments compiles to a slower loop: 0.347 -> 0.355 ms, round 6).  The includer defines, in the enclosing scope: STRICT and DEPTH (bool
+// constants), GS_BODY_SPLIT (waves per tile: 1, 2 or 4), `a` (RenderFwdArgs), `s_rec` (the wave's 3 * GS_BUCKET float4 of LDS), `tile` and `q0`
+// (first quadrant).  DEPTH: a fourth accumulator per pixel, D = sum T alpha z over exactly the colour's contributors (z = view-space depth, the
+// record's r2.y), checkpointed with {T, C} and written to out_depth / pix_depth; without it the body is what it was, instruction for instruction.
 {
     constexpr int QN = 4 / GS_BODY_SPLIT;          // quadrants (= pixels per lane) of this wave
     const int lane = threadIdx.x;
     const int tx0 = (tile % a.gx) * GS_TILE, ty0 = (tile / a.gx) * GS_TILE;
     if (a.status[2] != 0u) return;  // capacity mode: the instance lists did not fit; the host re-runs the step with larger buffers
     if (STRICT && !a.no_color && blockIdx.x == 0 && lane == 0) a.status[GS_FLAG_HITBITS] = 1u;   // this forward records SampleState::hit
+    if (DEPTH && blockIdx.x == 0 && lane == 0) a.status[GS_FLAG_DEPTH] = 1u;                       // ... and the depth arrays
     const uint2 range = a.ranges[tile];
     const int n = (int)(range.y - range.x);
     const bool color = !a.no_color;
@@ -31,12 +34,13 @@
     for (int q = 0; q < QN; q++) { pxi[q] = tx0 + tile_pix_x((q0 + q) * 64 + lane); pyi[q] = ty0 + tile_pix_y((q0 + q) * 64 + lane); }
     // The sign of T carries the `done` flag (forward.cu:352,439-443): T > 0 = still blending, T < 0 = finished with
     // transmittance |T| (T never reaches 0: blending stops below 1e-4).  One register and no flag bookkeeping per pixel.
-    float T[QN], Cr[QN], Cg[QN], Cb[QN];
+    float T[QN], Cr[QN], Cg[QN], Cb[QN], Dz[QN];
     uint32_t last[QN];
 #pragma unroll
     for (int q = 0; q < QN; q++) {
         T[q] = (pxi[q] < a.W && pyi[q] < a.H) ? 1.0f : -1.0f;
         Cr[q] = Cg[q] = Cb[q] = 0.0f;
+        Dz[q] = 0.0f;
         last[q] = 0;
     }
     const float LOG2E = 1.4426950408889634f;
@@ -65,10 +69,16 @@
 #pragma unroll
             for (int q = 0; q < QN; q++)
                 if (T[q] > 0.f) ck[(q0 + q) * 64] = make_float4(T[q], Cr[q], Cg[q], Cb[q]);
+            if constexpr (DEPTH) {
+                float* ckd = a.ckpt_depth + ((size_t)(bbm + (uint32_t)(base / GS_BUCKET)) * GS_TILE_PIX) + lane;
+#pragma unroll
+                for (int q = 0; q < QN; q++)
+                    if (T[q] > 0.f) ckd[(q0 + q) * 64] = Dz[q];
+            }
         }
         const int m = (n - base) < GS_BUCKET ? (n - base) : GS_BUCKET;
         // each lane fetches one record and pre-scales its conic: exponent in base 2, relative to this lane-independent tile origin
-        float fdx = 0, fdy = 0, fhA = 0, fhC = 0, fnB = 0, fop = 0, flop = -__builtin_inff(), fr = 0, fg = 0, fb = 0;
+        float fdx = 0, fdy = 0, fhA = 0, fhC = 0, fnB = 0, fop = 0, flop = -__builtin_inff(), fr = 0, fg = 0, fb = 0, fz = 0;
         uint32_t fmask = 0;
         float fthr = 0.f;
         if (lane < m && !((GS_FWD_SKIP & 8) && a.gx > -1)) {
@@ -78,6 +88,7 @@
             fdx = r0.x - (float)tx0; fdy = r0.y - (float)ty0;
             fhA = -0.5f * LOG2E * r0.z; fnB = -LOG2E * r0.w; fhC = -0.5f * LOG2E * r1.x;
             fop = r1.y; fr = r1.z; fg = r1.w; fb = r2.x;
+            if constexpr (DEPTH) fz = r2.y;   // p_view.z, the sort key
             flop = __builtin_amdgcn_logf(fop);  // log2(opacity): alpha = exp2(p2 + log2 opacity), one multiply less per (pixel, entry)
             // which of this wave's 8x8 quadrants (= the QN pixels of every lane) can this entry reach at all (bit q = quadrant q0 + q)
 #pragma unroll
@@ -103,7 +114,7 @@
         // issue slots, which is what bounds this kernel — LDS reads do not
         s_rec[3 * lane] = make_float4(fdx, fdy, fhA, fnB);
         s_rec[3 * lane + 1] = make_float4(fhC, STRICT ? fop : flop, fr, fg);
-        s_rec[3 * lane + 2] = make_float4(fb, __uint_as_float(fmask), fthr, 0.f);
+        s_rec[3 * lane + 2] = make_float4(fb, __uint_as_float(fmask), fthr, DEPTH ? fz : 0.f);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         // one list entry against this lane's four pixels.  STRICT: the reference's arithmetic with its branches.  Default: straight-line
@@ -122,7 +133,7 @@
             if constexpr (STRICT) vbit = 1u << ((contributor - 1u) & 31u);   // (wave-uniform; one v_mov per entry)
             const uint32_t smask = (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(e2.y));  // this wave's quadrants
             if (smask == 0u) return;
-            const float gdx = e0.x, gdy = e0.y, hA = e0.z, nB = e0.w, hC = e1.x, op = e1.y, colr = e1.z, colg = e1.w, colb = e2.x;
+            const float gdx = e0.x, gdy = e0.y, hA = e0.z, nB = e0.w, hC = e1.x, op = e1.y, colr = e1.z, colg = e1.w, colb = e2.x, z = e2.w;
             if constexpr (STRICT) {
 #pragma clang fp contract(off)
                 // forward.cu:424-445 operation for operation: d from absolute coordinates, the three products of the power rounded one by
@@ -153,6 +164,7 @@
                             asm("v_or_b32 %0, %0, %1" : "+v"(T[q]) : "v"(ksign));   // -|T|
                         } else {
                             Cr[q] = Cr[q] + (colr * alpha) * T[q]; Cg[q] = Cg[q] + (colg * alpha) * T[q]; Cb[q] = Cb[q] + (colb * alpha) * T[q];
+                            if constexpr (DEPTH) Dz[q] = Dz[q] + (z * alpha) * T[q];   // a fourth channel, in the colour's operation order
                             asm("v_mov_b32 %0, %1" : "+v"(T[q]) : "v"(test_T));
                             asm("v_mov_b32 %0, %1" : "+v"(last[q]) : "v"(vcontrib));
                             hcur[q] |= vbit;   // this pixel blended this entry
@@ -182,6 +194,7 @@
                     const bool app = ok & !stop;                                    // taken by a finished pixel: test_T < 0, and -|T| = T
                     const float w = app ? alpha * T[q] : 0.0f;
                     Cr[q] = __builtin_fmaf(colr, w, Cr[q]); Cg[q] = __builtin_fmaf(colg, w, Cg[q]); Cb[q] = __builtin_fmaf(colb, w, Cb[q]);
+                    if constexpr (DEPTH) Dz[q] = __builtin_fmaf(z, w, Dz[q]);
                     const float Tdone = stop ? -__builtin_fabsf(T[q]) : T[q];
                     T[q] = app ? test_T : Tdone;
                     last[q] = app ? vcontrib : last[q];
@@ -227,9 +240,11 @@
                 a.out_color[plane + pid] = Cg[q];
                 a.out_color[2 * plane + pid] = Cb[q];
             }
+            if constexpr (DEPTH) a.out_depth[pid] = Dz[q];
         }
         if (color) {
             a.pix_final[(size_t)tile * GS_TILE_PIX + (q0 + q) * 64 + lane] = make_float4(Cr[q], Cg[q], Cb[q], __uint_as_float(last[q]));
+            if constexpr (DEPTH) a.pix_depth[(size_t)tile * GS_TILE_PIX + (q0 + q) * 64 + lane] = Dz[q];
             mymax = last[q] > mymax ? last[q] : mymax;
         }
     }

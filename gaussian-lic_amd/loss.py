@@ -61,6 +61,15 @@ def l1_loss(network_output, gt):
     return torch.abs(network_output - gt).mean()
 
 
+def depth_l1(depth, gt_depth):
+    """Masked L1 for LiDAR depth supervision: mean |depth - gt_depth| over the pixels where gt_depth > 0 (a sparse projected depth image,
+    Camera.project_depth); 0 when there are none (still a tensor connected to `depth`, so backward() works)."""
+    mask = gt_depth > 0
+    n = mask.sum()
+    diff = torch.where(mask, (depth - gt_depth).abs(), torch.zeros_like(depth))
+    return diff.sum() / n.clamp_min(1).to(depth.dtype)
+
+
 def psnr(img1, img2):
     """loss_utils.h:35-39."""
     mse = torch.pow(img1 - img2, 2).mean()

@@ -87,6 +87,41 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     return (R.value, B.value, out_color, out_final_T, radii, allocs[0].tensor, allocs[1].tensor, allocs[2].tensor, allocs[3].tensor)
 
 
+def rasterize_gaussians_depth(background, means3D, opacity, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy,
+                              image_height, image_width, limx_neg, limx_pos, limy_neg, limy_pos, dc, sh, degree, campos, prefiltered=False,
+                              debug=False, raw_params=False, tie_rank=None):
+    """gslic_rasterize_forward_depth (no reference counterpart): rasterize_gaussians plus the depth image.  Returns
+    (num_rendered, num_buckets, out_color, out_final_T, out_depth, radii, geomBuffer, binningBuffer, imgBuffer, sampleBuffer).
+    out_depth [H,W] = sum T alpha z over the colour's contributors (z = view-space depth), NOT normalised (divide by 1 - final_T for
+    the expected depth of the covered part); colour, final_T and radii are bit-identical to rasterize_gaussians'."""
+    if means3D.dim() != 2 or means3D.size(1) != 3:
+        raise ValueError("means3D must have dimensions (num_points, 3)")
+    L = _lib.lib()
+    dev = means3D.device
+    P, H, W = means3D.size(0), int(image_height), int(image_width)
+    M = sh.size(1) if sh is not None and sh.size(0) != 0 else 0
+    alloc = torch.zeros if P == 0 else torch.empty
+    out_color = alloc(3, H, W, dtype=torch.float32, device=dev)
+    out_final_T = alloc(H, W, dtype=torch.float32, device=dev)
+    out_depth = alloc(H, W, dtype=torch.float32, device=dev)
+    radii = torch.empty(P, dtype=torch.int32, device=dev)
+    allocs = [_lib.TensorAllocator(dev) for _ in range(4)]  # geom, binning, img, sample
+    R, B = ctypes.c_int32(0), ctypes.c_int32(0)
+    if P != 0:
+        means3D, dc, opacity, scales, rotations = map(_f32c, (means3D, dc, opacity, scales, rotations))
+        sh_c = _f32c(sh) if M > 0 else None
+        viewmatrix, projmatrix, campos, background = map(_f32c, (viewmatrix, projmatrix, campos, background))
+        prm = _params(P, degree, M, H, W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier,
+                      prefiltered, debug, False, raw_params, tie_rank)
+        p = _lib.ptr
+        _lib.check(L.gslic_rasterize_forward_depth(
+            ctypes.byref(prm), allocs[0].cb, None, allocs[1].cb, None, allocs[2].cb, None, allocs[3].cb, None,
+            p(background), p(means3D), p(dc), p(sh_c), None, p(opacity), p(scales), p(rotations), None,
+            p(viewmatrix), p(projmatrix), p(campos), p(out_color), p(out_final_T), p(out_depth), p(radii),
+            ctypes.byref(R), ctypes.byref(B), _lib.current_stream_ptr()))
+    return (R.value, B.value, out_color, out_final_T, out_depth, radii, allocs[0].tensor, allocs[1].tensor, allocs[2].tensor, allocs[3].tensor)
+
+
 class CapacityBuffers:
     """Caller-owned scratch + outputs of gslic_rasterize_forward_capacity for one (P, W, H): nothing is allocated per step, every
     address is stable, so the step can be captured in a hipGraph.  cap_R / cap_B: how many instances / checkpoint buckets fit."""
@@ -237,6 +272,94 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     return res + cam if camera_grads else res
 
 
+def rasterize_gaussians_backward_depth(background, means3D, radii, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx,
+                                       tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, dL_dout_color, dL_dout_depth, dc, sh, degree, campos,
+                                       geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank=0.0, debug=False, raw_params=False):
+    """gslic_rasterize_backward_depth: rasterize_gaussians_backward with dL/d(out_depth) [H,W] as a second input, on the buffers of
+    rasterize_gaussians_depth.  Returns the same nine tensors (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc,
+    dL_dsh, dL_dscales, dL_drotations); dL_dout_depth = 0 gives rasterize_gaussians_backward's results bit for bit."""
+    L = _lib.lib()
+    dev = means3D.device
+    P, H, W = means3D.size(0), dL_dout_color.size(1), dL_dout_color.size(2)
+    M = sh.size(1) if sh is not None and sh.size(0) != 0 else 0
+    mk = (lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)) if P != 0 else \
+        (lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev))
+    dL_dmeans3D, dL_dmeans2D, dL_dcolors = mk(P, 3), mk(P, 3), mk(P, 3)
+    dL_dconic, dL_dopacities, dL_dcov3D = mk(P, 2, 2), mk(P, 1), mk(P, 6)
+    dL_ddc, dL_dsh, dL_dscales, dL_drotations = mk(P, 1, 3), mk(P, M, 3), mk(P, 3), mk(P, 4)
+    if P != 0:
+        means3D, dc, scales, rotations, dL, dLd = map(_f32c, (means3D, dc, scales, rotations, dL_dout_color, dL_dout_depth))
+        sh_c = _f32c(sh) if M > 0 else None
+        viewmatrix, projmatrix, campos, background = map(_f32c, (viewmatrix, projmatrix, campos, background))
+        prm = _params(P, degree, M, H, W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier,
+                      False, debug, False, raw_params)
+        p = _lib.ptr
+        _lib.check(L.gslic_rasterize_backward_depth(
+            ctypes.byref(prm), int(R), int(B), p(background), p(means3D), p(dc), p(sh_c), None, p(scales), p(rotations), None,
+            p(viewmatrix), p(projmatrix), p(campos), p(radii.contiguous()),
+            ctypes.c_void_p(geomBuffer.data_ptr()), ctypes.c_void_p(binningBuffer.data_ptr()),
+            ctypes.c_void_p(imageBuffer.data_ptr()), ctypes.c_void_p(sampleBuffer.data_ptr()), p(dL), p(dLd),
+            p(dL_dmeans2D), p(dL_dconic), p(dL_dopacities), p(dL_dcolors), p(dL_dmeans3D), p(dL_dcov3D), p(dL_ddc),
+            p(dL_dsh), p(dL_dscales), p(dL_drotations), float(lambda_erank), _lib.current_stream_ptr()))
+    return (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscales, dL_drotations)
+
+
+def _depth_grads(ctx, dL_dcolor, dL_ddepth, xyz, dc, sh, opacity, scaling, rotation, radii, geom, binning, img, sample, raw):
+    rs = ctx.rs
+    if dL_dcolor is None:
+        dL_dcolor = torch.zeros(3, rs.image_height, rs.image_width, dtype=torch.float32, device=xyz.device)
+    if dL_ddepth is None:
+        dL_ddepth = torch.zeros(rs.image_height, rs.image_width, dtype=torch.float32, device=xyz.device)
+    return rasterize_gaussians_backward_depth(
+        rs.bg, xyz, radii, scaling, rotation, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.limx_neg,
+        rs.limx_pos, rs.limy_neg, rs.limy_pos, dL_dcolor, dL_ddepth, dc, sh, rs.sh_degree, rs.campos, geom, ctx.R, binning, img, ctx.B,
+        sample, rs.lambda_erank, False, raw_params=raw)
+
+
+class GaussianRasterizerDepthFunction(torch.autograd.Function):
+    """GaussianRasterizerFunction plus a differentiable depth image (activated parameters): forward returns (color, radii, final_T, depth)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, dc, sh, opacities, scales, rotations, rs):
+        (R, B, color, final_T, depth, radii, geom, binning, img, sample) = rasterize_gaussians_depth(
+            rs.bg, means3D, opacities, scales, rotations, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
+            rs.image_height, rs.image_width, rs.limx_neg, rs.limx_pos, rs.limy_neg, rs.limy_pos, dc, sh, rs.sh_degree, rs.campos,
+            rs.prefiltered, rs.debug, tie_rank=rs.tie_rank)
+        ctx.rs, ctx.R, ctx.B = rs, R, B
+        ctx.save_for_backward(means3D, dc, sh, opacities, scales, rotations, radii, geom, binning, img, sample)
+        ctx.mark_non_differentiable(radii, final_T)
+        return color, radii, final_T, depth
+
+    @staticmethod
+    def backward(ctx, dL_dcolor, _dL_dradii, _dL_dfinal_T, dL_ddepth):
+        means3D, dc, sh, opacities, scales, rotations, radii, geom, binning, img, sample = ctx.saved_tensors
+        g = _depth_grads(ctx, dL_dcolor, dL_ddepth, means3D, dc, sh, opacities, scales, rotations, radii, geom, binning, img, sample, False)
+        (dL_dmeans2D, _dL_dcolors, dL_dopacities, dL_dmeans3D, _dL_dcov3D, dL_ddc, dL_dsh, dL_dscales, dL_drotations) = g
+        return (dL_dmeans3D, dL_dmeans2D, dL_ddc, dL_dsh, dL_dopacities, dL_dscales, dL_drotations, None)
+
+
+class RawGaussianRasterizerDepthFunction(torch.autograd.Function):
+    """RawGaussianRasterizerFunction plus a differentiable depth image (raw parameters): forward returns (color, radii, final_T, depth)."""
+
+    @staticmethod
+    def forward(ctx, xyz, dc, sh, opacity_raw, scaling_raw, rotation_raw, rs):
+        (R, B, color, final_T, depth, radii, geom, binning, img, sample) = rasterize_gaussians_depth(
+            rs.bg, xyz, opacity_raw, scaling_raw, rotation_raw, rs.scale_modifier, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
+            rs.image_height, rs.image_width, rs.limx_neg, rs.limx_pos, rs.limy_neg, rs.limy_pos, dc, sh, rs.sh_degree, rs.campos,
+            rs.prefiltered, rs.debug, raw_params=True, tie_rank=rs.tie_rank)
+        ctx.rs, ctx.R, ctx.B = rs, R, B
+        ctx.save_for_backward(xyz, dc, sh, opacity_raw, scaling_raw, rotation_raw, radii, geom, binning, img, sample)
+        ctx.mark_non_differentiable(radii, final_T)
+        return color, radii, final_T, depth
+
+    @staticmethod
+    def backward(ctx, dL_dcolor, _dL_dradii, _dL_dfinal_T, dL_ddepth):
+        xyz, dc, sh, opacity_raw, scaling_raw, rotation_raw, radii, geom, binning, img, sample = ctx.saved_tensors
+        g = _depth_grads(ctx, dL_dcolor, dL_ddepth, xyz, dc, sh, opacity_raw, scaling_raw, rotation_raw, radii, geom, binning, img, sample, True)
+        (_m2, _c, dL_dopacity, dL_dxyz, _cov, dL_ddc, dL_dsh, dL_dscaling, dL_drotation) = g
+        return (dL_dxyz, dL_ddc.view_as(dc), dL_dsh.view_as(sh), dL_dopacity.view_as(opacity_raw), dL_dscaling, dL_drotation, None)
+
+
 class GaussianRasterizerFunction(torch.autograd.Function):
     """rasterizer.cpp:21-183.  forward returns (color, radii, final_T); only d/dcolor flows back."""
 
@@ -323,7 +446,7 @@ def _raw_leaves(model):
     return None
 
 
-def render(camera, model, bg_color, no_color=False, scaling_modifier=1.0, raw=None):
+def render(camera, model, bg_color, no_color=False, scaling_modifier=1.0, raw=None, return_depth=False):
     """renderer.cpp:21-88 — same signature, same five results (image, final_T, screenspace_points, visible, radii).  `camera` =
     gaussian_lic_amd.camera.Camera with device tensors attached via to_device(); `model` exposes get_xyz / get_opacity / get_scaling /
     get_rotation / get_features_dc / get_features_rest, sh_degree, lambda_erank.
@@ -332,7 +455,12 @@ def render(camera, model, bg_color, no_color=False, scaling_modifier=1.0, raw=No
     one autograd node whose kernels apply the activations (RawGaussianRasterizerFunction) instead of calling getOpacity() / getScaling() /
     getRotation() (renderer.cpp:57-63).  Image and gradients equal the operator path's up to fp32 rounding of the activation chain
     (tests/test_fused_gpu.py).  screenspace_points is then a zero-stride view of one zero row: the reference allocates and zero-fills
-    [P,3] for a gradient (dL_dmeans2D) no caller of render() reads (gaussian.cpp:506,683,757,797); raw=False restores it."""
+    [P,3] for a gradient (dL_dmeans2D) no caller of render() reads (gaussian.cpp:506,683,757,797); raw=False restores it.
+
+    return_depth=True (not in the reference; LiDAR depth supervision): a sixth result, depth [H,W] = sum T alpha z over exactly the
+    contributors of the pixel's colour (z = view-space depth of the Gaussian), differentiable on the raw and the activated path.  It is
+    NOT normalised: the background contributes 0, and depth / (1 - final_T) is the expected depth of the covered part.  The five other
+    results are bit-identical to return_depth=False's.  Needs the colour (no_color=False)."""
     import os
     leaves = _raw_leaves(model)
     if raw is None:
@@ -347,11 +475,24 @@ def render(camera, model, bg_color, no_color=False, scaling_modifier=1.0, raw=No
             raise TypeError("render(raw=True): the model does not expose its raw parameter leaves (set raw_parameter_leaves = True on a model whose "
                             "xyz / features_dc / features_rest / opacity / scaling / rotation attributes are the PRE-activation tensors, or provide raw_leaves())")
         xyz, dc, rest, opacity, scaling, rotation = leaves
+        if return_depth:
+            if no_color:
+                raise ValueError("render(return_depth=True) needs the colour (no_color=False)")
+            image, radii, final_T, depth = RawGaussianRasterizerDepthFunction.apply(xyz, dc, rest, opacity, scaling, rotation, rs)
+            screenspace_points = torch.zeros(1, 3, dtype=xyz.dtype, device=xyz.device).expand(xyz.shape[0], 3)
+            return image, final_T, screenspace_points, radii > 0, radii, depth
         image, radii, final_T = RawGaussianRasterizerFunction.apply(xyz, dc, rest, opacity, scaling, rotation, rs)
         screenspace_points = torch.zeros(1, 3, dtype=xyz.dtype, device=xyz.device).expand(xyz.shape[0], 3)
         return image, final_T, screenspace_points, radii > 0, radii
     xyz = model.get_xyz()
     screenspace_points = torch.zeros_like(xyz, requires_grad=True)
+    if return_depth:
+        if no_color:
+            raise ValueError("render(return_depth=True) needs the colour (no_color=False)")
+        image, radii, final_T, depth = GaussianRasterizerDepthFunction.apply(
+            xyz, screenspace_points, model.get_features_dc(), model.get_features_rest(), model.get_opacity(), model.get_scaling(),
+            model.get_rotation(), rs)
+        return image, final_T, screenspace_points, radii > 0, radii, depth
     rasterizer = GaussianRasterizer(rs)
     image, radii, final_T = rasterizer(xyz, screenspace_points, model.get_opacity(), model.get_features_dc(),
                                        model.get_features_rest(), None, model.get_scaling(), model.get_rotation(), None)

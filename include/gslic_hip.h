@@ -205,6 +205,92 @@ int gslic_rasterize_backward(
     void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Depth rendering (LiDAR depth supervision; no reference counterpart).
+ *
+ * gslic_rasterize_forward_depth — gslic_rasterize_forward plus one output:
+ *  out_depth      [H,W]     depth[y,x] = sum_i T_i alpha_i z_i over EXACTLY the contributors of the pixel's colour (same alpha,
+ *                           transmittance, cut-offs and early stop; same arithmetic mode, gslic_set_math_mode), z_i = the Gaussian's
+ *                           view-space depth p_view.z (the key the forward sorts on).  The background contributes 0 and the depth is
+ *                           NOT normalised: divide by (1 - out_final_T) for the expected depth of the covered part.
+ *  Colour, final_T, radii, R and B are bit-identical to gslic_rasterize_forward's.  The allocator callbacks are asked for more bytes:
+ *  img + 4 per pixel (of the 16x16 tile grid), sample + 4 per bucket-pixel (1 KiB per checkpoint bucket), binning + 4 per instance,
+ *  carved behind every other array (the colour-only layout is an exact prefix).  no_color = 1, or out_depth == NULL with P > 0, is
+ *  GSLIC_ERR_INVALID_ARG; P == 0 returns at once and calls no allocator.
+ *
+ * gslic_rasterize_backward_depth — gslic_rasterize_backward plus one input:
+ *  dL_ddepth      [H,W]     gradient of the loss w.r.t. out_depth
+ *  The ten outputs are as gslic_rasterize_backward's, with the depth's share added: through alpha (dL_dmean2D, dL_dconic,
+ *  dL_dopacity and everything behind them) and through z (dL_dmean3D += dL/dz * row 2 of the view matrix, added last — so
+ *  dL_ddepth = 0 gives gslic_rasterize_backward's results bit for bit).  dL_dcolor stays the colour's.  The buffers must come from
+ *  gslic_rasterize_forward_depth (else GSLIC_ERR_INVALID_ARG; the library remembers its last 64 forwards, and only for buffers it does
+ *  not know the check costs one 4-byte device read, the call then waits for the stream).  gslic_rasterize_backward on a depth forward's buffers is valid and returns the colour-only gradients.
+ *  no_color = 1, or dL_ddepth == NULL with P > 0, is GSLIC_ERR_INVALID_ARG; P == 0 returns at once.
+ *
+ * Not covered by depth (unchanged, colour only): the capacity / graph path (gslic_rasterize_forward_capacity), the fused-Adam
+ * backward, the N-GPU colour exchange (gslic_rasterize_backward_rgb*), the camera-pose gradient (gslic_rasterize_backward_camera)
+ * and the LibTorch drop-in shim.
+ */
+int gslic_rasterize_forward_depth(
+    const gslic_raster_params* prm,
+    gslic_alloc_fn geom_alloc, void* geom_ctx,
+    gslic_alloc_fn binning_alloc, void* binning_ctx,
+    gslic_alloc_fn img_alloc, void* img_ctx,
+    gslic_alloc_fn sample_alloc, void* sample_ctx,
+    const float* background,
+    const float* means3D,
+    const float* dc,
+    const float* shs,
+    const float* colors_precomp,
+    const float* opacities,
+    const float* scales,
+    const float* rotations,
+    const float* cov3D_precomp,
+    const float* viewmatrix,
+    const float* projmatrix,
+    const float* cam_pos,
+    float* out_color,
+    float* out_final_T,
+    float* out_depth,
+    int32_t* radii,
+    int32_t* num_rendered,
+    int32_t* num_buckets,
+    void* stream);
+
+int gslic_rasterize_backward_depth(
+    const gslic_raster_params* prm,
+    int32_t R, int32_t B,
+    const float* background,
+    const float* means3D,
+    const float* dc,
+    const float* shs,
+    const float* colors_precomp,
+    const float* scales,
+    const float* rotations,
+    const float* cov3D_precomp,
+    const float* viewmatrix,
+    const float* projmatrix,
+    const float* cam_pos,
+    const int32_t* radii,
+    char* geom_buffer,
+    char* binning_buffer,
+    char* img_buffer,
+    char* sample_buffer,
+    const float* dL_dpix,
+    const float* dL_ddepth,
+    float* dL_dmean2D,
+    float* dL_dconic,
+    float* dL_dopacity,
+    float* dL_dcolor,
+    float* dL_dmean3D,
+    float* dL_dcov3D,
+    float* dL_ddc,
+    float* dL_dsh,
+    float* dL_dscale,
+    float* dL_drot,
+    float lambda_erank,
+    void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * gslic_rasterize_backward_adam — single-GPU fast path (no reference counterpart; SURVEY.md §8f row 2 taken one step further):
  * exactly gslic_rasterize_backward with raw_params = 1 followed by gslic_adam_update_groups(visible = radii > 0) over the six
  * parameter groups, but the Adam update is applied inside the per-Gaussian backward kernel while the gradients are still in

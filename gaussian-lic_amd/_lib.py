@@ -43,6 +43,8 @@ EXPORTS = [
     "gslic_rasterize_backward_rgb_rows", "gslic_sh_grad_from_rgb", "gslic_sh_grad_from_rgb_adam", "gslic_rasterize_backward_rgb_payload",
     "gslic_sh_grad_from_rgb_adam_all", "gslic_get_binning_path", "gslic_scratch_round_up",
     "gslic_rasterize_forward_depth", "gslic_rasterize_backward_depth",
+    "gslic_rasterize_forward_depth_capacity", "gslic_rasterize_backward_depth_adam", "gslic_depth_l1_loss_partials_count",
+    "gslic_depth_l1_loss_forward_backward", "gslic_img_bytes_depth", "gslic_binning_bytes_depth", "gslic_sample_bytes_depth",
 ]
 
 _lib = None
@@ -66,12 +68,24 @@ def lib():
     L.gslic_profile_kernel_name.restype = ctypes.c_char_p
     L.gslic_profile_kernel_name.argtypes = [i32]
     L.gslic_profile_get.argtypes = [i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
-    for n in ("gslic_geom_bytes", "gslic_img_bytes", "gslic_binning_bytes", "gslic_sample_bytes"):
+    for n in ("gslic_geom_bytes", "gslic_img_bytes", "gslic_binning_bytes", "gslic_sample_bytes", "gslic_img_bytes_depth", "gslic_binning_bytes_depth",
+              "gslic_sample_bytes_depth"):
         getattr(L, n).restype = ctypes.c_size_t
     L.gslic_geom_bytes.argtypes = [i32]
     L.gslic_img_bytes.argtypes = [i32, i32]
     L.gslic_binning_bytes.argtypes = [i32, i32]
     L.gslic_sample_bytes.argtypes = [i32]
+    L.gslic_img_bytes_depth.argtypes = [i32, i32]
+    L.gslic_binning_bytes_depth.argtypes = [i32]
+    L.gslic_sample_bytes_depth.argtypes = [i32]
+    L.gslic_rasterize_forward_depth_capacity.argtypes = (
+        [ctypes.POINTER(RasterParams)] + [vp, ctypes.c_size_t] * 4 + [vp] * 12 + [vp, vp, vp, vp] +
+        [ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp])
+    L.gslic_rasterize_backward_depth_adam.argtypes = (
+        [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp, vp] + [vp] * 6 + [f32, ctypes.POINTER(AdamFused), vp])
+    L.gslic_depth_l1_loss_partials_count.restype = ctypes.c_int64
+    L.gslic_depth_l1_loss_partials_count.argtypes = [i32, i32]
+    L.gslic_depth_l1_loss_forward_backward.argtypes = [i32, i32, f32, vp, vp, vp, vp, vp, vp]
     L.gslic_rasterize_forward.argtypes = (
         [ctypes.POINTER(RasterParams)] + [ALLOC_FN, vp] * 4 + [vp] * 12 + [vp, vp, vp] +
         [ctypes.POINTER(i32), ctypes.POINTER(i32), vp])

@@ -28,13 +28,14 @@ SOURCES = {
     "render_bwd_scan.hip": ["-fno-slp-vectorize"],
     "preprocess_bwd.hip": [],
     "adam.hip": [],
-    "ssim.hip": ["-ffp-contract=off"],    # the maps are held bit-exact to the reference kernels under the same flag (tests/golden/ssim_*.npz)
+    "ssim.hip": ["-ffp-contract=off"],
+    "depth_loss.hip": [],    # the maps are held bit-exact to the reference kernels under the same flag (tests/golden/ssim_*.npz)
     "knn.hip": [],
     "extend.hip": ["-ffp-contract=off"],  # pixel assignment decides integers: canonical order like preprocess.hip
 }
 COMMON = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-Wno-inline-asm",
           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]
-HEADERS = ["gslic_common.h", "kernels.h", "render_fwd_body.inc", os.path.join("..", "..", "include", "gslic_hip.h")]
+HEADERS = ["gslic_common.h", "kernels.h", "render_fwd_body.inc", "preprocess_bwd_body.inc", os.path.join("..", "..", "include", "gslic_hip.h")]
 
 
 def _newer(a, b):

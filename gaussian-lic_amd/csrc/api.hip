@@ -41,7 +41,7 @@ static bool g_prof_cur_on = false;
 static const char* const k_names[K_COUNT] = {
     "preprocess", "scan_reduce", "scan_spine", "scan_apply", "keybuild", "sort_hist", "sort_scatter", "finalize_lists",
     "bucket_count", "render_fwd", "render_bwd", "preprocess_bwd", "adam", "ssim_fwd", "ssim_bwd", "knn_minmax", "knn_morton",
-    "knn_boxes", "knn_search", "debug_export", "extend", "dsort_hist", "dsort_scatter", "sh_grad_from_rgb", "tile_lsort", "tile_hist", "tile_bin", "tile_scan", "tile_lsort_long"};
+    "knn_boxes", "knn_search", "debug_export", "extend", "dsort_hist", "dsort_scatter", "sh_grad_from_rgb", "tile_lsort", "tile_hist", "tile_bin", "tile_scan", "tile_lsort_long", "depth_loss"};
 uint32_t g_lds_pad[K_COUNT] = {0};
 static const bool g_lds_pad_parsed = [] {   // GSLIC_LDS_PAD="name=bytes,name=bytes"
     const char* e = getenv("GSLIC_LDS_PAD");
@@ -275,6 +275,8 @@ int loss_forward(int, int, int, int, float, float, const float*, const float*, f
 int loss_backward(int, int, int, int, float, const float*, const float*, const float*, const float*, const float*, float*, hipStream_t);
 int loss_forward_backward(int, int, int, int, float, float, float, const float*, const float*, float*, float*, float*, float*, float*, float*, hipStream_t);
 int64_t loss_partials_count(int, int, int, int);
+int depth_loss_forward_backward(int, int, float, const float*, const float*, float*, float*, float*, hipStream_t);
+int64_t depth_loss_partials_count(int, int);
 int extend_select(int, const float*, const float*, const float*, const float*, float, float, float, float, int, int, const float*,
                   gslic_alloc_fn, void*, uint32_t**, uint32_t**, int32_t*, hipStream_t);
 int extend_emit(int, const uint32_t*, const uint32_t*, const float*, const float*, const float*, float, float, int, float*, float*, float*,
@@ -324,6 +326,20 @@ size_t gslic_binning_bytes(int32_t R, int32_t no_color)
     return b;
 }
 size_t gslic_sample_bytes(int32_t B) { size_t b; SampleState::carve(nullptr, (size_t)(B > 0 ? B : 0), &b); return b; }
+// the depth carves (gslic_rasterize_forward_depth*): the colour-only layout plus the depth arrays behind it
+size_t gslic_img_bytes_depth(int32_t W, int32_t H)
+{
+    int gx, gy; size_t b;
+    ImageState::carve(nullptr, (size_t)tile_grid(W, H, gx, gy), &b, true);
+    return b;
+}
+size_t gslic_binning_bytes_depth(int32_t R)
+{
+    size_t b;
+    BinningState::carve(nullptr, (size_t)(R > 0 ? R : 0), 16, false, &b, true);  // (a depth forward always renders the colour)
+    return b;
+}
+size_t gslic_sample_bytes_depth(int32_t B) { size_t b; SampleState::carve(nullptr, (size_t)(B > 0 ? B : 0), &b, true); return b; }
 
 }  // extern "C"
 
@@ -510,7 +526,7 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
     if (cap) {
         // R = the number of instances the caller's binning buffer holds; the kernels stop at the real count (R_dev) and raise
         // status bit 0 when it does not fit.  No host read (the reference blocks here, rasterizer_impl.cu:398).
-        R = capacity_for(cap->binning_bytes, [&](uint32_t r) { size_t b; BinningState::carve(nullptr, (size_t)r, end_bit, no_color, &b); return b; });
+        R = capacity_for(cap->binning_bytes, [&](uint32_t r) { size_t b; BinningState::carve(nullptr, (size_t)r, end_bit, no_color, &b, depth); return b; });
         if (R == 0) return set_error(GSLIC_ERR_INVALID_ARG, "capacity mode: the binning buffer (%zu bytes) does not hold a single instance", cap->binning_bytes);
     } else {
         GS_TRY(fetch_counts(geom.point_offsets + (P - 1), geom.flags, hostbuf, s, geom.flags + GS_FLAG_FAULT));  // host needs R to size the binning buffer (rasterizer_impl.cu:398)
@@ -581,7 +597,7 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
     if (!no_color) {
         if (!use_bin) GS_TRY(launch_bucket_scan(T, img.ranges, img.bucket_offsets, img.max_contrib, s));
         if (cap) {
-            B = capacity_for(cap->sample_bytes, [&](uint32_t b) { size_t n; SampleState::carve(nullptr, (size_t)b, &n); return n; });
+            B = capacity_for(cap->sample_bytes, [&](uint32_t b) { size_t n; SampleState::carve(nullptr, (size_t)b, &n, depth); return n; });
         } else {
             uint32_t bin_sample[2] = {0, 0};   // {global atomics, instances} of the binning kernel's sampled workgroups
             GS_TRY(fetch_counts(img.bucket_offsets + (T - 1), nullptr, hostbuf, s, geom.flags + GS_FLAG_FAULT,
@@ -682,6 +698,20 @@ int gslic_rasterize_forward_capacity(const gslic_raster_params* prm, char* geom_
     return rasterize_forward_impl(prm, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &cap, background, means3D, dc, shs,
                                   colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, out_color,
                                   out_final_T, radii, capacity_R, capacity_B, stream);
+}
+
+int gslic_rasterize_forward_depth_capacity(const gslic_raster_params* prm, char* geom_buffer, size_t geom_bytes, char* binning_buffer,
+                                           size_t binning_bytes, char* img_buffer, size_t img_bytes, char* sample_buffer, size_t sample_bytes,
+                                           const float* background, const float* means3D, const float* dc, const float* shs,
+                                           const float* colors_precomp, const float* opacities, const float* scales, const float* rotations,
+                                           const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+                                           float* out_color, float* out_final_T, float* out_depth, int32_t* radii, int32_t* capacity_R,
+                                           int32_t* capacity_B, uint32_t* status, void* stream)
+{
+    ForwardCapacity cap{geom_buffer, binning_buffer, img_buffer, sample_buffer, geom_bytes, binning_bytes, img_bytes, sample_bytes, status};
+    return rasterize_forward_impl(prm, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &cap, background, means3D, dc, shs,
+                                  colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, out_color,
+                                  out_final_T, radii, capacity_R, capacity_B, stream, out_depth, true);
 }
 
 static int rasterize_backward_impl(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
@@ -951,6 +981,27 @@ int gslic_rasterize_backward_adam(const gslic_raster_params* prm, int32_t R, int
                                    adam, nullptr, stream, nullptr, 0, -1, false, adam->visible_out);
 }
 
+int gslic_rasterize_backward_depth_adam(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
+                                        const float* dc, const float* shs, const float* colors_precomp, const float* scales,
+                                        const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                        const float* cam_pos, const int32_t* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                                        char* sample_buffer, const float* dL_dpix, const float* dL_ddepth, float* dL_dopacity, float* dL_dmean3D,
+                                        float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_erank,
+                                        const gslic_adam_fused* adam, void* stream)
+{
+    GS_TRY(check_params(prm));
+    if (prm->P == 0) return GSLIC_OK;
+    if (!adam) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_adam: adam descriptor is NULL");
+    if (prm->no_color) return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no_color = 1 (no depth forward renders without colour)");
+    if (!dL_ddepth) return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: dL_ddepth is NULL (gslic_rasterize_backward_adam is the colour-only backward)");
+    if (!dL_dmean3D)
+        return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_adam: dL_dmean3D is NULL (the xyz gradient is assembled there before its update)");
+    return rasterize_backward_impl(prm, R, B, background, means3D, dc, shs, colors_precomp, scales, rotations, cov3D_precomp, viewmatrix,
+                                   projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, nullptr,
+                                   nullptr, dL_dopacity, nullptr, dL_dmean3D, nullptr, dL_ddc, dL_dsh, dL_dscale, dL_drot, lambda_erank,
+                                   adam, nullptr, stream, nullptr, 0, -1, false, adam->visible_out, nullptr, dL_ddepth);
+}
+
 int gslic_rasterize_backward_camera(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
                                     const float* dc, const float* shs, const float* colors_precomp, const float* scales,
                                     const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
@@ -1056,6 +1107,16 @@ int gslic_l1_ssim_loss_forward_backward(int32_t B, int32_t CH, int32_t H, int32_
         return set_error(GSLIC_ERR_INVALID_ARG, "loss forward_backward: NULL pointer");
     return loss_forward_backward(B, CH, H, W, C1, C2, lambda_dssim, img, gt, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, partials, terms, dL_dimg,
                                  (hipStream_t)stream);
+}
+
+int64_t gslic_depth_l1_loss_partials_count(int32_t H, int32_t W) { return (H <= 0 || W <= 0) ? 8 : depth_loss_partials_count(H, W); }
+
+int gslic_depth_l1_loss_forward_backward(int32_t H, int32_t W, float lambda_depth, const float* depth, const float* gt_depth, float* partials,
+                                         float* term, float* dL_ddepth, void* stream)
+{
+    if (H <= 0 || W <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "depth loss: empty image");
+    if (!depth || !gt_depth || !partials || !term || !dL_ddepth) return set_error(GSLIC_ERR_INVALID_ARG, "depth loss: NULL pointer");
+    return depth_loss_forward_backward(H, W, lambda_depth, depth, gt_depth, partials, term, dL_ddepth, (hipStream_t)stream);
 }
 
 int gslic_knn_mean_dist2(int32_t P, const float* points, float* mean_dists, gslic_alloc_fn scratch_alloc, void* scratch_ctx,

@@ -68,6 +68,7 @@ enum KernelId {
     K_TILE_BIN,
     K_TILE_SCAN,
     K_TILE_LSORT_LONG,
+    K_DEPTH_LOSS,
     K_COUNT
 };
 void prof_begin(int id, hipStream_t s);

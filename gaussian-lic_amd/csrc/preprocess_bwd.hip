@@ -62,14 +62,15 @@ struct ShOut {  // what phase B needs to write a Gaussian's dL_dsh row
 struct PartialSums { float mx, my, cx, cy, cw, op, r, g, b; };   // the nine per-Gaussian sums of render_bwd's per-instance rows
 
 __device__ __forceinline__ bool bwd_gather(const PreprocessBwdArgs& a, const int idx, const bool staged, PartialSums& ps);
-template <bool CAM>
+template <bool CAM, bool DEFER_XYZ = false>
 __device__ __forceinline__ void bwd_rest(const PreprocessBwdArgs& a, const int idx, const PartialSums& ps, const float* sh_row, const float* sk_row,
                                          ShOut& so, float* sg, float* cg);
 
 // Cooperative sink of the 14 small gradients per Gaussian of one block (see lds_g in the kernel): coalesced float4 stores into the
 // gradient tensors that were asked for (gout, group order of lds_g) and / or the in-place Adam update.  Group g of width w: the
 // block's region is rows * w floats starting at param[g] + row0 * w, 16-byte aligned because BS is a multiple of 4.
-template <int BS>
+// DEFER_XYZ (depth + fused Adam): group 0 (xyz) is stored to gout[0] but not updated — its gradient is not complete yet (depth_mean3d_kernel).
+template <int BS, bool DEFER_XYZ = false>
 __device__ __forceinline__ void small_groups_sink(const AdamFusedArgs& A, float* const (&gout)[5], const float* lds_g, const uint8_t* lds_vis, int row0,
                                                   int rows)
 {
@@ -87,7 +88,7 @@ __device__ __forceinline__ void small_groups_sink(const AdamFusedArgs& A, float*
             if (t < BS * wid[k] / 4) {
                 g[k] = reinterpret_cast<const float4*>(lds_g + off[k])[t];
                 if (gout[k]) reinterpret_cast<float4*>(gout[k] + (size_t)row0 * wid[k])[t] = g[k];
-                if (A.on) {
+                if (A.on && !(DEFER_XYZ && k == 0)) {
                     const int e = 4 * t;
 #pragma unroll
                     for (int c = 0; c < 4; c++) vis[k][c] = lds_vis[(e + c) / wid[k]];
@@ -120,7 +121,7 @@ __device__ __forceinline__ void small_groups_sink(const AdamFusedArgs& A, float*
             const size_t base = (size_t)row0 * wid[k];
             for (int i = t; i < rows * wid[k]; i += BS) {
                 if (gout[k]) gout[k][base + i] = lds_g[off[k] + i];
-                if (A.on && lds_vis[i / wid[k]])
+                if (A.on && !(DEFER_XYZ && k == 0) && lds_vis[i / wid[k]])
                     adam_scalar(A.p[gid[k]][base + i], lds_g[off[k] + i], A.m[gid[k]][base + i], A.v[gid[k]][base + i], A.lr[gid[k]], A.b1, A.b2, A.eps);
             }
         }
@@ -248,124 +249,19 @@ __device__ __forceinline__ void sh_columns_pass(const PreprocessBwdArgs& a, cons
 template <bool LDS_SH, int BS, bool CAM>
 __global__ __launch_bounds__(BS) GS_PBWD_OCC void preprocess_bwd_kernel(PreprocessBwdArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float lds_tab[LDS_SH ? BS * SHT : 4];   // {c_0..c_14, dRGB} per Gaussian; later the 14 small gradients
-    __shared__ float lds_sk[LDS_SH ? BS * 15 : 4];                                    // q_k per Gaussian
-    __shared__ uint8_t lds_vis[BS];
-    // the 14 small-group gradients of every Gaussian of the block, group-major (xyz | dc | opacity | scale | rotation), for the
-    // cooperative float4 Adam below: per-thread 4-byte accesses at stride 12 / 16 B cost this kernel 0.29 ms of 0.86
-    float* const lds_g = lds_tab;  // overlays the table once the column pass is through (14 * BS <= SHT * BS)
-    if (a.status[2] != 0u) return;  // capacity overflow in the forward: nothing of this step is valid — no gradients, no Adam
-    const int idx = a.row_begin + blockIdx.x * BS + threadIdx.x;
-    const int M = a.M;
-    const int row0 = a.row_begin + blockIdx.x * BS;
-    const int rows = (a.row_end - row0) < BS ? (a.row_end - row0) : BS;
-    ShOut so;
-    so.x = so.y = so.z = so.dR = so.dG = so.dB = 0.f;
-    so.on = false;
-    float sg[14];
-#pragma unroll
-    for (int k = 0; k < 14; k++) sg[k] = 0.f;
-    // camera gradient (CAM): 27 sums over the Gaussians — d/dviewmatrix rows 0..2, d/dprojmatrix rows 0, 1, 3, d/dcampos — with the
-    // three matrices treated as the independent inputs they are at this boundary (the reference returns no camera gradient at all:
-    // rasterizer.cpp:181).  Each wave reduces its 64 Gaussians and writes one row of partials; cam_reduce_kernel adds the rows.
-    float cg[CAM ? 27 : 1];
-    if constexpr (CAM) {
-#pragma unroll
-        for (int k = 0; k < 27; k++) cg[k] = 0.f;
-    }
-    PartialSums ps;
-    bool visible = false;
-    if (idx < a.row_end) visible = bwd_gather(a, idx, LDS_SH, ps);
-    lds_vis[threadIdx.x] = visible ? 1 : 0;
-    if (a.vis_out && idx < a.row_end) a.vis_out[idx] = visible ? 1 : 0;                                            // the exchange payload's mask ...
-    if (a.campos_out && blockIdx.x == 0 && threadIdx.x < 3) a.campos_out[threadIdx.x] = a.campos[threadIdx.x];     // ... and camera centre
-    if constexpr (LDS_SH) {
-        // ---- this Gaussian's row of the table (zeros when invisible: its gradient elements and products are then exact zeros)
-        float trow[18];
-#pragma unroll
-        for (int k = 0; k < 18; k++) trow[k] = 0.f;
-        if (visible) {
-            const uint32_t clamp_bits = __float_as_uint(a.rec[GS_REC_F4 * (size_t)idx + 2].z);
-            float dox, doy, doz, x, y, z;
-            sh_dir(a.means[3 * idx], a.means[3 * idx + 1], a.means[3 * idx + 2], a.campos, dox, doy, doz, x, y, z);
-            float c[15];
-            sh_coefs(a.D, x, y, z, c);
-#pragma unroll
-            for (int k = 0; k < 15; k++) trow[k] = c[k];
-            trow[15] = (clamp_bits & 1u) ? 0.f : ps.r; trow[16] = (clamp_bits & 2u) ? 0.f : ps.g; trow[17] = (clamp_bits & 4u) ? 0.f : ps.b;
-        }
-#pragma unroll
-        for (int k = 0; k < 18; k++) lds_tab[threadIdx.x * SHT + k] = trow[k];
-        __syncthreads();
-        // ---- the column pass over the block's SH parameters (full blocks); the last, partial block goes row by row
-        const bool sh_sink = a.dL_dsh || a.adam.on;
-        if (rows == BS) {
-            sh_columns_pass<BS>(a, lds_tab, lds_sk, lds_vis, row0);
-        } else {
-            const size_t base = (size_t)row0 * 45;
-            if ((int)threadIdx.x < rows) {
-#pragma clang fp contract(off)   // (as sh_columns_pass rounds them)
-                const float* __restrict__ sh = a.shs + base + 45 * threadIdx.x;
-                const float* __restrict__ tr = lds_tab + threadIdx.x * SHT;
-#pragma unroll
-                for (int k = 0; k < 15; k++) lds_sk[threadIdx.x * 15 + k] = (sh[3 * k] * tr[15] + sh[3 * k + 1] * tr[16]) + sh[3 * k + 2] * tr[17];
-            }
-            __syncthreads();   // every q_k has been formed from the parameters as they were
-            const AdamFusedArgs& A = a.adam;
-            if (sh_sink)
-                for (int i = threadIdx.x; i < rows * 45; i += BS) {
-                    const int r = i / 45, rem = i - 45 * r, k = rem / 3, ch = rem - 3 * k;
-                    const float g = lds_tab[r * SHT + k] * lds_tab[r * SHT + 15 + ch];
-                    if (a.dL_dsh) a.dL_dsh[base + i] = g;
-                    if (A.on && lds_vis[r]) adam_scalar(A.p[2][base + i], g, A.m[2][base + i], A.v[2][base + i], A.lr[2], A.b1, A.b2, A.eps);
-                }
-        }
-        __syncthreads();   // q_k complete; the table is free
-        if (visible) bwd_rest<CAM>(a, idx, ps, nullptr, lds_sk + threadIdx.x * 15, so, sg, cg);
-    } else {
-        const float* sh_row = a.shs ? a.shs + (size_t)3 * M * idx : nullptr;
-        if (visible) bwd_rest<CAM>(a, idx, ps, sh_row, nullptr, so, nullptr, cg);
-    }
-    if constexpr (CAM) {
-#pragma unroll
-        for (int k = 0; k < 27; k++) {
-            float v = cg[k];
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-            cg[k] = v;
-        }
-        if ((threadIdx.x & 63) == 0) {
-            float* row = a.cam_partials + 32 * ((size_t)blockIdx.x * (BS / 64) + (threadIdx.x >> 6));
-#pragma unroll
-            for (int k = 0; k < 27; k++) row[k] = cg[k];
-        }
-    }
-    if constexpr (LDS_SH) {
-        // ---- small groups: the block's rows of xyz / dc / opacity / scale / rotation are contiguous in memory, so the Adam update runs
-        // on float4 columns of those five regions (at most one float4 per thread and group, all fifteen loads issued before the math)
-        const int t = threadIdx.x;
-        lds_g[3 * t] = sg[0]; lds_g[3 * t + 1] = sg[1]; lds_g[3 * t + 2] = sg[2];
-        lds_g[3 * BS + 3 * t] = sg[3]; lds_g[3 * BS + 3 * t + 1] = sg[4]; lds_g[3 * BS + 3 * t + 2] = sg[5];
-        lds_g[6 * BS + t] = sg[6];
-        lds_g[7 * BS + 3 * t] = sg[7]; lds_g[7 * BS + 3 * t + 1] = sg[8]; lds_g[7 * BS + 3 * t + 2] = sg[9];
-        reinterpret_cast<float4*>(lds_g + 10 * BS)[t] = make_float4(sg[10], sg[11], sg[12], sg[13]);
-        __syncthreads();
-        float* const gout[5] = {a.dL_dmean3D, a.dL_drgb ? a.dL_drgb : a.dL_ddc, a.dL_dopacity, a.dL_dscale, a.dL_drot};
-        small_groups_sink<BS>(a.adam, gout, lds_g, lds_vis, row0, rows);
-    } else if (idx < a.row_end && M > 0 && (a.dL_dsh || a.adam.on)) {
-        // generic row width: per-thread strided rows (dL_dsh zeros when invisible, when shs == NULL, above the active degree)
-        const AdamFusedArgs& A = a.adam;
-        float c[15];
-        sh_coefs(a.D, so.x, so.y, so.z, c);
-        const int nk = M < 15 ? M : 15;
-        const float dR[3] = {so.dR, so.dG, so.dB};
-        const size_t rb = (size_t)3 * M * idx;
-        for (int k = 0; k < 3 * M; k++) {
-            const float g = (so.on && k < 3 * nk) ? c[k / 3] * dR[k % 3] : 0.f;
-            if (a.dL_dsh) a.dL_dsh[rb + k] = g;
-            if (A.on && lds_vis[threadIdx.x]) adam_scalar(A.p[2][rb + k], g, A.m[2][rb + k], A.v[2][rb + k], A.lr[2], A.b1, A.b2, A.eps);
-        }
-    }
+    constexpr bool DEFER_XYZ = false;
+#include "preprocess_bwd_body.inc"
+}
+// gslic_rasterize_backward_depth_adam: the same kernel with xyz's Adam update deferred (DEFER_XYZ).  Its fused Adam updates every group but xyz and
+// writes xyz's chain gradient to dL_dmean3D instead; the depth's share dL/dz (V[2], V[6], V[10]) is gathered after it (depth_mean3d_kernel<true>),
+// which then updates xyz from the complete gradient.  The body is included, not called: the colour-only instantiations above stay instruction for
+// instruction what they were (an inlined function taking the kernel argument by reference allocated registers differently).
+template <bool LDS_SH, int BS>
+__global__ __launch_bounds__(BS) GS_PBWD_OCC void preprocess_bwd_defer_xyz_kernel(PreprocessBwdArgs a)
+{
+    constexpr bool CAM = false;
+    constexpr bool DEFER_XYZ = true;
+#include "preprocess_bwd_body.inc"
 }
 
 // Zero rows of an invisible Gaussian / the segmented sum of a visible one's per-instance rows.  Returns the visibility.
@@ -438,7 +334,7 @@ __device__ __forceinline__ bool bwd_gather(const PreprocessBwdArgs& a, const int
 
 // Everything behind the sums for a VISIBLE Gaussian.  The SH block needs, per coefficient k, only q_k = sum_ch sh[k][ch] dRGB[ch]
 // (dL/ddir = sum_k dc_k/ddir q_k): sk_row hands them over when the block computed them cooperatively, else they are formed from sh_row.
-template <bool CAM>
+template <bool CAM, bool DEFER_XYZ>
 __device__ __forceinline__ void bwd_rest(const PreprocessBwdArgs& a, const int idx, const PartialSums& ps, const float* sh_row, const float* sk_row,
                                          ShOut& so, float* sg, float* cg)
 {
@@ -711,7 +607,7 @@ __device__ __forceinline__ void bwd_rest(const PreprocessBwdArgs& a, const int i
         const float dqv[4] = {dq.x, dq.y, dq.z, dq.w};
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            adam_scalar(A.p[0][3 * idx + k], dmean[k], A.m[0][3 * idx + k], A.v[0][3 * idx + k], A.lr[0], A.b1, A.b2, A.eps);
+            if constexpr (!DEFER_XYZ) adam_scalar(A.p[0][3 * idx + k], dmean[k], A.m[0][3 * idx + k], A.v[0][3 * idx + k], A.lr[0], A.b1, A.b2, A.eps);
             adam_scalar(A.p[1][3 * idx + k], ddc[k], A.m[1][3 * idx + k], A.v[1][3 * idx + k], A.lr[1], A.b1, A.b2, A.eps);
             adam_scalar(A.p[4][3 * idx + k], dscale[k], A.m[4][3 * idx + k], A.v[4][3 * idx + k], A.lr[4], A.b1, A.b2, A.eps);
         }
@@ -751,10 +647,15 @@ __global__ __launch_bounds__(256) void cam_reduce_kernel(size_t rows, const floa
 // A kernel of its own so that the per-Gaussian chain above stays the colour-only kernel instruction for instruction — the chain's contraction
 // choices move with any change to its code (the note above GS_PBWD_STRICT_CHAIN), and a zero depth gradient must leave dL_dmean3D as it is.  The
 // depth's share of dL/dopacity needs nothing here: it is inside the opacity partials already (the blend backward's fourth channel).
+// ADAM (gslic_rasterize_backward_depth_adam, behind preprocess_bwd_defer_xyz_kernel): dL_dmean3D holds the chain's xyz gradient, the sum is formed by
+// the same code and then consumed by the masked Adam update of group 0 (adam_scalar, as gslic_adam_update_groups applies it to visible rows): 12 B
+// per Gaussian read and 12 written more than the colour-only fused step, plus the dz gather.
+template <bool ADAM>
 __global__ __launch_bounds__(256) void depth_mean3d_kernel(int row_begin, int row_end, const int32_t* __restrict__ radii,
                                                            const uint32_t* __restrict__ gauss_start, const uint32_t* __restrict__ tiles_touched,
                                                            const uint8_t* __restrict__ dead, const float* __restrict__ partials_z,
-                                                           const float* __restrict__ V, const uint32_t* __restrict__ status, float* __restrict__ dL_dmean3D)
+                                                           const float* __restrict__ V, const uint32_t* __restrict__ status, float* __restrict__ dL_dmean3D,
+                                                           AdamFusedArgs A)
 {
     if (status[2] != 0u) return;   // capacity overflow in the forward: preprocess_bwd_kernel wrote nothing either
     const int idx = row_begin + (int)(blockIdx.x * 256u + threadIdx.x);
@@ -776,12 +677,18 @@ __global__ __launch_bounds__(256) void depth_mean3d_kernel(int row_begin, int ro
     dL_dmean3D[3 * idx] += dz * V[2];
     dL_dmean3D[3 * idx + 1] += dz * V[6];
     dL_dmean3D[3 * idx + 2] += dz * V[10];
+    if constexpr (ADAM) {
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            adam_scalar(A.p[0][3 * idx + k], dL_dmean3D[3 * idx + k], A.m[0][3 * idx + k], A.v[0][3 * idx + k], A.lr[0], A.b1, A.b2, A.eps);
+    }
 }
 
 int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s)
 {
-    if (a.partials_z && (a.cam_partials || a.adam.on || a.dL_drgb || !a.dL_dmean3D))
-        return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no camera gradient, fused Adam or dL_drgb output, and dL_dmean3D is required");
+    if (a.partials_z && (a.cam_partials || a.dL_drgb || !a.dL_dmean3D))
+        return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no camera gradient or dL_drgb output, and dL_dmean3D is required");
+    const bool defer = a.partials_z && a.adam.on;   // depth + fused Adam: xyz is updated by depth_mean3d_kernel<true> once dL/dz is in
     const bool cam = a.cam_partials != nullptr;
     const int nrows = a.row_end - a.row_begin;
     if (nrows <= 0) return GSLIC_OK;
@@ -790,14 +697,19 @@ int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s)
         // one wave per workgroup: 64 Gaussians' SH rows (11.25 KiB) + small-group gradients in LDS, the phase barriers are wave-level,
         // and ten workgroups per CU sit in different phases (measured 0.72 ms against 0.75 at 128 and 0.88 at 256 threads)
         if (cam) GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_kernel<true, 64, true>), dim3(div_up(nrows, 64)), dim3(64), 0, s, a);
+        else if (defer) GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_defer_xyz_kernel<true, 64>), dim3(div_up(nrows, 64)), dim3(64), 0, s, a);
         else GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_kernel<true, 64, false>), dim3(div_up(nrows, 64)), dim3(64), 0, s, a);
     } else {
         if (cam) GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_kernel<false, 256, true>), dim3(div_up(nrows, 256)), dim3(256), 0, s, a);
+        else if (defer) GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_defer_xyz_kernel<false, 256>), dim3(div_up(nrows, 256)), dim3(256), 0, s, a);
         else GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_kernel<false, 256, false>), dim3(div_up(nrows, 256)), dim3(256), 0, s, a);
     }
-    if (a.partials_z)
-        GS_LAUNCH(K_PREPROCESS_BWD, depth_mean3d_kernel, dim3(div_up(nrows, 256)), dim3(256), 0, s, a.row_begin, a.row_end, a.radii, a.gauss_start,
-                  a.tiles_touched, a.dead, a.partials_z, a.view, a.status, a.dL_dmean3D);
+    if (defer)
+        GS_LAUNCH(K_PREPROCESS_BWD, depth_mean3d_kernel<true>, dim3(div_up(nrows, 256)), dim3(256), 0, s, a.row_begin, a.row_end, a.radii, a.gauss_start,
+                  a.tiles_touched, a.dead, a.partials_z, a.view, a.status, a.dL_dmean3D, a.adam);
+    else if (a.partials_z)
+        GS_LAUNCH(K_PREPROCESS_BWD, depth_mean3d_kernel<false>, dim3(div_up(nrows, 256)), dim3(256), 0, s, a.row_begin, a.row_end, a.radii, a.gauss_start,
+                  a.tiles_touched, a.dead, a.partials_z, a.view, a.status, a.dL_dmean3D, a.adam);
     if (cam) {
         const size_t rows = (a.M == 15 && a.shs && (a.dL_dsh || a.adam.on || a.dL_drgb)) ? (size_t)div_up(a.P, 64) : (size_t)div_up(a.P, 256) * 4;
         GS_LAUNCH(K_PREPROCESS_BWD, cam_reduce_kernel, dim3(27), dim3(256), 0, s, rows, (const float*)a.cam_partials, a.cam_out);

@@ -155,18 +155,51 @@ def l1_ssim_loss(image, gt, lambda_dssim=0.2):
 
 class FusedLoss:
     """loss = (1-lambda) * L1 + lambda * (1 - SSIM) of optimize() (gaussian.cpp:685-691) computed by two kernels
-    (gslic_l1_ssim_loss_forward / _backward) with no LibTorch elementwise ops and no autograd graph."""
+    (gslic_l1_ssim_loss_forward / _backward) with no LibTorch elementwise ops and no autograd graph; with LiDAR depth supervision
+    (depth_forward_backward) + lambda_depth * L_d by two more.  The terms of a step live in one device tensor [mean L1, mean SSIM, L_d]:
+    forward_backward returns its first two elements, depth_forward_backward the third, `terms3` all of them."""
 
     def __init__(self, lambda_dssim=0.2):
         self.lambda_dssim = float(lambda_dssim)
         self._shape, self._buf = None, None
+        self._dshape, self._dbuf = None, None
+        self._terms = None
+
+    def _terms_buf(self, device):
+        if self._terms is None or self._terms.device != device:
+            self._terms = torch.zeros(3, device=device)
+        return self._terms
+
+    @property
+    def terms3(self):
+        """The device tensor [mean L1, mean SSIM, L_d] the last calls wrote (L_d: of the last depth_forward_backward)."""
+        return self._terms
 
     def _scratch(self, img):
         if self._shape != tuple(img.shape) or self._buf[0].device != img.device:
             n = int(_lib.lib().gslic_loss_partials_count(1, img.shape[0], img.shape[1], img.shape[2]))
-            self._buf = [torch.empty_like(img) for _ in range(4)] + [torch.empty(n, device=img.device), torch.empty(2, device=img.device)]
+            self._buf = [torch.empty_like(img) for _ in range(4)] + [torch.empty(n, device=img.device), self._terms_buf(img.device)[:2]]
             self._shape = tuple(img.shape)
         return self._buf
+
+    def _depth_scratch(self, depth):
+        if self._dshape != tuple(depth.shape) or self._dbuf[0].device != depth.device:
+            n = int(_lib.lib().gslic_depth_l1_loss_partials_count(depth.shape[0], depth.shape[1]))
+            self._dbuf = [torch.empty_like(depth), torch.empty(n, device=depth.device), self._terms_buf(depth.device)[2:3]]
+            self._dshape = tuple(depth.shape)
+        return self._dbuf
+
+    def depth_forward_backward(self, depth, gt_depth, lambda_depth):
+        """depth, gt_depth: [H,W] (gt_depth 0 = no measurement).  Returns (dL/ddepth of lambda_depth * L_d, term) with term = device [1] view of
+        L_d = depth_l1(depth, gt_depth) — gslic_depth_l1_loss_forward_backward, two launches; dL/ddepth equals autograd's bit for bit."""
+        depth, gt_depth = depth.contiguous(), gt_depth.contiguous()
+        H, W = depth.shape
+        assert tuple(gt_depth.shape) == (H, W), "gt_depth must have the depth image's shape [H,W]"
+        dL, partials, term = self._depth_scratch(depth)
+        p = _lib.ptr
+        _lib.check(_lib.lib().gslic_depth_l1_loss_forward_backward(H, W, float(lambda_depth), p(depth), p(gt_depth), p(partials), p(term), p(dL),
+                                                                   _lib.current_stream_ptr()))
+        return dL, term
 
     def forward_backward(self, image, gt):
         """image, gt: [3,H,W].  Returns (dL/dimage, terms) with terms = device tensor [mean|img-gt|, mean ssim]."""
@@ -179,5 +212,9 @@ class FusedLoss:
                                                          p(terms), p(dL), _lib.current_stream_ptr()))
         return dL, terms
 
-    def value(self, terms):
-        return (1.0 - self.lambda_dssim) * terms[0] + self.lambda_dssim * (1.0 - terms[1])
+    def value(self, terms, lambda_depth=0.0):
+        """The loss from the terms: [mean L1, mean SSIM] or, with lambda_depth != 0, [mean L1, mean SSIM, L_d]."""
+        v = (1.0 - self.lambda_dssim) * terms[0] + self.lambda_dssim * (1.0 - terms[1])
+        if lambda_depth:
+            v = v + float(lambda_depth) * terms[2]
+        return v

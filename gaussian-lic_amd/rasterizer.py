@@ -124,19 +124,28 @@ def rasterize_gaussians_depth(background, means3D, opacity, scales, rotations, s
 
 class CapacityBuffers:
     """Caller-owned scratch + outputs of gslic_rasterize_forward_capacity for one (P, W, H): nothing is allocated per step, every
-    address is stable, so the step can be captured in a hipGraph.  cap_R / cap_B: how many instances / checkpoint buckets fit."""
+    address is stable, so the step can be captured in a hipGraph.  cap_R / cap_B: how many instances / checkpoint buckets fit.
+    depth=True: the buffers of gslic_rasterize_forward_depth_capacity (the depth carves, gslic_*_bytes_depth) and a `depth` [H,W] output."""
 
-    def __init__(self, P, W, H, cap_R, cap_B, device, no_color=False):
+    def __init__(self, P, W, H, cap_R, cap_B, device, no_color=False, depth=False):
         L = _lib.lib()
-        self.P, self.W, self.H, self.no_color = int(P), int(W), int(H), bool(no_color)
+        self.P, self.W, self.H, self.no_color, self.with_depth = int(P), int(W), int(H), bool(no_color), bool(depth)
+        if depth and no_color:
+            raise ValueError("CapacityBuffers(depth=True) needs the colour (no_color=False)")
         mk = lambda n: torch.empty(int(n), dtype=torch.uint8, device=device)
         self.geom = mk(L.gslic_geom_bytes(self.P))
-        self.img = mk(L.gslic_img_bytes(self.W, self.H))
-        self.binning = mk(L.gslic_binning_bytes(int(cap_R), int(no_color)))
-        self.sample = mk(L.gslic_sample_bytes(int(cap_B)) if not no_color else 0)
+        if depth:
+            self.img = mk(L.gslic_img_bytes_depth(self.W, self.H))
+            self.binning = mk(L.gslic_binning_bytes_depth(int(cap_R)))
+            self.sample = mk(L.gslic_sample_bytes_depth(int(cap_B)))
+        else:
+            self.img = mk(L.gslic_img_bytes(self.W, self.H))
+            self.binning = mk(L.gslic_binning_bytes(int(cap_R), int(no_color)))
+            self.sample = mk(L.gslic_sample_bytes(int(cap_B)) if not no_color else 0)
         self.status = torch.zeros(8, dtype=torch.int32, device=device)
         self.color = torch.zeros(3, self.H, self.W, dtype=torch.float32, device=device)
         self.final_T = torch.empty(self.H, self.W, dtype=torch.float32, device=device)
+        self.depth = torch.zeros(self.H, self.W, dtype=torch.float32, device=device) if depth else None
         self.radii = torch.empty(self.P, dtype=torch.int32, device=device)
         self.cap_R = self.cap_B = 0   # filled by the first forward (what the library derives from the buffer sizes)
 
@@ -175,6 +184,32 @@ def rasterize_gaussians_capacity(bufs, background, means3D, opacity, scales, rot
         ctypes.byref(cB), p(bufs.status), _lib.current_stream_ptr()))
     bufs.cap_R, bufs.cap_B = cR.value, cB.value
     return (cR.value, cB.value, bufs.color, bufs.final_T, bufs.radii, bufs.geom, bufs.binning, bufs.img, bufs.sample)
+
+
+def rasterize_gaussians_depth_capacity(bufs, background, means3D, opacity, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx,
+                                       tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, dc, sh, degree, campos, raw_params=False, tie_rank=None):
+    """gslic_rasterize_forward_depth_capacity: rasterize_gaussians_capacity plus the depth image, into CapacityBuffers(depth=True).  Returns
+    (cap_R, cap_B, out_color, out_final_T, out_depth, radii, geom, binning, img, sample); bit-identical to rasterize_gaussians_depth."""
+    L = _lib.lib()
+    P = means3D.size(0)
+    assert P == bufs.P and P > 0
+    if not bufs.with_depth:
+        raise ValueError("rasterize_gaussians_depth_capacity needs CapacityBuffers(..., depth=True)")
+    M = sh.size(1) if sh is not None and sh.size(0) != 0 else 0
+    for t in (means3D, dc, opacity, scales, rotations, viewmatrix, projmatrix, campos):
+        assert t.is_contiguous() and t.dtype == torch.float32
+    prm = _params(P, degree, M, bufs.H, bufs.W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier, False, False,
+                  False, raw_params, tie_rank)
+    p = _lib.ptr
+    cR, cB = ctypes.c_int32(0), ctypes.c_int32(0)
+    bp = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+    _lib.check(L.gslic_rasterize_forward_depth_capacity(
+        ctypes.byref(prm), bp(bufs.geom), bufs.geom.numel(), bp(bufs.binning), bufs.binning.numel(), bp(bufs.img), bufs.img.numel(),
+        bp(bufs.sample), bufs.sample.numel(), p(background), p(means3D), p(dc), p(sh if M > 0 else None), None, p(opacity), p(scales),
+        p(rotations), None, p(viewmatrix), p(projmatrix), p(campos), p(bufs.color), p(bufs.final_T), p(bufs.depth), p(bufs.radii),
+        ctypes.byref(cR), ctypes.byref(cB), p(bufs.status), _lib.current_stream_ptr()))
+    bufs.cap_R, bufs.cap_B = cR.value, cB.value
+    return (cR.value, cB.value, bufs.color, bufs.final_T, bufs.depth, bufs.radii, bufs.geom, bufs.binning, bufs.img, bufs.sample)
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
@@ -274,19 +309,49 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
 
 def rasterize_gaussians_backward_depth(background, means3D, radii, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx,
                                        tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, dL_dout_color, dL_dout_depth, dc, sh, degree, campos,
-                                       geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank=0.0, debug=False, raw_params=False):
+                                       geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank=0.0, debug=False, raw_params=False,
+                                       out=None, adam=None, xyz_grad=None):
     """gslic_rasterize_backward_depth: rasterize_gaussians_backward with dL/d(out_depth) [H,W] as a second input, on the buffers of
-    rasterize_gaussians_depth.  Returns the same nine tensors (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc,
-    dL_dsh, dL_dscales, dL_drotations); dL_dout_depth = 0 gives rasterize_gaussians_backward's results bit for bit."""
+    rasterize_gaussians_depth (or rasterize_gaussians_depth_capacity: pass its cap_R / cap_B as R / B).  Returns the same nine tensors
+    (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscales, dL_drotations); dL_dout_depth = 0 gives
+    rasterize_gaussians_backward's results bit for bit.
+    out: caller-provided storage for the six parameter gradients (dict xyz / features_dc / features_rest / opacity / scaling / rotation, as
+    rasterize_gaussians_backward's `out`); the four the host discards are then not materialised.
+    adam (a gslic_adam_fused descriptor, raw_params implied): gslic_rasterize_backward_depth_adam — the Adam update inside the backward,
+    bit-identical to this backward followed by the masked Adam step; returns None.  xyz_grad [P,3]: where the xyz gradient is assembled before
+    its update (allocated when None; a graph-captured step passes a buffer of its own)."""
     L = _lib.lib()
     dev = means3D.device
     P, H, W = means3D.size(0), dL_dout_color.size(1), dL_dout_color.size(2)
     M = sh.size(1) if sh is not None and sh.size(0) != 0 else 0
+    if adam is not None:
+        if P == 0:
+            return None
+        means3D, dc, scales, rotations, dL, dLd = map(_f32c, (means3D, dc, scales, rotations, dL_dout_color, dL_dout_depth))
+        sh_c = _f32c(sh) if M > 0 else None
+        viewmatrix, projmatrix, campos, background = map(_f32c, (viewmatrix, projmatrix, campos, background))
+        if xyz_grad is None:
+            xyz_grad = torch.empty(P, 3, dtype=torch.float32, device=dev)
+        assert xyz_grad.is_contiguous() and xyz_grad.numel() >= 3 * P
+        prm = _params(P, degree, M, H, W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier, False, debug, False, True)
+        p = _lib.ptr
+        _lib.check(L.gslic_rasterize_backward_depth_adam(
+            ctypes.byref(prm), int(R), int(B), p(background), p(means3D), p(dc), p(sh_c), None, p(scales), p(rotations), None,
+            p(viewmatrix), p(projmatrix), p(campos), p(radii.contiguous()),
+            ctypes.c_void_p(geomBuffer.data_ptr()), ctypes.c_void_p(binningBuffer.data_ptr()), ctypes.c_void_p(imageBuffer.data_ptr()),
+            ctypes.c_void_p(sampleBuffer.data_ptr()), p(dL), p(dLd), None, p(xyz_grad), None, None, None, None, float(lambda_erank),
+            ctypes.byref(adam), _lib.current_stream_ptr()))
+        return None
     mk = (lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)) if P != 0 else \
         (lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev))
-    dL_dmeans3D, dL_dmeans2D, dL_dcolors = mk(P, 3), mk(P, 3), mk(P, 3)
-    dL_dconic, dL_dopacities, dL_dcov3D = mk(P, 2, 2), mk(P, 1), mk(P, 6)
-    dL_ddc, dL_dsh, dL_dscales, dL_drotations = mk(P, 1, 3), mk(P, M, 3), mk(P, 3), mk(P, 4)
+    if out is not None:
+        dL_dmeans3D, dL_ddc, dL_dsh = out["xyz"], out["features_dc"], out["features_rest"]
+        dL_dopacities, dL_dscales, dL_drotations = out["opacity"], out["scaling"], out["rotation"]
+        dL_dmeans2D = dL_dcolors = dL_dconic = dL_dcov3D = None
+    else:
+        dL_dmeans3D, dL_dmeans2D, dL_dcolors = mk(P, 3), mk(P, 3), mk(P, 3)
+        dL_dconic, dL_dopacities, dL_dcov3D = mk(P, 2, 2), mk(P, 1), mk(P, 6)
+        dL_ddc, dL_dsh, dL_dscales, dL_drotations = mk(P, 1, 3), mk(P, M, 3), mk(P, 3), mk(P, 4)
     if P != 0:
         means3D, dc, scales, rotations, dL, dLd = map(_f32c, (means3D, dc, scales, rotations, dL_dout_color, dL_dout_depth))
         sh_c = _f32c(sh) if M > 0 else None

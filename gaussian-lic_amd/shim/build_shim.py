@@ -99,15 +99,25 @@ def _build_check(CHECK, first_includes, force, extra_src=()):
 
 
 CHECK_FUSED = os.path.join(PKG, "fused_check")
+CHECK_FUSED_DEPTH = os.path.join(PKG, "fused_depth_check")
 
 
 def build_fused_check(force=False):
     """fused_check: the fused training step from C++ (shim/include/gslic_fused.h + fused_check.cpp) — LibTorch and libgslic_hip.so only,
     no reference source, so it builds anywhere this repository does."""
+    return _build_fused_program(os.path.join(HERE, "fused_check.cpp"), CHECK_FUSED, force)
+
+
+def build_fused_depth_check(force=False):
+    """fused_depth_check: the fused training step with LiDAR depth supervision from C++ (gslic::FusedStep::step with gt_depth) — built like
+    fused_check."""
+    return _build_fused_program(os.path.join(HERE, "fused_depth_check.cpp"), CHECK_FUSED_DEPTH, force)
+
+
+def _build_fused_program(src, CHECK_FUSED, force):
     import sysconfig
     import torch
     from torch.utils import cpp_extension
-    src = os.path.join(HERE, "fused_check.cpp")
     newest = max(os.path.getmtime(src), os.path.getmtime(os.path.join(HERE, "include", "gslic_fused.h")),
                  os.path.getmtime(os.path.join(PKG, "..", "include", "gslic_hip.h")), os.path.getmtime(os.path.join(PKG, "libgslic_hip.so")))
     if not force and os.path.exists(CHECK_FUSED) and os.path.getmtime(CHECK_FUSED) > newest:
@@ -123,7 +133,7 @@ def build_fused_check(force=False):
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stdout[-3000:] + r.stderr[-6000:])
-        raise RuntimeError("fused_check build failed")
+        raise RuntimeError(f"{os.path.basename(CHECK_FUSED)} build failed")
     return CHECK_FUSED
 
 
@@ -135,3 +145,4 @@ if __name__ == "__main__":
     for g in ("render_ref", "render", "render_loss", "render_refhost"):
         print(build_dropin_check(force="--force" in sys.argv, groups=g))
     print(build_fused_check(force="--force" in sys.argv))
+    print(build_fused_depth_check(force="--force" in sys.argv))

@@ -14,6 +14,12 @@
 //                       {1.6e-4f, 2.5e-3f, 2.5e-3f / 20, 5e-2f, 5e-3f, 1e-3f}, sh_degree_);
 //   for (view : keyframes) { auto terms = fs.step(cam, gt_image); }        // terms = device [mean |img - gt|, mean ssim]
 //   float loss = fs.loss_value(terms);                                     // only when the host wants the number (one sync)
+//
+// LiDAR depth supervision (gt_depth [H,W], 0 = no measurement; loss += lambda_depth * masked mean |depth - gt_depth|):
+//   auto terms = fs.step(cam, gt_image, gt_depth, lambda_depth);           // device [mean |img - gt|, mean ssim, L_d]
+//   float loss = fs.loss_value(terms, lambda_depth);
+// issues gslic_rasterize_forward_depth, the two loss calls, gslic_depth_l1_loss_forward_backward and gslic_rasterize_backward_depth_adam — the
+// calls of the Python host's training_step_fused(gt_depth=, lambda_depth=), so the two agree bit for bit (tests/test_depth_fused_gpu.py).
 #pragma once
 #include <torch/torch.h>
 
@@ -186,6 +192,63 @@ public:
         return terms;
     }
 
+    // One optimisation step on one view with LiDAR depth supervision.  Returns the device tensor [mean |image - gt|, mean ssim, L_d]; nothing
+    // synchronises.  An undefined gt_depth or lambda_depth == 0 is the colour-only step above (two terms).
+    torch::Tensor step(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor& gt_depth, float lambda_depth)
+    {
+        if (!gt_depth.defined() || lambda_depth == 0.0f) return step(cam, gt_image);
+        torch::NoGradGuard ng;
+        const int64_t P = prm_[0].size(0);
+        const int W = cam.image_width, H = cam.image_height;
+        TORCH_CHECK(gt_image.is_contiguous() && gt_image.dim() == 3 && gt_image.size(1) == H && gt_image.size(2) == W, "gt_image must be contiguous [3,H,W]");
+        TORCH_CHECK(gt_depth.is_contiguous() && gt_depth.scalar_type() == torch::kFloat32 && gt_depth.dim() == 2 && gt_depth.size(0) == H &&
+                    gt_depth.size(1) == W, "gt_depth must be contiguous fp32 [H,W]");
+        gslic_raster_params rp{};
+        rp.tie_rank = tie_.defined() ? reinterpret_cast<const uint32_t*>(tie_.data_ptr<int32_t>()) : nullptr;
+        rp.P = (int32_t)P; rp.D = deg_; rp.M = prm_[2].numel() ? (int32_t)prm_[2].size(1) : 0; rp.width = W; rp.height = H;
+        rp.tan_fovx = cam.tanfovx; rp.tan_fovy = cam.tanfovy;
+        rp.limx_neg = cam.limx_neg; rp.limx_pos = cam.limx_pos; rp.limy_neg = cam.limy_neg; rp.limy_pos = cam.limy_pos;
+        rp.scale_modifier = 1.0f; rp.raw_params = 1;
+        auto fo = prm_[0].options().requires_grad(false);
+        if (!image_.defined() || image_.size(1) != H || image_.size(2) != W) {
+            image_ = torch::empty({3, H, W}, fo);
+            final_T_ = torch::empty({H, W}, fo);
+            for (auto& d : dm_) d = torch::empty({3, H, W}, fo);
+            dL_dimage_ = torch::empty({3, H, W}, fo);
+            partials_ = torch::empty({gslic_loss_partials_count(1, 3, H, W)}, fo);
+        }
+        if (!depth_.defined() || depth_.size(0) != H || depth_.size(1) != W) {
+            depth_ = torch::empty({H, W}, fo);
+            dL_ddepth_ = torch::empty({H, W}, fo);
+            depth_partials_ = torch::empty({gslic_depth_l1_loss_partials_count(H, W)}, fo);
+        }
+        if (!radii_.defined() || radii_.size(0) != P) radii_ = torch::empty({P}, fo.dtype(torch::kInt32));
+        if (!xyz_grad_.defined() || xyz_grad_.size(0) != P) xyz_grad_ = torch::empty({P, 3}, fo);   // (xyz's gradient is assembled there before its update)
+        torch::Tensor terms = torch::empty({3}, fo);
+        const float *xyz = f(prm_[0]), *dc = f(prm_[1]), *rest = f(prm_[2]), *op = f(prm_[3]), *sc = f(prm_[4]), *rot = f(prm_[5]);
+        const float *view = f(cam.world_view_transform), *proj = f(cam.full_proj_transform), *cpos = f(cam.camera_center);
+        int32_t R = 0, B = 0;
+        check(gslic_rasterize_forward_depth(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), xyz,
+                                            dc, rest, nullptr, op, sc, rot, nullptr, view, proj, cpos, image_.data_ptr<float>(),
+                                            final_T_.data_ptr<float>(), depth_.data_ptr<float>(), radii_.data_ptr<int32_t>(), &R, &B, current_stream()),
+              "gslic_rasterize_forward_depth");
+        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;   // loss_utils.h:187-188
+        check(gslic_l1_ssim_loss_forward_backward(1, 3, H, W, C1, C2, lambda_dssim_, f(image_), f(gt_image), dm_[0].data_ptr<float>(),
+                                                  dm_[1].data_ptr<float>(), dm_[2].data_ptr<float>(), partials_.data_ptr<float>(),
+                                                  terms.data_ptr<float>(), dL_dimage_.data_ptr<float>(), current_stream()),
+              "gslic_l1_ssim_loss_forward_backward");
+        check(gslic_depth_l1_loss_forward_backward(H, W, lambda_depth, f(depth_), f(gt_depth), depth_partials_.data_ptr<float>(), terms.data_ptr<float>() + 2,
+                                                   dL_ddepth_.data_ptr<float>(), current_stream()),
+              "gslic_depth_l1_loss_forward_backward");
+        gslic_adam_fused ad = adam_descriptor();
+        check(gslic_rasterize_backward_depth_adam(&rp, R, B, f(bg_), xyz, dc, rest, nullptr, sc, rot, nullptr, view, proj, cpos, radii_.data_ptr<int32_t>(),
+                                                  cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), cptr(scratch_[3]), f(dL_dimage_), f(dL_ddepth_),
+                                                  nullptr, xyz_grad_.data_ptr<float>(), nullptr, nullptr, nullptr, nullptr, lambda_erank_, &ad,
+                                                  current_stream()),
+              "gslic_rasterize_backward_depth_adam");
+        return terms;
+    }
+
     // Gradient of the training loss w.r.t. a LEFT se(3) increment of the camera pose, T_cw <- exp(xi^) T_cw, xi = (rho, phi) — the "cam" of the
     // north-star; the reference's autograd node returns nothing for its camera inputs (rasterizer.cpp:171-182).  Forward + loss kernels +
     // gslic_rasterize_backward_camera (the map is NOT updated), then the chain of gaussian-lic_amd/camera.py:Camera.pose_gradient:
@@ -255,6 +318,13 @@ public:
         torch::Tensor t = terms.to(torch::kCPU);
         return (1.0f - lambda_dssim_) * t[0].item<float>() + lambda_dssim_ * (1.0f - t[1].item<float>());
     }
+    float loss_value(const torch::Tensor& terms, float lambda_depth) const   // + lambda_depth L_d for the three terms of a depth step; synchronises
+    {
+        if (lambda_depth == 0.0f) return loss_value(terms);
+        torch::Tensor t = terms.to(torch::kCPU);
+        return (1.0f - lambda_dssim_) * t[0].item<float>() + lambda_dssim_ * (1.0f - t[1].item<float>()) + lambda_depth * t[2].item<float>();
+    }
+    const torch::Tensor& depth() const { return depth_; }                 // last depth render [H,W] (depth steps)
     const torch::Tensor& image() const { return image_; }                 // last render [3,H,W]
     torch::Tensor visible() const { return radii_ > 0; }                  // render_pkg's visibility filter (renderer.cpp:86)
     const torch::Tensor& exp_avg(int group) const { return m_[group]; }
@@ -282,6 +352,19 @@ private:
     {
         for (int g = 0; g < 6; g++) { prm_[g] = buf_[g].narrow(0, 0, P); m_[g] = mbuf_[g].narrow(0, 0, P); v_[g] = vbuf_[g].narrow(0, 0, P); }
     }
+    gslic_adam_fused adam_descriptor()
+    {
+        gslic_adam_fused ad{};
+        for (int i = 0; i < 6; i++) {
+            const bool on = prm_[i].numel() != 0;   // features_rest is [P,0,3] at SH degree 0: an empty group is a no-op, as in the reference
+            ad.param[i] = on ? prm_[i].data_ptr<float>() : nullptr;
+            ad.exp_avg[i] = on ? m_[i].data_ptr<float>() : nullptr;
+            ad.exp_avg_sq[i] = on ? v_[i].data_ptr<float>() : nullptr;
+            ad.lr[i] = lrs_[i];
+        }
+        ad.b1 = b1_; ad.b2 = b2_; ad.eps = eps_;
+        return ad;
+    }
     static const float* f(const torch::Tensor& t) { return t.numel() ? t.data_ptr<float>() : nullptr; }
     static char* cptr(torch::Tensor& t) { return t.numel() ? reinterpret_cast<char*>(t.data_ptr()) : nullptr; }
     static void check(int rc, const char* what) { TORCH_CHECK(rc == GSLIC_OK, what, " failed (", rc, "): ", gslic_last_error()); }
@@ -301,6 +384,7 @@ private:
     float lambda_dssim_, lambda_erank_, b1_, b2_, eps_;
     torch::Tensor scratch_[4];   // geom, binning, img, sample — order of the C-ABI's allocator arguments
     torch::Tensor bg_, image_, final_T_, radii_, dm_[3], dL_dimage_, partials_, tie_;
+    torch::Tensor depth_, dL_ddepth_, depth_partials_, xyz_grad_;   // depth steps
 };
 
 }  // namespace gslic

@@ -632,13 +632,23 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
     return terms, visible, g
 
 
-def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=True, adam_in_backward=True):
+def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=True, adam_in_backward=True, gt_depth=None, lambda_depth=0.0):
     """The same iteration as training_step — identical arithmetic up to fp32 rounding — on the fused entry points
     (SURVEY.md §8f row 2): sigmoid / exp / normalize and their backward run inside preprocess / preprocess_bwd (raw_params),
     the loss and dL/dimage come from two loss kernels, and there is no autograd graph: 0 LibTorch elementwise launches per step
-    (the drop-in path issues ~35).  Returns (terms [mean L1, mean SSIM] device tensor, visible mask)."""
+    (the drop-in path issues ~35).  Returns (terms [mean L1, mean SSIM] device tensor, visible mask).
+    gt_depth [H,W] with lambda_depth != 0 (LiDAR depth supervision, as training_step's): the depth forward, the two colour-loss and the two
+    depth-loss kernels (gslic_depth_l1_loss_forward_backward), then the depth backward with the Adam update inside
+    (gslic_rasterize_backward_depth_adam) or, adam_in_backward=False, the depth backward and SparseGaussianAdam.step; terms is then
+    [mean L1, mean SSIM, L_d] and the loss FusedLoss.value(terms, lambda_depth).  gt_depth=None or lambda_depth=0 is exactly the colour-only
+    step.  Single GPU only: the N > 1 exchange carries no depth gradient (NotImplementedError)."""
     from . import rasterizer as rz
     fl = fused_loss or _default_fused_loss()
+    if gt_depth is not None and lambda_depth != 0.0:
+        if _dist_on():
+            raise NotImplementedError("training_step_fused with depth supervision is single-GPU only: the N > 1 gradient exchange (rank1 / slab "
+                                      "all-reduce) carries no depth gradient; use training_step(gt_depth=...) or run on one GPU")
+        return _training_step_fused_depth(model, camera, gt_image, bg, fl, do_step, adam_in_backward, gt_depth, float(lambda_depth))
     dev = model.device
     e = torch.empty(0, device=dev)
     if DIST_TIMING is not None and do_step and _dist_on():
@@ -717,6 +727,44 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
     return terms, visible
 
 
+def _training_step_fused_depth(model, cam, gt_image, bg, fl, do_step, adam_in_backward, gt_depth, lambda_depth):
+    """training_step_fused with LiDAR depth supervision (single GPU; see there)."""
+    from . import rasterizer as rz
+    dev = model.device
+    with torch.no_grad():
+        xyz, dc, rest = model.xyz.detach(), model.features_dc.detach(), model.features_rest.detach()
+        op, sc, rot = model.opacity.detach(), model.scaling.detach(), model.rotation.detach()
+        (R, B, image, _final_T, depth, radii, geom, binning, img, sample) = rz.rasterize_gaussians_depth(
+            bg, xyz, op, sc, rot, 1.0, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
+            cam.image_height, cam.image_width, float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dc, rest,
+            model.sh_degree, cam.d_camera_center, raw_params=True, tie_rank=getattr(model, "tie_rank", None))
+        dL_dimage, _ = fl.forward_backward(image, gt_image)
+        dL_ddepth, _ = fl.depth_forward_backward(depth, gt_depth, lambda_depth)
+        terms = fl.terms3
+        bwd = (bg, xyz, radii, sc, rot, 1.0, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
+               float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dL_dimage, dL_ddepth, dc, rest, model.sh_degree,
+               cam.d_camera_center, geom, R, binning, img, B, sample, model.lambda_erank, False)
+        if do_step and adam_in_backward:
+            # the Adam update inside the backward (every group but xyz in the per-Gaussian kernel, xyz once dL/dz is in): bit-identical to the
+            # depth backward + SparseGaussianAdam.step below
+            xg = getattr(model, "_depth_xyz_grad", None)
+            if xg is None or xg.shape[0] != model.P or xg.device != xyz.device:
+                xg = model._depth_xyz_grad = torch.empty(model.P, 3, dtype=torch.float32, device=dev)
+            vis_u8 = torch.empty(model.P, dtype=torch.uint8, device=dev)
+            rz.rasterize_gaussians_backward_depth(*bwd, raw_params=True, adam=model.optimizer.fused_descriptor(visible_out=vis_u8), xyz_grad=xg)
+            model.optimizer.count_step()
+            return terms, vis_u8.view(torch.bool)
+        slab = getattr(model, "_grad_slab", None)
+        if slab is None or slab.P != model.P:
+            slab = model._grad_slab = GradSlab(model)
+        rz.rasterize_gaussians_backward_depth(*bwd, raw_params=True, out=slab.views)
+        visible = radii > 0
+        if do_step:
+            model.optimizer.set_visibility_and_N(visible, model.P)
+            model.optimizer.step(slab.grads(model))
+    return terms, visible
+
+
 _FUSED_LOSS = None
 
 
@@ -748,9 +796,15 @@ class GraphedStep:
     end — grows the buffers from the largest counts seen, re-captures and repeats exactly the steps that did not fit, each with ITS
     pose (snapshotted by value) and ground truth (kept by reference with its version counter: a target that was modified in place, or
     replaced while steps were issued with gt_image=None, makes the repeat fail loudly instead of training on the wrong data), after the
-    ones that did.  extend() changes P: build a new GraphedStep afterwards."""
+    ones that did.  extend() changes P: build a new GraphedStep afterwards.
 
-    def __init__(self, model, camera, gt_image, bg, headroom=1.25, check_every=16, cap_R=None, cap_B=None, use_graph=False):
+    gt_depth [H,W] with lambda_depth != 0 (LiDAR depth supervision): the step is training_step_fused's depth step in capacity mode
+    (gslic_rasterize_forward_depth_capacity -> colour and depth loss kernels -> gslic_rasterize_backward_depth_adam).  lambda_depth is baked
+    into the step; the depth target lives in a static buffer like the image and is passed to step() the same way (and repeated steps use their
+    own, checked by reference and version counter like gt_image).  terms is then [mean L1, mean SSIM, L_d]."""
+
+    def __init__(self, model, camera, gt_image, bg, headroom=1.25, check_every=16, cap_R=None, cap_B=None, use_graph=False, gt_depth=None,
+                 lambda_depth=0.0):
         """use_graph=False (default since round 5): the capacity-mode step (caller-owned scratch, no host round trip, overflow checks and repeats as
         below) issued as eager launches; use_graph=True: captured in a hipGraph and replayed with one launch per step.  The two are equally fast at
         2M Gaussians (bench.py: `capacity_eager` / `graphed`; the host runs ahead of the device either way), and the eager form has no hazard:
@@ -768,6 +822,9 @@ class GraphedStep:
         self.proj = camera.d_full_proj_transform.clone()
         self.campos = camera.d_camera_center.clone()
         self.gt = gt_image.clone()
+        self.use_depth = gt_depth is not None and lambda_depth != 0.0
+        self.lambda_depth = float(lambda_depth) if self.use_depth else 0.0
+        self.gt_depth = gt_depth.detach().float().contiguous().clone() if self.use_depth else None
         self.fl = loss_utils.FusedLoss(LAMBDA_DSSIM)
         self.e = torch.empty(0, device=dev)
         # sizes from one eager forward of the current state
@@ -795,6 +852,17 @@ class GraphedStep:
         xyz, dc, rest = m.xyz.detach(), m.features_dc.detach(), m.features_rest.detach()
         op, sc, rot = m.opacity.detach(), m.scaling.detach(), m.rotation.detach()
         scal = (float(c.tanfovx), float(c.tanfovy), float(c.limx_neg), float(c.limx_pos), float(c.limy_neg), float(c.limy_pos))
+        if self.use_depth:
+            (R, B, image, _T, depth, radii, geom, binning, img, sample) = rz.rasterize_gaussians_depth_capacity(
+                self.bufs, self.bg, xyz, op, sc, rot, 1.0, self.view, self.proj, *scal, dc, rest, m.sh_degree, self.campos, raw_params=True,
+                tie_rank=getattr(m, "tie_rank", None))
+            dL_dimage, _ = self.fl.forward_backward(image, self.gt)
+            dL_ddepth, _ = self.fl.depth_forward_backward(depth, self.gt_depth, self.lambda_depth)
+            self.terms = self.fl.terms3
+            rz.rasterize_gaussians_backward_depth(self.bg, xyz, radii, sc, rot, 1.0, self.view, self.proj, *scal, dL_dimage, dL_ddepth, dc, rest,
+                                                  m.sh_degree, self.campos, geom, R, binning, img, B, sample, m.lambda_erank, False, raw_params=True,
+                                                  adam=self._adam, xyz_grad=self._xyz_grad)
+            return
         (R, B, image, _T, radii, geom, binning, img, sample) = rz.rasterize_gaussians_capacity(
             self.bufs, self.bg, xyz, op, sc, rot, 1.0, self.view, self.proj, *scal, dc, rest, m.sh_degree, self.campos, raw_params=True,
             tie_rank=getattr(m, "tie_rank", None))
@@ -806,8 +874,9 @@ class GraphedStep:
     def _capture(self):
         from . import rasterizer as rz
         dev = self.model.device
-        self.bufs = rz.CapacityBuffers(self.model.P, self.W, self.H, self.cap_R, self.cap_B, dev)
+        self.bufs = rz.CapacityBuffers(self.model.P, self.W, self.H, self.cap_R, self.cap_B, dev, depth=self.use_depth)
         self._adam = self.model.optimizer.fused_descriptor()
+        self._xyz_grad = torch.empty(self.model.P, 3, dtype=torch.float32, device=dev) if self.use_depth else None
         # warm-up on a side stream (allocations of the loss scratch, library one-offs), then capture.  The warm-up and the capture
         # pass both execute the step, so the parameters are saved and restored around them.
         names = self.model.NAMES
@@ -840,9 +909,15 @@ class GraphedStep:
         device between two replays)."""
         return (camera.world_view_transform.copy(), camera.full_proj_transform.copy(), camera.camera_center.copy())
 
-    def _load(self, camera, gt_image):
+    def _load(self, camera, gt_image, gt_depth=None):
         """Refresh the static buffers the captured step reads.  The pose is copied on every call that names a camera (the same Camera object
         may have been moved in place since it was loaded last)."""
+        if gt_depth is not None:
+            if not self.use_depth:
+                raise ValueError("GraphedStep: gt_depth given to a step built without depth supervision (pass gt_depth / lambda_depth to the constructor)")
+            if gt_depth.data_ptr() != self.gt_depth.data_ptr():
+                self.gt_depth.copy_(gt_depth)
+                self._gtd_serial = getattr(self, "_gtd_serial", 0) + 1
         if camera is not None:
             for k in self._BAKED:
                 assert float(getattr(camera, k)) == float(getattr(self.cam, k)), f"{k} is baked into the graph"
@@ -853,13 +928,14 @@ class GraphedStep:
             self.gt.copy_(gt_image)
             self._gt_serial = getattr(self, "_gt_serial", 0) + 1
 
-    def _snapshot(self, gt_image):
+    def _snapshot(self, gt_image, gt_depth=None):
         """What a repeat of this step needs, independent of what the caller does to its objects afterwards: the pose by VALUE (host copies of the
         35 floats that are loaded now) and the target by reference together with the evidence that it is still the same data (the tensor's
         version counter; for gt_image=None — "the target that is loaded" — the serial number of the load)."""
         if getattr(self, "_pose_host", None) is None:
             self._pose_host = self._pose_of(self.cam)
-        return dict(pose=self._pose_host, gt=gt_image, gt_version=None if gt_image is None else gt_image._version, gt_serial=getattr(self, "_gt_serial", 0))
+        return dict(pose=self._pose_host, gt=gt_image, gt_version=None if gt_image is None else gt_image._version, gt_serial=getattr(self, "_gt_serial", 0),
+                    gtd=gt_depth, gtd_version=None if gt_depth is None else gt_depth._version, gtd_serial=getattr(self, "_gtd_serial", 0))
 
     def _load_snapshot(self, snap):
         dev = self.view.device
@@ -877,6 +953,19 @@ class GraphedStep:
             if gt.data_ptr() != self.gt.data_ptr():
                 self.gt.copy_(gt)
                 self._gt_serial = getattr(self, "_gt_serial", 0) + 1
+        if not self.use_depth:
+            return
+        gtd = snap.get("gtd")
+        if gtd is None:
+            if snap.get("gtd_serial", 0) != getattr(self, "_gtd_serial", 0):
+                raise RuntimeError("GraphedStep: a step that has to be repeated ran on a depth target that has been replaced since (it was issued with "
+                                   "gt_depth=None); pass the depth target explicitly to step() when targets change between checks")
+        else:
+            if gtd._version != snap["gtd_version"]:
+                raise RuntimeError("GraphedStep: the depth target of a step that has to be repeated was modified in place after the step was issued")
+            if gtd.data_ptr() != self.gt_depth.data_ptr():
+                self.gt_depth.copy_(gtd)
+                self._gtd_serial = getattr(self, "_gtd_serial", 0) + 1
 
     def _issue(self):
         if self.graph is not None:
@@ -885,13 +974,14 @@ class GraphedStep:
             with torch.no_grad():
                 self._eager()
 
-    def step(self, camera=None, gt_image=None):
-        """One optimiser step (replay).  Returns the device tensor [mean L1, mean SSIM] of this step's loss terms."""
-        self._load(camera, gt_image)
+    def step(self, camera=None, gt_image=None, gt_depth=None):
+        """One optimiser step (replay).  Returns the device tensor [mean L1, mean SSIM] of this step's loss terms ([mean L1, mean SSIM, L_d]
+        with depth supervision; gt_depth: this step's depth target, None = the one that is loaded)."""
+        self._load(camera, gt_image, gt_depth)
         self._issue()
         self.steps_issued += 1
         if len(self.window) < 32:
-            self.window.append(self._snapshot(gt_image))
+            self.window.append(self._snapshot(gt_image, gt_depth))
         self.model.optimizer.count_step()
         if self.check_every and self.steps_issued >= self.check_every:
             self.check()

@@ -226,9 +226,10 @@ int gslic_rasterize_backward(
  *  not know the check costs one 4-byte device read, the call then waits for the stream).  gslic_rasterize_backward on a depth forward's buffers is valid and returns the colour-only gradients.
  *  no_color = 1, or dL_ddepth == NULL with P > 0, is GSLIC_ERR_INVALID_ARG; P == 0 returns at once.
  *
- * Not covered by depth (unchanged, colour only): the capacity / graph path (gslic_rasterize_forward_capacity), the fused-Adam
- * backward, the N-GPU colour exchange (gslic_rasterize_backward_rgb*), the camera-pose gradient (gslic_rasterize_backward_camera)
- * and the LibTorch drop-in shim.
+ * The single-GPU fast path has depth too: gslic_rasterize_forward_depth_capacity (capacity / graph mode), gslic_rasterize_backward_depth_adam
+ * (fused Adam) and gslic_depth_l1_loss_forward_backward (the loss) below.
+ * Not covered by depth (unchanged, colour only): the N-GPU colour exchange (gslic_rasterize_backward_rgb*), the camera-pose gradient
+ * (gslic_rasterize_backward_camera) and the LibTorch drop-in shim.
  */
 int gslic_rasterize_forward_depth(
     const gslic_raster_params* prm,
@@ -316,6 +317,41 @@ int gslic_rasterize_backward_adam(
     const float* scales, const float* rotations, const float* cov3D_precomp,
     const float* viewmatrix, const float* projmatrix, const float* cam_pos, const int32_t* radii,
     char* geom_buffer, char* binning_buffer, char* img_buffer, char* sample_buffer, const float* dL_dpix,
+    float* dL_dopacity, float* dL_dmean3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot,
+    float lambda_erank, const gslic_adam_fused* adam, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Depth on the single-GPU fast path (no reference counterpart).
+ *
+ * gslic_rasterize_forward_depth_capacity — gslic_rasterize_forward_capacity plus out_depth [H,W] (as gslic_rasterize_forward_depth): no host
+ *  round trip, results bit-identical to gslic_rasterize_forward_depth, the same status words and overflow behaviour (nothing is written out of
+ *  bounds; a following backward, _depth_adam included, does nothing).  The buffers are sized with the depth carves: img >= gslic_img_bytes_depth,
+ *  and the capacities R / B are derived from gslic_binning_bytes_depth / gslic_sample_bytes_depth (each monotonic; the colour-only size of the
+ *  same count is an exact prefix).  The forward leaves a host-side note, so a depth backward on these buffers needs no device read (graph capture).
+ *
+ * gslic_rasterize_backward_depth_adam — gslic_rasterize_backward_adam plus dL_ddepth [H,W]: bit-identical to gslic_rasterize_backward_depth with
+ *  raw_params = 1 followed by gslic_adam_update_groups(visible = radii > 0); fills adam->visible_out like the colour entry point.  The fused
+ *  kernel updates every group but xyz and leaves xyz's chain gradient in dL_dmean3D, which is therefore REQUIRED here ([P,3], any contents: every
+ *  row is written); a second kernel adds dL/dz * row 2 of the view matrix and updates xyz from the complete gradient (which dL_dmean3D then holds).
+ *  The other gradient pointers may be NULL.  dL_ddepth == NULL, dL_dmean3D == NULL or adam == NULL (P > 0) is GSLIC_ERR_INVALID_ARG.
+ */
+int gslic_rasterize_forward_depth_capacity(
+    const gslic_raster_params* prm,
+    char* geom_buffer, size_t geom_bytes,
+    char* binning_buffer, size_t binning_bytes,
+    char* img_buffer, size_t img_bytes,
+    char* sample_buffer, size_t sample_bytes,
+    const float* background, const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+    const float* opacities, const float* scales, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix, const float* cam_pos,
+    float* out_color, float* out_final_T, float* out_depth, int32_t* radii,
+    int32_t* capacity_R, int32_t* capacity_B, uint32_t* status, void* stream);
+int gslic_rasterize_backward_depth_adam(
+    const gslic_raster_params* prm, int32_t R, int32_t B,
+    const float* background, const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+    const float* scales, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix, const float* cam_pos, const int32_t* radii,
+    char* geom_buffer, char* binning_buffer, char* img_buffer, char* sample_buffer, const float* dL_dpix, const float* dL_ddepth,
     float* dL_dopacity, float* dL_dmean3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot,
     float lambda_erank, const gslic_adam_fused* adam, void* stream);
 
@@ -475,6 +511,16 @@ int gslic_l1_ssim_loss_forward_backward(
     int32_t B, int32_t CH, int32_t H, int32_t W, float C1, float C2, float lambda_dssim, const float* img, const float* gt,
     float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12, float* partials, float* terms /*[2] device*/, float* dL_dimg, void* stream);
 
+/* gslic_depth_l1_loss_forward_backward — the masked depth L1 of LiDAR depth supervision and its gradient in TWO launches (no reference
+ * counterpart): mask = gt_depth > 0, n = number of masked pixels, term[0] = L_d = sum_mask |depth - gt_depth| / max(n, 1) (DEVICE float, fixed-order
+ * reduction: bit-reproducible; n is an exact integer count), dL_ddepth [H,W] = (lambda_depth / max(n, 1)) sign(depth - gt_depth) on the mask and 0 off
+ * it (sign(0) = 0) — the gradient of lambda_depth * L_d, bit for bit what autograd forms for it.  depth, gt_depth [H,W] device; `partials` is DEVICE
+ * scratch of gslic_depth_l1_loss_partials_count(H, W) floats.  No allocation, no host synchronisation (graph-capturable). */
+int64_t gslic_depth_l1_loss_partials_count(int32_t H, int32_t W);
+int gslic_depth_l1_loss_forward_backward(
+    int32_t H, int32_t W, float lambda_depth, const float* depth, const float* gt_depth, float* partials, float* term /*[1] device*/,
+    float* dL_ddepth, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * gslic_knn_mean_dist2 — replaces SimpleKNN::knn (src/simple-knn/simple_knn.cu:185-221) behind distCUDA2
  * (src/simple-knn/spatial.cu:15-26): mean_dists[i] = mean of the 3 smallest squared distances from point i
@@ -559,6 +605,11 @@ size_t gslic_geom_bytes(int32_t P);
 size_t gslic_img_bytes(int32_t width, int32_t height);
 size_t gslic_binning_bytes(int32_t R, int32_t no_color);
 size_t gslic_sample_bytes(int32_t B);
+/* The same for the buffers of a depth forward (gslic_rasterize_forward_depth*): the colour layout plus 4 bytes per pixel of the tile grid / per
+ * instance / per bucket-pixel behind it. */
+size_t gslic_img_bytes_depth(int32_t width, int32_t height);
+size_t gslic_binning_bytes_depth(int32_t R);
+size_t gslic_sample_bytes_depth(int32_t B);
 
 /* Per-kernel HIP-event timing.  While enabled, every kernel launch of this library is bracketed by a
  * hipEvent pair recorded on the launch stream; gslic_profile_collect synchronises the device and adds the

@@ -45,6 +45,7 @@ EXPORTS = [
     "gslic_rasterize_forward_depth", "gslic_rasterize_backward_depth",
     "gslic_rasterize_forward_depth_capacity", "gslic_rasterize_backward_depth_adam", "gslic_depth_l1_loss_partials_count",
     "gslic_depth_l1_loss_forward_backward", "gslic_img_bytes_depth", "gslic_binning_bytes_depth", "gslic_sample_bytes_depth",
+    "gslic_rasterize_backward_depth_camera",
 ]
 
 _lib = None
@@ -103,6 +104,8 @@ def lib():
         [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp] + [vp] * 6 + [f32, ctypes.POINTER(AdamFused), vp])
     L.gslic_rasterize_backward_camera.argtypes = (
         [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp] + [vp] * 10 + [f32, vp, vp, vp, vp])
+    L.gslic_rasterize_backward_depth_camera.argtypes = (
+        [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp, vp] + [vp] * 10 + [f32, vp, vp, vp, vp])
     L.gslic_rasterize_backward_rgb.argtypes = (
         [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp] + [vp] * 5 + [f32, vp])
     L.gslic_rasterize_backward_rgb_rows.argtypes = (

@@ -1027,6 +1027,36 @@ int gslic_rasterize_backward_camera(const gslic_raster_params* prm, int32_t R, i
                                    lambda_erank, nullptr, cam, stream);
 }
 
+int gslic_rasterize_backward_depth_camera(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
+                                          const float* dc, const float* shs, const float* colors_precomp, const float* scales,
+                                          const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                          const float* cam_pos, const int32_t* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                                          char* sample_buffer, const float* dL_dpix, const float* dL_ddepth, float* dL_dmean2D, float* dL_dconic,
+                                          float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh,
+                                          float* dL_dscale, float* dL_drot, float lambda_erank, float* dL_dviewmatrix, float* dL_dprojmatrix,
+                                          float* dL_dcampos, void* stream)
+{
+    if (!dL_dviewmatrix || !dL_dprojmatrix || !dL_dcampos)
+        return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_camera: a camera-gradient output pointer is NULL");
+    GS_TRY(check_params(prm));   // (SH degree > 3 among them)
+    float* const cam[3] = {dL_dviewmatrix, dL_dprojmatrix, dL_dcampos};
+    if (prm->P == 0) {  // nothing rendered: zero gradients
+        hipStream_t s = (hipStream_t)stream;
+        GS_HIP(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float), s));
+        GS_HIP(hipMemsetAsync(dL_dprojmatrix, 0, 16 * sizeof(float), s));
+        GS_HIP(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float), s));
+        return GSLIC_OK;
+    }
+    if (prm->no_color) return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no_color = 1 (no depth forward renders without colour)");
+    if (!dL_ddepth)
+        return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: dL_ddepth is NULL (gslic_rasterize_backward_camera is the colour-only camera backward)");
+    if (!dL_dmean3D) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_camera: dL_dmean3D is NULL (the depth's share is added to it)");
+    return rasterize_backward_impl(prm, R, B, background, means3D, dc, shs, colors_precomp, scales, rotations, cov3D_precomp, viewmatrix,
+                                   projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, dL_dmean2D,
+                                   dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot,
+                                   lambda_erank, nullptr, cam, stream, nullptr, 0, -1, false, nullptr, nullptr, dL_ddepth);
+}
+
 int gslic_adam_update(float* param, const float* param_grad, float* exp_avg, float* exp_avg_sq, const uint8_t* visible, float lr,
                       float b1, float b2, float eps, uint32_t N, uint32_t M, void* stream)
 {

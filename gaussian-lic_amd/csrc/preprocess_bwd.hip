@@ -650,16 +650,12 @@ __global__ __launch_bounds__(256) void cam_reduce_kernel(size_t rows, const floa
 // ADAM (gslic_rasterize_backward_depth_adam, behind preprocess_bwd_defer_xyz_kernel): dL_dmean3D holds the chain's xyz gradient, the sum is formed by
 // the same code and then consumed by the masked Adam update of group 0 (adam_scalar, as gslic_adam_update_groups applies it to visible rows): 12 B
 // per Gaussian read and 12 written more than the colour-only fused step, plus the dz gather.
+// depth_mean3d_row: the work per visible Gaussian, shared by depth_mean3d_kernel and its camera variant below.  Returns dL/dz.
 template <bool ADAM>
-__global__ __launch_bounds__(256) void depth_mean3d_kernel(int row_begin, int row_end, const int32_t* __restrict__ radii,
-                                                           const uint32_t* __restrict__ gauss_start, const uint32_t* __restrict__ tiles_touched,
-                                                           const uint8_t* __restrict__ dead, const float* __restrict__ partials_z,
-                                                           const float* __restrict__ V, const uint32_t* __restrict__ status, float* __restrict__ dL_dmean3D,
-                                                           AdamFusedArgs A)
+__device__ __forceinline__ float depth_mean3d_row(const int idx, const uint32_t* __restrict__ gauss_start, const uint32_t* __restrict__ tiles_touched,
+                                                  const uint8_t* __restrict__ dead, const float* __restrict__ partials_z, const float* __restrict__ V,
+                                                  float* __restrict__ dL_dmean3D, const AdamFusedArgs& A)
 {
-    if (status[2] != 0u) return;   // capacity overflow in the forward: preprocess_bwd_kernel wrote nothing either
-    const int idx = row_begin + (int)(blockIdx.x * 256u + threadIdx.x);
-    if (idx >= row_end || radii[idx] <= 0) return;   // invisible: the chain wrote exact zeros and there is no instance
     const uint32_t u0 = gauss_start[idx], u1 = u0 + tiles_touched[idx];
     float dz = 0.f;
     constexpr int UP = 4;   // four instances in flight per trip (masked adds: the same summation order as one at a time)
@@ -682,12 +678,100 @@ __global__ __launch_bounds__(256) void depth_mean3d_kernel(int row_begin, int ro
         for (int k = 0; k < 3; k++)
             adam_scalar(A.p[0][3 * idx + k], dL_dmean3D[3 * idx + k], A.m[0][3 * idx + k], A.v[0][3 * idx + k], A.lr[0], A.b1, A.b2, A.eps);
     }
+    return dz;
+}
+
+template <bool ADAM>
+__global__ __launch_bounds__(256) void depth_mean3d_kernel(int row_begin, int row_end, const int32_t* __restrict__ radii,
+                                                           const uint32_t* __restrict__ gauss_start, const uint32_t* __restrict__ tiles_touched,
+                                                           const uint8_t* __restrict__ dead, const float* __restrict__ partials_z,
+                                                           const float* __restrict__ V, const uint32_t* __restrict__ status, float* __restrict__ dL_dmean3D,
+                                                           AdamFusedArgs A)
+{
+    if (status[2] != 0u) return;   // capacity overflow in the forward: preprocess_bwd_kernel wrote nothing either
+    const int idx = row_begin + (int)(blockIdx.x * 256u + threadIdx.x);
+    if (idx >= row_end || radii[idx] <= 0) return;   // invisible: the chain wrote exact zeros and there is no instance
+    depth_mean3d_row<ADAM>(idx, gauss_start, tiles_touched, dead, partials_z, V, dL_dmean3D, A);
+}
+
+// Camera variant (gslic_rasterize_backward_depth_camera, behind preprocess_bwd_kernel<.., CAM = true>).  The depth reaches the camera through the 2D
+// quantities — already inside the nine sums the CAM chain consumed — and directly through z = V[2] x + V[6] y + V[10] z + V[14]:
+//   dL_dviewmatrix[2, 6, 10, 14] += sum_i dL/dz_i (x_i, y_i, z_i, 1).
+// Per Gaussian the same gather and the same dL_dmean3D update as above, plus the four products; invisible lanes and lanes behind the range add
+// zeros (every lane of the wave takes part in the xor-shuffle tree, the one of the CAM body), and lane 0 writes the four sums into the free slots
+// 27..30 of the wave's 32-float partial row.  Row of a Gaussian = (idx - row_begin) / 64 in both layouts of the chain kernel (one-wave blocks of
+// 64; 256-thread blocks x 4 waves), so this 256-thread kernel addresses the chain's rows in either.  No atomics: cam_reduce_depth_kernel adds the rows.
+__global__ __launch_bounds__(256) void depth_mean3d_cam_kernel(int row_begin, int row_end, const int32_t* __restrict__ radii,
+                                                               const uint32_t* __restrict__ gauss_start, const uint32_t* __restrict__ tiles_touched,
+                                                               const uint8_t* __restrict__ dead, const float* __restrict__ partials_z,
+                                                               const float* __restrict__ V, const uint32_t* __restrict__ status, const float* __restrict__ means,
+                                                               float* __restrict__ dL_dmean3D, float* __restrict__ cam_partials)
+{
+#pragma clang fp contract(off)   // the four products are rounded on their own: the sums below depend on nothing but their order
+    if (status[2] != 0u) return;   // capacity overflow in the forward: no row is written, cam_reduce_depth_kernel sums none
+    const int idx = row_begin + (int)(blockIdx.x * 256u + threadIdx.x);
+    float c[4] = {0.f, 0.f, 0.f, 0.f};
+    if (idx < row_end && radii[idx] > 0) {
+        AdamFusedArgs none;   // (never read: ADAM = false)
+        none.on = 0;
+        const float dz = depth_mean3d_row<false>(idx, gauss_start, tiles_touched, dead, partials_z, V, dL_dmean3D, none);
+        c[0] = dz * means[3 * idx]; c[1] = dz * means[3 * idx + 1]; c[2] = dz * means[3 * idx + 2]; c[3] = dz;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        float v = c[k];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+        c[k] = v;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        float* row = cam_partials + 32 * ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6));
+#pragma unroll
+        for (int k = 0; k < 4; k++) row[27 + k] = c[k];
+    }
+}
+
+// cam_reduce_kernel for the depth camera backward: the same 27 sums in the same order, and for the view terms k = 2, 5, 8, 11 (row 2 of the view
+// matrix, columns 0..3) the sum of slot 27 + k / 3 over the same rows in the same order, added last.  After a forward capacity overflow no row was
+// written: nothing is summed and the outputs keep the zeros of the launch's memset.
+__global__ __launch_bounds__(256) void cam_reduce_depth_kernel(size_t rows, const float* __restrict__ partials, const uint32_t* __restrict__ status,
+                                                               float* __restrict__ out)
+{
+    __shared__ float red[256], redz[256];
+    if (status[2] != 0u) return;
+    const int k = blockIdx.x;
+    const bool direct = k < 12 && (k % 3) == 2;
+    const int kz = 27 + k / 3;
+    float s = 0.f, sz = 0.f;
+    for (size_t r = threadIdx.x; r < rows; r += 256) {
+        s += partials[32 * r + k];
+        if (direct) sz += partials[32 * r + kz];
+    }
+    red[threadIdx.x] = s;
+    redz[threadIdx.x] = sz;
+    __syncthreads();
+    for (int d = 128; d >= 1; d >>= 1) {
+        if ((int)threadIdx.x < d) {
+            red[threadIdx.x] += red[threadIdx.x + d];
+            redz[threadIdx.x] += redz[threadIdx.x + d];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        int dst;   // as cam_reduce_kernel
+        if (k < 12) dst = 4 * (k / 3) + (k % 3);
+        else if (k < 24) { const int kk = k - 12; const int r = kk % 3; dst = 16 + 4 * (kk / 3) + (r == 2 ? 3 : r); }
+        else dst = 32 + (k - 24);
+        out[dst] = direct ? red[0] + redz[0] : red[0];
+    }
 }
 
 int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s)
 {
-    if (a.partials_z && (a.cam_partials || a.dL_drgb || !a.dL_dmean3D))
-        return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no camera gradient or dL_drgb output, and dL_dmean3D is required");
+    if (a.partials_z && (a.dL_drgb || !a.dL_dmean3D))
+        return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no dL_drgb output, and dL_dmean3D is required");
+    if (a.partials_z && a.cam_partials && (a.adam.on || a.row_begin != 0))
+        return set_error(GSLIC_ERR_INVALID_ARG, "depth camera backward: no fused Adam and no row range");
     const bool defer = a.partials_z && a.adam.on;   // depth + fused Adam: xyz is updated by depth_mean3d_kernel<true> once dL/dz is in
     const bool cam = a.cam_partials != nullptr;
     const int nrows = a.row_end - a.row_begin;
@@ -707,12 +791,16 @@ int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s)
     if (defer)
         GS_LAUNCH(K_PREPROCESS_BWD, depth_mean3d_kernel<true>, dim3(div_up(nrows, 256)), dim3(256), 0, s, a.row_begin, a.row_end, a.radii, a.gauss_start,
                   a.tiles_touched, a.dead, a.partials_z, a.view, a.status, a.dL_dmean3D, a.adam);
+    else if (a.partials_z && cam)
+        GS_LAUNCH(K_PREPROCESS_BWD, depth_mean3d_cam_kernel, dim3(div_up(nrows, 256)), dim3(256), 0, s, a.row_begin, a.row_end, a.radii, a.gauss_start,
+                  a.tiles_touched, a.dead, a.partials_z, a.view, a.status, a.means, a.dL_dmean3D, a.cam_partials);
     else if (a.partials_z)
         GS_LAUNCH(K_PREPROCESS_BWD, depth_mean3d_kernel<false>, dim3(div_up(nrows, 256)), dim3(256), 0, s, a.row_begin, a.row_end, a.radii, a.gauss_start,
                   a.tiles_touched, a.dead, a.partials_z, a.view, a.status, a.dL_dmean3D, a.adam);
     if (cam) {
         const size_t rows = (a.M == 15 && a.shs && (a.dL_dsh || a.adam.on || a.dL_drgb)) ? (size_t)div_up(a.P, 64) : (size_t)div_up(a.P, 256) * 4;
-        GS_LAUNCH(K_PREPROCESS_BWD, cam_reduce_kernel, dim3(27), dim3(256), 0, s, rows, (const float*)a.cam_partials, a.cam_out);
+        if (a.partials_z) GS_LAUNCH(K_PREPROCESS_BWD, cam_reduce_depth_kernel, dim3(27), dim3(256), 0, s, rows, (const float*)a.cam_partials, a.status, a.cam_out);
+        else GS_LAUNCH(K_PREPROCESS_BWD, cam_reduce_kernel, dim3(27), dim3(256), 0, s, rows, (const float*)a.cam_partials, a.cam_out);
     }
     return GSLIC_OK;
 }

@@ -310,7 +310,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
 def rasterize_gaussians_backward_depth(background, means3D, radii, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx,
                                        tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, dL_dout_color, dL_dout_depth, dc, sh, degree, campos,
                                        geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank=0.0, debug=False, raw_params=False,
-                                       out=None, adam=None, xyz_grad=None):
+                                       out=None, adam=None, xyz_grad=None, camera_grads=False):
     """gslic_rasterize_backward_depth: rasterize_gaussians_backward with dL/d(out_depth) [H,W] as a second input, on the buffers of
     rasterize_gaussians_depth (or rasterize_gaussians_depth_capacity: pass its cap_R / cap_B as R / B).  Returns the same nine tensors
     (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscales, dL_drotations); dL_dout_depth = 0 gives
@@ -319,11 +319,15 @@ def rasterize_gaussians_backward_depth(background, means3D, radii, scales, rotat
     rasterize_gaussians_backward's `out`); the four the host discards are then not materialised.
     adam (a gslic_adam_fused descriptor, raw_params implied): gslic_rasterize_backward_depth_adam — the Adam update inside the backward,
     bit-identical to this backward followed by the masked Adam step; returns None.  xyz_grad [P,3]: where the xyz gradient is assembled before
-    its update (allocated when None; a graph-captured step passes a buffer of its own)."""
+    its update (allocated when None; a graph-captured step passes a buffer of its own).
+    camera_grads=True (gslic_rasterize_backward_depth_camera): three more tensors are appended — dL_dviewmatrix [16], dL_dprojmatrix [16],
+    dL_dcampos [3] of the colour AND depth loss, as rasterize_gaussians_backward(camera_grads=True) does; not with adam."""
     L = _lib.lib()
     dev = means3D.device
     P, H, W = means3D.size(0), dL_dout_color.size(1), dL_dout_color.size(2)
     M = sh.size(1) if sh is not None and sh.size(0) != 0 else 0
+    if adam is not None and camera_grads:
+        raise ValueError("rasterize_gaussians_backward_depth: camera_grads with the fused Adam backward is not available")
     if adam is not None:
         if P == 0:
             return None
@@ -359,14 +363,21 @@ def rasterize_gaussians_backward_depth(background, means3D, radii, scales, rotat
         prm = _params(P, degree, M, H, W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier,
                       False, debug, False, raw_params)
         p = _lib.ptr
-        _lib.check(L.gslic_rasterize_backward_depth(
-            ctypes.byref(prm), int(R), int(B), p(background), p(means3D), p(dc), p(sh_c), None, p(scales), p(rotations), None,
-            p(viewmatrix), p(projmatrix), p(campos), p(radii.contiguous()),
-            ctypes.c_void_p(geomBuffer.data_ptr()), ctypes.c_void_p(binningBuffer.data_ptr()),
-            ctypes.c_void_p(imageBuffer.data_ptr()), ctypes.c_void_p(sampleBuffer.data_ptr()), p(dL), p(dLd),
-            p(dL_dmeans2D), p(dL_dconic), p(dL_dopacities), p(dL_dcolors), p(dL_dmeans3D), p(dL_dcov3D), p(dL_ddc),
-            p(dL_dsh), p(dL_dscales), p(dL_drotations), float(lambda_erank), _lib.current_stream_ptr()))
-    return (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscales, dL_drotations)
+        common = (ctypes.byref(prm), int(R), int(B), p(background), p(means3D), p(dc), p(sh_c), None, p(scales), p(rotations), None,
+                  p(viewmatrix), p(projmatrix), p(campos), p(radii.contiguous()),
+                  ctypes.c_void_p(geomBuffer.data_ptr()), ctypes.c_void_p(binningBuffer.data_ptr()),
+                  ctypes.c_void_p(imageBuffer.data_ptr()), ctypes.c_void_p(sampleBuffer.data_ptr()), p(dL), p(dLd),
+                  p(dL_dmeans2D), p(dL_dconic), p(dL_dopacities), p(dL_dcolors), p(dL_dmeans3D), p(dL_dcov3D), p(dL_ddc),
+                  p(dL_dsh), p(dL_dscales), p(dL_drotations), float(lambda_erank))
+        if camera_grads:
+            cam = (torch.empty(16, device=dev), torch.empty(16, device=dev), torch.empty(3, device=dev))
+            _lib.check(L.gslic_rasterize_backward_depth_camera(*common, p(cam[0]), p(cam[1]), p(cam[2]), _lib.current_stream_ptr()))
+        else:
+            _lib.check(L.gslic_rasterize_backward_depth(*common, _lib.current_stream_ptr()))
+    elif camera_grads:
+        cam = (torch.zeros(16, device=dev), torch.zeros(16, device=dev), torch.zeros(3, device=dev))
+    res = (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscales, dL_drotations)
+    return res + cam if camera_grads else res
 
 
 def _depth_grads(ctx, dL_dcolor, dL_ddepth, xyz, dc, sh, opacity, scaling, rotation, radii, geom, binning, img, sample, raw):

@@ -100,6 +100,7 @@ def _build_check(CHECK, first_includes, force, extra_src=()):
 
 CHECK_FUSED = os.path.join(PKG, "fused_check")
 CHECK_FUSED_DEPTH = os.path.join(PKG, "fused_depth_check")
+CHECK_FUSED_DEPTH_POSE = os.path.join(PKG, "fused_depth_pose_check")
 
 
 def build_fused_check(force=False):
@@ -112,6 +113,12 @@ def build_fused_depth_check(force=False):
     """fused_depth_check: the fused training step with LiDAR depth supervision from C++ (gslic::FusedStep::step with gt_depth) — built like
     fused_check."""
     return _build_fused_program(os.path.join(HERE, "fused_depth_check.cpp"), CHECK_FUSED_DEPTH, force)
+
+
+def build_fused_depth_pose_check(force=False):
+    """fused_depth_pose_check: the camera-pose gradient with LiDAR depth supervision from C++ (gslic::FusedStep::pose_gradient with gt_depth) —
+    built like fused_check."""
+    return _build_fused_program(os.path.join(HERE, "fused_depth_pose_check.cpp"), CHECK_FUSED_DEPTH_POSE, force)
 
 
 def _build_fused_program(src, CHECK_FUSED, force):
@@ -146,3 +153,4 @@ if __name__ == "__main__":
         print(build_dropin_check(force="--force" in sys.argv, groups=g))
     print(build_fused_check(force="--force" in sys.argv))
     print(build_fused_depth_check(force="--force" in sys.argv))
+    print(build_fused_depth_pose_check(force="--force" in sys.argv))

@@ -290,6 +290,59 @@ public:
         torch::Tensor hc = camg.to(torch::kCPU), hv = cam.world_view_transform.to(torch::kCPU).contiguous(), hp = cam.full_proj_transform.to(torch::kCPU).contiguous();
         return se3_pose_gradient(hv.data_ptr<float>(), hp.data_ptr<float>(), hc.data_ptr<float>(), hc.data_ptr<float>() + 16, hc.data_ptr<float>() + 32);
     }
+    // The same gradient under LiDAR depth supervision: loss = (1 - lambda) L1 + lambda (1 - SSIM) + lambda_depth L_d.  gslic_rasterize_forward_depth, the
+    // colour and depth loss calls of step(cam, gt_image, gt_depth, lambda_depth), gslic_rasterize_backward_depth_camera, the same chain — the calls
+    // gaussian-lic_amd/trainer.py:pose_gradient(gt_depth=...) issues.  terms_out (optional): the device tensor [mean L1, mean SSIM, L_d].  An undefined
+    // gt_depth or lambda_depth == 0 is the colour-only gradient above.
+    std::array<double, 6> pose_gradient(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor& gt_depth, float lambda_depth,
+                                        torch::Tensor* terms_out = nullptr)
+    {
+        if (!gt_depth.defined() || lambda_depth == 0.0f) return pose_gradient(cam, gt_image);
+        torch::NoGradGuard ng;
+        const int64_t P = prm_[0].size(0);
+        const int W = cam.image_width, H = cam.image_height;
+        TORCH_CHECK(gt_image.is_contiguous() && gt_image.dim() == 3 && gt_image.size(1) == H && gt_image.size(2) == W, "gt_image must be contiguous [3,H,W]");
+        TORCH_CHECK(gt_depth.is_contiguous() && gt_depth.scalar_type() == torch::kFloat32 && gt_depth.dim() == 2 && gt_depth.size(0) == H &&
+                    gt_depth.size(1) == W, "gt_depth must be contiguous fp32 [H,W]");
+        gslic_raster_params rp{};
+        rp.tie_rank = tie_.defined() ? reinterpret_cast<const uint32_t*>(tie_.data_ptr<int32_t>()) : nullptr;
+        rp.P = (int32_t)P; rp.D = deg_; rp.M = prm_[2].numel() ? (int32_t)prm_[2].size(1) : 0; rp.width = W; rp.height = H;
+        rp.tan_fovx = cam.tanfovx; rp.tan_fovy = cam.tanfovy;
+        rp.limx_neg = cam.limx_neg; rp.limx_pos = cam.limx_pos; rp.limy_neg = cam.limy_neg; rp.limy_pos = cam.limy_pos;
+        rp.scale_modifier = 1.0f; rp.raw_params = 1;
+        auto fo = prm_[0].options().requires_grad(false);
+        torch::Tensor image = torch::empty({3, H, W}, fo), final_T = torch::empty({H, W}, fo), depth = torch::empty({H, W}, fo);
+        torch::Tensor radii = torch::empty({P}, fo.dtype(torch::kInt32));
+        torch::Tensor d1 = torch::empty({3, H, W}, fo), d2 = torch::empty({3, H, W}, fo), d3 = torch::empty({3, H, W}, fo), dL = torch::empty({3, H, W}, fo);
+        torch::Tensor dLd = torch::empty({H, W}, fo), dpartials = torch::empty({gslic_depth_l1_loss_partials_count(H, W)}, fo);
+        torch::Tensor partials = torch::empty({gslic_loss_partials_count(1, 3, H, W)}, fo), terms = torch::empty({3}, fo), camg = torch::zeros({35}, fo);
+        std::array<torch::Tensor, 6> g;
+        for (int i = 0; i < 6; i++) g[i] = torch::empty_like(prm_[i], fo);
+        const float *xyz = f(prm_[0]), *dc = f(prm_[1]), *rest = f(prm_[2]), *op = f(prm_[3]), *sc = f(prm_[4]), *rot = f(prm_[5]);
+        const float *view = f(cam.world_view_transform), *proj = f(cam.full_proj_transform), *cpos = f(cam.camera_center);
+        int32_t R = 0, B = 0;
+        check(gslic_rasterize_forward_depth(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), xyz,
+                                            dc, rest, nullptr, op, sc, rot, nullptr, view, proj, cpos, image.data_ptr<float>(), final_T.data_ptr<float>(),
+                                            depth.data_ptr<float>(), radii.data_ptr<int32_t>(), &R, &B, current_stream()),
+              "gslic_rasterize_forward_depth");
+        check(gslic_l1_ssim_loss_forward_backward(1, 3, H, W, 0.01f * 0.01f, 0.03f * 0.03f, lambda_dssim_, f(image), f(gt_image), d1.data_ptr<float>(),
+                                                  d2.data_ptr<float>(), d3.data_ptr<float>(), partials.data_ptr<float>(), terms.data_ptr<float>(),
+                                                  dL.data_ptr<float>(), current_stream()),
+              "gslic_l1_ssim_loss_forward_backward");
+        check(gslic_depth_l1_loss_forward_backward(H, W, lambda_depth, f(depth), f(gt_depth), dpartials.data_ptr<float>(), terms.data_ptr<float>() + 2,
+                                                   dLd.data_ptr<float>(), current_stream()),
+              "gslic_depth_l1_loss_forward_backward");
+        auto w = [](torch::Tensor& t) { return t.numel() ? t.data_ptr<float>() : nullptr; };
+        float* cg = camg.data_ptr<float>();
+        check(gslic_rasterize_backward_depth_camera(&rp, R, B, f(bg_), xyz, dc, rest, nullptr, sc, rot, nullptr, view, proj, cpos, radii.data_ptr<int32_t>(),
+                                                    cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), cptr(scratch_[3]), f(dL), f(dLd), nullptr, nullptr,
+                                                    w(g[3]), nullptr, w(g[0]), nullptr, w(g[1]), w(g[2]), w(g[4]), w(g[5]), lambda_erank_, cg, cg + 16, cg + 32,
+                                                    current_stream()),
+              "gslic_rasterize_backward_depth_camera");
+        if (terms_out) *terms_out = terms;
+        torch::Tensor hc = camg.to(torch::kCPU), hv = cam.world_view_transform.to(torch::kCPU).contiguous(), hp = cam.full_proj_transform.to(torch::kCPU).contiguous();
+        return se3_pose_gradient(hv.data_ptr<float>(), hp.data_ptr<float>(), hc.data_ptr<float>(), hc.data_ptr<float>() + 16, hc.data_ptr<float>() + 32);
+    }
     // the chain alone, on host arrays in the element order of the kernels' inputs (float[16] with (r, c) at [4c + r])
     static std::array<double, 6> se3_pose_gradient(const float* view16, const float* fullproj16, const float* dview16, const float* dproj16, const float* dcampos3)
     {

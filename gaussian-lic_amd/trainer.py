@@ -576,12 +576,37 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
     return loss.detach(), visible
 
 
-def pose_gradient(model, camera, gt_image, bg, fused_loss=None):
+def _pose_depth_forward_losses(model, cam, gt_image, bg, fl, gt_depth, lambda_depth):
+    """Depth forward and the colour / depth loss kernels of the pose steps: (backward's positional arguments, radii, terms [L1, SSIM, L_d])."""
+    from . import rasterizer as rz
+    xyz, dc, rest = model.xyz.detach(), model.features_dc.detach(), model.features_rest.detach()
+    op, sc, rot = model.opacity.detach(), model.scaling.detach(), model.rotation.detach()
+    (R, B, image, _final_T, depth, radii, geom, binning, img, sample) = rz.rasterize_gaussians_depth(
+        bg, xyz, op, sc, rot, 1.0, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
+        cam.image_height, cam.image_width, float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dc, rest,
+        model.sh_degree, cam.d_camera_center, raw_params=True, tie_rank=getattr(model, "tie_rank", None))
+    dL_dimage, _ = fl.forward_backward(image, gt_image)
+    dL_ddepth, _ = fl.depth_forward_backward(depth, gt_depth, lambda_depth)
+    bwd = (bg, xyz, radii, sc, rot, 1.0, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
+           float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dL_dimage, dL_ddepth, dc, rest, model.sh_degree,
+           cam.d_camera_center, geom, R, binning, img, B, sample, model.lambda_erank, False)
+    return bwd, radii, fl.terms3
+
+
+def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, lambda_depth=0.0):
     """dL/dxi of the training loss w.r.t. a left se(3) increment of the camera pose (Camera.pose_gradient) for the current map: forward -> loss
     kernels -> gslic_rasterize_backward_camera -> the chain.  The map is not touched.  Returns (float64 [6] = (d/drho, d/dphi), terms).
-    One step of pose refinement is `camera.apply_pose_increment(-lr * g); camera.to_device(dev)`."""
+    One step of pose refinement is `camera.apply_pose_increment(-lr * g); camera.to_device(dev)`.
+    gt_depth [H,W] with lambda_depth != 0 (LiDAR depth supervision, as training_step_fused's): the loss gains lambda_depth * depth_l1 and the
+    gradient its share — depth forward -> colour and depth loss kernels -> gslic_rasterize_backward_depth_camera -> the same chain; terms is
+    then [mean L1, mean SSIM, L_d].  gt_depth=None or lambda_depth=0 is exactly the colour-only path."""
     from . import rasterizer as rz
     fl = fused_loss or _default_fused_loss()
+    if gt_depth is not None and lambda_depth != 0.0:
+        with torch.no_grad():
+            bwd, _radii, terms = _pose_depth_forward_losses(model, camera, gt_image, bg, fl, gt_depth, float(lambda_depth))
+            out = rz.rasterize_gaussians_backward_depth(*bwd, raw_params=True, camera_grads=True)
+        return camera.pose_gradient(out[9], out[10], out[11]), terms
     e = torch.empty(0, device=model.device)
     cam = camera
     with torch.no_grad():
@@ -599,30 +624,39 @@ def pose_gradient(model, camera, gt_image, bg, fused_loss=None):
     return cam.pose_gradient(out[9], out[10], out[11]), terms
 
 
-def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None):
+def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None, gt_depth=None, lambda_depth=0.0):
     """One joint map + pose iteration: forward -> loss kernels -> gslic_rasterize_backward_camera (parameter gradients AND the camera gradient in
     one pass) -> masked Adam on the map -> `camera` moved by -pose_lr * dL/dxi (left se(3) increment; 35 floats cross to the host, which is the
-    step's only synchronisation).  Returns (terms, visible, dL/dxi)."""
+    step's only synchronisation).  Returns (terms, visible, dL/dxi).
+    gt_depth [H,W] with lambda_depth != 0: the same step under LiDAR depth supervision (depth forward, colour and depth loss kernels,
+    gslic_rasterize_backward_depth_camera); the map update equals training_step_fused(gt_depth=...)'s, terms is [mean L1, mean SSIM, L_d].
+    gt_depth=None or lambda_depth=0 is exactly the colour-only step."""
     from . import rasterizer as rz
     fl = fused_loss or _default_fused_loss()
     dev = model.device
     e = torch.empty(0, device=dev)
     cam = camera
     with torch.no_grad():
-        xyz, dc, rest = model.xyz.detach(), model.features_dc.detach(), model.features_rest.detach()
-        op, sc, rot = model.opacity.detach(), model.scaling.detach(), model.rotation.detach()
-        (R, B, image, _final_T, radii, geom, binning, img, sample) = rz.rasterize_gaussians(
-            bg, xyz, e, op, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-            cam.image_height, cam.image_width, float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dc, rest,
-            model.sh_degree, cam.d_camera_center, False, False, False, raw_params=True, tie_rank=getattr(model, "tie_rank", None))
-        dL_dimage, terms = fl.forward_backward(image, gt_image)
         slab = getattr(model, "_grad_slab", None)
-        if slab is None or slab.P != model.P:
-            slab = model._grad_slab = GradSlab(model)
-        out = rz.rasterize_gaussians_backward(
-            bg, xyz, radii, e, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-            float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dL_dimage, dc, rest, model.sh_degree,
-            cam.d_camera_center, geom, R, binning, img, B, sample, model.lambda_erank, False, raw_params=True, out=slab.views, camera_grads=True)
+        if gt_depth is not None and lambda_depth != 0.0:
+            if slab is None or slab.P != model.P:
+                slab = model._grad_slab = GradSlab(model)
+            bwd, radii, terms = _pose_depth_forward_losses(model, cam, gt_image, bg, fl, gt_depth, float(lambda_depth))
+            out = rz.rasterize_gaussians_backward_depth(*bwd, raw_params=True, out=slab.views, camera_grads=True)
+        else:
+            xyz, dc, rest = model.xyz.detach(), model.features_dc.detach(), model.features_rest.detach()
+            op, sc, rot = model.opacity.detach(), model.scaling.detach(), model.rotation.detach()
+            (R, B, image, _final_T, radii, geom, binning, img, sample) = rz.rasterize_gaussians(
+                bg, xyz, e, op, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
+                cam.image_height, cam.image_width, float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dc, rest,
+                model.sh_degree, cam.d_camera_center, False, False, False, raw_params=True, tie_rank=getattr(model, "tie_rank", None))
+            dL_dimage, terms = fl.forward_backward(image, gt_image)
+            if slab is None or slab.P != model.P:
+                slab = model._grad_slab = GradSlab(model)
+            out = rz.rasterize_gaussians_backward(
+                bg, xyz, radii, e, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
+                float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dL_dimage, dc, rest, model.sh_degree,
+                cam.d_camera_center, geom, R, binning, img, B, sample, model.lambda_erank, False, raw_params=True, out=slab.views, camera_grads=True)
         visible = radii > 0
         model.optimizer.set_visibility_and_N(visible, model.P)
         model.optimizer.step(slab.grads(model))

@@ -228,8 +228,8 @@ int gslic_rasterize_backward(
  *
  * The single-GPU fast path has depth too: gslic_rasterize_forward_depth_capacity (capacity / graph mode), gslic_rasterize_backward_depth_adam
  * (fused Adam) and gslic_depth_l1_loss_forward_backward (the loss) below.
- * Not covered by depth (unchanged, colour only): the N-GPU colour exchange (gslic_rasterize_backward_rgb*), the camera-pose gradient
- * (gslic_rasterize_backward_camera) and the LibTorch drop-in shim.
+ * The camera-pose gradient has depth too: gslic_rasterize_backward_depth_camera (behind gslic_rasterize_backward_camera, below).
+ * Not covered by depth (unchanged, colour only): the N-GPU colour exchange (gslic_rasterize_backward_rgb*) and the LibTorch drop-in shim.
  */
 int gslic_rasterize_forward_depth(
     const gslic_raster_params* prm,
@@ -446,6 +446,26 @@ int gslic_rasterize_backward_camera(
     const float* scales, const float* rotations, const float* cov3D_precomp,
     const float* viewmatrix, const float* projmatrix, const float* cam_pos, const int32_t* radii,
     char* geom_buffer, char* binning_buffer, char* img_buffer, char* sample_buffer, const float* dL_dpix,
+    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+    float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_erank,
+    float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream);
+
+/* gslic_rasterize_backward_depth_camera — gslic_rasterize_backward_depth plus the three camera gradients of gslic_rasterize_backward_camera, for a
+ * loss on colour AND depth (buffers of gslic_rasterize_forward_depth).  The depth reaches the camera through the 2D quantities (its share is inside
+ * dL_dmean2D / dL_dconic / dL_dopacity, so all three camera outputs carry it) and directly through the view-space depth
+ * z = V[2] x + V[6] y + V[10] z + V[14]:  dL_dviewmatrix[2, 6, 10, 14] += sum_i dL/dz_i (x_i, y_i, z_i, 1), added last.  dL_dprojmatrix and dL_dcampos
+ * get no direct term.  The ten per-Gaussian outputs are gslic_rasterize_backward_depth's; dL_ddepth = 0 gives gslic_rasterize_backward_camera's
+ * results bit for bit.  View row 3 and projection row 2 are exact zeros; the sums are reduced in a fixed order (bit-reproducible).
+ * A NULL camera output, dL_ddepth == NULL, no_color = 1, SH degree > 3 or buffers of a colour-only forward: GSLIC_ERR_INVALID_ARG before any
+ * device work.  P == 0: the three camera outputs are zeroed.  After a capacity-mode forward that overflowed, the per-Gaussian outputs are
+ * left untouched and the three camera outputs are zeros.
+ */
+int gslic_rasterize_backward_depth_camera(
+    const gslic_raster_params* prm, int32_t R, int32_t B,
+    const float* background, const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+    const float* scales, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix, const float* cam_pos, const int32_t* radii,
+    char* geom_buffer, char* binning_buffer, char* img_buffer, char* sample_buffer, const float* dL_dpix, const float* dL_ddepth,
     float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
     float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_erank,
     float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream);

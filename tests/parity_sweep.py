@@ -1,6 +1,8 @@
 """Randomised HIP-vs-oracle parity sweep (run on the MI355X: `python tests/parity_sweep.py [n_cases] [seed]`).  Draws scene kind, size,
 image shape (ragged on purpose), SH degree and seeds; checks the integer stages bit-exactly and images / gradients with the bars of
-tests/test_parity_gpu.py.  A one-off confidence run, not part of the test suite (the oracle needs seconds per case)."""
+tests/test_parity_gpu.py.  Next to each case it prints, per gradient, the worst stratum ratio of the row-wise comparison (tests/rowwise.py:
+HIP error / fp32-oracle error per decade of row magnitude, both against the fp64 oracle) — printed, not asserted.
+A one-off confidence run, not part of the test suite (the oracle needs seconds per case)."""
 import os
 import sys
 
@@ -19,6 +21,8 @@ def main(n_cases, seed):
     from oracle.oracle import Oracle, build
     build()
     orc = Oracle(np.float32)
+    orc64 = Oracle(np.float64)
+    import rowwise
     rng = np.random.default_rng(seed)
     bad = 0
     for c in range(n_cases):
@@ -30,6 +34,7 @@ def main(n_cases, seed):
         ref = orc.forward(sc, camd)
         got = hip_forward(raw, cam, export=("tiles_touched", "sorted_keys", "point_list", "ranges"))
         tag = f"case {c}: {kind} P={P} {W}x{H} deg={deg} seed={s} R={got['R']}"
+        strata = ""
         try:
             d = got["dbg"]
             assert got["R"] == ref["num_rendered"], "R"
@@ -41,13 +46,16 @@ def main(n_cases, seed):
             dL = pixel_grad(H, W, seed=1)
             g = hip_backward(got, dL)
             rg = orc.backward(sc, camd, ref, dL.numpy())
+            ref64 = orc64.forward(sc, camd)
+            rg64 = orc64.backward(sc, camd, ref64, dL.numpy())
+            strata = "  rowwise: " + rowwise.worst_line(rowwise.compare(g, rg, rg64, (ref["pre"]["radii"] > 0) & (ref64["pre"]["radii"] > 0), P))
             for k in ("dL_dmean3D", "dL_dopacity", "dL_ddc", "dL_dsh", "dL_dscale"):
                 if rg[k].size:
                     assert_close_flips(g[k].reshape(rg[k].shape), rg[k], 1e-4, k, flip_bound=2e-2)
-            print("ok  ", tag, flush=True)
+            print("ok  ", tag + strata, flush=True)
         except AssertionError as ex:
             bad += 1
-            print("FAIL", tag, str(ex)[:200], flush=True)
+            print("FAIL", tag + strata, str(ex)[:200], flush=True)
     print("sweep done:", n_cases - bad, "ok,", bad, "failed")
     return bad
 

@@ -1,6 +1,7 @@
 """HIP path vs the REFERENCE's own kernels (oracle/_ref/libref_hip.so) on the same MI355X and the same inputs: one function that
 runs both and returns every count the parity gate needs — integer-stage mismatches, the exact number of elements over the 1e-4
-bar, the maximum error — for the fast and the strict arithmetic of the blend kernels.  Shared by
+bar, the maximum error, and (scenes small enough for the CPU oracle) the worst stratum ratio of the row-wise comparison of tests/rowwise.py —
+for the fast and the strict arithmetic of the blend kernels.  Shared by
 tests/test_fullsize_reference_gpu.py (asserts) and tests/parity_report.py (prints / writes profiles/*parity*.json).
 Test infrastructure: imports oracle/ (the checker)."""
 import numpy as np
@@ -80,6 +81,16 @@ def conditioning_probe(st, sc, camd, dL, scale_modifier, lambda_erank=0.0, ref_r
             st[k].pop("_over_idx", None); st[k].pop("_scale", None); st[k].pop("_got_over", None)
 
 
+def _fp64_rows(sc, camd, dL, scale_modifier):
+    """(the double-precision oracle's gradients, its visibility mask) on the inputs of compare()."""
+    from oracle.oracle import Oracle, build
+    build()
+    o = Oracle(np.float64)
+    sc = dict(sc, scale_modifier=scale_modifier)
+    f = o.forward(sc, camd)
+    return o.backward(sc, camd, f, dL), f["pre"]["radii"] > 0
+
+
 PATH_KERNELS = {"atomic": ("tile_hist", "tile_scan", "tile_bin"), "radix": ("sort_hist", "sort_scatter", "finalize_lists")}
 
 
@@ -131,6 +142,7 @@ def compare(kind, P, W, H, deg, seed, modes=("fast", "strict"), backward=True, v
         o[perm] = a
         return o
 
+    rows64 = None
     prev_binning = _lib.set_binning_mode(binning)
     try:
         for mode in modes:
@@ -172,6 +184,15 @@ def compare(kind, P, W, H, deg, seed, modes=("fast", "strict"), backward=True, v
                         if k == "dL_drot":   # unnormalised-quaternion gradient: scale of the chain it belongs to (as test_vs_reference_kernels_gpu.py)
                             scale = max(float(np.abs(ref["dL_drot"]).max()), float(np.abs(ref["dL_dscale"]).max() * sc["scales"].max()), 1e-30)   # (a view that sees nothing: all zeros)
                         st[k] = _err_stats(unperm(g[k]), ref[k], scale, keep_over=(mode == "strict" and P <= PROBE_MAX_P))
+                    if P <= PROBE_MAX_P:
+                        # reported next to the max-abs figures, never asserted: the worst stratum ratio of the row-wise comparison (tests/rowwise.py) —
+                        # HIP error / the reference run's error per decade of row magnitude, both against the double-precision oracle
+                        if rows64 is None:
+                            rows64 = _fp64_rows(sc, camd, dL.numpy(), scale_modifier)
+                        import rowwise
+                        cmp = rowwise.compare({k: unperm(g[k]) for k in GRADS}, ref, rows64[0], vis & rows64[1], P, GRADS)
+                        for k, best in rowwise.worst_per_tensor(cmp, ("median", "p90") if mode == "strict" else ("median",)).items():
+                            st[k]["rowwise_worst"] = [float(f"{best[0]:.3g}"), int(best[1]), best[2]]
                     if mode == "strict" and P <= PROBE_MAX_P:
                         # (only when an element is over the bar: further runs of the reference's kernels, whose atomics make every run a slightly
                         # different answer — the element counts when it is over the bar against every one of them)
@@ -284,6 +305,8 @@ def summarize(res):
         for k in GRADS:
             if k in st:
                 ill = f" (ill-conditioned in fp32: {st[k]['over_ill_conditioned']}, fp32 vs fp64 there {st[k]['fp32_vs_fp64_at_over']}, HIP vs fp64 {st[k].get('hip_vs_fp64_at_over')}, reference vs fp64 {st[k].get('ref_vs_fp64_at_over')}" + (f"; against {len(st[k]['err_per_run_at_over'])} runs of the reference's atomics the first of them is {st[k]['err_per_run_at_over']} away: {st[k]['over_within_other_run']} within 1e-4 of another run, {st[k].get('over_hip_closer_to_fp64', 0)} closer to fp64 than the reference" if "over_within_other_run" in st[k] else "") + ")" if "over_ill_conditioned" in st[k] else ""
-                parts.append(f"{k} over={st[k]['over']}/{st[k]['n']} max={st[k]['max_rel']:.2e}{ill}")
+                rw_ = st[k].get("rowwise_worst")
+                rw_ = "" if rw_ is None else (f" rowwise x{rw_[0]:.2f}@1e-{rw_[1]}/{rw_[2]}" if rw_[1] >= 0 else " rowwise -")
+                parts.append(f"{k} over={st[k]['over']}/{st[k]['n']} max={st[k]['max_rel']:.2e}{rw_}{ill}")
         lines.append(f"  [{mode}] " + "  ".join(parts))
     return "\n".join(lines)

@@ -79,39 +79,29 @@ def lib():
     L.gslic_img_bytes_depth.argtypes = [i32, i32]
     L.gslic_binning_bytes_depth.argtypes = [i32]
     L.gslic_sample_bytes_depth.argtypes = [i32]
-    L.gslic_rasterize_forward_depth_capacity.argtypes = (
-        [ctypes.POINTER(RasterParams)] + [vp, ctypes.c_size_t] * 4 + [vp] * 12 + [vp, vp, vp, vp] +
-        [ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp])
-    L.gslic_rasterize_backward_depth_adam.argtypes = (
-        [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp, vp] + [vp] * 6 + [f32, ctypes.POINTER(AdamFused), vp])
     L.gslic_depth_l1_loss_partials_count.restype = ctypes.c_int64
     L.gslic_depth_l1_loss_partials_count.argtypes = [i32, i32]
     L.gslic_depth_l1_loss_forward_backward.argtypes = [i32, i32, f32, vp, vp, vp, vp, vp, vp]
-    L.gslic_rasterize_forward.argtypes = (
-        [ctypes.POINTER(RasterParams)] + [ALLOC_FN, vp] * 4 + [vp] * 12 + [vp, vp, vp] +
-        [ctypes.POINTER(i32), ctypes.POINTER(i32), vp])
-    L.gslic_rasterize_forward_capacity.argtypes = (
-        [ctypes.POINTER(RasterParams)] + [vp, ctypes.c_size_t] * 4 + [vp] * 12 + [vp, vp, vp] +
-        [ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp])
-    L.gslic_rasterize_backward.argtypes = (
-        [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp] + [vp] * 10 + [f32, vp])
-    L.gslic_rasterize_forward_depth.argtypes = (
-        [ctypes.POINTER(RasterParams)] + [ALLOC_FN, vp] * 4 + [vp] * 12 + [vp, vp, vp, vp] +
-        [ctypes.POINTER(i32), ctypes.POINTER(i32), vp])
-    L.gslic_rasterize_backward_depth.argtypes = (
-        [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp, vp] + [vp] * 10 + [f32, vp])
-    L.gslic_rasterize_backward_adam.argtypes = (
-        [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp] + [vp] * 6 + [f32, ctypes.POINTER(AdamFused), vp])
-    L.gslic_rasterize_backward_camera.argtypes = (
-        [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp] + [vp] * 10 + [f32, vp, vp, vp, vp])
-    L.gslic_rasterize_backward_depth_camera.argtypes = (
-        [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp, vp] + [vp] * 10 + [f32, vp, vp, vp, vp])
-    L.gslic_rasterize_backward_rgb.argtypes = (
-        [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp] + [vp] * 5 + [f32, vp])
-    L.gslic_rasterize_backward_rgb_rows.argtypes = (
-        [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp] + [vp] * 5 + [f32, i32, i32, i32, vp])
-    L.gslic_rasterize_backward_rgb_payload.argtypes = (
-        [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 12 + [vp] * 4 + [vp] + [vp] * 5 + [f32, vp, vp, vp])
+    # the rasterize entry points, from the pieces their signatures share (include/gslic_hip.h)
+    prm, counts, adam = ctypes.POINTER(RasterParams), [ctypes.POINTER(i32), ctypes.POINTER(i32)], ctypes.POINTER(AdamFused)
+    inputs = [vp] * 12                                 # background ... cam_pos (the backward: radii in place of opacities)
+    fwd_head = [prm] + [ALLOC_FN, vp] * 4 + inputs     # four (allocator, context) pairs: geom, binning, img, sample
+    cap_head = [prm] + [vp, ctypes.c_size_t] * 4 + inputs   # four (buffer, bytes) pairs
+    bwd_head = [prm, i32, i32] + inputs + [vp] * 4     # R, B, the inputs, the four buffers: 19 arguments; dL_dpix (and dL_ddepth) follow
+    ten, six, five = [vp] * 10 + [f32], [vp] * 6 + [f32], [vp] * 5 + [f32]   # gradient outputs (all / fused Adam / dL_drgb mode), lambda_erank
+    L.gslic_rasterize_forward.argtypes = fwd_head + [vp] * 3 + counts + [vp]   # out_color, out_final_T, radii; R, B; stream
+    L.gslic_rasterize_forward_depth.argtypes = fwd_head + [vp] * 4 + counts + [vp]   # + out_depth
+    L.gslic_rasterize_forward_capacity.argtypes = cap_head + [vp] * 3 + counts + [vp, vp]   # + status
+    L.gslic_rasterize_forward_depth_capacity.argtypes = cap_head + [vp] * 4 + counts + [vp, vp]
+    L.gslic_rasterize_backward.argtypes = bwd_head + [vp] + ten + [vp]
+    L.gslic_rasterize_backward_depth.argtypes = bwd_head + [vp, vp] + ten + [vp]
+    L.gslic_rasterize_backward_adam.argtypes = bwd_head + [vp] + six + [adam, vp]
+    L.gslic_rasterize_backward_depth_adam.argtypes = bwd_head + [vp, vp] + six + [adam, vp]
+    L.gslic_rasterize_backward_camera.argtypes = bwd_head + [vp] + ten + [vp] * 3 + [vp]
+    L.gslic_rasterize_backward_depth_camera.argtypes = bwd_head + [vp, vp] + ten + [vp] * 3 + [vp]
+    L.gslic_rasterize_backward_rgb.argtypes = bwd_head + [vp] + five + [vp]
+    L.gslic_rasterize_backward_rgb_rows.argtypes = bwd_head + [vp] + five + [i32, i32, i32, vp]
+    L.gslic_rasterize_backward_rgb_payload.argtypes = bwd_head + [vp] + five + [vp, vp, vp]
     L.gslic_sh_grad_from_rgb_adam_all.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, vp, ctypes.c_int64, vp, ctypes.POINTER(AdamFused), vp, vp, vp, vp,
                                                   ctypes.c_int64, vp]
     L.gslic_sh_grad_from_rgb.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, ctypes.c_int64, vp]

@@ -460,32 +460,42 @@ static int known_depth(const void* flags)   // 1: a depth forward, 0: a colour-o
     return -1;
 }
 
-static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn geom_alloc, void* geom_ctx, gslic_alloc_fn binning_alloc,
-                            void* binning_ctx, gslic_alloc_fn img_alloc, void* img_ctx, gslic_alloc_fn sample_alloc,
-                            void* sample_ctx, const ForwardCapacity* cap, const float* background, const float* means3D, const float* dc, const float* shs,
-                            const float* colors_precomp, const float* opacities, const float* scales, const float* rotations,
-                            const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* cam_pos,
-                            float* out_color, float* out_final_T, int32_t* radii, int32_t* num_rendered, int32_t* num_buckets,
-                            void* stream, float* out_depth = nullptr, bool depth = false)
+// One forward call, filled by field name by the extern "C" wrappers.  Value-initialised ({}) it is "allocator mode, colour only": a wrapper sets
+// the four allocator pairs OR cap (capacity mode), and out_depth + depth for the depth entry points.
+struct ForwardCall {
+    const gslic_raster_params* prm;
+    gslic_alloc_fn geom_alloc, binning_alloc, img_alloc, sample_alloc;
+    void *geom_ctx, *binning_ctx, *img_ctx, *sample_ctx;
+    const ForwardCapacity* cap;
+    const float *means3D, *dc, *shs, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp, *viewmatrix, *projmatrix, *cam_pos;
+    float *out_color, *out_final_T, *out_depth;
+    int32_t *radii, *num_rendered, *num_buckets;
+    bool depth;
+    void* stream;
+};
+
+static int rasterize_forward_impl(const ForwardCall& c)
 {
-    (void)background;
+    const gslic_raster_params* const prm = c.prm;
+    const ForwardCapacity* const cap = c.cap;
+    const bool depth = c.depth;
     GS_TRY(check_params(prm));
-    if (!num_rendered || !num_buckets) return set_error(GSLIC_ERR_INVALID_ARG, "num_rendered / num_buckets is NULL");
-    *num_rendered = 0;
-    *num_buckets = 0;
+    if (!c.num_rendered || !c.num_buckets) return set_error(GSLIC_ERR_INVALID_ARG, "num_rendered / num_buckets is NULL");
+    *c.num_rendered = 0;
+    *c.num_buckets = 0;
     const int P = prm->P;
     if (P == 0) return GSLIC_OK;  // rasterize_points.cu:110
     if (depth && prm->no_color)
         return set_error(GSLIC_ERR_INVALID_ARG, "depth forward: no_color = 1 (the depth is blended with the colour and needs its checkpoints)");
-    if (depth && !out_depth) return set_error(GSLIC_ERR_INVALID_ARG, "depth forward: out_depth is NULL");
-    if (colors_precomp || cov3D_precomp)
+    if (depth && !c.out_depth) return set_error(GSLIC_ERR_INVALID_ARG, "depth forward: out_depth is NULL");
+    if (c.colors_precomp || c.cov3D_precomp)
         return set_error(GSLIC_ERR_UNSUPPORTED, "colors_precomp / cov3D_precomp are not supported (the reference host always passes empty tensors)");
-    if (!cap && (!geom_alloc || !binning_alloc || !img_alloc || (!prm->no_color && !sample_alloc)))
+    if (!cap && (!c.geom_alloc || !c.binning_alloc || !c.img_alloc || (!prm->no_color && !c.sample_alloc)))
         return set_error(GSLIC_ERR_INVALID_ARG, "allocator callback is NULL");
-    if (!means3D || !dc || !opacities || !scales || !rotations || !viewmatrix || !projmatrix || !cam_pos || !out_final_T || !radii ||
-        (!prm->no_color && !out_color) || (prm->M > 0 && !shs))
+    if (!c.means3D || !c.dc || !c.opacities || !c.scales || !c.rotations || !c.viewmatrix || !c.projmatrix || !c.cam_pos || !c.out_final_T || !c.radii ||
+        (!prm->no_color && !c.out_color) || (prm->M > 0 && !c.shs))
         return set_error(GSLIC_ERR_INVALID_ARG, "required tensor pointer is NULL");
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = (hipStream_t)c.stream;
     const bool no_color = prm->no_color != 0;
     int gx, gy;
     const int T = tile_grid(prm->width, prm->height, gx, gy);
@@ -496,10 +506,10 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
     if (cap && (cap->geom_bytes < geom_bytes || cap->img_bytes < img_bytes || !cap->geom || !cap->img || !cap->binning ||
                 (!no_color && !cap->sample) || !cap->status_out))
         return set_error(GSLIC_ERR_INVALID_ARG, "capacity mode: geometry / image buffer too small (need %zu / %zu bytes) or a NULL buffer", geom_bytes, img_bytes);
-    char* geom_base = cap ? cap->geom : geom_alloc(geom_ctx, geom_bytes);
+    char* geom_base = cap ? cap->geom : c.geom_alloc(c.geom_ctx, geom_bytes);
     if (!geom_base) return set_error(GSLIC_ERR_ALLOC, "geometry allocator returned NULL for %zu bytes", geom_bytes);
     GeomState geom = GeomState::carve(align256(geom_base), (size_t)P, nullptr);
-    char* img_base = cap ? cap->img : img_alloc(img_ctx, img_bytes);
+    char* img_base = cap ? cap->img : c.img_alloc(c.img_ctx, img_bytes);
     if (!img_base) return set_error(GSLIC_ERR_ALLOC, "image allocator returned NULL for %zu bytes", img_bytes);
     ImageState img = ImageState::carve(align256(img_base), (size_t)T, nullptr, depth);
 
@@ -510,9 +520,9 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
     pa.focal_x = prm->width / (2.0f * prm->tan_fovx);
     pa.limx_neg = prm->limx_neg; pa.limx_pos = prm->limx_pos; pa.limy_neg = prm->limy_neg; pa.limy_pos = prm->limy_pos;
     pa.scale_modifier = prm->scale_modifier; pa.prefiltered = prm->prefiltered; pa.no_color = prm->no_color; pa.raw = prm->raw_params;
-    pa.means = means3D; pa.scales = scales; pa.rots = rotations; pa.opac = opacities; pa.dc = dc; pa.shs = shs;
-    pa.view = viewmatrix; pa.proj = projmatrix; pa.campos = cam_pos;
-    pa.radii = radii; pa.rec = geom.rec; pa.tiles_touched = geom.tiles_touched; pa.depth_keys = nullptr; pa.flags = geom.flags; pa.ranges = img.ranges;
+    pa.means = c.means3D; pa.scales = c.scales; pa.rots = c.rotations; pa.opac = c.opacities; pa.dc = c.dc; pa.shs = c.shs;
+    pa.view = c.viewmatrix; pa.proj = c.projmatrix; pa.campos = c.cam_pos;
+    pa.radii = c.radii; pa.rec = geom.rec; pa.tiles_touched = geom.tiles_touched; pa.depth_keys = nullptr; pa.flags = geom.flags; pa.ranges = img.ranges;
     GS_TRY(launch_preprocess(pa, s));
     DEBUG_SYNC(prm, s);
 
@@ -539,7 +549,7 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
 
     size_t bin_bytes;
     BinningState::carve(nullptr, (size_t)R, end_bit, no_color, &bin_bytes, depth);
-    char* bin_base = cap ? cap->binning : binning_alloc(binning_ctx, bin_bytes);
+    char* bin_base = cap ? cap->binning : c.binning_alloc(c.binning_ctx, bin_bytes);
     if (!bin_base) return set_error(GSLIC_ERR_ALLOC, "binning allocator returned NULL for %zu bytes", bin_bytes);
     BinningState bin = BinningState::carve(align256(bin_base), (size_t)R, end_bit, no_color, nullptr, depth);
 
@@ -608,7 +618,7 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
         }
         size_t smp_bytes;
         SampleState::carve(nullptr, (size_t)B, &smp_bytes, depth);
-        char* smp_base = cap ? cap->sample : sample_alloc(sample_ctx, smp_bytes);
+        char* smp_base = cap ? cap->sample : c.sample_alloc(c.sample_ctx, smp_bytes);
         if (!smp_base) return set_error(GSLIC_ERR_ALLOC, "sample allocator returned NULL for %zu bytes", smp_bytes);
         smp = SampleState::carve(align256(smp_base), (size_t)B, nullptr, depth);
     }
@@ -617,8 +627,8 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
     ra.W = prm->width; ra.H = prm->height; ra.gx = gx; ra.gy = gy; ra.no_color = prm->no_color;
     ra.ranges = img.ranges; ra.point_list = bin.point_list(); ra.rec = geom.rec; ra.bucket_offsets = img.bucket_offsets;
     ra.bucket_to_tile = smp.bucket_to_tile; ra.ckpt = smp.ckpt; ra.hit = smp.hit; ra.pix_final = img.pix_final; ra.max_contrib = img.max_contrib;
-    ra.out_color = out_color; ra.out_final_T = out_final_T; ra.capB = B; ra.status = geom.flags; ra.tail4_from = T;   // (launch_render_fwd decides)
-    ra.out_depth = depth ? out_depth : nullptr; ra.ckpt_depth = smp.ckpt_depth; ra.pix_depth = img.pix_depth;   // (NULL without depth)
+    ra.out_color = c.out_color; ra.out_final_T = c.out_final_T; ra.capB = B; ra.status = geom.flags; ra.tail4_from = T;   // (launch_render_fwd decides)
+    ra.out_depth = depth ? c.out_depth : nullptr; ra.ckpt_depth = smp.ckpt_depth; ra.pix_depth = img.pix_depth;   // (NULL without depth)
     GS_TRY(launch_render_fwd(ra, s));
     note_depth(geom.flags, depth);
     DEBUG_SYNC(prm, s);
@@ -629,8 +639,8 @@ static int rasterize_forward_impl(const gslic_raster_params* prm, gslic_alloc_fn
         GS_HIP(hipGetLastError());
     }
 
-    *num_rendered = (int32_t)R;
-    *num_buckets = (int32_t)B;
+    *c.num_rendered = (int32_t)R;
+    *c.num_buckets = (int32_t)B;
     return GSLIC_OK;
 }
 
@@ -660,6 +670,19 @@ size_t gslic_scratch_round_up(size_t n)
     }
     return (n + g - 1) / g * g;
 }
+// The wrappers' parameters carry the fields' names: what every variant shares is copied BY NAME, once (a renamed or missing parameter does not
+// compile, and two pointers cannot change places); each wrapper then sets, by name, only what is its own.
+#define GS_FORWARD_SHARED(c)                                                                                                               \
+    c.prm = prm; c.means3D = means3D; c.dc = dc; c.shs = shs; c.colors_precomp = colors_precomp; c.opacities = opacities; c.scales = scales;       \
+    c.rotations = rotations; c.cov3D_precomp = cov3D_precomp; c.viewmatrix = viewmatrix; c.projmatrix = projmatrix; c.cam_pos = cam_pos;           \
+    c.out_color = out_color; c.out_final_T = out_final_T; c.radii = radii; c.stream = stream
+#define GS_FORWARD_ALLOCATORS(c)                                                                                                           \
+    c.geom_alloc = geom_alloc; c.geom_ctx = geom_ctx; c.binning_alloc = binning_alloc; c.binning_ctx = binning_ctx; c.img_alloc = img_alloc;       \
+    c.img_ctx = img_ctx; c.sample_alloc = sample_alloc; c.sample_ctx = sample_ctx; c.num_rendered = num_rendered; c.num_buckets = num_buckets
+#define GS_FORWARD_CAPACITY(c, cap)                                                                                                        \
+    const ForwardCapacity cap{geom_buffer, binning_buffer, img_buffer, sample_buffer, geom_bytes, binning_bytes, img_bytes, sample_bytes, status}; \
+    c.cap = &cap; c.num_rendered = capacity_R; c.num_buckets = capacity_B
+
 int gslic_rasterize_forward(const gslic_raster_params* prm, gslic_alloc_fn geom_alloc, void* geom_ctx, gslic_alloc_fn binning_alloc,
                             void* binning_ctx, gslic_alloc_fn img_alloc, void* img_ctx, gslic_alloc_fn sample_alloc,
                             void* sample_ctx, const float* background, const float* means3D, const float* dc, const float* shs,
@@ -668,9 +691,9 @@ int gslic_rasterize_forward(const gslic_raster_params* prm, gslic_alloc_fn geom_
                             float* out_color, float* out_final_T, int32_t* radii, int32_t* num_rendered, int32_t* num_buckets,
                             void* stream)
 {
-    return rasterize_forward_impl(prm, geom_alloc, geom_ctx, binning_alloc, binning_ctx, img_alloc, img_ctx, sample_alloc, sample_ctx, nullptr,
-                                  background, means3D, dc, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                                  cam_pos, out_color, out_final_T, radii, num_rendered, num_buckets, stream);
+    ForwardCall c{};
+    GS_FORWARD_SHARED(c); GS_FORWARD_ALLOCATORS(c);
+    return rasterize_forward_impl(c);
 }
 
 int gslic_rasterize_forward_depth(const gslic_raster_params* prm, gslic_alloc_fn geom_alloc, void* geom_ctx, gslic_alloc_fn binning_alloc,
@@ -681,9 +704,10 @@ int gslic_rasterize_forward_depth(const gslic_raster_params* prm, gslic_alloc_fn
                                   float* out_color, float* out_final_T, float* out_depth, int32_t* radii, int32_t* num_rendered,
                                   int32_t* num_buckets, void* stream)
 {
-    return rasterize_forward_impl(prm, geom_alloc, geom_ctx, binning_alloc, binning_ctx, img_alloc, img_ctx, sample_alloc, sample_ctx, nullptr,
-                                  background, means3D, dc, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
-                                  cam_pos, out_color, out_final_T, radii, num_rendered, num_buckets, stream, out_depth, true);
+    ForwardCall c{};
+    GS_FORWARD_SHARED(c); GS_FORWARD_ALLOCATORS(c);
+    c.out_depth = out_depth; c.depth = true;
+    return rasterize_forward_impl(c);
 }
 
 int gslic_rasterize_forward_capacity(const gslic_raster_params* prm, char* geom_buffer, size_t geom_bytes, char* binning_buffer,
@@ -694,10 +718,9 @@ int gslic_rasterize_forward_capacity(const gslic_raster_params* prm, char* geom_
                                      float* out_color, float* out_final_T, int32_t* radii, int32_t* capacity_R, int32_t* capacity_B,
                                      uint32_t* status, void* stream)
 {
-    ForwardCapacity cap{geom_buffer, binning_buffer, img_buffer, sample_buffer, geom_bytes, binning_bytes, img_bytes, sample_bytes, status};
-    return rasterize_forward_impl(prm, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &cap, background, means3D, dc, shs,
-                                  colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, out_color,
-                                  out_final_T, radii, capacity_R, capacity_B, stream);
+    ForwardCall c{};
+    GS_FORWARD_SHARED(c); GS_FORWARD_CAPACITY(c, cap);
+    return rasterize_forward_impl(c);
 }
 
 int gslic_rasterize_forward_depth_capacity(const gslic_raster_params* prm, char* geom_buffer, size_t geom_bytes, char* binning_buffer,
@@ -708,36 +731,63 @@ int gslic_rasterize_forward_depth_capacity(const gslic_raster_params* prm, char*
                                            float* out_color, float* out_final_T, float* out_depth, int32_t* radii, int32_t* capacity_R,
                                            int32_t* capacity_B, uint32_t* status, void* stream)
 {
-    ForwardCapacity cap{geom_buffer, binning_buffer, img_buffer, sample_buffer, geom_bytes, binning_bytes, img_bytes, sample_bytes, status};
-    return rasterize_forward_impl(prm, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &cap, background, means3D, dc, shs,
-                                  colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, out_color,
-                                  out_final_T, radii, capacity_R, capacity_B, stream, out_depth, true);
+    ForwardCall c{};
+    GS_FORWARD_SHARED(c); GS_FORWARD_CAPACITY(c, cap);
+    c.out_depth = out_depth; c.depth = true;
+    return rasterize_forward_impl(c);
+}
+#undef GS_FORWARD_SHARED
+#undef GS_FORWARD_ALLOCATORS
+#undef GS_FORWARD_CAPACITY
+
+// gslic_adam_fused groups [g0, g1) -> the kernels' AdamFusedArgs (adam == NULL: the update is off)
+static void adam_args(AdamFusedArgs& a, const gslic_adam_fused* adam, int g0, int g1)
+{
+    memset(&a, 0, sizeof(a));
+    if (!adam) return;
+    for (int g = g0; g < g1; g++) { a.p[g] = adam->param[g]; a.m[g] = adam->exp_avg[g]; a.v[g] = adam->exp_avg_sq[g]; a.lr[g] = adam->lr[g]; }
+    a.b1 = adam->b1; a.b2 = adam->b2; a.eps = adam->eps; a.on = 1;
 }
 
-static int rasterize_backward_impl(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
-                             const float* dc, const float* shs, const float* colors_precomp, const float* scales,
-                             const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
-                             const float* cam_pos, const int32_t* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
-                             char* sample_buffer, const float* dL_dpix, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
-                             float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale,
-                             float* dL_drot, float lambda_erank, const gslic_adam_fused* adam, float* const dL_dcam[3], void* stream,
-                             float* dL_drgb = nullptr, int32_t row_begin = 0, int32_t row_end = -1, bool skip_blend = false, uint8_t* vis_out = nullptr,
-                             float* campos_out = nullptr, const float* dL_ddepth = nullptr)
+// One backward call, filled by field name by the extern "C" wrappers.  Value-initialised ({}) it is "colour only, all rows, nothing optional":
+// no depth gradient, no gradient output, no fused Adam, no camera gradient, no dL_drgb, rows [0, P), the blend backward runs.
+struct BackwardCall {
+    const gslic_raster_params* prm;
+    int32_t R, B;
+    const float *means3D, *dc, *shs, *colors_precomp, *scales, *rotations, *cov3D_precomp, *viewmatrix, *projmatrix, *cam_pos;
+    const int32_t* radii;
+    char *geom_buffer, *binning_buffer, *img_buffer, *sample_buffer;
+    const float *dL_dpix, *dL_ddepth;   // dL_ddepth != NULL: the depth backward (on a depth forward's buffers)
+    float *dL_dmean2D, *dL_dconic, *dL_dopacity, *dL_dcolor, *dL_dmean3D, *dL_dcov3D, *dL_ddc, *dL_dsh, *dL_dscale, *dL_drot;
+    float lambda_erank;
+    const gslic_adam_fused* adam;
+    float* dL_dcam[3];                  // dL_dviewmatrix [16], dL_dprojmatrix [16], dL_dcampos [3]: all three or none
+    float* dL_drgb;
+    int32_t row_begin, row_end = -1;    // (row_end < 0: P)
+    bool skip_blend;
+    uint8_t* vis_out;
+    float* campos_out;
+    void* stream;
+};
+
+static int rasterize_backward_impl(const BackwardCall& c)
 {
-    (void)background; (void)dc;
+    const gslic_raster_params* const prm = c.prm;
+    const gslic_adam_fused* const adam = c.adam;
+    const bool dL_dcam = c.dL_dcam[0] != nullptr;
     GS_TRY(check_params(prm));
     const int P = prm->P;
     if (P == 0) return GSLIC_OK;  // rasterize_points.cu:203
-    if (colors_precomp || cov3D_precomp)
+    if (c.colors_precomp || c.cov3D_precomp)
         return set_error(GSLIC_ERR_UNSUPPORTED, "colors_precomp / cov3D_precomp are not supported");
     if (prm->no_color) return set_error(GSLIC_ERR_INVALID_ARG, "backward of a no_color forward is undefined (no checkpoints were stored)");
-    if (R < 0 || B < 0) return set_error(GSLIC_ERR_INVALID_ARG, "negative R / B");
-    if (!means3D || !scales || !rotations || !viewmatrix || !projmatrix || !cam_pos || !radii || !geom_buffer || !binning_buffer ||
-        !img_buffer || !sample_buffer || !dL_dpix || (prm->M > 0 && !shs))
+    if (c.R < 0 || c.B < 0) return set_error(GSLIC_ERR_INVALID_ARG, "negative R / B");
+    if (!c.means3D || !c.scales || !c.rotations || !c.viewmatrix || !c.projmatrix || !c.cam_pos || !c.radii || !c.geom_buffer || !c.binning_buffer ||
+        !c.img_buffer || !c.sample_buffer || !c.dL_dpix || (prm->M > 0 && !c.shs))
         return set_error(GSLIC_ERR_INVALID_ARG, "required tensor pointer is NULL");
-    if (!adam && !dL_drgb && (!dL_dopacity || !dL_dmean3D || !dL_ddc || !dL_dscale || !dL_drot || (prm->M > 0 && !dL_dsh)))
+    if (!adam && !c.dL_drgb && (!c.dL_dopacity || !c.dL_dmean3D || !c.dL_ddc || !c.dL_dscale || !c.dL_drot || (prm->M > 0 && !c.dL_dsh)))
         return set_error(GSLIC_ERR_INVALID_ARG, "required gradient output pointer is NULL");
-    if (dL_drgb && (adam || dL_ddc || dL_dsh || !dL_dopacity || !dL_dmean3D || !dL_dscale || !dL_drot))
+    if (c.dL_drgb && (adam || c.dL_ddc || c.dL_dsh || !c.dL_dopacity || !c.dL_dmean3D || !c.dL_dscale || !c.dL_drot))
         return set_error(GSLIC_ERR_INVALID_ARG, "dL_drgb mode: dL_ddc / dL_dsh / adam must be NULL, the four other parameter gradients are required");
     if (adam) {
         if (!prm->raw_params) return set_error(GSLIC_ERR_INVALID_ARG, "fused Adam needs raw_params = 1 (it updates the raw parameters)");
@@ -745,19 +795,19 @@ static int rasterize_backward_impl(const gslic_raster_params* prm, int32_t R, in
             if (g == 2 && prm->M == 0) continue;
             if (!adam->param[g] || !adam->exp_avg[g] || !adam->exp_avg_sq[g]) return set_error(GSLIC_ERR_INVALID_ARG, "fused Adam: group %d has a NULL pointer", g);
         }
-        if (adam->param[0] != means3D || adam->param[4] != scales || adam->param[5] != rotations || (prm->M > 0 && adam->param[2] != shs))
+        if (adam->param[0] != c.means3D || adam->param[4] != c.scales || adam->param[5] != c.rotations || (prm->M > 0 && adam->param[2] != c.shs))
             return set_error(GSLIC_ERR_INVALID_ARG, "fused Adam: param[] must alias the tensors passed as means3D / shs / scales / rotations");
     }
     {   // (checked before anything is enqueued: a bad row range must not leave a blend backward behind)
-        const int re = row_end < 0 ? P : row_end;
-        if (row_begin < 0 || re > P || row_begin > re || (row_begin & 63))
-            return set_error(GSLIC_ERR_INVALID_ARG, "row range [%d, %d) of %d Gaussians (row_begin must be a multiple of 64)", row_begin, re, P);
+        const int re = c.row_end < 0 ? P : c.row_end;
+        if (c.row_begin < 0 || re > P || c.row_begin > re || (c.row_begin & 63))
+            return set_error(GSLIC_ERR_INVALID_ARG, "row range [%d, %d) of %d Gaussians (row_begin must be a multiple of 64)", c.row_begin, re, P);
     }
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = (hipStream_t)c.stream;
     int gx, gy;
     const int T = tile_grid(prm->width, prm->height, gx, gy);
-    const bool depth = dL_ddepth != nullptr;
-    GeomState geom = GeomState::carve(align256(geom_buffer), (size_t)P, nullptr);
+    const bool depth = c.dL_ddepth != nullptr;
+    GeomState geom = GeomState::carve(align256(c.geom_buffer), (size_t)P, nullptr);
     if (depth) {
         // the depth arrays exist only behind a depth forward's buffers.  Known buffers: the host note; else the flag its render kernel set (one
         // 4-byte read, the stream waits for it)
@@ -771,40 +821,36 @@ static int rasterize_backward_impl(const gslic_raster_params* prm, int32_t R, in
         if (known != 1)
             return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: these buffers come from a forward that rendered no depth (use gslic_rasterize_forward_depth)");
     }
-    ImageState img = ImageState::carve(align256(img_buffer), (size_t)T, nullptr, depth);
-    BinningState bin = BinningState::carve(align256(binning_buffer), (size_t)R, sort_end_bit(T), false, nullptr, depth);
-    SampleState smp = SampleState::carve(align256(sample_buffer), (size_t)B, nullptr, depth);
+    ImageState img = ImageState::carve(align256(c.img_buffer), (size_t)T, nullptr, depth);
+    BinningState bin = BinningState::carve(align256(c.binning_buffer), (size_t)c.R, sort_end_bit(T), false, nullptr, depth);
+    SampleState smp = SampleState::carve(align256(c.sample_buffer), (size_t)c.B, nullptr, depth);
 
     RenderBwdArgs rb;
-    rb.W = prm->width; rb.H = prm->height; rb.gx = gx; rb.B = B;
+    rb.W = prm->width; rb.H = prm->height; rb.gx = gx; rb.B = c.B;
     rb.ranges = img.ranges; rb.point_list = bin.point_list(); rb.inst_slot = bin.inst_slot(); rb.rec = geom.rec;
     rb.bucket_offsets = img.bucket_offsets; rb.bucket_to_tile = smp.bucket_to_tile; rb.ckpt = smp.ckpt; rb.hit = smp.hit; rb.pix_final = img.pix_final;
-    rb.max_contrib = img.max_contrib; rb.dL_dpix = dL_dpix; rb.partials = bin.partials; rb.dead = bin.dead; rb.status = geom.flags; rb.T = T;
-    rb.dL_ddepth = dL_ddepth; rb.ckpt_depth = smp.ckpt_depth; rb.pix_depth = img.pix_depth; rb.partials_z = bin.partials_z;   // (NULL without depth)
-    if (!skip_blend) GS_TRY(launch_render_bwd(rb, s));   // (a chunked per-Gaussian backward runs the blend backward with its first chunk only)
+    rb.max_contrib = img.max_contrib; rb.dL_dpix = c.dL_dpix; rb.partials = bin.partials; rb.dead = bin.dead; rb.status = geom.flags; rb.T = T;
+    rb.dL_ddepth = c.dL_ddepth; rb.ckpt_depth = smp.ckpt_depth; rb.pix_depth = img.pix_depth; rb.partials_z = bin.partials_z;   // (NULL without depth)
+    if (!c.skip_blend) GS_TRY(launch_render_bwd(rb, s));   // (a chunked per-Gaussian backward runs the blend backward with its first chunk only)
     DEBUG_SYNC(prm, s);
 
     PreprocessBwdArgs pb;
     pb.P = P; pb.D = prm->D; pb.M = prm->M; pb.W = prm->width; pb.H = prm->height; pb.raw = prm->raw_params;
-    pb.row_begin = row_begin; pb.row_end = row_end < 0 ? P : row_end;
+    pb.row_begin = c.row_begin; pb.row_end = c.row_end < 0 ? P : c.row_end;
     pb.focal_y = prm->height / (2.0f * prm->tan_fovy);
     pb.focal_x = prm->width / (2.0f * prm->tan_fovx);
     pb.limx_neg = prm->limx_neg; pb.limx_pos = prm->limx_pos; pb.limy_neg = prm->limy_neg; pb.limy_pos = prm->limy_pos;
-    pb.scale_modifier = prm->scale_modifier; pb.lambda_erank = lambda_erank;
-    pb.means = means3D; pb.scales = scales; pb.rots = rotations; pb.dc = dc; pb.shs = shs; pb.view = viewmatrix; pb.proj = projmatrix;
-    pb.campos = cam_pos; pb.radii = radii; pb.rec = geom.rec; pb.tiles_touched = geom.tiles_touched; pb.gauss_start = geom.gauss_start; pb.partials = bin.partials; pb.dead = bin.dead;
-    pb.dL_dmean2D = dL_dmean2D; pb.dL_dconic = dL_dconic; pb.dL_dopacity = dL_dopacity; pb.dL_dcolor = dL_dcolor;
-    pb.dL_dmean3D = dL_dmean3D; pb.dL_dcov3D = dL_dcov3D; pb.dL_ddc = dL_ddc; pb.dL_dsh = dL_dsh; pb.dL_dscale = dL_dscale;
-    pb.dL_drot = dL_drot; pb.dL_drgb = dL_drgb;
-    memset(&pb.adam, 0, sizeof(pb.adam));
-    if (adam) {
-        for (int g = 0; g < 6; g++) { pb.adam.p[g] = adam->param[g]; pb.adam.m[g] = adam->exp_avg[g]; pb.adam.v[g] = adam->exp_avg_sq[g]; pb.adam.lr[g] = adam->lr[g]; }
-        pb.adam.b1 = adam->b1; pb.adam.b2 = adam->b2; pb.adam.eps = adam->eps; pb.adam.on = 1;
-    }
+    pb.scale_modifier = prm->scale_modifier; pb.lambda_erank = c.lambda_erank;
+    pb.means = c.means3D; pb.scales = c.scales; pb.rots = c.rotations; pb.dc = c.dc; pb.shs = c.shs; pb.view = c.viewmatrix; pb.proj = c.projmatrix;
+    pb.campos = c.cam_pos; pb.radii = c.radii; pb.rec = geom.rec; pb.tiles_touched = geom.tiles_touched; pb.gauss_start = geom.gauss_start; pb.partials = bin.partials; pb.dead = bin.dead;
+    pb.dL_dmean2D = c.dL_dmean2D; pb.dL_dconic = c.dL_dconic; pb.dL_dopacity = c.dL_dopacity; pb.dL_dcolor = c.dL_dcolor;
+    pb.dL_dmean3D = c.dL_dmean3D; pb.dL_dcov3D = c.dL_dcov3D; pb.dL_ddc = c.dL_ddc; pb.dL_dsh = c.dL_dsh; pb.dL_dscale = c.dL_dscale;
+    pb.dL_drot = c.dL_drot; pb.dL_drgb = c.dL_drgb;
+    adam_args(pb.adam, adam, 0, 6);
     pb.status = geom.flags;
     pb.cam_partials = nullptr; pb.cam_out = nullptr;
     pb.partials_z = depth ? bin.partials_z : nullptr;
-    pb.vis_out = vis_out; pb.campos_out = campos_out;
+    pb.vis_out = c.vis_out; pb.campos_out = c.campos_out;
     if (dL_dcam) {
         // scratch of the geometry buffer: the per-wave partial rows (128 B per wave; the generic 256-thread path writes 4 rows per block even
         // when P < 256, i.e. up to 4 ceil(P / 256) rows), the 35 reduced terms behind them
@@ -813,11 +859,43 @@ static int rasterize_backward_impl(const gslic_raster_params* prm, int32_t R, in
     }
     GS_TRY(launch_preprocess_bwd(pb, s));
     if (dL_dcam) {
-        GS_HIP(hipMemcpyAsync(dL_dcam[0], pb.cam_out, 16 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        GS_HIP(hipMemcpyAsync(dL_dcam[1], pb.cam_out + 16, 16 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        GS_HIP(hipMemcpyAsync(dL_dcam[2], pb.cam_out + 32, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        GS_HIP(hipMemcpyAsync(c.dL_dcam[0], pb.cam_out, 16 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        GS_HIP(hipMemcpyAsync(c.dL_dcam[1], pb.cam_out + 16, 16 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        GS_HIP(hipMemcpyAsync(c.dL_dcam[2], pb.cam_out + 32, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     DEBUG_SYNC(prm, s);
+    return GSLIC_OK;
+}
+
+#define GS_BACKWARD_SHARED(c)                                                                                                              \
+    c.prm = prm; c.R = R; c.B = B; c.means3D = means3D; c.dc = dc; c.shs = shs; c.colors_precomp = colors_precomp; c.scales = scales;              \
+    c.rotations = rotations; c.cov3D_precomp = cov3D_precomp; c.viewmatrix = viewmatrix; c.projmatrix = projmatrix; c.cam_pos = cam_pos;           \
+    c.radii = radii; c.geom_buffer = geom_buffer; c.binning_buffer = binning_buffer; c.img_buffer = img_buffer; c.sample_buffer = sample_buffer;   \
+    c.dL_dpix = dL_dpix; c.lambda_erank = lambda_erank; c.stream = stream
+#define GS_BACKWARD_TEN_GRADS(c)                                                                                                           \
+    c.dL_dmean2D = dL_dmean2D; c.dL_dconic = dL_dconic; c.dL_dopacity = dL_dopacity; c.dL_dcolor = dL_dcolor; c.dL_dmean3D = dL_dmean3D;           \
+    c.dL_dcov3D = dL_dcov3D; c.dL_ddc = dL_ddc; c.dL_dsh = dL_dsh; c.dL_dscale = dL_dscale; c.dL_drot = dL_drot
+#define GS_BACKWARD_RGB_GRADS(c)                                                                                                           \
+    c.dL_dopacity = dL_dopacity; c.dL_dmean3D = dL_dmean3D; c.dL_drgb = dL_drgb; c.dL_dscale = dL_dscale; c.dL_drot = dL_drot
+#define GS_BACKWARD_ADAM(c)                                                                                                                \
+    c.dL_dopacity = dL_dopacity; c.dL_dmean3D = dL_dmean3D; c.dL_ddc = dL_ddc; c.dL_dsh = dL_dsh; c.dL_dscale = dL_dscale; c.dL_drot = dL_drot;    \
+    c.adam = adam; c.vis_out = adam->visible_out
+#define GS_BACKWARD_CAMERA(c) c.dL_dcam[0] = dL_dviewmatrix; c.dL_dcam[1] = dL_dprojmatrix; c.dL_dcam[2] = dL_dcampos
+
+// what the three depth backwards check before the shared implementation (after check_params and P == 0); colour_only: the entry the message names
+static int depth_backward_checks(const gslic_raster_params* prm, const float* dL_ddepth, const char* colour_only, const char* kind)
+{
+    if (prm->no_color) return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no_color = 1 (no depth forward renders without colour)");
+    if (!dL_ddepth) return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: dL_ddepth is NULL (%s is the colour-only %sbackward)", colour_only, kind);
+    return GSLIC_OK;
+}
+// P == 0 of the two camera backwards — nothing rendered: zero gradients
+static int zero_camera_grads(float* const dL_dcam[3], void* stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    GS_HIP(hipMemsetAsync(dL_dcam[0], 0, 16 * sizeof(float), s));
+    GS_HIP(hipMemsetAsync(dL_dcam[1], 0, 16 * sizeof(float), s));
+    GS_HIP(hipMemsetAsync(dL_dcam[2], 0, 3 * sizeof(float), s));
     return GSLIC_OK;
 }
 
@@ -829,10 +907,9 @@ int gslic_rasterize_backward(const gslic_raster_params* prm, int32_t R, int32_t 
                              float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_ddc, float* dL_dsh, float* dL_dscale,
                              float* dL_drot, float lambda_erank, void* stream)
 {
-    return rasterize_backward_impl(prm, R, B, background, means3D, dc, shs, colors_precomp, scales, rotations, cov3D_precomp, viewmatrix,
-                                   projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, dL_dmean2D,
-                                   dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot,
-                                   lambda_erank, nullptr, nullptr, stream);
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_TEN_GRADS(c);
+    return rasterize_backward_impl(c);
 }
 
 int gslic_rasterize_backward_depth(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
@@ -845,12 +922,11 @@ int gslic_rasterize_backward_depth(const gslic_raster_params* prm, int32_t R, in
 {
     GS_TRY(check_params(prm));
     if (prm->P == 0) return GSLIC_OK;
-    if (prm->no_color) return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no_color = 1 (no depth forward renders without colour)");
-    if (!dL_ddepth) return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: dL_ddepth is NULL (gslic_rasterize_backward is the colour-only backward)");
-    return rasterize_backward_impl(prm, R, B, background, means3D, dc, shs, colors_precomp, scales, rotations, cov3D_precomp, viewmatrix,
-                                   projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, dL_dmean2D,
-                                   dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot,
-                                   lambda_erank, nullptr, nullptr, stream, nullptr, 0, -1, false, nullptr, nullptr, dL_ddepth);
+    GS_TRY(depth_backward_checks(prm, dL_ddepth, "gslic_rasterize_backward", ""));
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_TEN_GRADS(c);
+    c.dL_ddepth = dL_ddepth;
+    return rasterize_backward_impl(c);
 }
 
 int gslic_rasterize_backward_rgb(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
@@ -861,10 +937,9 @@ int gslic_rasterize_backward_rgb(const gslic_raster_params* prm, int32_t R, int3
                                  float* dL_dscale, float* dL_drot, float lambda_erank, void* stream)
 {
     if (!dL_drgb) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_rgb: dL_drgb is NULL");
-    return rasterize_backward_impl(prm, R, B, background, means3D, dc, shs, colors_precomp, scales, rotations, cov3D_precomp, viewmatrix,
-                                   projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, nullptr,
-                                   nullptr, dL_dopacity, nullptr, dL_dmean3D, nullptr, nullptr, nullptr, dL_dscale, dL_drot, lambda_erank,
-                                   nullptr, nullptr, stream, dL_drgb);
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_RGB_GRADS(c);
+    return rasterize_backward_impl(c);
 }
 
 int gslic_rasterize_backward_rgb_payload(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
@@ -875,10 +950,10 @@ int gslic_rasterize_backward_rgb_payload(const gslic_raster_params* prm, int32_t
                                          float* dL_dscale, float* dL_drot, float lambda_erank, uint8_t* vis_out, float* campos_out, void* stream)
 {
     if (!dL_drgb) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_rgb_payload: dL_drgb is NULL");
-    return rasterize_backward_impl(prm, R, B, background, means3D, dc, shs, colors_precomp, scales, rotations, cov3D_precomp, viewmatrix,
-                                   projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, nullptr,
-                                   nullptr, dL_dopacity, nullptr, dL_dmean3D, nullptr, nullptr, nullptr, dL_dscale, dL_drot, lambda_erank,
-                                   nullptr, nullptr, stream, dL_drgb, 0, -1, false, vis_out, campos_out);
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_RGB_GRADS(c);
+    c.vis_out = vis_out; c.campos_out = campos_out;
+    return rasterize_backward_impl(c);
 }
 
 int gslic_rasterize_backward_rgb_rows(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
@@ -890,26 +965,40 @@ int gslic_rasterize_backward_rgb_rows(const gslic_raster_params* prm, int32_t R,
                                       void* stream)
 {
     if (!dL_drgb) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_rgb_rows: dL_drgb is NULL");
-    return rasterize_backward_impl(prm, R, B, background, means3D, dc, shs, colors_precomp, scales, rotations, cov3D_precomp, viewmatrix,
-                                   projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, nullptr,
-                                   nullptr, dL_dopacity, nullptr, dL_dmean3D, nullptr, nullptr, nullptr, dL_dscale, dL_drot, lambda_erank,
-                                   nullptr, nullptr, stream, dL_drgb, row_begin, row_end, skip_blend != 0);
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_RGB_GRADS(c);
+    c.row_begin = row_begin; c.row_end = row_end; c.skip_blend = skip_blend != 0;
+    return rasterize_backward_impl(c);
+}
+
+// What the three gslic_sh_grad_from_rgb* share: the checks up to the NULL test (`null_ptr`: the caller's own set of required pointers; `more_bad` /
+// `more_names`: its own size checks and their names in the message) and the fields all three fill alike.  Returns 1 to go on, else the
+// function's result (an error, or GSLIC_OK for P == 0).
+static int sh_grad_begin(const char* fn, int32_t P, int32_t D, int32_t M, int32_t n_views, const float* means3D, const float* campos_all,
+                         const float* rgb_all, int32_t input_is_ddc, int64_t view_stride, bool more_bad, const char* more_names, bool null_ptr,
+                         ShGradFromRgbArgs& a)
+{
+    if (view_stride < 0 || (view_stride > 0 && view_stride < 3 * (int64_t)P)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: bad view_stride", fn);
+    if (P < 0 || D < 0 || D > 3 || M < 0 || n_views < 1 || more_bad) return set_error(GSLIC_ERR_INVALID_ARG, "%s: bad P / D / M / n_views%s", fn, more_names);
+    if (P == 0) return GSLIC_OK;
+    if (!means3D || !campos_all || !rgb_all || null_ptr) return set_error(GSLIC_ERR_INVALID_ARG, "%s: NULL pointer", fn);
+    a.P = P; a.D = D; a.M = M; a.n_views = n_views; a.input_is_ddc = input_is_ddc ? 1 : 0;
+    a.means3D = means3D; a.campos_all = campos_all; a.rgb_all = rgb_all; a.dL_ddc = nullptr; a.dL_dsh = nullptr;
+    a.rgb_stride = view_stride ? (size_t)view_stride : (size_t)3 * (size_t)P; a.campos_stride = view_stride ? (size_t)view_stride : 3;
+    a.visible = nullptr; a.vis_stride = 0; a.vis_out = nullptr;
+    for (auto& g : a.g_small) g = nullptr;
+    adam_args(a.adam, nullptr, 0, 0);
+    return 1;
 }
 
 int gslic_sh_grad_from_rgb(int32_t P, int32_t D, int32_t M, int32_t n_views, const float* means3D, const float* campos_all,
                            const float* rgb_all, int32_t input_is_ddc, float* dL_ddc, float* dL_dsh, int64_t view_stride, void* stream)
 {
-    if (view_stride < 0 || (view_stride > 0 && view_stride < 3 * (int64_t)P)) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_sh_grad_from_rgb: bad view_stride");
-    if (P < 0 || D < 0 || D > 3 || M < 0 || n_views < 1) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_sh_grad_from_rgb: bad P / D / M / n_views");
-    if (P == 0) return GSLIC_OK;
-    if (!means3D || !campos_all || !rgb_all || !dL_ddc || (M > 0 && !dL_dsh)) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_sh_grad_from_rgb: NULL pointer");
     ShGradFromRgbArgs a;
-    a.P = P; a.D = D; a.M = M; a.n_views = n_views; a.input_is_ddc = input_is_ddc ? 1 : 0;
-    a.means3D = means3D; a.campos_all = campos_all; a.rgb_all = rgb_all; a.dL_ddc = dL_ddc; a.dL_dsh = dL_dsh;
-    a.rgb_stride = view_stride ? (size_t)view_stride : (size_t)3 * (size_t)P; a.campos_stride = view_stride ? (size_t)view_stride : 3;
-    a.visible = nullptr; a.vis_stride = 0; a.vis_out = nullptr;
-    for (auto& g : a.g_small) g = nullptr;
-    memset(&a.adam, 0, sizeof(a.adam));
+    const int go = sh_grad_begin("gslic_sh_grad_from_rgb", P, D, M, n_views, means3D, campos_all, rgb_all, input_is_ddc, view_stride, false, "",
+                                 !dL_ddc || (M > 0 && !dL_dsh), a);
+    if (go != 1) return go;
+    a.dL_ddc = dL_ddc; a.dL_dsh = dL_dsh;
     return launch_sh_grad_from_rgb(a, (hipStream_t)stream);
 }
 
@@ -917,23 +1006,17 @@ int gslic_sh_grad_from_rgb_adam(int32_t P, int32_t D, int32_t M, int32_t n_views
                                 const float* rgb_all, int32_t input_is_ddc, const uint8_t* visible, const gslic_adam_fused* adam, float* dL_ddc,
                                 float* dL_dsh, int64_t view_stride, void* stream)
 {
-    if (view_stride < 0 || (view_stride > 0 && view_stride < 3 * (int64_t)P)) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_sh_grad_from_rgb_adam: bad view_stride");
-    if (P < 0 || D < 0 || D > 3 || M < 0 || n_views < 1) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_sh_grad_from_rgb_adam: bad P / D / M / n_views");
-    if (P == 0) return GSLIC_OK;
-    if (!means3D || !campos_all || !rgb_all || !visible || !adam) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_sh_grad_from_rgb_adam: NULL pointer");
+    const char* const fn = "gslic_sh_grad_from_rgb_adam";
+    ShGradFromRgbArgs a;
+    const int go = sh_grad_begin(fn, P, D, M, n_views, means3D, campos_all, rgb_all, input_is_ddc, view_stride, false, "", !visible || !adam, a);
+    if (go != 1) return go;
     for (int g = 1; g <= 2; g++) {
         if (g == 2 && M == 0) continue;
-        if (!adam->param[g] || !adam->exp_avg[g] || !adam->exp_avg_sq[g]) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_sh_grad_from_rgb_adam: group %d has a NULL pointer", g);
+        if (!adam->param[g] || !adam->exp_avg[g] || !adam->exp_avg_sq[g]) return set_error(GSLIC_ERR_INVALID_ARG, "%s: group %d has a NULL pointer", fn, g);
     }
-    ShGradFromRgbArgs a;
-    a.P = P; a.D = D; a.M = M; a.n_views = n_views; a.input_is_ddc = input_is_ddc ? 1 : 0;
-    a.means3D = means3D; a.campos_all = campos_all; a.rgb_all = rgb_all; a.dL_ddc = dL_ddc; a.dL_dsh = M > 0 ? dL_dsh : nullptr;
-    a.rgb_stride = view_stride ? (size_t)view_stride : (size_t)3 * (size_t)P; a.campos_stride = view_stride ? (size_t)view_stride : 3;
-    a.visible = visible; a.vis_stride = 0; a.vis_out = nullptr;
-    for (auto& g : a.g_small) g = nullptr;
-    memset(&a.adam, 0, sizeof(a.adam));
-    for (int g = 1; g <= 2; g++) { a.adam.p[g] = adam->param[g]; a.adam.m[g] = adam->exp_avg[g]; a.adam.v[g] = adam->exp_avg_sq[g]; a.adam.lr[g] = adam->lr[g]; }
-    a.adam.b1 = adam->b1; a.adam.b2 = adam->b2; a.adam.eps = adam->eps; a.adam.on = 1;
+    a.dL_ddc = dL_ddc; a.dL_dsh = M > 0 ? dL_dsh : nullptr;
+    a.visible = visible;
+    adam_args(a.adam, adam, 1, 3);
     return launch_sh_grad_from_rgb(a, (hipStream_t)stream);
 }
 
@@ -942,27 +1025,21 @@ int gslic_sh_grad_from_rgb_adam_all(int32_t P, int32_t D, int32_t M, int32_t n_v
                                     const gslic_adam_fused* adam, const float* dL_dmean3D, const float* dL_dopacity, const float* dL_dscale,
                                     const float* dL_drot, int64_t view_stride, void* stream)
 {
-    if (view_stride < 0 || (view_stride > 0 && view_stride < 3 * (int64_t)P)) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_sh_grad_from_rgb_adam_all: bad view_stride");
-    if (P < 0 || D < 0 || D > 3 || M < 0 || n_views < 1 || vis_stride < 0 || (vis_stride > 0 && vis_stride < (int64_t)P))
-        return set_error(GSLIC_ERR_INVALID_ARG, "gslic_sh_grad_from_rgb_adam_all: bad P / D / M / n_views / vis_stride");
-    if (P == 0) return GSLIC_OK;
-    if (!means3D || !campos_all || !rgb_all || !vis_all || !adam) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_sh_grad_from_rgb_adam_all: NULL pointer");
+    const char* const fn = "gslic_sh_grad_from_rgb_adam_all";
+    ShGradFromRgbArgs a;
+    const int go = sh_grad_begin(fn, P, D, M, n_views, means3D, campos_all, rgb_all, input_is_ddc, view_stride,
+                                 vis_stride < 0 || (vis_stride > 0 && vis_stride < (int64_t)P), " / vis_stride", !vis_all || !adam, a);
+    if (go != 1) return go;
     const bool small = dL_dmean3D || dL_dopacity || dL_dscale || dL_drot;
     if (small && !(dL_dmean3D && dL_dopacity && dL_dscale && dL_drot))
-        return set_error(GSLIC_ERR_INVALID_ARG, "gslic_sh_grad_from_rgb_adam_all: the four small gradients are given together or not at all");
+        return set_error(GSLIC_ERR_INVALID_ARG, "%s: the four small gradients are given together or not at all", fn);
     for (int g = 0; g < 6; g++) {
         if ((g == 2 && M == 0) || (!small && g != 1 && g != 2)) continue;
-        if (!adam->param[g] || !adam->exp_avg[g] || !adam->exp_avg_sq[g]) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_sh_grad_from_rgb_adam_all: group %d has a NULL pointer", g);
+        if (!adam->param[g] || !adam->exp_avg[g] || !adam->exp_avg_sq[g]) return set_error(GSLIC_ERR_INVALID_ARG, "%s: group %d has a NULL pointer", fn, g);
     }
-    ShGradFromRgbArgs a;
-    a.P = P; a.D = D; a.M = M; a.n_views = n_views; a.input_is_ddc = input_is_ddc ? 1 : 0;
-    a.means3D = means3D; a.campos_all = campos_all; a.rgb_all = rgb_all; a.dL_ddc = nullptr; a.dL_dsh = nullptr;
-    a.rgb_stride = view_stride ? (size_t)view_stride : (size_t)3 * (size_t)P; a.campos_stride = view_stride ? (size_t)view_stride : 3;
     a.visible = vis_all; a.vis_stride = (size_t)vis_stride; a.vis_out = vis_out;
     a.g_small[0] = dL_dmean3D; a.g_small[1] = dL_dopacity; a.g_small[2] = dL_dscale; a.g_small[3] = dL_drot;
-    memset(&a.adam, 0, sizeof(a.adam));
-    for (int g = 0; g < 6; g++) { a.adam.p[g] = adam->param[g]; a.adam.m[g] = adam->exp_avg[g]; a.adam.v[g] = adam->exp_avg_sq[g]; a.adam.lr[g] = adam->lr[g]; }
-    a.adam.b1 = adam->b1; a.adam.b2 = adam->b2; a.adam.eps = adam->eps; a.adam.on = 1;
+    adam_args(a.adam, adam, 0, 6);
     return launch_sh_grad_from_rgb(a, (hipStream_t)stream);
 }
 
@@ -975,10 +1052,9 @@ int gslic_rasterize_backward_adam(const gslic_raster_params* prm, int32_t R, int
                                   void* stream)
 {
     if (!adam) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_adam: adam descriptor is NULL");
-    return rasterize_backward_impl(prm, R, B, background, means3D, dc, shs, colors_precomp, scales, rotations, cov3D_precomp, viewmatrix,
-                                   projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, nullptr,
-                                   nullptr, dL_dopacity, nullptr, dL_dmean3D, nullptr, dL_ddc, dL_dsh, dL_dscale, dL_drot, lambda_erank,
-                                   adam, nullptr, stream, nullptr, 0, -1, false, adam->visible_out);
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_ADAM(c);
+    return rasterize_backward_impl(c);
 }
 
 int gslic_rasterize_backward_depth_adam(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
@@ -992,14 +1068,13 @@ int gslic_rasterize_backward_depth_adam(const gslic_raster_params* prm, int32_t 
     GS_TRY(check_params(prm));
     if (prm->P == 0) return GSLIC_OK;
     if (!adam) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_adam: adam descriptor is NULL");
-    if (prm->no_color) return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no_color = 1 (no depth forward renders without colour)");
-    if (!dL_ddepth) return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: dL_ddepth is NULL (gslic_rasterize_backward_adam is the colour-only backward)");
+    GS_TRY(depth_backward_checks(prm, dL_ddepth, "gslic_rasterize_backward_adam", ""));
     if (!dL_dmean3D)
         return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_adam: dL_dmean3D is NULL (the xyz gradient is assembled there before its update)");
-    return rasterize_backward_impl(prm, R, B, background, means3D, dc, shs, colors_precomp, scales, rotations, cov3D_precomp, viewmatrix,
-                                   projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, nullptr,
-                                   nullptr, dL_dopacity, nullptr, dL_dmean3D, nullptr, dL_ddc, dL_dsh, dL_dscale, dL_drot, lambda_erank,
-                                   adam, nullptr, stream, nullptr, 0, -1, false, adam->visible_out, nullptr, dL_ddepth);
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_ADAM(c);
+    c.dL_ddepth = dL_ddepth;
+    return rasterize_backward_impl(c);
 }
 
 int gslic_rasterize_backward_camera(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
@@ -1013,18 +1088,10 @@ int gslic_rasterize_backward_camera(const gslic_raster_params* prm, int32_t R, i
 {
     if (!dL_dviewmatrix || !dL_dprojmatrix || !dL_dcampos)
         return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_camera: a camera-gradient output pointer is NULL");
-    float* const cam[3] = {dL_dviewmatrix, dL_dprojmatrix, dL_dcampos};
-    if (prm && prm->P == 0) {  // nothing rendered: zero gradients
-        hipStream_t s = (hipStream_t)stream;
-        GS_HIP(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float), s));
-        GS_HIP(hipMemsetAsync(dL_dprojmatrix, 0, 16 * sizeof(float), s));
-        GS_HIP(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float), s));
-        return GSLIC_OK;
-    }
-    return rasterize_backward_impl(prm, R, B, background, means3D, dc, shs, colors_precomp, scales, rotations, cov3D_precomp, viewmatrix,
-                                   projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, dL_dmean2D,
-                                   dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot,
-                                   lambda_erank, nullptr, cam, stream);
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_TEN_GRADS(c); GS_BACKWARD_CAMERA(c);
+    if (prm && prm->P == 0) return zero_camera_grads(c.dL_dcam, stream);
+    return rasterize_backward_impl(c);
 }
 
 int gslic_rasterize_backward_depth_camera(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
@@ -1039,23 +1106,19 @@ int gslic_rasterize_backward_depth_camera(const gslic_raster_params* prm, int32_
     if (!dL_dviewmatrix || !dL_dprojmatrix || !dL_dcampos)
         return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_camera: a camera-gradient output pointer is NULL");
     GS_TRY(check_params(prm));   // (SH degree > 3 among them)
-    float* const cam[3] = {dL_dviewmatrix, dL_dprojmatrix, dL_dcampos};
-    if (prm->P == 0) {  // nothing rendered: zero gradients
-        hipStream_t s = (hipStream_t)stream;
-        GS_HIP(hipMemsetAsync(dL_dviewmatrix, 0, 16 * sizeof(float), s));
-        GS_HIP(hipMemsetAsync(dL_dprojmatrix, 0, 16 * sizeof(float), s));
-        GS_HIP(hipMemsetAsync(dL_dcampos, 0, 3 * sizeof(float), s));
-        return GSLIC_OK;
-    }
-    if (prm->no_color) return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no_color = 1 (no depth forward renders without colour)");
-    if (!dL_ddepth)
-        return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: dL_ddepth is NULL (gslic_rasterize_backward_camera is the colour-only camera backward)");
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_TEN_GRADS(c); GS_BACKWARD_CAMERA(c);
+    c.dL_ddepth = dL_ddepth;
+    if (prm->P == 0) return zero_camera_grads(c.dL_dcam, stream);
+    GS_TRY(depth_backward_checks(prm, dL_ddepth, "gslic_rasterize_backward_camera", "camera "));
     if (!dL_dmean3D) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_camera: dL_dmean3D is NULL (the depth's share is added to it)");
-    return rasterize_backward_impl(prm, R, B, background, means3D, dc, shs, colors_precomp, scales, rotations, cov3D_precomp, viewmatrix,
-                                   projmatrix, cam_pos, radii, geom_buffer, binning_buffer, img_buffer, sample_buffer, dL_dpix, dL_dmean2D,
-                                   dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscale, dL_drot,
-                                   lambda_erank, nullptr, cam, stream, nullptr, 0, -1, false, nullptr, nullptr, dL_ddepth);
+    return rasterize_backward_impl(c);
 }
+#undef GS_BACKWARD_SHARED
+#undef GS_BACKWARD_TEN_GRADS
+#undef GS_BACKWARD_RGB_GRADS
+#undef GS_BACKWARD_ADAM
+#undef GS_BACKWARD_CAMERA
 
 int gslic_adam_update(float* param, const float* param_grad, float* exp_avg, float* exp_avg_sq, const uint8_t* visible, float lr,
                       float b1, float b2, float eps, uint32_t N, uint32_t M, void* stream)

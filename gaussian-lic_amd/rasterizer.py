@@ -53,6 +53,61 @@ def _f32c(t):
     return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
 
 
+def _sh_width(sh):
+    return sh.size(1) if sh is not None and sh.size(0) != 0 else 0
+
+
+def _forward(bufs, depth, view, degree, prefiltered, debug, no_color, raw_params, tie_rank, background, means3D, dc, sh, colors, opacity, scales,
+             rotations, cov3D_precomp, viewmatrix, projmatrix, campos):
+    """The one forward behind the four public ones.  bufs: None = the library's allocator callbacks size the scratch (two host round trips), a
+    CapacityBuffers = caller-owned scratch and outputs (no copies are made: addresses have to be stable for graph capture); depth: also render
+    the depth image.  view = (H, W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier), _params' order.
+    Returns (R, B, out_color, out_final_T, out_depth or None, radii, geom, binning, img, sample)."""
+    L = _lib.lib()
+    P, M = means3D.size(0), _sh_width(sh)
+    p = _lib.ptr
+    R, B = ctypes.c_int32(0), ctypes.c_int32(0)
+    if bufs is None:
+        dev, (H, W) = means3D.device, view[:2]
+        mk = torch.zeros if P == 0 else torch.empty
+        out_color = (torch.zeros if no_color else mk)(3, H, W, dtype=torch.float32, device=dev)
+        out_final_T = mk(H, W, dtype=torch.float32, device=dev)
+        out_depth = mk(H, W, dtype=torch.float32, device=dev) if depth else None
+        radii = torch.empty(P, dtype=torch.int32, device=dev)
+        allocs = [_lib.TensorAllocator(dev) for _ in range(4)]  # geom, binning, img, sample
+        scratch = (allocs[0].cb, None, allocs[1].cb, None, allocs[2].cb, None, allocs[3].cb, None)
+        status = ()
+        if P != 0:
+            means3D, dc, opacity, scales, rotations = map(_f32c, (means3D, dc, opacity, scales, rotations))
+            sh = _f32c(sh) if M > 0 else None
+            viewmatrix, projmatrix, campos, background = map(_f32c, (viewmatrix, projmatrix, campos, background))
+        fn = L.gslic_rasterize_forward_depth if depth else L.gslic_rasterize_forward
+    else:
+        assert P == bufs.P and P > 0
+        if depth and not bufs.with_depth:
+            raise ValueError("rasterize_gaussians_depth_capacity needs CapacityBuffers(..., depth=True)")
+        for t in (means3D, dc, opacity, scales, rotations, viewmatrix, projmatrix, campos):
+            assert t.is_contiguous() and t.dtype == torch.float32
+        out_color, out_final_T, out_depth, radii = bufs.color, bufs.final_T, bufs.depth if depth else None, bufs.radii
+        bp = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+        scratch = (bp(bufs.geom), bufs.geom.numel(), bp(bufs.binning), bufs.binning.numel(), bp(bufs.img), bufs.img.numel(), bp(bufs.sample),
+                   bufs.sample.numel())
+        status = (p(bufs.status),)
+        sh = sh if M > 0 else None
+        fn = L.gslic_rasterize_forward_depth_capacity if depth else L.gslic_rasterize_forward_capacity
+    if P != 0:
+        prm = _params(P, degree, M, *view, prefiltered, debug, no_color, raw_params, tie_rank)
+        _lib.check(fn(ctypes.byref(prm), *scratch, p(background), p(means3D), p(dc), p(sh), p(colors), p(opacity), p(scales), p(rotations),
+                      p(cov3D_precomp), p(viewmatrix), p(projmatrix), p(campos), p(out_color), p(out_final_T), *((p(out_depth),) if depth else ()),
+                      p(radii), ctypes.byref(R), ctypes.byref(B), *status, _lib.current_stream_ptr()))
+    if bufs is None:
+        geom, binning, img, sample = (a.tensor for a in allocs)
+    else:
+        bufs.cap_R, bufs.cap_B = R.value, B.value
+        geom, binning, img, sample = bufs.geom, bufs.binning, bufs.img, bufs.sample
+    return (R.value, B.value, out_color, out_final_T, out_depth, radii, geom, binning, img, sample)
+
+
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
                         projmatrix, tan_fovx, tan_fovy, image_height, image_width, limx_neg, limx_pos, limy_neg, limy_pos,
                         dc, sh, degree, campos, prefiltered, debug, no_color=False, raw_params=False, tie_rank=None):
@@ -62,29 +117,10 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
     tie_rank (not in the reference): see _params — a map stored in a permuted row order renders as the unpermuted one."""
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise ValueError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:77-80
-    L = _lib.lib()
-    dev = means3D.device
-    P, H, W = means3D.size(0), int(image_height), int(image_width)
-    M = sh.size(1) if sh is not None and sh.size(0) != 0 else 0
-    out_color = torch.zeros(3, H, W, dtype=torch.float32, device=dev) if (P == 0 or no_color) else \
-        torch.empty(3, H, W, dtype=torch.float32, device=dev)
-    out_final_T = torch.zeros(H, W, dtype=torch.float32, device=dev) if P == 0 else torch.empty(H, W, dtype=torch.float32, device=dev)
-    radii = torch.empty(P, dtype=torch.int32, device=dev)
-    allocs = [_lib.TensorAllocator(dev) for _ in range(4)]  # geom, binning, img, sample
-    R, B = ctypes.c_int32(0), ctypes.c_int32(0)
-    if P != 0:
-        means3D, dc, opacity, scales, rotations = map(_f32c, (means3D, dc, opacity, scales, rotations))
-        sh_c = _f32c(sh) if M > 0 else None
-        viewmatrix, projmatrix, campos, background = map(_f32c, (viewmatrix, projmatrix, campos, background))
-        prm = _params(P, degree, M, H, W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier,
-                      prefiltered, debug, no_color, raw_params, tie_rank)
-        p = _lib.ptr
-        _lib.check(L.gslic_rasterize_forward(
-            ctypes.byref(prm), allocs[0].cb, None, allocs[1].cb, None, allocs[2].cb, None, allocs[3].cb, None,
-            p(background), p(means3D), p(dc), p(sh_c), p(colors), p(opacity), p(scales), p(rotations), p(cov3D_precomp),
-            p(viewmatrix), p(projmatrix), p(campos), p(out_color), p(out_final_T), p(radii),
-            ctypes.byref(R), ctypes.byref(B), _lib.current_stream_ptr()))
-    return (R.value, B.value, out_color, out_final_T, radii, allocs[0].tensor, allocs[1].tensor, allocs[2].tensor, allocs[3].tensor)
+    view = (int(image_height), int(image_width), tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier)
+    r = _forward(None, False, view, degree, prefiltered, debug, no_color, raw_params, tie_rank, background, means3D, dc, sh, colors, opacity, scales,
+                 rotations, cov3D_precomp, viewmatrix, projmatrix, campos)
+    return r[:4] + r[5:]
 
 
 def rasterize_gaussians_depth(background, means3D, opacity, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx, tan_fovy,
@@ -96,30 +132,9 @@ def rasterize_gaussians_depth(background, means3D, opacity, scales, rotations, s
     the expected depth of the covered part); colour, final_T and radii are bit-identical to rasterize_gaussians'."""
     if means3D.dim() != 2 or means3D.size(1) != 3:
         raise ValueError("means3D must have dimensions (num_points, 3)")
-    L = _lib.lib()
-    dev = means3D.device
-    P, H, W = means3D.size(0), int(image_height), int(image_width)
-    M = sh.size(1) if sh is not None and sh.size(0) != 0 else 0
-    alloc = torch.zeros if P == 0 else torch.empty
-    out_color = alloc(3, H, W, dtype=torch.float32, device=dev)
-    out_final_T = alloc(H, W, dtype=torch.float32, device=dev)
-    out_depth = alloc(H, W, dtype=torch.float32, device=dev)
-    radii = torch.empty(P, dtype=torch.int32, device=dev)
-    allocs = [_lib.TensorAllocator(dev) for _ in range(4)]  # geom, binning, img, sample
-    R, B = ctypes.c_int32(0), ctypes.c_int32(0)
-    if P != 0:
-        means3D, dc, opacity, scales, rotations = map(_f32c, (means3D, dc, opacity, scales, rotations))
-        sh_c = _f32c(sh) if M > 0 else None
-        viewmatrix, projmatrix, campos, background = map(_f32c, (viewmatrix, projmatrix, campos, background))
-        prm = _params(P, degree, M, H, W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier,
-                      prefiltered, debug, False, raw_params, tie_rank)
-        p = _lib.ptr
-        _lib.check(L.gslic_rasterize_forward_depth(
-            ctypes.byref(prm), allocs[0].cb, None, allocs[1].cb, None, allocs[2].cb, None, allocs[3].cb, None,
-            p(background), p(means3D), p(dc), p(sh_c), None, p(opacity), p(scales), p(rotations), None,
-            p(viewmatrix), p(projmatrix), p(campos), p(out_color), p(out_final_T), p(out_depth), p(radii),
-            ctypes.byref(R), ctypes.byref(B), _lib.current_stream_ptr()))
-    return (R.value, B.value, out_color, out_final_T, out_depth, radii, allocs[0].tensor, allocs[1].tensor, allocs[2].tensor, allocs[3].tensor)
+    view = (int(image_height), int(image_width), tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier)
+    return _forward(None, True, view, degree, prefiltered, debug, False, raw_params, tie_rank, background, means3D, dc, sh, None, opacity, scales,
+                    rotations, None, viewmatrix, projmatrix, campos)
 
 
 class CapacityBuffers:
@@ -166,50 +181,95 @@ def rasterize_gaussians_capacity(bufs, background, means3D, opacity, scales, rot
     """gslic_rasterize_forward_capacity: RasterizeGaussiansCUDA without a host round trip, into caller-owned buffers.  The tensors must
     already be contiguous fp32 (no copies are made: addresses have to be stable for graph capture).  Returns the same 9-tuple as
     rasterize_gaussians with (cap_R, cap_B) in place of (R, B) — pass them on to rasterize_gaussians_backward unchanged."""
-    L = _lib.lib()
-    P = means3D.size(0)
-    assert P == bufs.P and P > 0
-    M = sh.size(1) if sh is not None and sh.size(0) != 0 else 0
-    for t in (means3D, dc, opacity, scales, rotations, viewmatrix, projmatrix, campos):
-        assert t.is_contiguous() and t.dtype == torch.float32
-    prm = _params(P, degree, M, bufs.H, bufs.W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier, False, False,
-                  bufs.no_color, raw_params, tie_rank)
-    p = _lib.ptr
-    cR, cB = ctypes.c_int32(0), ctypes.c_int32(0)
-    bp = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
-    _lib.check(L.gslic_rasterize_forward_capacity(
-        ctypes.byref(prm), bp(bufs.geom), bufs.geom.numel(), bp(bufs.binning), bufs.binning.numel(), bp(bufs.img), bufs.img.numel(),
-        bp(bufs.sample), bufs.sample.numel(), p(background), p(means3D), p(dc), p(sh if M > 0 else None), None, p(opacity), p(scales),
-        p(rotations), None, p(viewmatrix), p(projmatrix), p(campos), p(bufs.color), p(bufs.final_T), p(bufs.radii), ctypes.byref(cR),
-        ctypes.byref(cB), p(bufs.status), _lib.current_stream_ptr()))
-    bufs.cap_R, bufs.cap_B = cR.value, cB.value
-    return (cR.value, cB.value, bufs.color, bufs.final_T, bufs.radii, bufs.geom, bufs.binning, bufs.img, bufs.sample)
+    view = (bufs.H, bufs.W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier)
+    r = _forward(bufs, False, view, degree, False, False, bufs.no_color, raw_params, tie_rank, background, means3D, dc, sh, None, opacity, scales,
+                 rotations, None, viewmatrix, projmatrix, campos)
+    return r[:4] + r[5:]
 
 
 def rasterize_gaussians_depth_capacity(bufs, background, means3D, opacity, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx,
                                        tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, dc, sh, degree, campos, raw_params=False, tie_rank=None):
     """gslic_rasterize_forward_depth_capacity: rasterize_gaussians_capacity plus the depth image, into CapacityBuffers(depth=True).  Returns
     (cap_R, cap_B, out_color, out_final_T, out_depth, radii, geom, binning, img, sample); bit-identical to rasterize_gaussians_depth."""
+    view = (bufs.H, bufs.W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier)
+    return _forward(bufs, True, view, degree, False, False, False, raw_params, tie_rank, background, means3D, dc, sh, None, opacity, scales,
+                    rotations, None, viewmatrix, projmatrix, campos)
+
+
+def _backward(view, degree, debug, raw_params, background, means3D, radii, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+              dL_dout_color, dL_dout_depth, dc, sh, geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank, out=None, adam=None,
+              camera_grads=False, rgb_out=None, rows=None, skip_blend=False, out_addr=None, payload=None, xyz_grad=None):
+    """The one backward behind the two public ones (see there for the modes).  dL_dout_depth: None = the colour-only entry points, a tensor =
+    their depth twins.  view as _forward's."""
     L = _lib.lib()
-    P = means3D.size(0)
-    assert P == bufs.P and P > 0
-    if not bufs.with_depth:
-        raise ValueError("rasterize_gaussians_depth_capacity needs CapacityBuffers(..., depth=True)")
-    M = sh.size(1) if sh is not None and sh.size(0) != 0 else 0
-    for t in (means3D, dc, opacity, scales, rotations, viewmatrix, projmatrix, campos):
-        assert t.is_contiguous() and t.dtype == torch.float32
-    prm = _params(P, degree, M, bufs.H, bufs.W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier, False, False,
-                  False, raw_params, tie_rank)
-    p = _lib.ptr
-    cR, cB = ctypes.c_int32(0), ctypes.c_int32(0)
-    bp = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
-    _lib.check(L.gslic_rasterize_forward_depth_capacity(
-        ctypes.byref(prm), bp(bufs.geom), bufs.geom.numel(), bp(bufs.binning), bufs.binning.numel(), bp(bufs.img), bufs.img.numel(),
-        bp(bufs.sample), bufs.sample.numel(), p(background), p(means3D), p(dc), p(sh if M > 0 else None), None, p(opacity), p(scales),
-        p(rotations), None, p(viewmatrix), p(projmatrix), p(campos), p(bufs.color), p(bufs.final_T), p(bufs.depth), p(bufs.radii),
-        ctypes.byref(cR), ctypes.byref(cB), p(bufs.status), _lib.current_stream_ptr()))
-    bufs.cap_R, bufs.cap_B = cR.value, cB.value
-    return (cR.value, cB.value, bufs.color, bufs.final_T, bufs.depth, bufs.radii, bufs.geom, bufs.binning, bufs.img, bufs.sample)
+    dev, P, M = means3D.device, means3D.size(0), _sh_width(sh)
+    depth = dL_dout_depth is not None
+    full = adam is None and rgb_out is None   # the nine gradient tensors are returned (else: None)
+    if rgb_out is not None:
+        assert out is not None   # the four other parameter gradients go into the caller's storage, nothing else is materialised
+    if adam is not None and depth and P == 0:
+        return None   # (the colour-only fused backward leaves P == 0 to the library, which returns at once)
+    if full and out is not None:
+        # caller-provided gradient storage (e.g. views of one flat slab for a zero-copy all-reduce); the tensors the host
+        # discards (means2D, conic, colors_precomp, cov3D: rasterizer.cpp:171-182) are not materialised at all
+        dL_dmeans3D, dL_ddc, dL_dsh = out["xyz"], out["features_dc"], out["features_rest"]
+        dL_dopacities, dL_dscales, dL_drotations = out["opacity"], out["scaling"], out["rotation"]
+        dL_dmeans2D = dL_dcolors = dL_dconic = dL_dcov3D = None
+    elif full:
+        mk = (lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)) if P != 0 else \
+            (lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev))
+        dL_dmeans3D, dL_dmeans2D, dL_dcolors = mk(P, 3), mk(P, 3), mk(P, 3)
+        dL_dconic, dL_dopacities, dL_dcov3D = mk(P, 2, 2), mk(P, 1), mk(P, 6)
+        dL_ddc, dL_dsh, dL_dscales, dL_drotations = mk(P, 1, 3), mk(P, M, 3), mk(P, 3), mk(P, 4)
+    if P != 0 or adam is not None:
+        means3D, dc, scales, rotations, dL = map(_f32c, (means3D, dc, scales, rotations, dL_dout_color))
+        dLd = _f32c(dL_dout_depth) if depth else None
+        sh_c = _f32c(sh) if M > 0 else None
+        viewmatrix, projmatrix, campos, background = map(_f32c, (viewmatrix, projmatrix, campos, background))
+        if adam is not None and depth:
+            if xyz_grad is None:
+                xyz_grad = torch.empty(P, 3, dtype=torch.float32, device=dev)
+            assert xyz_grad.is_contiguous() and xyz_grad.numel() >= 3 * P
+        prm = _params(P, degree, M, *view, False, debug, False, True if adam is not None else raw_params)
+        p, vp, erank = _lib.ptr, ctypes.c_void_p, float(lambda_erank)
+        # what every variant starts with: params, R, B, the twelve inputs, the four buffers, dL (and dL/d depth)
+        head = (ctypes.byref(prm), int(R), int(B), p(background), p(means3D), p(dc), p(sh_c), p(colors), p(scales), p(rotations), p(cov3D_precomp),
+                p(viewmatrix), p(projmatrix), p(campos), p(radii.contiguous()), vp(geomBuffer.data_ptr()), vp(binningBuffer.data_ptr()),
+                vp(imageBuffer.data_ptr()), vp(sampleBuffer.data_ptr()), p(dL)) + ((p(dLd),) if depth else ())
+        if adam is not None:
+            # single-GPU fast path: Adam applied inside the backward kernel, no gradient tensors at all (but xyz's under depth supervision)
+            fn = L.gslic_rasterize_backward_depth_adam if depth else L.gslic_rasterize_backward_adam
+            tail = (None, p(xyz_grad) if depth else None, None, None, None, None, erank, ctypes.byref(adam))
+        elif rgb_out is not None and rows is not None:
+            # chunked (gslic_rasterize_backward_rgb_rows): Gaussians [rows[0], rows[1]) only; the kernels index the gradient pointers by the
+            # ABSOLUTE Gaussian index, so a caller that keeps its chunks in separate blocks passes `out_addr` = {name: address of row 0}
+            addr = out_addr or {k: out[k].data_ptr() for k in ("opacity", "xyz", "scaling", "rotation")}
+            rgb_addr = (out_addr or {}).get("rgb", rgb_out.data_ptr())
+            fn = L.gslic_rasterize_backward_rgb_rows
+            tail = (vp(addr["opacity"]), vp(addr["xyz"]), vp(rgb_addr), vp(addr["scaling"]), vp(addr["rotation"]), erank, int(rows[0]), int(rows[1]),
+                    int(bool(skip_blend)))
+        elif rgb_out is not None:
+            # N > 1 exchange: the clamp-masked colour gradient [P,3] is written instead of dL_ddc / dL_dsh, and the rest of the rank's all-gather
+            # payload (mask, camera centre) by the same kernel (no compare / copy launches)
+            pay_vis, pay_campos = (payload or (None, None))
+            fn = L.gslic_rasterize_backward_rgb_payload
+            tail = (p(out["opacity"]), p(out["xyz"]), p(rgb_out), p(out["scaling"]), p(out["rotation"]), erank, p(pay_vis), p(pay_campos))
+        else:
+            tail = (p(dL_dmeans2D), p(dL_dconic), p(dL_dopacities), p(dL_dcolors), p(dL_dmeans3D), p(dL_dcov3D), p(dL_ddc), p(dL_dsh), p(dL_dscales),
+                    p(dL_drotations), erank)
+            if camera_grads:
+                cam = (torch.empty(16, device=dev), torch.empty(16, device=dev), torch.empty(3, device=dev))
+                fn = L.gslic_rasterize_backward_depth_camera if depth else L.gslic_rasterize_backward_camera
+                tail += (p(cam[0]), p(cam[1]), p(cam[2]))
+            else:
+                fn = L.gslic_rasterize_backward_depth if depth else L.gslic_rasterize_backward
+        _lib.check(fn(*head, *tail, _lib.current_stream_ptr()))
+    elif full and camera_grads:
+        cam = (torch.zeros(16, device=dev), torch.zeros(16, device=dev), torch.zeros(3, device=dev))
+    if not full:
+        return None
+    res = (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscales, dL_drotations)
+    return res + cam if camera_grads else res
 
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
@@ -220,91 +280,16 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     """RasterizeGaussiansBackwardCUDA (rasterize_points.cu:151-246): returns (dL_dmeans2D, dL_dcolors_precomp,
     dL_dopacities, dL_dmeans3D, dL_dcov3Ds_precomp, dL_ddc, dL_dsh, dL_dscales, dL_drotations).
     raw_params=True: scales / rotations are raw and dL_dopacities / dL_dscales / dL_drotations are w.r.t. the raw parameters.
+    out: caller-provided storage for the six parameter gradients (dict xyz / features_dc / features_rest / opacity / scaling / rotation); the
+    four the host discards are then not materialised.
+    adam (a gslic_adam_fused descriptor, raw_params implied): gslic_rasterize_backward_adam, the Adam update inside the backward; returns None.
+    rgb_out [P,3] (with out; returns None): gslic_rasterize_backward_rgb_payload, or with rows=(p0, p1) gslic_rasterize_backward_rgb_rows.
     camera_grads=True (gslic_rasterize_backward_camera; no reference counterpart): three more tensors are appended —
     dL_dviewmatrix [16], dL_dprojmatrix [16], dL_dcampos [3], element order of the inputs."""
-    L = _lib.lib()
-    dev = means3D.device
-    P, H, W = means3D.size(0), dL_dout_color.size(1), dL_dout_color.size(2)
-    M = sh.size(1) if sh is not None and sh.size(0) != 0 else 0
-    mk = (lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)) if P != 0 else \
-        (lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev))
-    if adam is not None:
-        # single-GPU fast path: Adam applied inside the backward kernel, no gradient tensors at all (gslic_rasterize_backward_adam)
-        means3D, dc, scales, rotations, dL = map(_f32c, (means3D, dc, scales, rotations, dL_dout_color))
-        sh_c = _f32c(sh) if M > 0 else None
-        viewmatrix, projmatrix, campos, background = map(_f32c, (viewmatrix, projmatrix, campos, background))
-        prm = _params(P, degree, M, H, W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier, False, debug, False, True)
-        p = _lib.ptr
-        _lib.check(L.gslic_rasterize_backward_adam(
-            ctypes.byref(prm), int(R), int(B), p(background), p(means3D), p(dc), p(sh_c), p(colors), p(scales), p(rotations),
-            p(cov3D_precomp), p(viewmatrix), p(projmatrix), p(campos), p(radii.contiguous()),
-            ctypes.c_void_p(geomBuffer.data_ptr()), ctypes.c_void_p(binningBuffer.data_ptr()), ctypes.c_void_p(imageBuffer.data_ptr()),
-            ctypes.c_void_p(sampleBuffer.data_ptr()), p(dL), None, None, None, None, None, None, float(lambda_erank), ctypes.byref(adam),
-            _lib.current_stream_ptr()))
-        return None
-    if rgb_out is not None:
-        # N > 1 exchange (gslic_rasterize_backward_rgb): the clamp-masked colour gradient [P,3] is written instead of dL_ddc / dL_dsh; the
-        # four other parameter gradients go into the caller's storage (`out`), nothing else is materialised
-        assert out is not None
-        if P != 0:
-            means3D, dc, scales, rotations, dL = map(_f32c, (means3D, dc, scales, rotations, dL_dout_color))
-            sh_c = _f32c(sh) if M > 0 else None
-            viewmatrix, projmatrix, campos, background = map(_f32c, (viewmatrix, projmatrix, campos, background))
-            prm = _params(P, degree, M, H, W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier, False, debug, False, raw_params)
-            p = _lib.ptr
-            if rows is not None:
-                # chunked (gslic_rasterize_backward_rgb_rows): Gaussians [rows[0], rows[1]) only; the kernels index the gradient pointers by the
-                # ABSOLUTE Gaussian index, so a caller that keeps its chunks in separate blocks passes `out_addr` = {name: address of row 0}
-                addr = out_addr or {k: out[k].data_ptr() for k in ("opacity", "xyz", "scaling", "rotation")}
-                rgb_addr = (out_addr or {}).get("rgb", rgb_out.data_ptr())
-                vp = ctypes.c_void_p
-                _lib.check(L.gslic_rasterize_backward_rgb_rows(
-                    ctypes.byref(prm), int(R), int(B), p(background), p(means3D), p(dc), p(sh_c), p(colors), p(scales), p(rotations),
-                    p(cov3D_precomp), p(viewmatrix), p(projmatrix), p(campos), p(radii.contiguous()),
-                    vp(geomBuffer.data_ptr()), vp(binningBuffer.data_ptr()), vp(imageBuffer.data_ptr()), vp(sampleBuffer.data_ptr()), p(dL),
-                    vp(addr["opacity"]), vp(addr["xyz"]), vp(rgb_addr), vp(addr["scaling"]), vp(addr["rotation"]),
-                    float(lambda_erank), int(rows[0]), int(rows[1]), int(bool(skip_blend)), _lib.current_stream_ptr()))
-                return None
-            pay_vis, pay_campos = (payload or (None, None))   # the rest of the rank's all-gather payload, written by the kernel (no compare / copy launches)
-            _lib.check(L.gslic_rasterize_backward_rgb_payload(
-                ctypes.byref(prm), int(R), int(B), p(background), p(means3D), p(dc), p(sh_c), p(colors), p(scales), p(rotations),
-                p(cov3D_precomp), p(viewmatrix), p(projmatrix), p(campos), p(radii.contiguous()),
-                ctypes.c_void_p(geomBuffer.data_ptr()), ctypes.c_void_p(binningBuffer.data_ptr()), ctypes.c_void_p(imageBuffer.data_ptr()),
-                ctypes.c_void_p(sampleBuffer.data_ptr()), p(dL), p(out["opacity"]), p(out["xyz"]), p(rgb_out), p(out["scaling"]), p(out["rotation"]),
-                float(lambda_erank), p(pay_vis), p(pay_campos), _lib.current_stream_ptr()))
-        return None
-    if out is not None:
-        # caller-provided gradient storage (e.g. views of one flat slab for a zero-copy all-reduce); the tensors the host
-        # discards (means2D, conic, colors_precomp, cov3D: rasterizer.cpp:171-182) are not materialised at all
-        dL_dmeans3D, dL_ddc, dL_dsh = out["xyz"], out["features_dc"], out["features_rest"]
-        dL_dopacities, dL_dscales, dL_drotations = out["opacity"], out["scaling"], out["rotation"]
-        dL_dmeans2D = dL_dcolors = dL_dconic = dL_dcov3D = None
-    else:
-        dL_dmeans3D, dL_dmeans2D, dL_dcolors = mk(P, 3), mk(P, 3), mk(P, 3)
-        dL_dconic, dL_dopacities, dL_dcov3D = mk(P, 2, 2), mk(P, 1), mk(P, 6)
-        dL_ddc, dL_dsh, dL_dscales, dL_drotations = mk(P, 1, 3), mk(P, M, 3), mk(P, 3), mk(P, 4)
-    if P != 0:
-        means3D, dc, scales, rotations, dL = map(_f32c, (means3D, dc, scales, rotations, dL_dout_color))
-        sh_c = _f32c(sh) if M > 0 else None
-        viewmatrix, projmatrix, campos, background = map(_f32c, (viewmatrix, projmatrix, campos, background))
-        prm = _params(P, degree, M, H, W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier,
-                      False, debug, False, raw_params)
-        p = _lib.ptr
-        common = (ctypes.byref(prm), int(R), int(B), p(background), p(means3D), p(dc), p(sh_c), p(colors), p(scales), p(rotations),
-                  p(cov3D_precomp), p(viewmatrix), p(projmatrix), p(campos), p(radii.contiguous()),
-                  ctypes.c_void_p(geomBuffer.data_ptr()), ctypes.c_void_p(binningBuffer.data_ptr()),
-                  ctypes.c_void_p(imageBuffer.data_ptr()), ctypes.c_void_p(sampleBuffer.data_ptr()), p(dL),
-                  p(dL_dmeans2D), p(dL_dconic), p(dL_dopacities), p(dL_dcolors), p(dL_dmeans3D), p(dL_dcov3D), p(dL_ddc),
-                  p(dL_dsh), p(dL_dscales), p(dL_drotations), float(lambda_erank))
-        if camera_grads:
-            cam = (torch.empty(16, device=dev), torch.empty(16, device=dev), torch.empty(3, device=dev))
-            _lib.check(L.gslic_rasterize_backward_camera(*common, p(cam[0]), p(cam[1]), p(cam[2]), _lib.current_stream_ptr()))
-        else:
-            _lib.check(L.gslic_rasterize_backward(*common, _lib.current_stream_ptr()))
-    elif camera_grads:
-        cam = (torch.zeros(16, device=dev), torch.zeros(16, device=dev), torch.zeros(3, device=dev))
-    res = (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscales, dL_drotations)
-    return res + cam if camera_grads else res
+    view = (dL_dout_color.size(1), dL_dout_color.size(2), tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier)
+    return _backward(view, degree, debug, raw_params, background, means3D, radii, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
+                     campos, dL_dout_color, None, dc, sh, geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank, out=out, adam=adam,
+                     camera_grads=camera_grads, rgb_out=rgb_out, rows=rows, skip_blend=skip_blend, out_addr=out_addr, payload=payload)
 
 
 def rasterize_gaussians_backward_depth(background, means3D, radii, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx,
@@ -322,62 +307,12 @@ def rasterize_gaussians_backward_depth(background, means3D, radii, scales, rotat
     its update (allocated when None; a graph-captured step passes a buffer of its own).
     camera_grads=True (gslic_rasterize_backward_depth_camera): three more tensors are appended — dL_dviewmatrix [16], dL_dprojmatrix [16],
     dL_dcampos [3] of the colour AND depth loss, as rasterize_gaussians_backward(camera_grads=True) does; not with adam."""
-    L = _lib.lib()
-    dev = means3D.device
-    P, H, W = means3D.size(0), dL_dout_color.size(1), dL_dout_color.size(2)
-    M = sh.size(1) if sh is not None and sh.size(0) != 0 else 0
     if adam is not None and camera_grads:
         raise ValueError("rasterize_gaussians_backward_depth: camera_grads with the fused Adam backward is not available")
-    if adam is not None:
-        if P == 0:
-            return None
-        means3D, dc, scales, rotations, dL, dLd = map(_f32c, (means3D, dc, scales, rotations, dL_dout_color, dL_dout_depth))
-        sh_c = _f32c(sh) if M > 0 else None
-        viewmatrix, projmatrix, campos, background = map(_f32c, (viewmatrix, projmatrix, campos, background))
-        if xyz_grad is None:
-            xyz_grad = torch.empty(P, 3, dtype=torch.float32, device=dev)
-        assert xyz_grad.is_contiguous() and xyz_grad.numel() >= 3 * P
-        prm = _params(P, degree, M, H, W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier, False, debug, False, True)
-        p = _lib.ptr
-        _lib.check(L.gslic_rasterize_backward_depth_adam(
-            ctypes.byref(prm), int(R), int(B), p(background), p(means3D), p(dc), p(sh_c), None, p(scales), p(rotations), None,
-            p(viewmatrix), p(projmatrix), p(campos), p(radii.contiguous()),
-            ctypes.c_void_p(geomBuffer.data_ptr()), ctypes.c_void_p(binningBuffer.data_ptr()), ctypes.c_void_p(imageBuffer.data_ptr()),
-            ctypes.c_void_p(sampleBuffer.data_ptr()), p(dL), p(dLd), None, p(xyz_grad), None, None, None, None, float(lambda_erank),
-            ctypes.byref(adam), _lib.current_stream_ptr()))
-        return None
-    mk = (lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)) if P != 0 else \
-        (lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev))
-    if out is not None:
-        dL_dmeans3D, dL_ddc, dL_dsh = out["xyz"], out["features_dc"], out["features_rest"]
-        dL_dopacities, dL_dscales, dL_drotations = out["opacity"], out["scaling"], out["rotation"]
-        dL_dmeans2D = dL_dcolors = dL_dconic = dL_dcov3D = None
-    else:
-        dL_dmeans3D, dL_dmeans2D, dL_dcolors = mk(P, 3), mk(P, 3), mk(P, 3)
-        dL_dconic, dL_dopacities, dL_dcov3D = mk(P, 2, 2), mk(P, 1), mk(P, 6)
-        dL_ddc, dL_dsh, dL_dscales, dL_drotations = mk(P, 1, 3), mk(P, M, 3), mk(P, 3), mk(P, 4)
-    if P != 0:
-        means3D, dc, scales, rotations, dL, dLd = map(_f32c, (means3D, dc, scales, rotations, dL_dout_color, dL_dout_depth))
-        sh_c = _f32c(sh) if M > 0 else None
-        viewmatrix, projmatrix, campos, background = map(_f32c, (viewmatrix, projmatrix, campos, background))
-        prm = _params(P, degree, M, H, W, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier,
-                      False, debug, False, raw_params)
-        p = _lib.ptr
-        common = (ctypes.byref(prm), int(R), int(B), p(background), p(means3D), p(dc), p(sh_c), None, p(scales), p(rotations), None,
-                  p(viewmatrix), p(projmatrix), p(campos), p(radii.contiguous()),
-                  ctypes.c_void_p(geomBuffer.data_ptr()), ctypes.c_void_p(binningBuffer.data_ptr()),
-                  ctypes.c_void_p(imageBuffer.data_ptr()), ctypes.c_void_p(sampleBuffer.data_ptr()), p(dL), p(dLd),
-                  p(dL_dmeans2D), p(dL_dconic), p(dL_dopacities), p(dL_dcolors), p(dL_dmeans3D), p(dL_dcov3D), p(dL_ddc),
-                  p(dL_dsh), p(dL_dscales), p(dL_drotations), float(lambda_erank))
-        if camera_grads:
-            cam = (torch.empty(16, device=dev), torch.empty(16, device=dev), torch.empty(3, device=dev))
-            _lib.check(L.gslic_rasterize_backward_depth_camera(*common, p(cam[0]), p(cam[1]), p(cam[2]), _lib.current_stream_ptr()))
-        else:
-            _lib.check(L.gslic_rasterize_backward_depth(*common, _lib.current_stream_ptr()))
-    elif camera_grads:
-        cam = (torch.zeros(16, device=dev), torch.zeros(16, device=dev), torch.zeros(3, device=dev))
-    res = (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscales, dL_drotations)
-    return res + cam if camera_grads else res
+    view = (dL_dout_color.size(1), dL_dout_color.size(2), tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier)
+    return _backward(view, degree, debug, raw_params, background, means3D, radii, None, scales, rotations, None, viewmatrix, projmatrix, campos,
+                     dL_dout_color, dL_dout_depth, dc, sh, geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank, out=out, adam=adam,
+                     camera_grads=camera_grads, xyz_grad=xyz_grad)
 
 
 def _depth_grads(ctx, dL_dcolor, dL_ddepth, xyz, dc, sh, opacity, scaling, rotation, radii, geom, binning, img, sample, raw):
@@ -546,33 +481,30 @@ def render(camera, model, bg_color, no_color=False, scaling_modifier=1.0, raw=No
         float(camera.limx_pos), float(camera.limy_neg), float(camera.limy_pos), bg_color, scaling_modifier,
         camera.d_world_view_transform, camera.d_full_proj_transform, model.sh_degree, camera.d_camera_center, False, False,
         no_color, model.lambda_erank, getattr(model, "tie_rank", None))
+    if raw and leaves is None:
+        raise TypeError("render(raw=True): the model does not expose its raw parameter leaves (set raw_parameter_leaves = True on a model whose "
+                        "xyz / features_dc / features_rest / opacity / scaling / rotation attributes are the PRE-activation tensors, or provide raw_leaves())")
+    if return_depth and no_color:
+        raise ValueError("render(return_depth=True) needs the colour (no_color=False)")
+    depth = ()
     if raw:
-        if leaves is None:
-            raise TypeError("render(raw=True): the model does not expose its raw parameter leaves (set raw_parameter_leaves = True on a model whose "
-                            "xyz / features_dc / features_rest / opacity / scaling / rotation attributes are the PRE-activation tensors, or provide raw_leaves())")
         xyz, dc, rest, opacity, scaling, rotation = leaves
         if return_depth:
-            if no_color:
-                raise ValueError("render(return_depth=True) needs the colour (no_color=False)")
-            image, radii, final_T, depth = RawGaussianRasterizerDepthFunction.apply(xyz, dc, rest, opacity, scaling, rotation, rs)
-            screenspace_points = torch.zeros(1, 3, dtype=xyz.dtype, device=xyz.device).expand(xyz.shape[0], 3)
-            return image, final_T, screenspace_points, radii > 0, radii, depth
-        image, radii, final_T = RawGaussianRasterizerFunction.apply(xyz, dc, rest, opacity, scaling, rotation, rs)
+            image, radii, final_T, *depth = RawGaussianRasterizerDepthFunction.apply(xyz, dc, rest, opacity, scaling, rotation, rs)
+        else:
+            image, radii, final_T = RawGaussianRasterizerFunction.apply(xyz, dc, rest, opacity, scaling, rotation, rs)
         screenspace_points = torch.zeros(1, 3, dtype=xyz.dtype, device=xyz.device).expand(xyz.shape[0], 3)
-        return image, final_T, screenspace_points, radii > 0, radii
+        return (image, final_T, screenspace_points, radii > 0, radii, *depth)
     xyz = model.get_xyz()
     screenspace_points = torch.zeros_like(xyz, requires_grad=True)
     if return_depth:
-        if no_color:
-            raise ValueError("render(return_depth=True) needs the colour (no_color=False)")
-        image, radii, final_T, depth = GaussianRasterizerDepthFunction.apply(
+        image, radii, final_T, *depth = GaussianRasterizerDepthFunction.apply(
             xyz, screenspace_points, model.get_features_dc(), model.get_features_rest(), model.get_opacity(), model.get_scaling(),
             model.get_rotation(), rs)
-        return image, final_T, screenspace_points, radii > 0, radii, depth
-    rasterizer = GaussianRasterizer(rs)
-    image, radii, final_T = rasterizer(xyz, screenspace_points, model.get_opacity(), model.get_features_dc(),
-                                       model.get_features_rest(), None, model.get_scaling(), model.get_rotation(), None)
-    return image, final_T, screenspace_points, radii > 0, radii
+    else:
+        image, radii, final_T = GaussianRasterizer(rs)(xyz, screenspace_points, model.get_opacity(), model.get_features_dc(),
+                                                       model.get_features_rest(), None, model.get_scaling(), model.get_rotation(), None)
+    return (image, final_T, screenspace_points, radii > 0, radii, *depth)
 
 
 def sh_grad_from_rgb(means3D, campos_all, rgb_all, degree, dL_ddc, dL_dsh, input_is_ddc=False, n_views=None, view_stride=0):

@@ -447,6 +447,58 @@ def exchange_rank1(slab, rgb_local, visible, model, campos):
     return vis, [(_Rebuild(), [] if fused else [1, 2])] + works
 
 
+class _RawRaster:
+    """(model, camera, background) as the pieces the raw-parameter forward and backward take (rasterizer._forward / _backward: activations
+    inside the kernels, no autograd), with or without the depth image.  pose: (view, proj, campos) device tensors in place of the camera's own
+    (GraphedStep's static buffers).  forward() keeps what backward() needs in `state` = (R, B, radii, geom, binning, img, sample)."""
+
+    def __init__(self, model, cam, bg, depth=False, e=None, pose=None):
+        self.depth, self.bg = depth, bg
+        self.xyz, self.dc, self.rest = model.xyz.detach(), model.features_dc.detach(), model.features_rest.detach()
+        self.op, self.sc, self.rot = model.opacity.detach(), model.scaling.detach(), model.rotation.detach()
+        self.pose = pose or (cam.d_world_view_transform, cam.d_full_proj_transform, cam.d_camera_center)
+        self.hw = (int(cam.image_height), int(cam.image_width))
+        self.scal = (float(cam.tanfovx), float(cam.tanfovy), float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), 1.0)
+        self.degree, self.lambda_erank, self.tie_rank = model.sh_degree, model.lambda_erank, getattr(model, "tie_rank", None)
+        # colors_precomp / cov3D_precomp: the empty tensors of the reference's host on the colour path, nothing at all on the depth path
+        self.e = e if (e is not None or depth) else torch.empty(0, device=model.device)
+        self.state = None
+
+    def forward(self, bufs=None):
+        """bufs: a CapacityBuffers (capacity mode) or None.  Returns (image, depth image or None, radii)."""
+        from . import rasterizer as rz
+        (R, B, image, _final_T, depth, radii, geom, binning, img, sample) = rz._forward(
+            bufs, self.depth, self.hw + self.scal, self.degree, False, False, False, True, self.tie_rank, self.bg, self.xyz, self.dc, self.rest, self.e,
+            self.op, self.sc, self.rot, self.e, *self.pose)
+        self.state = (R, B, radii, geom, binning, img, sample)
+        return image, depth, radii
+
+    def backward(self, dL_dimage, dL_ddepth=None, **modes):
+        """modes: out= / adam= / xyz_grad= / camera_grads= / rgb_out= ... of rasterizer.rasterize_gaussians_backward[_depth]."""
+        from . import rasterizer as rz
+        R, B, radii, geom, binning, img, sample = self.state
+        return rz._backward((dL_dimage.size(1), dL_dimage.size(2)) + self.scal, self.degree, False, True, self.bg, self.xyz, radii, self.e, self.sc,
+                            self.rot, self.e, *self.pose, dL_dimage, dL_ddepth if self.depth else None, self.dc, self.rest, geom, R, binning, img, B,
+                            sample, self.lambda_erank, **modes)
+
+
+def _fused_losses(fl, image, gt_image, depth, gt_depth, lambda_depth):
+    """The colour loss kernels and, for a depth image, the depth loss kernels: (dL/dimage, dL/ddepth or None, terms)."""
+    if depth is None:
+        dL_dimage, terms = fl.forward_backward(image, gt_image)
+        return dL_dimage, None, terms
+    dL_dimage, _ = fl.forward_backward(image, gt_image)
+    dL_ddepth, _ = fl.depth_forward_backward(depth, gt_depth, lambda_depth)
+    return dL_dimage, dL_ddepth, fl.terms3
+
+
+def _grad_slab(model):
+    slab = getattr(model, "_grad_slab", None)
+    if slab is None or slab.P != model.P:
+        slab = model._grad_slab = GradSlab(model)
+    return slab
+
+
 class _ChunkedExchange:
     """Buffers of the chunked rank-1 exchange for one (P, world, chunks): per chunk c = rows [p0, p1) a block of the 11 small gradient floats
     {xyz [n,3] | opacity [n] | scaling [n,3] | rotation [n,4]} (ONE all-reduce) and an all-gather payload {dRGB [n,3], camera centre [3],
@@ -477,17 +529,16 @@ def training_step_rank1_chunked(model, cam, bg, dL_dimage, fwd, chunks):
     all-gather of the chunk's {dRGB, camera centre, mask} and ONE all-reduce of its 11 small gradient floats, while the next chunk is being
     computed.  Then, chunk by chunk as the collectives land: OR of the masks, SH rows rebuilt and consumed by the masked Adam of
     features_dc / features_rest, Adam of the four small groups.  Same arithmetic per Gaussian as the unchunked step."""
-    from . import rasterizer as rz
     dist = torch.distributed
-    R, B, radii, geom, binning, img, sample = fwd
+    radii = fwd[2]
     dev = model.device
-    e = torch.empty(0, device=dev)
+    rr = _RawRaster(model, cam, bg)
+    rr.state = fwd
+    xyz = rr.xyz
     n_world = dist.get_world_size()
     cx = getattr(model, "_chunk_xchg", None)
     if cx is None or cx.P != model.P or cx.world != n_world or cx.chunks != chunks:
         cx = model._chunk_xchg = _ChunkedExchange(model.P, n_world, chunks, dev)
-    xyz, dc, rest = model.xyz.detach(), model.features_dc.detach(), model.features_rest.detach()
-    sc, rot = model.scaling.detach(), model.rotation.detach()
     slab = model._grad_slab
     visible_local = (radii > 0).to(torch.uint8)
     works = []
@@ -497,11 +548,7 @@ def training_step_rank1_chunked(model, cam, bg, dL_dimage, fwd, chunks):
         pay = cx.pay[c]
         addr = {"xyz": sm - 12 * p0, "opacity": sm + 12 * n - 4 * p0, "scaling": sm + 16 * n - 12 * p0, "rotation": sm + 28 * n - 16 * p0,
                 "rgb": pay.data_ptr() - 12 * p0}
-        rz.rasterize_gaussians_backward(
-            bg, xyz, radii, e, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-            float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dL_dimage, dc, rest, model.sh_degree,
-            cam.d_camera_center, geom, R, binning, img, B, sample, model.lambda_erank, False, raw_params=True, out=slab.views, rgb_out=slab.rgb,
-            rows=(p0, p1), skip_blend=(c > 0), out_addr=addr)
+        rr.backward(dL_dimage, out=slab.views, rgb_out=slab.rgb, rows=(p0, p1), skip_blend=(c > 0), out_addr=addr)
         pay[12 * n:12 * n + 12].view(torch.float32).copy_(cam.d_camera_center.reshape(3))
         pay[12 * n + 12:12 * n + 12 + n].copy_(visible_local[p0:p1])
         if c == 0:
@@ -576,23 +623,6 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
     return loss.detach(), visible
 
 
-def _pose_depth_forward_losses(model, cam, gt_image, bg, fl, gt_depth, lambda_depth):
-    """Depth forward and the colour / depth loss kernels of the pose steps: (backward's positional arguments, radii, terms [L1, SSIM, L_d])."""
-    from . import rasterizer as rz
-    xyz, dc, rest = model.xyz.detach(), model.features_dc.detach(), model.features_rest.detach()
-    op, sc, rot = model.opacity.detach(), model.scaling.detach(), model.rotation.detach()
-    (R, B, image, _final_T, depth, radii, geom, binning, img, sample) = rz.rasterize_gaussians_depth(
-        bg, xyz, op, sc, rot, 1.0, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-        cam.image_height, cam.image_width, float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dc, rest,
-        model.sh_degree, cam.d_camera_center, raw_params=True, tie_rank=getattr(model, "tie_rank", None))
-    dL_dimage, _ = fl.forward_backward(image, gt_image)
-    dL_ddepth, _ = fl.depth_forward_backward(depth, gt_depth, lambda_depth)
-    bwd = (bg, xyz, radii, sc, rot, 1.0, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-           float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dL_dimage, dL_ddepth, dc, rest, model.sh_degree,
-           cam.d_camera_center, geom, R, binning, img, B, sample, model.lambda_erank, False)
-    return bwd, radii, fl.terms3
-
-
 def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, lambda_depth=0.0):
     """dL/dxi of the training loss w.r.t. a left se(3) increment of the camera pose (Camera.pose_gradient) for the current map: forward -> loss
     kernels -> gslic_rasterize_backward_camera -> the chain.  The map is not touched.  Returns (float64 [6] = (d/drho, d/dphi), terms).
@@ -600,28 +630,14 @@ def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, l
     gt_depth [H,W] with lambda_depth != 0 (LiDAR depth supervision, as training_step_fused's): the loss gains lambda_depth * depth_l1 and the
     gradient its share — depth forward -> colour and depth loss kernels -> gslic_rasterize_backward_depth_camera -> the same chain; terms is
     then [mean L1, mean SSIM, L_d].  gt_depth=None or lambda_depth=0 is exactly the colour-only path."""
-    from . import rasterizer as rz
     fl = fused_loss or _default_fused_loss()
-    if gt_depth is not None and lambda_depth != 0.0:
-        with torch.no_grad():
-            bwd, _radii, terms = _pose_depth_forward_losses(model, camera, gt_image, bg, fl, gt_depth, float(lambda_depth))
-            out = rz.rasterize_gaussians_backward_depth(*bwd, raw_params=True, camera_grads=True)
-        return camera.pose_gradient(out[9], out[10], out[11]), terms
-    e = torch.empty(0, device=model.device)
-    cam = camera
+    use_depth = gt_depth is not None and lambda_depth != 0.0
     with torch.no_grad():
-        xyz, dc, rest = model.xyz.detach(), model.features_dc.detach(), model.features_rest.detach()
-        op, sc, rot = model.opacity.detach(), model.scaling.detach(), model.rotation.detach()
-        (R, B, image, _final_T, radii, geom, binning, img, sample) = rz.rasterize_gaussians(
-            bg, xyz, e, op, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-            cam.image_height, cam.image_width, float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dc, rest,
-            model.sh_degree, cam.d_camera_center, False, False, False, raw_params=True, tie_rank=getattr(model, "tie_rank", None))
-        dL_dimage, terms = fl.forward_backward(image, gt_image)
-        out = rz.rasterize_gaussians_backward(
-            bg, xyz, radii, e, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-            float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dL_dimage, dc, rest, model.sh_degree,
-            cam.d_camera_center, geom, R, binning, img, B, sample, model.lambda_erank, False, raw_params=True, camera_grads=True)
-    return cam.pose_gradient(out[9], out[10], out[11]), terms
+        rr = _RawRaster(model, camera, bg, use_depth)
+        image, depth, _radii = rr.forward()
+        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth))
+        out = rr.backward(dL_dimage, dL_ddepth, camera_grads=True)
+    return camera.pose_gradient(out[9], out[10], out[11]), terms
 
 
 def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None, gt_depth=None, lambda_depth=0.0):
@@ -631,38 +647,23 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
     gt_depth [H,W] with lambda_depth != 0: the same step under LiDAR depth supervision (depth forward, colour and depth loss kernels,
     gslic_rasterize_backward_depth_camera); the map update equals training_step_fused(gt_depth=...)'s, terms is [mean L1, mean SSIM, L_d].
     gt_depth=None or lambda_depth=0 is exactly the colour-only step."""
-    from . import rasterizer as rz
     fl = fused_loss or _default_fused_loss()
-    dev = model.device
-    e = torch.empty(0, device=dev)
+    use_depth = gt_depth is not None and lambda_depth != 0.0
     cam = camera
     with torch.no_grad():
-        slab = getattr(model, "_grad_slab", None)
-        if gt_depth is not None and lambda_depth != 0.0:
-            if slab is None or slab.P != model.P:
-                slab = model._grad_slab = GradSlab(model)
-            bwd, radii, terms = _pose_depth_forward_losses(model, cam, gt_image, bg, fl, gt_depth, float(lambda_depth))
-            out = rz.rasterize_gaussians_backward_depth(*bwd, raw_params=True, out=slab.views, camera_grads=True)
-        else:
-            xyz, dc, rest = model.xyz.detach(), model.features_dc.detach(), model.features_rest.detach()
-            op, sc, rot = model.opacity.detach(), model.scaling.detach(), model.rotation.detach()
-            (R, B, image, _final_T, radii, geom, binning, img, sample) = rz.rasterize_gaussians(
-                bg, xyz, e, op, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-                cam.image_height, cam.image_width, float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dc, rest,
-                model.sh_degree, cam.d_camera_center, False, False, False, raw_params=True, tie_rank=getattr(model, "tie_rank", None))
-            dL_dimage, terms = fl.forward_backward(image, gt_image)
-            if slab is None or slab.P != model.P:
-                slab = model._grad_slab = GradSlab(model)
-            out = rz.rasterize_gaussians_backward(
-                bg, xyz, radii, e, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-                float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dL_dimage, dc, rest, model.sh_degree,
-                cam.d_camera_center, geom, R, binning, img, B, sample, model.lambda_erank, False, raw_params=True, out=slab.views, camera_grads=True)
+        if use_depth:
+            _grad_slab(model)   # (the depth step sets the slab up ahead of its forward, the colour step behind its loss: both as they were)
+        rr = _RawRaster(model, cam, bg, use_depth)
+        image, depth, radii = rr.forward()
+        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth))
+        slab = _grad_slab(model)
+        out = rr.backward(dL_dimage, dL_ddepth, out=slab.views, camera_grads=True)
         visible = radii > 0
         model.optimizer.set_visibility_and_N(visible, model.P)
         model.optimizer.step(slab.grads(model))
         g = cam.pose_gradient(out[9], out[10], out[11])
         if pose_lr:
-            cam.apply_pose_increment(-float(pose_lr) * g).to_device(dev)
+            cam.apply_pose_increment(-float(pose_lr) * g).to_device(model.device)
     return terms, visible, g
 
 
@@ -676,51 +677,41 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
     (gslic_rasterize_backward_depth_adam) or, adam_in_backward=False, the depth backward and SparseGaussianAdam.step; terms is then
     [mean L1, mean SSIM, L_d] and the loss FusedLoss.value(terms, lambda_depth).  gt_depth=None or lambda_depth=0 is exactly the colour-only
     step.  Single GPU only: the N > 1 exchange carries no depth gradient (NotImplementedError)."""
-    from . import rasterizer as rz
     fl = fused_loss or _default_fused_loss()
-    if gt_depth is not None and lambda_depth != 0.0:
-        if _dist_on():
-            raise NotImplementedError("training_step_fused with depth supervision is single-GPU only: the N > 1 gradient exchange (rank1 / slab "
-                                      "all-reduce) carries no depth gradient; use training_step(gt_depth=...) or run on one GPU")
-        return _training_step_fused_depth(model, camera, gt_image, bg, fl, do_step, adam_in_backward, gt_depth, float(lambda_depth))
+    use_depth = gt_depth is not None and lambda_depth != 0.0
+    if use_depth and _dist_on():
+        raise NotImplementedError("training_step_fused with depth supervision is single-GPU only: the N > 1 gradient exchange (rank1 / slab "
+                                  "all-reduce) carries no depth gradient; use training_step(gt_depth=...) or run on one GPU")
     dev = model.device
-    e = torch.empty(0, device=dev)
+    cam = camera
     if DIST_TIMING is not None and do_step and _dist_on():
         _dist_mark("start")
     with torch.no_grad():
-        xyz, dc, rest = model.xyz.detach(), model.features_dc.detach(), model.features_rest.detach()
-        op, sc, rot = model.opacity.detach(), model.scaling.detach(), model.rotation.detach()
-        cam = camera
-        (R, B, image, _final_T, radii, geom, binning, img, sample) = rz.rasterize_gaussians(
-            bg, xyz, e, op, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-            cam.image_height, cam.image_width, float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dc, rest,
-            model.sh_degree, cam.d_camera_center, False, False, False, raw_params=True, tie_rank=getattr(model, "tie_rank", None))
-        dL_dimage, terms = fl.forward_backward(image, gt_image)
+        rr = _RawRaster(model, cam, bg, use_depth)
+        image, depth, radii = rr.forward()
+        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth))
         if do_step and adam_in_backward and not _dist_on():
             # single GPU: nothing to exchange, so the Adam update runs inside the per-Gaussian backward kernel while the
-            # gradients are still in registers / LDS (bit-identical to backward + SparseGaussianAdam.step, ~2 GB less HBM traffic)
+            # gradients are still in registers / LDS (bit-identical to backward + SparseGaussianAdam.step, ~2 GB less HBM traffic);
+            # under depth supervision every group but xyz there, xyz once dL/dz is in (its gradient is assembled in a buffer kept on the model)
+            xg = None
+            if use_depth:
+                xg = getattr(model, "_depth_xyz_grad", None)
+                if xg is None or xg.shape[0] != model.P or xg.device != rr.xyz.device:
+                    xg = model._depth_xyz_grad = torch.empty(model.P, 3, dtype=torch.float32, device=dev)
             vis_u8 = torch.empty(model.P, dtype=torch.uint8, device=dev)
-            rz.rasterize_gaussians_backward(
-                bg, xyz, radii, e, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx),
-                float(cam.tanfovy), float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dL_dimage, dc, rest,
-                model.sh_degree, cam.d_camera_center, geom, R, binning, img, B, sample, model.lambda_erank, False, raw_params=True,
-                adam=model.optimizer.fused_descriptor(visible_out=vis_u8))
+            rr.backward(dL_dimage, dL_ddepth, adam=model.optimizer.fused_descriptor(visible_out=vis_u8), xyz_grad=xg)
             model.optimizer.count_step()
             return terms, vis_u8.view(torch.bool)   # `radii > 0` (renderer.cpp:85), written by the backward kernel: no compare launch
-        slab = getattr(model, "_grad_slab", None)
-        if slab is None or slab.P != model.P:
-            slab = model._grad_slab = GradSlab(model)
+        slab = _grad_slab(model)
         mode = exchange_mode() if (do_step and _dist_on()) else None
         if mode == "rank1" and exchange_chunks() > 1 and os.environ.get("GSLIC_RANK1_SPLIT_ADAM") != "1":
-            visible = training_step_rank1_chunked(model, cam, bg, dL_dimage, (R, B, radii, geom, binning, img, sample), exchange_chunks())
+            visible = training_step_rank1_chunked(model, cam, bg, dL_dimage, rr.state, exchange_chunks())
             return terms, visible
         if mode == "rank1":
-            # the SH gradients travel as the 3-float colour gradient they are the outer product of (exchange_rank1)
-            rz.rasterize_gaussians_backward(
-                bg, xyz, radii, e, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-                float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dL_dimage, dc, rest, model.sh_degree,
-                cam.d_camera_center, geom, R, binning, img, B, sample, model.lambda_erank, False, raw_params=True, out=slab.views, rgb_out=slab.rgb,
-                payload=(slab.pay_vis, slab.pay_campos))   # mask and camera centre of the all-gather payload come out of the same kernel
+            # the SH gradients travel as the 3-float colour gradient they are the outer product of (exchange_rank1);
+            # mask and camera centre of the all-gather payload come out of the same kernel
+            rr.backward(dL_dimage, out=slab.views, rgb_out=slab.rgb, payload=(slab.pay_vis, slab.pay_campos))
             _dist_mark("bwd_done")
             visible, works = exchange_rank1(slab, slab.rgb, None, model, None)
             model.optimizer.set_visibility_and_N(visible, model.P)
@@ -730,10 +721,7 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
                 model.optimizer.step(grads, only=idx)
             _dist_mark("end")
             return terms, visible
-        rz.rasterize_gaussians_backward(
-            bg, xyz, radii, e, sc, rot, 1.0, e, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-            float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dL_dimage, dc, rest, model.sh_degree,
-            cam.d_camera_center, geom, R, binning, img, B, sample, model.lambda_erank, False, raw_params=True, out=slab.views)
+        rr.backward(dL_dimage, dL_ddepth, out=slab.views)
         visible = radii > 0
         if do_step:
             if _dist_on():
@@ -758,44 +746,6 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
                 model.optimizer.step(slab.grads(model))       # group order of gaussian.cpp:399-418
             if _dist_on():
                 _dist_mark("end")
-    return terms, visible
-
-
-def _training_step_fused_depth(model, cam, gt_image, bg, fl, do_step, adam_in_backward, gt_depth, lambda_depth):
-    """training_step_fused with LiDAR depth supervision (single GPU; see there)."""
-    from . import rasterizer as rz
-    dev = model.device
-    with torch.no_grad():
-        xyz, dc, rest = model.xyz.detach(), model.features_dc.detach(), model.features_rest.detach()
-        op, sc, rot = model.opacity.detach(), model.scaling.detach(), model.rotation.detach()
-        (R, B, image, _final_T, depth, radii, geom, binning, img, sample) = rz.rasterize_gaussians_depth(
-            bg, xyz, op, sc, rot, 1.0, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-            cam.image_height, cam.image_width, float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dc, rest,
-            model.sh_degree, cam.d_camera_center, raw_params=True, tie_rank=getattr(model, "tie_rank", None))
-        dL_dimage, _ = fl.forward_backward(image, gt_image)
-        dL_ddepth, _ = fl.depth_forward_backward(depth, gt_depth, lambda_depth)
-        terms = fl.terms3
-        bwd = (bg, xyz, radii, sc, rot, 1.0, cam.d_world_view_transform, cam.d_full_proj_transform, float(cam.tanfovx), float(cam.tanfovy),
-               float(cam.limx_neg), float(cam.limx_pos), float(cam.limy_neg), float(cam.limy_pos), dL_dimage, dL_ddepth, dc, rest, model.sh_degree,
-               cam.d_camera_center, geom, R, binning, img, B, sample, model.lambda_erank, False)
-        if do_step and adam_in_backward:
-            # the Adam update inside the backward (every group but xyz in the per-Gaussian kernel, xyz once dL/dz is in): bit-identical to the
-            # depth backward + SparseGaussianAdam.step below
-            xg = getattr(model, "_depth_xyz_grad", None)
-            if xg is None or xg.shape[0] != model.P or xg.device != xyz.device:
-                xg = model._depth_xyz_grad = torch.empty(model.P, 3, dtype=torch.float32, device=dev)
-            vis_u8 = torch.empty(model.P, dtype=torch.uint8, device=dev)
-            rz.rasterize_gaussians_backward_depth(*bwd, raw_params=True, adam=model.optimizer.fused_descriptor(visible_out=vis_u8), xyz_grad=xg)
-            model.optimizer.count_step()
-            return terms, vis_u8.view(torch.bool)
-        slab = getattr(model, "_grad_slab", None)
-        if slab is None or slab.P != model.P:
-            slab = model._grad_slab = GradSlab(model)
-        rz.rasterize_gaussians_backward_depth(*bwd, raw_params=True, out=slab.views)
-        visible = radii > 0
-        if do_step:
-            model.optimizer.set_visibility_and_N(visible, model.P)
-            model.optimizer.step(slab.grads(model))
     return terms, visible
 
 
@@ -845,7 +795,6 @@ class GraphedStep:
         on ROCm 7.2 a replay FAULTS (GPU memory access fault) when the host has called torch.cuda.synchronize() and then enqueued ANY other device
         work — a copy, a fill — before it (tools/experiments/graph_check_repro.py, modes B / C / E; a synchronise alone, or a blocking .cpu() copy
         alone, is harmless: modes A / D / F).  A host that uses the graph must keep its own device work off that pattern."""
-        from . import rasterizer as rz
         assert not _dist_on(), "GraphedStep is the single-GPU path"
         self.use_graph = bool(use_graph)
         self.model, self.bg, self.headroom, self.check_every = model, bg, float(headroom), int(check_every)
@@ -863,11 +812,9 @@ class GraphedStep:
         self.e = torch.empty(0, device=dev)
         # sizes from one eager forward of the current state
         with torch.no_grad():
-            R, B = rz.rasterize_gaussians(bg, model.xyz.detach(), self.e, model.opacity.detach(), model.scaling.detach(), model.rotation.detach(),
-                                          1.0, self.e, self.view, self.proj, float(camera.tanfovx), float(camera.tanfovy), self.H, self.W,
-                                          float(camera.limx_neg), float(camera.limx_pos), float(camera.limy_neg), float(camera.limy_pos),
-                                          model.features_dc.detach(), model.features_rest.detach(), model.sh_degree, self.campos, False, False,
-                                          False, raw_params=True, tie_rank=getattr(model, "tie_rank", None))[:2]
+            sizing = _RawRaster(model, camera, bg, False, e=self.e, pose=(self.view, self.proj, self.campos))
+            sizing.forward()
+            R, B = sizing.state[:2]
         self.cap_R, self.cap_B = int(R * self.headroom) + 65536, int(B * self.headroom) + 1024
         if cap_R is not None:
             self.cap_R = int(cap_R)
@@ -881,29 +828,10 @@ class GraphedStep:
         self._capture()
 
     def _eager(self):
-        from . import rasterizer as rz
-        m, c = self.model, self.cam
-        xyz, dc, rest = m.xyz.detach(), m.features_dc.detach(), m.features_rest.detach()
-        op, sc, rot = m.opacity.detach(), m.scaling.detach(), m.rotation.detach()
-        scal = (float(c.tanfovx), float(c.tanfovy), float(c.limx_neg), float(c.limx_pos), float(c.limy_neg), float(c.limy_pos))
-        if self.use_depth:
-            (R, B, image, _T, depth, radii, geom, binning, img, sample) = rz.rasterize_gaussians_depth_capacity(
-                self.bufs, self.bg, xyz, op, sc, rot, 1.0, self.view, self.proj, *scal, dc, rest, m.sh_degree, self.campos, raw_params=True,
-                tie_rank=getattr(m, "tie_rank", None))
-            dL_dimage, _ = self.fl.forward_backward(image, self.gt)
-            dL_ddepth, _ = self.fl.depth_forward_backward(depth, self.gt_depth, self.lambda_depth)
-            self.terms = self.fl.terms3
-            rz.rasterize_gaussians_backward_depth(self.bg, xyz, radii, sc, rot, 1.0, self.view, self.proj, *scal, dL_dimage, dL_ddepth, dc, rest,
-                                                  m.sh_degree, self.campos, geom, R, binning, img, B, sample, m.lambda_erank, False, raw_params=True,
-                                                  adam=self._adam, xyz_grad=self._xyz_grad)
-            return
-        (R, B, image, _T, radii, geom, binning, img, sample) = rz.rasterize_gaussians_capacity(
-            self.bufs, self.bg, xyz, op, sc, rot, 1.0, self.view, self.proj, *scal, dc, rest, m.sh_degree, self.campos, raw_params=True,
-            tie_rank=getattr(m, "tie_rank", None))
-        dL_dimage, self.terms = self.fl.forward_backward(image, self.gt)
-        rz.rasterize_gaussians_backward(self.bg, xyz, radii, self.e, sc, rot, 1.0, self.e, self.view, self.proj, scal[0], scal[1], *scal[2:],
-                                        dL_dimage, dc, rest, m.sh_degree, self.campos, geom, R, binning, img, B, sample, m.lambda_erank, False,
-                                        raw_params=True, adam=self._adam)
+        rr = _RawRaster(self.model, self.cam, self.bg, self.use_depth, e=self.e, pose=(self.view, self.proj, self.campos))
+        image, depth, _radii = rr.forward(self.bufs)
+        dL_dimage, dL_ddepth, self.terms = _fused_losses(self.fl, image, self.gt, depth, self.gt_depth, self.lambda_depth)
+        rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad)
 
     def _capture(self):
         from . import rasterizer as rz

@@ -28,6 +28,11 @@ class AdamGroup(ctypes.Structure):
                 ("exp_avg_sq", ctypes.c_void_p), ("lr", ctypes.c_float), ("M", ctypes.c_uint32)]
 
 
+class RowArray(ctypes.Structure):
+    """gslic_row_array: one per-row array of gslic_gather_rows (device pointers; row width in 4-byte words)."""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("row_dwords", ctypes.c_uint32)]
+
+
 class AdamFused(ctypes.Structure):
     _fields_ = [("param", ctypes.c_void_p * 6), ("exp_avg", ctypes.c_void_p * 6), ("exp_avg_sq", ctypes.c_void_p * 6),
                 ("lr", ctypes.c_float * 6), ("b1", ctypes.c_float), ("b2", ctypes.c_float), ("eps", ctypes.c_float), ("visible_out", ctypes.c_void_p)]
@@ -45,7 +50,7 @@ EXPORTS = [
     "gslic_rasterize_forward_depth", "gslic_rasterize_backward_depth",
     "gslic_rasterize_forward_depth_capacity", "gslic_rasterize_backward_depth_adam", "gslic_depth_l1_loss_partials_count",
     "gslic_depth_l1_loss_forward_backward", "gslic_img_bytes_depth", "gslic_binning_bytes_depth", "gslic_sample_bytes_depth",
-    "gslic_rasterize_backward_depth_camera",
+    "gslic_rasterize_backward_depth_camera", "gslic_prune_select", "gslic_gather_rows",
 ]
 
 _lib = None
@@ -114,6 +119,9 @@ def lib():
     L.gslic_extend_select.argtypes = [i32, vp, vp, vp, vp, f32, f32, f32, f32, i32, i32, vp, ALLOC_FN, vp,
                                       ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i32), vp]
     L.gslic_extend_emit.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.gslic_prune_select.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, i32, ALLOC_FN, vp, vp, vp,
+                                     ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
+    L.gslic_gather_rows.argtypes = [ctypes.POINTER(RowArray), i32, vp, i32, vp]
     L.gslic_debug_export.argtypes = [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 4 + [vp] * 10 + [vp]
     L.gslic_loss_partials_count.restype = ctypes.c_int64
     L.gslic_loss_partials_count.argtypes = [i32, i32, i32, i32]

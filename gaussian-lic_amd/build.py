@@ -32,6 +32,7 @@ SOURCES = {
     "depth_loss.hip": [],    # the maps are held bit-exact to the reference kernels under the same flag (tests/golden/ssim_*.npz)
     "knn.hip": [],
     "extend.hip": ["-ffp-contract=off"],  # pixel assignment decides integers: canonical order like preprocess.hip
+    "prune.hip": [],         # comparisons and copies only: no arithmetic a flag could change
 }
 COMMON = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-Wno-inline-asm",
           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]

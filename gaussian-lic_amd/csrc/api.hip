@@ -41,7 +41,7 @@ static bool g_prof_cur_on = false;
 static const char* const k_names[K_COUNT] = {
     "preprocess", "scan_reduce", "scan_spine", "scan_apply", "keybuild", "sort_hist", "sort_scatter", "finalize_lists",
     "bucket_count", "render_fwd", "render_bwd", "preprocess_bwd", "adam", "ssim_fwd", "ssim_bwd", "knn_minmax", "knn_morton",
-    "knn_boxes", "knn_search", "debug_export", "extend", "dsort_hist", "dsort_scatter", "sh_grad_from_rgb", "tile_lsort", "tile_hist", "tile_bin", "tile_scan", "tile_lsort_long", "depth_loss"};
+    "knn_boxes", "knn_search", "debug_export", "extend", "dsort_hist", "dsort_scatter", "sh_grad_from_rgb", "tile_lsort", "tile_hist", "tile_bin", "tile_scan", "tile_lsort_long", "depth_loss", "prune_select", "gather_rows"};
 uint32_t g_lds_pad[K_COUNT] = {0};
 static const bool g_lds_pad_parsed = [] {   // GSLIC_LDS_PAD="name=bytes,name=bytes"
     const char* e = getenv("GSLIC_LDS_PAD");
@@ -1243,6 +1243,45 @@ int gslic_extend_emit(int32_t n, const uint32_t* keep_flags, const uint32_t* kee
         return set_error(GSLIC_ERR_INVALID_ARG, "extend emit: NULL pointer");
     return extend_emit(n, keep_flags, keep_pos, points, colors, depths_rsp, scaling_scale, focal, M, xyz, dc, rest, opacity, scaling,
                        rotation, (hipStream_t)stream);
+}
+
+int gslic_prune_select(int32_t P, const float* xyz, const float* dc, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw,
+                       float opacity_raw_min, float scaling_raw_max, int32_t drop_nonfinite, const uint8_t* drop, const uint8_t* protect,
+                       const uint32_t* tie_rank, int32_t split_row, gslic_alloc_fn scratch_alloc, void* scratch_ctx, uint32_t* kept_index,
+                       uint32_t* new_tie, int32_t* count, int32_t* count_below, void* stream)
+{
+    if (!count || !count_below) return set_error(GSLIC_ERR_INVALID_ARG, "prune select: NULL count output");
+    *count = 0; *count_below = 0;
+    if (P < 0) return set_error(GSLIC_ERR_INVALID_ARG, "prune select: negative P");
+    if (P == 0) return GSLIC_OK;
+    if (!xyz || !dc || !opacity_raw || !scaling_raw || !rotation_raw || !kept_index || !scratch_alloc)
+        return set_error(GSLIC_ERR_INVALID_ARG, "prune select: NULL pointer");
+    return prune_select(P, xyz, dc, opacity_raw, scaling_raw, rotation_raw, opacity_raw_min, scaling_raw_max, drop_nonfinite, drop, protect, tie_rank,
+                        split_row, scratch_alloc, scratch_ctx, kept_index, new_tie, count, count_below, (hipStream_t)stream);
+}
+
+int gslic_gather_rows(const gslic_row_array* arrays, int32_t n_arrays, const uint32_t* index, int32_t n_rows, void* stream)
+{
+    if (n_arrays < 0 || n_rows < 0) return set_error(GSLIC_ERR_INVALID_ARG, "gather rows: negative n_arrays / n_rows");
+    if (n_arrays == 0 || n_rows == 0) return GSLIC_OK;
+    if (!arrays || !index) return set_error(GSLIC_ERR_INVALID_ARG, "gather rows: NULL pointer");
+    // byte ranges of the first n_rows rows: [lo, hi) of every source and destination
+    auto lo = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    auto hi = [&](const void* p, const gslic_row_array& a) { return reinterpret_cast<uintptr_t>(p) + (size_t)n_rows * a.row_dwords * sizeof(uint32_t); };
+    for (int i = 0; i < n_arrays; i++) {
+        const gslic_row_array& a = arrays[i];
+        if (a.row_dwords == 0) continue;
+        if (!a.src || !a.dst) return set_error(GSLIC_ERR_INVALID_ARG, "gather rows: array %d has a NULL pointer", i);
+        for (int j = 0; j < n_arrays; j++) {
+            const gslic_row_array& b = arrays[j];
+            if (b.row_dwords == 0 || !b.src || !b.dst) continue;
+            if (lo(a.dst) < hi(b.src, b) && lo(b.src) < hi(a.dst, a))
+                return set_error(GSLIC_ERR_INVALID_ARG, "gather rows: dst of array %d overlaps src of array %d (the gather is out of place)", i, j);
+            if (j != i && lo(a.dst) < hi(b.dst, b) && lo(b.dst) < hi(a.dst, a))
+                return set_error(GSLIC_ERR_INVALID_ARG, "gather rows: dst of array %d overlaps dst of array %d", i, j);
+        }
+    }
+    return gather_rows(arrays, n_arrays, index, n_rows, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -69,6 +69,8 @@ enum KernelId {
     K_TILE_SCAN,
     K_TILE_LSORT_LONG,
     K_DEPTH_LOSS,
+    K_PRUNE_SELECT,
+    K_GATHER_ROWS,
     K_COUNT
 };
 void prof_begin(int id, hipStream_t s);

@@ -139,4 +139,11 @@ struct ShGradFromRgbArgs {
 };
 int launch_sh_grad_from_rgb(const ShGradFromRgbArgs& a, hipStream_t s);
 
+// prune.hip: the keep rule of gslic_prune_select on the raw parameters -> kept_index / new_tie / the two counts (one stream synchronisation), and
+// the gather of gslic_gather_rows (arguments validated by the caller; arrays of width 0 are skipped)
+int prune_select(int P, const float* xyz, const float* dc, const float* opacity, const float* scaling, const float* rotation, float opacity_min,
+                 float scaling_max, int drop_nonfinite, const uint8_t* drop, const uint8_t* protect, const uint32_t* tie_rank, int split_row,
+                 gslic_alloc_fn alloc, void* ctx, uint32_t* kept_index, uint32_t* new_tie, int32_t* count, int32_t* count_below, hipStream_t s);
+int gather_rows(const gslic_row_array* arrays, int n_arrays, const uint32_t* index, int n_rows, hipStream_t s);
+
 }  // namespace gslic

@@ -101,6 +101,7 @@ def _build_check(CHECK, first_includes, force, extra_src=()):
 CHECK_FUSED = os.path.join(PKG, "fused_check")
 CHECK_FUSED_DEPTH = os.path.join(PKG, "fused_depth_check")
 CHECK_FUSED_DEPTH_POSE = os.path.join(PKG, "fused_depth_pose_check")
+CHECK_FUSED_PRUNE = os.path.join(PKG, "fused_prune_check")
 
 
 def build_fused_check(force=False):
@@ -119,6 +120,11 @@ def build_fused_depth_pose_check(force=False):
     """fused_depth_pose_check: the camera-pose gradient with LiDAR depth supervision from C++ (gslic::FusedStep::pose_gradient with gt_depth) —
     built like fused_check."""
     return _build_fused_program(os.path.join(HERE, "fused_depth_pose_check.cpp"), CHECK_FUSED_DEPTH_POSE, force)
+
+
+def build_fused_prune_check(force=False):
+    """fused_prune_check: pruning the map from C++ (gslic::FusedStep::prune between fused steps) — built like fused_check."""
+    return _build_fused_program(os.path.join(HERE, "fused_prune_check.cpp"), CHECK_FUSED_PRUNE, force)
 
 
 def _build_fused_program(src, CHECK_FUSED, force):
@@ -154,3 +160,4 @@ if __name__ == "__main__":
     print(build_fused_check(force="--force" in sys.argv))
     print(build_fused_depth_check(force="--force" in sys.argv))
     print(build_fused_depth_pose_check(force="--force" in sys.argv))
+    print(build_fused_prune_check(force="--force" in sys.argv))

@@ -25,6 +25,9 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
+#include <limits>
+#include <optional>
 #include <vector>
 
 #include "gslic_stream.h"
@@ -130,6 +133,68 @@ public:
         bind(P + count);
         torch::cuda::synchronize();   // (the selection scratch is released on return)
         return count;
+    }
+    // Removes rows from the map on the device — the Python host's GaussianModel.prune (gaussian-lic_amd/trainer.py), same calls, same result:
+    // ONE gslic_prune_select (which rows stay) and ONE gslic_gather_rows over the 18 parameter and moment arrays, out of place into fresh storage
+    // of the same capacity.  min_opacity in (0, 1) and max_scale > 0 are limits in the ACTIVATED domain (nullopt: no limit); each is converted
+    // once, in double, to logit(min_opacity) / log(max_scale) and rounded to float — the two thresholds of the raw-domain rule of
+    // include/gslic_hip.h: a row goes when raw opacity < logit(min_opacity), some raw scaling > log(max_scale) (both strict) or drop[row] is set,
+    // unless protect[row] is set; a row with a non-finite xyz / features_dc / opacity / scaling / rotation goes always (drop_nonfinite).
+    // drop / protect: undefined or bool / uint8 [P] on the map's device.  A tie rank (set_tie_rank) is replaced by the kept rows' dense ranks.
+    // Returns the kept rows' OLD indices (device int64 [P'], ascending): per-row state the host keeps is re-aligned with index_select(0, kept).
+    // After a call that removed rows the six parameter tensors are NEW views: fetch them with param(i).
+    torch::Tensor prune(std::optional<double> min_opacity, std::optional<double> max_scale, const torch::Tensor& drop = torch::Tensor(),
+                        const torch::Tensor& protect = torch::Tensor(), bool drop_nonfinite = true)
+    {
+        torch::NoGradGuard ng;
+        const int64_t P = prm_[0].size(0);
+        auto io = prm_[0].options().requires_grad(false).dtype(torch::kInt32);
+        float lo = -std::numeric_limits<float>::infinity(), hi = std::numeric_limits<float>::infinity();
+        if (min_opacity) {
+            TORCH_CHECK(*min_opacity > 0.0 && *min_opacity < 1.0, "FusedStep::prune: min_opacity must lie in (0, 1)");
+            lo = (float)std::log(*min_opacity / (1.0 - *min_opacity));
+        }
+        if (max_scale) {
+            TORCH_CHECK(*max_scale > 0.0 && std::isfinite(*max_scale), "FusedStep::prune: max_scale must be a finite number > 0");
+            hi = (float)std::log(*max_scale);
+        }
+        if (P == 0) return torch::empty({0}, io.dtype(torch::kInt64));
+        auto mask = [&](const torch::Tensor& t, const char* what) {
+            if (!t.defined()) return torch::Tensor();
+            TORCH_CHECK(t.dim() == 1 && t.size(0) == P && (t.scalar_type() == torch::kBool || t.scalar_type() == torch::kByte),
+                        "FusedStep::prune: ", what, " must be a bool / uint8 tensor of ", P, " rows");
+            return t.to(prm_[0].device()).to(torch::kByte).contiguous();
+        };
+        const torch::Tensor dr = mask(drop, "drop"), pr = mask(protect, "protect");
+        auto u8 = [](const torch::Tensor& t) { return t.defined() ? t.data_ptr<uint8_t>() : nullptr; };
+        torch::Tensor kept = torch::empty({P}, io), new_tie = tie_.defined() ? torch::empty({P}, io) : torch::Tensor();
+        torch::Tensor sel_scratch = torch::empty({0}, io.dtype(torch::kByte));
+        int32_t count = 0, below = 0;
+        check(gslic_prune_select((int32_t)P, f(prm_[0]), f(prm_[1]), f(prm_[3]), f(prm_[4]), f(prm_[5]), lo, hi, drop_nonfinite ? 1 : 0, u8(dr), u8(pr),
+                                 tie_.defined() ? reinterpret_cast<const uint32_t*>(tie_.data_ptr<int32_t>()) : nullptr, (int32_t)P, grow_cb, &sel_scratch,
+                                 reinterpret_cast<uint32_t*>(kept.data_ptr<int32_t>()),
+                                 new_tie.defined() ? reinterpret_cast<uint32_t*>(new_tie.data_ptr<int32_t>()) : nullptr, &count, &below, current_stream()),
+              "gslic_prune_select");
+        if (count == P) return torch::arange(P, io.dtype(torch::kInt64));
+        const int64_t cap = capacity();
+        std::array<torch::Tensor, 6> nb, nm, nv;
+        std::vector<gslic_row_array> rows;
+        for (int g = 0; g < 6; g++) {
+            std::vector<int64_t> shp = prm_[g].sizes().vec();
+            shp[0] = cap;
+            nb[g] = torch::empty(shp, prm_[g].options().requires_grad(false)); nm[g] = torch::empty(shp, m_[g].options()); nv[g] = torch::empty(shp, v_[g].options());
+            const uint32_t w = (uint32_t)(prm_[g].numel() / P);
+            if (w == 0) continue;   // features_rest at SH degree 0
+            rows.push_back({prm_[g].data_ptr(), nb[g].data_ptr(), w});
+            rows.push_back({m_[g].data_ptr(), nm[g].data_ptr(), w});
+            rows.push_back({v_[g].data_ptr(), nv[g].data_ptr(), w});
+        }
+        check(gslic_gather_rows(rows.data(), (int32_t)rows.size(), reinterpret_cast<const uint32_t*>(kept.data_ptr<int32_t>()), count, current_stream()),
+              "gslic_gather_rows");
+        buf_ = nb; mbuf_ = nm; vbuf_ = nv;
+        bind(count);
+        if (tie_.defined()) tie_ = new_tie.narrow(0, 0, count).clone();
+        return kept.narrow(0, 0, count).to(torch::kInt64);
     }
     const torch::Tensor& param(int group) const { return prm_[group]; }
     int64_t size() const { return prm_[0].size(0); }

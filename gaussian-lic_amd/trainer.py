@@ -65,6 +65,27 @@ def morton_order_device(xyz, bits=10):
     return torch.sort(code, stable=True).indices
 
 
+def prune_thresholds(min_opacity=None, max_scale=None):
+    """The two float32 thresholds of the raw-domain keep rule (include/gslic_hip.h: gslic_prune_select) for limits given in the ACTIVATED domain:
+    min_opacity in (0, 1) -> logit(min_opacity) = log(p / (1 - p)), max_scale > 0 -> log(max_scale), each computed ONCE on the host in float64 and
+    rounded to float32.  None disables a threshold (-inf / +inf).  Returns (opacity_raw_min, scaling_raw_max) as Python floats holding float32
+    values: a row is hit when raw opacity < opacity_raw_min or some raw scaling > scaling_raw_max (both strict)."""
+    import math
+    import numpy as np
+    lo, hi = -math.inf, math.inf
+    if min_opacity is not None:
+        p = float(min_opacity)
+        if not 0.0 < p < 1.0:
+            raise ValueError(f"prune: min_opacity must lie in (0, 1), got {min_opacity!r}")
+        lo = float(np.float32(math.log(p / (1.0 - p))))
+    if max_scale is not None:
+        s = float(max_scale)
+        if not (s > 0.0 and math.isfinite(s)):
+            raise ValueError(f"prune: max_scale must be a finite number > 0, got {max_scale!r}")
+        hi = float(np.float32(math.log(s)))
+    return lo, hi
+
+
 class GaussianModel:
     """Parameters + activations of src/gaussian.{h,cpp} that the hot path touches, with capacity-doubling storage so that
     extend() appends rows in place instead of six torch::cat reallocations of every parameter and Adam moment per keyframe
@@ -113,6 +134,7 @@ class GaussianModel:
             self._tie[:self.P].copy_(perm.to(torch.int32))
             self.sort_ms.append(round(1e3 * (_time.perf_counter() - _t0), 2))   # (CPU sort + the permuted upload, once, outside any timed region)
         self._sorted_P = self.P      # rows [0, _sorted_P) are in Morton order (order == "morton")
+        self.layout_version = 0      # counts the calls that replaced the storage and renumbered the rows (prune())
         self.optimizer = None
         self._rebind()
 
@@ -172,6 +194,79 @@ class GaussianModel:
             tie = torch.empty(cap, dtype=torch.int32, device=self.device)
             tie[:self.P].copy_(self._tie[:self.P])
             self._tie = tie
+
+    @torch.no_grad()
+    def prune(self, min_opacity=None, max_scale=None, drop=None, protect=None, drop_nonfinite=True):
+        """Removes rows from the map on the device: one gslic_prune_select (which rows stay) and one gslic_gather_rows over the 18 parameter and
+        moment arrays plus tie_rank (a stable compaction).  Returns (n_removed, kept): kept is a device LongTensor [P'] holding the OLD storage
+        row of every new row — per-row state a host keeps outside the model is re-aligned with x = x[kept].
+
+        min_opacity in (0, 1) and max_scale > 0 are given in the ACTIVATED domain.  Both are converted once on the host, in float64, to
+        logit(min_opacity) and log(max_scale) and each rounded to float32 (prune_thresholds); those two float32 values are the thresholds of
+        the raw-domain rule, which the device evaluates with comparisons only:
+            bad[i]  = any of xyz, features_dc, opacity, scaling, rotation of row i is not finite            (only if drop_nonfinite)
+            hit[i]  = drop[i] or opacity[i] < logit(min_opacity) or max_j scaling[i, j] > log(max_scale)      (raw values; both strict)
+            keep[i] = not bad[i] and (protect[i] or not hit[i])
+        drop / protect: optional bool / uint8 [P] in STORAGE row order (protect: rows that are large by construction, a skybox; a non-finite
+        row goes even when protected).  features_rest is not scanned for non-finite values.  The rule is the host's to parametrise: when to
+        prune and with which limits is policy.
+
+        The gather is out of place: it writes fresh storage of the same capacity, the model adopts it and the old storage is released.
+        Afterwards P = P', tie_rank holds the kept rows' original indices re-ranked densely to 0..P'-1 (what original_order(), save_map and
+        extend()'s "appended row k gets tie k" rely on), the Morton-sorted prefix ends at the kept rows below the old bound, the optimizer is
+        re-bound and layout_version is incremented: anything that baked P or addresses in (GraphedStep) must be rebuilt.  If nothing is
+        removed the storage is left untouched and kept = arange(P).  Works on both row orders and before training_setup().  With N > 1
+        GPUs every rank calls it with identical arguments."""
+        import ctypes
+        from . import _lib
+        L = _lib.lib()
+        dev, P = self.device, self.P
+        lo, hi = prune_thresholds(min_opacity, max_scale)
+        if P == 0:
+            return 0, torch.empty(0, dtype=torch.int64, device=dev)
+
+        def mask(t, what):
+            if t is None:
+                return None
+            t = torch.as_tensor(t, device=dev)
+            if tuple(t.shape) != (P,) or t.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f"prune: {what} must be a bool / uint8 tensor of {P} rows, got {t.dtype} {tuple(t.shape)}")
+            return t.to(torch.uint8).contiguous()
+        drop, protect = mask(drop, "drop"), mask(protect, "protect")
+        p = _lib.ptr
+        kept_index = torch.empty(P, dtype=torch.int32, device=dev)
+        new_tie = torch.empty(P, dtype=torch.int32, device=dev) if self._tie is not None else None
+        scratch = _lib.TensorAllocator(dev)
+        count, below = ctypes.c_int32(0), ctypes.c_int32(0)
+        b = self._buf
+        _lib.check(L.gslic_prune_select(P, p(b["xyz"][:P]), p(b["features_dc"][:P]), p(b["opacity"][:P]), p(b["scaling"][:P]), p(b["rotation"][:P]),
+                                        lo, hi, int(bool(drop_nonfinite)), p(drop), p(protect), p(self.tie_rank), int(self._sorted_P), scratch.cb, None,
+                                        p(kept_index), p(new_tie), ctypes.byref(count), ctypes.byref(below), _lib.current_stream_ptr()))
+        Pn = count.value
+        if Pn == P:
+            return 0, torch.arange(P, dtype=torch.int64, device=dev)
+        cap = self.capacity
+        fresh = [{n: torch.empty_like(d[n]) for n in self.NAMES} for d in (self._buf, self._m, self._v)]
+        rows = []
+        for d, f in zip((self._buf, self._m, self._v), fresh):
+            for n in self.NAMES:
+                w = d[n][0].numel() if cap else 0
+                rows.append(_lib.RowArray(d[n].data_ptr() if w else None, f[n].data_ptr() if w else None, w))
+        tie = None
+        if self._tie is not None:
+            tie = torch.empty_like(self._tie)
+            rows.append(_lib.RowArray(self._tie.data_ptr(), tie.data_ptr(), 1))   # (gathered like every other array, then replaced by the dense ranks)
+        arr = (_lib.RowArray * len(rows))(*rows)
+        _lib.check(L.gslic_gather_rows(arr, len(rows), p(kept_index), Pn, _lib.current_stream_ptr()))
+        self._buf, self._m, self._v = fresh
+        if tie is not None:
+            tie[:Pn].copy_(new_tie[:Pn])
+            self._tie = tie
+        self.P = Pn
+        self._sorted_P = below.value
+        self.layout_version += 1
+        self._rebind()
+        return P - Pn, kept_index[:Pn].long()
 
     # gaussian.cpp:147-175
     def get_xyz(self): return self.xyz
@@ -780,7 +875,7 @@ class GraphedStep:
     end — grows the buffers from the largest counts seen, re-captures and repeats exactly the steps that did not fit, each with ITS
     pose (snapshotted by value) and ground truth (kept by reference with its version counter: a target that was modified in place, or
     replaced while steps were issued with gt_image=None, makes the repeat fail loudly instead of training on the wrong data), after the
-    ones that did.  extend() changes P: build a new GraphedStep afterwards.
+    ones that did.  extend() and prune() change P / the rows: build a new GraphedStep afterwards (step() raises otherwise).
 
     gt_depth [H,W] with lambda_depth != 0 (LiDAR depth supervision): the step is training_step_fused's depth step in capacity mode
     (gslic_rasterize_forward_depth_capacity -> colour and depth loss kernels -> gslic_rasterize_backward_depth_adam).  lambda_depth is baked
@@ -862,6 +957,7 @@ class GraphedStep:
         self.graph = g
         self.steps_issued = 0
         self.window = []
+        self._captured_layout = (self.model.P, getattr(self.model, "layout_version", 0))   # what the buffers, the Adam descriptor and a graph bake in
 
     _BAKED = ("tanfovx", "tanfovy", "limx_neg", "limx_pos", "limy_neg", "limy_pos")   # scalars of the camera that are constants of the captured graph
 
@@ -930,6 +1026,11 @@ class GraphedStep:
                 self._gtd_serial = getattr(self, "_gtd_serial", 0) + 1
 
     def _issue(self):
+        now = (self.model.P, getattr(self.model, "layout_version", 0))
+        if now != self._captured_layout:
+            raise RuntimeError(f"GraphedStep: the model's rows changed since this step was built (P / layout_version {self._captured_layout} -> {now}: "
+                               "extend() or prune()); its buffers, Adam descriptor and graph hold the old row count and addresses — build a new "
+                               "GraphedStep")
         if self.graph is not None:
             self.graph.replay()
         else:

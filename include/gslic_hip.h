@@ -577,6 +577,48 @@ int gslic_extend_emit(
     float* xyz, float* dc, float* rest, float* opacity, float* scaling, float* rotation, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * gslic_prune_select / gslic_gather_rows — removing rows from the map (no reference counterpart: its map only grows; a LibTorch host
+ * would run 19 boolean-index launches with 19 temporaries: 6 groups x {parameter, exp_avg, exp_avg_sq} + tie_rank).
+ *
+ *  select: one thread per row, then the u32 scan.  The rule is defined on the RAW (pre-activation) parameters xyz [P,3], dc [P,3],
+ *          opacity_raw [P], scaling_raw [P,3], rotation_raw [P,4] and involves no transcendental on the device, so the same comparisons on the
+ *          same float32 thresholds reproduce it exactly:
+ *
+ *            bad[i]  = any of xyz[i,0..2], dc[i,0..2], opacity[i], scaling[i,0..2], rotation[i,0..3] is not finite   (only if drop_nonfinite)
+ *            hit[i]  = (drop != NULL && drop[i]) || opacity[i] < opacity_raw_min || max_j scaling[i,j] > scaling_raw_max
+ *            keep[i] = !bad[i] && ((protect != NULL && protect[i]) || !hit[i])
+ *
+ *          Both comparisons are strict: a row AT a threshold stays.  opacity_raw_min = -inf or scaling_raw_max = +inf disables a threshold.
+ *          (max_j ... > t is evaluated as "some scaling[i,j] > t": a NaN component compares false.)  features_rest is NOT scanned for
+ *          non-finite values (180 B per row at SH degree 3).  protect is for rows that are large by construction (a skybox); a non-finite
+ *          row goes even when protected.  drop / protect: one byte per row, non-zero = set.
+ *          Outputs: kept_index (DEVICE [P]) — its first *count entries are the old row indices of the kept rows, ascending (a stable
+ *          compaction); *count (host) — the number of kept rows, reading it is the call's one stream synchronisation; *count_below (host) —
+ *          the kept rows with old index < split_row (a host that keeps rows [0, split_row) sorted moves that bound to it; split_row <= 0
+ *          gives 0, split_row >= P gives *count); new_tie (DEVICE, its first *count entries), written only when tie_rank and new_tie are
+ *          both given — the kept rows' ORIGINAL indices (gslic_raster_params.tie_rank, a permutation of 0..P-1) re-ranked densely:
+ *          a permutation of 0..*count-1 in the same relative order as the old tie_rank of the kept rows.  Dense ranks keep "row appended as
+ *          number k gets tie k" collision-free after a prune.  Scratch (16 P bytes, 8 P without ties) comes from the caller's allocator and
+ *          is dead when the call returns.
+ *  gather: dst_a[k, :] = src_a[index[k], :] for k < n_rows and every array a of the HOST array `arrays`, in one launch per 32 arrays
+ *          (the map's 19 arrays: one).  Rows are row_dwords 4-byte words wide (any width >= 1; an array of width 0 is skipped);
+ *          index [n_rows] is on the DEVICE, every entry below the source's row count.  src and dst must not overlap — tested on
+ *          the first n_rows rows of every src against every dst, and dst against dst, before any device work: GSLIC_ERR_INVALID_ARG.
+ *          No atomics; rows of dst from n_rows on are not written.
+ *  P == 0 / n_rows == 0 / n_arrays == 0 return at once (no allocator call); negative sizes and NULL required pointers: GSLIC_ERR_INVALID_ARG.
+ */
+int gslic_prune_select(
+    int32_t P, const float* xyz, const float* dc, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw,
+    float opacity_raw_min, float scaling_raw_max, int32_t drop_nonfinite,
+    const uint8_t* drop /*[P] or NULL*/, const uint8_t* protect /*[P] or NULL*/,
+    const uint32_t* tie_rank /*[P] or NULL*/, int32_t split_row,
+    gslic_alloc_fn scratch_alloc, void* scratch_ctx,
+    uint32_t* kept_index /*[P]*/, uint32_t* new_tie /*[P] or NULL*/, int32_t* count, int32_t* count_below, void* stream);
+
+typedef struct gslic_row_array { const void* src; void* dst; uint32_t row_dwords; } gslic_row_array;   /* HOST array */
+int gslic_gather_rows(const gslic_row_array* arrays, int32_t n_arrays, const uint32_t* index, int32_t n_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Introspection / measurement (no reference counterpart; used by bench.py and the tests).
  */
 int gslic_abi_version(void);

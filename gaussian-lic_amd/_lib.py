@@ -50,7 +50,7 @@ EXPORTS = [
     "gslic_rasterize_forward_depth", "gslic_rasterize_backward_depth",
     "gslic_rasterize_forward_depth_capacity", "gslic_rasterize_backward_depth_adam", "gslic_depth_l1_loss_partials_count",
     "gslic_depth_l1_loss_forward_backward", "gslic_img_bytes_depth", "gslic_binning_bytes_depth", "gslic_sample_bytes_depth",
-    "gslic_rasterize_backward_depth_camera", "gslic_prune_select", "gslic_gather_rows",
+    "gslic_rasterize_backward_depth_camera", "gslic_prune_select", "gslic_gather_rows", "gslic_contribution_accumulate",
 ]
 
 _lib = None
@@ -122,6 +122,7 @@ def lib():
     L.gslic_prune_select.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, i32, ALLOC_FN, vp, vp, vp,
                                      ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.gslic_gather_rows.argtypes = [ctypes.POINTER(RowArray), i32, vp, i32, vp]
+    L.gslic_contribution_accumulate.argtypes = [prm, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp]   # params, R, B, geom / binning / img, w_min, 3 outputs, stream
     L.gslic_debug_export.argtypes = [ctypes.POINTER(RasterParams), i32, i32] + [vp] * 4 + [vp] * 10 + [vp]
     L.gslic_loss_partials_count.restype = ctypes.c_int64
     L.gslic_loss_partials_count.argtypes = [i32, i32, i32, i32]

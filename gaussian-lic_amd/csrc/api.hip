@@ -1284,6 +1284,29 @@ int gslic_gather_rows(const gslic_row_array* arrays, int32_t n_arrays, const uin
     return gather_rows(arrays, n_arrays, index, n_rows, (hipStream_t)stream);
 }
 
+int gslic_contribution_accumulate(const gslic_raster_params* prm, int32_t R, int32_t B, const char* geom_buffer, const char* binning_buffer,
+                                  const char* img_buffer, float w_min, uint32_t* max_w, uint32_t* n_pix, uint64_t* sum_w, void* stream)
+{
+    GS_TRY(check_params(prm));
+    if (R < 0 || B < 0) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: negative R / B");
+    if (prm->no_color) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: a no_color forward stores no n_contrib (nothing says where a pixel stopped)");
+    if (w_min != w_min) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: w_min is NaN");
+    if (prm->P == 0 || R == 0) return GSLIC_OK;
+    if (!geom_buffer || !binning_buffer || !img_buffer) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: NULL forward buffer");
+    if (!max_w && !n_pix && !sum_w) return GSLIC_OK;
+    int gx, gy;
+    const int T = tile_grid(prm->width, prm->height, gx, gy);
+    // the colour-only carve: a prefix of the depth layouts, and the capacity variants carve the same blocks for their capacity R
+    GeomState geom = GeomState::carve(align256(const_cast<char*>(geom_buffer)), (size_t)prm->P, nullptr);
+    ImageState img = ImageState::carve(align256(const_cast<char*>(img_buffer)), (size_t)T, nullptr);
+    BinningState bin = BinningState::carve(align256(const_cast<char*>(binning_buffer)), (size_t)R, sort_end_bit(T), false, nullptr);
+    ContribArgs ca;
+    ca.W = prm->width; ca.H = prm->height; ca.gx = gx; ca.T = T; ca.P = prm->P; ca.R = (uint32_t)R;
+    ca.ranges = img.ranges; ca.point_list = bin.point_list(); ca.rec = geom.rec; ca.pix_final = img.pix_final; ca.status = geom.flags;
+    ca.w_min = w_min; ca.max_w = max_w; ca.n_pix = n_pix; ca.sum_w = reinterpret_cast<unsigned long long*>(sum_w);
+    return launch_contribution(ca, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 int gslic_profile_enable(int32_t on)
 {

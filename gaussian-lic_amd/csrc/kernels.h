@@ -146,4 +146,21 @@ int prune_select(int P, const float* xyz, const float* dc, const float* opacity,
                  gslic_alloc_fn alloc, void* ctx, uint32_t* kept_index, uint32_t* new_tie, int32_t* count, int32_t* count_below, hipStream_t s);
 int gather_rows(const gslic_row_array* arrays, int n_arrays, const uint32_t* index, int n_rows, hipStream_t s);
 
+// contrib.hip: the per-Gaussian contribution statistics of gslic_contribution_accumulate from a completed forward's lists (one workgroup per tile;
+// arguments validated by the caller; any of the three accumulators may be NULL)
+struct ContribArgs {
+    int W, H, gx, T, P;
+    uint32_t R;                       // entries of the point list: the exact count, or the capacity the binning block was carved for
+    const uint2* ranges;              // ImageState::ranges
+    const uint32_t* point_list;       // BinningState::point_list()
+    const float4* rec;                // GeomState::rec
+    const float4* pix_final;          // ImageState::pix_final (.w = n_contrib bits, tile-major)
+    const uint32_t* status;           // GeomState::flags: a non-zero [2] (capacity overflow) makes the kernel return
+    float w_min;
+    uint32_t* max_w;                  // [P] float bits
+    uint32_t* n_pix;                  // [P]
+    unsigned long long* sum_w;        // [P] 32.32 fixed point
+};
+int launch_contribution(const ContribArgs& a, hipStream_t s);
+
 }  // namespace gslic

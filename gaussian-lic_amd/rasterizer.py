@@ -522,6 +522,20 @@ def sh_grad_from_rgb(means3D, campos_all, rgb_all, degree, dL_ddc, dL_dsh, input
                                                  p(dL_dsh) if M else None, int(view_stride), _lib.current_stream_ptr()))
 
 
+def contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, max_w=None, n_pix=None, sum_w=None):
+    """gslic_contribution_accumulate: adds ONE view's per-Gaussian contribution statistics, replayed from the buffers of a completed forward
+    (rasterize_gaussians / _depth / _capacity / _depth_capacity; R, B as that forward returned them), to the caller's accumulators —
+    max_w int32 [>= P] (float bits), n_pix int32 [>= P], sum_w int64 [>= P] (32.32 fixed point), device tensors indexed by storage row, any of
+    them None.  The rule is written out in include/gslic_hip.h.  One launch on the current stream, no synchronisation."""
+    for t, dt in ((max_w, torch.int32), (n_pix, torch.int32), (sum_w, torch.int64)):
+        if t is not None and not (t.is_contiguous() and t.dtype == dt and t.numel() >= int(P)):
+            raise ValueError(f"contribution_accumulate: an accumulator must be a contiguous {dt} tensor of at least {int(P)} rows")
+    prm = _params(P, 0, 0, H, W, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, False, False, False)   # (only P, W and H are read)
+    bp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    _lib.check(_lib.lib().gslic_contribution_accumulate(ctypes.byref(prm), int(R), int(B), bp(geom), bp(binning), bp(img), float(w_min), bp(max_w),
+                                                        bp(n_pix), bp(sum_w), _lib.current_stream_ptr()))
+
+
 def debug_export(settings, P, M, R, B, geom, binning, img, sample, what=("tiles_touched", "point_list", "ranges")):
     """Test-only: copy stage boundaries out of the opaque scratch buffers (gslic_debug_export)."""
     L = _lib.lib()

@@ -42,6 +42,17 @@ struct FusedCamera {
     torch::Tensor world_view_transform, full_proj_transform, camera_center;  // device fp32 [4,4] (stored transposed, camera.h:86,109), [4,4], [3]
 };
 
+// Per-Gaussian contribution statistics accumulated over views (gslic_contribution_accumulate, include/gslic_hip.h) — the Python host's
+// trainer.ContributionStats as plain data: three device arrays indexed by storage row, created (zero) and grown to the map's capacity by
+// FusedStep::accumulate_contribution, carried through FusedStep::prune when handed to it.  Rows behind size() are zero, so rows appended by
+// extend() start at zero.  max_w.view(kFloat32) is the largest weight; sum in float units = sum_w / 2^32.
+struct ContributionStats {
+    torch::Tensor max_w;   // int32 [capacity]: uint32 float bits of the largest w = alpha T
+    torch::Tensor n_pix;   // int32 [capacity]: uint32 count of (pixel, view) pairs with w >= w_min (saturating)
+    torch::Tensor sum_w;   // int64 [capacity]: uint64 sum of w, 32.32 fixed point
+    int64_t views = 0;
+};
+
 class FusedStep {
 public:
     // params: the six raw leaf tensors in the group order of trainingSetup (gaussian.cpp:399-418); updated IN PLACE.
@@ -143,8 +154,9 @@ public:
     // drop / protect: undefined or bool / uint8 [P] on the map's device.  A tie rank (set_tie_rank) is replaced by the kept rows' dense ranks.
     // Returns the kept rows' OLD indices (device int64 [P'], ascending): per-row state the host keeps is re-aligned with index_select(0, kept).
     // After a call that removed rows the six parameter tensors are NEW views: fetch them with param(i).
+    // stats: contribution statistics of this map (accumulate_contribution) — gathered with the map by the same kept index (row widths 1, 1, 2).
     torch::Tensor prune(std::optional<double> min_opacity, std::optional<double> max_scale, const torch::Tensor& drop = torch::Tensor(),
-                        const torch::Tensor& protect = torch::Tensor(), bool drop_nonfinite = true)
+                        const torch::Tensor& protect = torch::Tensor(), bool drop_nonfinite = true, ContributionStats* stats = nullptr)
     {
         torch::NoGradGuard ng;
         const int64_t P = prm_[0].size(0);
@@ -193,8 +205,50 @@ public:
               "gslic_gather_rows");
         buf_ = nb; mbuf_ = nm; vbuf_ = nv;
         bind(count);
+        if (stats && stats->max_w.defined()) {
+            ContributionStats old = *stats;
+            stats->max_w = torch::zeros({cap}, io); stats->n_pix = torch::zeros({cap}, io); stats->sum_w = torch::zeros({cap}, io.dtype(torch::kInt64));
+            if (count > 0) {
+                TORCH_CHECK(old.max_w.size(0) >= P && old.n_pix.size(0) >= P && old.sum_w.size(0) >= P, "FusedStep::prune: the statistics hold fewer rows than the map");
+                const gslic_row_array sr[3] = {{old.max_w.data_ptr(), stats->max_w.data_ptr(), 1u}, {old.n_pix.data_ptr(), stats->n_pix.data_ptr(), 1u},
+                                               {old.sum_w.data_ptr(), stats->sum_w.data_ptr(), 2u}};
+                check(gslic_gather_rows(sr, 3, reinterpret_cast<const uint32_t*>(kept.data_ptr<int32_t>()), count, current_stream()), "gslic_gather_rows (statistics)");
+            }
+        }
         if (tie_.defined()) tie_ = new_tie.narrow(0, 0, count).clone();
         return kept.narrow(0, 0, count).to(torch::kInt64);
+    }
+    // Adds the contribution statistics of ONE view to `stats` — the Python host's ContributionStats.accumulate: a raw-parameter forward of its own
+    // (it reuses the step's scratch; call it between steps) and one gslic_contribution_accumulate on its buffers.  w_min: a (pixel, Gaussian)
+    // pair counts into n_pix when its weight w = alpha T reaches it.  The arrays are created zero-filled on first use and grown to capacity().
+    void accumulate_contribution(const FusedCamera& cam, ContributionStats& stats, float w_min)
+    {
+        torch::NoGradGuard ng;
+        const int64_t P = prm_[0].size(0), cap = capacity();
+        auto io = prm_[0].options().requires_grad(false).dtype(torch::kInt32);
+        auto fit = [&](torch::Tensor& t, torch::ScalarType dt) {
+            if (t.defined() && t.size(0) >= cap) return;
+            torch::Tensor n = torch::zeros({cap}, io.dtype(dt));
+            if (t.defined()) n.narrow(0, 0, t.size(0)).copy_(t);
+            t = n;
+        };
+        fit(stats.max_w, torch::kInt32); fit(stats.n_pix, torch::kInt32); fit(stats.sum_w, torch::kInt64);
+        stats.views++;
+        if (P == 0) return;
+        const int W = cam.image_width, H = cam.image_height;
+        const gslic_raster_params rp = raster_params(cam, true, false);
+        ensure_image_buffers(H, W);
+        ensure_rows(P);
+        int32_t R = 0, B = 0;
+        check(gslic_rasterize_forward(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), f(prm_[0]),
+                                      f(prm_[1]), f(prm_[2]), nullptr, f(prm_[3]), f(prm_[4]), f(prm_[5]), nullptr, f(cam.world_view_transform),
+                                      f(cam.full_proj_transform), f(cam.camera_center), image_.data_ptr<float>(), final_T_.data_ptr<float>(),
+                                      radii_.data_ptr<int32_t>(), &R, &B, current_stream()),
+              "gslic_rasterize_forward");
+        check(gslic_contribution_accumulate(&rp, R, B, cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), w_min,
+                                            reinterpret_cast<uint32_t*>(stats.max_w.data_ptr<int32_t>()), reinterpret_cast<uint32_t*>(stats.n_pix.data_ptr<int32_t>()),
+                                            reinterpret_cast<uint64_t*>(stats.sum_w.data_ptr<int64_t>()), current_stream()),
+              "gslic_contribution_accumulate");
     }
     const torch::Tensor& param(int group) const { return prm_[group]; }
     int64_t size() const { return prm_[0].size(0); }

@@ -135,6 +135,8 @@ class GaussianModel:
             self.sort_ms.append(round(1e3 * (_time.perf_counter() - _t0), 2))   # (CPU sort + the permuted upload, once, outside any timed region)
         self._sorted_P = self.P      # rows [0, _sorted_P) are in Morton order (order == "morton")
         self.layout_version = 0      # counts the calls that replaced the storage and renumbered the rows (prune())
+        self._rows_version = 0       # counts every call that changed which row is where or how many there are (prune(), extend(), resort())
+        self._stats = []             # weak references to the attached ContributionStats: carried through prune() / extend() / resort()
         self.optimizer = None
         self._rebind()
 
@@ -142,8 +144,8 @@ class GaussianModel:
     def resort(self):
         """Puts ALL rows back into Morton order (order == "morton" only): parameters, both Adam moments and tie_rank are permuted together on the
         device, so the map renders, trains and exports exactly as before (tie_rank still holds every row's ORIGINAL index).  Invalidates hipGraph
-        captures of nothing (addresses do not change) but any per-row state a host keeps outside the model must be permuted by the same index:
-        returns the permutation applied (LongTensor [P] on the device; new row s = old row perm[s])."""
+        captures of nothing (addresses do not change) but any per-row state a host keeps outside the model must be permuted by the same index
+        (attached ContributionStats are): returns the permutation applied (LongTensor [P] on the device; new row s = old row perm[s])."""
         assert self._tie is not None, "resort(): the model keeps its rows in insertion order"
         import time as _time
         torch.cuda.synchronize(self.device) if self.device.type == "cuda" else None
@@ -155,6 +157,9 @@ class GaussianModel:
                 d[n][:P] = d[n][:P][perm]
         self._tie[:P] = self._tie[:P][perm]
         self._sorted_P = P
+        self._rows_version += 1
+        for st in self._attached_stats():
+            st._permute(perm)
         self._rebind()
         torch.cuda.synchronize(self.device) if self.device.type == "cuda" else None
         self.sort_ms.append(round(1e3 * (_time.perf_counter() - t0), 2))
@@ -172,6 +177,12 @@ class GaussianModel:
     @property
     def capacity(self):
         return self._buf["xyz"].shape[0]
+
+    def _attached_stats(self):
+        """The live ContributionStats attached to this model (dead references are dropped)."""
+        live = [(r, r()) for r in self._stats]
+        self._stats = [r for r, st in live if st is not None]
+        return [st for _r, st in live if st is not None]
 
     def _rebind(self):
         for n in self.NAMES:
@@ -216,7 +227,7 @@ class GaussianModel:
         extend()'s "appended row k gets tie k" rely on), the Morton-sorted prefix ends at the kept rows below the old bound, the optimizer is
         re-bound and layout_version is incremented: anything that baked P or addresses in (GraphedStep) must be rebuilt.  If nothing is
         removed the storage is left untouched and kept = arange(P).  Works on both row orders and before training_setup().  With N > 1
-        GPUs every rank calls it with identical arguments."""
+        GPUs every rank calls it with identical arguments.  Attached ContributionStats are gathered with the map (the same kept index)."""
         import ctypes
         from . import _lib
         L = _lib.lib()
@@ -265,6 +276,9 @@ class GaussianModel:
         self.P = Pn
         self._sorted_P = below.value
         self.layout_version += 1
+        self._rows_version += 1
+        for st in self._attached_stats():   # the statistics follow their rows: the same gather, on the same kept index
+            st._gather(kept_index, Pn)
         self._rebind()
         return P - Pn, kept_index[:Pn].long()
 
@@ -293,7 +307,7 @@ class GaussianModel:
         """extend() of gaussian.cpp:499-638 for one new frame: transmittance-only render of the latest camera, GPU selection of
         the LiDAR points that land on not-yet-opaque pixels (nearest per pixel), append of the new Gaussians (+ zero Adam moments)
         in place.  points/colors [n,3], depths_rsp [n] on the device; R_cw [3,3], t_cw [3]; intrinsics = (fx, fy, cx, cy).
-        Returns the number of Gaussians inserted."""
+        Returns the number of Gaussians inserted.  Attached ContributionStats get zeros for the appended rows."""
         import ctypes
         from . import _lib
         from .rasterizer import render
@@ -328,11 +342,186 @@ class GaussianModel:
         if self._tie is not None:          # appended rows are in insertion order behind the sorted block: their original index is their row
             self._tie[P0:P0 + k].copy_(torch.arange(P0, P0 + k, dtype=torch.int32, device=dev))
         self.P = P0 + k
+        self._rows_version += 1
+        for st in self._attached_stats():   # appended rows have contributed to nothing yet
+            st._appended(P0, k)
         self._rebind()
         torch.cuda.current_stream().synchronize()  # scratch (flags/pos) is released on return
         if self._tie is not None and self.resort_fraction is not None and (self.P - self._sorted_P) > self.resort_fraction * self.P:
             self.resort()    # the appended tail has grown past resort_fraction of the map: Morton order again (a few ms, between keyframes)
         return k
+
+
+FIXED_FRAC_BITS = 32   # sum_w of gslic_contribution_accumulate: unsigned fixed point with this many fractional bits
+
+
+def weight_to_fixed(x):
+    """float / float64 tensor of non-negative weights -> the int64 bit patterns of their 32.32 fixed-point values, rounded to nearest (ties to even),
+    as the kernel converts a tile's partial sum.  Exact for every float32 weight in [2^-9, 2^31): such a value has no bits below 2^-32."""
+    return torch.round(torch.as_tensor(x, dtype=torch.float64) * float(1 << FIXED_FRAC_BITS)).to(torch.int64)
+
+
+def fixed_to_weight(q):
+    """int64 tensor holding the bit patterns of unsigned 32.32 fixed-point sums -> float64 (the two 32-bit halves are converted separately,
+    so a sum with bit 63 set is not read as negative; exact below 2^21, rounded to float64 above)."""
+    q = torch.as_tensor(q, dtype=torch.int64)
+    hi, lo = (q >> 32) & 0xffffffff, q & 0xffffffff
+    return hi.to(torch.float64) + lo.to(torch.float64) / float(1 << FIXED_FRAC_BITS)
+
+
+def contribution_drop_mask(max_w, n_pix, max_weight_below=None, pixels_below=None):
+    """uint8 [P]: 1 where max_w < max_weight_below (float32 comparison) OR n_pix < pixels_below (integer comparison); a limit of None takes
+    no part.  max_w float32 [P], n_pix integer [P].  Comparisons only: the same expression in torch on ContributionStats.max_weight() /
+    .pixels() gives the same mask."""
+    import numpy as np
+    drop = torch.zeros(max_w.shape[0], dtype=torch.bool, device=max_w.device)
+    if max_weight_below is not None:
+        drop |= max_w < float(np.float32(max_weight_below))
+    if pixels_below is not None:
+        drop |= n_pix < int(pixels_below)
+    return drop.to(torch.uint8)
+
+
+class ContributionStats:
+    """Per-Gaussian contribution statistics accumulated over views (gslic_contribution_accumulate, include/gslic_hip.h): for every storage row
+    the largest blend weight w = alpha T it reached in a pixel, the number of (pixel, view) pairs where w >= w_min, and the sum of w — what a
+    mapper decides by whether a Gaussian ever contributes, which raw opacity and scale do not say.  When to accumulate, over which keyframes
+    and with which limits to prune is the host's policy.
+
+    The object owns three device arrays sized to the model's capacity, zero-filled, and ATTACHES itself to the model (a weak reference):
+    model.prune() gathers them with the map, model.extend() gives appended rows zeros, model.resort() permutes them.  detach() ends that; a
+    detached object raises from every accessor once the model's rows have changed instead of indexing the wrong rows."""
+
+    W_MIN = 0.05   # default of accumulate(): a pair counts into pixels() when the Gaussian supplies at least 5 % of the pixel
+
+    def __init__(self, model):
+        self.model = model
+        self._alloc(model.capacity)
+        self.views = 0
+        self._attached = True
+        self._sync()
+        import weakref
+        model._stats.append(weakref.ref(self))
+
+    def _alloc(self, cap):
+        dev = self.model.device
+        self._max = torch.zeros(cap, dtype=torch.int32, device=dev)    # uint32 [cap]: float bits
+        self._npix = torch.zeros(cap, dtype=torch.int32, device=dev)   # uint32 [cap]
+        self._sum = torch.zeros(cap, dtype=torch.int64, device=dev)    # uint64 [cap]: 32.32 fixed point
+
+    def _sync(self):
+        self._seen = (self.model.layout_version, self.model._rows_version, self.model.P)
+
+    def _check(self):
+        now = (self.model.layout_version, self.model._rows_version, self.model.P)
+        if now != self._seen:
+            raise RuntimeError(f"ContributionStats: the model's rows changed since these statistics were taken (layout_version / row changes / P "
+                               f"{self._seen} -> {now}: prune(), extend() or resort()) and this object was detached, so it was not carried along — "
+                               "its rows no longer are the model's; build a new ContributionStats")
+
+    def detach(self):
+        """The model stops carrying this object through prune() / extend() / resort(); it stays readable until the rows change."""
+        self._attached = False
+        self.model._stats = [r for r in self.model._stats if r() is not None and r() is not self]
+
+    # --- what the model calls (attached objects only)
+    def _gather(self, kept_index, Pn):
+        from . import _lib
+        old = (self._max, self._npix, self._sum)
+        self._alloc(self.model.capacity)    # fresh and zero: the rows behind Pn stay zero
+        if Pn:
+            rows = [_lib.RowArray(o.data_ptr(), n.data_ptr(), w) for o, n, w in zip(old, (self._max, self._npix, self._sum), (1, 1, 2))]
+            arr = (_lib.RowArray * 3)(*rows)
+            _lib.check(_lib.lib().gslic_gather_rows(arr, 3, _lib.ptr(kept_index), int(Pn), _lib.current_stream_ptr()))
+        self._sync()
+
+    def _appended(self, P0, k):
+        if self._max.shape[0] < self.model.capacity:
+            old = (self._max, self._npix, self._sum)
+            self._alloc(self.model.capacity)
+            for o, n in zip(old, (self._max, self._npix, self._sum)):
+                n[:P0].copy_(o[:P0])
+        else:
+            for a in (self._max, self._npix, self._sum):
+                a[P0:P0 + k].zero_()
+        self._sync()
+
+    def _permute(self, perm):
+        P = perm.shape[0]
+        for a in (self._max, self._npix, self._sum):
+            a[:P] = a[:P][perm]
+        self._sync()
+
+    # --- accumulation
+    @torch.no_grad()
+    def accumulate(self, camera, bg=None, w_min=None):
+        """Renders `camera` (a forward of its own, raw parameters, no autograd) and adds that view's statistics."""
+        self._check()
+        if self.model.P == 0:
+            self.views += 1
+            return
+        bg = torch.zeros(3, device=self.model.device) if bg is None else bg
+        fwd = _RawRaster(self.model, camera, bg)
+        fwd.forward()
+        self.accumulate_from(fwd, w_min)
+
+    @torch.no_grad()
+    def accumulate_from(self, fwd, w_min=None):
+        """Adds the statistics of a forward the caller already has: a _RawRaster after forward() (training_step_fused's pieces) or the
+        rasterizer.CapacityBuffers a capacity forward filled (GraphedStep.bufs: the launch is sized from the capacities, stops at the real
+        counts on the device and does nothing when the forward's status says the lists did not fit).  The forward must be of THIS model's rows."""
+        from . import rasterizer as rz
+        self._check()
+        w_min = self.W_MIN if w_min is None else float(w_min)
+        if isinstance(fwd, rz.CapacityBuffers):
+            if fwd.no_color:
+                raise ValueError("ContributionStats: a no_color forward stores no n_contrib")
+            P, H, W, R, B, geom, binning, img = fwd.P, fwd.H, fwd.W, fwd.cap_R, fwd.cap_B, fwd.geom, fwd.binning, fwd.img
+        else:
+            if fwd.state is None:
+                raise ValueError("ContributionStats: run forward() on the _RawRaster first")
+            R, B, _radii, geom, binning, img, _sample = fwd.state
+            P, (H, W) = fwd.xyz.shape[0], fwd.hw
+        if P != self.model.P:
+            raise ValueError(f"ContributionStats: the forward rendered {P} rows, the model has {self.model.P}")
+        rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, self._max, self._npix, self._sum)
+        self.views += 1
+
+    def reset(self):
+        self._check()
+        for a in (self._max, self._npix, self._sum):
+            a.zero_()
+        self.views = 0
+
+    # --- results, [P] in storage row order
+    def max_weight(self):
+        """float32 [P]: the largest w = alpha T the row reached in any pixel of any accumulated view (0: it never contributed)."""
+        self._check()
+        return self._max[:self.model.P].view(torch.float32)
+
+    def pixels(self):
+        """int64 [P]: the (pixel, view) pairs in which the row's w reached w_min (saturating at 2^32 - 1)."""
+        self._check()
+        return self._npix[:self.model.P].long() & 0xffffffff
+
+    def sum_fixed(self):
+        """int64 [P]: the bit patterns of the 32.32 fixed-point sums of w (what is compared bit for bit)."""
+        self._check()
+        return self._sum[:self.model.P]
+
+    def sum_weight(self):
+        """float64 [P]: the sum of w over every contributing (pixel, view) pair of the row."""
+        return fixed_to_weight(self.sum_fixed())
+
+    def mean_weight(self):
+        """float64 [P]: sum_weight() / pixels(), 0 where pixels() is 0 — the mean weight per counted pair when the views were accumulated with
+        w_min = 0 (every contributing pair is counted); with a larger w_min the numerator still holds the pairs below it."""
+        n = self.pixels()
+        return torch.where(n > 0, self.sum_weight() / n.clamp_min(1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=n.device))
+
+    def drop_mask(self, max_weight_below=None, pixels_below=None):
+        """The uint8 [P] mask model.prune(drop=...) takes: contribution_drop_mask on max_weight() and pixels()."""
+        return contribution_drop_mask(self.max_weight(), self.pixels(), max_weight_below, pixels_below)
 
 
 def exchange_mode():

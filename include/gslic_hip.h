@@ -619,6 +619,44 @@ typedef struct gslic_row_array { const void* src; void* dst; uint32_t row_dwords
 int gslic_gather_rows(const gslic_row_array* arrays, int32_t n_arrays, const uint32_t* index, int32_t n_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * gslic_contribution_accumulate — per-Gaussian contribution statistics of ONE view, from the buffers a completed forward filled (no
+ * reference counterpart; the signal a mapper prunes by: did this Gaussian ever carry weight in a pixel).  One launch, a pass of its own: the
+ * training step is not touched.  geom / binning / img: the buffers of gslic_rasterize_forward, _forward_depth or their _capacity variants
+ * (the colour-only layout is a prefix of all of them) with the R and B that forward returned — in capacity mode the capacities, as for the
+ * backward.  A no_color forward stores no n_contrib: GSLIC_ERR_INVALID_ARG.
+ *
+ *  The rule.  For every pixel p of the image, with its tile's list e_0, e_1, ... (front to back) and its stored n_contrib[p]:
+ *      T = 1
+ *      for k in [0, n_contrib[p]):   d = mean2D(e_k) - p;  power = -0.5 (A d.x d.x + C d.y d.y) - B d.x d.y
+ *          if power > 0: continue;   alpha = min(0.99, opacity(e_k) exp(power));   if alpha < 1/255: continue
+ *          w = alpha T;   the pair (p, e_k) CONTRIBUTES with weight w;   T = T (1 - alpha)
+ *  i.e. exactly the pairs the forward blended into the pixel, with the weight it gave them.  The arithmetic is the strict forward's
+ *  (absolute pixel coordinates, every product rounded on its own, hipcc's expf): on a strict forward's buffers w is the forward's value bit
+ *  for bit.  There is NO fast-math variant: on the buffers of a fast-mode forward (gslic_set_math_mode(0)) the kernel still replays in the
+ *  strict arithmetic and honours that forward's n_contrib; the two arithmetics differ by rounding, so a few pairs per million sit on the
+ *  other side of alpha < 1/255 and are classified differently from what that forward did.
+ *  Accumulators (DEVICE, caller-owned, persistent across calls, indexed by STORAGE row g; each may be NULL; zero them to start):
+ *      max_w [P] uint32  the float bits of max(max_w[g], w) over the contributing pairs of g — an unsigned integer max on the bit pattern
+ *                        (w >= 0, so the patterns order like the values): exact and independent of the order of the updates
+ *      n_pix [P] uint32  += the number of contributing pairs of g with w >= w_min.  It SATURATES at 2^32 - 1 and never wraps:
+ *                        n_pix[g] = min(2^32 - 1, true count) whatever the order of the updates
+ *      sum_w [P] uint64  += sum of w over the contributing pairs of g, in fixed point with 32 fractional bits.  A tile's partial sum for an
+ *                        entry is formed in float in a fixed order over the tile's 256 pixels, converted ONCE (round to nearest) and added with a
+ *                        64-bit integer add.  A tile partial is at most 256 = 2^8, i.e. 2^40 in fixed point: more than 2^24 tile partials fit
+ *                        into a row before the 64 bits overflow.  sum in float units = sum_w / 2^32.
+ *  All three are deterministic from run to run and independent of the order in which tiles finish (integer max and adds commute), so the
+ *  ranks of an N-GPU run reach identical decisions from identical views.  Calls that share accumulators must be ordered (one stream).
+ *  Capacity mode: the launch is sized from the image, the lists end at the real counts on the device, and nothing is accumulated when the
+ *  forward's status words say the lists did not fit (what the backward does).  No host synchronisation, no allocation.
+ *  P == 0 or R == 0 returns at once; all three outputs NULL likewise.  Negative R / B, no_color, a NaN w_min and NULL buffers are reported
+ *  before any device work (GSLIC_ERR_INVALID_ARG, gslic_last_error).
+ */
+int gslic_contribution_accumulate(
+    const gslic_raster_params* prm, int32_t R, int32_t B,
+    const char* geom_buffer, const char* binning_buffer, const char* img_buffer, float w_min,
+    uint32_t* max_w /*[P] or NULL*/, uint32_t* n_pix /*[P] or NULL*/, uint64_t* sum_w /*[P] or NULL*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Introspection / measurement (no reference counterpart; used by bench.py and the tests).
  */
 int gslic_abi_version(void);

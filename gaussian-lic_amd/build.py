@@ -34,10 +34,11 @@ SOURCES = {
     "extend.hip": ["-ffp-contract=off"],  # pixel assignment decides integers: canonical order like preprocess.hip
     "prune.hip": [],         # comparisons and copies only: no arithmetic a flag could change
     "contrib.hip": ["-ffp-contract=off"],  # replays the strict blend: every product of the power and of w = alpha T is rounded on its own
+    "densify.hip": ["-ffp-contract=off"],  # the split children's positions: every product and sum rounded on its own, as the header writes them
 }
 COMMON = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-Wno-inline-asm",
           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]
-HEADERS = ["gslic_common.h", "kernels.h", "render_fwd_body.inc", "preprocess_bwd_body.inc", os.path.join("..", "..", "include", "gslic_hip.h")]
+HEADERS = ["gslic_common.h", "kernels.h", "render_fwd_body.inc", "preprocess_bwd_body.inc", "contrib_body.inc", os.path.join("..", "..", "include", "gslic_hip.h")]
 
 
 def _newer(a, b):

@@ -1284,16 +1284,19 @@ int gslic_gather_rows(const gslic_row_array* arrays, int32_t n_arrays, const uin
     return gather_rows(arrays, n_arrays, index, n_rows, (hipStream_t)stream);
 }
 
-int gslic_contribution_accumulate(const gslic_raster_params* prm, int32_t R, int32_t B, const char* geom_buffer, const char* binning_buffer,
-                                  const char* img_buffer, float w_min, uint32_t* max_w, uint32_t* n_pix, uint64_t* sum_w, void* stream)
+// the two contribution entry points: same checks, same early returns, same launch geometry; with_err adds the error image and its accumulator
+static int contribution_accumulate(const gslic_raster_params* prm, int32_t R, int32_t B, const char* geom_buffer, const char* binning_buffer,
+                                   const char* img_buffer, float w_min, uint32_t* max_w, uint32_t* n_pix, uint64_t* sum_w, bool with_err,
+                                   const float* err, uint64_t* err_sum, void* stream)
 {
     GS_TRY(check_params(prm));
     if (R < 0 || B < 0) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: negative R / B");
     if (prm->no_color) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: a no_color forward stores no n_contrib (nothing says where a pixel stopped)");
     if (w_min != w_min) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: w_min is NaN");
+    if (with_err && (!err || !err_sum)) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: NULL error image / err_sum");
     if (prm->P == 0 || R == 0) return GSLIC_OK;
     if (!geom_buffer || !binning_buffer || !img_buffer) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: NULL forward buffer");
-    if (!max_w && !n_pix && !sum_w) return GSLIC_OK;
+    if (!with_err && !max_w && !n_pix && !sum_w) return GSLIC_OK;
     int gx, gy;
     const int T = tile_grid(prm->width, prm->height, gx, gy);
     // the colour-only carve: a prefix of the depth layouts, and the capacity variants carve the same blocks for their capacity R
@@ -1304,7 +1307,51 @@ int gslic_contribution_accumulate(const gslic_raster_params* prm, int32_t R, int
     ca.W = prm->width; ca.H = prm->height; ca.gx = gx; ca.T = T; ca.P = prm->P; ca.R = (uint32_t)R;
     ca.ranges = img.ranges; ca.point_list = bin.point_list(); ca.rec = geom.rec; ca.pix_final = img.pix_final; ca.status = geom.flags;
     ca.w_min = w_min; ca.max_w = max_w; ca.n_pix = n_pix; ca.sum_w = reinterpret_cast<unsigned long long*>(sum_w);
-    return launch_contribution(ca, (hipStream_t)stream);
+    return launch_contribution(ca, (hipStream_t)stream, with_err ? err : nullptr, with_err ? reinterpret_cast<unsigned long long*>(err_sum) : nullptr);
+}
+
+int gslic_contribution_accumulate(const gslic_raster_params* prm, int32_t R, int32_t B, const char* geom_buffer, const char* binning_buffer,
+                                  const char* img_buffer, float w_min, uint32_t* max_w, uint32_t* n_pix, uint64_t* sum_w, void* stream)
+{
+    return contribution_accumulate(prm, R, B, geom_buffer, binning_buffer, img_buffer, w_min, max_w, n_pix, sum_w, false, nullptr, nullptr, stream);
+}
+
+int gslic_contribution_accumulate_error(const gslic_raster_params* prm, int32_t R, int32_t B, const char* geom_buffer, const char* binning_buffer,
+                                        const char* img_buffer, float w_min, uint32_t* max_w, uint32_t* n_pix, uint64_t* sum_w, const float* err,
+                                        uint64_t* err_sum, void* stream)
+{
+    return contribution_accumulate(prm, R, B, geom_buffer, binning_buffer, img_buffer, w_min, max_w, n_pix, sum_w, true, err, err_sum, stream);
+}
+
+int gslic_densify_select(int32_t P, const float* xyz, const float* dc, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw,
+                         const uint8_t* grow, const uint8_t* protect, const uint32_t* tie_rank, float scaling_raw_split, gslic_alloc_fn scratch_alloc,
+                         void* scratch_ctx, uint32_t* parent_index, int32_t* count, int32_t* count_split, void* stream)
+{
+    if (!count || !count_split) return set_error(GSLIC_ERR_INVALID_ARG, "densify select: NULL count output");
+    *count = 0; *count_split = 0;
+    if (P < 0) return set_error(GSLIC_ERR_INVALID_ARG, "densify select: negative P");
+    if (scaling_raw_split != scaling_raw_split) return set_error(GSLIC_ERR_INVALID_ARG, "densify select: scaling_raw_split is NaN");
+    if (P == 0) return GSLIC_OK;
+    if (!xyz || !dc || !opacity_raw || !scaling_raw || !rotation_raw || !grow || !parent_index || !scratch_alloc)
+        return set_error(GSLIC_ERR_INVALID_ARG, "densify select: NULL pointer");
+    return densify_select(P, xyz, dc, opacity_raw, scaling_raw, rotation_raw, grow, protect, tie_rank, scaling_raw_split, scratch_alloc, scratch_ctx,
+                          parent_index, count, count_split, (hipStream_t)stream);
+}
+
+int gslic_densify_emit(int32_t P, int32_t count, const uint32_t* parent_index, int32_t M, float* const param[6], float* const exp_avg[6],
+                       float* const exp_avg_sq[6], uint32_t* tie_rank, float scaling_raw_split, uint32_t seed, void* stream)
+{
+    if (P < 0 || count < 0 || M < 0) return set_error(GSLIC_ERR_INVALID_ARG, "densify emit: negative P / count / M");
+    if (count > P) return set_error(GSLIC_ERR_INVALID_ARG, "densify emit: %d new rows from %d parents (every parent adds one row)", count, P);
+    if ((int64_t)P + count > 0x7fffffffll) return set_error(GSLIC_ERR_INVALID_ARG, "densify emit: P + count does not fit 31 bits");
+    if (scaling_raw_split != scaling_raw_split) return set_error(GSLIC_ERR_INVALID_ARG, "densify emit: scaling_raw_split is NaN");
+    if (P == 0 || count == 0) return GSLIC_OK;
+    if (!parent_index || !param || !exp_avg || !exp_avg_sq) return set_error(GSLIC_ERR_INVALID_ARG, "densify emit: NULL pointer");
+    for (int g = 0; g < 6; g++) {
+        if (g == 2 && M == 0) continue;   // features_rest is empty at SH degree 0
+        if (!param[g] || !exp_avg[g] || !exp_avg_sq[g]) return set_error(GSLIC_ERR_INVALID_ARG, "densify emit: group %d has a NULL pointer", g);
+    }
+    return densify_emit(P, count, parent_index, M, param, exp_avg, exp_avg_sq, tie_rank, scaling_raw_split, seed, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

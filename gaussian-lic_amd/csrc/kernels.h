@@ -161,6 +161,16 @@ struct ContribArgs {
     uint32_t* n_pix;                  // [P]
     unsigned long long* sum_w;        // [P] 32.32 fixed point
 };
-int launch_contribution(const ContribArgs& a, hipStream_t s);
+// err_sum != NULL: the error-weighted variant of gslic_contribution_accumulate_error (err [H,W] row-major; err_sum [P] 32.32 fixed point)
+int launch_contribution(const ContribArgs& a, hipStream_t s, const float* err = nullptr, unsigned long long* err_sum = nullptr);
+
+// densify.hip: the clone / split rule of gslic_densify_select on the raw parameters -> parent_index / the two counts (one stream synchronisation),
+// and the new rows of gslic_densify_emit: the wide launch (copied fields, zeroed moments) and then one thread per parent (arguments validated by
+// the caller)
+int densify_select(int P, const float* xyz, const float* dc, const float* opacity, const float* scaling, const float* rotation, const uint8_t* grow,
+                   const uint8_t* protect, const uint32_t* tie_rank, float split_above, gslic_alloc_fn alloc, void* ctx, uint32_t* parent_index,
+                   int32_t* count, int32_t* count_split, hipStream_t s);
+int densify_emit(int P, int count, const uint32_t* parent_index, int M, float* const param[6], float* const exp_avg[6], float* const exp_avg_sq[6],
+                 uint32_t* tie_rank, float split_above, uint32_t seed, hipStream_t s);
 
 }  // namespace gslic

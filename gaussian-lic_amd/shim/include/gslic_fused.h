@@ -50,6 +50,7 @@ struct ContributionStats {
     torch::Tensor max_w;   // int32 [capacity]: uint32 float bits of the largest w = alpha T
     torch::Tensor n_pix;   // int32 [capacity]: uint32 count of (pixel, view) pairs with w >= w_min (saturating)
     torch::Tensor sum_w;   // int64 [capacity]: uint64 sum of w, 32.32 fixed point
+    torch::Tensor err_sum; // int64 [capacity]: uint64 sum of w e(p), 32.32 fixed point — undefined until a view is accumulated with an error image
     int64_t views = 0;
 };
 
@@ -208,11 +209,15 @@ public:
         if (stats && stats->max_w.defined()) {
             ContributionStats old = *stats;
             stats->max_w = torch::zeros({cap}, io); stats->n_pix = torch::zeros({cap}, io); stats->sum_w = torch::zeros({cap}, io.dtype(torch::kInt64));
+            if (old.err_sum.defined()) stats->err_sum = torch::zeros({cap}, io.dtype(torch::kInt64));
             if (count > 0) {
-                TORCH_CHECK(old.max_w.size(0) >= P && old.n_pix.size(0) >= P && old.sum_w.size(0) >= P, "FusedStep::prune: the statistics hold fewer rows than the map");
-                const gslic_row_array sr[3] = {{old.max_w.data_ptr(), stats->max_w.data_ptr(), 1u}, {old.n_pix.data_ptr(), stats->n_pix.data_ptr(), 1u},
-                                               {old.sum_w.data_ptr(), stats->sum_w.data_ptr(), 2u}};
-                check(gslic_gather_rows(sr, 3, reinterpret_cast<const uint32_t*>(kept.data_ptr<int32_t>()), count, current_stream()), "gslic_gather_rows (statistics)");
+                TORCH_CHECK(old.max_w.size(0) >= P && old.n_pix.size(0) >= P && old.sum_w.size(0) >= P && (!old.err_sum.defined() || old.err_sum.size(0) >= P),
+                            "FusedStep::prune: the statistics hold fewer rows than the map");
+                std::vector<gslic_row_array> sr = {{old.max_w.data_ptr(), stats->max_w.data_ptr(), 1u}, {old.n_pix.data_ptr(), stats->n_pix.data_ptr(), 1u},
+                                                   {old.sum_w.data_ptr(), stats->sum_w.data_ptr(), 2u}};
+                if (old.err_sum.defined()) sr.push_back({old.err_sum.data_ptr(), stats->err_sum.data_ptr(), 2u});
+                check(gslic_gather_rows(sr.data(), (int32_t)sr.size(), reinterpret_cast<const uint32_t*>(kept.data_ptr<int32_t>()), count, current_stream()),
+                      "gslic_gather_rows (statistics)");
             }
         }
         if (tie_.defined()) tie_ = new_tie.narrow(0, 0, count).clone();
@@ -221,21 +226,24 @@ public:
     // Adds the contribution statistics of ONE view to `stats` — the Python host's ContributionStats.accumulate: a raw-parameter forward of its own
     // (it reuses the step's scratch; call it between steps) and one gslic_contribution_accumulate on its buffers.  w_min: a (pixel, Gaussian)
     // pair counts into n_pix when its weight w = alpha T reaches it.  The arrays are created zero-filled on first use and grown to capacity().
-    void accumulate_contribution(const FusedCamera& cam, ContributionStats& stats, float w_min)
+    // error: undefined, or the view's per-pixel error image, float [H,W] on the map's device (host policy, e.g. (image - gt).abs().mean(0)).  The
+    // launch is then gslic_contribution_accumulate_error: the same three statistics bit for bit, and stats.err_sum += sum of w e(p) with
+    // e = error clamped to [0, 4] (NaN and negative values read as 0) — the error-based densification score.  stats.err_sum is created at the
+    // first such call.
+    void accumulate_contribution(const FusedCamera& cam, ContributionStats& stats, float w_min, const torch::Tensor& error = torch::Tensor())
     {
         torch::NoGradGuard ng;
-        const int64_t P = prm_[0].size(0), cap = capacity();
-        auto io = prm_[0].options().requires_grad(false).dtype(torch::kInt32);
-        auto fit = [&](torch::Tensor& t, torch::ScalarType dt) {
-            if (t.defined() && t.size(0) >= cap) return;
-            torch::Tensor n = torch::zeros({cap}, io.dtype(dt));
-            if (t.defined()) n.narrow(0, 0, t.size(0)).copy_(t);
-            t = n;
-        };
-        fit(stats.max_w, torch::kInt32); fit(stats.n_pix, torch::kInt32); fit(stats.sum_w, torch::kInt64);
+        const int64_t P = prm_[0].size(0);
+        const int W = cam.image_width, H = cam.image_height;
+        torch::Tensor err;
+        if (error.defined()) {
+            TORCH_CHECK(error.dim() == 2 && error.size(0) == H && error.size(1) == W && error.is_floating_point() && error.device() == prm_[0].device(),
+                        "FusedStep::accumulate_contribution: error must be a float [", H, ", ", W, "] tensor on the map's device");
+            err = error.detach().to(torch::kFloat32).contiguous();
+        }
+        fit_stats(stats, capacity(), err.defined());
         stats.views++;
         if (P == 0) return;
-        const int W = cam.image_width, H = cam.image_height;
         const gslic_raster_params rp = raster_params(cam, true, false);
         ensure_image_buffers(H, W);
         ensure_rows(P);
@@ -245,12 +253,92 @@ public:
                                       f(cam.full_proj_transform), f(cam.camera_center), image_.data_ptr<float>(), final_T_.data_ptr<float>(),
                                       radii_.data_ptr<int32_t>(), &R, &B, current_stream()),
               "gslic_rasterize_forward");
+        if (err.defined()) {
+            check(gslic_contribution_accumulate_error(&rp, R, B, cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), w_min,
+                                                      reinterpret_cast<uint32_t*>(stats.max_w.data_ptr<int32_t>()),
+                                                      reinterpret_cast<uint32_t*>(stats.n_pix.data_ptr<int32_t>()),
+                                                      reinterpret_cast<uint64_t*>(stats.sum_w.data_ptr<int64_t>()), err.data_ptr<float>(),
+                                                      reinterpret_cast<uint64_t*>(stats.err_sum.data_ptr<int64_t>()), current_stream()),
+                  "gslic_contribution_accumulate_error");
+            return;
+        }
         check(gslic_contribution_accumulate(&rp, R, B, cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), w_min,
                                             reinterpret_cast<uint32_t*>(stats.max_w.data_ptr<int32_t>()), reinterpret_cast<uint32_t*>(stats.n_pix.data_ptr<int32_t>()),
                                             reinterpret_cast<uint64_t*>(stats.sum_w.data_ptr<int64_t>()), current_stream()),
               "gslic_contribution_accumulate");
     }
+    // Clone / split densification on the device — the Python host's GaussianModel.densify (gaussian-lic_amd/trainer.py), same calls, same result:
+    // ONE gslic_densify_select (which rows grow, and where their new rows go) and ONE gslic_densify_emit (the new rows of the 18 parameter and
+    // moment arrays plus the tie rank; the split parents' rows rewritten in place).  grow / protect: bool / uint8 [P] on the map's device in STORAGE
+    // row order (protect may be undefined).  split_scale > 0 is a limit in the ACTIVATED domain, converted once, in double, to log(split_scale) and
+    // rounded to float (nullopt or +inf: every row clones); the rule, the placement of the new rows and the counter-based noise keyed by `seed` and
+    // the row's ORIGINAL index are written out in include/gslic_hip.h.  Every rank of an N-GPU run calls it with identical arguments and seed.
+    // Returns the parents (device int64 [k]): parents[j] is the storage row of the parent of new row P + j.  max_new: more eligible rows than
+    // this throw before anything is changed.  After a call that returned k > 0 the six parameter tensors are NEW views: fetch them with param(i);
+    // a tie rank (set_tie_rank) gains the ties P .. P + k - 1.  stats: contribution statistics of this map — zero for the new rows and for the
+    // split parents' rows (child 0 has contributed to nothing yet), unchanged for clone parents.  n_split: how many parents split.
+    torch::Tensor densify(const torch::Tensor& grow, std::optional<double> split_scale, const torch::Tensor& protect = torch::Tensor(), uint32_t seed = 0,
+                          ContributionStats* stats = nullptr, int64_t* n_split = nullptr, std::optional<int64_t> max_new = std::nullopt)
+    {
+        torch::NoGradGuard ng;
+        const int64_t P = prm_[0].size(0);
+        auto io = prm_[0].options().requires_grad(false).dtype(torch::kInt32);
+        float thr = std::numeric_limits<float>::infinity();
+        if (split_scale) {
+            TORCH_CHECK(*split_scale > 0.0, "FusedStep::densify: split_scale must be a number > 0");
+            if (std::isfinite(*split_scale)) thr = (float)std::log(*split_scale);
+        }
+        if (n_split) *n_split = 0;
+        TORCH_CHECK(grow.defined(), "FusedStep::densify: grow is required");
+        auto mask = [&](const torch::Tensor& t, const char* what) {
+            if (!t.defined()) return torch::Tensor();
+            TORCH_CHECK(t.dim() == 1 && t.size(0) == P && (t.scalar_type() == torch::kBool || t.scalar_type() == torch::kByte),
+                        "FusedStep::densify: ", what, " must be a bool / uint8 tensor of ", P, " rows");
+            return t.to(prm_[0].device()).to(torch::kByte).contiguous();
+        };
+        const torch::Tensor gr = mask(grow, "grow"), pr = mask(protect, "protect");
+        if (P == 0) return torch::empty({0}, io.dtype(torch::kInt64));
+        auto u8 = [](const torch::Tensor& t) { return t.defined() ? t.data_ptr<uint8_t>() : nullptr; };
+        torch::Tensor parent = torch::empty({P}, io), sel_scratch = torch::empty({0}, io.dtype(torch::kByte));
+        int32_t count = 0, splits = 0;
+        check(gslic_densify_select((int32_t)P, f(prm_[0]), f(prm_[1]), f(prm_[3]), f(prm_[4]), f(prm_[5]), u8(gr), u8(pr),
+                                   tie_.defined() ? reinterpret_cast<const uint32_t*>(tie_.data_ptr<int32_t>()) : nullptr, thr, grow_cb, &sel_scratch,
+                                   reinterpret_cast<uint32_t*>(parent.data_ptr<int32_t>()), &count, &splits, current_stream()),
+              "gslic_densify_select");
+        TORCH_CHECK(!max_new || count <= *max_new, "FusedStep::densify: ", count, " rows would be added, max_new is ", *max_new);
+        if (count == 0) return torch::empty({0}, io.dtype(torch::kInt64));
+        const torch::Tensor parents = parent.narrow(0, 0, count).to(torch::kInt64);
+        torch::Tensor split_rows;   // which parents split, from the scaling the emission has not yet rewritten (the rule's own comparison)
+        if (stats && stats->max_w.defined() && splits > 0) split_rows = parents.masked_select(prm_[4].detach().index_select(0, parents).gt(thr).any(1));
+        reserve(P + count);
+        if (tie_.defined()) {
+            torch::Tensor nt = torch::empty({P + count}, tie_.options());
+            nt.narrow(0, 0, P).copy_(tie_);
+            tie_ = nt;
+        }
+        const int64_t M = buf_[2].numel() ? buf_[2].size(1) : 0;
+        float *pp[6], *pm[6], *pv[6];
+        for (int g = 0; g < 6; g++) {
+            const bool on = buf_[g].numel() != 0;   // features_rest is [cap,0,3] at SH degree 0
+            pp[g] = on ? buf_[g].data_ptr<float>() : nullptr; pm[g] = on ? mbuf_[g].data_ptr<float>() : nullptr; pv[g] = on ? vbuf_[g].data_ptr<float>() : nullptr;
+        }
+        check(gslic_densify_emit((int32_t)P, count, reinterpret_cast<const uint32_t*>(parent.data_ptr<int32_t>()), (int32_t)M, pp, pm, pv,
+                                 tie_.defined() ? reinterpret_cast<uint32_t*>(tie_.data_ptr<int32_t>()) : nullptr, thr, seed, current_stream()),
+              "gslic_densify_emit");
+        bind(P + count);
+        if (stats && stats->max_w.defined()) {
+            fit_stats(*stats, capacity(), false);
+            for (torch::Tensor* t : {&stats->max_w, &stats->n_pix, &stats->sum_w, &stats->err_sum}) {
+                if (!t->defined()) continue;
+                t->narrow(0, P, count).zero_();
+                if (split_rows.defined()) t->index_fill_(0, split_rows, 0);
+            }
+        }
+        if (n_split) *n_split = splits;
+        return parents;
+    }
     const torch::Tensor& param(int group) const { return prm_[group]; }
+    const torch::Tensor& tie_rank() const { return tie_; }   // int32 [P] original index of every storage row; undefined: the rows are in their original order
     int64_t size() const { return prm_[0].size(0); }
     int64_t capacity() const { return buf_[0].defined() ? buf_[0].size(0) : prm_[0].size(0); }
 
@@ -479,6 +567,19 @@ private:
         return se3_pose_gradient(hv.data_ptr<float>(), hp.data_ptr<float>(), hc.data_ptr<float>(), hc.data_ptr<float>() + 16, hc.data_ptr<float>() + 32);
     }
 
+    // the statistics' arrays, created zero-filled and grown (zero-extended) to `cap` rows; err_sum only once a view brought an error image
+    void fit_stats(ContributionStats& stats, int64_t cap, bool with_err)
+    {
+        auto io = prm_[0].options().requires_grad(false).dtype(torch::kInt32);
+        auto fit = [&](torch::Tensor& t, torch::ScalarType dt) {
+            if (t.defined() && t.size(0) >= cap) return;
+            torch::Tensor n = torch::zeros({cap}, io.dtype(dt));
+            if (t.defined()) n.narrow(0, 0, t.size(0)).copy_(t);
+            t = n;
+        };
+        fit(stats.max_w, torch::kInt32); fit(stats.n_pix, torch::kInt32); fit(stats.sum_w, torch::kInt64);
+        if (with_err || stats.err_sum.defined()) fit(stats.err_sum, torch::kInt64);
+    }
     // capacity storage: created by the first extend(); until then the tensors handed to the constructor are used in place
     void reserve(int64_t newP)
     {

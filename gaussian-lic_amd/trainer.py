@@ -86,6 +86,20 @@ def prune_thresholds(min_opacity=None, max_scale=None):
     return lo, hi
 
 
+def densify_threshold(split_scale):
+    """The float32 threshold of the raw-domain split rule (include/gslic_hip.h: gslic_densify_select) for a limit given in the ACTIVATED domain:
+    split_scale > 0 -> log(split_scale), computed once on the host in float64 and rounded to float32 (like prune_thresholds); None or +inf: no
+    row splits (+inf).  A row splits when some raw scaling > the threshold (strict)."""
+    import math
+    import numpy as np
+    if split_scale is None:
+        return math.inf
+    s = float(split_scale)
+    if not s > 0.0:
+        raise ValueError(f"densify: split_scale must be a number > 0, got {split_scale!r}")
+    return math.inf if math.isinf(s) else float(np.float32(math.log(s)))
+
+
 class GaussianModel:
     """Parameters + activations of src/gaussian.{h,cpp} that the hot path touches, with capacity-doubling storage so that
     extend() appends rows in place instead of six torch::cat reallocations of every parameter and Adam moment per keyframe
@@ -282,6 +296,85 @@ class GaussianModel:
         self._rebind()
         return P - Pn, kept_index[:Pn].long()
 
+    @torch.no_grad()
+    def densify(self, grow, split_scale, protect=None, seed=0, max_new=None):
+        """Clone / split densification on the device: one gslic_densify_select (which rows grow, and where their new rows go) and one
+        gslic_densify_emit (the new rows of the 18 parameter and moment arrays plus tie_rank, and the split parents' rows rewritten in place).
+        Returns (k, n_split, parents): k new rows of which n_split come from splits; parents is a device LongTensor [k] holding the storage row
+        of the parent of new row P0 + j.
+
+        grow / protect: bool / uint8 [P] in STORAGE row order (protect optional).  split_scale > 0 is given in the ACTIVATED domain and converted
+        once on the host to the float32 of log(split_scale) (densify_threshold); the device evaluates the raw-domain rule with comparisons only:
+            eligible[i] = grow[i] and not protect[i] and xyz, features_dc, opacity, scaling, rotation of row i are all finite and |rotation_i|^2 > 0 (in float32)
+            split[i]    = eligible[i] and some scaling[i, j] > log(split_scale)      (raw values; strict: a row at the threshold clones)
+            clone[i]    = eligible[i] and not split[i]
+        Every eligible row adds one row.  A clone's new row is a bit copy of its parent with zero moments; the parent keeps everything.  A split
+        (3DGS densify_and_split, N = 2) replaces the parent's row by child 0 and appends child 1: both shrink the raw scaling by (float)log(1.6)
+        and are drawn from N(xyz, R diag(exp(scaling))^2 R^T) of the parent, with zero moments.  The noise is a counter generator keyed by `seed`
+        and the row's ORIGINAL index, and new rows are placed in the order of their parents' original indices: a Morton-ordered and an
+        insertion-ordered model of the same map densify to the same map, and so do the ranks of an N-GPU run (every rank calls it with
+        identical arguments and seed).  Which rows to grow (ContributionStats.grow_mask) and when is the host's policy.
+
+        max_new: if the number of eligible rows exceeds it, ValueError is raised before anything is changed.  Afterwards P = P0 + k, the
+        optimizer is re-bound and layout_version is incremented (a GraphedStep built before must be rebuilt); attached ContributionStats get
+        zeros for the new rows and for the split parents' rows; the resort_fraction rule of extend() applies.  Works on both row orders and
+        before training_setup()."""
+        import ctypes
+        from . import _lib
+        L = _lib.lib()
+        dev, P0 = self.device, self.P
+        thr = densify_threshold(split_scale)
+        if grow is None:
+            raise ValueError("densify: grow is required")
+
+        def mask(t, what):
+            if t is None:
+                return None
+            t = torch.as_tensor(t, device=dev)
+            if tuple(t.shape) != (P0,) or t.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f"densify: {what} must be a bool / uint8 tensor of {P0} rows, got {t.dtype} {tuple(t.shape)}")
+            return t.to(torch.uint8).contiguous()
+        grow, protect = mask(grow, "grow"), mask(protect, "protect")
+        if P0 == 0:
+            return 0, 0, torch.empty(0, dtype=torch.int64, device=dev)
+        p = _lib.ptr
+        parent_index = torch.empty(P0, dtype=torch.int32, device=dev)
+        scratch = _lib.TensorAllocator(dev)
+        count, n_split = ctypes.c_int32(0), ctypes.c_int32(0)
+        b = self._buf
+        _lib.check(L.gslic_densify_select(P0, p(b["xyz"][:P0]), p(b["features_dc"][:P0]), p(b["opacity"][:P0]), p(b["scaling"][:P0]), p(b["rotation"][:P0]),
+                                          p(grow), p(protect), p(self.tie_rank), thr, scratch.cb, None, p(parent_index), ctypes.byref(count),
+                                          ctypes.byref(n_split), _lib.current_stream_ptr()))
+        k = count.value
+        if max_new is not None and k > int(max_new):
+            raise ValueError(f"densify: {k} rows would be added, max_new is {int(max_new)}")
+        if k == 0:
+            return 0, 0, torch.empty(0, dtype=torch.int64, device=dev)
+        parents = parent_index[:k].long()
+        stats = self._attached_stats()
+        split_rows = None
+        if stats and n_split.value:   # which parents split, from the scaling the emission has not yet rewritten (the rule's own comparison)
+            split_rows = parents[(self._buf["scaling"][:P0][parents] > thr).any(1)]
+        self._reserve(P0 + k)
+        M = self._buf["features_rest"].shape[1]
+
+        def six(d):
+            return (ctypes.c_void_p * 6)(*[(d[n].data_ptr() if d[n].numel() else None) for n in self.NAMES])
+        _lib.check(L.gslic_densify_emit(P0, k, p(parent_index), M, six(self._buf), six(self._m), six(self._v),
+                                        None if self._tie is None else ctypes.c_void_p(self._tie.data_ptr()), thr, int(seed) & 0xffffffff,
+                                        _lib.current_stream_ptr()))
+        self.P = P0 + k
+        self.layout_version += 1
+        self._rows_version += 1
+        for st in stats:   # new rows and children have contributed to nothing yet; a clone's parent is the Gaussian it was
+            st._appended(P0, k)
+            if split_rows is not None:
+                st._zero_rows(split_rows)
+        self._rebind()
+        if self._tie is not None and self.resort_fraction is not None and (self.P - self._sorted_P) > self.resort_fraction * self.P:
+            self.resort()
+        return k, n_split.value, parents
+
     # gaussian.cpp:147-175
     def get_xyz(self): return self.xyz
     def get_features_dc(self): return self.features_dc
@@ -382,6 +475,19 @@ def contribution_drop_mask(max_w, n_pix, max_weight_below=None, pixels_below=Non
     return drop.to(torch.uint8)
 
 
+def contribution_grow_mask(err_fixed, n_pix, error_above, min_pixels=None):
+    """uint8 [P]: 1 where the 32.32 fixed-point error sum exceeds weight_to_fixed(error_above) (an integer comparison on the stored bits,
+    unsigned: a sum with bit 63 set is above every limit) AND, with min_pixels, n_pix >= min_pixels.  err_fixed int64 [P], n_pix integer [P]."""
+    lim = int(weight_to_fixed(float(error_above)))
+    if lim < 0:
+        raise ValueError(f"grow_mask: error_above must be >= 0, got {error_above!r}")
+    err_fixed = torch.as_tensor(err_fixed, dtype=torch.int64)
+    grow = (err_fixed > lim) | (err_fixed < 0)
+    if min_pixels is not None:
+        grow &= torch.as_tensor(n_pix).to(err_fixed.device) >= int(min_pixels)
+    return grow.to(torch.uint8)
+
+
 class ContributionStats:
     """Per-Gaussian contribution statistics accumulated over views (gslic_contribution_accumulate, include/gslic_hip.h): for every storage row
     the largest blend weight w = alpha T it reached in a pixel, the number of (pixel, view) pairs where w >= w_min, and the sum of w — what a
@@ -396,6 +502,7 @@ class ContributionStats:
 
     def __init__(self, model):
         self.model = model
+        self._err = None             # the error accumulator: allocated by the first accumulate with an error image
         self._alloc(model.capacity)
         self.views = 0
         self._attached = True
@@ -408,6 +515,12 @@ class ContributionStats:
         self._max = torch.zeros(cap, dtype=torch.int32, device=dev)    # uint32 [cap]: float bits
         self._npix = torch.zeros(cap, dtype=torch.int32, device=dev)   # uint32 [cap]
         self._sum = torch.zeros(cap, dtype=torch.int64, device=dev)    # uint64 [cap]: 32.32 fixed point
+        self._err = torch.zeros(cap, dtype=torch.int64, device=dev) if self._err is not None else None   # uint64 [cap], lazily
+
+    def _arrays(self):
+        """The accumulators that exist, with their row widths in dwords."""
+        a = [(self._max, 1), (self._npix, 1), (self._sum, 2)]
+        return a + ([(self._err, 2)] if self._err is not None else [])
 
     def _sync(self):
         self._seen = (self.model.layout_version, self.model._rows_version, self.model.P)
@@ -427,35 +540,41 @@ class ContributionStats:
     # --- what the model calls (attached objects only)
     def _gather(self, kept_index, Pn):
         from . import _lib
-        old = (self._max, self._npix, self._sum)
+        old = self._arrays()
         self._alloc(self.model.capacity)    # fresh and zero: the rows behind Pn stay zero
         if Pn:
-            rows = [_lib.RowArray(o.data_ptr(), n.data_ptr(), w) for o, n, w in zip(old, (self._max, self._npix, self._sum), (1, 1, 2))]
-            arr = (_lib.RowArray * 3)(*rows)
-            _lib.check(_lib.lib().gslic_gather_rows(arr, 3, _lib.ptr(kept_index), int(Pn), _lib.current_stream_ptr()))
+            rows = [_lib.RowArray(o.data_ptr(), n.data_ptr(), w) for (o, w), (n, _w) in zip(old, self._arrays())]
+            arr = (_lib.RowArray * len(rows))(*rows)
+            _lib.check(_lib.lib().gslic_gather_rows(arr, len(rows), _lib.ptr(kept_index), int(Pn), _lib.current_stream_ptr()))
         self._sync()
 
     def _appended(self, P0, k):
         if self._max.shape[0] < self.model.capacity:
-            old = (self._max, self._npix, self._sum)
+            old = self._arrays()
             self._alloc(self.model.capacity)
-            for o, n in zip(old, (self._max, self._npix, self._sum)):
+            for (o, _w), (n, _w2) in zip(old, self._arrays()):
                 n[:P0].copy_(o[:P0])
         else:
-            for a in (self._max, self._npix, self._sum):
+            for a, _w in self._arrays():
                 a[P0:P0 + k].zero_()
+        self._sync()
+
+    def _zero_rows(self, rows):
+        """densify(): the rows of split parents now hold child 0, which has contributed to nothing yet."""
+        for a, _w in self._arrays():
+            a[rows] = 0
         self._sync()
 
     def _permute(self, perm):
         P = perm.shape[0]
-        for a in (self._max, self._npix, self._sum):
+        for a, _w in self._arrays():
             a[:P] = a[:P][perm]
         self._sync()
 
     # --- accumulation
     @torch.no_grad()
-    def accumulate(self, camera, bg=None, w_min=None):
-        """Renders `camera` (a forward of its own, raw parameters, no autograd) and adds that view's statistics."""
+    def accumulate(self, camera, bg=None, w_min=None, error=None):
+        """Renders `camera` (a forward of its own, raw parameters, no autograd) and adds that view's statistics.  error: see accumulate_from."""
         self._check()
         if self.model.P == 0:
             self.views += 1
@@ -463,13 +582,16 @@ class ContributionStats:
         bg = torch.zeros(3, device=self.model.device) if bg is None else bg
         fwd = _RawRaster(self.model, camera, bg)
         fwd.forward()
-        self.accumulate_from(fwd, w_min)
+        self.accumulate_from(fwd, w_min, error=error)
 
     @torch.no_grad()
-    def accumulate_from(self, fwd, w_min=None):
+    def accumulate_from(self, fwd, w_min=None, error=None):
         """Adds the statistics of a forward the caller already has: a _RawRaster after forward() (training_step_fused's pieces) or the
         rasterizer.CapacityBuffers a capacity forward filled (GraphedStep.bufs: the launch is sized from the capacities, stops at the real
-        counts on the device and does nothing when the forward's status says the lists did not fit).  The forward must be of THIS model's rows."""
+        counts on the device and does nothing when the forward's status says the lists did not fit).  The forward must be of THIS model's rows.
+        error: an [H, W] float device tensor, the view's per-pixel error (host policy, plain torch: (image - gt).abs().mean(0)).  The launch is
+        then gslic_contribution_accumulate_error: the same statistics, and error_sum() += sum of w e(p) with e = error clamped to [0, 4]
+        (NaN and negative values read as 0).  The fourth accumulator is allocated at the first such call; without `error` it does not exist."""
         from . import rasterizer as rz
         self._check()
         w_min = self.W_MIN if w_min is None else float(w_min)
@@ -484,12 +606,22 @@ class ContributionStats:
             P, (H, W) = fwd.xyz.shape[0], fwd.hw
         if P != self.model.P:
             raise ValueError(f"ContributionStats: the forward rendered {P} rows, the model has {self.model.P}")
-        rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, self._max, self._npix, self._sum)
+        if error is None:
+            rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, self._max, self._npix, self._sum)
+        else:
+            error = torch.as_tensor(error)
+            if tuple(error.shape) != (int(H), int(W)) or not error.is_floating_point() or error.device != self._max.device:
+                raise ValueError(f"ContributionStats: error must be a float [{int(H)}, {int(W)}] tensor on the model's device, got {error.dtype} "
+                                 f"{tuple(error.shape)} on {error.device}")
+            if self._err is None:
+                self._err = torch.zeros(self._max.shape[0], dtype=torch.int64, device=self._max.device)
+            rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, self._max, self._npix, self._sum,
+                                       error=error.detach().float().contiguous(), err_sum=self._err)
         self.views += 1
 
     def reset(self):
         self._check()
-        for a in (self._max, self._npix, self._sum):
+        for a, _w in self._arrays():
             a.zero_()
         self.views = 0
 
@@ -518,6 +650,21 @@ class ContributionStats:
         w_min = 0 (every contributing pair is counted); with a larger w_min the numerator still holds the pairs below it."""
         n = self.pixels()
         return torch.where(n > 0, self.sum_weight() / n.clamp_min(1).to(torch.float64), torch.zeros((), dtype=torch.float64, device=n.device))
+
+    def error_fixed(self):
+        """int64 [P]: the bit patterns of the 32.32 fixed-point sums of w e(p) (zeros before the first accumulate with an error image)."""
+        self._check()
+        if self._err is None:
+            return torch.zeros(self.model.P, dtype=torch.int64, device=self._max.device)
+        return self._err[:self.model.P]
+
+    def error_sum(self):
+        """float64 [P]: the sum of w e(p) over every contributing (pixel, view) pair of the row — the error-based densification score."""
+        return fixed_to_weight(self.error_fixed())
+
+    def grow_mask(self, error_above, min_pixels=None):
+        """The uint8 [P] mask model.densify(grow=...) takes: contribution_grow_mask on error_fixed() and pixels()."""
+        return contribution_grow_mask(self.error_fixed(), self.pixels(), error_above, min_pixels)
 
     def drop_mask(self, max_weight_below=None, pixels_below=None):
         """The uint8 [P] mask model.prune(drop=...) takes: contribution_drop_mask on max_weight() and pixels()."""

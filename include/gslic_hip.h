@@ -657,6 +657,89 @@ int gslic_contribution_accumulate(
     uint32_t* max_w /*[P] or NULL*/, uint32_t* n_pix /*[P] or NULL*/, uint64_t* sum_w /*[P] or NULL*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * gslic_contribution_accumulate_error — the same launch over the same pairs as gslic_contribution_accumulate, which in addition weights the
+ * replay with a per-pixel error image: err_sum[g] += sum of w e(p) over the contributing pairs (p, g).  This is the error-based densification
+ * score of Bulo et al., "Revising Densification in Gaussian Splatting": it needs no backward (the fused step's dL/dmean2D never leaves
+ * registers) and stays an integer like the other statistics.  Building the error image is the host's policy (an L1 or 1 - SSIM map).
+ *
+ *  err [H,W] float, row-major, DEVICE.  e(p) = err[p] clamped to [0, 4]: a negative value or a NaN reads as 0, +inf reads as 4 (L1 and
+ *  1 - SSIM maps live in [0, 2]).
+ *  err_sum [P] uint64, DEVICE, caller-owned and persistent like sum_w, 32.32 fixed point.  Each pixel forms the product w e(p) in float32,
+ *  rounded on its own; a wave combines its 64 products with the wave butterfly (a fixed order); the four waves' partials are added in wave
+ *  order; the tile partial is converted ONCE (round to nearest) and added with one 64-bit integer add per (tile, entry).  A tile partial is
+ *  at most 256 * 4 = 1024 = 2^10, i.e. 2^42 in fixed point: 2^22 tile partials fit into a row before the 64 bits overflow.
+ *  err_sum in float units = err_sum / 2^32.
+ *  Deterministic from run to run and independent of the order in which tiles finish.  max_w / n_pix / sum_w (each may be NULL) come out
+ *  bit-identical to gslic_contribution_accumulate's: the same operations in the same order.  An error image of all ones gives
+ *  err_sum == sum_w bit for bit.
+ *  Argument checks, the capacity-mode rule and the early returns are those of gslic_contribution_accumulate (all three of max_w / n_pix /
+ *  sum_w NULL does NOT return early here: err_sum is still accumulated); in addition err == NULL or err_sum == NULL is
+ *  GSLIC_ERR_INVALID_ARG, reported before any device work.
+ */
+int gslic_contribution_accumulate_error(
+    const gslic_raster_params* prm, int32_t R, int32_t B,
+    const char* geom_buffer, const char* binning_buffer, const char* img_buffer, float w_min,
+    uint32_t* max_w /*[P] or NULL*/, uint32_t* n_pix /*[P] or NULL*/, uint64_t* sum_w /*[P] or NULL*/,
+    const float* err /*[H,W]*/, uint64_t* err_sum /*[P]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * gslic_densify_select / gslic_densify_emit — clone / split densification on the device (no reference counterpart: its map grows from
+ * LiDAR returns only; a LibTorch host would run 18 index + cat launches plus the rewrite of the split parents).  Which rows to grow
+ * (`grow`, e.g. a threshold on err_sum) and when is the host's policy.
+ *
+ *  select: one thread per row, then the u32 scan.  The rule is defined on the RAW (pre-activation) parameters and uses comparisons only:
+ *
+ *            eligible[i] = grow[i] && !(protect != NULL && protect[i])
+ *                          && every one of xyz[i,0..2], dc[i,0..2], opacity[i], scaling[i,0..2], rotation[i,0..3] is finite
+ *                          && |rotation[i]|^2 > 0      (the FLOAT32 value ((q0 q0 + q1 q1) + q2 q2) + q3 q3, every product and sum rounded on its
+ *                                                       own: the number the split divides by; a quaternion whose squares all underflow is not eligible)
+ *            split[i]    = eligible[i] && (some scaling[i,j] > scaling_raw_split)       (strict: a row AT the threshold clones)
+ *            clone[i]    = eligible[i] && !split[i]
+ *
+ *          scaling_raw_split is the float32 of log(split_scale), converted once on the host (NaN: GSLIC_ERR_INVALID_ARG; +inf: every row
+ *          clones).  grow / protect: one byte per row, non-zero = set.  features_rest is not scanned.  Every eligible row adds exactly ONE row.
+ *          Positions: let o_i be row i's ORIGINAL index (tie_rank[i], or i without tie_rank; a row whose tie_rank is outside 0..P-1 is
+ *          not eligible).  rank_i is the rank of o_i among the eligible rows' original indices (flags scattered to the original index,
+ *          scanned, gathered back — as gslic_prune_select ranks its dense ties).  The new row of parent i is storage row P + rank_i and
+ *          its tie is P + rank_i: a Morton-ordered and an insertion-ordered model of the same map densify to the same map.
+ *          Outputs: parent_index (DEVICE [P]) — its first *count entries, parent_index[rank] = storage row of the parent of new row
+ *          P + rank; *count (host) — the eligible rows, reading it is the call's one stream synchronisation; *count_split (host) — how
+ *          many of them split.  Scratch — ONE allocator call for about 8 P bytes (two uint32 [P] arrays) plus the u32 scan's temporaries (a few
+ *          words per 1024 rows) plus 1 KB of counters and alignment slack; the exact size is what the callback is asked for — is dead when the
+ *          call returns.
+ *  emit:   param / exp_avg / exp_avg_sq: HOST arrays of the six DEVICE base pointers (xyz [.,3], features_dc [.,3], features_rest [.,3M],
+ *          opacity [.,1], scaling [.,3], rotation [.,4]; features_rest may be NULL when M == 0), each with capacity >= P + count rows.
+ *          tie_rank: DEVICE [>= P + count] or NULL.  Two launches on the stream: the wide one (the 3 + 3M + 1 copied dwords of every new row
+ *          and the zeroed moments, cut along the destination, contiguous dwords per wave, no atomics; it reads only parent fields that no
+ *          thread writes, plus the parents' scaling BEFORE the second launch rewrites it), then one thread per parent, which reads its
+ *          parent's xyz / scaling / rotation once and writes both children.
+ *          Clone:  the new row is a bit copy of the parent's six parameter rows, its 2 x (14 + 3M) moment values are zero; the parent is
+ *                  untouched, moments included.
+ *          Split (3DGS densify_and_split with N = 2, in place): child 0 replaces the parent's row, child 1 is the new row.  Both take dc,
+ *                  features_rest, opacity and rotation as bit copies, scaling_child = scaling_raw - (float)log(1.6) (ONE float32
+ *                  subtraction per component) and xyz_child_c = xyz + R(q / |q|) (exp(scaling_raw_parent) (.) z_c), R the rotation matrix
+ *                  of the unit quaternion (r, x, y, z) = q / |q|; all moment values of both rows are zero.
+ *          Noise:  z_c comes from a counter generator keyed by the ORIGINAL index o_i — identical on every rank and in both row orders:
+ *                    fmix32(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16            (uint32)
+ *                    word(n) = fmix32( fmix32(fmix32(seed) ^ o_i) + 0x9E3779B9 * (n + 1) ),   n = 4c .. 4c + 3 for child c
+ *                    u_n     = (2 * (word(n) >> 9) + 1) * 2^-24                                (exact in float32, inside (0, 1))
+ *                    z_c     = ( r0 cos(2 pi u_{4c+1}), r0 sin(2 pi u_{4c+1}), r2 cos(2 pi u_{4c+3}) ),
+ *                              r0 = sqrt(-2 ln u_{4c}),  r2 = sqrt(-2 ln u_{4c+2})
+ *          scaling_raw_split and tie_rank must be those given to select.  Rows >= P + count and every row that is not a parent are not written.
+ *  P == 0 / count == 0 return at once (no allocator call); negative sizes, count > P and NULL required pointers: GSLIC_ERR_INVALID_ARG before
+ *  any device work.  With N > 1 GPUs every rank calls both with identical arguments and seed.
+ */
+int gslic_densify_select(
+    int32_t P, const float* xyz, const float* dc, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw,
+    const uint8_t* grow /*[P]*/, const uint8_t* protect /*[P] or NULL*/, const uint32_t* tie_rank /*[P] or NULL*/, float scaling_raw_split,
+    gslic_alloc_fn scratch_alloc, void* scratch_ctx,
+    uint32_t* parent_index /*[P]*/, int32_t* count, int32_t* count_split, void* stream);
+int gslic_densify_emit(
+    int32_t P, int32_t count, const uint32_t* parent_index, int32_t M,
+    float* const param[6], float* const exp_avg[6], float* const exp_avg_sq[6],
+    uint32_t* tie_rank /*[>= P + count] or NULL*/, float scaling_raw_split, uint32_t seed, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Introspection / measurement (no reference counterpart; used by bench.py and the tests).
  */
 int gslic_abi_version(void);

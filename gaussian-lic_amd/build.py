@@ -33,12 +33,13 @@ SOURCES = {
     "knn.hip": [],
     "extend.hip": ["-ffp-contract=off"],  # pixel assignment decides integers: canonical order like preprocess.hip
     "prune.hip": [],         # comparisons and copies only: no arithmetic a flag could change
+    "row_ops.hip": [],       # the segmented row kernel of prune and densify: copies, zeros and comparisons only
     "contrib.hip": ["-ffp-contract=off"],  # replays the strict blend: every product of the power and of w = alpha T is rounded on its own
     "densify.hip": ["-ffp-contract=off"],  # the split children's positions: every product and sum rounded on its own, as the header writes them
 }
 COMMON = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-Wno-inline-asm",
           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]
-HEADERS = ["gslic_common.h", "kernels.h", "render_fwd_body.inc", "preprocess_bwd_body.inc", "contrib_body.inc", os.path.join("..", "..", "include", "gslic_hip.h")]
+HEADERS = ["gslic_common.h", "kernels.h", "render_fwd_body.inc", "preprocess_bwd_body.inc", "contrib_body.inc", "row_rules.h", os.path.join("..", "..", "include", "gslic_hip.h")]
 
 
 def _newer(a, b):

@@ -94,11 +94,7 @@ int extend_select(int n, const float* points, const float* depths_rsp, const flo
     GS_LAUNCH(K_EXTEND, extend_flag_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, n, (const int32_t*)pix,
               (const unsigned long long*)zbuf, depths_rsp, final_T, flags);
     GS_TRY(scan_u32(flags, pos, (size_t)n, true, stemp, s));
-    uint32_t last[2] = {0, 0};
-    GS_HIP(hipMemcpyAsync(&last[0], pos + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(hipMemcpyAsync(&last[1], flags + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    GS_HIP(hipStreamSynchronize(s));  // the host sizes the append from the count (the reference syncs many times here)
-    *count = (int32_t)(last[0] + last[1]);
+    GS_TRY(scan_count(pos, flags, (size_t)n, s, count));  // one synchronisation: the host sizes the append from the count (the reference syncs many times here)
     *flags_out = flags;
     *pos_out = pos;
     return GSLIC_OK;

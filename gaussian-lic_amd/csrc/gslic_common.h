@@ -139,6 +139,10 @@ size_t scan_state_bytes(size_t n);
 // fault: the word that receives the timeout / overflow bits (NULL: the device-global word — callers outside a forward: knn, extend)
 int scan_u32_chained(const uint32_t* in, const uint32_t* gather, uint32_t* out, size_t n, bool exclusive, void* zeroed_state, hipStream_t s,
                      uint32_t* fault = nullptr);
+// The tail of a select call (extend, prune, densify): *count = pos[n - 1] + flags[n - 1] for the exclusive scan `pos` of `flags` (n > 0) and
+// *out_j = *extra_j for up to two more device words (NULL: not copied), read back with ONE stream synchronisation — the call's only one.
+int scan_count(const uint32_t* pos, const uint32_t* flags, size_t n, hipStream_t s, int32_t* count, const uint32_t* extra0 = nullptr,
+               uint32_t* out0 = nullptr, const uint32_t* extra1 = nullptr, uint32_t* out1 = nullptr);
 
 // radix_sort.hip ------------------------------------------------------------------------------------------
 #define GS_SORT_ITEMS 16

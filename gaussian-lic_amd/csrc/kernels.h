@@ -139,8 +139,28 @@ struct ShGradFromRgbArgs {
 };
 int launch_sh_grad_from_rgb(const ShGradFromRgbArgs& a, hipStream_t s);
 
+// row_ops.hip: the segmented row kernel behind gslic_gather_rows and the wide launch of gslic_densify_emit (segment semantics: its header).  A
+// caller value-initialises the block, sets n_rows, adds its segments (the copies [0, n_copy) first, then the zero segments) and launches.
+static constexpr int ROW_OPS_MAX_SEGMENTS = 32;      // segments per launch (the map has 19 row arrays)
+struct RowOpsArgs {
+    uint32_t* src[ROW_OPS_MAX_SEGMENTS];             // row 0 of the source (only a zero segment stores to it)
+    uint32_t* dst[ROW_OPS_MAX_SEGMENTS];             // destination row 0
+    uint32_t width[ROW_OPS_MAX_SEGMENTS];            // dwords per row (> 0)
+    uint32_t rows_per_block[ROW_OPS_MAX_SEGMENTS];   // max(1, 4096 / width)
+    uint32_t block_end[ROW_OPS_MAX_SEGMENTS];        // exclusive end of the segment's workgroups in the grid
+    int n_copy, n_segments;
+    uint32_t n_rows;                                 // destination rows of every segment = entries of index
+    uint32_t src_rows;                               // an index >= src_rows is never used as an address: its destination row is left as it is
+    const uint32_t* index;
+    const float* scaling;                            // zero segments only: [src_rows, 3] raw scaling and the split threshold
+    float split_above;
+};
+// appends a segment of rows `width` dwords wide (0: skipped) and cuts its share of the grid; false when the grid no longer fits 31 bits
+bool row_ops_add(RowOpsArgs& a, const void* src, void* dst, uint32_t width);
+int launch_row_ops(const RowOpsArgs& a, hipStream_t s);   // one launch, booked as gather_rows; nothing to do without segments
+
 // prune.hip: the keep rule of gslic_prune_select on the raw parameters -> kept_index / new_tie / the two counts (one stream synchronisation), and
-// the gather of gslic_gather_rows (arguments validated by the caller; arrays of width 0 are skipped)
+// the gather of gslic_gather_rows over row_ops (arguments validated by the caller; arrays of width 0 are skipped)
 int prune_select(int P, const float* xyz, const float* dc, const float* opacity, const float* scaling, const float* rotation, float opacity_min,
                  float scaling_max, int drop_nonfinite, const uint8_t* drop, const uint8_t* protect, const uint32_t* tie_rank, int split_row,
                  gslic_alloc_fn alloc, void* ctx, uint32_t* kept_index, uint32_t* new_tie, int32_t* count, int32_t* count_below, hipStream_t s);

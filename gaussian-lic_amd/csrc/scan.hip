@@ -274,4 +274,17 @@ int scan_u32(const uint32_t* in, uint32_t* out, size_t n, bool exclusive, uint32
     return GSLIC_OK;
 }
 
+int scan_count(const uint32_t* pos, const uint32_t* flags, size_t n, hipStream_t s, int32_t* count, const uint32_t* extra0, uint32_t* out0,
+               const uint32_t* extra1, uint32_t* out1)
+{
+    uint32_t last[2] = {0, 0};
+    GS_HIP(hipMemcpyAsync(&last[0], pos + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GS_HIP(hipMemcpyAsync(&last[1], flags + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (extra0) GS_HIP(hipMemcpyAsync(out0, extra0, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (extra1) GS_HIP(hipMemcpyAsync(out1, extra1, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    GS_HIP(hipStreamSynchronize(s));
+    *count = (int32_t)(last[0] + last[1]);
+    return GSLIC_OK;
+}
+
 }  // namespace gslic

@@ -172,14 +172,7 @@ public:
             hi = (float)std::log(*max_scale);
         }
         if (P == 0) return torch::empty({0}, io.dtype(torch::kInt64));
-        auto mask = [&](const torch::Tensor& t, const char* what) {
-            if (!t.defined()) return torch::Tensor();
-            TORCH_CHECK(t.dim() == 1 && t.size(0) == P && (t.scalar_type() == torch::kBool || t.scalar_type() == torch::kByte),
-                        "FusedStep::prune: ", what, " must be a bool / uint8 tensor of ", P, " rows");
-            return t.to(prm_[0].device()).to(torch::kByte).contiguous();
-        };
-        const torch::Tensor dr = mask(drop, "drop"), pr = mask(protect, "protect");
-        auto u8 = [](const torch::Tensor& t) { return t.defined() ? t.data_ptr<uint8_t>() : nullptr; };
+        const torch::Tensor dr = row_mask(drop, "FusedStep::prune: ", "drop", P), pr = row_mask(protect, "FusedStep::prune: ", "protect", P);
         torch::Tensor kept = torch::empty({P}, io), new_tie = tie_.defined() ? torch::empty({P}, io) : torch::Tensor();
         torch::Tensor sel_scratch = torch::empty({0}, io.dtype(torch::kByte));
         int32_t count = 0, below = 0;
@@ -290,15 +283,8 @@ public:
         }
         if (n_split) *n_split = 0;
         TORCH_CHECK(grow.defined(), "FusedStep::densify: grow is required");
-        auto mask = [&](const torch::Tensor& t, const char* what) {
-            if (!t.defined()) return torch::Tensor();
-            TORCH_CHECK(t.dim() == 1 && t.size(0) == P && (t.scalar_type() == torch::kBool || t.scalar_type() == torch::kByte),
-                        "FusedStep::densify: ", what, " must be a bool / uint8 tensor of ", P, " rows");
-            return t.to(prm_[0].device()).to(torch::kByte).contiguous();
-        };
-        const torch::Tensor gr = mask(grow, "grow"), pr = mask(protect, "protect");
+        const torch::Tensor gr = row_mask(grow, "FusedStep::densify: ", "grow", P), pr = row_mask(protect, "FusedStep::densify: ", "protect", P);
         if (P == 0) return torch::empty({0}, io.dtype(torch::kInt64));
-        auto u8 = [](const torch::Tensor& t) { return t.defined() ? t.data_ptr<uint8_t>() : nullptr; };
         torch::Tensor parent = torch::empty({P}, io), sel_scratch = torch::empty({0}, io.dtype(torch::kByte));
         int32_t count = 0, splits = 0;
         check(gslic_densify_select((int32_t)P, f(prm_[0]), f(prm_[1]), f(prm_[3]), f(prm_[4]), f(prm_[5]), u8(gr), u8(pr),
@@ -615,6 +601,15 @@ private:
         return ad;
     }
     static const float* f(const torch::Tensor& t) { return t.numel() ? t.data_ptr<float>() : nullptr; }
+    static const uint8_t* u8(const torch::Tensor& t) { return t.defined() ? t.data_ptr<uint8_t>() : nullptr; }
+    // a per-row mask argument of prune() / densify() as a contiguous uint8 tensor [P] on the parameters' device (undefined stays undefined)
+    torch::Tensor row_mask(const torch::Tensor& t, const char* who, const char* what, int64_t P) const
+    {
+        if (!t.defined()) return torch::Tensor();
+        TORCH_CHECK(t.dim() == 1 && t.size(0) == P && (t.scalar_type() == torch::kBool || t.scalar_type() == torch::kByte), who, what,
+                    " must be a bool / uint8 tensor of ", P, " rows");
+        return t.to(prm_[0].device()).to(torch::kByte).contiguous();
+    }
     static char* cptr(torch::Tensor& t) { return t.numel() ? reinterpret_cast<char*>(t.data_ptr()) : nullptr; }
     static void check(int rc, const char* what) { TORCH_CHECK(rc == GSLIC_OK, what, " failed (", rc, "): ", gslic_last_error()); }
     // the role of resizeFunctional (rasterize_points.cu:40-48) for buffers that persist across steps: grow only, with headroom, so a

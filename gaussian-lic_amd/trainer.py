@@ -6,6 +6,7 @@ One process per GPU (torch.distributed, backend "nccl" = RCCL over xGMI; "gloo" 
 holds a full replica of the parameters and Adam state, renders a different camera view, and applies the identical
 sparse-Adam update, so replicas stay bit-identical without a broadcast.
 """
+import math
 import os
 
 import torch
@@ -100,6 +101,24 @@ def densify_threshold(split_scale):
     return math.inf if math.isinf(s) else float(np.float32(math.log(s)))
 
 
+def _row_mask(t, what, who, P, dev):
+    """A per-row mask argument of `who` (prune / densify) as a contiguous uint8 tensor [P] on dev, or None; anything else is a ValueError."""
+    if t is None:
+        return None
+    t = torch.as_tensor(t, device=dev)
+    if tuple(t.shape) != (P,) or t.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"{who}: {what} must be a bool / uint8 tensor of {P} rows, got {t.dtype} {tuple(t.shape)}")
+    return t.to(torch.uint8).contiguous()
+
+
+def _gather_into(pairs, index, n):
+    """dst[k, :] = src[index[k], :] for k < n and every (src, dst, row_dwords) of pairs: ONE gslic_gather_rows (an array of width 0 is skipped)."""
+    from . import _lib
+    rows = [_lib.RowArray(s.data_ptr() if w else None, d.data_ptr() if w else None, w) for s, d, w in pairs]
+    arr = (_lib.RowArray * len(rows))(*rows)
+    _lib.check(_lib.lib().gslic_gather_rows(arr, len(rows), _lib.ptr(index), int(n), _lib.current_stream_ptr()))
+
+
 class GaussianModel:
     """Parameters + activations of src/gaussian.{h,cpp} that the hot path touches, with capacity-doubling storage so that
     extend() appends rows in place instead of six torch::cat reallocations of every parameter and Adam moment per keyframe
@@ -166,10 +185,8 @@ class GaussianModel:
         t0 = _time.perf_counter()
         P = self.P
         perm = morton_order_device(self._buf["xyz"][:P])
-        for d in (self._buf, self._m, self._v):
-            for n in self.NAMES:
-                d[n][:P] = d[n][:P][perm]
-        self._tie[:P] = self._tie[:P][perm]
+        for _d, _n, t, _w, _zero in self._row_arrays():
+            t[:P] = t[:P][perm]
         self._sorted_P = P
         self._rows_version += 1
         for st in self._attached_stats():
@@ -204,21 +221,41 @@ class GaussianModel:
         if self.optimizer is not None:
             self.optimizer.rebind(self.parameters(), [self._m[n][:self.P] for n in self.NAMES], [self._v[n][:self.P] for n in self.NAMES])
 
+    def _row_arrays(self, include_tie=True):
+        """Every per-row storage array once — the parameters, exp_avg, exp_avg_sq (NAMES order each), then tie_rank — as (owner dict or None for
+        tie_rank, name, tensor [capacity, ...], row width in dwords, whether rows of new storage must start as zeros: the moments)."""
+        for d in (self._buf, self._m, self._v):
+            for n in self.NAMES:
+                yield d, n, d[n], math.prod(d[n].shape[1:]), d is not self._buf
+        if include_tie and self._tie is not None:
+            yield None, "tie_rank", self._tie, 1, False
+
+    def _adopt(self, d, n, t):   # t becomes the storage of the row array (d, n) of _row_arrays()
+        if d is None:
+            self._tie = t
+        else:
+            d[n] = t
+
     def _reserve(self, newP):
         if newP <= self.capacity:
             return
         cap = max(2 * self.capacity, newP)
-        for d in (self._buf, self._m, self._v):
-            for n in self.NAMES:
-                old = d[n]
-                new = torch.zeros((cap,) + tuple(old.shape[1:]), device=self.device) if d is not self._buf else \
-                    torch.empty((cap,) + tuple(old.shape[1:]), device=self.device)
-                new[:self.P].copy_(old[:self.P])
-                d[n] = new
-        if self._tie is not None:
-            tie = torch.empty(cap, dtype=torch.int32, device=self.device)
-            tie[:self.P].copy_(self._tie[:self.P])
-            self._tie = tie
+        for d, n, old, _w, zero in list(self._row_arrays()):
+            new = (torch.zeros if zero else torch.empty)((cap,) + tuple(old.shape[1:]), dtype=old.dtype, device=self.device)
+            new[:self.P].copy_(old[:self.P])
+            self._adopt(d, n, new)
+
+    def _rows_appended(self, P0, k, bump_layout):
+        """Rows [P0, P0 + k) were appended (extend(), densify()): the counts (bump_layout: layout_version too), the statistics, the views, the re-sort."""
+        self.P = P0 + k
+        if bump_layout:
+            self.layout_version += 1
+        self._rows_version += 1
+        for st in self._attached_stats():   # appended rows have contributed to nothing yet
+            st._appended(P0, k)
+        self._rebind()
+        if self._tie is not None and self.resort_fraction is not None and (self.P - self._sorted_P) > self.resort_fraction * self.P:
+            self.resort()    # the appended tail has grown past resort_fraction of the map: Morton order again (a few ms, between keyframes)
 
     @torch.no_grad()
     def prune(self, min_opacity=None, max_scale=None, drop=None, protect=None, drop_nonfinite=True):
@@ -249,15 +286,7 @@ class GaussianModel:
         lo, hi = prune_thresholds(min_opacity, max_scale)
         if P == 0:
             return 0, torch.empty(0, dtype=torch.int64, device=dev)
-
-        def mask(t, what):
-            if t is None:
-                return None
-            t = torch.as_tensor(t, device=dev)
-            if tuple(t.shape) != (P,) or t.dtype not in (torch.bool, torch.uint8):
-                raise ValueError(f"prune: {what} must be a bool / uint8 tensor of {P} rows, got {t.dtype} {tuple(t.shape)}")
-            return t.to(torch.uint8).contiguous()
-        drop, protect = mask(drop, "drop"), mask(protect, "protect")
+        drop, protect = _row_mask(drop, "drop", "prune", P, dev), _row_mask(protect, "protect", "prune", P, dev)
         p = _lib.ptr
         kept_index = torch.empty(P, dtype=torch.int32, device=dev)
         new_tie = torch.empty(P, dtype=torch.int32, device=dev) if self._tie is not None else None
@@ -270,23 +299,13 @@ class GaussianModel:
         Pn = count.value
         if Pn == P:
             return 0, torch.arange(P, dtype=torch.int64, device=dev)
-        cap = self.capacity
-        fresh = [{n: torch.empty_like(d[n]) for n in self.NAMES} for d in (self._buf, self._m, self._v)]
-        rows = []
-        for d, f in zip((self._buf, self._m, self._v), fresh):
-            for n in self.NAMES:
-                w = d[n][0].numel() if cap else 0
-                rows.append(_lib.RowArray(d[n].data_ptr() if w else None, f[n].data_ptr() if w else None, w))
-        tie = None
+        arrays = list(self._row_arrays())   # (tie_rank is gathered like every other array, then replaced by the dense ranks)
+        fresh = [torch.empty_like(t) for _d, _n, t, _w, _zero in arrays]
+        _gather_into([(t, f, w) for (_d, _n, t, w, _zero), f in zip(arrays, fresh)], kept_index, Pn)
+        for (d, n, _t, _w, _zero), f in zip(arrays, fresh):
+            self._adopt(d, n, f)
         if self._tie is not None:
-            tie = torch.empty_like(self._tie)
-            rows.append(_lib.RowArray(self._tie.data_ptr(), tie.data_ptr(), 1))   # (gathered like every other array, then replaced by the dense ranks)
-        arr = (_lib.RowArray * len(rows))(*rows)
-        _lib.check(L.gslic_gather_rows(arr, len(rows), p(kept_index), Pn, _lib.current_stream_ptr()))
-        self._buf, self._m, self._v = fresh
-        if tie is not None:
-            tie[:Pn].copy_(new_tie[:Pn])
-            self._tie = tie
+            self._tie[:Pn].copy_(new_tie[:Pn])
         self.P = Pn
         self._sorted_P = below.value
         self.layout_version += 1
@@ -326,15 +345,7 @@ class GaussianModel:
         thr = densify_threshold(split_scale)
         if grow is None:
             raise ValueError("densify: grow is required")
-
-        def mask(t, what):
-            if t is None:
-                return None
-            t = torch.as_tensor(t, device=dev)
-            if tuple(t.shape) != (P0,) or t.dtype not in (torch.bool, torch.uint8):
-                raise ValueError(f"densify: {what} must be a bool / uint8 tensor of {P0} rows, got {t.dtype} {tuple(t.shape)}")
-            return t.to(torch.uint8).contiguous()
-        grow, protect = mask(grow, "grow"), mask(protect, "protect")
+        grow, protect = _row_mask(grow, "grow", "densify", P0, dev), _row_mask(protect, "protect", "densify", P0, dev)
         if P0 == 0:
             return 0, 0, torch.empty(0, dtype=torch.int64, device=dev)
         p = _lib.ptr
@@ -363,16 +374,9 @@ class GaussianModel:
         _lib.check(L.gslic_densify_emit(P0, k, p(parent_index), M, six(self._buf), six(self._m), six(self._v),
                                         None if self._tie is None else ctypes.c_void_p(self._tie.data_ptr()), thr, int(seed) & 0xffffffff,
                                         _lib.current_stream_ptr()))
-        self.P = P0 + k
-        self.layout_version += 1
-        self._rows_version += 1
-        for st in stats:   # new rows and children have contributed to nothing yet; a clone's parent is the Gaussian it was
-            st._appended(P0, k)
-            if split_rows is not None:
-                st._zero_rows(split_rows)
-        self._rebind()
-        if self._tie is not None and self.resort_fraction is not None and (self.P - self._sorted_P) > self.resort_fraction * self.P:
-            self.resort()
+        for st in stats if split_rows is not None else ():   # child 0 has contributed to nothing yet; a clone's parent is the Gaussian it was
+            st._zero_rows(split_rows)                         # (before _rows_appended: a resort there renumbers the rows)
+        self._rows_appended(P0, k, bump_layout=True)
         return k, n_split.value, parents
 
     # gaussian.cpp:147-175
@@ -429,19 +433,13 @@ class GaussianModel:
         _lib.check(L.gslic_extend_emit(n, flags, pos, p(points), p(colors), p(depths_rsp), self.scaling_scale, focal, M, row("xyz"),
                                        row("features_dc"), row("features_rest"), row("opacity"), row("scaling"), row("rotation"),
                                        _lib.current_stream_ptr()))
-        for d in (self._m, self._v):       # new rows start with zero moments (gaussian.cpp:458-459)
-            for name in self.NAMES:
-                d[name][P0:P0 + k].zero_()
+        for _d, _n, t, _w, zero in self._row_arrays(include_tie=False):
+            if zero:                       # new rows start with zero moments (gaussian.cpp:458-459)
+                t[P0:P0 + k].zero_()
         if self._tie is not None:          # appended rows are in insertion order behind the sorted block: their original index is their row
             self._tie[P0:P0 + k].copy_(torch.arange(P0, P0 + k, dtype=torch.int32, device=dev))
-        self.P = P0 + k
-        self._rows_version += 1
-        for st in self._attached_stats():   # appended rows have contributed to nothing yet
-            st._appended(P0, k)
-        self._rebind()
         torch.cuda.current_stream().synchronize()  # scratch (flags/pos) is released on return
-        if self._tie is not None and self.resort_fraction is not None and (self.P - self._sorted_P) > self.resort_fraction * self.P:
-            self.resort()    # the appended tail has grown past resort_fraction of the map: Morton order again (a few ms, between keyframes)
+        self._rows_appended(P0, k, bump_layout=False)
         return k
 
 
@@ -539,13 +537,10 @@ class ContributionStats:
 
     # --- what the model calls (attached objects only)
     def _gather(self, kept_index, Pn):
-        from . import _lib
         old = self._arrays()
         self._alloc(self.model.capacity)    # fresh and zero: the rows behind Pn stay zero
         if Pn:
-            rows = [_lib.RowArray(o.data_ptr(), n.data_ptr(), w) for (o, w), (n, _w) in zip(old, self._arrays())]
-            arr = (_lib.RowArray * len(rows))(*rows)
-            _lib.check(_lib.lib().gslic_gather_rows(arr, len(rows), _lib.ptr(kept_index), int(Pn), _lib.current_stream_ptr()))
+            _gather_into([(o, n, w) for (o, w), (n, _w) in zip(old, self._arrays())], kept_index, Pn)
         self._sync()
 
     def _appended(self, P0, k):

@@ -332,11 +332,9 @@ def _xyz_gap(c):
     return gap
 
 
-@pytest.mark.parametrize("M", [15, 0])
-@pytest.mark.parametrize("P", [1, 63, 64, 65, 257, 4097])
-def test_emission(P, M):
+def _check_emission(P, M):
     for with_tie in (False, True):
-        mask = "all" if P == 1 else "random"
+        mask = "all" if P < 63 else "random"
         c = _emit_case(P, M, with_tie, seed=9, mask=mask)
         k, par = c.k, c.parent
         assert k > 0
@@ -384,6 +382,63 @@ def test_emission(P, M):
                 assert torch.equal(_bits(other.buf[n]), _bits(c.buf[n])), n
         if c.n_split:
             assert not torch.equal(other.buf["xyz"][sp], c.buf["xyz"][sp]) and torch.equal(_bits(other.buf["xyz"][cl]), _bits(c.buf["xyz"][cl]))
+
+
+@pytest.mark.parametrize("M", [15, 0])
+@pytest.mark.parametrize("P", [1, 63, 64, 65, 257, 4097])
+def test_emission(P, M):
+    _check_emission(P, M)
+
+
+@pytest.mark.parametrize("P", [3, 65])
+def test_emission_of_rows_wider_than_one_workgroup_takes(P):
+    """features_rest rows of 4200 dwords: more than the 4096 a workgroup of the wide launch owns, so one row is walked by a workgroup's lanes alone —
+    in a copy segment (features_rest) and in two zero segments (its moments).  The smallest shape that gets there; about 1 MB of storage."""
+    _check_emission(P, 1400)
+
+
+def test_a_parent_index_outside_the_map_is_never_an_address():
+    """gslic_densify_emit on a parent_index with entries >= P (select writes none): their new rows are left alone in all 18 arrays, the other new
+    rows are those of the emission without them, bit for bit, and nothing else is touched."""
+    from gaussian_lic_amd import _lib
+    L, p = _lib.lib(), _lib.ptr
+    P, M, thr, seed = 65, 15, 0.0, 5
+    t = _rows(P, M, 91)
+    t["scaling"][2] = torch.tensor([1.0, -1.0, -1.0])                          # parent 2 splits
+    t["scaling"][64] = torch.tensor([-0.5, -1.0, 0.0])                         # parent 64 (the last row, at the threshold) clones
+    six = lambda d: (ctypes.c_void_p * 6)(*[d[n].data_ptr() for n in NAMES])
+
+    def emit(parents):
+        count = len(parents)
+        cap = P + count + 8
+        st = []
+        for fill in (SENT_F, 0.25, 0.5):                                       # parameters, exp_avg, exp_avg_sq: sentinels beyond P, non-zero moments
+            d = {n: torch.full((cap, t[n].shape[1]), SENT_F, device=_dev()) for n in NAMES}
+            for n in NAMES:
+                d[n][:P] = t[n] if fill == SENT_F else fill
+            st.append(d)
+        before = [{n: d[n].clone() for n in NAMES} for d in st]
+        index = torch.tensor(parents, dtype=torch.int32, device=_dev())
+        _lib.check(L.gslic_densify_emit(P, count, p(index), M, six(st[0]), six(st[1]), six(st[2]), None, thr, seed, _lib.current_stream_ptr()))
+        torch.cuda.synchronize()
+        return st, before
+
+    (got, before), (want, _b) = emit([2, -1, 64, 70]), emit([2, 64])          # (-1: the 32 bits of 0xffffffff)
+    for g, b, w in zip(got, before, want):
+        for n in NAMES:
+            what = (n, g is got[0])
+            assert torch.equal(_bits(g[n][P + 0]), _bits(w[n][P + 0])) and torch.equal(_bits(g[n][P + 2]), _bits(w[n][P + 1])), what   # as without them
+            assert not bool((_bits(w[n][P:P + 2]) == SENTINEL).any()), what                                                            # (and written)
+            assert bool((_bits(g[n][P + 1]) == SENTINEL).all()) and bool((_bits(g[n][P + 3]) == SENTINEL).all()), what                 # left alone
+            assert bool((_bits(g[n][P + 4:]) == SENTINEL).all()), what                                                                 # the guard rows
+            rest = torch.arange(P, device=_dev()) != 2
+            assert torch.equal(_bits(g[n][:P][rest]), _bits(b[n][:P][rest])), what                                                     # every other old row
+            assert torch.equal(_bits(g[n][2]), _bits(w[n][2])), what                                                                   # the split parent
+    for d in got[1:]:
+        for n in NAMES:
+            assert not bool(_bits(d[n][2]).any()) and not bool(_bits(d[n][P + 0]).any()) and not bool(_bits(d[n][P + 2]).any()), n     # zero moments
+    for n in ("features_dc", "features_rest", "opacity", "rotation"):
+        assert torch.equal(_bits(got[0][n][2]), _bits(before[0][n][2])), n                                                             # no thread writes these
 
 
 def test_tiny_quaternions_split_to_finite_children():

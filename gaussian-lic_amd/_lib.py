@@ -52,6 +52,7 @@ EXPORTS = [
     "gslic_depth_l1_loss_forward_backward", "gslic_img_bytes_depth", "gslic_binning_bytes_depth", "gslic_sample_bytes_depth",
     "gslic_rasterize_backward_depth_camera", "gslic_prune_select", "gslic_gather_rows", "gslic_contribution_accumulate",
     "gslic_contribution_accumulate_error", "gslic_densify_select", "gslic_densify_emit",
+    "gslic_l1_ssim_loss_weighted_partials_count", "gslic_l1_ssim_loss_weighted_forward_backward",
 ]
 
 _lib = None
@@ -134,6 +135,9 @@ def lib():
     L.gslic_l1_ssim_loss_forward.argtypes = [i32, i32, i32, i32, f32, f32] + [vp] * 7 + [vp]
     L.gslic_l1_ssim_loss_backward.argtypes = [i32, i32, i32, i32, f32] + [vp] * 6 + [vp]
     L.gslic_l1_ssim_loss_forward_backward.argtypes = [i32, i32, i32, i32, f32, f32, f32] + [vp] * 8 + [vp]
+    L.gslic_l1_ssim_loss_weighted_partials_count.restype = ctypes.c_int64
+    L.gslic_l1_ssim_loss_weighted_partials_count.argtypes = [i32, i32, i32]
+    L.gslic_l1_ssim_loss_weighted_forward_backward.argtypes = [i32, i32, i32, f32, f32, f32] + [vp] * 9 + [vp]
     L.gslic_set_math_mode.argtypes = [i32]
     L.gslic_set_binning_mode.argtypes = [i32]
     L.gslic_get_binning_path.argtypes = [ctypes.POINTER(u32), ctypes.POINTER(u32)]

@@ -39,7 +39,7 @@ SOURCES = {
 }
 COMMON = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-Wno-inline-asm",
           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]
-HEADERS = ["gslic_common.h", "kernels.h", "render_fwd_body.inc", "preprocess_bwd_body.inc", "contrib_body.inc", "row_rules.h", os.path.join("..", "..", "include", "gslic_hip.h")]
+HEADERS = ["gslic_common.h", "kernels.h", "render_fwd_body.inc", "preprocess_bwd_body.inc", "contrib_body.inc", "loss_bwd_body.inc", "row_rules.h", os.path.join("..", "..", "include", "gslic_hip.h")]
 
 
 def _newer(a, b):

@@ -275,6 +275,9 @@ int loss_forward(int, int, int, int, float, float, const float*, const float*, f
 int loss_backward(int, int, int, int, float, const float*, const float*, const float*, const float*, const float*, float*, hipStream_t);
 int loss_forward_backward(int, int, int, int, float, float, float, const float*, const float*, float*, float*, float*, float*, float*, float*, hipStream_t);
 int64_t loss_partials_count(int, int, int, int);
+int loss_weighted_forward_backward(int, int, int, float, float, float, const float*, const float*, const float*, float*, float*, float*, float*, float*,
+                                   float*, hipStream_t);
+int64_t loss_weighted_partials_count(int, int, int);
 int depth_loss_forward_backward(int, int, float, const float*, const float*, float*, float*, float*, hipStream_t);
 int64_t depth_loss_partials_count(int, int);
 int extend_select(int, const float*, const float*, const float*, const float*, float, float, float, float, int, int, const float*,
@@ -1200,6 +1203,22 @@ int gslic_l1_ssim_loss_forward_backward(int32_t B, int32_t CH, int32_t H, int32_
         return set_error(GSLIC_ERR_INVALID_ARG, "loss forward_backward: NULL pointer");
     return loss_forward_backward(B, CH, H, W, C1, C2, lambda_dssim, img, gt, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, partials, terms, dL_dimg,
                                  (hipStream_t)stream);
+}
+
+int64_t gslic_l1_ssim_loss_weighted_partials_count(int32_t CH, int32_t H, int32_t W)
+{
+    return (CH <= 0 || H <= 0 || W <= 0) ? 8 : loss_weighted_partials_count(CH, H, W);
+}
+
+int gslic_l1_ssim_loss_weighted_forward_backward(int32_t CH, int32_t H, int32_t W, float C1, float C2, float lambda_dssim, const float* img,
+                                                 const float* gt, const float* weight, float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12,
+                                                 float* partials, float* terms, float* dL_dimg, void* stream)
+{
+    if (CH <= 0 || H <= 0 || W <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "loss: empty image");
+    if (!img || !gt || !weight || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !partials || !terms || !dL_dimg)
+        return set_error(GSLIC_ERR_INVALID_ARG, "weighted loss forward_backward: NULL pointer");
+    return loss_weighted_forward_backward(CH, H, W, C1, C2, lambda_dssim, img, gt, weight, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, partials, terms,
+                                          dL_dimg, (hipStream_t)stream);
 }
 
 int64_t gslic_depth_l1_loss_partials_count(int32_t H, int32_t W) { return (H <= 0 || W <= 0) ? 8 : depth_loss_partials_count(H, W); }

@@ -72,8 +72,14 @@ struct FwdLds {
 };
 struct FwdStats { float mu1, mu2, e11, e22, e12; };
 
-// l1: += |a - b| over this thread's elements of the 32 x 32 centre (0 outside the image: both read as zero there)
-__device__ __forceinline__ void ssim_fwd_stage(FwdLds& L, const float* __restrict__ a, const float* __restrict__ b, int H, int W, int x0, int y0, float& l1)
+// The per-pixel weight of the weighted loss as the kernels read it: NaN and negative values are 0, values above 1 (+inf included) are 1.
+__device__ __forceinline__ float loss_weight(float w) { return (w > 0.f) ? fminf(w, 1.0f) : 0.f; }
+
+// l1: += |a - b| over this thread's elements of the 32 x 32 centre (0 outside the image: both read as zero there).
+// WEIGHTED (the weighted loss): l1 += w * |a - b| and sw += w with w = loss_weight(wt[pixel]), same elements, same order.
+template <bool WEIGHTED = false>
+__device__ __forceinline__ void ssim_fwd_stage(FwdLds& L, const float* __restrict__ a, const float* __restrict__ b, int H, int W, int x0, int y0, float& l1,
+                                               const float* __restrict__ wt = nullptr, float* sw = nullptr)
 {
     const int tid = threadIdx.x;
     // all of a thread's halo loads are issued before the first LDS store: a rolled loop pays one memory round trip per trip
@@ -84,7 +90,15 @@ __device__ __forceinline__ void ssim_fwd_stage(FwdLds& L, const float* __restric
         const int ly = t / SH_, lx = t - ly * SH_;
         va[k] = (t < SH_ * SH_) ? pix_or_zero(a, H, W, y0 + ly - 5, x0 + lx - 5) : 0.f;
         vb[k] = (t < SH_ * SH_) ? pix_or_zero(b, H, W, y0 + ly - 5, x0 + lx - 5) : 0.f;
-        if (t < SH_ * SH_ && ly >= 5 && ly < 5 + ST && lx >= 5 && lx < 5 + ST) l1 += fabsf(va[k] - vb[k]);
+        if constexpr (WEIGHTED) {
+            if (t < SH_ * SH_ && ly >= 5 && ly < 5 + ST && lx >= 5 && lx < 5 + ST) {
+                const float w = loss_weight(pix_or_zero(wt, H, W, y0 + ly - 5, x0 + lx - 5));
+                l1 += w * fabsf(va[k] - vb[k]);
+                *sw += w;
+            }
+        } else {
+            if (t < SH_ * SH_ && ly >= 5 && ly < 5 + ST && lx >= 5 && lx < 5 + ST) l1 += fabsf(va[k] - vb[k]);
+        }
     }
 #pragma unroll
     for (int k = 0; k < HALO_TRIPS; k++) {
@@ -369,75 +383,101 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(SsimGrid grid, int H, int
         const float t1 = block256_sum(r1, red);
         if (threadIdx.x == 0) { red_terms[0] = t0 * red_inv_n; red_terms[1] = t1 * red_inv_n; }
     }
+#define LOSS_BWD_WEIGHTED 0
+#include "loss_bwd_body.inc"
+#undef LOSS_BWD_WEIGHTED
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same loss under a per-pixel weight image w [H,W] shared by the channels (a mask is the 0/1 case), S = sum_p w_p:
+//   L1_w = sum_p w_p sum_c |img - gt| / (CH S),  SSIM_w = sum_p w_p sum_c ssim_c(p) / (CH S),  loss = (1-lambda) L1_w + lambda (1 - SSIM_w).
+// The window statistics are taken over all pixels as above; only the map is weighted.  S is not known before the forward has run and every
+// workgroup of the backward needs 1/(CH S), so the reduction is a launch of its own between the two: forward -> reduce -> backward, no host
+// synchronisation.  partials: [2 nblk] pairs (sum w|d|, sum w ssim) per tile and plane, [gx gy] sums of w per tile (written by plane 0),
+// then the two coefficients {c_l1, c_ssim} the reduce leaves for the backward.
+__global__ __launch_bounds__(256) void loss_weighted_fwd_kernel(SsimGrid grid, int H, int W, float C1, float C2, const float* __restrict__ img1,
+                                                                const float* __restrict__ img2, const float* __restrict__ weight,
+                                                                float* __restrict__ dm_dmu1, float* __restrict__ dm_dsigma1_sq,
+                                                                float* __restrict__ dm_dsigma12, float* __restrict__ partials,
+                                                                float* __restrict__ partials_w)
+{
+    __shared__ FwdLds L;
+    __shared__ float red[4];
     int tile_x, tile_y, plane_i;
     size_t tile_linear;
     if (!ssim_tile(grid, tile_x, tile_y, plane_i, tile_linear)) return;   // (whole workgroup: before any barrier)
     const size_t plane = (size_t)plane_i * H * W;
     const int x0 = tile_x * ST, y0 = tile_y * ST;
     const int tid = threadIdx.x;
-    {
-        float v1[HALO_TRIPS], v2[HALO_TRIPS], v3[HALO_TRIPS];
-#pragma unroll
-        for (int k = 0; k < HALO_TRIPS; k++) {
-            const int t = tid + 256 * k;
-            const int ly = t / SH_, lx = t - ly * SH_;
-            const int y = y0 + ly - 5, x = x0 + lx - 5;
-            const bool in = t < SH_ * SH_;
-            v1[k] = in ? pix_or_zero(dm_dmu1 + plane, H, W, y, x) : 0.f;
-            v2[k] = in ? pix_or_zero(dm_dsigma1_sq + plane, H, W, y, x) : 0.f;
-            v3[k] = in ? pix_or_zero(dm_dsigma12 + plane, H, W, y, x) : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < HALO_TRIPS; k++) {
-            const int t = tid + 256 * k;
-            if (t < SH_ * SH_) { (&s1[0][0])[t] = v1[k] * w_ssim; (&s2[0][0])[t] = v2[k] * w_ssim; (&s3[0][0])[t] = v3[k] * w_ssim; }
-        }
-    }
-    __syncthreads();
-    for (int t = tid; t < SH_ * ST; t += 256) {
-        const int ly = t / ST, lx = t % ST;
-        float r0 = 0.f, r1 = 0.f, r2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 11; i++) {
-            const float g = c_G[i];
-            r0 += g * s1[ly][lx + i]; r1 += g * s2[ly][lx + i]; r2 += g * s3[ly][lx + i];
-        }
-        s1[ly][lx] = r0; s2[ly][lx] = r1; s3[ly][lx] = r2;
-    }
-    __syncthreads();
+    float sum_l1 = 0.f, sum_ssim = 0.f, sum_w = 0.f;
+    ssim_fwd_stage<true>(L, img1 + plane, img2 + plane, H, W, x0, y0, sum_l1, weight, &sum_w);
     const int lx = tid & 31;
-    // four consecutive rows per thread, one sweep over the 14 rows of hs they share (ssim_fwd_column4): taps in ascending order per output
-    const int ly0 = 4 * (tid >> 5);
-    float w0[4] = {0.f, 0.f, 0.f, 0.f}, w1[4] = {0.f, 0.f, 0.f, 0.f}, w2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int r = 0; r < 14; r++) {
-        const float a0 = s1[ly0 + r][lx], a1 = s2[ly0 + r][lx], a2 = s3[ly0 + r][lx];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int j = r - k;
-            if (j >= 0 && j <= 10) {
-                const float g = c_G[j];
-                w0[k] += g * a0; w1[k] += g * a1; w2[k] += g * a2;
-            }
-        }
-    }
+    FwdStats st4[4];
+    ssim_fwd_column4(L, 4 * (tid >> 5), lx, st4);
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        const int ly = ly0 + q;
-        const float v0 = w0[q], v1 = w1[q], v2 = w2[q];
+        const int ly = 4 * (tid >> 5) + q;
+        const FwdStats st = st4[q];
         const int px = x0 + lx, py = y0 + ly;
         if (px < W && py < H) {
+            const SsimTerms t = ssim_terms(st, C1, C2);
             const size_t o = plane + (size_t)py * W + px;
-            const float pix1 = img1[o], pix2 = img2[o];
-            const float d = pix1 - pix2;
-            const float sgn = (d > 0.f) ? 1.f : ((d < 0.f) ? -1.f : 0.f);  // torch.sign (abs backward)
-            float acc = 0.0f;
-            acc += v0;
-            acc += pix1 * 2.0f * v1;
-            acc += pix2 * v2;
-            dL_dimg1[o] = w_l1 * sgn + acc;
+            sum_ssim += loss_weight(weight[(size_t)py * W + px]) * t.map;
+            dm_dmu1[o] = t.d_mu1;
+            dm_dsigma1_sq[o] = t.d_sigma1_sq;
+            dm_dsigma12[o] = t.d_sigma12;
         }
     }
+    const float bl1 = block256_sum(sum_l1, red);
+    const float bss = block256_sum(sum_ssim, red);
+    const float bw = block256_sum(sum_w, red);
+    if (tid == 0) {
+        const size_t blk = tile_linear;
+        partials[2 * blk] = bl1;
+        partials[2 * blk + 1] = bss;
+        if (plane_i == 0) partials_w[blk] = bw;   // (plane 0 holds tiles 0 .. gx gy - 1)
+    }
+}
+
+// One workgroup: the three sums in loss_reduce_kernel's order (bit-reproducible), then terms = {L1_w, SSIM_w, S} and the backward's coefficients
+// coef = {(1-lambda)/(CH S), -lambda/(CH S)}: each one float division, CH S one float product, the terms sum * (1.0f / (CH S)) — with w == 1
+// the bits of loss_forward_backward.  S == 0 (nothing to train on): terms 0, 0, 0 and coefficients 0, 0, so the gradient is all zeros.
+__global__ __launch_bounds__(256) void loss_weighted_reduce_kernel(size_t nblk, size_t ntile, const float* __restrict__ partials,
+                                                                   const float* __restrict__ partials_w, float ch, float lambda_dssim,
+                                                                   float* __restrict__ terms, float* __restrict__ coef)
+{
+    __shared__ float red[4];
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (size_t i = threadIdx.x; i < nblk; i += 256) { s0 += partials[2 * i]; s1 += partials[2 * i + 1]; }
+    for (size_t i = threadIdx.x; i < ntile; i += 256) s2 += partials_w[i];
+    const float t0 = block256_sum(s0, red);
+    const float t1 = block256_sum(s1, red);
+    const float S = block256_sum(s2, red);
+    if (threadIdx.x == 0) {
+        const float n = ch * S;
+        const bool any = S > 0.f;
+        const float inv_n = any ? 1.0f / n : 0.f;
+        terms[0] = any ? t0 * inv_n : 0.f;
+        terms[1] = any ? t1 * inv_n : 0.f;
+        terms[2] = S;
+        coef[0] = any ? (1.0f - lambda_dssim) / n : 0.f;
+        coef[1] = any ? -lambda_dssim / n : 0.f;
+    }
+}
+
+// loss_bwd_kernel with the upstream gradients per pixel: bit-identical to fusedssim_backward(dL_dmap = c_ssim * w) + (c_l1 * w) * sign(img - gt).
+__global__ __launch_bounds__(256) void loss_weighted_bwd_kernel(SsimGrid grid, int H, int W, const float* __restrict__ coef,
+                                                                const float* __restrict__ weight, const float* __restrict__ img1,
+                                                                const float* __restrict__ img2, const float* __restrict__ dm_dmu1,
+                                                                const float* __restrict__ dm_dsigma1_sq, const float* __restrict__ dm_dsigma12,
+                                                                float* __restrict__ dL_dimg1)
+{
+    __shared__ float s1[SH_][SH_];   // (the layout of loss_bwd_kernel: 21.2 KB, six workgroups per CU)
+    __shared__ float s2[SH_][SH_];
+    __shared__ float s3[SH_][SH_];
+#define LOSS_BWD_WEIGHTED 1
+#include "loss_bwd_body.inc"
+#undef LOSS_BWD_WEIGHTED
 }
 
 int loss_forward(int B, int CH, int H, int W, float C1, float C2, const float* img, const float* gt, float* d1, float* d2, float* d3,
@@ -475,6 +515,24 @@ int loss_forward_backward(int B, int CH, int H, int W, float C1, float C2, float
     return GSLIC_OK;
 }
 int64_t loss_partials_count(int B, int CH, int H, int W) { return 2 * (int64_t)div_up(W, ST) * div_up(H, ST) * B * CH + 8; }
+
+// the weighted loss, forward + backward in THREE launches (see above loss_weighted_fwd_kernel); one image
+int loss_weighted_forward_backward(int CH, int H, int W, float C1, float C2, float lambda_dssim, const float* img, const float* gt,
+                                   const float* weight, float* d1, float* d2, float* d3, float* partials, float* terms, float* dL_dimg, hipStream_t s)
+{
+    unsigned blocks;
+    const SsimGrid grid = ssim_grid(W, H, CH, blocks);
+    const size_t nblk = (size_t)grid.gx * grid.gy * grid.planes, ntile = (size_t)grid.gx * grid.gy;
+    float* const partials_w = partials + 2 * nblk;
+    float* const coef = partials_w + ntile;
+    GS_LAUNCH(K_SSIM_FWD, loss_weighted_fwd_kernel, dim3(blocks), dim3(256), 0, s, grid, H, W, C1, C2, img, gt, weight, d1, d2, d3, partials, partials_w);
+    GS_LAUNCH(K_SSIM_FWD, loss_weighted_reduce_kernel, dim3(1), dim3(256), 0, s, nblk, ntile, (const float*)partials, (const float*)partials_w,
+              (float)CH, lambda_dssim, terms, coef);
+    GS_LAUNCH(K_SSIM_BWD, loss_weighted_bwd_kernel, dim3(blocks), dim3(256), 0, s, grid, H, W, (const float*)coef, weight, img, gt, (const float*)d1,
+              (const float*)d2, (const float*)d3, dL_dimg);
+    return GSLIC_OK;
+}
+int64_t loss_weighted_partials_count(int CH, int H, int W) { return (2 * (int64_t)CH + 1) * div_up(W, ST) * div_up(H, ST) + 8; }
 
 int ssim_forward(int B, int CH, int H, int W, float C1, float C2, const float* img1, const float* img2, float* ssim_map,
                  float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12, hipStream_t s)

@@ -70,9 +70,19 @@ def depth_l1(depth, gt_depth):
     return diff.sum() / n.clamp_min(1).to(depth.dtype)
 
 
-def psnr(img1, img2):
-    """loss_utils.h:35-39."""
-    mse = torch.pow(img1 - img2, 2).mean()
+def clamp_weight(weight):
+    """A per-pixel weight image as the weighted loss kernels read it: NaN and negative values are 0, values above 1 (+inf included) are 1."""
+    return torch.where(weight > 0, weight.clamp(max=1.0), torch.zeros_like(weight))
+
+
+def psnr(img1, img2, weight=None):
+    """loss_utils.h:35-39.  weight [H,W] (not in the reference): the MSE is the weighted mean sum_p w_p sum_c d^2 / (C sum_p w_p), so that an
+    evaluation can leave out the pixels the training left out."""
+    if weight is None:
+        mse = torch.pow(img1 - img2, 2).mean()
+    else:
+        w = clamp_weight(weight.to(img1.dtype))
+        mse = (torch.pow(img1 - img2, 2) * w).sum() / (img1.size(-3) * w.sum())
     return 10.0 * torch.log10(1.0 / mse)
 
 
@@ -103,23 +113,33 @@ def ssim(img1, img2, window_size=11, size_average=True):
     sigma12 = conv(img1 * img2) - mu1_mu2
     c1, c2 = 0.01 * 0.01, 0.03 * 0.03
     ssim_map = ((2 * mu1_mu2 + c1) * (2 * sigma12 + c2)) / ((mu1_sq + mu2_sq + c1) * (sigma1_sq + sigma2_sq + c2))
+    if size_average is None:
+        return ssim_map                                         # (the map itself: evaluate_visual_quality's weighted mean)
     return ssim_map.mean() if size_average else ssim_map.mean(1).mean(1).mean(1)
 
 
-def evaluate_visual_quality(model, cameras, gt_images, bg, fused=True):
+def evaluate_visual_quality(model, cameras, gt_images, bg, fused=True, weights=None):
     """PSNR / SSIM over a set of views — the metric part of evaluateVisualQuality (gaussian.cpp:751-789): render, clamp to [0,1],
     psnr + SSIM per image, averaged over the views.  fused=True evaluates the SSIM map with the fused-SSIM kernel
     (gslic_fusedssim_forward, train = 0: the same 11-tap sigma-1.5 window with zero padding as loss_utils.h:41-128, separable, one
     launch) instead of five LibTorch conv2d calls; fused=False is the reference's formulation verbatim.  Returns device scalars
-    (mean PSNR, mean SSIM).  (LPIPS needs the TorchScript AlexNet blob the reference does not ship.)"""
+    (mean PSNR, mean SSIM).  (LPIPS needs the TorchScript AlexNet blob the reference does not ship.)
+    weights: one [H,W] weight image per view (or None per view): PSNR from the weighted MSE and SSIM as the weighted mean of the SSIM map
+    (window statistics over all pixels, as in the weighted training loss), in plain torch on top of the same map."""
     from .rasterizer import render
     ps, ss = [], []
     with torch.no_grad():
-        for cam, gt in zip(cameras, gt_images):
+        for i, (cam, gt) in enumerate(zip(cameras, gt_images)):
             img = torch.clamp(render(cam, model, bg)[0], 0.0, 1.0)
             gt = torch.clamp(gt, 0.0, 1.0)                      # gaussian.cpp:759
-            ps.append(psnr(img, gt))
-            if fused:
+            w = None if weights is None else weights[i]
+            ps.append(psnr(img, gt, w))
+            if w is not None:
+                m = (fusedssim(C1, C2, img.unsqueeze(0).contiguous(), gt.unsqueeze(0).contiguous(), False)[0] if fused
+                     else ssim(img.unsqueeze(0), gt.unsqueeze(0), size_average=None))
+                wc = clamp_weight(w.to(m.dtype))
+                ss.append((m * wc).sum() / (m.size(-3) * wc.sum()))
+            elif fused:
                 ss.append(fusedssim(C1, C2, img.unsqueeze(0).contiguous(), gt.unsqueeze(0).contiguous(), False)[0].mean())
             else:
                 ss.append(ssim(img.unsqueeze(0), gt.unsqueeze(0)))
@@ -133,24 +153,26 @@ class _L1SsimLoss(torch.autograd.Function):
     (tests/test_vs_reference_kernels_gpu.py::test_fused_loss_gradient_is_the_reference_chain_bit_for_bit) times the upstream scalar."""
 
     @staticmethod
-    def forward(ctx, image, gt, lambda_dssim):
+    def forward(ctx, image, gt, lambda_dssim, weight=None):
         fl = FusedLoss(lambda_dssim)
         ctx.fl, ctx.shape = fl, image.shape
         img3, gt3 = image.reshape(image.shape[-3:]), gt.reshape(gt.shape[-3:])
-        dL, terms = fl.forward_backward(img3, gt3)
+        dL, terms = fl.forward_backward(img3, gt3, weight)
         ctx.save_for_backward(dL)
         return fl.value(terms)
 
     @staticmethod
     def backward(ctx, g):
         (dL,) = ctx.saved_tensors
-        return (dL * g).reshape(ctx.shape), None, None
+        return (dL * g).reshape(ctx.shape), None, None, None
 
 
-def l1_ssim_loss(image, gt, lambda_dssim=0.2):
+def l1_ssim_loss(image, gt, lambda_dssim=0.2, weight=None):
     """Optional one-call replacement for the loss lines of optimize() (gaussian.cpp:685-691): `loss = l1_ssim_loss(rendered_image, gt_image,
-    lambda_dssim)`.  image, gt: [3,H,W] (or [1,3,H,W])."""
-    return _L1SsimLoss.apply(image, gt, float(lambda_dssim))
+    lambda_dssim)`.  image, gt: [3,H,W] (or [1,3,H,W]).  weight [H,W]: the weighted loss of FusedLoss.forward_backward (no gradient to it)."""
+    if weight is None:
+        return _L1SsimLoss.apply(image, gt, float(lambda_dssim))
+    return _L1SsimLoss.apply(image, gt, float(lambda_dssim), weight.detach())
 
 
 class FusedLoss:
@@ -164,6 +186,7 @@ class FusedLoss:
         self._shape, self._buf = None, None
         self._dshape, self._dbuf = None, None
         self._terms = None
+        self._wshape, self._wbuf = None, None
 
     def _terms_buf(self, device):
         if self._terms is None or self._terms.device != device:
@@ -201,10 +224,37 @@ class FusedLoss:
                                                                    _lib.current_stream_ptr()))
         return dL, term
 
-    def forward_backward(self, image, gt):
-        """image, gt: [3,H,W].  Returns (dL/dimage, terms) with terms = device tensor [mean|img-gt|, mean ssim]."""
+    @property
+    def weight_sum(self):
+        """S = sum of the (clamped) weights of the last forward_backward(weight=...): a device [1] view; None before the first such call."""
+        return None if self._wbuf is None else self._wbuf[1][2:3]
+
+    def _weighted_scratch(self, img):
+        if self._wshape != tuple(img.shape) or self._wbuf[0].device != img.device:
+            n = int(_lib.lib().gslic_l1_ssim_loss_weighted_partials_count(img.shape[0], img.shape[1], img.shape[2]))
+            self._wbuf = [torch.empty(n, device=img.device), torch.zeros(3, device=img.device)]
+            self._wshape = tuple(img.shape)
+        return self._wbuf
+
+    def forward_backward(self, image, gt, weight=None):
+        """image, gt: [3,H,W].  Returns (dL/dimage, terms) with terms = device tensor [mean|img-gt|, mean ssim].
+        weight [H,W] float (a mask is the 0/1 case; NaN and negative read as 0, above 1 as 1): the weighted loss — terms are the weighted means
+        sum_p w_p sum_c (.) / (3 S), S = sum_p w_p (`weight_sum`), and dL/dimage their gradient (gslic_l1_ssim_loss_weighted_forward_backward:
+        three launches and an 8-byte copy into `terms3`).  The SSIM window statistics still run over all pixels.  S == 0: terms 0, 0 and a zero
+        gradient.  weight=None is the unweighted call, the same two launches as ever."""
         image, gt = image.contiguous(), gt.contiguous()
         CH, H, W = image.shape
+        if weight is not None:
+            if tuple(weight.shape) != (H, W) or weight.dtype != torch.float32 or weight.device != image.device:
+                raise ValueError(f"weight must be a float32 [H,W] = [{H},{W}] tensor on the image's device")
+            weight = weight.contiguous()
+            d1, d2, d3, dL, _partials, terms = self._scratch(image)
+            wpartials, wterms = self._weighted_scratch(image)
+            p, L = _lib.ptr, _lib.lib()
+            _lib.check(L.gslic_l1_ssim_loss_weighted_forward_backward(CH, H, W, C1, C2, self.lambda_dssim, p(image), p(gt), p(weight), p(d1), p(d2),
+                                                                      p(d3), p(wpartials), p(wterms), p(dL), _lib.current_stream_ptr()))
+            terms.copy_(wterms[:2])   # terms3 stays [L1, SSIM, L_d]; S is `weight_sum`
+            return dL, terms
         d1, d2, d3, dL, partials, terms = self._scratch(image)
         p, L = _lib.ptr, _lib.lib()
         # (two launches: the reduction of the forward's partial sums rides on the backward kernel; gslic_l1_ssim_loss_forward + _backward are three)

@@ -104,6 +104,7 @@ CHECK_FUSED_DEPTH_POSE = os.path.join(PKG, "fused_depth_pose_check")
 CHECK_FUSED_PRUNE = os.path.join(PKG, "fused_prune_check")
 CHECK_FUSED_CONTRIBUTION = os.path.join(PKG, "fused_contribution_check")
 CHECK_FUSED_DENSIFY = os.path.join(PKG, "fused_densify_check")
+CHECK_FUSED_WEIGHTED = os.path.join(PKG, "fused_weighted_check")
 
 
 def build_fused_check(force=False):
@@ -139,6 +140,12 @@ def build_fused_densify_check(force=False):
     """fused_densify_check: densification from C++ (gslic::FusedStep::accumulate_contribution with an error image, gslic::FusedStep::densify
     between fused steps) — built like fused_check."""
     return _build_fused_program(os.path.join(HERE, "fused_densify_check.cpp"), CHECK_FUSED_DENSIFY, force)
+
+
+def build_fused_weighted_check(force=False):
+    """fused_weighted_check: the fused training step and the pose gradient under a per-pixel weight image from C++ (gslic::FusedStep::step /
+    pose_gradient with weight) — built like fused_check."""
+    return _build_fused_program(os.path.join(HERE, "fused_weighted_check.cpp"), CHECK_FUSED_WEIGHTED, force)
 
 
 def _build_fused_program(src, CHECK_FUSED, force):
@@ -177,3 +184,4 @@ if __name__ == "__main__":
     print(build_fused_prune_check(force="--force" in sys.argv))
     print(build_fused_contribution_check(force="--force" in sys.argv))
     print(build_fused_densify_check(force="--force" in sys.argv))
+    print(build_fused_weighted_check(force="--force" in sys.argv))

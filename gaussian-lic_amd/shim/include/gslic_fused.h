@@ -329,30 +329,37 @@ public:
     int64_t capacity() const { return buf_[0].defined() ? buf_[0].size(0) : prm_[0].size(0); }
 
     // One optimisation step on one view.  Returns the device tensor [mean |image - gt|, mean ssim]; nothing synchronises.
-    torch::Tensor step(const FusedCamera& cam, const torch::Tensor& gt_image) { return step_body(cam, gt_image, nullptr, 0.0f); }
+    torch::Tensor step(const FusedCamera& cam, const torch::Tensor& gt_image) { return step_body(cam, gt_image, nullptr, 0.0f, nullptr); }
 
     // One optimisation step on one view with LiDAR depth supervision.  Returns the device tensor [mean |image - gt|, mean ssim, L_d]; nothing
     // synchronises.  An undefined gt_depth or lambda_depth == 0 is the colour-only step above (two terms).
-    torch::Tensor step(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor& gt_depth, float lambda_depth)
+    // weight (optional, fp32 [H,W]; a mask is the 0/1 case): the colour loss becomes the weighted one — gslic_l1_ssim_loss_weighted_forward_backward,
+    // the calls of the Python host's training_step_fused(weight=...); terms[0:2] are the weighted means and weight_sum() the sum of the weights.  An
+    // undefined weight is the unweighted step, the same calls as ever.
+    torch::Tensor step(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor& gt_depth, float lambda_depth,
+                       const torch::Tensor& weight = torch::Tensor())
     {
-        return step_body(cam, gt_image, gt_depth.defined() && lambda_depth != 0.0f ? &gt_depth : nullptr, lambda_depth);
+        return step_body(cam, gt_image, gt_depth.defined() && lambda_depth != 0.0f ? &gt_depth : nullptr, lambda_depth, weight.defined() ? &weight : nullptr);
     }
+    // S = the sum of the (clamped) weights of the last weighted step / pose gradient: a device [1] view (undefined before the first)
+    torch::Tensor weight_sum() const { return wterms_.defined() ? wterms_.slice(0, 2, 3) : torch::Tensor(); }
 
     // Gradient of the training loss w.r.t. a LEFT se(3) increment of the camera pose, T_cw <- exp(xi^) T_cw, xi = (rho, phi) — the "cam" of the
     // north-star; the reference's autograd node returns nothing for its camera inputs (rasterizer.cpp:171-182).  Forward + loss kernels +
     // gslic_rasterize_backward_camera (the map is NOT updated), then the chain of gaussian-lic_amd/camera.py:Camera.pose_gradient:
     //   G = dL/dV + Proj^T dL/d(Proj V) (top three rows; Proj = (Proj V) V^-1),  G_R = G[:, :3] - t g_c^T,  G_t = G[:, 3] - R g_c,
     //   dL/drho = G_t,  dL/dphi = vee(M - M^T) + t x G_t,  M = G_R R^T.          Returns {d/drho[3], d/dphi[3]}; synchronises (35 floats to the host).
-    std::array<double, 6> pose_gradient(const FusedCamera& cam, const torch::Tensor& gt_image) { return pose_gradient_body(cam, gt_image, nullptr, 0.0f, nullptr); }
+    std::array<double, 6> pose_gradient(const FusedCamera& cam, const torch::Tensor& gt_image) { return pose_gradient_body(cam, gt_image, nullptr, 0.0f, nullptr, nullptr); }
     // The same gradient under LiDAR depth supervision: loss = (1 - lambda) L1 + lambda (1 - SSIM) + lambda_depth L_d.  gslic_rasterize_forward_depth, the
     // colour and depth loss calls of step(cam, gt_image, gt_depth, lambda_depth), gslic_rasterize_backward_depth_camera, the same chain — the calls
     // gaussian-lic_amd/trainer.py:pose_gradient(gt_depth=...) issues.  terms_out (optional): the device tensor [mean L1, mean SSIM, L_d].  An undefined
-    // gt_depth or lambda_depth == 0 is the colour-only gradient above.
+    // gt_depth or lambda_depth == 0 is the colour-only gradient above.  weight (optional, fp32 [H,W]): the weighted colour loss, as step()'s.
     std::array<double, 6> pose_gradient(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor& gt_depth, float lambda_depth,
-                                        torch::Tensor* terms_out = nullptr)
+                                        torch::Tensor* terms_out = nullptr, const torch::Tensor& weight = torch::Tensor())
     {
-        if (!gt_depth.defined() || lambda_depth == 0.0f) return pose_gradient(cam, gt_image);
-        return pose_gradient_body(cam, gt_image, &gt_depth, lambda_depth, terms_out);
+        const torch::Tensor* w = weight.defined() ? &weight : nullptr;
+        if (!gt_depth.defined() || lambda_depth == 0.0f) return w ? pose_gradient_body(cam, gt_image, nullptr, 0.0f, terms_out, w) : pose_gradient(cam, gt_image);
+        return pose_gradient_body(cam, gt_image, &gt_depth, lambda_depth, terms_out, w);
     }
     // the chain alone, on host arrays in the element order of the kernels' inputs (float[16] with (r, c) at [4c + r])
     static std::array<double, 6> se3_pose_gradient(const float* view16, const float* fullproj16, const float* dview16, const float* dproj16, const float* dcampos3)
@@ -430,6 +437,23 @@ private:
     {
         if (!radii_.defined() || radii_.size(0) != P) radii_ = torch::empty({P}, prm_[0].options().requires_grad(false).dtype(torch::kInt32));
     }
+    // the weighted colour loss of a step: the three launches, then terms[0:2] <- the weighted means (S stays in wterms_[2]: weight_sum())
+    void weighted_loss(int H, int W, const torch::Tensor& image, const torch::Tensor& gt_image, const torch::Tensor& weight, torch::Tensor& d1,
+                       torch::Tensor& d2, torch::Tensor& d3, torch::Tensor& terms, torch::Tensor& dL)
+    {
+        TORCH_CHECK(weight.is_contiguous() && weight.scalar_type() == torch::kFloat32 && weight.dim() == 2 && weight.size(0) == H && weight.size(1) == W,
+                    "weight must be contiguous fp32 [H,W]");
+        auto fo = prm_[0].options().requires_grad(false);
+        const int64_t n = gslic_l1_ssim_loss_weighted_partials_count(3, H, W);
+        if (!wpartials_.defined() || wpartials_.size(0) != n) wpartials_ = torch::empty({n}, fo);
+        if (!wterms_.defined()) wterms_ = torch::zeros({3}, fo);
+        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;   // loss_utils.h:187-188
+        check(gslic_l1_ssim_loss_weighted_forward_backward(3, H, W, C1, C2, lambda_dssim_, f(image), f(gt_image), f(weight), d1.data_ptr<float>(),
+                                                           d2.data_ptr<float>(), d3.data_ptr<float>(), wpartials_.data_ptr<float>(), wterms_.data_ptr<float>(),
+                                                           dL.data_ptr<float>(), current_stream()),
+              "gslic_l1_ssim_loss_weighted_forward_backward");
+        terms.slice(0, 0, 2).copy_(wterms_.slice(0, 0, 2));
+    }
     static void check_targets(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor* gt_depth)
     {
         const int W = cam.image_width, H = cam.image_height;
@@ -439,7 +463,8 @@ private:
     }
 
     // the step; gt_depth != nullptr: under depth supervision (the depth forward, the depth loss, the depth backward)
-    torch::Tensor step_body(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor* gt_depth, float lambda_depth)
+    torch::Tensor step_body(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor* gt_depth, float lambda_depth,
+                            const torch::Tensor* weight)
     {
         torch::NoGradGuard ng;
         const bool depth = gt_depth != nullptr;
@@ -468,6 +493,9 @@ private:
                   "gslic_rasterize_forward");
         const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;   // loss_utils.h:187-188
         // (forward + backward of the loss in two launches: the reduction of the partial sums rides on the backward kernel)
+        if (weight)
+            weighted_loss(H, W, image_, gt_image, *weight, dm_[0], dm_[1], dm_[2], terms, dL_dimage_);
+        else
         check(gslic_l1_ssim_loss_forward_backward(1, 3, H, W, C1, C2, lambda_dssim_, f(image_), f(gt_image), dm_[0].data_ptr<float>(),
                                                   dm_[1].data_ptr<float>(), dm_[2].data_ptr<float>(), partials_.data_ptr<float>(),
                                                   terms.data_ptr<float>(), dL_dimage_.data_ptr<float>(), current_stream()),
@@ -494,7 +522,7 @@ private:
     // the pose gradient; gt_depth != nullptr: under depth supervision.  (The colour-only path runs the loss as gslic_l1_ssim_loss_forward + _backward,
     // the depth path as the fused pair of calls: both as they were.)
     std::array<double, 6> pose_gradient_body(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor* gt_depth, float lambda_depth,
-                                             torch::Tensor* terms_out)
+                                             torch::Tensor* terms_out, const torch::Tensor* weight)
     {
         torch::NoGradGuard ng;
         const bool depth = gt_depth != nullptr;
@@ -522,6 +550,9 @@ private:
                                                 dc, rest, nullptr, op, sc, rot, nullptr, view, proj, cpos, image.data_ptr<float>(), final_T.data_ptr<float>(),
                                                 zimg.data_ptr<float>(), radii.data_ptr<int32_t>(), &R, &B, current_stream()),
                   "gslic_rasterize_forward_depth");
+            if (weight)
+                weighted_loss(H, W, image, gt_image, *weight, d1, d2, d3, terms, dL);
+            else
             check(gslic_l1_ssim_loss_forward_backward(1, 3, H, W, C1, C2, lambda_dssim_, f(image), f(gt_image), d1.data_ptr<float>(), d2.data_ptr<float>(),
                                                       d3.data_ptr<float>(), partials.data_ptr<float>(), terms.data_ptr<float>(), dL.data_ptr<float>(),
                                                       current_stream()),
@@ -538,10 +569,14 @@ private:
             check(gslic_rasterize_forward(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), xyz, dc, rest,
                                           nullptr, op, sc, rot, nullptr, view, proj, cpos, image.data_ptr<float>(), final_T.data_ptr<float>(),
                                           radii.data_ptr<int32_t>(), &R, &B, current_stream()), "gslic_rasterize_forward");
+            if (weight) {
+                weighted_loss(H, W, image, gt_image, *weight, d1, d2, d3, terms, dL);
+            } else {
             check(gslic_l1_ssim_loss_forward(1, 3, H, W, C1, C2, f(image), f(gt_image), d1.data_ptr<float>(), d2.data_ptr<float>(), d3.data_ptr<float>(),
                                              partials.data_ptr<float>(), terms.data_ptr<float>(), current_stream()), "gslic_l1_ssim_loss_forward");
             check(gslic_l1_ssim_loss_backward(1, 3, H, W, lambda_dssim_, f(image), f(gt_image), f(d1), f(d2), f(d3), dL.data_ptr<float>(), current_stream()),
                   "gslic_l1_ssim_loss_backward");
+            }
             check(gslic_rasterize_backward_camera(&rp, R, B, f(bg_), xyz, dc, rest, nullptr, sc, rot, nullptr, view, proj, cpos, radii.data_ptr<int32_t>(),
                                                   cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), cptr(scratch_[3]), f(dL), nullptr, nullptr, w(g[3]),
                                                   nullptr, w(g[0]), nullptr, w(g[1]), w(g[2]), w(g[4]), w(g[5]), lambda_erank_, cg, cg + 16, cg + 32,
@@ -629,6 +664,7 @@ private:
     torch::Tensor scratch_[4];   // geom, binning, img, sample — order of the C-ABI's allocator arguments
     torch::Tensor bg_, image_, final_T_, radii_, dm_[3], dL_dimage_, partials_, tie_;
     torch::Tensor depth_, dL_ddepth_, depth_partials_, xyz_grad_;   // depth steps
+    torch::Tensor wpartials_, wterms_;                              // weighted loss: scratch and {L1_w, SSIM_w, S}
 };
 
 }  // namespace gslic

@@ -908,12 +908,12 @@ class _RawRaster:
                             sample, self.lambda_erank, **modes)
 
 
-def _fused_losses(fl, image, gt_image, depth, gt_depth, lambda_depth):
-    """The colour loss kernels and, for a depth image, the depth loss kernels: (dL/dimage, dL/ddepth or None, terms)."""
+def _fused_losses(fl, image, gt_image, depth, gt_depth, lambda_depth, weight=None):
+    """The colour loss kernels (weight [H,W]: the weighted ones) and, for a depth image, the depth loss kernels: (dL/dimage, dL/ddepth or None, terms)."""
     if depth is None:
-        dL_dimage, terms = fl.forward_backward(image, gt_image)
+        dL_dimage, terms = fl.forward_backward(image, gt_image, weight)
         return dL_dimage, None, terms
-    dL_dimage, _ = fl.forward_backward(image, gt_image)
+    dL_dimage, _ = fl.forward_backward(image, gt_image, weight)
     dL_ddepth, _ = fl.depth_forward_backward(depth, gt_depth, lambda_depth)
     return dL_dimage, dL_ddepth, fl.terms3
 
@@ -1015,7 +1015,7 @@ def allreduce_gradients(grads, visible):
 
 
 def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_step=True, raw_render=None, one_node_loss=False, gt_depth=None,
-                  lambda_depth=0.0):
+                  lambda_depth=0.0, weight=None):
     """One iteration of optimize()'s loop (gaussian.cpp:674-716) the way the reference's host writes it: render -> 0.8*L1 + 0.2*(1-SSIM) ->
     loss.backward() -> sparse Adam, on LibTorch autograd.  Returns (loss tensor, visible mask).
     raw_render: passed to render() — None = its default (the drop-in renderer: activations inside the kernels), False = renderer.cpp as written
@@ -1023,14 +1023,22 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
     instead of the reference's l1_loss + fused_ssim lines (gaussian.cpp:685-691).
     gt_depth [H,W] (0 = no measurement, e.g. Camera.project_depth of the LiDAR points) with lambda_depth > 0 (not in the reference): the
     rendered depth (render(return_depth=True)) is supervised too, loss += lambda_depth * depth_l1(depth, gt_depth).  gt_depth=None or
-    lambda_depth=0 is exactly the colour-only step (no depth is rendered)."""
+    lambda_depth=0 is exactly the colour-only step (no depth is rendered).
+    weight [H,W] (not in the reference; a mask is the 0/1 case, clamped to [0,1]): the colour terms become the weighted means
+    (w |d|).sum() / (3 S) and (FusedSSIMMap w).sum() / (3 S), S = w.sum() (both 0 when S == 0), from the existing operators; None = the plain means."""
     use_depth = gt_depth is not None and lambda_depth != 0.0
     if use_depth:
         image, _final_T, _pts, visible, _radii, depth = render(camera, model, bg, raw=raw_render, return_depth=True)
     else:
         image, _final_T, _pts, visible, _radii = render(camera, model, bg, raw=raw_render)
     if one_node_loss:
-        loss = loss_utils.l1_ssim_loss(image, gt_image, lambda_dssim)
+        loss = loss_utils.l1_ssim_loss(image, gt_image, lambda_dssim, weight)
+    elif weight is not None:
+        w = loss_utils.clamp_weight(weight.detach())
+        n = (3.0 * w.sum()).clamp_min(torch.finfo(torch.float32).tiny)
+        Ll1 = (w * torch.abs(image - gt_image)).sum() / n
+        ssim_value = (loss_utils.FusedSSIMMap.apply(loss_utils.C1, loss_utils.C2, image.unsqueeze(0), gt_image.unsqueeze(0)) * w).sum() / n
+        loss = (1.0 - lambda_dssim) * Ll1 + lambda_dssim * (1.0 - ssim_value)
     else:
         Ll1 = loss_utils.l1_loss(image, gt_image)
         ssim_value = loss_utils.fused_ssim(image.unsqueeze(0), gt_image.unsqueeze(0))
@@ -1049,30 +1057,31 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
     return loss.detach(), visible
 
 
-def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, lambda_depth=0.0):
+def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None):
     """dL/dxi of the training loss w.r.t. a left se(3) increment of the camera pose (Camera.pose_gradient) for the current map: forward -> loss
     kernels -> gslic_rasterize_backward_camera -> the chain.  The map is not touched.  Returns (float64 [6] = (d/drho, d/dphi), terms).
     One step of pose refinement is `camera.apply_pose_increment(-lr * g); camera.to_device(dev)`.
     gt_depth [H,W] with lambda_depth != 0 (LiDAR depth supervision, as training_step_fused's): the loss gains lambda_depth * depth_l1 and the
     gradient its share — depth forward -> colour and depth loss kernels -> gslic_rasterize_backward_depth_camera -> the same chain; terms is
-    then [mean L1, mean SSIM, L_d].  gt_depth=None or lambda_depth=0 is exactly the colour-only path."""
+    then [mean L1, mean SSIM, L_d].  gt_depth=None or lambda_depth=0 is exactly the colour-only path.
+    weight [H,W]: the weighted colour loss (FusedLoss.forward_backward); it combines freely with gt_depth."""
     fl = fused_loss or _default_fused_loss()
     use_depth = gt_depth is not None and lambda_depth != 0.0
     with torch.no_grad():
         rr = _RawRaster(model, camera, bg, use_depth)
         image, depth, _radii = rr.forward()
-        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth))
+        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight)
         out = rr.backward(dL_dimage, dL_ddepth, camera_grads=True)
     return camera.pose_gradient(out[9], out[10], out[11]), terms
 
 
-def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None, gt_depth=None, lambda_depth=0.0):
+def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None):
     """One joint map + pose iteration: forward -> loss kernels -> gslic_rasterize_backward_camera (parameter gradients AND the camera gradient in
     one pass) -> masked Adam on the map -> `camera` moved by -pose_lr * dL/dxi (left se(3) increment; 35 floats cross to the host, which is the
     step's only synchronisation).  Returns (terms, visible, dL/dxi).
     gt_depth [H,W] with lambda_depth != 0: the same step under LiDAR depth supervision (depth forward, colour and depth loss kernels,
     gslic_rasterize_backward_depth_camera); the map update equals training_step_fused(gt_depth=...)'s, terms is [mean L1, mean SSIM, L_d].
-    gt_depth=None or lambda_depth=0 is exactly the colour-only step."""
+    gt_depth=None or lambda_depth=0 is exactly the colour-only step.  weight [H,W]: the weighted colour loss, as training_step_fused's."""
     fl = fused_loss or _default_fused_loss()
     use_depth = gt_depth is not None and lambda_depth != 0.0
     cam = camera
@@ -1081,7 +1090,7 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
             _grad_slab(model)   # (the depth step sets the slab up ahead of its forward, the colour step behind its loss: both as they were)
         rr = _RawRaster(model, cam, bg, use_depth)
         image, depth, radii = rr.forward()
-        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth))
+        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight)
         slab = _grad_slab(model)
         out = rr.backward(dL_dimage, dL_ddepth, out=slab.views, camera_grads=True)
         visible = radii > 0
@@ -1093,7 +1102,8 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
     return terms, visible, g
 
 
-def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=True, adam_in_backward=True, gt_depth=None, lambda_depth=0.0):
+def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=True, adam_in_backward=True, gt_depth=None, lambda_depth=0.0,
+                        weight=None):
     """The same iteration as training_step — identical arithmetic up to fp32 rounding — on the fused entry points
     (SURVEY.md §8f row 2): sigmoid / exp / normalize and their backward run inside preprocess / preprocess_bwd (raw_params),
     the loss and dL/dimage come from two loss kernels, and there is no autograd graph: 0 LibTorch elementwise launches per step
@@ -1102,7 +1112,10 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
     depth-loss kernels (gslic_depth_l1_loss_forward_backward), then the depth backward with the Adam update inside
     (gslic_rasterize_backward_depth_adam) or, adam_in_backward=False, the depth backward and SparseGaussianAdam.step; terms is then
     [mean L1, mean SSIM, L_d] and the loss FusedLoss.value(terms, lambda_depth).  gt_depth=None or lambda_depth=0 is exactly the colour-only
-    step.  Single GPU only: the N > 1 exchange carries no depth gradient (NotImplementedError)."""
+    step.  Single GPU only: the N > 1 exchange carries no depth gradient (NotImplementedError).
+    weight [H,W] float (a mask is the 0/1 case): the colour loss becomes the weighted one (FusedLoss.forward_backward(weight=...): three loss
+    launches instead of two, terms the weighted means, FusedLoss.weight_sum the sum of the weights); it combines freely with gt_depth and, the
+    loss being rank-local, with N > 1.  weight=None is exactly the unweighted step."""
     fl = fused_loss or _default_fused_loss()
     use_depth = gt_depth is not None and lambda_depth != 0.0
     if use_depth and _dist_on():
@@ -1115,7 +1128,7 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
     with torch.no_grad():
         rr = _RawRaster(model, cam, bg, use_depth)
         image, depth, radii = rr.forward()
-        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth))
+        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight)
         if do_step and adam_in_backward and not _dist_on():
             # single GPU: nothing to exchange, so the Adam update runs inside the per-Gaussian backward kernel while the
             # gradients are still in registers / LDS (bit-identical to backward + SparseGaussianAdam.step, ~2 GB less HBM traffic);
@@ -1211,10 +1224,14 @@ class GraphedStep:
     gt_depth [H,W] with lambda_depth != 0 (LiDAR depth supervision): the step is training_step_fused's depth step in capacity mode
     (gslic_rasterize_forward_depth_capacity -> colour and depth loss kernels -> gslic_rasterize_backward_depth_adam).  lambda_depth is baked
     into the step; the depth target lives in a static buffer like the image and is passed to step() the same way (and repeated steps use their
-    own, checked by reference and version counter like gt_image).  terms is then [mean L1, mean SSIM, L_d]."""
+    own, checked by reference and version counter like gt_image).  terms is then [mean L1, mean SSIM, L_d].
+
+    weight [H,W]: the step runs the weighted colour loss (training_step_fused(weight=...)).  Whether it does is baked into the step; the weight
+    image lives in a static buffer like the depth target and is passed to step() the same way (None = the one that is loaded), under the same
+    checks when a step is repeated.  A step built without a weight raises when it is handed one; a step built with one raises on weight=False."""
 
     def __init__(self, model, camera, gt_image, bg, headroom=1.25, check_every=16, cap_R=None, cap_B=None, use_graph=False, gt_depth=None,
-                 lambda_depth=0.0):
+                 lambda_depth=0.0, weight=None):
         """use_graph=False (default since round 5): the capacity-mode step (caller-owned scratch, no host round trip, overflow checks and repeats as
         below) issued as eager launches; use_graph=True: captured in a hipGraph and replayed with one launch per step.  The two are equally fast at
         2M Gaussians (bench.py: `capacity_eager` / `graphed`; the host runs ahead of the device either way), and the eager form has no hazard:
@@ -1234,6 +1251,8 @@ class GraphedStep:
         self.use_depth = gt_depth is not None and lambda_depth != 0.0
         self.lambda_depth = float(lambda_depth) if self.use_depth else 0.0
         self.gt_depth = gt_depth.detach().float().contiguous().clone() if self.use_depth else None
+        self.use_weight = weight is not None
+        self.weight = weight.detach().float().contiguous().clone() if self.use_weight else None
         self.fl = loss_utils.FusedLoss(LAMBDA_DSSIM)
         self.e = torch.empty(0, device=dev)
         # sizes from one eager forward of the current state
@@ -1256,7 +1275,7 @@ class GraphedStep:
     def _eager(self):
         rr = _RawRaster(self.model, self.cam, self.bg, self.use_depth, e=self.e, pose=(self.view, self.proj, self.campos))
         image, depth, _radii = rr.forward(self.bufs)
-        dL_dimage, dL_ddepth, self.terms = _fused_losses(self.fl, image, self.gt, depth, self.gt_depth, self.lambda_depth)
+        dL_dimage, dL_ddepth, self.terms = _fused_losses(self.fl, image, self.gt, depth, self.gt_depth, self.lambda_depth, self.weight)
         rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad)
 
     def _capture(self):
@@ -1298,9 +1317,22 @@ class GraphedStep:
         device between two replays)."""
         return (camera.world_view_transform.copy(), camera.full_proj_transform.copy(), camera.camera_center.copy())
 
-    def _load(self, camera, gt_image, gt_depth=None):
+    def _load(self, camera, gt_image, gt_depth=None, weight=None):
         """Refresh the static buffers the captured step reads.  The pose is copied on every call that names a camera (the same Camera object
         may have been moved in place since it was loaded last)."""
+        if weight is False:   # "this step runs without a weight": true only of a step that was built without one
+            if self.use_weight:
+                raise ValueError("GraphedStep: this step was built with a weight and always runs the weighted loss (pass ones to weigh every pixel "
+                                 "alike, or build a step without a weight)")
+            weight = None
+        if weight is not None:
+            if not self.use_weight:
+                raise ValueError("GraphedStep: weight given to a step built without one (pass weight to the constructor)")
+            if tuple(weight.shape) != tuple(self.weight.shape):
+                raise ValueError(f"GraphedStep: weight of shape {tuple(weight.shape)} given to a step built for {tuple(self.weight.shape)}")
+            if weight.data_ptr() != self.weight.data_ptr():
+                self.weight.copy_(weight)
+                self._w_serial = getattr(self, "_w_serial", 0) + 1
         if gt_depth is not None:
             if not self.use_depth:
                 raise ValueError("GraphedStep: gt_depth given to a step built without depth supervision (pass gt_depth / lambda_depth to the constructor)")
@@ -1317,14 +1349,15 @@ class GraphedStep:
             self.gt.copy_(gt_image)
             self._gt_serial = getattr(self, "_gt_serial", 0) + 1
 
-    def _snapshot(self, gt_image, gt_depth=None):
+    def _snapshot(self, gt_image, gt_depth=None, weight=None):
         """What a repeat of this step needs, independent of what the caller does to its objects afterwards: the pose by VALUE (host copies of the
         35 floats that are loaded now) and the target by reference together with the evidence that it is still the same data (the tensor's
         version counter; for gt_image=None — "the target that is loaded" — the serial number of the load)."""
         if getattr(self, "_pose_host", None) is None:
             self._pose_host = self._pose_of(self.cam)
         return dict(pose=self._pose_host, gt=gt_image, gt_version=None if gt_image is None else gt_image._version, gt_serial=getattr(self, "_gt_serial", 0),
-                    gtd=gt_depth, gtd_version=None if gt_depth is None else gt_depth._version, gtd_serial=getattr(self, "_gtd_serial", 0))
+                    gtd=gt_depth, gtd_version=None if gt_depth is None else gt_depth._version, gtd_serial=getattr(self, "_gtd_serial", 0),
+                    w=weight, w_version=None if weight is None else weight._version, w_serial=getattr(self, "_w_serial", 0))
 
     def _load_snapshot(self, snap):
         dev = self.view.device
@@ -1342,6 +1375,18 @@ class GraphedStep:
             if gt.data_ptr() != self.gt.data_ptr():
                 self.gt.copy_(gt)
                 self._gt_serial = getattr(self, "_gt_serial", 0) + 1
+        if self.use_weight:
+            w = snap.get("w")
+            if w is None:
+                if snap.get("w_serial", 0) != getattr(self, "_w_serial", 0):
+                    raise RuntimeError("GraphedStep: a step that has to be repeated ran on a weight image that has been replaced since (it was issued "
+                                       "with weight=None); pass the weight explicitly to step() when it changes between checks")
+            else:
+                if w._version != snap["w_version"]:
+                    raise RuntimeError("GraphedStep: the weight image of a step that has to be repeated was modified in place after the step was issued")
+                if w.data_ptr() != self.weight.data_ptr():
+                    self.weight.copy_(w)
+                    self._w_serial = getattr(self, "_w_serial", 0) + 1
         if not self.use_depth:
             return
         gtd = snap.get("gtd")
@@ -1368,14 +1413,14 @@ class GraphedStep:
             with torch.no_grad():
                 self._eager()
 
-    def step(self, camera=None, gt_image=None, gt_depth=None):
+    def step(self, camera=None, gt_image=None, gt_depth=None, weight=None):
         """One optimiser step (replay).  Returns the device tensor [mean L1, mean SSIM] of this step's loss terms ([mean L1, mean SSIM, L_d]
-        with depth supervision; gt_depth: this step's depth target, None = the one that is loaded)."""
-        self._load(camera, gt_image, gt_depth)
+        with depth supervision; gt_depth: this step's depth target, None = the one that is loaded; weight: this step's weight image, likewise)."""
+        self._load(camera, gt_image, gt_depth, weight)
         self._issue()
         self.steps_issued += 1
         if len(self.window) < 32:
-            self.window.append(self._snapshot(gt_image, gt_depth))
+            self.window.append(self._snapshot(gt_image, gt_depth, None if weight is False else weight))
         self.model.optimizer.count_step()
         if self.check_every and self.steps_issued >= self.check_every:
             self.check()

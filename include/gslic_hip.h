@@ -531,6 +531,21 @@ int gslic_l1_ssim_loss_forward_backward(
     int32_t B, int32_t CH, int32_t H, int32_t W, float C1, float C2, float lambda_dssim, const float* img, const float* gt,
     float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12, float* partials, float* terms /*[2] device*/, float* dL_dimg, void* stream);
 
+/* gslic_l1_ssim_loss_weighted_forward_backward — the same loss and its gradient under a per-pixel weight image (additive, ABI 8; one image,
+ * the fused callers never batch).  weight [H,W] float DEVICE, shared by the CH channels; a mask is the 0/1 case.  The kernels read NaN and
+ * negative weights as 0 and weights above 1 (+inf included) as 1.  With S = sum_p w_p:
+ *   terms[0] = L1_w = sum_p w_p sum_c |img - gt| / (CH S),  terms[1] = SSIM_w = sum_p w_p sum_c ssim_c(p) / (CH S),  terms[2] = S,
+ *   dL_dimg = c_l1 w_p sign(img - gt) + fusedssim_backward(dL_dmap = c_ssim w_p),  c_l1 = (1-lambda)/(CH S),  c_ssim = -lambda/(CH S)
+ * (each coefficient one float division by the float product CH * S; bit for bit that chain on the entry points above, and with w == 1 the
+ * bits of gslic_l1_ssim_loss_forward_backward).  The window statistics are taken over ALL pixels: a window that straddles masked pixels is not
+ * re-normalised.  S == 0: terms 0, 0, 0 and dL_dimg all zeros.  THREE launches (forward, a one-workgroup reduction that leaves the coefficients
+ * in `partials`, backward), fixed summation order (bit-reproducible), no allocation, no host synchronisation (graph-capturable).
+ * `partials`: DEVICE scratch of gslic_l1_ssim_loss_weighted_partials_count(CH, H, W) floats. */
+int64_t gslic_l1_ssim_loss_weighted_partials_count(int32_t CH, int32_t H, int32_t W);
+int gslic_l1_ssim_loss_weighted_forward_backward(
+    int32_t CH, int32_t H, int32_t W, float C1, float C2, float lambda_dssim, const float* img, const float* gt, const float* weight,
+    float* dm_dmu1, float* dm_dsigma1_sq, float* dm_dsigma12, float* partials, float* terms /*[3] device*/, float* dL_dimg, void* stream);
+
 /* gslic_depth_l1_loss_forward_backward — the masked depth L1 of LiDAR depth supervision and its gradient in TWO launches (no reference
  * counterpart): mask = gt_depth > 0, n = number of masked pixels, term[0] = L_d = sum_mask |depth - gt_depth| / max(n, 1) (DEVICE float, fixed-order
  * reduction: bit-reproducible; n is an exact integer count), dL_ddepth [H,W] = (lambda_depth / max(n, 1)) sign(depth - gt_depth) on the mask and 0 off

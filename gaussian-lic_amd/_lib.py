@@ -53,6 +53,7 @@ EXPORTS = [
     "gslic_rasterize_backward_depth_camera", "gslic_prune_select", "gslic_gather_rows", "gslic_contribution_accumulate",
     "gslic_contribution_accumulate_error", "gslic_densify_select", "gslic_densify_emit",
     "gslic_l1_ssim_loss_weighted_partials_count", "gslic_l1_ssim_loss_weighted_forward_backward",
+    "gslic_morton_order", "gslic_permute_rows", "gslic_permute_rows_staging_bytes",
 ]
 
 _lib = None
@@ -124,6 +125,10 @@ def lib():
     L.gslic_prune_select.argtypes = [i32, vp, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, i32, ALLOC_FN, vp, vp, vp,
                                      ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.gslic_gather_rows.argtypes = [ctypes.POINTER(RowArray), i32, vp, i32, vp]
+    L.gslic_morton_order.argtypes = [i32, vp, vp, ALLOC_FN, vp, vp, vp, vp]   # P, xyz, box, allocator + context, perm, keys_sorted, stream
+    L.gslic_permute_rows.argtypes = [ctypes.POINTER(RowArray), i32, vp, i32, vp, ctypes.c_size_t, vp]   # arrays, n, perm, n_rows, staging + bytes, stream
+    L.gslic_permute_rows_staging_bytes.restype = ctypes.c_size_t
+    L.gslic_permute_rows_staging_bytes.argtypes = [ctypes.POINTER(RowArray), i32, i32]
     L.gslic_contribution_accumulate.argtypes = [prm, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp]   # params, R, B, geom / binning / img, w_min, 3 outputs, stream
     L.gslic_contribution_accumulate_error.argtypes = [prm, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]   # ... 3 outputs, err, err_sum, stream
     L.gslic_densify_select.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, ALLOC_FN, vp, vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]

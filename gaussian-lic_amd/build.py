@@ -34,6 +34,7 @@ SOURCES = {
     "extend.hip": ["-ffp-contract=off"],  # pixel assignment decides integers: canonical order like preprocess.hip
     "prune.hip": [],         # comparisons and copies only: no arithmetic a flag could change
     "row_ops.hip": [],       # the segmented row kernel of prune and densify: copies, zeros and comparisons only
+    "morton.hip": ["-ffp-contract=off"],   # the key rule of gslic_morton_order: every float32 step rounded on its own, tested on bits
     "contrib.hip": ["-ffp-contract=off"],  # replays the strict blend: every product of the power and of w = alpha T is rounded on its own
     "densify.hip": ["-ffp-contract=off"],  # the split children's positions: every product and sum rounded on its own, as the header writes them
 }

@@ -1303,6 +1303,51 @@ int gslic_gather_rows(const gslic_row_array* arrays, int32_t n_arrays, const uin
     return gather_rows(arrays, n_arrays, index, n_rows, (hipStream_t)stream);
 }
 
+int gslic_morton_order(int32_t P, const float* xyz, const float* box, gslic_alloc_fn scratch_alloc, void* scratch_ctx, uint32_t* perm,
+                       uint32_t* keys_sorted, void* stream)
+{
+    if (P < 0) return set_error(GSLIC_ERR_INVALID_ARG, "morton order: negative P");
+    if (P == 0) return GSLIC_OK;
+    if (!xyz || !box || !perm || !scratch_alloc) return set_error(GSLIC_ERR_INVALID_ARG, "morton order: NULL pointer");
+    return morton_order(P, xyz, box, scratch_alloc, scratch_ctx, perm, keys_sorted, (hipStream_t)stream);
+}
+
+size_t gslic_permute_rows_staging_bytes(const gslic_row_array* arrays, int32_t n_arrays, int32_t n_rows)
+{
+    if (!arrays || n_arrays <= 0 || n_rows <= 0) return 0;
+    return gslic_scratch_round_up(permute_rows_bytes(arrays, n_arrays, n_rows));
+}
+
+int gslic_permute_rows(const gslic_row_array* arrays, int32_t n_arrays, const uint32_t* perm, int32_t n_rows, void* staging, size_t staging_bytes,
+                       void* stream)
+{
+    if (n_arrays < 0 || n_rows < 0) return set_error(GSLIC_ERR_INVALID_ARG, "permute rows: negative n_arrays / n_rows");
+    if (n_arrays == 0 || n_rows == 0) return GSLIC_OK;
+    if (!arrays || !perm) return set_error(GSLIC_ERR_INVALID_ARG, "permute rows: NULL pointer");
+    const size_t need = permute_rows_bytes(arrays, n_arrays, n_rows);
+    if (need == 0) return GSLIC_OK;   // (every array has width 0)
+    if (!staging) return set_error(GSLIC_ERR_INVALID_ARG, "permute rows: NULL pointer (staging)");
+    if (staging_bytes < need)
+        return set_error(GSLIC_ERR_INVALID_ARG, "permute rows: staging holds %zu bytes, %zu are needed (gslic_permute_rows_staging_bytes)", staging_bytes, need);
+    // byte ranges of the first n_rows rows of every array, and the staging buffer as declared
+    auto lo = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    auto hi = [&](const gslic_row_array& a) { return reinterpret_cast<uintptr_t>(a.dst) + (size_t)n_rows * a.row_dwords * sizeof(uint32_t); };
+    for (int i = 0; i < n_arrays; i++) {
+        const gslic_row_array& a = arrays[i];
+        if (a.row_dwords == 0) continue;
+        if (!a.src || !a.dst) return set_error(GSLIC_ERR_INVALID_ARG, "permute rows: array %d has a NULL pointer", i);
+        if (a.src != a.dst) return set_error(GSLIC_ERR_INVALID_ARG, "permute rows: array %d has src != dst (the permutation is in place; gslic_gather_rows moves rows between arrays)", i);
+        if (lo(a.dst) < lo(staging) + staging_bytes && lo(staging) < hi(a))
+            return set_error(GSLIC_ERR_INVALID_ARG, "permute rows: staging overlaps array %d", i);
+        for (int j = 0; j < i; j++) {
+            const gslic_row_array& b = arrays[j];
+            if (b.row_dwords == 0) continue;
+            if (lo(a.dst) < hi(b) && lo(b.dst) < hi(a)) return set_error(GSLIC_ERR_INVALID_ARG, "permute rows: array %d overlaps array %d", i, j);
+        }
+    }
+    return permute_rows(arrays, n_arrays, perm, n_rows, staging, (hipStream_t)stream);
+}
+
 // the two contribution entry points: same checks, same early returns, same launch geometry; with_err adds the error image and its accumulator
 static int contribution_accumulate(const gslic_raster_params* prm, int32_t R, int32_t B, const char* geom_buffer, const char* binning_buffer,
                                    const char* img_buffer, float w_min, uint32_t* max_w, uint32_t* n_pix, uint64_t* sum_w, bool with_err,

@@ -166,6 +166,13 @@ int prune_select(int P, const float* xyz, const float* dc, const float* opacity,
                  gslic_alloc_fn alloc, void* ctx, uint32_t* kept_index, uint32_t* new_tie, int32_t* count, int32_t* count_below, hipStream_t s);
 int gather_rows(const gslic_row_array* arrays, int n_arrays, const uint32_t* index, int n_rows, hipStream_t s);
 
+// morton.hip: the key rule of gslic_morton_order and the stable argsort over its 30 bits -> perm / keys_sorted (no synchronisation), and the
+// in-place row permutation of gslic_permute_rows: gather_rows into `staging` (array i at the running sum of the widths before it, times
+// 4 n_rows bytes), then one device-to-device copy per array back (arguments validated by the caller)
+int morton_order(int P, const float* xyz, const float* box, gslic_alloc_fn alloc, void* ctx, uint32_t* perm, uint32_t* keys_sorted, hipStream_t s);
+size_t permute_rows_bytes(const gslic_row_array* arrays, int n_arrays, int n_rows);   // the sum of row_dwords * 4 * n_rows, not rounded
+int permute_rows(const gslic_row_array* arrays, int n_arrays, const uint32_t* perm, int n_rows, void* staging, hipStream_t s);
+
 // contrib.hip: the per-Gaussian contribution statistics of gslic_contribution_accumulate from a completed forward's lists (one workgroup per tile;
 // arguments validated by the caller; any of the three accumulators may be NULL)
 struct ContribArgs {

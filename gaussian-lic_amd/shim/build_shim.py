@@ -105,6 +105,7 @@ CHECK_FUSED_PRUNE = os.path.join(PKG, "fused_prune_check")
 CHECK_FUSED_CONTRIBUTION = os.path.join(PKG, "fused_contribution_check")
 CHECK_FUSED_DENSIFY = os.path.join(PKG, "fused_densify_check")
 CHECK_FUSED_WEIGHTED = os.path.join(PKG, "fused_weighted_check")
+CHECK_FUSED_RESORT = os.path.join(PKG, "fused_resort_check")
 
 
 def build_fused_check(force=False):
@@ -148,6 +149,12 @@ def build_fused_weighted_check(force=False):
     return _build_fused_program(os.path.join(HERE, "fused_weighted_check.cpp"), CHECK_FUSED_WEIGHTED, force)
 
 
+def build_fused_resort_check(force=False):
+    """fused_resort_check: keeping the map in Morton order from C++ (gslic::FusedStep::resort and the set_resort_fraction rule, through extend
+    and prune, between fused steps) — built like fused_check."""
+    return _build_fused_program(os.path.join(HERE, "fused_resort_check.cpp"), CHECK_FUSED_RESORT, force)
+
+
 def _build_fused_program(src, CHECK_FUSED, force):
     import sysconfig
     import torch
@@ -185,3 +192,4 @@ if __name__ == "__main__":
     print(build_fused_contribution_check(force="--force" in sys.argv))
     print(build_fused_densify_check(force="--force" in sys.argv))
     print(build_fused_weighted_check(force="--force" in sys.argv))
+    print(build_fused_resort_check(force="--force" in sys.argv))

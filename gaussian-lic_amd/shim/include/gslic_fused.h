@@ -96,7 +96,61 @@ public:
                     "FusedStep::set_tie_rank: expected one index per Gaussian (", prm_[0].size(0), ") on the model's device; got ", original_index.numel(),
                     " on ", original_index.device());   // (its data pointer goes straight to the kernels)
         tie_ = original_index.to(torch::kInt32).contiguous();
+        sorted_P_ = prm_[0].size(0);   // (the host sorted its rows: the re-sort rule counts the rows appended from here on)
     }
+    // Puts ALL rows into Morton order on the device — the Python host's GaussianModel.resort / to_morton_order (gaussian-lic_amd/trainer.py), same
+    // calls, same result: the robust box from a strided sample of at most 65 536 rows (LibTorch: one sort of the sample, no host read-back),
+    // ONE gslic_morton_order (the exact key rule of include/gslic_hip.h and the stable sort) and ONE gslic_permute_rows over the 18 parameter and
+    // moment arrays, the tie rank and the statistics' arrays, in place through one staging tensor: addresses do not change, param(i) stays valid.
+    // Without a tie rank (rows in insertion order) one is created as arange(P) first: every row's original index is its present row.  The map
+    // renders and trains exactly as before.  Returns the permutation applied (device int64 [P]; new row s = old row perm[s]): per-row state the
+    // host keeps outside is re-aligned with index_select(0, perm).  stats: contribution statistics of this map, permuted with it.
+    torch::Tensor resort(ContributionStats* stats = nullptr)
+    {
+        torch::NoGradGuard ng;
+        const int64_t P = prm_[0].size(0);
+        auto io = prm_[0].options().requires_grad(false).dtype(torch::kInt32);
+        if (!tie_.defined()) tie_ = torch::arange(P, io);
+        sorted_P_ = P;
+        n_resorts_++;
+        if (P == 0) return last_perm_ = torch::empty({0}, io.dtype(torch::kInt64));
+        const torch::Tensor q = prm_[0].detach();
+        const torch::Tensor srt = std::get<0>(torch::sort(q.slice(0, 0, P, std::max<int64_t>(1, P / 65536)), 0));
+        const int64_t ns = srt.size(0);
+        const int64_t i_lo = std::min<int64_t>(ns - 1, (int64_t)(0.001 * (double)ns)), i_hi = std::max<int64_t>(0, std::min<int64_t>(ns - 1, (int64_t)(0.999 * (double)ns)));
+        const torch::Tensor box = torch::cat({srt[i_lo], srt[i_hi]}).contiguous();   // lo xyz, hi xyz: the 0.1 % / 99.9 % order statistics per axis
+        torch::Tensor perm = torch::empty({P}, io), sort_scratch = torch::empty({0}, io.dtype(torch::kByte));
+        check(gslic_morton_order((int32_t)P, f(prm_[0]), box.data_ptr<float>(), grow_cb, &sort_scratch, reinterpret_cast<uint32_t*>(perm.data_ptr<int32_t>()),
+                                 nullptr, current_stream()),
+              "gslic_morton_order");
+        std::vector<gslic_row_array> rows;
+        auto add = [&](const torch::Tensor& t, uint32_t w) { if (w) rows.push_back({t.data_ptr(), t.data_ptr(), w}); };
+        for (int g = 0; g < 6; g++) {
+            const uint32_t w = (uint32_t)(prm_[g].numel() / P);   // (0: features_rest at SH degree 0)
+            add(prm_[g], w); add(m_[g], w); add(v_[g], w);
+        }
+        add(tie_, 1u);
+        if (stats && stats->max_w.defined()) {
+            fit_stats(*stats, capacity(), false);
+            add(stats->max_w, 1u); add(stats->n_pix, 1u); add(stats->sum_w, 2u);
+            if (stats->err_sum.defined()) add(stats->err_sum, 2u);
+        }
+        const size_t bytes = gslic_permute_rows_staging_bytes(rows.data(), (int32_t)rows.size(), (int32_t)P);
+        torch::Tensor staging = torch::empty({(int64_t)bytes}, io.dtype(torch::kByte));
+        check(gslic_permute_rows(rows.data(), (int32_t)rows.size(), reinterpret_cast<const uint32_t*>(perm.data_ptr<int32_t>()), (int32_t)P, staging.data_ptr(),
+                                 bytes, current_stream()),
+              "gslic_permute_rows");
+        return last_perm_ = perm.to(torch::kInt64);
+    }
+    // The re-sort rule of the Python model (GaussianModel.resort_fraction): once the rows appended by extend() / densify() behind the sorted block
+    // make up more than `fraction` of the map, the call that appended them re-sorts the whole map (resort()).  nullopt (the default): never — a
+    // host that does not ask sees no change.  It applies to maps with a tie rank (set_tie_rank, or a first resort()); prune() moves the sorted
+    // block's bound to the kept rows below it.  resorts() counts the re-sorts so far and last_resort() is the last permutation applied (device
+    // int64 [P]; undefined before the first): a host with per-row state of its own compares the count around extend() / densify().
+    void set_resort_fraction(std::optional<double> fraction) { resort_fraction_ = fraction; }
+    int64_t resorts() const { return n_resorts_; }
+    const torch::Tensor& last_resort() const { return last_perm_; }
+    int64_t sorted_rows() const { return sorted_P_; }   // rows [0, sorted_rows()) are in Morton order (0: no sort so far)
 
     // extend() of gaussian.cpp:499-638 for one new LiDAR frame: transmittance-only render of `cam` (no_color, :501-507), device-side
     // selection of the points that land on not-yet-opaque pixels (nearest per pixel, gslic_extend_select), append of the new Gaussians'
@@ -104,8 +158,10 @@ public:
     // instead of the reference's six torch::cat of every parameter and moment (densificationPostfix, :426-497).  After a call that
     // returned k > 0 the six parameter tensors are NEW views: fetch them with param(i).
     //   points, colors [n,3], depths_rsp [n]: device fp32; R_cw [3,3] row-major, t_cw [3] (any device); returns the number inserted.
+    // stats: contribution statistics of this map — only read when the append triggers the re-sort rule (set_resort_fraction), which permutes them.
     int64_t extend(const FusedCamera& cam, const torch::Tensor& points, const torch::Tensor& colors, const torch::Tensor& depths_rsp,
-                   const torch::Tensor& R_cw, const torch::Tensor& t_cw, float fx, float fy, float cx, float cy, float scaling_scale = 1.0f)
+                   const torch::Tensor& R_cw, const torch::Tensor& t_cw, float fx, float fy, float cx, float cy, float scaling_scale = 1.0f,
+                   ContributionStats* stats = nullptr)
     {
         torch::NoGradGuard ng;
         const int64_t P = prm_[0].size(0), n = points.size(0);
@@ -144,6 +200,7 @@ public:
         if (tie_.defined()) tie_ = torch::cat({tie_, torch::arange(P, P + count, tie_.options())});
         bind(P + count);
         torch::cuda::synchronize();   // (the selection scratch is released on return)
+        rows_appended(stats);
         return count;
     }
     // Removes rows from the map on the device — the Python host's GaussianModel.prune (gaussian-lic_amd/trainer.py), same calls, same result:
@@ -177,8 +234,8 @@ public:
         torch::Tensor sel_scratch = torch::empty({0}, io.dtype(torch::kByte));
         int32_t count = 0, below = 0;
         check(gslic_prune_select((int32_t)P, f(prm_[0]), f(prm_[1]), f(prm_[3]), f(prm_[4]), f(prm_[5]), lo, hi, drop_nonfinite ? 1 : 0, u8(dr), u8(pr),
-                                 tie_.defined() ? reinterpret_cast<const uint32_t*>(tie_.data_ptr<int32_t>()) : nullptr, (int32_t)P, grow_cb, &sel_scratch,
-                                 reinterpret_cast<uint32_t*>(kept.data_ptr<int32_t>()),
+                                 tie_.defined() ? reinterpret_cast<const uint32_t*>(tie_.data_ptr<int32_t>()) : nullptr, (int32_t)std::min(sorted_P_, P), grow_cb,
+                                 &sel_scratch, reinterpret_cast<uint32_t*>(kept.data_ptr<int32_t>()),
                                  new_tie.defined() ? reinterpret_cast<uint32_t*>(new_tie.data_ptr<int32_t>()) : nullptr, &count, &below, current_stream()),
               "gslic_prune_select");
         if (count == P) return torch::arange(P, io.dtype(torch::kInt64));
@@ -199,6 +256,7 @@ public:
               "gslic_gather_rows");
         buf_ = nb; mbuf_ = nm; vbuf_ = nv;
         bind(count);
+        sorted_P_ = below;   // the kept rows below the old bound of the sorted block
         if (stats && stats->max_w.defined()) {
             ContributionStats old = *stats;
             stats->max_w = torch::zeros({cap}, io); stats->n_pix = torch::zeros({cap}, io); stats->sum_w = torch::zeros({cap}, io.dtype(torch::kInt64));
@@ -321,6 +379,7 @@ public:
             }
         }
         if (n_split) *n_split = splits;
+        rows_appended(stats);   // (parents are the rows BEFORE a re-sort, as the Python host returns them)
         return parents;
     }
     const torch::Tensor& param(int group) const { return prm_[group]; }
@@ -588,6 +647,12 @@ private:
         return se3_pose_gradient(hv.data_ptr<float>(), hp.data_ptr<float>(), hc.data_ptr<float>(), hc.data_ptr<float>() + 16, hc.data_ptr<float>() + 32);
     }
 
+    // GaussianModel._rows_appended's rule: the appended tail has grown past resort_fraction of the map
+    void rows_appended(ContributionStats* stats)
+    {
+        const int64_t P = prm_[0].size(0);
+        if (tie_.defined() && resort_fraction_ && (double)(P - sorted_P_) > *resort_fraction_ * (double)P) resort(stats);
+    }
     // the statistics' arrays, created zero-filled and grown (zero-extended) to `cap` rows; err_sum only once a view brought an error image
     void fit_stats(ContributionStats& stats, int64_t cap, bool with_err)
     {
@@ -665,6 +730,9 @@ private:
     torch::Tensor bg_, image_, final_T_, radii_, dm_[3], dL_dimage_, partials_, tie_;
     torch::Tensor depth_, dL_ddepth_, depth_partials_, xyz_grad_;   // depth steps
     torch::Tensor wpartials_, wterms_;                              // weighted loss: scratch and {L1_w, SSIM_w, S}
+    std::optional<double> resort_fraction_;                         // the re-sort rule (off by default)
+    int64_t sorted_P_ = 0, n_resorts_ = 0;                          // rows [0, sorted_P_) are in Morton order; resort() calls so far
+    torch::Tensor last_perm_;                                       // the last resort()'s permutation
 };
 
 }  // namespace gslic

@@ -40,6 +40,46 @@ def morton_order(xyz, bits=10):
     return torch.from_numpy(np.argsort(code, kind="stable").astype(np.int64))
 
 
+def morton_box(xyz):
+    """The robust bounding box the device re-sorts quantise over, as a float32 tensor [6] = (lo xyz, hi xyz) on xyz's device: the 0.1 % / 99.9 %
+    order statistics per axis of a strided sample of at most 65 536 rows (sorted per axis).  The bounds only place the quantisation grid, and
+    torch.kthvalue over all rows cost 100 ms of the 103 a re-sort of 2M rows took (profiles/r06d: resort_on_device_ms).  No host read-back."""
+    q = xyz.detach().float()
+    P = int(q.shape[0])
+    smp = q[::max(1, P // 65536)]
+    srt = torch.sort(smp, dim=0).values
+    n_s = int(srt.shape[0])
+    return torch.cat([srt[min(n_s - 1, int(0.001 * n_s))], srt[max(0, min(n_s - 1, int(0.999 * n_s)))]]).contiguous()
+
+
+def morton_order_library(xyz, box, keys=False):
+    """gslic_morton_order on xyz [P,3] (float32, contiguous, on the GPU) and box [6]: the permutation as an int32 device tensor [P] (perm[s] = the old
+    row that becomes row s; ascending keys, equal keys in storage order), and with keys=True also the sorted keys (int32 [P] holding the 30-bit codes).
+    The key rule is exact (include/gslic_hip.h); for finite inputs and the same box it is morton_order_device's construction."""
+    from . import _lib
+    P = int(xyz.shape[0])
+    assert xyz.dtype == torch.float32 and xyz.is_contiguous() and box.dtype == torch.float32 and box.numel() == 6 and box.is_contiguous()
+    perm = torch.empty(P, dtype=torch.int32, device=xyz.device)
+    ks = torch.empty(P, dtype=torch.int32, device=xyz.device) if keys else None
+    scratch = _lib.TensorAllocator(xyz.device)
+    _lib.check(_lib.lib().gslic_morton_order(P, _lib.ptr(xyz), _lib.ptr(box), scratch.cb, None, _lib.ptr(perm), _lib.ptr(ks), _lib.current_stream_ptr()))
+    return (perm, ks) if keys else perm
+
+
+def _permute_in_place(rows, perm, n):
+    """a[s, :] = a[perm[s], :] for s < n and every (tensor, row_dwords) of rows, in place: ONE gslic_permute_rows through one staging tensor."""
+    from . import _lib
+    L = _lib.lib()
+    rows = [(t, w) for t, w in rows if w]
+    if not rows or not n:
+        return
+    arr = (_lib.RowArray * len(rows))(*[_lib.RowArray(t.data_ptr(), t.data_ptr(), w) for t, w in rows])
+    nbytes = int(L.gslic_permute_rows_staging_bytes(arr, len(rows), int(n)))
+    staging = torch.empty(nbytes, dtype=torch.uint8, device=perm.device)
+    _lib.check(L.gslic_permute_rows(arr, len(rows), _lib.ptr(perm), int(n), _lib.ptr(staging), nbytes, _lib.current_stream_ptr()))
+    # (scratch and staging go back to torch's caching allocator, which hands them out again on this same stream only: behind the launches)
+
+
 def morton_order_device(xyz, bits=10):
     """morton_order with torch ops on xyz's own device (a few ms for 2M rows on the GPU: what GaussianModel.resort() runs between keyframes).
     Same construction — `bits` per axis over a robust bounding box (the 0.1 % / 99.9 % order statistics per axis), outliers clamped, ties in row
@@ -47,13 +87,8 @@ def morton_order_device(xyz, bits=10):
     bit-identically (tie_rank), the order only decides how coherent memory is."""
     assert bits <= 10
     q = xyz.detach().float()
-    P = int(q.shape[0])
-    # the robust box from a strided sample of at most 65 536 rows (sorted per axis): the bounds only place the quantisation grid, and
-    # torch.kthvalue over all rows cost 100 ms of the 103 a re-sort of 2M rows took (profiles/r06d: resort_on_device_ms)
-    smp = q[::max(1, P // 65536)]
-    srt = torch.sort(smp, dim=0).values
-    n_s = int(srt.shape[0])
-    lo, hi = srt[min(n_s - 1, int(0.001 * n_s))], srt[max(0, min(n_s - 1, int(0.999 * n_s)))]
+    box = morton_box(q)
+    lo, hi = box[:3], box[3:]
     u = (((q - lo) / (hi - lo).clamp_min(1e-30)).clamp(0.0, 1.0) * ((1 << bits) - 1)).to(torch.int64)
 
     def spread(v):   # 10 bits -> every third bit
@@ -184,17 +219,36 @@ class GaussianModel:
         torch.cuda.synchronize(self.device) if self.device.type == "cuda" else None
         t0 = _time.perf_counter()
         P = self.P
-        perm = morton_order_device(self._buf["xyz"][:P])
-        for _d, _n, t, _w, _zero in self._row_arrays():
-            t[:P] = t[:P][perm]
+        if os.environ.get("GSLIC_RESORT", "library") == "torch":   # the LibTorch route (A/B: tools/resort_probe.py): ~10 elementwise kernels, torch.sort, 19 round trips
+            perm = moved = morton_order_device(self._buf["xyz"][:P])
+            for _d, _n, t, _w, _zero in self._row_arrays():
+                t[:P] = t[:P][perm]
+        else:   # the box (torch, a sample), one gslic_morton_order, ONE gslic_permute_rows over every row array: in place, addresses unchanged
+            xyz = self._buf["xyz"][:P]
+            moved = morton_order_library(xyz, morton_box(xyz))
+            _permute_in_place([(t, w) for _d, _n, t, w, _zero in self._row_arrays()], moved, P)
+            perm = moved.long()
         self._sorted_P = P
         self._rows_version += 1
         for st in self._attached_stats():
-            st._permute(perm)
+            st._permute(moved)
         self._rebind()
         torch.cuda.synchronize(self.device) if self.device.type == "cuda" else None
         self.sort_ms.append(round(1e3 * (_time.perf_counter() - t0), 2))
         return perm
+
+    @torch.no_grad()
+    def to_morton_order(self, resort_fraction=0.1):
+        """Turns a model whose rows are in insertion order into a Morton-ordered one on the device: tie_rank = arange(P) (every row's original
+        index is its present row), then resort().  Afterwards the model behaves as one constructed with order="morton" and grown to this map:
+        extend() / densify() append behind the sorted block and re-sort past `resort_fraction` (None: never).  Returns resort()'s permutation.
+        A model that already is in Morton order is only re-sorted."""
+        if self._tie is None:
+            self._tie = torch.empty(self.capacity, dtype=torch.int32, device=self.device)
+            self._tie[:self.P].copy_(torch.arange(self.P, dtype=torch.int32, device=self.device))
+        self.order = "morton"
+        self.resort_fraction = resort_fraction
+        return self.resort()
 
     @property
     def tie_rank(self):
@@ -561,9 +615,13 @@ class ContributionStats:
         self._sync()
 
     def _permute(self, perm):
+        """resort(): int32 perm = the library route (one gslic_permute_rows over the accumulators), int64 = torch indexing (GSLIC_RESORT=torch)."""
         P = perm.shape[0]
-        for a, _w in self._arrays():
-            a[:P] = a[:P][perm]
+        if perm.dtype == torch.int32:
+            _permute_in_place(self._arrays(), perm, P)
+        else:
+            for a, _w in self._arrays():
+                a[:P] = a[:P][perm]
         self._sync()
 
     # --- accumulation

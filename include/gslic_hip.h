@@ -634,6 +634,51 @@ typedef struct gslic_row_array { const void* src; void* dst; uint32_t row_dwords
 int gslic_gather_rows(const gslic_row_array* arrays, int32_t n_arrays, const uint32_t* index, int32_t n_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * gslic_morton_order / gslic_permute_rows — putting the map's rows (back) into Morton order on the device (no reference counterpart: its rows
+ * stay in insertion order; a LibTorch host would run about ten elementwise int64 kernels, torch.sort and 19 index + copy round trips).  The
+ * step runs measurably faster on rows in Morton order; rendering and training do not depend on the row order as long as
+ * gslic_raster_params.tie_rank holds every row's original index, so tie_rank is one of the arrays a host permutes.
+ *
+ *  order:  one thread per row, then the library's stable radix sort over the 30 key bits.  The key rule is EXACT — every step below is one IEEE
+ *          float32 operation rounded on its own (no contraction, a true division, no reciprocal), so the same steps in any IEEE float32
+ *          arithmetic give the same keys bit for bit.  xyz [P,3] and box [6] = (lo_0, lo_1, lo_2, hi_0, hi_1, hi_2) are on the DEVICE.  Per axis k:
+ *
+ *            e = hi_k - lo_k;            d = (e > 1e-30f) ? e : 1e-30f             (max(hi - lo, 1e-30f); a NaN extent, inf - inf, reads as 1e-30f)
+ *            t = (xyz[i,k] - lo_k) / d
+ *            c = (t > 0) ? ((t < 1) ? t : 1) : 0                                    (min(max(t, 0), 1); NaN reads as 0)
+ *            u_k = (uint32) trunc(c * 1023.0f)                                      (0 .. 1023)
+ *            spread(u): u = (u | u << 16) & 0x030000FF;  u = (u | u << 8) & 0x0300F00F;  u = (u | u << 4) & 0x030C30C3;  u = (u | u << 2) & 0x09249249
+ *          key[i] = spread(u_0) | spread(u_1) << 1 | spread(u_2) << 2                (30 bits)
+ *
+ *          A row outside the box is clamped onto its faces; a row with a NaN coordinate gets 0 on that axis, +inf 1023, -inf 0; an axis with
+ *          hi <= lo puts rows at or below lo on 0 and rows 1e-30 or more above it on 1023.  The box is the caller's: where to put the grid is policy (this
+ *          repository's hosts take a robust box from a sample of the rows).
+ *          Outputs (DEVICE): perm [P] — perm[s] is the old row that becomes row s: rows ascending by key, equal keys in their current storage
+ *          order (the sort is stable), so an already sorted map gives the identity; keys_sorted [P] or NULL — key[perm[s]].  Both are written
+ *          by the sort's last pass; exactly P entries each.  Scratch (12 P bytes plus the sort's histograms) comes from the caller's allocator
+ *          in ONE call and is dead when the launches have run; no stream synchronisation, no host read-back, no atomics.
+ *  permute: a[s, :] <- a[perm[s], :] for s < n_rows and every array a of the HOST array `arrays`, IN PLACE: src == dst names the array (an
+ *          entry with src != dst is GSLIC_ERR_INVALID_ARG; an array of width 0 is skipped).  perm [n_rows] on the DEVICE must be a permutation of
+ *          0 .. n_rows-1: that is the caller's responsibility and is not checked on the device (an entry >= n_rows reads outside the rows).  Two
+ *          steps on the stream: gslic_gather_rows' launch into `staging` (DEVICE; array i's rows at byte offset 4 n_rows times the sum of the
+ *          row_dwords before it; one launch per 32 arrays, the map's 19: one), then one device-to-device copy per array back.  Rows from n_rows on are not
+ *          touched.  staging must hold the sum of row_dwords * 4 * n_rows bytes; gslic_permute_rows_staging_bytes returns that sum rounded as
+ *          gslic_scratch_round_up does (what a caching allocator should be asked for; 0 for no arrays / no rows).  A staging buffer that is
+ *          smaller than the sum, or whose staging_bytes overlap the first n_rows rows of any array, and arrays that overlap each other, are
+ *          GSLIC_ERR_INVALID_ARG before any device work.
+ *  P == 0 / n_rows == 0 / n_arrays == 0 return at once (no allocator call); negative sizes and NULL required pointers: GSLIC_ERR_INVALID_ARG.
+ *  With N > 1 GPUs every rank calls both with identical arguments.
+ */
+int gslic_morton_order(
+    int32_t P, const float* xyz /*[P,3]*/, const float* box /*[6]: lo xyz, hi xyz*/,
+    gslic_alloc_fn scratch_alloc, void* scratch_ctx,
+    uint32_t* perm /*[P]*/, uint32_t* keys_sorted /*[P] or NULL*/, void* stream);
+int gslic_permute_rows(
+    const gslic_row_array* arrays /*HOST; src == dst: the array itself*/, int32_t n_arrays,
+    const uint32_t* perm /*[n_rows]*/, int32_t n_rows, void* staging, size_t staging_bytes, void* stream);
+size_t gslic_permute_rows_staging_bytes(const gslic_row_array* arrays, int32_t n_arrays, int32_t n_rows);
+
+/* ------------------------------------------------------------------------------------------------
  * gslic_contribution_accumulate — per-Gaussian contribution statistics of ONE view, from the buffers a completed forward filled (no
  * reference counterpart; the signal a mapper prunes by: did this Gaussian ever carry weight in a pixel).  One launch, a pass of its own: the
  * training step is not touched.  geom / binning / img: the buffers of gslic_rasterize_forward, _forward_depth or their _capacity variants

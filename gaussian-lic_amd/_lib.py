@@ -38,6 +38,11 @@ class AdamFused(ctypes.Structure):
                 ("lr", ctypes.c_float * 6), ("b1", ctypes.c_float), ("b2", ctypes.c_float), ("eps", ctypes.c_float), ("visible_out", ctypes.c_void_p)]
 
 
+class GradStats(ctypes.Structure):
+    """gslic_grad_stats: the three per-row accumulators of the gradient densification statistics (device pointers, [P] each)."""
+    _fields_ = [("grad_sum", ctypes.c_void_p), ("n_seen", ctypes.c_void_p), ("max_radius", ctypes.c_void_p)]
+
+
 EXPORTS = [
     "gslic_rasterize_forward", "gslic_rasterize_backward", "gslic_rasterize_backward_adam", "gslic_rasterize_backward_camera", "gslic_adam_update", "gslic_adam_update_groups",
     "gslic_fusedssim_forward", "gslic_fusedssim_backward", "gslic_knn_mean_dist2", "gslic_abi_version",
@@ -54,6 +59,7 @@ EXPORTS = [
     "gslic_contribution_accumulate_error", "gslic_densify_select", "gslic_densify_emit",
     "gslic_l1_ssim_loss_weighted_partials_count", "gslic_l1_ssim_loss_weighted_forward_backward",
     "gslic_morton_order", "gslic_permute_rows", "gslic_permute_rows_staging_bytes",
+    "gslic_rasterize_backward_adam_stats", "gslic_rasterize_backward_depth_adam_stats", "gslic_gradient_stats_accumulate",
 ]
 
 _lib = None
@@ -105,6 +111,10 @@ def lib():
     L.gslic_rasterize_backward_depth.argtypes = bwd_head + [vp, vp] + ten + [vp]
     L.gslic_rasterize_backward_adam.argtypes = bwd_head + [vp] + six + [adam, vp]
     L.gslic_rasterize_backward_depth_adam.argtypes = bwd_head + [vp, vp] + six + [adam, vp]
+    gstats = ctypes.POINTER(GradStats)
+    L.gslic_rasterize_backward_adam_stats.argtypes = bwd_head + [vp] + six + [adam, gstats, vp]
+    L.gslic_rasterize_backward_depth_adam_stats.argtypes = bwd_head + [vp, vp] + six + [adam, gstats, vp]
+    L.gslic_gradient_stats_accumulate.argtypes = [i32, vp, vp, gstats, i32, i32, vp]   # P, dL_dmean2D, radii, stats, row_begin, row_end, stream
     L.gslic_rasterize_backward_camera.argtypes = bwd_head + [vp] + ten + [vp] * 3 + [vp]
     L.gslic_rasterize_backward_depth_camera.argtypes = bwd_head + [vp, vp] + ten + [vp] * 3 + [vp]
     L.gslic_rasterize_backward_rgb.argtypes = bwd_head + [vp] + five + [vp]

@@ -27,6 +27,7 @@ SOURCES = {
     "render.hip": ["-fno-slp-vectorize"],
     "render_bwd_scan.hip": ["-fno-slp-vectorize"],
     "preprocess_bwd.hip": [],
+    "preprocess_bwd_gstat.hip": [],   # the gradient-statistics variants of preprocess_bwd.hip's kernels, in a module of their own (their rule pins its own rounding: fp contract(off))
     "adam.hip": [],
     "ssim.hip": ["-ffp-contract=off"],
     "depth_loss.hip": [],    # the maps are held bit-exact to the reference kernels under the same flag (tests/golden/ssim_*.npz)
@@ -40,7 +41,7 @@ SOURCES = {
 }
 COMMON = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-Wno-inline-asm",
           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]
-HEADERS = ["gslic_common.h", "kernels.h", "render_fwd_body.inc", "preprocess_bwd_body.inc", "contrib_body.inc", "loss_bwd_body.inc", "row_rules.h", os.path.join("..", "..", "include", "gslic_hip.h")]
+HEADERS = ["gslic_common.h", "kernels.h", "render_fwd_body.inc", "preprocess_bwd_body.inc", "preprocess_bwd_device.inc", "contrib_body.inc", "loss_bwd_body.inc", "row_rules.h", os.path.join("..", "..", "include", "gslic_hip.h")]
 
 
 def _newer(a, b):

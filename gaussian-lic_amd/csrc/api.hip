@@ -770,6 +770,7 @@ struct BackwardCall {
     bool skip_blend;
     uint8_t* vis_out;
     float* campos_out;
+    const gslic_grad_stats* stats;      // the gradient densification statistics (the fused Adam backwards only); NULL: none
     void* stream;
 };
 
@@ -860,7 +861,12 @@ static int rasterize_backward_impl(const BackwardCall& c)
         pb.cam_partials = geom.cam_scratch;
         pb.cam_out = geom.cam_scratch + 128 * (((size_t)P + 255) / 256);
     }
-    GS_TRY(launch_preprocess_bwd(pb, s));
+    if (c.stats) {
+        const GradStatArgs gs{c.stats->grad_sum, c.stats->n_seen, c.stats->max_radius};
+        GS_TRY(launch_preprocess_bwd(pb, s, &gs));
+    } else {
+        GS_TRY(launch_preprocess_bwd(pb, s));
+    }
     if (dL_dcam) {
         GS_HIP(hipMemcpyAsync(c.dL_dcam[0], pb.cam_out, 16 * sizeof(float), hipMemcpyDeviceToDevice, s));
         GS_HIP(hipMemcpyAsync(c.dL_dcam[1], pb.cam_out + 16, 16 * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1078,6 +1084,84 @@ int gslic_rasterize_backward_depth_adam(const gslic_raster_params* prm, int32_t 
     GS_BACKWARD_SHARED(c); GS_BACKWARD_ADAM(c);
     c.dL_ddepth = dL_ddepth;
     return rasterize_backward_impl(c);
+}
+
+// What the three statistics entry points check before any device work: the pointers, and that none of the three [P] arrays overlaps another or
+// (adam != NULL) a tensor of the Adam descriptor.  fn: the entry the message names.
+static int grad_stats_checks(const char* fn, const gslic_grad_stats* st, int64_t P, int32_t M, const gslic_adam_fused* adam)
+{
+    if (!st || !st->grad_sum || !st->n_seen || !st->max_radius)
+        return set_error(GSLIC_ERR_INVALID_ARG, "%s: stats and its three arrays (grad_sum, n_seen, max_radius) must not be NULL", fn);
+    const char* const names[3] = {"grad_sum", "n_seen", "max_radius"};
+    const uintptr_t a[3] = {reinterpret_cast<uintptr_t>(st->grad_sum), reinterpret_cast<uintptr_t>(st->n_seen), reinterpret_cast<uintptr_t>(st->max_radius)};
+    const uintptr_t len = (uintptr_t)P * 4u;
+    auto overlap = [](uintptr_t x, uintptr_t xn, uintptr_t y, uintptr_t yn) { return x < y + yn && y < x + xn; };
+    for (int i = 0; i < 3; i++)
+        for (int j = i + 1; j < 3; j++)
+            if (overlap(a[i], len, a[j], len)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s and %s overlap", fn, names[i], names[j]);
+    if (!adam) return GSLIC_OK;
+    const uintptr_t width[6] = {3u, 3u, 3u * (uintptr_t)(M > 0 ? M : 0), 1u, 3u, 4u};
+    for (int g = 0; g < 6; g++) {
+        const float* const t[3] = {adam->param[g], adam->exp_avg[g], adam->exp_avg_sq[g]};
+        for (int k = 0; k < 3; k++)
+            for (int i = 0; i < 3; i++)
+                if (t[k] && width[g] && overlap(a[i], len, reinterpret_cast<uintptr_t>(t[k]), len * width[g]))
+                    return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s overlaps an Adam tensor of group %d", fn, names[i], g);
+    }
+    return GSLIC_OK;
+}
+
+int gslic_rasterize_backward_adam_stats(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
+                                        const float* dc, const float* shs, const float* colors_precomp, const float* scales,
+                                        const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                        const float* cam_pos, const int32_t* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                                        char* sample_buffer, const float* dL_dpix, float* dL_dopacity, float* dL_dmean3D, float* dL_ddc,
+                                        float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_erank, const gslic_adam_fused* adam,
+                                        const gslic_grad_stats* stats, void* stream)
+{
+    if (!adam) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_adam_stats: adam descriptor is NULL");
+    GS_TRY(check_params(prm));
+    GS_TRY(grad_stats_checks("gslic_rasterize_backward_adam_stats", stats, prm->P, prm->M, adam));
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_ADAM(c);
+    c.stats = stats;
+    return rasterize_backward_impl(c);
+}
+
+int gslic_rasterize_backward_depth_adam_stats(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
+                                              const float* dc, const float* shs, const float* colors_precomp, const float* scales,
+                                              const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                              const float* cam_pos, const int32_t* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                                              char* sample_buffer, const float* dL_dpix, const float* dL_ddepth, float* dL_dopacity,
+                                              float* dL_dmean3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_erank,
+                                              const gslic_adam_fused* adam, const gslic_grad_stats* stats, void* stream)
+{
+    GS_TRY(check_params(prm));
+    GS_TRY(grad_stats_checks("gslic_rasterize_backward_depth_adam_stats", stats, prm->P, prm->M, adam));
+    if (prm->P == 0) return GSLIC_OK;
+    if (!adam) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_adam_stats: adam descriptor is NULL");
+    GS_TRY(depth_backward_checks(prm, dL_ddepth, "gslic_rasterize_backward_adam_stats", ""));
+    if (!dL_dmean3D)
+        return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_adam_stats: dL_dmean3D is NULL (the xyz gradient is assembled there before its update)");
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_ADAM(c);
+    c.dL_ddepth = dL_ddepth;
+    c.stats = stats;
+    return rasterize_backward_impl(c);
+}
+
+int gslic_gradient_stats_accumulate(int32_t P, const float* dL_dmean2D, const int32_t* radii, const gslic_grad_stats* stats, int32_t row_begin,
+                                    int32_t row_end, void* stream)
+{
+    if (P < 0) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_gradient_stats_accumulate: P=%d", P);
+    GS_TRY(grad_stats_checks("gslic_gradient_stats_accumulate", stats, P, 0, nullptr));
+    const int re = row_end < 0 ? P : row_end;
+    if (row_begin < 0 || re > P || row_begin > re)
+        return set_error(GSLIC_ERR_INVALID_ARG, "gslic_gradient_stats_accumulate: row range [%d, %d) of %d Gaussians", row_begin, re, P);
+    if (re == row_begin) return GSLIC_OK;
+    if (!dL_dmean2D || !radii) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_gradient_stats_accumulate: dL_dmean2D / radii is NULL");
+    const GradStatArgs gs{stats->grad_sum, stats->n_seen, stats->max_radius};
+    return launch_gradient_stats(row_begin, re, dL_dmean2D, radii, gs, (hipStream_t)stream);
 }
 
 int gslic_rasterize_backward_camera(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,

@@ -120,7 +120,17 @@ struct PreprocessBwdArgs {
     float* cam_out;       // [35] = dL_dviewmatrix[16] | dL_dprojmatrix[16] | dL_dcampos[3]
     const float* partials_z;  // optional [R] (depth backward): dL/dz per instance, gathered like `partials`; dL_dmean3D += sum * (V[2], V[6], V[10])
 };
-int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s);
+// The three per-row accumulators of the gradient densification statistics (gslic_grad_stats, include/gslic_hip.h): storage row order, caller-owned.
+struct GradStatArgs {
+    float* grad_sum;       // [P] sum over views of |dL/dmean2D| (finite norms only)
+    uint32_t* n_seen;      // [P] views that added a finite norm
+    int32_t* max_radius;   // [P] largest screen radius seen
+};
+// gs != NULL (fused Adam only, no camera gradient): the *_gstat_kernel instantiations, which also apply the statistics rule to every visible row
+int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s, const GradStatArgs* gs = nullptr);
+int launch_preprocess_bwd_gstat(const PreprocessBwdArgs& a, const GradStatArgs& gs, bool lds_sh, bool defer, hipStream_t s);   // preprocess_bwd_gstat.hip
+// the same rule on a dL_dmean2D [P,3] the caller already has, rows [row_begin, row_end): one thread per row
+int launch_gradient_stats(int row_begin, int row_end, const float* dL_dmean2D, const int32_t* radii, const GradStatArgs& gs, hipStream_t s);
 
 // dL_ddc [P,3] and dL_dsh [P,M,3] summed over n_views views from the views' masked colour gradients (rgb_all [n_views][P][3], or the
 // views' dL_ddc when input_is_ddc) and camera centres (campos_all [n_views][3]): the SH backward (backward.cu:27-136) is the outer

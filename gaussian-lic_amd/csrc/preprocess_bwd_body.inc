@@ -1,5 +1,6 @@
 // preprocess_bwd_body.inc — the body of preprocess_bwd_kernel / preprocess_bwd_defer_xyz_kernel (preprocess_bwd.hip), included inside each kernel
-// with LDS_SH, BS, CAM and DEFER_XYZ in scope.  DEFER_XYZ: the fused Adam update skips group 0 (xyz), whose chain gradient goes to dL_dmean3D.
+// with LDS_SH, BS, CAM, DEFER_XYZ and GSTAT (+ the GradStatArgs gs) in scope.  DEFER_XYZ: the fused Adam update skips group 0 (xyz), whose chain
+// gradient goes to dL_dmean3D.  GSTAT: the gradient densification statistics are accumulated into gs (grad_stat_update); false: gs is never read.
     __shared__ __attribute__((aligned(16))) float lds_tab[LDS_SH ? BS * SHT : 4];   // {c_0..c_14, dRGB} per Gaussian; later the 14 small gradients
     __shared__ float lds_sk[LDS_SH ? BS * 15 : 4];                                    // q_k per Gaussian
     __shared__ uint8_t lds_vis[BS];
@@ -28,6 +29,9 @@
     PartialSums ps;
     bool visible = false;
     if (idx < a.row_end) visible = bwd_gather(a, idx, LDS_SH, ps);
+    if constexpr (GSTAT) {   // the densification statistics of this row, from the two sums dL_dmean2D would hold (rows of a failed forward never get here)
+        if (visible) grad_stat_update(gs, idx, ps.mx, ps.my, a.radii[idx]);
+    }
     lds_vis[threadIdx.x] = visible ? 1 : 0;
     if (a.vis_out && idx < a.row_end) a.vis_out[idx] = visible ? 1 : 0;                                            // the exchange payload's mask ...
     if (a.campos_out && blockIdx.x == 0 && threadIdx.x < 3) a.campos_out[threadIdx.x] = a.campos[threadIdx.x];     // ... and camera centre

@@ -37,6 +37,7 @@ class GaussianRasterizationSettings:
     no_color: bool = False
     lambda_erank: float = 0.0
     tie_rank: torch.Tensor = None   # not in the reference: int32 [P], set by render() for a model that keeps its rows in a permuted order (_params)
+    mean2d_grad_out: torch.Tensor = None   # not in the reference: float32 [P,3] the raw nodes' backward writes dL_dmeans2D into (render(mean2d_grad_out=))
 
 
 def _params(P, D, M, H, W, tanfovx, tanfovy, lxn, lxp, lyn, lyp, scale_modifier, prefiltered, debug, no_color, raw=False, tie_rank=None):
@@ -198,9 +199,13 @@ def rasterize_gaussians_depth_capacity(bufs, background, means3D, opacity, scale
 
 def _backward(view, degree, debug, raw_params, background, means3D, radii, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
               dL_dout_color, dL_dout_depth, dc, sh, geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank, out=None, adam=None,
-              camera_grads=False, rgb_out=None, rows=None, skip_blend=False, out_addr=None, payload=None, xyz_grad=None):
+              camera_grads=False, rgb_out=None, rows=None, skip_blend=False, out_addr=None, payload=None, xyz_grad=None, grad_stats=None,
+              mean2d_out=None):
     """The one backward behind the two public ones (see there for the modes).  dL_dout_depth: None = the colour-only entry points, a tensor =
-    their depth twins.  view as _forward's."""
+    their depth twins.  view as _forward's.  grad_stats (a _lib.GradStats, with adam only): the *_adam_stats entry points; mean2d_out
+    (float32 [P,3], with out and no adam / rgb_out): dL_dmeans2D is written there instead of not being materialised."""
+    if grad_stats is not None and adam is None:
+        raise ValueError("grad_stats goes with adam (the fused backward); the other backwards give dL_dmeans2D to gradient_stats_accumulate")
     L = _lib.lib()
     dev, P, M = means3D.device, means3D.size(0), _sh_width(sh)
     depth = dL_dout_depth is not None
@@ -215,6 +220,9 @@ def _backward(view, degree, debug, raw_params, background, means3D, radii, color
         dL_dmeans3D, dL_ddc, dL_dsh = out["xyz"], out["features_dc"], out["features_rest"]
         dL_dopacities, dL_dscales, dL_drotations = out["opacity"], out["scaling"], out["rotation"]
         dL_dmeans2D = dL_dcolors = dL_dconic = dL_dcov3D = None
+        if mean2d_out is not None:
+            assert mean2d_out.is_contiguous() and mean2d_out.dtype == torch.float32 and mean2d_out.numel() >= 3 * P
+            dL_dmeans2D = mean2d_out
     elif full:
         mk = (lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)) if P != 0 else \
             (lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev))
@@ -240,6 +248,9 @@ def _backward(view, degree, debug, raw_params, background, means3D, radii, color
             # single-GPU fast path: Adam applied inside the backward kernel, no gradient tensors at all (but xyz's under depth supervision)
             fn = L.gslic_rasterize_backward_depth_adam if depth else L.gslic_rasterize_backward_adam
             tail = (None, p(xyz_grad) if depth else None, None, None, None, None, erank, ctypes.byref(adam))
+            if grad_stats is not None:   # the same call plus the statistics descriptor
+                fn = L.gslic_rasterize_backward_depth_adam_stats if depth else L.gslic_rasterize_backward_adam_stats
+                tail += (ctypes.byref(grad_stats),)
         elif rgb_out is not None and rows is not None:
             # chunked (gslic_rasterize_backward_rgb_rows): Gaussians [rows[0], rows[1]) only; the kernels index the gradient pointers by the
             # ABSOLUTE Gaussian index, so a caller that keeps its chunks in separate blocks passes `out_addr` = {name: address of row 0}
@@ -276,7 +287,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  projmatrix, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, dL_dout_color, dc, sh,
                                  degree, campos, geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank, debug,
                                  raw_params=False, out=None, adam=None, camera_grads=False, rgb_out=None, rows=None, skip_blend=False,
-                                 out_addr=None, payload=None):
+                                 out_addr=None, payload=None, grad_stats=None, mean2d_out=None):
     """RasterizeGaussiansBackwardCUDA (rasterize_points.cu:151-246): returns (dL_dmeans2D, dL_dcolors_precomp,
     dL_dopacities, dL_dmeans3D, dL_dcov3Ds_precomp, dL_ddc, dL_dsh, dL_dscales, dL_drotations).
     raw_params=True: scales / rotations are raw and dL_dopacities / dL_dscales / dL_drotations are w.r.t. the raw parameters.
@@ -285,17 +296,19 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     adam (a gslic_adam_fused descriptor, raw_params implied): gslic_rasterize_backward_adam, the Adam update inside the backward; returns None.
     rgb_out [P,3] (with out; returns None): gslic_rasterize_backward_rgb_payload, or with rows=(p0, p1) gslic_rasterize_backward_rgb_rows.
     camera_grads=True (gslic_rasterize_backward_camera; no reference counterpart): three more tensors are appended —
-    dL_dviewmatrix [16], dL_dprojmatrix [16], dL_dcampos [3], element order of the inputs."""
+    dL_dviewmatrix [16], dL_dprojmatrix [16], dL_dcampos [3], element order of the inputs.
+    grad_stats (a _lib.GradStats, with adam): gslic_rasterize_backward_adam_stats.  mean2d_out [P,3] (with out): dL_dmeans2D is written there."""
     view = (dL_dout_color.size(1), dL_dout_color.size(2), tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier)
     return _backward(view, degree, debug, raw_params, background, means3D, radii, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
                      campos, dL_dout_color, None, dc, sh, geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank, out=out, adam=adam,
-                     camera_grads=camera_grads, rgb_out=rgb_out, rows=rows, skip_blend=skip_blend, out_addr=out_addr, payload=payload)
+                     camera_grads=camera_grads, rgb_out=rgb_out, rows=rows, skip_blend=skip_blend, out_addr=out_addr, payload=payload,
+                     grad_stats=grad_stats, mean2d_out=mean2d_out)
 
 
 def rasterize_gaussians_backward_depth(background, means3D, radii, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx,
                                        tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, dL_dout_color, dL_dout_depth, dc, sh, degree, campos,
                                        geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank=0.0, debug=False, raw_params=False,
-                                       out=None, adam=None, xyz_grad=None, camera_grads=False):
+                                       out=None, adam=None, xyz_grad=None, camera_grads=False, grad_stats=None, mean2d_out=None):
     """gslic_rasterize_backward_depth: rasterize_gaussians_backward with dL/d(out_depth) [H,W] as a second input, on the buffers of
     rasterize_gaussians_depth (or rasterize_gaussians_depth_capacity: pass its cap_R / cap_B as R / B).  Returns the same nine tensors
     (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscales, dL_drotations); dL_dout_depth = 0 gives
@@ -306,13 +319,14 @@ def rasterize_gaussians_backward_depth(background, means3D, radii, scales, rotat
     bit-identical to this backward followed by the masked Adam step; returns None.  xyz_grad [P,3]: where the xyz gradient is assembled before
     its update (allocated when None; a graph-captured step passes a buffer of its own).
     camera_grads=True (gslic_rasterize_backward_depth_camera): three more tensors are appended — dL_dviewmatrix [16], dL_dprojmatrix [16],
-    dL_dcampos [3] of the colour AND depth loss, as rasterize_gaussians_backward(camera_grads=True) does; not with adam."""
+    dL_dcampos [3] of the colour AND depth loss, as rasterize_gaussians_backward(camera_grads=True) does; not with adam.
+    grad_stats (with adam): gslic_rasterize_backward_depth_adam_stats.  mean2d_out [P,3] (with out): dL_dmeans2D is written there."""
     if adam is not None and camera_grads:
         raise ValueError("rasterize_gaussians_backward_depth: camera_grads with the fused Adam backward is not available")
     view = (dL_dout_color.size(1), dL_dout_color.size(2), tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier)
     return _backward(view, degree, debug, raw_params, background, means3D, radii, None, scales, rotations, None, viewmatrix, projmatrix, campos,
                      dL_dout_color, dL_dout_depth, dc, sh, geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank, out=out, adam=adam,
-                     camera_grads=camera_grads, xyz_grad=xyz_grad)
+                     camera_grads=camera_grads, xyz_grad=xyz_grad, grad_stats=grad_stats, mean2d_out=mean2d_out)
 
 
 def _depth_grads(ctx, dL_dcolor, dL_ddepth, xyz, dc, sh, opacity, scaling, rotation, radii, geom, binning, img, sample, raw):
@@ -368,6 +382,8 @@ class RawGaussianRasterizerDepthFunction(torch.autograd.Function):
         xyz, dc, sh, opacity_raw, scaling_raw, rotation_raw, radii, geom, binning, img, sample = ctx.saved_tensors
         g = _depth_grads(ctx, dL_dcolor, dL_ddepth, xyz, dc, sh, opacity_raw, scaling_raw, rotation_raw, radii, geom, binning, img, sample, True)
         (_m2, _c, dL_dopacity, dL_dxyz, _cov, dL_ddc, dL_dsh, dL_dscaling, dL_drotation) = g
+        if ctx.rs.mean2d_grad_out is not None:
+            ctx.rs.mean2d_grad_out.copy_(_m2)
         return (dL_dxyz, dL_ddc.view_as(dc), dL_dsh.view_as(sh), dL_dopacity.view_as(opacity_raw), dL_dscaling, dL_drotation, None)
 
 
@@ -440,7 +456,7 @@ class RawGaussianRasterizerFunction(torch.autograd.Function):
                    scaling=torch.empty_like(scaling_raw), rotation=torch.empty_like(rotation_raw))   # (every row is written by the kernel)
         rasterize_gaussians_backward(rs.bg, xyz, radii, e, scaling_raw, rotation_raw, rs.scale_modifier, e, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
                                      rs.tanfovy, rs.limx_neg, rs.limx_pos, rs.limy_neg, rs.limy_pos, dL_dcolor, dc, sh, rs.sh_degree, rs.campos, geom, ctx.R,
-                                     binning, img, ctx.B, sample, rs.lambda_erank, False, raw_params=True, out=out)
+                                     binning, img, ctx.B, sample, rs.lambda_erank, False, raw_params=True, out=out, mean2d_out=rs.mean2d_grad_out)
         return out["xyz"], out["features_dc"], out["features_rest"], out["opacity"], out["scaling"], out["rotation"], None
 
 
@@ -457,7 +473,7 @@ def _raw_leaves(model):
     return None
 
 
-def render(camera, model, bg_color, no_color=False, scaling_modifier=1.0, raw=None, return_depth=False):
+def render(camera, model, bg_color, no_color=False, scaling_modifier=1.0, raw=None, return_depth=False, mean2d_grad_out=None):
     """renderer.cpp:21-88 — same signature, same five results (image, final_T, screenspace_points, visible, radii).  `camera` =
     gaussian_lic_amd.camera.Camera with device tensors attached via to_device(); `model` exposes get_xyz / get_opacity / get_scaling /
     get_rotation / get_features_dc / get_features_rest, sh_degree, lambda_erank.
@@ -471,7 +487,10 @@ def render(camera, model, bg_color, no_color=False, scaling_modifier=1.0, raw=No
     return_depth=True (not in the reference; LiDAR depth supervision): a sixth result, depth [H,W] = sum T alpha z over exactly the
     contributors of the pixel's colour (z = view-space depth of the Gaussian), differentiable on the raw and the activated path.  It is
     NOT normalised: the background contributes 0, and depth / (1 - final_T) is the expected depth of the covered part.  The five other
-    results are bit-identical to return_depth=False's.  Needs the colour (no_color=False)."""
+    results are bit-identical to return_depth=False's.  Needs the colour (no_color=False).
+
+    mean2d_grad_out (not in the reference; float32 [P,3] on the device): on the raw path, whose screenspace_points carries no gradient, the backward
+    writes dL_dmeans2D there (what screenspace_points.grad holds on the raw=False path) — the input of the gradient densification statistics."""
     import os
     leaves = _raw_leaves(model)
     if raw is None:
@@ -480,7 +499,7 @@ def render(camera, model, bg_color, no_color=False, scaling_modifier=1.0, raw=No
         camera.image_height, camera.image_width, float(camera.tanfovx), float(camera.tanfovy), float(camera.limx_neg),
         float(camera.limx_pos), float(camera.limy_neg), float(camera.limy_pos), bg_color, scaling_modifier,
         camera.d_world_view_transform, camera.d_full_proj_transform, model.sh_degree, camera.d_camera_center, False, False,
-        no_color, model.lambda_erank, getattr(model, "tie_rank", None))
+        no_color, model.lambda_erank, getattr(model, "tie_rank", None), mean2d_grad_out)
     if raw and leaves is None:
         raise TypeError("render(raw=True): the model does not expose its raw parameter leaves (set raw_parameter_leaves = True on a model whose "
                         "xyz / features_dc / features_rest / opacity / scaling / rotation attributes are the PRE-activation tensors, or provide raw_leaves())")
@@ -520,6 +539,28 @@ def sh_grad_from_rgb(means3D, campos_all, rgb_all, degree, dL_ddc, dL_dsh, input
     p = _lib.ptr
     _lib.check(_lib.lib().gslic_sh_grad_from_rgb(P, int(degree), M, n, p(_f32c(means3D)), p(campos_all), p(rgb_all), int(bool(input_is_ddc)), p(dL_ddc),
                                                  p(dL_dsh) if M else None, int(view_stride), _lib.current_stream_ptr()))
+
+
+def grad_stats_descriptor(grad_sum, n_seen, max_radius, P):
+    """The _lib.GradStats (gslic_grad_stats) of three device accumulators of at least P rows: float32, int32 (uint32 bits), int32."""
+    for t, dt in ((grad_sum, torch.float32), (n_seen, torch.int32), (max_radius, torch.int32)):
+        if not (torch.is_tensor(t) and t.is_contiguous() and t.dtype == dt and t.numel() >= int(P)):
+            raise ValueError(f"gradient statistics: an accumulator must be a contiguous {dt} tensor of at least {int(P)} rows")
+    return _lib.GradStats(grad_sum.data_ptr(), n_seen.data_ptr(), max_radius.data_ptr())
+
+
+def gradient_stats_accumulate(dL_dmean2D, radii, grad_sum, n_seen, max_radius, rows=None):
+    """gslic_gradient_stats_accumulate: applies the rule of the gradient densification statistics (include/gslic_hip.h) to a dL_dmeans2D [P,3] and
+    radii [P] the caller already has — rows [rows[0], rows[1]) or all — adding into grad_sum float32 / n_seen int32 / max_radius int32 [>= P].
+    One launch on the current stream, no synchronisation; bit-identical to the fused backward's own accumulation on the same gradient."""
+    P = int(radii.shape[0])
+    if not (dL_dmean2D.is_contiguous() and dL_dmean2D.dtype == torch.float32 and dL_dmean2D.numel() >= 3 * P):
+        raise ValueError(f"gradient_stats_accumulate: dL_dmean2D must be a contiguous float32 tensor of at least {P} rows of 3")
+    if not (radii.is_contiguous() and radii.dtype == torch.int32):
+        raise ValueError("gradient_stats_accumulate: radii must be a contiguous int32 tensor")
+    gs = grad_stats_descriptor(grad_sum, n_seen, max_radius, P)
+    r0, r1 = (0, -1) if rows is None else (int(rows[0]), int(rows[1]))
+    _lib.check(_lib.lib().gslic_gradient_stats_accumulate(P, _lib.ptr(dL_dmean2D), _lib.ptr(radii), ctypes.byref(gs), r0, r1, _lib.current_stream_ptr()))
 
 
 def contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, max_w=None, n_pix=None, sum_w=None, error=None, err_sum=None):

@@ -106,6 +106,7 @@ CHECK_FUSED_CONTRIBUTION = os.path.join(PKG, "fused_contribution_check")
 CHECK_FUSED_DENSIFY = os.path.join(PKG, "fused_densify_check")
 CHECK_FUSED_WEIGHTED = os.path.join(PKG, "fused_weighted_check")
 CHECK_FUSED_RESORT = os.path.join(PKG, "fused_resort_check")
+CHECK_FUSED_GRADIENT_STATS = os.path.join(PKG, "fused_gradient_stats_check")
 
 
 def build_fused_check(force=False):
@@ -155,6 +156,12 @@ def build_fused_resort_check(force=False):
     return _build_fused_program(os.path.join(HERE, "fused_resort_check.cpp"), CHECK_FUSED_RESORT, force)
 
 
+def build_fused_gradient_stats_check(force=False):
+    """fused_gradient_stats_check: the gradient densification statistics from C++ (gslic::GradientStats, gslic::FusedStep::set_gradient_stats,
+    carried through densify, prune and resort between fused steps) — built like fused_check."""
+    return _build_fused_program(os.path.join(HERE, "fused_gradient_stats_check.cpp"), CHECK_FUSED_GRADIENT_STATS, force)
+
+
 def _build_fused_program(src, CHECK_FUSED, force):
     import sysconfig
     import torch
@@ -193,3 +200,4 @@ if __name__ == "__main__":
     print(build_fused_densify_check(force="--force" in sys.argv))
     print(build_fused_weighted_check(force="--force" in sys.argv))
     print(build_fused_resort_check(force="--force" in sys.argv))
+    print(build_fused_gradient_stats_check(force="--force" in sys.argv))

@@ -54,6 +54,29 @@ struct ContributionStats {
     int64_t views = 0;
 };
 
+// The gradient densification statistics of 3DGS accumulated over views (gslic_grad_stats, include/gslic_hip.h) — the Python host's
+// trainer.GradientStats as plain data: per storage row the sum of the norms of dL/dmean2D (xyz_gradient_accum), the number of views that added one
+// (denom) and the largest screen radius (max_radii2D).  Handed to FusedStep::set_gradient_stats, every step() adds its view inside the backward
+// kernel, and prune / extend / densify / resort carry the arrays with the rows (created zero-filled, grown to the map's capacity; rows behind
+// size() are zero).  When to densify or reset, and with which thresholds, is the host's policy.
+struct GradientStats {
+    torch::Tensor grad_sum;     // float32 [capacity]
+    torch::Tensor n_seen;       // int32 [capacity]: uint32 count
+    torch::Tensor max_radius;   // int32 [capacity]
+    bool defined() const { return grad_sum.defined(); }
+    void reset() { if (defined()) { grad_sum.zero_(); n_seen.zero_(); max_radius.zero_(); } }
+    // bool [P] for FusedStep::densify: n_seen >= max(min_seen, 1) and grad_sum >= float(grad_above) * float(n_seen) — comparisons and one float32
+    // product, the Python host's grow_mask (3DGS's >= is kept; a NaN sum does not grow)
+    torch::Tensor grow_mask(int64_t P, float grad_above, int64_t min_seen = 1) const
+    {
+        const torch::Tensor n = n_seen.narrow(0, 0, P).to(torch::kInt64).bitwise_and(0xffffffffLL);
+        const torch::Tensor lim = torch::full({}, grad_above, grad_sum.options()) * n.to(torch::kFloat32);
+        return n.ge(std::max<int64_t>(min_seen, 1)).logical_and(grad_sum.narrow(0, 0, P).ge(lim));
+    }
+    // bool [P] for FusedStep::prune(drop): max_radius > max_screen_radius (3DGS's screen-size prune)
+    torch::Tensor big_mask(int64_t P, int32_t max_screen_radius) const { return max_radius.narrow(0, 0, P).gt(max_screen_radius); }
+};
+
 class FusedStep {
 public:
     // params: the six raw leaf tensors in the group order of trainingSetup (gaussian.cpp:399-418); updated IN PLACE.
@@ -86,6 +109,14 @@ public:
         prm_ = std::move(params); m_ = std::move(exp_avg); v_ = std::move(exp_avg_sq);
     }
     void set_lr(int group, float lr) { lrs_[group] = lr; }
+    // From here on every step() adds its view to *stats (gslic_rasterize_backward_adam_stats / _depth_adam_stats: the same step, bit-identical
+    // parameters and moments) and prune() / extend() / densify() / resort() carry its arrays with the rows, beside the contribution statistics:
+    // gathered, zero for new rows and split parents, permuted.  The object must outlive the step or be taken off with nullptr.
+    void set_gradient_stats(GradientStats* stats)
+    {
+        gstats_ = stats;
+        if (gstats_) fit_gradient_stats(capacity());
+    }
     // A host that keeps the map's rows in a PERMUTED order (e.g. sorted along a space-filling curve so that what a view sees is contiguous in
     // memory) passes the rows' ORIGINAL indices (device int32 [P]): the forward then lists Gaussians of equal depth in the original order, as the
     // reference's stable sort does (gslic_raster_params.tie_rank), and the map renders / trains bit-identically to the unpermuted one.
@@ -134,6 +165,10 @@ public:
             fit_stats(*stats, capacity(), false);
             add(stats->max_w, 1u); add(stats->n_pix, 1u); add(stats->sum_w, 2u);
             if (stats->err_sum.defined()) add(stats->err_sum, 2u);
+        }
+        if (gstats_) {
+            fit_gradient_stats(capacity());
+            add(gstats_->grad_sum, 1u); add(gstats_->n_seen, 1u); add(gstats_->max_radius, 1u);
         }
         const size_t bytes = gslic_permute_rows_staging_bytes(rows.data(), (int32_t)rows.size(), (int32_t)P);
         torch::Tensor staging = torch::empty({(int64_t)bytes}, io.dtype(torch::kByte));
@@ -199,6 +234,10 @@ public:
         }
         if (tie_.defined()) tie_ = torch::cat({tie_, torch::arange(P, P + count, tie_.options())});
         bind(P + count);
+        if (gstats_) {   // appended rows have been seen by no view yet
+            fit_gradient_stats(capacity());
+            for (torch::Tensor* t : {&gstats_->grad_sum, &gstats_->n_seen, &gstats_->max_radius}) t->narrow(0, P, count).zero_();
+        }
         torch::cuda::synchronize();   // (the selection scratch is released on return)
         rows_appended(stats);
         return count;
@@ -269,6 +308,18 @@ public:
                 if (old.err_sum.defined()) sr.push_back({old.err_sum.data_ptr(), stats->err_sum.data_ptr(), 2u});
                 check(gslic_gather_rows(sr.data(), (int32_t)sr.size(), reinterpret_cast<const uint32_t*>(kept.data_ptr<int32_t>()), count, current_stream()),
                       "gslic_gather_rows (statistics)");
+            }
+        }
+        if (gstats_ && gstats_->defined()) {   // the gradient statistics follow their rows: the same gather, on the same kept index
+            GradientStats old = *gstats_;
+            TORCH_CHECK(old.grad_sum.size(0) >= P && old.n_seen.size(0) >= P && old.max_radius.size(0) >= P,
+                        "FusedStep::prune: the gradient statistics hold fewer rows than the map");
+            gstats_->grad_sum = torch::zeros({cap}, io.dtype(torch::kFloat32)); gstats_->n_seen = torch::zeros({cap}, io); gstats_->max_radius = torch::zeros({cap}, io);
+            if (count > 0) {
+                std::vector<gslic_row_array> sr = {{old.grad_sum.data_ptr(), gstats_->grad_sum.data_ptr(), 1u}, {old.n_seen.data_ptr(), gstats_->n_seen.data_ptr(), 1u},
+                                                   {old.max_radius.data_ptr(), gstats_->max_radius.data_ptr(), 1u}};
+                check(gslic_gather_rows(sr.data(), (int32_t)sr.size(), reinterpret_cast<const uint32_t*>(kept.data_ptr<int32_t>()), count, current_stream()),
+                      "gslic_gather_rows (gradient statistics)");
             }
         }
         if (tie_.defined()) tie_ = new_tie.narrow(0, 0, count).clone();
@@ -353,7 +404,7 @@ public:
         if (count == 0) return torch::empty({0}, io.dtype(torch::kInt64));
         const torch::Tensor parents = parent.narrow(0, 0, count).to(torch::kInt64);
         torch::Tensor split_rows;   // which parents split, from the scaling the emission has not yet rewritten (the rule's own comparison)
-        if (stats && stats->max_w.defined() && splits > 0) split_rows = parents.masked_select(prm_[4].detach().index_select(0, parents).gt(thr).any(1));
+        if (((stats && stats->max_w.defined()) || gstats_) && splits > 0) split_rows = parents.masked_select(prm_[4].detach().index_select(0, parents).gt(thr).any(1));
         reserve(P + count);
         if (tie_.defined()) {
             torch::Tensor nt = torch::empty({P + count}, tie_.options());
@@ -374,6 +425,13 @@ public:
             fit_stats(*stats, capacity(), false);
             for (torch::Tensor* t : {&stats->max_w, &stats->n_pix, &stats->sum_w, &stats->err_sum}) {
                 if (!t->defined()) continue;
+                t->narrow(0, P, count).zero_();
+                if (split_rows.defined()) t->index_fill_(0, split_rows, 0);
+            }
+        }
+        if (gstats_) {   // new rows and child 0 of a split have been seen by no view yet; a clone's parent is the Gaussian it was
+            fit_gradient_stats(capacity());
+            for (torch::Tensor* t : {&gstats_->grad_sum, &gstats_->n_seen, &gstats_->max_radius}) {
                 t->narrow(0, P, count).zero_();
                 if (split_rows.defined()) t->index_fill_(0, split_rows, 0);
             }
@@ -564,6 +622,23 @@ private:
                                                        terms.data_ptr<float>() + 2, dL_ddepth_.data_ptr<float>(), current_stream()),
                   "gslic_depth_l1_loss_forward_backward");
         const gslic_adam_fused ad = adam_descriptor();
+        if (gstats_) {   // the same backward, which also adds this view to the gradient statistics
+            fit_gradient_stats(capacity());
+            const gslic_grad_stats gs{gstats_->grad_sum.data_ptr<float>(), reinterpret_cast<uint32_t*>(gstats_->n_seen.data_ptr<int32_t>()),
+                                      gstats_->max_radius.data_ptr<int32_t>()};
+            if (depth)
+                check(gslic_rasterize_backward_depth_adam_stats(&rp, R, B, f(bg_), xyz, dc, rest, nullptr, sc, rot, nullptr, view, proj, cpos,
+                                                                radii_.data_ptr<int32_t>(), cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), cptr(scratch_[3]),
+                                                                f(dL_dimage_), f(dL_ddepth_), nullptr, xyz_grad_.data_ptr<float>(), nullptr, nullptr, nullptr, nullptr,
+                                                                lambda_erank_, &ad, &gs, current_stream()),
+                      "gslic_rasterize_backward_depth_adam_stats");
+            else
+                check(gslic_rasterize_backward_adam_stats(&rp, R, B, f(bg_), xyz, dc, rest, nullptr, sc, rot, nullptr, view, proj, cpos, radii_.data_ptr<int32_t>(),
+                                                          cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), cptr(scratch_[3]), f(dL_dimage_), nullptr, nullptr,
+                                                          nullptr, nullptr, nullptr, nullptr, lambda_erank_, &ad, &gs, current_stream()),
+                      "gslic_rasterize_backward_adam_stats");
+            return terms;
+        }
         if (depth)
             check(gslic_rasterize_backward_depth_adam(&rp, R, B, f(bg_), xyz, dc, rest, nullptr, sc, rot, nullptr, view, proj, cpos, radii_.data_ptr<int32_t>(),
                                                       cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), cptr(scratch_[3]), f(dL_dimage_), f(dL_ddepth_),
@@ -666,6 +741,18 @@ private:
         fit(stats.max_w, torch::kInt32); fit(stats.n_pix, torch::kInt32); fit(stats.sum_w, torch::kInt64);
         if (with_err || stats.err_sum.defined()) fit(stats.err_sum, torch::kInt64);
     }
+    // the gradient statistics' arrays, created zero-filled and grown (zero-extended) to `cap` rows
+    void fit_gradient_stats(int64_t cap)
+    {
+        auto io = prm_[0].options().requires_grad(false).dtype(torch::kInt32);
+        auto fit = [&](torch::Tensor& t, torch::ScalarType dt) {
+            if (t.defined() && t.size(0) >= cap) return;
+            torch::Tensor n = torch::zeros({cap}, io.dtype(dt));
+            if (t.defined()) n.narrow(0, 0, t.size(0)).copy_(t);
+            t = n;
+        };
+        fit(gstats_->grad_sum, torch::kFloat32); fit(gstats_->n_seen, torch::kInt32); fit(gstats_->max_radius, torch::kInt32);
+    }
     // capacity storage: created by the first extend(); until then the tensors handed to the constructor are used in place
     void reserve(int64_t newP)
     {
@@ -733,6 +820,7 @@ private:
     std::optional<double> resort_fraction_;                         // the re-sort rule (off by default)
     int64_t sorted_P_ = 0, n_resorts_ = 0;                          // rows [0, sorted_P_) are in Morton order; resort() calls so far
     torch::Tensor last_perm_;                                       // the last resort()'s permutation
+    GradientStats* gstats_ = nullptr;                               // set_gradient_stats: accumulated by step(), carried by the row changes
 };
 
 }  // namespace gslic

@@ -540,39 +540,18 @@ def contribution_grow_mask(err_fixed, n_pix, error_above, min_pixels=None):
     return grow.to(torch.uint8)
 
 
-class ContributionStats:
-    """Per-Gaussian contribution statistics accumulated over views (gslic_contribution_accumulate, include/gslic_hip.h): for every storage row
-    the largest blend weight w = alpha T it reached in a pixel, the number of (pixel, view) pairs where w >= w_min, and the sum of w — what a
-    mapper decides by whether a Gaussian ever contributes, which raw opacity and scale do not say.  When to accumulate, over which keyframes
-    and with which limits to prune is the host's policy (DESIGN.md section 8).
-
-    The object owns three device arrays sized to the model's capacity, zero-filled, and ATTACHES itself to the model (a weak reference):
-    model.prune() gathers them with the map, model.extend() gives appended rows zeros, model.resort() permutes them.  detach() ends that; a
-    detached object raises from every accessor once the model's rows have changed instead of indexing the wrong rows."""
-
-    W_MIN = 0.05   # default of accumulate(): a pair counts into pixels() when the Gaussian supplies at least 5 % of the pixel
+class _RowStatistics:
+    """What GaussianModel's row changes walk on an attached per-row statistics object (a weak reference in model._stats): _gather (prune), _appended
+    (extend / densify), _zero_rows (densify's split parents), _permute (resort), on the arrays a subclass lists in _arrays() and creates, zero-filled
+    and sized to the model's capacity, in _alloc(cap).  detach() ends the carriage; a detached object raises from _check() once the rows have changed."""
 
     def __init__(self, model):
         self.model = model
-        self._err = None             # the error accumulator: allocated by the first accumulate with an error image
         self._alloc(model.capacity)
-        self.views = 0
         self._attached = True
         self._sync()
         import weakref
         model._stats.append(weakref.ref(self))
-
-    def _alloc(self, cap):
-        dev = self.model.device
-        self._max = torch.zeros(cap, dtype=torch.int32, device=dev)    # uint32 [cap]: float bits
-        self._npix = torch.zeros(cap, dtype=torch.int32, device=dev)   # uint32 [cap]
-        self._sum = torch.zeros(cap, dtype=torch.int64, device=dev)    # uint64 [cap]: 32.32 fixed point
-        self._err = torch.zeros(cap, dtype=torch.int64, device=dev) if self._err is not None else None   # uint64 [cap], lazily
-
-    def _arrays(self):
-        """The accumulators that exist, with their row widths in dwords."""
-        a = [(self._max, 1), (self._npix, 1), (self._sum, 2)]
-        return a + ([(self._err, 2)] if self._err is not None else [])
 
     def _sync(self):
         self._seen = (self.model.layout_version, self.model._rows_version, self.model.P)
@@ -580,9 +559,10 @@ class ContributionStats:
     def _check(self):
         now = (self.model.layout_version, self.model._rows_version, self.model.P)
         if now != self._seen:
-            raise RuntimeError(f"ContributionStats: the model's rows changed since these statistics were taken (layout_version / row changes / P "
+            name = type(self).__name__
+            raise RuntimeError(f"{name}: the model's rows changed since these statistics were taken (layout_version / row changes / P "
                                f"{self._seen} -> {now}: prune(), extend() or resort()) and this object was detached, so it was not carried along — "
-                               "its rows no longer are the model's; build a new ContributionStats")
+                               f"its rows no longer are the model's; build a new {name}")
 
     def detach(self):
         """The model stops carrying this object through prune() / extend() / resort(); it stays readable until the rows change."""
@@ -598,7 +578,7 @@ class ContributionStats:
         self._sync()
 
     def _appended(self, P0, k):
-        if self._max.shape[0] < self.model.capacity:
+        if self._arrays()[0][0].shape[0] < self.model.capacity:
             old = self._arrays()
             self._alloc(self.model.capacity)
             for (o, _w), (n, _w2) in zip(old, self._arrays()):
@@ -623,6 +603,36 @@ class ContributionStats:
             for a, _w in self._arrays():
                 a[:P] = a[:P][perm]
         self._sync()
+
+
+class ContributionStats(_RowStatistics):
+    """Per-Gaussian contribution statistics accumulated over views (gslic_contribution_accumulate, include/gslic_hip.h): for every storage row
+    the largest blend weight w = alpha T it reached in a pixel, the number of (pixel, view) pairs where w >= w_min, and the sum of w — what a
+    mapper decides by whether a Gaussian ever contributes, which raw opacity and scale do not say.  When to accumulate, over which keyframes
+    and with which limits to prune is the host's policy (DESIGN.md section 8).
+
+    The object owns three device arrays sized to the model's capacity, zero-filled, and ATTACHES itself to the model (a weak reference):
+    model.prune() gathers them with the map, model.extend() gives appended rows zeros, model.resort() permutes them.  detach() ends that; a
+    detached object raises from every accessor once the model's rows have changed instead of indexing the wrong rows."""
+
+    W_MIN = 0.05   # default of accumulate(): a pair counts into pixels() when the Gaussian supplies at least 5 % of the pixel
+
+    def __init__(self, model):
+        self._err = None             # the error accumulator: allocated by the first accumulate with an error image
+        self.views = 0
+        super().__init__(model)
+
+    def _alloc(self, cap):
+        dev = self.model.device
+        self._max = torch.zeros(cap, dtype=torch.int32, device=dev)    # uint32 [cap]: float bits
+        self._npix = torch.zeros(cap, dtype=torch.int32, device=dev)   # uint32 [cap]
+        self._sum = torch.zeros(cap, dtype=torch.int64, device=dev)    # uint64 [cap]: 32.32 fixed point
+        self._err = torch.zeros(cap, dtype=torch.int64, device=dev) if self._err is not None else None   # uint64 [cap], lazily
+
+    def _arrays(self):
+        """The accumulators that exist, with their row widths in dwords."""
+        a = [(self._max, 1), (self._npix, 1), (self._sum, 2)]
+        return a + ([(self._err, 2)] if self._err is not None else [])
 
     # --- accumulation
     @torch.no_grad()
@@ -722,6 +732,113 @@ class ContributionStats:
     def drop_mask(self, max_weight_below=None, pixels_below=None):
         """The uint8 [P] mask model.prune(drop=...) takes: contribution_drop_mask on max_weight() and pixels()."""
         return contribution_drop_mask(self.max_weight(), self.pixels(), max_weight_below, pixels_below)
+
+
+def gradient_grow_mask(grad_sum, n_seen, grad_above, min_seen=1):
+    """uint8 [P]: 1 where n_seen >= max(min_seen, 1) and grad_sum >= float32(grad_above) * float32(n_seen) — the 3DGS test "mean gradient >=
+    threshold" without the division: comparisons and ONE float32 product, so the same expression in torch or numpy gives the same mask.  3DGS's
+    >= is kept.  A NaN in grad_sum (or a NaN threshold) compares false: the row does not grow.  grad_sum float32 [P], n_seen integer [P]."""
+    import numpy as np
+    thr = torch.tensor(float(np.float32(grad_above)), dtype=torch.float32, device=grad_sum.device)
+    n = torch.as_tensor(n_seen).to(grad_sum.device)
+    return ((n >= max(int(min_seen), 1)) & (grad_sum >= thr * n.to(torch.float32))).to(torch.uint8)
+
+
+class GradientStats(_RowStatistics):
+    """The densification statistics of 3DGS accumulated over views, on every training path (the rule: include/gslic_hip.h, gslic_grad_stats): per
+    storage row the sum of the norms of the view-space positional gradient dL/dmean2D (xyz_gradient_accum), the number of views that added one
+    (denom) and the largest screen radius (max_radii2D).  Pass the object as grad_stats= to training_step_fused / training_step /
+    training_step_with_pose / GraphedStep: the fused Adam backward accumulates inside its per-Gaussian kernel (the gradient never leaves it), the
+    other paths hand their dL_dmeans2D to one small kernel.  When to densify or reset, and with which thresholds, is the host's policy.
+
+    Like ContributionStats the object owns its device arrays (sized to the model's capacity, zero-filled) and ATTACHES itself to the model:
+    prune() gathers them, extend() / densify() give new rows and split parents zeros, resort() permutes them; detach() ends that and a detached
+    object raises once the rows have changed.  Single GPU: under N > 1 ranks the steps refuse it (summing across ranks is not done)."""
+
+    def _alloc(self, cap):
+        dev = self.model.device
+        self._sum = torch.zeros(cap, dtype=torch.float32, device=dev)     # float32 [cap]
+        self._seen_n = torch.zeros(cap, dtype=torch.int32, device=dev)    # uint32 [cap]
+        self._maxr = torch.zeros(cap, dtype=torch.int32, device=dev)      # int32 [cap]
+        self._m2d = None                                                  # [P,3] scratch of the paths that materialise dL_dmeans2D
+
+    def _arrays(self):
+        return [(self._sum, 1), (self._seen_n, 1), (self._maxr, 1)]
+
+    def _descriptor(self):
+        """The gslic_grad_stats of the arrays as they are now (what a fused backward takes)."""
+        from . import rasterizer as rz
+        self._check()
+        return rz.grad_stats_descriptor(self._sum, self._seen_n, self._maxr, self.model.P)
+
+    def _mean2d_buffer(self):
+        """float32 [P,3] the unfused paths let their backward write dL_dmeans2D into (kept: no allocation per step)."""
+        P = self.model.P
+        if self._m2d is None or self._m2d.shape[0] != P:
+            self._m2d = torch.empty(P, 3, dtype=torch.float32, device=self.model.device)
+        return self._m2d
+
+    def _addresses(self):
+        return tuple(a.data_ptr() for a, _w in self._arrays())
+
+    @torch.no_grad()
+    def accumulate_from(self, dL_dmean2D, radii, rows=None):
+        """Adds one view from a dL_dmeans2D [P,3] and radii [P] the caller has (screenspace_points.grad of the operator path, the first result of
+        rasterize_gaussians_backward): one gslic_gradient_stats_accumulate on rows [rows[0], rows[1]) or all.  The tensors must be of THIS model's rows."""
+        from . import rasterizer as rz
+        self._check()
+        P = self.model.P
+        if tuple(dL_dmean2D.shape) != (P, 3) or tuple(radii.shape) != (P,):
+            raise ValueError(f"GradientStats: expected dL_dmean2D [{P}, 3] and radii [{P}], got {tuple(dL_dmean2D.shape)} and {tuple(radii.shape)}")
+        if P == 0:
+            return
+        rz.gradient_stats_accumulate(dL_dmean2D.detach().float().contiguous(), radii.to(torch.int32).contiguous(), self._sum, self._seen_n, self._maxr, rows)
+
+    def reset(self):
+        self._check()
+        for a, _w in self._arrays():
+            a.zero_()
+
+    # --- results, [P] in storage row order
+    def grad_sum(self):
+        """float32 [P]: the sum of |dL/dmean2D| over the views that saw the row (3DGS: xyz_gradient_accum)."""
+        self._check()
+        return self._sum[:self.model.P]
+
+    def n_seen(self):
+        """int64 [P]: how many views added a (finite) norm (3DGS: denom)."""
+        self._check()
+        return self._seen_n[:self.model.P].long() & 0xffffffff
+
+    def max_radius(self):
+        """int32 [P]: the largest screen radius of the row in any accumulated view (3DGS: max_radii2D); 0: never visible."""
+        self._check()
+        return self._maxr[:self.model.P]
+
+    def mean_gradient(self):
+        """float32 [P]: grad_sum / n_seen, 0 where the row was never seen."""
+        n = self.n_seen()
+        return torch.where(n > 0, self.grad_sum() / n.clamp_min(1).to(torch.float32), torch.zeros((), dtype=torch.float32, device=n.device))
+
+    def grow_mask(self, grad_above, min_seen=1):
+        """The uint8 [P] mask model.densify(grow=...) takes: gradient_grow_mask on grad_sum() and n_seen()."""
+        return gradient_grow_mask(self.grad_sum(), self.n_seen(), grad_above, min_seen)
+
+    def big_mask(self, max_screen_radius):
+        """The uint8 [P] mask model.prune(drop=...) takes for 3DGS's screen-size prune: max_radius() > max_screen_radius (integer comparison)."""
+        return (self.max_radius() > int(max_screen_radius)).to(torch.uint8)
+
+
+def _grad_stats_for_step(grad_stats, model):
+    """The checks every step makes on its grad_stats= argument (None passes): this model's object, its rows current, one GPU."""
+    if grad_stats is None:
+        return None
+    if not isinstance(grad_stats, GradientStats) or grad_stats.model is not model:
+        raise ValueError("grad_stats must be a GradientStats of the model that is trained")
+    if _dist_on():
+        raise NotImplementedError("grad_stats is single-GPU only: the statistics of the ranks' views are not summed across ranks")
+    grad_stats._check()
+    return grad_stats
 
 
 def exchange_mode():
@@ -1073,7 +1190,7 @@ def allreduce_gradients(grads, visible):
 
 
 def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_step=True, raw_render=None, one_node_loss=False, gt_depth=None,
-                  lambda_depth=0.0, weight=None):
+                  lambda_depth=0.0, weight=None, grad_stats=None):
     """One iteration of optimize()'s loop (gaussian.cpp:674-716) the way the reference's host writes it: render -> 0.8*L1 + 0.2*(1-SSIM) ->
     loss.backward() -> sparse Adam, on LibTorch autograd.  Returns (loss tensor, visible mask).
     raw_render: passed to render() — None = its default (the drop-in renderer: activations inside the kernels), False = renderer.cpp as written
@@ -1083,12 +1200,16 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
     rendered depth (render(return_depth=True)) is supervised too, loss += lambda_depth * depth_l1(depth, gt_depth).  gt_depth=None or
     lambda_depth=0 is exactly the colour-only step (no depth is rendered).
     weight [H,W] (not in the reference; a mask is the 0/1 case, clamped to [0,1]): the colour terms become the weighted means
-    (w |d|).sum() / (3 S) and (FusedSSIMMap w).sum() / (3 S), S = w.sum() (both 0 when S == 0), from the existing operators; None = the plain means."""
+    (w |d|).sum() / (3 S) and (FusedSSIMMap w).sum() / (3 S), S = w.sum() (both 0 when S == 0), from the existing operators; None = the plain means.
+    grad_stats (a GradientStats of this model; single GPU): this view's dL_dmeans2D — screenspace_points.grad, or on the raw path what its backward
+    node writes out — and radii are added to it by one small kernel (GradientStats.accumulate_from); the step itself is unchanged."""
     use_depth = gt_depth is not None and lambda_depth != 0.0
+    grad_stats = _grad_stats_for_step(grad_stats, model)
+    m2d = {} if grad_stats is None else dict(mean2d_grad_out=grad_stats._mean2d_buffer())
     if use_depth:
-        image, _final_T, _pts, visible, _radii, depth = render(camera, model, bg, raw=raw_render, return_depth=True)
+        image, _final_T, _pts, visible, _radii, depth = render(camera, model, bg, raw=raw_render, return_depth=True, **m2d)
     else:
-        image, _final_T, _pts, visible, _radii = render(camera, model, bg, raw=raw_render)
+        image, _final_T, _pts, visible, _radii = render(camera, model, bg, raw=raw_render, **m2d)
     if one_node_loss:
         loss = loss_utils.l1_ssim_loss(image, gt_image, lambda_dssim, weight)
     elif weight is not None:
@@ -1104,6 +1225,8 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
     if use_depth:
         loss = loss + lambda_depth * loss_utils.depth_l1(depth, gt_depth)
     loss.backward()
+    if grad_stats is not None:
+        grad_stats.accumulate_from(_pts.grad if _pts.grad is not None else m2d["mean2d_grad_out"], _radii)
     if do_step:
         params = model.parameters()
         grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
@@ -1133,15 +1256,17 @@ def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, l
     return camera.pose_gradient(out[9], out[10], out[11]), terms
 
 
-def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None):
+def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None, grad_stats=None):
     """One joint map + pose iteration: forward -> loss kernels -> gslic_rasterize_backward_camera (parameter gradients AND the camera gradient in
     one pass) -> masked Adam on the map -> `camera` moved by -pose_lr * dL/dxi (left se(3) increment; 35 floats cross to the host, which is the
     step's only synchronisation).  Returns (terms, visible, dL/dxi).
     gt_depth [H,W] with lambda_depth != 0: the same step under LiDAR depth supervision (depth forward, colour and depth loss kernels,
     gslic_rasterize_backward_depth_camera); the map update equals training_step_fused(gt_depth=...)'s, terms is [mean L1, mean SSIM, L_d].
-    gt_depth=None or lambda_depth=0 is exactly the colour-only step.  weight [H,W]: the weighted colour loss, as training_step_fused's."""
+    gt_depth=None or lambda_depth=0 is exactly the colour-only step.  weight [H,W]: the weighted colour loss, as training_step_fused's.
+    grad_stats (a GradientStats of this model): the backward also writes dL_dmeans2D, which one small kernel adds to the statistics."""
     fl = fused_loss or _default_fused_loss()
     use_depth = gt_depth is not None and lambda_depth != 0.0
+    grad_stats = _grad_stats_for_step(grad_stats, model)
     cam = camera
     with torch.no_grad():
         if use_depth:
@@ -1150,7 +1275,11 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
         image, depth, radii = rr.forward()
         dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight)
         slab = _grad_slab(model)
-        out = rr.backward(dL_dimage, dL_ddepth, out=slab.views, camera_grads=True)
+        if grad_stats is None:
+            out = rr.backward(dL_dimage, dL_ddepth, out=slab.views, camera_grads=True)
+        else:
+            out = rr.backward(dL_dimage, dL_ddepth, out=slab.views, camera_grads=True, mean2d_out=grad_stats._mean2d_buffer())
+            grad_stats.accumulate_from(out[0], radii)
         visible = radii > 0
         model.optimizer.set_visibility_and_N(visible, model.P)
         model.optimizer.step(slab.grads(model))
@@ -1161,7 +1290,7 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
 
 
 def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=True, adam_in_backward=True, gt_depth=None, lambda_depth=0.0,
-                        weight=None):
+                        weight=None, grad_stats=None):
     """The same iteration as training_step — identical arithmetic up to fp32 rounding — on the fused entry points
     (SURVEY.md §8f row 2): sigmoid / exp / normalize and their backward run inside preprocess / preprocess_bwd (raw_params),
     the loss and dL/dimage come from two loss kernels, and there is no autograd graph: 0 LibTorch elementwise launches per step
@@ -1173,9 +1302,14 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
     step.  Single GPU only: the N > 1 exchange carries no depth gradient (NotImplementedError).
     weight [H,W] float (a mask is the 0/1 case): the colour loss becomes the weighted one (FusedLoss.forward_backward(weight=...): three loss
     launches instead of two, terms the weighted means, FusedLoss.weight_sum the sum of the weights); it combines freely with gt_depth and, the
-    loss being rank-local, with N > 1.  weight=None is exactly the unweighted step."""
+    loss being rank-local, with N > 1.  weight=None is exactly the unweighted step.
+    grad_stats (a GradientStats of this model; single GPU): the view is added to the densification statistics — with the Adam update inside the
+    backward by that kernel itself (gslic_rasterize_backward_adam_stats / _depth_adam_stats: the gradient never leaves it), otherwise from the
+    dL_dmeans2D the backward then also writes (one small kernel).  Parameters and moments are bit-identical with and without it; None is today's
+    step, launch for launch."""
     fl = fused_loss or _default_fused_loss()
     use_depth = gt_depth is not None and lambda_depth != 0.0
+    grad_stats = _grad_stats_for_step(grad_stats, model)
     if use_depth and _dist_on():
         raise NotImplementedError("training_step_fused with depth supervision is single-GPU only: the N > 1 gradient exchange (rank1 / slab "
                                   "all-reduce) carries no depth gradient; use training_step(gt_depth=...) or run on one GPU")
@@ -1197,7 +1331,10 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
                 if xg is None or xg.shape[0] != model.P or xg.device != rr.xyz.device:
                     xg = model._depth_xyz_grad = torch.empty(model.P, 3, dtype=torch.float32, device=dev)
             vis_u8 = torch.empty(model.P, dtype=torch.uint8, device=dev)
-            rr.backward(dL_dimage, dL_ddepth, adam=model.optimizer.fused_descriptor(visible_out=vis_u8), xyz_grad=xg)
+            if grad_stats is None:
+                rr.backward(dL_dimage, dL_ddepth, adam=model.optimizer.fused_descriptor(visible_out=vis_u8), xyz_grad=xg)
+            else:
+                rr.backward(dL_dimage, dL_ddepth, adam=model.optimizer.fused_descriptor(visible_out=vis_u8), xyz_grad=xg, grad_stats=grad_stats._descriptor())
             model.optimizer.count_step()
             return terms, vis_u8.view(torch.bool)   # `radii > 0` (renderer.cpp:85), written by the backward kernel: no compare launch
         slab = _grad_slab(model)
@@ -1218,7 +1355,10 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
                 model.optimizer.step(grads, only=idx)
             _dist_mark("end")
             return terms, visible
-        rr.backward(dL_dimage, dL_ddepth, out=slab.views)
+        if grad_stats is None:
+            rr.backward(dL_dimage, dL_ddepth, out=slab.views)
+        else:
+            grad_stats.accumulate_from(rr.backward(dL_dimage, dL_ddepth, out=slab.views, mean2d_out=grad_stats._mean2d_buffer())[0], radii)
         visible = radii > 0
         if do_step:
             if _dist_on():
@@ -1289,7 +1429,7 @@ class GraphedStep:
     checks when a step is repeated.  A step built without a weight raises when it is handed one; a step built with one raises on weight=False."""
 
     def __init__(self, model, camera, gt_image, bg, headroom=1.25, check_every=16, cap_R=None, cap_B=None, use_graph=False, gt_depth=None,
-                 lambda_depth=0.0, weight=None):
+                 lambda_depth=0.0, weight=None, grad_stats=None):
         """use_graph=False (default since round 5): the capacity-mode step (caller-owned scratch, no host round trip, overflow checks and repeats as
         below) issued as eager launches; use_graph=True: captured in a hipGraph and replayed with one launch per step.  The two are equally fast at
         2M Gaussians (bench.py: `capacity_eager` / `graphed`; the host runs ahead of the device either way), and the eager form has no hazard:
@@ -1297,6 +1437,9 @@ class GraphedStep:
         work — a copy, a fill — before it (tools/experiments/graph_check_repro.py, modes B / C / E; a synchronise alone, or a blocking .cpu() copy
         alone, is harmless: modes A / D / F).  A host that uses the graph must keep its own device work off that pattern."""
         assert not _dist_on(), "GraphedStep is the single-GPU path"
+        # grad_stats (a GradientStats of this model): every step that fits adds its view to the statistics inside the backward kernel; a step that
+        # did not fit touches nothing (and is repeated).  The three arrays are fixed when the step is built: see _issue.
+        self.grad_stats = _grad_stats_for_step(grad_stats, model)
         self.use_graph = bool(use_graph)
         self.model, self.bg, self.headroom, self.check_every = model, bg, float(headroom), int(check_every)
         dev = model.device
@@ -1334,7 +1477,10 @@ class GraphedStep:
         rr = _RawRaster(self.model, self.cam, self.bg, self.use_depth, e=self.e, pose=(self.view, self.proj, self.campos))
         image, depth, _radii = rr.forward(self.bufs)
         dL_dimage, dL_ddepth, self.terms = _fused_losses(self.fl, image, self.gt, depth, self.gt_depth, self.lambda_depth, self.weight)
-        rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad)
+        if self._gstat is None:
+            rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad)
+        else:
+            rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad, grad_stats=self._gstat)
 
     def _capture(self):
         from . import rasterizer as rz
@@ -1342,11 +1488,14 @@ class GraphedStep:
         self.bufs = rz.CapacityBuffers(self.model.P, self.W, self.H, self.cap_R, self.cap_B, dev, depth=self.use_depth)
         self._adam = self.model.optimizer.fused_descriptor()
         self._xyz_grad = torch.empty(self.model.P, 3, dtype=torch.float32, device=dev) if self.use_depth else None
+        self._gstat = None if self.grad_stats is None else self.grad_stats._descriptor()
+        self._gstat_addr = None if self.grad_stats is None else self.grad_stats._addresses()
         # warm-up on a side stream (allocations of the loss scratch, library one-offs), then capture.  The warm-up and the capture
         # pass both execute the step, so the parameters are saved and restored around them.
         names = self.model.NAMES
         saved = [(self.model._buf[n][:self.model.P].clone(), self.model._m[n][:self.model.P].clone(), self.model._v[n][:self.model.P].clone())
                  for n in names]
+        saved_stats = [] if self.grad_stats is None else [a.clone() for a, _w in self.grad_stats._arrays()]   # (the two passes are no views of the host's)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s), torch.no_grad():
@@ -1361,6 +1510,8 @@ class GraphedStep:
             torch.cuda.synchronize()
         for n, (p, m1, m2) in zip(names, saved):
             self.model._buf[n][:self.model.P].copy_(p); self.model._m[n][:self.model.P].copy_(m1); self.model._v[n][:self.model.P].copy_(m2)
+        for (a, _w), keep in zip(self.grad_stats._arrays() if saved_stats else (), saved_stats):
+            a.copy_(keep)
         self.bufs.status.zero_()
         self.graph = g
         self.steps_issued = 0
@@ -1465,6 +1616,11 @@ class GraphedStep:
             raise RuntimeError(f"GraphedStep: the model's rows changed since this step was built (P / layout_version {self._captured_layout} -> {now}: "
                                "extend() or prune()); its buffers, Adam descriptor and graph hold the old row count and addresses — build a new "
                                "GraphedStep")
+        if self.grad_stats is not None:
+            self.grad_stats._check()
+            if self.grad_stats._addresses() != self._gstat_addr:
+                raise RuntimeError("GraphedStep: the arrays of the GradientStats were reallocated since this step was built; the step holds the old "
+                                   "addresses — build a new GraphedStep")
         if self.graph is not None:
             self.graph.replay()
         else:

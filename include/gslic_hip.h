@@ -356,6 +356,59 @@ int gslic_rasterize_backward_depth_adam(
     float lambda_erank, const gslic_adam_fused* adam, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Gradient densification statistics (no reference counterpart; additive exports, ABI 8).
+ *
+ * The signal 3DGS hosts densify by is the accumulated norm of the view-space positional gradient (xyz_gradient_accum / denom) and, for the
+ * screen-size prune, max_radii2D.  On the fused-Adam backwards that gradient never leaves the per-Gaussian kernel; these entry points accumulate
+ * it there, in the one thread that owns the row.
+ *
+ * gslic_grad_stats: three per-row accumulators, DEVICE arrays of P elements each, caller-owned, persistent over views, in STORAGE row order.
+ * All three pointers are required.
+ *
+ * THE RULE.  For one backward, every row i of the call's row range with radii[i] > 0 is updated as follows.  mx, my are the two sums the
+ * per-Gaussian backward forms over the row's instances — the very numbers gslic_rasterize_backward writes to dL_dmean2D[3i] and [3i + 1]; the
+ * 0.5 W / 0.5 H factors are in them, as in 3DGS's viewspace_points.grad.
+ *     n = sqrtf((mx * mx) + (my * my))          each operation one float32 operation rounded on its own (no contraction), the square root
+ *                                               correctly rounded
+ *     if n is finite:  grad_sum[i] = grad_sum[i] + n,  n_seen[i] += 1        (a non-finite n changes neither)
+ *     max_radius[i] = max(max_radius[i], radii[i])                           (whether or not n is finite)
+ * Rows with radii[i] <= 0 and rows outside the range are not touched.  When the forward's status word reports a capacity overflow
+ * (status[2] != 0: the step is a no-op) nothing is touched.  One thread owns a row: plain loads and stores, no atomics, and the result is a
+ * fixed function of the sequence of views.
+ *
+ * gslic_rasterize_backward_adam_stats / gslic_rasterize_backward_depth_adam_stats — gslic_rasterize_backward_adam / _depth_adam (same
+ *  arguments, same checks, bit-identical parameters and moments) which also apply the rule.  Refused with GSLIC_ERR_INVALID_ARG before any
+ *  device work: stats == NULL or one of its pointers NULL; one of the three arrays ([P] x 4 bytes) overlapping another, or overlapping a
+ *  param / exp_avg / exp_avg_sq tensor of the Adam descriptor.
+ * gslic_gradient_stats_accumulate — the rule on a dL_dmean2D [P,3] (elements 0 and 1 of a row are mx, my) and radii [P] the caller already has
+ *  (gslic_rasterize_backward and its depth / camera variants write them), rows [row_begin, row_end) (row_end < 0: P): one launch, one thread per
+ *  row, bit-identical to the fused route on the same gradient.  NULL pointers, overlapping arrays and a bad row range are refused.
+ */
+typedef struct gslic_grad_stats {
+    float* grad_sum;       /* float32 [P] */
+    uint32_t* n_seen;      /* uint32  [P] */
+    int32_t* max_radius;   /* int32   [P] */
+} gslic_grad_stats;
+int gslic_rasterize_backward_adam_stats(
+    const gslic_raster_params* prm, int32_t R, int32_t B,
+    const float* background, const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+    const float* scales, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix, const float* cam_pos, const int32_t* radii,
+    char* geom_buffer, char* binning_buffer, char* img_buffer, char* sample_buffer, const float* dL_dpix,
+    float* dL_dopacity, float* dL_dmean3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot,
+    float lambda_erank, const gslic_adam_fused* adam, const gslic_grad_stats* stats, void* stream);
+int gslic_rasterize_backward_depth_adam_stats(
+    const gslic_raster_params* prm, int32_t R, int32_t B,
+    const float* background, const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+    const float* scales, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix, const float* cam_pos, const int32_t* radii,
+    char* geom_buffer, char* binning_buffer, char* img_buffer, char* sample_buffer, const float* dL_dpix, const float* dL_ddepth,
+    float* dL_dopacity, float* dL_dmean3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot,
+    float lambda_erank, const gslic_adam_fused* adam, const gslic_grad_stats* stats, void* stream);
+int gslic_gradient_stats_accumulate(
+    int32_t P, const float* dL_dmean2D, const int32_t* radii, const gslic_grad_stats* stats, int32_t row_begin, int32_t row_end, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * gslic_rasterize_backward_rgb + gslic_sh_grad_from_rgb — the backward split for the N-GPU exchange (no reference counterpart: the
  * reference is single-GPU).  The SH backward (computeColorFromSH, backward.cu:27-136) is linear in the clamp-masked colour gradient
  * dRGB: dL_ddc = SH_C0 dRGB and dL_dsh[k] = c_k(dir) dRGB, with c_k a function of the view direction normalize(p - campos) only.

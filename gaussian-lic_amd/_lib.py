@@ -56,7 +56,7 @@ EXPORTS = [
     "gslic_rasterize_forward_depth_capacity", "gslic_rasterize_backward_depth_adam", "gslic_depth_l1_loss_partials_count",
     "gslic_depth_l1_loss_forward_backward", "gslic_img_bytes_depth", "gslic_binning_bytes_depth", "gslic_sample_bytes_depth",
     "gslic_rasterize_backward_depth_camera", "gslic_prune_select", "gslic_gather_rows", "gslic_contribution_accumulate",
-    "gslic_contribution_accumulate_error", "gslic_densify_select", "gslic_densify_emit",
+    "gslic_contribution_accumulate_error", "gslic_contribution_accumulate_free_space", "gslic_densify_select", "gslic_densify_emit",
     "gslic_l1_ssim_loss_weighted_partials_count", "gslic_l1_ssim_loss_weighted_forward_backward",
     "gslic_morton_order", "gslic_permute_rows", "gslic_permute_rows_staging_bytes",
     "gslic_rasterize_backward_adam_stats", "gslic_rasterize_backward_depth_adam_stats", "gslic_gradient_stats_accumulate",
@@ -141,6 +141,7 @@ def lib():
     L.gslic_permute_rows_staging_bytes.argtypes = [ctypes.POINTER(RowArray), i32, i32]
     L.gslic_contribution_accumulate.argtypes = [prm, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp]   # params, R, B, geom / binning / img, w_min, 3 outputs, stream
     L.gslic_contribution_accumulate_error.argtypes = [prm, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]   # ... 3 outputs, err, err_sum, stream
+    L.gslic_contribution_accumulate_free_space.argtypes = [prm, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]   # ... 3 outputs, near_bound, free_sum, meas_sum, stream
     L.gslic_densify_select.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, ALLOC_FN, vp, vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     six_ptrs = ctypes.POINTER(vp)   # HOST array of six device base pointers
     L.gslic_densify_emit.argtypes = [i32, i32, vp, i32, six_ptrs, six_ptrs, six_ptrs, vp, f32, u32, vp]

@@ -1432,19 +1432,22 @@ int gslic_permute_rows(const gslic_row_array* arrays, int32_t n_arrays, const ui
     return permute_rows(arrays, n_arrays, perm, n_rows, staging, (hipStream_t)stream);
 }
 
-// the two contribution entry points: same checks, same early returns, same launch geometry; with_err adds the error image and its accumulator
+// the three contribution entry points: same checks, same early returns, same launch geometry; with_err adds the error image and its accumulator,
+// with_free the near-bound image and its two
 static int contribution_accumulate(const gslic_raster_params* prm, int32_t R, int32_t B, const char* geom_buffer, const char* binning_buffer,
                                    const char* img_buffer, float w_min, uint32_t* max_w, uint32_t* n_pix, uint64_t* sum_w, bool with_err,
-                                   const float* err, uint64_t* err_sum, void* stream)
+                                   const float* err, uint64_t* err_sum, void* stream, bool with_free = false, const float* near_bound = nullptr,
+                                   uint64_t* free_sum = nullptr, uint64_t* meas_sum = nullptr)
 {
     GS_TRY(check_params(prm));
     if (R < 0 || B < 0) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: negative R / B");
     if (prm->no_color) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: a no_color forward stores no n_contrib (nothing says where a pixel stopped)");
     if (w_min != w_min) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: w_min is NaN");
     if (with_err && (!err || !err_sum)) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: NULL error image / err_sum");
+    if (with_free && (!near_bound || !free_sum || !meas_sum)) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: NULL near_bound image / free_sum / meas_sum");
     if (prm->P == 0 || R == 0) return GSLIC_OK;
     if (!geom_buffer || !binning_buffer || !img_buffer) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: NULL forward buffer");
-    if (!with_err && !max_w && !n_pix && !sum_w) return GSLIC_OK;
+    if (!with_err && !with_free && !max_w && !n_pix && !sum_w) return GSLIC_OK;
     int gx, gy;
     const int T = tile_grid(prm->width, prm->height, gx, gy);
     // the colour-only carve: a prefix of the depth layouts, and the capacity variants carve the same blocks for their capacity R
@@ -1455,6 +1458,9 @@ static int contribution_accumulate(const gslic_raster_params* prm, int32_t R, in
     ca.W = prm->width; ca.H = prm->height; ca.gx = gx; ca.T = T; ca.P = prm->P; ca.R = (uint32_t)R;
     ca.ranges = img.ranges; ca.point_list = bin.point_list(); ca.rec = geom.rec; ca.pix_final = img.pix_final; ca.status = geom.flags;
     ca.w_min = w_min; ca.max_w = max_w; ca.n_pix = n_pix; ca.sum_w = reinterpret_cast<unsigned long long*>(sum_w);
+    if (with_free)
+        return launch_contribution(ca, (hipStream_t)stream, nullptr, nullptr, near_bound, reinterpret_cast<unsigned long long*>(free_sum),
+                                   reinterpret_cast<unsigned long long*>(meas_sum));
     return launch_contribution(ca, (hipStream_t)stream, with_err ? err : nullptr, with_err ? reinterpret_cast<unsigned long long*>(err_sum) : nullptr);
 }
 
@@ -1469,6 +1475,14 @@ int gslic_contribution_accumulate_error(const gslic_raster_params* prm, int32_t 
                                         uint64_t* err_sum, void* stream)
 {
     return contribution_accumulate(prm, R, B, geom_buffer, binning_buffer, img_buffer, w_min, max_w, n_pix, sum_w, true, err, err_sum, stream);
+}
+
+int gslic_contribution_accumulate_free_space(const gslic_raster_params* prm, int32_t R, int32_t B, const char* geom_buffer, const char* binning_buffer,
+                                             const char* img_buffer, float w_min, uint32_t* max_w, uint32_t* n_pix, uint64_t* sum_w,
+                                             const float* near_bound, uint64_t* free_sum, uint64_t* meas_sum, void* stream)
+{
+    return contribution_accumulate(prm, R, B, geom_buffer, binning_buffer, img_buffer, w_min, max_w, n_pix, sum_w, false, nullptr, nullptr, stream, true,
+                                   near_bound, free_sum, meas_sum);
 }
 
 int gslic_densify_select(int32_t P, const float* xyz, const float* dc, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw,

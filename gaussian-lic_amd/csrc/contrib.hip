@@ -15,6 +15,8 @@
 //   the tile does not blend.  Integer max / add / saturating add commute: the accumulators do not depend on the order in which tiles finish.
 // contribution_error_kernel (gslic_contribution_accumulate_error): the same body (contrib_body.inc, CONTRIB_ERR = 1) which also reduces w e(p),
 //   e = the caller's per-pixel error image clamped to [0, 4], into a fourth accumulator by the same route.
+// contribution_free_space_kernel (gslic_contribution_accumulate_free_space): the same body (CONTRIB_FREE = 1) which also reduces w over the pixels
+//   with a measured near bound, and over those of them the entry lies in front of (z_g < near_bound[p]), into two more accumulators by that route.
 #include "gslic_common.h"
 #include "kernels.h"
 
@@ -62,22 +64,38 @@ __device__ __forceinline__ float error_value(float e)
 __global__ __launch_bounds__(256) void contribution_kernel(ContribArgs a)
 {
 #define CONTRIB_ERR 0
+#define CONTRIB_FREE 0
 #include "contrib_body.inc"
+#undef CONTRIB_FREE
 #undef CONTRIB_ERR
 }
 
 __global__ __launch_bounds__(256) void contribution_error_kernel(ContribArgs a, const float* __restrict__ err, unsigned long long* __restrict__ err_sum)
 {
 #define CONTRIB_ERR 1
+#define CONTRIB_FREE 0
 #include "contrib_body.inc"
+#undef CONTRIB_FREE
 #undef CONTRIB_ERR
 }
 
-int launch_contribution(const ContribArgs& a, hipStream_t s, const float* err, unsigned long long* err_sum)
+__global__ __launch_bounds__(256) void contribution_free_space_kernel(ContribArgs a, const float* __restrict__ near_bound,
+                                                                      unsigned long long* __restrict__ free_sum, unsigned long long* __restrict__ meas_sum)
+{
+#define CONTRIB_ERR 0
+#define CONTRIB_FREE 1
+#include "contrib_body.inc"
+#undef CONTRIB_FREE
+#undef CONTRIB_ERR
+}
+
+int launch_contribution(const ContribArgs& a, hipStream_t s, const float* err, unsigned long long* err_sum, const float* near_bound,
+                        unsigned long long* free_sum, unsigned long long* meas_sum)
 {
     if (a.T <= 0) return GSLIC_OK;
     if ((uint64_t)a.T * GS_TILE_PIX >= 0x80000000ull) return set_error(GSLIC_ERR_INVALID_ARG, "contribution: %d tiles are more than one launch counts", a.T);
-    if (err_sum) hipLaunchKernelGGL(contribution_error_kernel, dim3((unsigned)a.T), dim3(256), 0, s, a, err, err_sum);
+    if (free_sum) hipLaunchKernelGGL(contribution_free_space_kernel, dim3((unsigned)a.T), dim3(256), 0, s, a, near_bound, free_sum, meas_sum);
+    else if (err_sum) hipLaunchKernelGGL(contribution_error_kernel, dim3((unsigned)a.T), dim3(256), 0, s, a, err, err_sum);
     else hipLaunchKernelGGL(contribution_kernel, dim3((unsigned)a.T), dim3(256), 0, s, a);
     GS_HIP(hipGetLastError());
     return GSLIC_OK;

@@ -199,7 +199,9 @@ struct ContribArgs {
     unsigned long long* sum_w;        // [P] 32.32 fixed point
 };
 // err_sum != NULL: the error-weighted variant of gslic_contribution_accumulate_error (err [H,W] row-major; err_sum [P] 32.32 fixed point)
-int launch_contribution(const ContribArgs& a, hipStream_t s, const float* err = nullptr, unsigned long long* err_sum = nullptr);
+// free_sum != NULL: the free-space variant of gslic_contribution_accumulate_free_space (near_bound [H,W] row-major; free_sum / meas_sum [P] 32.32)
+int launch_contribution(const ContribArgs& a, hipStream_t s, const float* err = nullptr, unsigned long long* err_sum = nullptr,
+                        const float* near_bound = nullptr, unsigned long long* free_sum = nullptr, unsigned long long* meas_sum = nullptr);
 
 // densify.hip: the clone / split rule of gslic_densify_select on the raw parameters -> parent_index / the two counts (one stream synchronisation),
 // and the new rows of gslic_densify_emit: the wide launch (copied fields, zeroed moments) and then one thread per parent (arguments validated by

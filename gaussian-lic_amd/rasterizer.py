@@ -563,18 +563,29 @@ def gradient_stats_accumulate(dL_dmean2D, radii, grad_sum, n_seen, max_radius, r
     _lib.check(_lib.lib().gslic_gradient_stats_accumulate(P, _lib.ptr(dL_dmean2D), _lib.ptr(radii), ctypes.byref(gs), r0, r1, _lib.current_stream_ptr()))
 
 
-def contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, max_w=None, n_pix=None, sum_w=None, error=None, err_sum=None):
+def contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, max_w=None, n_pix=None, sum_w=None, error=None, err_sum=None,
+                            near_bound=None, free_sum=None, meas_sum=None):
     """gslic_contribution_accumulate: adds ONE view's per-Gaussian contribution statistics, replayed from the buffers of a completed forward
     (rasterize_gaussians / _depth / _capacity / _depth_capacity; R, B as that forward returned them), to the caller's accumulators —
     max_w int32 [>= P] (float bits), n_pix int32 [>= P], sum_w int64 [>= P] (32.32 fixed point), device tensors indexed by storage row, any of
     them None.  The rule is written out in include/gslic_hip.h.  One launch on the current stream, no synchronisation.
     error (float32 [H, W] device tensor) together with err_sum (int64 [>= P], 32.32 fixed point) takes gslic_contribution_accumulate_error: the
-    same launch, which also adds sum w e(p) to err_sum (e = error clamped to [0, 4], NaN and negative values read as 0)."""
+    same launch, which also adds sum w e(p) to err_sum (e = error clamped to [0, 4], NaN and negative values read as 0).
+    near_bound (float32 [H, W] device tensor) together with free_sum and meas_sum (int64 [>= P], 32.32 fixed point) takes
+    gslic_contribution_accumulate_free_space instead: meas_sum += sum of w over the pixels with near_bound > 0, free_sum += sum of w over those of
+    them with the Gaussian's view depth < near_bound.  One call takes one of the two images (they are two entry points)."""
     if (error is None) != (err_sum is None):
         raise ValueError("contribution_accumulate: error and err_sum go together")
+    if not ((near_bound is None) == (free_sum is None) == (meas_sum is None)):
+        raise ValueError("contribution_accumulate: near_bound, free_sum and meas_sum go together")
+    if error is not None and near_bound is not None:
+        raise ValueError("contribution_accumulate: error and near_bound are two launches (call twice, the second with max_w = n_pix = sum_w = None)")
+    if near_bound is not None and not (near_bound.is_contiguous() and near_bound.dtype == torch.float32 and tuple(near_bound.shape) == (int(H), int(W))
+                                       and near_bound.device == free_sum.device):
+        raise ValueError(f"contribution_accumulate: near_bound must be a contiguous float32 [{int(H)}, {int(W)}] tensor on the accumulators' device")
     if error is not None and not (error.is_contiguous() and error.dtype == torch.float32 and tuple(error.shape) == (int(H), int(W)) and error.device == err_sum.device):
         raise ValueError(f"contribution_accumulate: error must be a contiguous float32 [{int(H)}, {int(W)}] tensor on the accumulators' device")
-    for t, dt in ((max_w, torch.int32), (n_pix, torch.int32), (sum_w, torch.int64), (err_sum, torch.int64)):
+    for t, dt in ((max_w, torch.int32), (n_pix, torch.int32), (sum_w, torch.int64), (err_sum, torch.int64), (free_sum, torch.int64), (meas_sum, torch.int64)):
         if t is not None and not (t.is_contiguous() and t.dtype == dt and t.numel() >= int(P)):
             raise ValueError(f"contribution_accumulate: an accumulator must be a contiguous {dt} tensor of at least {int(P)} rows")
     prm = _params(P, 0, 0, H, W, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, False, False, False)   # (only P, W and H are read)
@@ -582,6 +593,11 @@ def contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, max_w=None
     if error is not None:
         _lib.check(_lib.lib().gslic_contribution_accumulate_error(ctypes.byref(prm), int(R), int(B), bp(geom), bp(binning), bp(img), float(w_min),
                                                                   bp(max_w), bp(n_pix), bp(sum_w), bp(error), bp(err_sum), _lib.current_stream_ptr()))
+        return
+    if near_bound is not None:
+        _lib.check(_lib.lib().gslic_contribution_accumulate_free_space(ctypes.byref(prm), int(R), int(B), bp(geom), bp(binning), bp(img), float(w_min),
+                                                                       bp(max_w), bp(n_pix), bp(sum_w), bp(near_bound), bp(free_sum), bp(meas_sum),
+                                                                       _lib.current_stream_ptr()))
         return
     _lib.check(_lib.lib().gslic_contribution_accumulate(ctypes.byref(prm), int(R), int(B), bp(geom), bp(binning), bp(img), float(w_min), bp(max_w),
                                                         bp(n_pix), bp(sum_w), _lib.current_stream_ptr()))

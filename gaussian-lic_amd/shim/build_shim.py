@@ -107,6 +107,7 @@ CHECK_FUSED_DENSIFY = os.path.join(PKG, "fused_densify_check")
 CHECK_FUSED_WEIGHTED = os.path.join(PKG, "fused_weighted_check")
 CHECK_FUSED_RESORT = os.path.join(PKG, "fused_resort_check")
 CHECK_FUSED_GRADIENT_STATS = os.path.join(PKG, "fused_gradient_stats_check")
+CHECK_FUSED_FREE_SPACE = os.path.join(PKG, "fused_free_space_check")
 
 
 def build_fused_check(force=False):
@@ -162,6 +163,12 @@ def build_fused_gradient_stats_check(force=False):
     return _build_fused_program(os.path.join(HERE, "fused_gradient_stats_check.cpp"), CHECK_FUSED_GRADIENT_STATS, force)
 
 
+def build_fused_free_space_check(force=False):
+    """fused_free_space_check: the free-space statistics from C++ (gslic::FusedStep::accumulate_free_space, carried through prune and resort
+    between fused steps) — built like fused_check."""
+    return _build_fused_program(os.path.join(HERE, "fused_free_space_check.cpp"), CHECK_FUSED_FREE_SPACE, force)
+
+
 def _build_fused_program(src, CHECK_FUSED, force):
     import sysconfig
     import torch
@@ -201,3 +208,4 @@ if __name__ == "__main__":
     print(build_fused_weighted_check(force="--force" in sys.argv))
     print(build_fused_resort_check(force="--force" in sys.argv))
     print(build_fused_gradient_stats_check(force="--force" in sys.argv))
+    print(build_fused_free_space_check(force="--force" in sys.argv))

@@ -51,6 +51,8 @@ struct ContributionStats {
     torch::Tensor n_pix;   // int32 [capacity]: uint32 count of (pixel, view) pairs with w >= w_min (saturating)
     torch::Tensor sum_w;   // int64 [capacity]: uint64 sum of w, 32.32 fixed point
     torch::Tensor err_sum; // int64 [capacity]: uint64 sum of w e(p), 32.32 fixed point — undefined until a view is accumulated with an error image
+    torch::Tensor free_sum; // int64 [capacity]: uint64 sum of w over the measured pixels the row lies in front of (z_g < near_bound[p]), 32.32 fixed point
+    torch::Tensor meas_sum; // int64 [capacity]: uint64 sum of w over the measured pixels (near_bound[p] > 0) — both undefined until accumulate_free_space
     int64_t views = 0;
 };
 
@@ -165,6 +167,7 @@ public:
             fit_stats(*stats, capacity(), false);
             add(stats->max_w, 1u); add(stats->n_pix, 1u); add(stats->sum_w, 2u);
             if (stats->err_sum.defined()) add(stats->err_sum, 2u);
+            if (stats->free_sum.defined()) { add(stats->free_sum, 2u); add(stats->meas_sum, 2u); }
         }
         if (gstats_) {
             fit_gradient_stats(capacity());
@@ -300,12 +303,18 @@ public:
             ContributionStats old = *stats;
             stats->max_w = torch::zeros({cap}, io); stats->n_pix = torch::zeros({cap}, io); stats->sum_w = torch::zeros({cap}, io.dtype(torch::kInt64));
             if (old.err_sum.defined()) stats->err_sum = torch::zeros({cap}, io.dtype(torch::kInt64));
+            if (old.free_sum.defined()) { stats->free_sum = torch::zeros({cap}, io.dtype(torch::kInt64)); stats->meas_sum = torch::zeros({cap}, io.dtype(torch::kInt64)); }
             if (count > 0) {
-                TORCH_CHECK(old.max_w.size(0) >= P && old.n_pix.size(0) >= P && old.sum_w.size(0) >= P && (!old.err_sum.defined() || old.err_sum.size(0) >= P),
+                TORCH_CHECK(old.max_w.size(0) >= P && old.n_pix.size(0) >= P && old.sum_w.size(0) >= P && (!old.err_sum.defined() || old.err_sum.size(0) >= P) &&
+                                (!old.free_sum.defined() || (old.free_sum.size(0) >= P && old.meas_sum.size(0) >= P)),
                             "FusedStep::prune: the statistics hold fewer rows than the map");
                 std::vector<gslic_row_array> sr = {{old.max_w.data_ptr(), stats->max_w.data_ptr(), 1u}, {old.n_pix.data_ptr(), stats->n_pix.data_ptr(), 1u},
                                                    {old.sum_w.data_ptr(), stats->sum_w.data_ptr(), 2u}};
                 if (old.err_sum.defined()) sr.push_back({old.err_sum.data_ptr(), stats->err_sum.data_ptr(), 2u});
+                if (old.free_sum.defined()) {
+                    sr.push_back({old.free_sum.data_ptr(), stats->free_sum.data_ptr(), 2u});
+                    sr.push_back({old.meas_sum.data_ptr(), stats->meas_sum.data_ptr(), 2u});
+                }
                 check(gslic_gather_rows(sr.data(), (int32_t)sr.size(), reinterpret_cast<const uint32_t*>(kept.data_ptr<int32_t>()), count, current_stream()),
                       "gslic_gather_rows (statistics)");
             }
@@ -346,15 +355,8 @@ public:
         fit_stats(stats, capacity(), err.defined());
         stats.views++;
         if (P == 0) return;
-        const gslic_raster_params rp = raster_params(cam, true, false);
-        ensure_image_buffers(H, W);
-        ensure_rows(P);
         int32_t R = 0, B = 0;
-        check(gslic_rasterize_forward(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), f(prm_[0]),
-                                      f(prm_[1]), f(prm_[2]), nullptr, f(prm_[3]), f(prm_[4]), f(prm_[5]), nullptr, f(cam.world_view_transform),
-                                      f(cam.full_proj_transform), f(cam.camera_center), image_.data_ptr<float>(), final_T_.data_ptr<float>(),
-                                      radii_.data_ptr<int32_t>(), &R, &B, current_stream()),
-              "gslic_rasterize_forward");
+        const gslic_raster_params rp = statistics_forward(cam, R, B);
         if (err.defined()) {
             check(gslic_contribution_accumulate_error(&rp, R, B, cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), w_min,
                                                       reinterpret_cast<uint32_t*>(stats.max_w.data_ptr<int32_t>()),
@@ -368,6 +370,33 @@ public:
                                             reinterpret_cast<uint32_t*>(stats.max_w.data_ptr<int32_t>()), reinterpret_cast<uint32_t*>(stats.n_pix.data_ptr<int32_t>()),
                                             reinterpret_cast<uint64_t*>(stats.sum_w.data_ptr<int64_t>()), current_stream()),
               "gslic_contribution_accumulate");
+    }
+    // Adds ONE view with a near-bound image — the Python host's ContributionStats.accumulate(camera, free_space=near): the same forward, then one
+    // gslic_contribution_accumulate_free_space.  near_bound: float [H,W] on the map's device in view-space depth units (a pixel is measured where
+    // it is > 0; typically d - (margin_abs + margin_rel d) of a LiDAR depth image, 0 where nothing was measured).  The three base statistics come out
+    // as accumulate_contribution's, bit for bit; stats.meas_sum += sum of w over the measured pixels, stats.free_sum += sum of w over the
+    // measured pixels the Gaussian lies in front of (view depth < bound).  The two arrays are created at the first such call.
+    void accumulate_free_space(const FusedCamera& cam, ContributionStats& stats, float w_min, const torch::Tensor& near_bound)
+    {
+        torch::NoGradGuard ng;
+        const int64_t P = prm_[0].size(0);
+        const int W = cam.image_width, H = cam.image_height;
+        TORCH_CHECK(near_bound.defined() && near_bound.dim() == 2 && near_bound.size(0) == H && near_bound.size(1) == W && near_bound.is_floating_point() &&
+                        near_bound.device() == prm_[0].device(),
+                    "FusedStep::accumulate_free_space: near_bound must be a float [", H, ", ", W, "] tensor on the map's device");
+        const torch::Tensor near = near_bound.detach().to(torch::kFloat32).contiguous();
+        fit_stats(stats, capacity(), false, true);
+        stats.views++;
+        if (P == 0) return;
+        int32_t R = 0, B = 0;
+        const gslic_raster_params rp = statistics_forward(cam, R, B);
+        check(gslic_contribution_accumulate_free_space(&rp, R, B, cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), w_min,
+                                                       reinterpret_cast<uint32_t*>(stats.max_w.data_ptr<int32_t>()),
+                                                       reinterpret_cast<uint32_t*>(stats.n_pix.data_ptr<int32_t>()),
+                                                       reinterpret_cast<uint64_t*>(stats.sum_w.data_ptr<int64_t>()), near.data_ptr<float>(),
+                                                       reinterpret_cast<uint64_t*>(stats.free_sum.data_ptr<int64_t>()),
+                                                       reinterpret_cast<uint64_t*>(stats.meas_sum.data_ptr<int64_t>()), current_stream()),
+              "gslic_contribution_accumulate_free_space");
     }
     // Clone / split densification on the device — the Python host's GaussianModel.densify (gaussian-lic_amd/trainer.py), same calls, same result:
     // ONE gslic_densify_select (which rows grow, and where their new rows go) and ONE gslic_densify_emit (the new rows of the 18 parameter and
@@ -423,7 +452,7 @@ public:
         bind(P + count);
         if (stats && stats->max_w.defined()) {
             fit_stats(*stats, capacity(), false);
-            for (torch::Tensor* t : {&stats->max_w, &stats->n_pix, &stats->sum_w, &stats->err_sum}) {
+            for (torch::Tensor* t : {&stats->max_w, &stats->n_pix, &stats->sum_w, &stats->err_sum, &stats->free_sum, &stats->meas_sum}) {
                 if (!t->defined()) continue;
                 t->narrow(0, P, count).zero_();
                 if (split_rows.defined()) t->index_fill_(0, split_rows, 0);
@@ -722,14 +751,28 @@ private:
         return se3_pose_gradient(hv.data_ptr<float>(), hp.data_ptr<float>(), hc.data_ptr<float>(), hc.data_ptr<float>() + 16, hc.data_ptr<float>() + 32);
     }
 
+    // the raw-parameter forward the statistics passes replay (P > 0): fills scratch_[0..2], returns its parameters and the two counts
+    gslic_raster_params statistics_forward(const FusedCamera& cam, int32_t& R, int32_t& B)
+    {
+        const gslic_raster_params rp = raster_params(cam, true, false);
+        ensure_image_buffers(cam.image_height, cam.image_width);
+        ensure_rows(prm_[0].size(0));
+        check(gslic_rasterize_forward(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), f(prm_[0]),
+                                      f(prm_[1]), f(prm_[2]), nullptr, f(prm_[3]), f(prm_[4]), f(prm_[5]), nullptr, f(cam.world_view_transform),
+                                      f(cam.full_proj_transform), f(cam.camera_center), image_.data_ptr<float>(), final_T_.data_ptr<float>(),
+                                      radii_.data_ptr<int32_t>(), &R, &B, current_stream()),
+              "gslic_rasterize_forward");
+        return rp;
+    }
     // GaussianModel._rows_appended's rule: the appended tail has grown past resort_fraction of the map
     void rows_appended(ContributionStats* stats)
     {
         const int64_t P = prm_[0].size(0);
         if (tie_.defined() && resort_fraction_ && (double)(P - sorted_P_) > *resort_fraction_ * (double)P) resort(stats);
     }
-    // the statistics' arrays, created zero-filled and grown (zero-extended) to `cap` rows; err_sum only once a view brought an error image
-    void fit_stats(ContributionStats& stats, int64_t cap, bool with_err)
+    // the statistics' arrays, created zero-filled and grown (zero-extended) to `cap` rows; err_sum only once a view brought an error image,
+    // free_sum / meas_sum only once one brought a near-bound image
+    void fit_stats(ContributionStats& stats, int64_t cap, bool with_err, bool with_free = false)
     {
         auto io = prm_[0].options().requires_grad(false).dtype(torch::kInt32);
         auto fit = [&](torch::Tensor& t, torch::ScalarType dt) {
@@ -740,6 +783,7 @@ private:
         };
         fit(stats.max_w, torch::kInt32); fit(stats.n_pix, torch::kInt32); fit(stats.sum_w, torch::kInt64);
         if (with_err || stats.err_sum.defined()) fit(stats.err_sum, torch::kInt64);
+        if (with_free || stats.free_sum.defined()) { fit(stats.free_sum, torch::kInt64); fit(stats.meas_sum, torch::kInt64); }
     }
     // the gradient statistics' arrays, created zero-filled and grown (zero-extended) to `cap` rows
     void fit_gradient_stats(int64_t cap)

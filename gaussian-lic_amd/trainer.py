@@ -540,6 +540,37 @@ def contribution_grow_mask(err_fixed, n_pix, error_above, min_pixels=None):
     return grow.to(torch.uint8)
 
 
+def contribution_floater_mask(free_fixed, measured_fixed, free_fraction_above, min_measured=0.0):
+    """uint8 [P]: 1 where the row was measured at all (measured_fixed != 0), its measured weight reaches min_measured (measured_fixed >=
+    weight_to_fixed(min_measured), an integer comparison on the stored bits, unsigned: a sum with bit 63 set reaches every limit) AND more than
+    free_fraction_above of that weight lay in front of the measured surface: free_weight > float64(free_fraction_above) * measured_weight, in
+    float64 through fixed_to_weight with ONE product and ONE strict comparison — a row at exactly the fraction stays.  free_fixed,
+    measured_fixed int64 [P] (ContributionStats.free_fixed() / .measured_fixed()); free_fraction_above in [0, 1]."""
+    frac = float(free_fraction_above)
+    if not (0.0 <= frac <= 1.0):   # (a NaN fails both comparisons)
+        raise ValueError(f"floater_mask: free_fraction_above must be in [0, 1], got {free_fraction_above!r}")
+    lim = int(weight_to_fixed(float(min_measured)))
+    if not (float(min_measured) >= 0.0) or lim < 0:
+        raise ValueError(f"floater_mask: min_measured must be >= 0 and below 2^31, got {min_measured!r}")
+    free_fixed = torch.as_tensor(free_fixed, dtype=torch.int64)
+    measured_fixed = torch.as_tensor(measured_fixed, dtype=torch.int64).to(free_fixed.device)
+    enough = ((measured_fixed >= lim) | (measured_fixed < 0)) & (measured_fixed != 0)
+    return (enough & (fixed_to_weight(free_fixed) > frac * fixed_to_weight(measured_fixed))).to(torch.uint8)
+
+
+def free_space_bound(depth, margin_abs, margin_rel):
+    """The near-bound image ContributionStats.accumulate(free_space=...) takes, from a depth image such as camera.project_depth(points) (0 where
+    no return fell): float32 [H, W], d - (margin_abs + margin_rel * d) where d > 0 and 0 elsewhere (d <= 0, NaN) — one product, one add, one
+    subtraction, each a float32 torch operation in that order.  A Gaussian whose view depth is below the bound sits more than the margin in
+    front of the measured surface.  Where the margin exceeds d the bound is <= 0: the pixel reads as not measured.  Plain torch, host policy."""
+    if not (float(margin_abs) >= 0.0 and float(margin_rel) >= 0.0):   # (a NaN fails)
+        raise ValueError(f"free_space_bound: the margins must be >= 0, got {margin_abs!r} and {margin_rel!r}")
+    d = torch.as_tensor(depth).detach().to(torch.float32)
+    ma = torch.tensor(float(margin_abs), dtype=torch.float32, device=d.device)
+    mr = torch.tensor(float(margin_rel), dtype=torch.float32, device=d.device)
+    return torch.where(d > 0, d - (ma + mr * d), torch.zeros((), dtype=torch.float32, device=d.device))
+
+
 class _RowStatistics:
     """What GaussianModel's row changes walk on an attached per-row statistics object (a weak reference in model._stats): _gather (prune), _appended
     (extend / densify), _zero_rows (densify's split parents), _permute (resort), on the arrays a subclass lists in _arrays() and creates, zero-filled
@@ -619,6 +650,8 @@ class ContributionStats(_RowStatistics):
 
     def __init__(self, model):
         self._err = None             # the error accumulator: allocated by the first accumulate with an error image
+        self._free = None            # the two free-space accumulators: allocated by the first accumulate with a near-bound image
+        self._meas = None
         self.views = 0
         super().__init__(model)
 
@@ -628,16 +661,21 @@ class ContributionStats(_RowStatistics):
         self._npix = torch.zeros(cap, dtype=torch.int32, device=dev)   # uint32 [cap]
         self._sum = torch.zeros(cap, dtype=torch.int64, device=dev)    # uint64 [cap]: 32.32 fixed point
         self._err = torch.zeros(cap, dtype=torch.int64, device=dev) if self._err is not None else None   # uint64 [cap], lazily
+        if self._free is not None:                                     # uint64 [cap] each, lazily and together
+            self._free = torch.zeros(cap, dtype=torch.int64, device=dev)
+            self._meas = torch.zeros(cap, dtype=torch.int64, device=dev)
 
     def _arrays(self):
         """The accumulators that exist, with their row widths in dwords."""
         a = [(self._max, 1), (self._npix, 1), (self._sum, 2)]
-        return a + ([(self._err, 2)] if self._err is not None else [])
+        a += [(self._err, 2)] if self._err is not None else []
+        return a + ([(self._free, 2), (self._meas, 2)] if self._free is not None else [])
 
     # --- accumulation
     @torch.no_grad()
-    def accumulate(self, camera, bg=None, w_min=None, error=None):
-        """Renders `camera` (a forward of its own, raw parameters, no autograd) and adds that view's statistics.  error: see accumulate_from."""
+    def accumulate(self, camera, bg=None, w_min=None, error=None, free_space=None):
+        """Renders `camera` (a forward of its own, raw parameters, no autograd) and adds that view's statistics.  error, free_space: see
+        accumulate_from."""
         self._check()
         if self.model.P == 0:
             self.views += 1
@@ -645,16 +683,21 @@ class ContributionStats(_RowStatistics):
         bg = torch.zeros(3, device=self.model.device) if bg is None else bg
         fwd = _RawRaster(self.model, camera, bg)
         fwd.forward()
-        self.accumulate_from(fwd, w_min, error=error)
+        self.accumulate_from(fwd, w_min, error=error, free_space=free_space)
 
     @torch.no_grad()
-    def accumulate_from(self, fwd, w_min=None, error=None):
+    def accumulate_from(self, fwd, w_min=None, error=None, free_space=None):
         """Adds the statistics of a forward the caller already has: a _RawRaster after forward() (training_step_fused's pieces) or the
         rasterizer.CapacityBuffers a capacity forward filled (GraphedStep.bufs: the launch is sized from the capacities, stops at the real
         counts on the device and does nothing when the forward's status says the lists did not fit).  The forward must be of THIS model's rows.
         error: an [H, W] float device tensor, the view's per-pixel error (host policy, plain torch: (image - gt).abs().mean(0)).  The launch is
         then gslic_contribution_accumulate_error: the same statistics, and error_sum() += sum of w e(p) with e = error clamped to [0, 4]
-        (NaN and negative values read as 0).  The fourth accumulator is allocated at the first such call; without `error` it does not exist."""
+        (NaN and negative values read as 0).  The fourth accumulator is allocated at the first such call; without `error` it does not exist.
+        free_space: an [H, W] float device tensor, the view's near bound in view-space depth units (free_space_bound() of a LiDAR depth image;
+        a pixel is measured where it is > 0).  The launch is then gslic_contribution_accumulate_free_space: the same statistics, and
+        measured_weight() += sum of w over the measured pixels, free_weight() += sum of w over the measured pixels the Gaussian lies in front
+        of (view depth < bound).  Its two accumulators are allocated at the first such call.  With error AND free_space the view takes two
+        launches: the error launch with the three base statistics, then the free-space launch without them — nothing is counted twice."""
         from . import rasterizer as rz
         self._check()
         w_min = self.W_MIN if w_min is None else float(w_min)
@@ -669,17 +712,28 @@ class ContributionStats(_RowStatistics):
             P, (H, W) = fwd.xyz.shape[0], fwd.hw
         if P != self.model.P:
             raise ValueError(f"ContributionStats: the forward rendered {P} rows, the model has {self.model.P}")
-        if error is None:
-            rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, self._max, self._npix, self._sum)
-        else:
-            error = torch.as_tensor(error)
-            if tuple(error.shape) != (int(H), int(W)) or not error.is_floating_point() or error.device != self._max.device:
-                raise ValueError(f"ContributionStats: error must be a float [{int(H)}, {int(W)}] tensor on the model's device, got {error.dtype} "
-                                 f"{tuple(error.shape)} on {error.device}")
+        for name, t in (("error", error), ("free_space", free_space)):   # both validated before either launch
+            if t is None:
+                continue
+            t = torch.as_tensor(t)
+            if tuple(t.shape) != (int(H), int(W)) or not t.is_floating_point() or t.device != self._max.device:
+                raise ValueError(f"ContributionStats: {name} must be a float [{int(H)}, {int(W)}] tensor on the model's device, got {t.dtype} "
+                                 f"{tuple(t.shape)} on {t.device}")
+        base = (self._max, self._npix, self._sum)
+        if error is None and free_space is None:
+            rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, *base)
+        if error is not None:
             if self._err is None:
                 self._err = torch.zeros(self._max.shape[0], dtype=torch.int64, device=self._max.device)
-            rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, self._max, self._npix, self._sum,
-                                       error=error.detach().float().contiguous(), err_sum=self._err)
+            rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, *base,
+                                       error=torch.as_tensor(error).detach().float().contiguous(), err_sum=self._err)
+            base = (None, None, None)   # the free-space launch of the same view leaves them alone
+        if free_space is not None:
+            if self._free is None:
+                self._free = torch.zeros(self._max.shape[0], dtype=torch.int64, device=self._max.device)
+                self._meas = torch.zeros(self._max.shape[0], dtype=torch.int64, device=self._max.device)
+            rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, *base,
+                                       near_bound=torch.as_tensor(free_space).detach().float().contiguous(), free_sum=self._free, meas_sum=self._meas)
         self.views += 1
 
     def reset(self):
@@ -728,6 +782,33 @@ class ContributionStats(_RowStatistics):
     def grow_mask(self, error_above, min_pixels=None):
         """The uint8 [P] mask model.densify(grow=...) takes: contribution_grow_mask on error_fixed() and pixels()."""
         return contribution_grow_mask(self.error_fixed(), self.pixels(), error_above, min_pixels)
+
+    def free_fixed(self):
+        """int64 [P]: the bit patterns of the 32.32 fixed-point sums of w over the measured pixels the row lies in front of (zeros before the
+        first accumulate with a near-bound image)."""
+        self._check()
+        if self._free is None:
+            return torch.zeros(self.model.P, dtype=torch.int64, device=self._max.device)
+        return self._free[:self.model.P]
+
+    def measured_fixed(self):
+        """int64 [P]: the bit patterns of the 32.32 fixed-point sums of w over the measured pixels (zeros before the first such accumulate)."""
+        self._check()
+        if self._meas is None:
+            return torch.zeros(self.model.P, dtype=torch.int64, device=self._max.device)
+        return self._meas[:self.model.P]
+
+    def free_weight(self):
+        """float64 [P]: the blend weight the row carried in front of the measured surface — in known free space."""
+        return fixed_to_weight(self.free_fixed())
+
+    def measured_weight(self):
+        """float64 [P]: the blend weight the row carried in pixels with a measurement."""
+        return fixed_to_weight(self.measured_fixed())
+
+    def floater_mask(self, free_fraction_above, min_measured=0.0):
+        """The uint8 [P] mask model.prune(drop=...) takes: contribution_floater_mask on free_fixed() and measured_fixed()."""
+        return contribution_floater_mask(self.free_fixed(), self.measured_fixed(), free_fraction_above, min_measured)
 
     def drop_mask(self, max_weight_below=None, pixels_below=None):
         """The uint8 [P] mask model.prune(drop=...) takes: contribution_drop_mask on max_weight() and pixels()."""

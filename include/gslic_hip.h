@@ -796,6 +796,38 @@ int gslic_contribution_accumulate_error(
     const float* err /*[H,W]*/, uint64_t* err_sum /*[P]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * gslic_contribution_accumulate_free_space — the same launch over the same pairs as gslic_contribution_accumulate, which in addition tells a
+ * mapper with a measured range per pixel (a LiDAR depth image) which Gaussians carry blend weight IN FRONT of the measured surface, i.e. in
+ * known free space: the floaters the colour loss keeps alive.  A pass of its own like _error; the training step is not touched.  How the bound
+ * image is made (margins, dilation of sparse returns, dynamic objects) and when to prune is the host's policy.
+ *
+ *  near_bound [H,W] float, row-major, DEVICE, in view-space depth units: the nearest depth at which the measurement still allows a surface in
+ *  that pixel — typically d - (margin_abs + margin_rel d) where the LiDAR depth d > 0, and 0 elsewhere.
+ *  Pixel p is MEASURED iff near_bound[p] > 0: NaN, 0 and negative values are not measured, +inf is.
+ *  The pairs are exactly the contributing pairs of gslic_contribution_accumulate, with the same w from the same operations in the same order.
+ *  z_g is the float32 view depth in the Gaussian's record (what the depth blend reads).
+ *      meas_sum [P] uint64  += sum of w over the contributing pairs (p, g) whose pixel is measured
+ *      free_sum [P] uint64  += sum of w over the contributing pairs (p, g) whose pixel is measured AND z_g < near_bound[p]
+ *  The comparison is a strict float32 < with no arithmetic on either side, so torch or numpy reproduce it exactly.  Both are DEVICE,
+ *  caller-owned and persistent like sum_w, in 32.32 fixed point, formed by the route of sum_w and err_sum: the per-pixel addend is w or +0; a
+ *  wave combines its 64 addends with the wave butterfly (a fixed order); the four waves' partials are added in wave order; the tile partial is
+ *  converted ONCE (round to nearest) and added with one 64-bit integer add per (tile, entry), skipped when the partial is 0.  A tile partial is at
+ *  most 256 = 2^8, i.e. 2^40 in fixed point: 2^24 tile partials fit into a row.  Deterministic from run to run and independent of the order
+ *  in which tiles finish.  free_sum[g] <= meas_sum[g] <= what sum_w[g] gains, per tile partial and hence in total.
+ *  Consequences:  max_w / n_pix / sum_w (each may be NULL) come out bit-identical to gslic_contribution_accumulate's.  near_bound = +inf
+ *  everywhere gives free_sum == meas_sum == sum_w bit for bit.  A near_bound image of 0 and +inf only gives free_sum == meas_sum == the err_sum
+ *  of gslic_contribution_accumulate_error with the error image that is 1 where near_bound is +inf and 0 elsewhere, bit for bit.
+ *  Argument checks, the capacity-mode rule (nothing is accumulated when the forward's status words say the lists did not fit) and the early
+ *  returns are those of gslic_contribution_accumulate_error: all three of max_w / n_pix / sum_w NULL does NOT return early; near_bound, free_sum
+ *  or meas_sum NULL is GSLIC_ERR_INVALID_ARG, reported before any device work.  The replay is in the strict arithmetic only.
+ */
+int gslic_contribution_accumulate_free_space(
+    const gslic_raster_params* prm, int32_t R, int32_t B,
+    const char* geom_buffer, const char* binning_buffer, const char* img_buffer, float w_min,
+    uint32_t* max_w /*[P] or NULL*/, uint32_t* n_pix /*[P] or NULL*/, uint64_t* sum_w /*[P] or NULL*/,
+    const float* near_bound /*[H,W]*/, uint64_t* free_sum /*[P]*/, uint64_t* meas_sum /*[P]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * gslic_densify_select / gslic_densify_emit — clone / split densification on the device (no reference counterpart: its map grows from
  * LiDAR returns only; a LibTorch host would run 18 index + cat launches plus the rewrite of the split parents).  Which rows to grow
  * (`grow`, e.g. a threshold on err_sum) and when is the host's policy.

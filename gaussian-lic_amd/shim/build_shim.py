@@ -98,84 +98,34 @@ def _build_check(CHECK, first_includes, force, extra_src=()):
     return CHECK
 
 
-CHECK_FUSED = os.path.join(PKG, "fused_check")
-CHECK_FUSED_DEPTH = os.path.join(PKG, "fused_depth_check")
-CHECK_FUSED_DEPTH_POSE = os.path.join(PKG, "fused_depth_pose_check")
-CHECK_FUSED_PRUNE = os.path.join(PKG, "fused_prune_check")
-CHECK_FUSED_CONTRIBUTION = os.path.join(PKG, "fused_contribution_check")
-CHECK_FUSED_DENSIFY = os.path.join(PKG, "fused_densify_check")
-CHECK_FUSED_WEIGHTED = os.path.join(PKG, "fused_weighted_check")
-CHECK_FUSED_RESORT = os.path.join(PKG, "fused_resort_check")
-CHECK_FUSED_GRADIENT_STATS = os.path.join(PKG, "fused_gradient_stats_check")
-CHECK_FUSED_FREE_SPACE = os.path.join(PKG, "fused_free_space_check")
+# The programs that drive gslic::FusedStep (shim/include/gslic_fused.h) from C++ so that tests can hold it against the Python host — LibTorch and
+# libgslic_hip.so only, no reference source, so they build anywhere this repository does.  name -> (source, binary); what each one runs is in the
+# comment at the top of its source.
+FUSED_CHECKS = {name: (os.path.join(HERE, name + "_check.cpp"), os.path.join(PKG, name + "_check")) for name in (
+    "fused",                  # the fused training step (+ one extend, + timed steps: bench_legs.py runs it by path)
+    "fused_depth",            # ... with LiDAR depth supervision
+    "fused_depth_pose",       # the camera-pose gradient with LiDAR depth supervision
+    "fused_prune",            # prune between steps
+    "fused_contribution",     # contribution statistics, carried through prune
+    "fused_densify",          # the error score and densify between steps
+    "fused_weighted",         # the step and the pose gradient under a per-pixel weight image
+    "fused_resort",           # resort and the set_resort_fraction rule, through extend and prune
+    "fused_gradient_stats",   # gradient statistics, carried through densify, prune and resort
+    "fused_free_space",       # free-space statistics, carried through prune and resort
+    "fused_rows",             # both statistics objects at once through densify, extend, prune and resort
+)}
 
 
-def build_fused_check(force=False):
-    """fused_check: the fused training step from C++ (shim/include/gslic_fused.h + fused_check.cpp) — LibTorch and libgslic_hip.so only,
-    no reference source, so it builds anywhere this repository does."""
-    return _build_fused_program(os.path.join(HERE, "fused_check.cpp"), CHECK_FUSED, force)
-
-
-def build_fused_depth_check(force=False):
-    """fused_depth_check: the fused training step with LiDAR depth supervision from C++ (gslic::FusedStep::step with gt_depth) — built like
-    fused_check."""
-    return _build_fused_program(os.path.join(HERE, "fused_depth_check.cpp"), CHECK_FUSED_DEPTH, force)
-
-
-def build_fused_depth_pose_check(force=False):
-    """fused_depth_pose_check: the camera-pose gradient with LiDAR depth supervision from C++ (gslic::FusedStep::pose_gradient with gt_depth) —
-    built like fused_check."""
-    return _build_fused_program(os.path.join(HERE, "fused_depth_pose_check.cpp"), CHECK_FUSED_DEPTH_POSE, force)
-
-
-def build_fused_prune_check(force=False):
-    """fused_prune_check: pruning the map from C++ (gslic::FusedStep::prune between fused steps) — built like fused_check."""
-    return _build_fused_program(os.path.join(HERE, "fused_prune_check.cpp"), CHECK_FUSED_PRUNE, force)
-
-
-def build_fused_contribution_check(force=False):
-    """fused_contribution_check: contribution statistics from C++ (gslic::FusedStep::accumulate_contribution, carried through prune) — built like
-    fused_check."""
-    return _build_fused_program(os.path.join(HERE, "fused_contribution_check.cpp"), CHECK_FUSED_CONTRIBUTION, force)
-
-
-def build_fused_densify_check(force=False):
-    """fused_densify_check: densification from C++ (gslic::FusedStep::accumulate_contribution with an error image, gslic::FusedStep::densify
-    between fused steps) — built like fused_check."""
-    return _build_fused_program(os.path.join(HERE, "fused_densify_check.cpp"), CHECK_FUSED_DENSIFY, force)
-
-
-def build_fused_weighted_check(force=False):
-    """fused_weighted_check: the fused training step and the pose gradient under a per-pixel weight image from C++ (gslic::FusedStep::step /
-    pose_gradient with weight) — built like fused_check."""
-    return _build_fused_program(os.path.join(HERE, "fused_weighted_check.cpp"), CHECK_FUSED_WEIGHTED, force)
-
-
-def build_fused_resort_check(force=False):
-    """fused_resort_check: keeping the map in Morton order from C++ (gslic::FusedStep::resort and the set_resort_fraction rule, through extend
-    and prune, between fused steps) — built like fused_check."""
-    return _build_fused_program(os.path.join(HERE, "fused_resort_check.cpp"), CHECK_FUSED_RESORT, force)
-
-
-def build_fused_gradient_stats_check(force=False):
-    """fused_gradient_stats_check: the gradient densification statistics from C++ (gslic::GradientStats, gslic::FusedStep::set_gradient_stats,
-    carried through densify, prune and resort between fused steps) — built like fused_check."""
-    return _build_fused_program(os.path.join(HERE, "fused_gradient_stats_check.cpp"), CHECK_FUSED_GRADIENT_STATS, force)
-
-
-def build_fused_free_space_check(force=False):
-    """fused_free_space_check: the free-space statistics from C++ (gslic::FusedStep::accumulate_free_space, carried through prune and resort
-    between fused steps) — built like fused_check."""
-    return _build_fused_program(os.path.join(HERE, "fused_free_space_check.cpp"), CHECK_FUSED_FREE_SPACE, force)
-
-
-def _build_fused_program(src, CHECK_FUSED, force):
+def build_fused_check(name="fused", force=False):
+    """Builds the program `name` of FUSED_CHECKS (stale when its source, shim/fused_check_io.h, gslic_fused.h, gslic_hip.h or libgslic_hip.so is
+    newer) and returns the binary's path."""
     import sysconfig
     import torch
     from torch.utils import cpp_extension
-    newest = max(os.path.getmtime(src), os.path.getmtime(os.path.join(HERE, "include", "gslic_fused.h")),
-                 os.path.getmtime(os.path.join(PKG, "..", "include", "gslic_hip.h")), os.path.getmtime(os.path.join(PKG, "libgslic_hip.so")))
-    if not force and os.path.exists(CHECK_FUSED) and os.path.getmtime(CHECK_FUSED) > newest:
+    src, CHECK_FUSED = FUSED_CHECKS[name]
+    deps = [src, os.path.join(HERE, "fused_check_io.h"), os.path.join(HERE, "include", "gslic_fused.h"), os.path.join(PKG, "..", "include", "gslic_hip.h"),
+            os.path.join(PKG, "libgslic_hip.so")]
+    if not force and os.path.exists(CHECK_FUSED) and os.path.getmtime(CHECK_FUSED) > max(os.path.getmtime(p) for p in deps):
         return CHECK_FUSED
     tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
     cmd = ["g++", "-O1", "-std=c++17", "-w", f"-D_GLIBCXX_USE_CXX11_ABI={int(torch._C._GLIBCXX_USE_CXX11_ABI)}"] + STREAM_FLAGS
@@ -192,6 +142,15 @@ def _build_fused_program(src, CHECK_FUSED, force):
     return CHECK_FUSED
 
 
+def __getattr__(attr):
+    """The one-builder-per-program names this module had before the table (build_fused_resort_check(force) and the like): callers written
+    against them get build_fused_check(name, force)."""
+    name = attr[len("build_"):-len("_check")] if attr.startswith("build_") and attr.endswith("_check") else None
+    if name in FUSED_CHECKS:
+        return lambda force=False: build_fused_check(name, force)
+    raise AttributeError(f"module 'build_shim' has no attribute {attr!r}")
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))
     print(build_dropin_check(force="--force" in sys.argv))
@@ -199,13 +158,5 @@ if __name__ == "__main__":
     print(build_dropin_check(force="--force" in sys.argv, groups="dist"))
     for g in ("render_ref", "render", "render_loss", "render_refhost"):
         print(build_dropin_check(force="--force" in sys.argv, groups=g))
-    print(build_fused_check(force="--force" in sys.argv))
-    print(build_fused_depth_check(force="--force" in sys.argv))
-    print(build_fused_depth_pose_check(force="--force" in sys.argv))
-    print(build_fused_prune_check(force="--force" in sys.argv))
-    print(build_fused_contribution_check(force="--force" in sys.argv))
-    print(build_fused_densify_check(force="--force" in sys.argv))
-    print(build_fused_weighted_check(force="--force" in sys.argv))
-    print(build_fused_resort_check(force="--force" in sys.argv))
-    print(build_fused_gradient_stats_check(force="--force" in sys.argv))
-    print(build_fused_free_space_check(force="--force" in sys.argv))
+    for name in FUSED_CHECKS:
+        print(build_fused_check(name, force="--force" in sys.argv))

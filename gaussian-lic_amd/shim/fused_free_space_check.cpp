@@ -10,30 +10,12 @@
 // <iters> steps.  Writes the raw bytes of all 19 arrays — out_{xyz,dc,rest,opacity,scaling,rotation}.f32, out_m_<name>.f32, out_v_<name>.f32,
 // out_tie.i32 — of the five accumulators out_{max_w,n_pix}.i32, out_{sum_w,free_sum,meas_sum}.i64, of out_mask.u8, out_kept.i64 and
 // out_perm.i64, printing "free space pruned <r> size <P'>".  LibTorch and libgslic_hip.so only.
-#include "gslic_fused.h"
+#include "fused_check_io.h"
 
 #include <cmath>
-#include <fstream>
-#include <iostream>
-#include <string>
-#include <vector>
 
-static torch::Tensor load(const std::string& path, std::vector<int64_t> shape)
-{
-    int64_t n = 1;
-    for (auto s : shape) n *= s;
-    std::vector<float> buf(n);
-    std::ifstream f(path, std::ios::binary);
-    TORCH_CHECK(f.good(), "cannot open ", path);
-    f.read(reinterpret_cast<char*>(buf.data()), n * sizeof(float));
-    return torch::from_blob(buf.data(), shape, torch::kFloat32).clone().to(torch::kCUDA);
-}
-static void save_raw(const std::string& path, const torch::Tensor& t)   // the tensor's bytes as they are
-{
-    torch::Tensor c = t.detach().to(torch::kCPU).contiguous();
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(c.data_ptr()), (std::streamsize)c.nbytes());
-}
+using namespace check_io;
+
 static double fixed_to_weight(uint64_t q) { return (double)(q >> 32) + (double)(q & 0xffffffffull) / 4294967296.0; }   // trainer.fixed_to_weight
 
 // trainer.contribution_floater_mask: measured >= round(min_measured 2^32) (unsigned), measured != 0, free_weight > fraction * measured_weight
@@ -57,24 +39,11 @@ int main(int argc, char** argv)
     const int deg = std::stoi(argv[5]), iters = std::stoi(argv[6]);
     const float w_min = std::stof(argv[7]);
     const double fraction = std::stod(argv[8]), min_measured = std::stod(argv[9]);
-    const int64_t M = deg > 0 ? 15 : 0;
-    torch::Tensor xyz = load(d + "/xyz.f32", {P, 3}), scaling = load(d + "/scaling.f32", {P, 3}), rotation = load(d + "/rotation.f32", {P, 4});
-    torch::Tensor opacity = load(d + "/opacity.f32", {P, 1}), dc = load(d + "/dc.f32", {P, 1, 3});
-    torch::Tensor rest = M > 0 ? load(d + "/rest.f32", {P, M, 3}) : torch::zeros({P, 0, 3}, torch::kCUDA);
-    torch::Tensor sc = load(d + "/scalars.f32", {6}).to(torch::kCPU);
-    const float* s = sc.data_ptr<float>();
-    gslic::FusedCamera cam[2];
-    const char* tag[2] = {"", "2"};
-    for (int c = 0; c < 2; c++) {
-        cam[c].image_width = (int)W; cam[c].image_height = (int)H;
-        cam[c].world_view_transform = load(d + "/view" + tag[c] + ".f32", {4, 4}); cam[c].full_proj_transform = load(d + "/proj" + tag[c] + ".f32", {4, 4});
-        cam[c].camera_center = load(d + "/campos" + tag[c] + ".f32", {3});
-        cam[c].tanfovx = s[0]; cam[c].tanfovy = s[1]; cam[c].limx_neg = s[2]; cam[c].limx_pos = s[3]; cam[c].limy_neg = s[4]; cam[c].limy_pos = s[5];
-    }
+    const Inputs in = read_inputs(d, P, W, H, deg);
+    const gslic::FusedCamera cam[2] = {in.cam, read_camera(d, W, H, in.scalars.data(), "2")};
     torch::Tensor gt = load(d + "/gt.f32", {3, H, W}), near1 = load(d + "/near1.f32", {H, W}), near2 = load(d + "/near2.f32", {H, W});
 
-    // trainingSetup (gaussian.cpp:399-418) with config/fastlivo.yaml learning rates
-    gslic::FusedStep fs({xyz, dc, rest, opacity, scaling, rotation}, {1.6e-4f, 2.5e-3f, (float)(2.5e-3 / 20.0), 5e-2f, 5e-3f, 1e-3f}, deg);
+    gslic::FusedStep fs = make_step(in, deg);
     auto steps = [&]() {
         for (int it = 0; it < iters; it++) {
             torch::Tensor terms = fs.step(cam[0], gt);
@@ -93,15 +62,8 @@ int main(int argc, char** argv)
     TORCH_CHECK(fs.tie_rank().defined() && st.views == 3);
     steps();
     std::cout << "free space pruned " << removed << " size " << fs.size() << std::endl;
-    const char* names[6] = {"xyz", "dc", "rest", "opacity", "scaling", "rotation"};
-    for (int g = 0; g < 6; g++) {
-        if (g == 2 && M == 0) continue;
-        save_raw(d + "/out_" + names[g] + ".f32", fs.param(g));
-        save_raw(d + "/out_m_" + names[g] + ".f32", fs.exp_avg(g));
-        save_raw(d + "/out_v_" + names[g] + ".f32", fs.exp_avg_sq(g));
-    }
+    dump_rows(fs, d);
     const int64_t Pn = fs.size();
-    save_raw(d + "/out_tie.i32", fs.tie_rank());
     save_raw(d + "/out_max_w.i32", st.max_w.narrow(0, 0, Pn)); save_raw(d + "/out_n_pix.i32", st.n_pix.narrow(0, 0, Pn));
     save_raw(d + "/out_sum_w.i64", st.sum_w.narrow(0, 0, Pn)); save_raw(d + "/out_free_sum.i64", st.free_sum.narrow(0, 0, Pn));
     save_raw(d + "/out_meas_sum.i64", st.meas_sum.narrow(0, 0, Pn));

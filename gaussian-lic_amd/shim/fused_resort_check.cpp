@@ -9,29 +9,9 @@
 // prune() with the two limits (activated domain); resort(); <iters> steps.  Writes the raw bytes of all 19 arrays —
 // out_{xyz,dc,rest,opacity,scaling,rotation}.f32, out_m_<name>.f32, out_v_<name>.f32, out_tie.i32 — of out_err_sum.i64 and of the three
 // permutations out_perm{0,1,2}.i64, printing "resort extended <k> resorts <n> pruned <r> size <P'>".  LibTorch and libgslic_hip.so only.
-#include "gslic_fused.h"
+#include "fused_check_io.h"
 
-#include <fstream>
-#include <iostream>
-#include <string>
-#include <vector>
-
-static torch::Tensor load(const std::string& path, std::vector<int64_t> shape)
-{
-    int64_t n = 1;
-    for (auto s : shape) n *= s;
-    std::vector<float> buf(n);
-    std::ifstream f(path, std::ios::binary);
-    TORCH_CHECK(f.good(), "cannot open ", path);
-    f.read(reinterpret_cast<char*>(buf.data()), n * sizeof(float));
-    return torch::from_blob(buf.data(), shape, torch::kFloat32).clone().to(torch::kCUDA);
-}
-static void save_raw(const std::string& path, const torch::Tensor& t)   // the tensor's bytes as they are
-{
-    torch::Tensor c = t.detach().to(torch::kCPU).contiguous();
-    std::ofstream f(path, std::ios::binary);
-    f.write(reinterpret_cast<const char*>(c.data_ptr()), (std::streamsize)c.nbytes());
-}
+using namespace check_io;
 
 int main(int argc, char** argv)
 {
@@ -42,22 +22,14 @@ int main(int argc, char** argv)
     const int64_t n_pts = std::stoll(argv[7]);
     const double fraction = std::stod(argv[8]), min_opacity = std::stod(argv[9]), max_scale = std::stod(argv[10]);
     const float w_min = std::stof(argv[11]);
-    const int64_t M = deg > 0 ? 15 : 0;
-    torch::Tensor xyz = load(d + "/xyz.f32", {P, 3}), scaling = load(d + "/scaling.f32", {P, 3}), rotation = load(d + "/rotation.f32", {P, 4});
-    torch::Tensor opacity = load(d + "/opacity.f32", {P, 1}), dc = load(d + "/dc.f32", {P, 1, 3});
-    torch::Tensor rest = M > 0 ? load(d + "/rest.f32", {P, M, 3}) : torch::zeros({P, 0, 3}, torch::kCUDA);
-    gslic::FusedCamera cam;
-    cam.image_width = (int)W; cam.image_height = (int)H;
-    cam.world_view_transform = load(d + "/view.f32", {4, 4}); cam.full_proj_transform = load(d + "/proj.f32", {4, 4}); cam.camera_center = load(d + "/campos.f32", {3});
+    const Inputs in = read_inputs(d, P, W, H, deg, 10);
+    const gslic::FusedCamera& cam = in.cam;
+    const float* s = in.scalars.data();
     torch::Tensor gt = load(d + "/gt.f32", {3, H, W}), err = load(d + "/err.f32", {H, W});
     torch::Tensor pts = load(d + "/pts.f32", {n_pts, 3}), col = load(d + "/col.f32", {n_pts, 3}), rsp = load(d + "/rsp.f32", {n_pts});
     torch::Tensor Rcw = load(d + "/Rcw.f32", {3, 3}), tcw = load(d + "/tcw.f32", {3});
-    torch::Tensor sc = load(d + "/scalars.f32", {10}).to(torch::kCPU);
-    const float* s = sc.data_ptr<float>();
-    cam.tanfovx = s[0]; cam.tanfovy = s[1]; cam.limx_neg = s[2]; cam.limx_pos = s[3]; cam.limy_neg = s[4]; cam.limy_pos = s[5];
 
-    // trainingSetup (gaussian.cpp:399-418) with config/fastlivo.yaml learning rates
-    gslic::FusedStep fs({xyz, dc, rest, opacity, scaling, rotation}, {1.6e-4f, 2.5e-3f, (float)(2.5e-3 / 20.0), 5e-2f, 5e-3f, 1e-3f}, deg);
+    gslic::FusedStep fs = make_step(in, deg);
     auto steps = [&]() {
         for (int it = 0; it < iters; it++) {
             torch::Tensor terms = fs.step(cam, gt);
@@ -82,14 +54,7 @@ int main(int argc, char** argv)
     const torch::Tensor perm2 = fs.resort(&st);
     steps();
     std::cout << "resort extended " << k << " resorts " << resorts << " pruned " << removed << " size " << fs.size() << std::endl;
-    const char* names[6] = {"xyz", "dc", "rest", "opacity", "scaling", "rotation"};
-    for (int g = 0; g < 6; g++) {
-        if (g == 2 && M == 0) continue;
-        save_raw(d + "/out_" + names[g] + ".f32", fs.param(g));
-        save_raw(d + "/out_m_" + names[g] + ".f32", fs.exp_avg(g));
-        save_raw(d + "/out_v_" + names[g] + ".f32", fs.exp_avg_sq(g));
-    }
-    save_raw(d + "/out_tie.i32", fs.tie_rank());
+    dump_rows(fs, d);
     save_raw(d + "/out_err_sum.i64", st.err_sum.narrow(0, 0, fs.size()));
     save_raw(d + "/out_perm0.i64", perm0); save_raw(d + "/out_perm1.i64", perm1); save_raw(d + "/out_perm2.i64", perm2);
     return 0;

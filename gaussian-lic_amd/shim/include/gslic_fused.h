@@ -20,6 +20,11 @@
 //   float loss = fs.loss_value(terms, lambda_depth);
 // issues gslic_rasterize_forward_depth, the two loss calls, gslic_depth_l1_loss_forward_backward and gslic_rasterize_backward_depth_adam — the
 // calls of the Python host's training_step_fused(gt_depth=, lambda_depth=), so the two agree bit for bit (tests/test_depth_fused_gpu.py).
+//
+// Per-row statistics (ContributionStats, GradientStats) follow the map's rows the way the Python host's _RowStatistics do: each object lists its
+// arrays ONCE (rows(): tensor, scalar type, row width in dwords, created only when asked for), and the four row changes — prune, extend, densify,
+// resort — walk the lists of the objects they carry (the ContributionStats* argument when it holds anything, the attached GradientStats) with four
+// operations: fit to capacity, gather, zero rows, append to the permute list.  A new array is a field, an entry in its list and its accumulate call.
 #pragma once
 #include <torch/torch.h>
 
@@ -42,10 +47,18 @@ struct FusedCamera {
     torch::Tensor world_view_transform, full_proj_transform, camera_center;  // device fp32 [4,4] (stored transposed, camera.h:86,109), [4,4], [3]
 };
 
+// One per-row array of a statistics object, as the row changes of FusedStep see it
+struct StatRow {
+    torch::Tensor* array;     // [capacity] on the map's device, indexed by storage row
+    torch::ScalarType type;
+    uint32_t width;           // row width in dwords: 1 or 2
+    bool lazy;                // exists only once an accumulate call asked for it; until then the row changes pass over it
+};
+
 // Per-Gaussian contribution statistics accumulated over views (gslic_contribution_accumulate, include/gslic_hip.h) — the Python host's
-// trainer.ContributionStats as plain data: three device arrays indexed by storage row, created (zero) and grown to the map's capacity by
-// FusedStep::accumulate_contribution, carried through FusedStep::prune when handed to it.  Rows behind size() are zero, so rows appended by
-// extend() start at zero.  max_w.view(kFloat32) is the largest weight; sum in float units = sum_w / 2^32.
+// trainer.ContributionStats as plain data: device arrays indexed by storage row, created (zero) and grown to the map's capacity by
+// FusedStep::accumulate_contribution, carried through the row changes of FusedStep when handed to them.  Rows behind size() are zero, so rows
+// appended by extend() start at zero.  max_w.view(kFloat32) is the largest weight; sum in float units = sum_w / 2^32.
 struct ContributionStats {
     torch::Tensor max_w;   // int32 [capacity]: uint32 float bits of the largest w = alpha T
     torch::Tensor n_pix;   // int32 [capacity]: uint32 count of (pixel, view) pairs with w >= w_min (saturating)
@@ -54,6 +67,12 @@ struct ContributionStats {
     torch::Tensor free_sum; // int64 [capacity]: uint64 sum of w over the measured pixels the row lies in front of (z_g < near_bound[p]), 32.32 fixed point
     torch::Tensor meas_sum; // int64 [capacity]: uint64 sum of w over the measured pixels (near_bound[p] > 0) — both undefined until accumulate_free_space
     int64_t views = 0;
+    bool defined() const { return max_w.defined(); }   // an object no view was accumulated into is not carried
+    std::vector<StatRow> rows()
+    {
+        return {{&max_w, torch::kInt32, 1u, false}, {&n_pix, torch::kInt32, 1u, false}, {&sum_w, torch::kInt64, 2u, false},
+                {&err_sum, torch::kInt64, 2u, true}, {&free_sum, torch::kInt64, 2u, true}, {&meas_sum, torch::kInt64, 2u, true}};
+    }
 };
 
 // The gradient densification statistics of 3DGS accumulated over views (gslic_grad_stats, include/gslic_hip.h) — the Python host's
@@ -66,7 +85,9 @@ struct GradientStats {
     torch::Tensor n_seen;       // int32 [capacity]: uint32 count
     torch::Tensor max_radius;   // int32 [capacity]
     bool defined() const { return grad_sum.defined(); }
+    std::vector<StatRow> rows() { return {{&grad_sum, torch::kFloat32, 1u, false}, {&n_seen, torch::kInt32, 1u, false}, {&max_radius, torch::kInt32, 1u, false}}; }
     void reset() { if (defined()) { grad_sum.zero_(); n_seen.zero_(); max_radius.zero_(); } }
+    gslic_grad_stats descriptor() { return {grad_sum.data_ptr<float>(), reinterpret_cast<uint32_t*>(n_seen.data_ptr<int32_t>()), max_radius.data_ptr<int32_t>()}; }   // what the backward takes
     // bool [P] for FusedStep::densify: n_seen >= max(min_seen, 1) and grad_sum >= float(grad_above) * float(n_seen) — comparisons and one float32
     // product, the Python host's grow_mask (3DGS's >= is kept; a NaN sum does not grow)
     torch::Tensor grow_mask(int64_t P, float grad_above, int64_t min_seen = 1) const
@@ -117,7 +138,7 @@ public:
     void set_gradient_stats(GradientStats* stats)
     {
         gstats_ = stats;
-        if (gstats_) fit_gradient_stats(capacity());
+        if (gstats_) fit_rows(gstats_->rows());
     }
     // A host that keeps the map's rows in a PERMUTED order (e.g. sorted along a space-filling curve so that what a view sees is contiguous in
     // memory) passes the rows' ORIGINAL indices (device int32 [P]): the forward then lists Gaussians of equal depth in the original order, as the
@@ -163,16 +184,7 @@ public:
             add(prm_[g], w); add(m_[g], w); add(v_[g], w);
         }
         add(tie_, 1u);
-        if (stats && stats->max_w.defined()) {
-            fit_stats(*stats, capacity(), false);
-            add(stats->max_w, 1u); add(stats->n_pix, 1u); add(stats->sum_w, 2u);
-            if (stats->err_sum.defined()) add(stats->err_sum, 2u);
-            if (stats->free_sum.defined()) { add(stats->free_sum, 2u); add(stats->meas_sum, 2u); }
-        }
-        if (gstats_) {
-            fit_gradient_stats(capacity());
-            add(gstats_->grad_sum, 1u); add(gstats_->n_seen, 1u); add(gstats_->max_radius, 1u);
-        }
+        for (const auto& list : carried(stats)) permute_rows(list, rows);
         const size_t bytes = gslic_permute_rows_staging_bytes(rows.data(), (int32_t)rows.size(), (int32_t)P);
         torch::Tensor staging = torch::empty({(int64_t)bytes}, io.dtype(torch::kByte));
         check(gslic_permute_rows(rows.data(), (int32_t)rows.size(), reinterpret_cast<const uint32_t*>(perm.data_ptr<int32_t>()), (int32_t)P, staging.data_ptr(),
@@ -196,7 +208,8 @@ public:
     // instead of the reference's six torch::cat of every parameter and moment (densificationPostfix, :426-497).  After a call that
     // returned k > 0 the six parameter tensors are NEW views: fetch them with param(i).
     //   points, colors [n,3], depths_rsp [n]: device fp32; R_cw [3,3] row-major, t_cw [3] (any device); returns the number inserted.
-    // stats: contribution statistics of this map — only read when the append triggers the re-sort rule (set_resort_fraction), which permutes them.
+    // stats: contribution statistics of this map — grown with it (the appended rows are zero) and permuted when the append triggers the re-sort rule
+    // (set_resort_fraction).
     int64_t extend(const FusedCamera& cam, const torch::Tensor& points, const torch::Tensor& colors, const torch::Tensor& depths_rsp,
                    const torch::Tensor& R_cw, const torch::Tensor& t_cw, float fx, float fy, float cx, float cy, float scaling_scale = 1.0f,
                    ContributionStats* stats = nullptr)
@@ -211,11 +224,7 @@ public:
         torch::Tensor rot = torch::nn::functional::normalize(prm_[5]).contiguous();
         torch::Tensor final_T = torch::empty({H, W}, fo), color = torch::empty({3, H, W}, fo), radii = torch::empty({P}, fo.dtype(torch::kInt32));
         int32_t R = 0, B = 0;
-        check(gslic_rasterize_forward(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), f(prm_[0]),
-                                      f(prm_[1]), f(prm_[2]), nullptr, f(op), f(sc), f(rot), nullptr, f(cam.world_view_transform),
-                                      f(cam.full_proj_transform), f(cam.camera_center), color.data_ptr<float>(), final_T.data_ptr<float>(),
-                                      radii.data_ptr<int32_t>(), &R, &B, current_stream()),
-              "gslic_rasterize_forward (no_color)");
+        forward(rp, cam, f(op), f(sc), f(rot), color, final_T, nullptr, radii, R, B);
         torch::Tensor pts = points.to(fo).contiguous(), col = colors.to(fo).contiguous(), rsp = depths_rsp.to(fo).contiguous();
         torch::Tensor Rc = R_cw.to(fo).contiguous(), tc = t_cw.to(fo).contiguous();
         torch::Tensor sel_scratch = torch::empty({0}, fo.dtype(torch::kByte));
@@ -237,10 +246,7 @@ public:
         }
         if (tie_.defined()) tie_ = torch::cat({tie_, torch::arange(P, P + count, tie_.options())});
         bind(P + count);
-        if (gstats_) {   // appended rows have been seen by no view yet
-            fit_gradient_stats(capacity());
-            for (torch::Tensor* t : {&gstats_->grad_sum, &gstats_->n_seen, &gstats_->max_radius}) t->narrow(0, P, count).zero_();
-        }
+        for (const auto& list : carried(stats)) zero_rows(list, P, count);   // appended rows have been seen by no view yet
         torch::cuda::synchronize();   // (the selection scratch is released on return)
         rows_appended(stats);
         return count;
@@ -299,38 +305,7 @@ public:
         buf_ = nb; mbuf_ = nm; vbuf_ = nv;
         bind(count);
         sorted_P_ = below;   // the kept rows below the old bound of the sorted block
-        if (stats && stats->max_w.defined()) {
-            ContributionStats old = *stats;
-            stats->max_w = torch::zeros({cap}, io); stats->n_pix = torch::zeros({cap}, io); stats->sum_w = torch::zeros({cap}, io.dtype(torch::kInt64));
-            if (old.err_sum.defined()) stats->err_sum = torch::zeros({cap}, io.dtype(torch::kInt64));
-            if (old.free_sum.defined()) { stats->free_sum = torch::zeros({cap}, io.dtype(torch::kInt64)); stats->meas_sum = torch::zeros({cap}, io.dtype(torch::kInt64)); }
-            if (count > 0) {
-                TORCH_CHECK(old.max_w.size(0) >= P && old.n_pix.size(0) >= P && old.sum_w.size(0) >= P && (!old.err_sum.defined() || old.err_sum.size(0) >= P) &&
-                                (!old.free_sum.defined() || (old.free_sum.size(0) >= P && old.meas_sum.size(0) >= P)),
-                            "FusedStep::prune: the statistics hold fewer rows than the map");
-                std::vector<gslic_row_array> sr = {{old.max_w.data_ptr(), stats->max_w.data_ptr(), 1u}, {old.n_pix.data_ptr(), stats->n_pix.data_ptr(), 1u},
-                                                   {old.sum_w.data_ptr(), stats->sum_w.data_ptr(), 2u}};
-                if (old.err_sum.defined()) sr.push_back({old.err_sum.data_ptr(), stats->err_sum.data_ptr(), 2u});
-                if (old.free_sum.defined()) {
-                    sr.push_back({old.free_sum.data_ptr(), stats->free_sum.data_ptr(), 2u});
-                    sr.push_back({old.meas_sum.data_ptr(), stats->meas_sum.data_ptr(), 2u});
-                }
-                check(gslic_gather_rows(sr.data(), (int32_t)sr.size(), reinterpret_cast<const uint32_t*>(kept.data_ptr<int32_t>()), count, current_stream()),
-                      "gslic_gather_rows (statistics)");
-            }
-        }
-        if (gstats_ && gstats_->defined()) {   // the gradient statistics follow their rows: the same gather, on the same kept index
-            GradientStats old = *gstats_;
-            TORCH_CHECK(old.grad_sum.size(0) >= P && old.n_seen.size(0) >= P && old.max_radius.size(0) >= P,
-                        "FusedStep::prune: the gradient statistics hold fewer rows than the map");
-            gstats_->grad_sum = torch::zeros({cap}, io.dtype(torch::kFloat32)); gstats_->n_seen = torch::zeros({cap}, io); gstats_->max_radius = torch::zeros({cap}, io);
-            if (count > 0) {
-                std::vector<gslic_row_array> sr = {{old.grad_sum.data_ptr(), gstats_->grad_sum.data_ptr(), 1u}, {old.n_seen.data_ptr(), gstats_->n_seen.data_ptr(), 1u},
-                                                   {old.max_radius.data_ptr(), gstats_->max_radius.data_ptr(), 1u}};
-                check(gslic_gather_rows(sr.data(), (int32_t)sr.size(), reinterpret_cast<const uint32_t*>(kept.data_ptr<int32_t>()), count, current_stream()),
-                      "gslic_gather_rows (gradient statistics)");
-            }
-        }
+        for (const auto& list : carried(stats)) gather_rows(list, kept, P, count);   // the statistics follow their rows: the same gather, on the same kept index
         if (tie_.defined()) tie_ = new_tie.narrow(0, 0, count).clone();
         return kept.narrow(0, 0, count).to(torch::kInt64);
     }
@@ -352,7 +327,7 @@ public:
                         "FusedStep::accumulate_contribution: error must be a float [", H, ", ", W, "] tensor on the map's device");
             err = error.detach().to(torch::kFloat32).contiguous();
         }
-        fit_stats(stats, capacity(), err.defined());
+        if (err.defined()) fit_rows(stats.rows(), {&stats.err_sum}); else fit_rows(stats.rows());
         stats.views++;
         if (P == 0) return;
         int32_t R = 0, B = 0;
@@ -385,7 +360,7 @@ public:
                         near_bound.device() == prm_[0].device(),
                     "FusedStep::accumulate_free_space: near_bound must be a float [", H, ", ", W, "] tensor on the map's device");
         const torch::Tensor near = near_bound.detach().to(torch::kFloat32).contiguous();
-        fit_stats(stats, capacity(), false, true);
+        fit_rows(stats.rows(), {&stats.free_sum, &stats.meas_sum});
         stats.views++;
         if (P == 0) return;
         int32_t R = 0, B = 0;
@@ -433,7 +408,7 @@ public:
         if (count == 0) return torch::empty({0}, io.dtype(torch::kInt64));
         const torch::Tensor parents = parent.narrow(0, 0, count).to(torch::kInt64);
         torch::Tensor split_rows;   // which parents split, from the scaling the emission has not yet rewritten (the rule's own comparison)
-        if (((stats && stats->max_w.defined()) || gstats_) && splits > 0) split_rows = parents.masked_select(prm_[4].detach().index_select(0, parents).gt(thr).any(1));
+        if (!carried(stats).empty() && splits > 0) split_rows = parents.masked_select(prm_[4].detach().index_select(0, parents).gt(thr).any(1));
         reserve(P + count);
         if (tie_.defined()) {
             torch::Tensor nt = torch::empty({P + count}, tie_.options());
@@ -450,21 +425,8 @@ public:
                                  tie_.defined() ? reinterpret_cast<uint32_t*>(tie_.data_ptr<int32_t>()) : nullptr, thr, seed, current_stream()),
               "gslic_densify_emit");
         bind(P + count);
-        if (stats && stats->max_w.defined()) {
-            fit_stats(*stats, capacity(), false);
-            for (torch::Tensor* t : {&stats->max_w, &stats->n_pix, &stats->sum_w, &stats->err_sum, &stats->free_sum, &stats->meas_sum}) {
-                if (!t->defined()) continue;
-                t->narrow(0, P, count).zero_();
-                if (split_rows.defined()) t->index_fill_(0, split_rows, 0);
-            }
-        }
-        if (gstats_) {   // new rows and child 0 of a split have been seen by no view yet; a clone's parent is the Gaussian it was
-            fit_gradient_stats(capacity());
-            for (torch::Tensor* t : {&gstats_->grad_sum, &gstats_->n_seen, &gstats_->max_radius}) {
-                t->narrow(0, P, count).zero_();
-                if (split_rows.defined()) t->index_fill_(0, split_rows, 0);
-            }
-        }
+        // new rows and child 0 of a split have contributed to nothing and been seen by no view yet; a clone's parent is the Gaussian it was
+        for (const auto& list : carried(stats)) zero_rows(list, P, count, split_rows);
         if (n_split) *n_split = splits;
         rows_appended(stats);   // (parents are the rows BEFORE a re-sort, as the Python host returns them)
         return parents;
@@ -583,22 +545,44 @@ private:
     {
         if (!radii_.defined() || radii_.size(0) != P) radii_ = torch::empty({P}, prm_[0].options().requires_grad(false).dtype(torch::kInt32));
     }
-    // the weighted colour loss of a step: the three launches, then terms[0:2] <- the weighted means (S stays in wterms_[2]: weight_sum())
-    void weighted_loss(int H, int W, const torch::Tensor& image, const torch::Tensor& gt_image, const torch::Tensor& weight, torch::Tensor& d1,
-                       torch::Tensor& d2, torch::Tensor& d3, torch::Tensor& terms, torch::Tensor& dL)
+    // The colour loss of a view, forward and backward: terms[0:2] and dL.  weight: the weighted loss (its three launches, then terms[0:2] <- the
+    // weighted means; S stays in wterms_[2]: weight_sum()).  Otherwise the fused pair of launches — the reduction of the partial sums rides on the
+    // backward kernel — or, two_calls, gslic_l1_ssim_loss_forward + _backward: the colour-only pose gradient, as it always ran.
+    void colour_loss(int H, int W, const torch::Tensor& image, const torch::Tensor& gt_image, const torch::Tensor* weight, torch::Tensor (&dm)[3],
+                     torch::Tensor& partials, torch::Tensor& terms, torch::Tensor& dL, bool two_calls = false)
     {
-        TORCH_CHECK(weight.is_contiguous() && weight.scalar_type() == torch::kFloat32 && weight.dim() == 2 && weight.size(0) == H && weight.size(1) == W,
-                    "weight must be contiguous fp32 [H,W]");
-        auto fo = prm_[0].options().requires_grad(false);
-        const int64_t n = gslic_l1_ssim_loss_weighted_partials_count(3, H, W);
-        if (!wpartials_.defined() || wpartials_.size(0) != n) wpartials_ = torch::empty({n}, fo);
-        if (!wterms_.defined()) wterms_ = torch::zeros({3}, fo);
         const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;   // loss_utils.h:187-188
-        check(gslic_l1_ssim_loss_weighted_forward_backward(3, H, W, C1, C2, lambda_dssim_, f(image), f(gt_image), f(weight), d1.data_ptr<float>(),
-                                                           d2.data_ptr<float>(), d3.data_ptr<float>(), wpartials_.data_ptr<float>(), wterms_.data_ptr<float>(),
-                                                           dL.data_ptr<float>(), current_stream()),
-              "gslic_l1_ssim_loss_weighted_forward_backward");
-        terms.slice(0, 0, 2).copy_(wterms_.slice(0, 0, 2));
+        float *d1 = dm[0].data_ptr<float>(), *d2 = dm[1].data_ptr<float>(), *d3 = dm[2].data_ptr<float>();
+        if (weight) {
+            TORCH_CHECK(weight->is_contiguous() && weight->scalar_type() == torch::kFloat32 && weight->dim() == 2 && weight->size(0) == H && weight->size(1) == W,
+                        "weight must be contiguous fp32 [H,W]");
+            auto fo = prm_[0].options().requires_grad(false);
+            const int64_t n = gslic_l1_ssim_loss_weighted_partials_count(3, H, W);
+            if (!wpartials_.defined() || wpartials_.size(0) != n) wpartials_ = torch::empty({n}, fo);
+            if (!wterms_.defined()) wterms_ = torch::zeros({3}, fo);
+            check(gslic_l1_ssim_loss_weighted_forward_backward(3, H, W, C1, C2, lambda_dssim_, f(image), f(gt_image), f(*weight), d1, d2, d3,
+                                                               wpartials_.data_ptr<float>(), wterms_.data_ptr<float>(), dL.data_ptr<float>(), current_stream()),
+                  "gslic_l1_ssim_loss_weighted_forward_backward");
+            terms.slice(0, 0, 2).copy_(wterms_.slice(0, 0, 2));
+        } else if (two_calls) {
+            check(gslic_l1_ssim_loss_forward(1, 3, H, W, C1, C2, f(image), f(gt_image), d1, d2, d3, partials.data_ptr<float>(), terms.data_ptr<float>(),
+                                             current_stream()),
+                  "gslic_l1_ssim_loss_forward");
+            check(gslic_l1_ssim_loss_backward(1, 3, H, W, lambda_dssim_, f(image), f(gt_image), d1, d2, d3, dL.data_ptr<float>(), current_stream()),
+                  "gslic_l1_ssim_loss_backward");
+        } else {
+            check(gslic_l1_ssim_loss_forward_backward(1, 3, H, W, C1, C2, lambda_dssim_, f(image), f(gt_image), d1, d2, d3, partials.data_ptr<float>(),
+                                                      terms.data_ptr<float>(), dL.data_ptr<float>(), current_stream()),
+                  "gslic_l1_ssim_loss_forward_backward");
+        }
+    }
+    // the depth loss of a view, forward and backward: terms[2] and dLd
+    void depth_loss(int H, int W, float lambda_depth, const torch::Tensor& depth, const torch::Tensor& gt_depth, torch::Tensor& partials, torch::Tensor& terms,
+                    torch::Tensor& dLd)
+    {
+        check(gslic_depth_l1_loss_forward_backward(H, W, lambda_depth, f(depth), f(gt_depth), partials.data_ptr<float>(), terms.data_ptr<float>() + 2,
+                                                   dLd.data_ptr<float>(), current_stream()),
+              "gslic_depth_l1_loss_forward_backward");
     }
     static void check_targets(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor* gt_depth)
     {
@@ -608,7 +592,74 @@ private:
                                   gt_depth->size(0) == H && gt_depth->size(1) == W), "gt_depth must be contiguous fp32 [H,W]");
     }
 
-    // the step; gt_depth != nullptr: under depth supervision (the depth forward, the depth loss, the depth backward)
+    // The forward of a view: gslic_rasterize_forward, or gslic_rasterize_forward_depth when a depth image is asked for.  op / sc / rot: opacity, scaling
+    // and rotation as rp.raw_params says (the raw parameters, or LibTorch's activations of them).  Fills scratch_[0..3] and the two counts.
+    void forward(const gslic_raster_params& rp, const FusedCamera& cam, const float* op, const float* sc, const float* rot, torch::Tensor& image,
+                 torch::Tensor& final_T, torch::Tensor* depth, torch::Tensor& radii, int32_t& R, int32_t& B)
+    {
+        const float *xyz = f(prm_[0]), *dc = f(prm_[1]), *rest = f(prm_[2]);
+        const float *view = f(cam.world_view_transform), *proj = f(cam.full_proj_transform), *cpos = f(cam.camera_center);
+        if (depth)
+            check(gslic_rasterize_forward_depth(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), xyz,
+                                                dc, rest, nullptr, op, sc, rot, nullptr, view, proj, cpos, image.data_ptr<float>(), final_T.data_ptr<float>(),
+                                                depth->data_ptr<float>(), radii.data_ptr<int32_t>(), &R, &B, current_stream()),
+                  "gslic_rasterize_forward_depth");
+        else
+            check(gslic_rasterize_forward(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), xyz, dc,
+                                          rest, nullptr, op, sc, rot, nullptr, view, proj, cpos, image.data_ptr<float>(), final_T.data_ptr<float>(),
+                                          radii.data_ptr<int32_t>(), &R, &B, current_stream()),
+                  "gslic_rasterize_forward");
+    }
+// what all six backward entry points take first: the forward's parameters, inputs and buffers, and dL/dimage
+#define GSLIC_FUSED_BACKWARD_INPUTS(radii, dL)                                                                                                                \
+    &rp, R, B, f(bg_), f(prm_[0]), f(prm_[1]), f(prm_[2]), nullptr, f(prm_[4]), f(prm_[5]), nullptr, f(cam.world_view_transform),                              \
+        f(cam.full_proj_transform), f(cam.camera_center), (radii).data_ptr<int32_t>(), cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]),              \
+        cptr(scratch_[3]), f(dL)
+    // The backward of a step with the masked Adam inside: one of the four *_adam* entry points, by whether the view is depth-supervised and whether
+    // gradient statistics are attached (the same step, which also adds this view to them).  Reads the step's own buffers.
+    void backward_adam(const gslic_raster_params& rp, const FusedCamera& cam, int32_t R, int32_t B, bool depth)
+    {
+        const gslic_adam_fused ad = adam_descriptor();
+        float* xg = depth ? xyz_grad_.data_ptr<float>() : nullptr;
+        if (gstats_) {
+            fit_rows(gstats_->rows());
+            const gslic_grad_stats gs = gstats_->descriptor();
+            if (depth)
+                check(gslic_rasterize_backward_depth_adam_stats(GSLIC_FUSED_BACKWARD_INPUTS(radii_, dL_dimage_), f(dL_ddepth_), nullptr, xg, nullptr, nullptr,
+                                                                nullptr, nullptr, lambda_erank_, &ad, &gs, current_stream()),
+                      "gslic_rasterize_backward_depth_adam_stats");
+            else
+                check(gslic_rasterize_backward_adam_stats(GSLIC_FUSED_BACKWARD_INPUTS(radii_, dL_dimage_), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                          lambda_erank_, &ad, &gs, current_stream()),
+                      "gslic_rasterize_backward_adam_stats");
+        } else if (depth) {
+            check(gslic_rasterize_backward_depth_adam(GSLIC_FUSED_BACKWARD_INPUTS(radii_, dL_dimage_), f(dL_ddepth_), nullptr, xg, nullptr, nullptr, nullptr,
+                                                      nullptr, lambda_erank_, &ad, current_stream()),
+                  "gslic_rasterize_backward_depth_adam");
+        } else {
+            check(gslic_rasterize_backward_adam(GSLIC_FUSED_BACKWARD_INPUTS(radii_, dL_dimage_), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                lambda_erank_, &ad, current_stream()),
+                  "gslic_rasterize_backward_adam");
+        }
+    }
+    // The backward of a pose gradient: the six parameter gradients into g (group order) and the camera's 16 + 16 + 3 floats into cg; with a defined dLd
+    // the depth entry point.  The map is not touched.
+    void backward_camera(const gslic_raster_params& rp, const FusedCamera& cam, int32_t R, int32_t B, torch::Tensor& radii, const torch::Tensor& dL,
+                         const torch::Tensor& dLd, std::array<torch::Tensor, 6>& g, float* cg)
+    {
+        auto w = [](torch::Tensor& t) { return t.numel() ? t.data_ptr<float>() : nullptr; };
+        if (dLd.defined())
+            check(gslic_rasterize_backward_depth_camera(GSLIC_FUSED_BACKWARD_INPUTS(radii, dL), f(dLd), nullptr, nullptr, w(g[3]), nullptr, w(g[0]), nullptr,
+                                                        w(g[1]), w(g[2]), w(g[4]), w(g[5]), lambda_erank_, cg, cg + 16, cg + 32, current_stream()),
+                  "gslic_rasterize_backward_depth_camera");
+        else
+            check(gslic_rasterize_backward_camera(GSLIC_FUSED_BACKWARD_INPUTS(radii, dL), nullptr, nullptr, w(g[3]), nullptr, w(g[0]), nullptr, w(g[1]), w(g[2]),
+                                                  w(g[4]), w(g[5]), lambda_erank_, cg, cg + 16, cg + 32, current_stream()),
+                  "gslic_rasterize_backward_camera");
+    }
+#undef GSLIC_FUSED_BACKWARD_INPUTS
+
+    // the step: forward, loss, depth loss, backward.  gt_depth != nullptr: under depth supervision
     torch::Tensor step_body(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor* gt_depth, float lambda_depth,
                             const torch::Tensor* weight)
     {
@@ -624,66 +675,16 @@ private:
         ensure_rows(P);
         if (depth && (!xyz_grad_.defined() || xyz_grad_.size(0) != P)) xyz_grad_ = torch::empty({P, 3}, fo);   // (xyz's gradient is assembled there before its update)
         torch::Tensor terms = torch::empty({depth ? 3 : 2}, fo);
-        const float *xyz = f(prm_[0]), *dc = f(prm_[1]), *rest = f(prm_[2]), *op = f(prm_[3]), *sc = f(prm_[4]), *rot = f(prm_[5]);
-        const float *view = f(cam.world_view_transform), *proj = f(cam.full_proj_transform), *cpos = f(cam.camera_center);
         int32_t R = 0, B = 0;
-        if (depth)
-            check(gslic_rasterize_forward_depth(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), xyz,
-                                                dc, rest, nullptr, op, sc, rot, nullptr, view, proj, cpos, image_.data_ptr<float>(),
-                                                final_T_.data_ptr<float>(), depth_.data_ptr<float>(), radii_.data_ptr<int32_t>(), &R, &B, current_stream()),
-                  "gslic_rasterize_forward_depth");
-        else
-            check(gslic_rasterize_forward(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), xyz, dc,
-                                          rest, nullptr, op, sc, rot, nullptr, view, proj, cpos, image_.data_ptr<float>(), final_T_.data_ptr<float>(),
-                                          radii_.data_ptr<int32_t>(), &R, &B, current_stream()),
-                  "gslic_rasterize_forward");
-        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;   // loss_utils.h:187-188
-        // (forward + backward of the loss in two launches: the reduction of the partial sums rides on the backward kernel)
-        if (weight)
-            weighted_loss(H, W, image_, gt_image, *weight, dm_[0], dm_[1], dm_[2], terms, dL_dimage_);
-        else
-        check(gslic_l1_ssim_loss_forward_backward(1, 3, H, W, C1, C2, lambda_dssim_, f(image_), f(gt_image), dm_[0].data_ptr<float>(),
-                                                  dm_[1].data_ptr<float>(), dm_[2].data_ptr<float>(), partials_.data_ptr<float>(),
-                                                  terms.data_ptr<float>(), dL_dimage_.data_ptr<float>(), current_stream()),
-              "gslic_l1_ssim_loss_forward_backward");
-        if (depth)
-            check(gslic_depth_l1_loss_forward_backward(H, W, lambda_depth, f(depth_), f(*gt_depth), depth_partials_.data_ptr<float>(),
-                                                       terms.data_ptr<float>() + 2, dL_ddepth_.data_ptr<float>(), current_stream()),
-                  "gslic_depth_l1_loss_forward_backward");
-        const gslic_adam_fused ad = adam_descriptor();
-        if (gstats_) {   // the same backward, which also adds this view to the gradient statistics
-            fit_gradient_stats(capacity());
-            const gslic_grad_stats gs{gstats_->grad_sum.data_ptr<float>(), reinterpret_cast<uint32_t*>(gstats_->n_seen.data_ptr<int32_t>()),
-                                      gstats_->max_radius.data_ptr<int32_t>()};
-            if (depth)
-                check(gslic_rasterize_backward_depth_adam_stats(&rp, R, B, f(bg_), xyz, dc, rest, nullptr, sc, rot, nullptr, view, proj, cpos,
-                                                                radii_.data_ptr<int32_t>(), cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), cptr(scratch_[3]),
-                                                                f(dL_dimage_), f(dL_ddepth_), nullptr, xyz_grad_.data_ptr<float>(), nullptr, nullptr, nullptr, nullptr,
-                                                                lambda_erank_, &ad, &gs, current_stream()),
-                      "gslic_rasterize_backward_depth_adam_stats");
-            else
-                check(gslic_rasterize_backward_adam_stats(&rp, R, B, f(bg_), xyz, dc, rest, nullptr, sc, rot, nullptr, view, proj, cpos, radii_.data_ptr<int32_t>(),
-                                                          cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), cptr(scratch_[3]), f(dL_dimage_), nullptr, nullptr,
-                                                          nullptr, nullptr, nullptr, nullptr, lambda_erank_, &ad, &gs, current_stream()),
-                      "gslic_rasterize_backward_adam_stats");
-            return terms;
-        }
-        if (depth)
-            check(gslic_rasterize_backward_depth_adam(&rp, R, B, f(bg_), xyz, dc, rest, nullptr, sc, rot, nullptr, view, proj, cpos, radii_.data_ptr<int32_t>(),
-                                                      cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), cptr(scratch_[3]), f(dL_dimage_), f(dL_ddepth_),
-                                                      nullptr, xyz_grad_.data_ptr<float>(), nullptr, nullptr, nullptr, nullptr, lambda_erank_, &ad,
-                                                      current_stream()),
-                  "gslic_rasterize_backward_depth_adam");
-        else
-            check(gslic_rasterize_backward_adam(&rp, R, B, f(bg_), xyz, dc, rest, nullptr, sc, rot, nullptr, view, proj, cpos, radii_.data_ptr<int32_t>(),
-                                                cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), cptr(scratch_[3]), f(dL_dimage_), nullptr, nullptr,
-                                                nullptr, nullptr, nullptr, nullptr, lambda_erank_, &ad, current_stream()),
-                  "gslic_rasterize_backward_adam");
+        forward(rp, cam, f(prm_[3]), f(prm_[4]), f(prm_[5]), image_, final_T_, depth ? &depth_ : nullptr, radii_, R, B);
+        colour_loss(H, W, image_, gt_image, weight, dm_, partials_, terms, dL_dimage_);
+        if (depth) depth_loss(H, W, lambda_depth, depth_, *gt_depth, depth_partials_, terms, dL_ddepth_);
+        backward_adam(rp, cam, R, B, depth);
         return terms;
     }
 
-    // the pose gradient; gt_depth != nullptr: under depth supervision.  (The colour-only path runs the loss as gslic_l1_ssim_loss_forward + _backward,
-    // the depth path as the fused pair of calls: both as they were.)
+    // the pose gradient: forward, loss, depth loss, camera backward, the chain on the host.  gt_depth != nullptr: under depth supervision.  (The
+    // colour-only path runs the unweighted loss as gslic_l1_ssim_loss_forward + _backward, every other path as the fused pair: both as they were.)
     std::array<double, 6> pose_gradient_body(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor* gt_depth, float lambda_depth,
                                              torch::Tensor* terms_out, const torch::Tensor* weight)
     {
@@ -694,58 +695,18 @@ private:
         if (depth) check_targets(cam, gt_image, gt_depth);
         const gslic_raster_params rp = raster_params(cam, true, false);
         auto fo = prm_[0].options().requires_grad(false);
-        torch::Tensor image = torch::empty({3, H, W}, fo), final_T = torch::empty({H, W}, fo), zimg, dLd, dpartials;
-        if (depth) zimg = torch::empty({H, W}, fo);
+        torch::Tensor image = torch::empty({3, H, W}, fo), final_T = torch::empty({H, W}, fo), dL = torch::empty({3, H, W}, fo), dm[3], zimg, dLd, dpartials;
+        for (torch::Tensor& d : dm) d = torch::empty({3, H, W}, fo);
+        if (depth) { zimg = torch::empty({H, W}, fo); dLd = torch::empty({H, W}, fo); dpartials = torch::empty({gslic_depth_l1_loss_partials_count(H, W)}, fo); }
         torch::Tensor radii = torch::empty({P}, fo.dtype(torch::kInt32));
-        torch::Tensor d1 = torch::empty({3, H, W}, fo), d2 = torch::empty({3, H, W}, fo), d3 = torch::empty({3, H, W}, fo), dL = torch::empty({3, H, W}, fo);
-        if (depth) { dLd = torch::empty({H, W}, fo); dpartials = torch::empty({gslic_depth_l1_loss_partials_count(H, W)}, fo); }
         torch::Tensor partials = torch::empty({gslic_loss_partials_count(1, 3, H, W)}, fo), terms = torch::empty({depth ? 3 : 2}, fo), camg = torch::zeros({35}, fo);
         std::array<torch::Tensor, 6> g;
         for (int i = 0; i < 6; i++) g[i] = torch::empty_like(prm_[i], fo);
-        const float *xyz = f(prm_[0]), *dc = f(prm_[1]), *rest = f(prm_[2]), *op = f(prm_[3]), *sc = f(prm_[4]), *rot = f(prm_[5]);
-        const float *view = f(cam.world_view_transform), *proj = f(cam.full_proj_transform), *cpos = f(cam.camera_center);
-        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-        auto w = [](torch::Tensor& t) { return t.numel() ? t.data_ptr<float>() : nullptr; };
-        float* cg = camg.data_ptr<float>();
         int32_t R = 0, B = 0;
-        if (depth) {
-            check(gslic_rasterize_forward_depth(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), xyz,
-                                                dc, rest, nullptr, op, sc, rot, nullptr, view, proj, cpos, image.data_ptr<float>(), final_T.data_ptr<float>(),
-                                                zimg.data_ptr<float>(), radii.data_ptr<int32_t>(), &R, &B, current_stream()),
-                  "gslic_rasterize_forward_depth");
-            if (weight)
-                weighted_loss(H, W, image, gt_image, *weight, d1, d2, d3, terms, dL);
-            else
-            check(gslic_l1_ssim_loss_forward_backward(1, 3, H, W, C1, C2, lambda_dssim_, f(image), f(gt_image), d1.data_ptr<float>(), d2.data_ptr<float>(),
-                                                      d3.data_ptr<float>(), partials.data_ptr<float>(), terms.data_ptr<float>(), dL.data_ptr<float>(),
-                                                      current_stream()),
-                  "gslic_l1_ssim_loss_forward_backward");
-            check(gslic_depth_l1_loss_forward_backward(H, W, lambda_depth, f(zimg), f(*gt_depth), dpartials.data_ptr<float>(), terms.data_ptr<float>() + 2,
-                                                       dLd.data_ptr<float>(), current_stream()),
-                  "gslic_depth_l1_loss_forward_backward");
-            check(gslic_rasterize_backward_depth_camera(&rp, R, B, f(bg_), xyz, dc, rest, nullptr, sc, rot, nullptr, view, proj, cpos, radii.data_ptr<int32_t>(),
-                                                        cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), cptr(scratch_[3]), f(dL), f(dLd), nullptr, nullptr,
-                                                        w(g[3]), nullptr, w(g[0]), nullptr, w(g[1]), w(g[2]), w(g[4]), w(g[5]), lambda_erank_, cg, cg + 16, cg + 32,
-                                                        current_stream()),
-                  "gslic_rasterize_backward_depth_camera");
-        } else {
-            check(gslic_rasterize_forward(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), xyz, dc, rest,
-                                          nullptr, op, sc, rot, nullptr, view, proj, cpos, image.data_ptr<float>(), final_T.data_ptr<float>(),
-                                          radii.data_ptr<int32_t>(), &R, &B, current_stream()), "gslic_rasterize_forward");
-            if (weight) {
-                weighted_loss(H, W, image, gt_image, *weight, d1, d2, d3, terms, dL);
-            } else {
-            check(gslic_l1_ssim_loss_forward(1, 3, H, W, C1, C2, f(image), f(gt_image), d1.data_ptr<float>(), d2.data_ptr<float>(), d3.data_ptr<float>(),
-                                             partials.data_ptr<float>(), terms.data_ptr<float>(), current_stream()), "gslic_l1_ssim_loss_forward");
-            check(gslic_l1_ssim_loss_backward(1, 3, H, W, lambda_dssim_, f(image), f(gt_image), f(d1), f(d2), f(d3), dL.data_ptr<float>(), current_stream()),
-                  "gslic_l1_ssim_loss_backward");
-            }
-            check(gslic_rasterize_backward_camera(&rp, R, B, f(bg_), xyz, dc, rest, nullptr, sc, rot, nullptr, view, proj, cpos, radii.data_ptr<int32_t>(),
-                                                  cptr(scratch_[0]), cptr(scratch_[1]), cptr(scratch_[2]), cptr(scratch_[3]), f(dL), nullptr, nullptr, w(g[3]),
-                                                  nullptr, w(g[0]), nullptr, w(g[1]), w(g[2]), w(g[4]), w(g[5]), lambda_erank_, cg, cg + 16, cg + 32,
-                                                  current_stream()),
-                  "gslic_rasterize_backward_camera");
-        }
+        forward(rp, cam, f(prm_[3]), f(prm_[4]), f(prm_[5]), image, final_T, depth ? &zimg : nullptr, radii, R, B);
+        colour_loss(H, W, image, gt_image, weight, dm, partials, terms, dL, /*two_calls=*/!depth);
+        if (depth) depth_loss(H, W, lambda_depth, zimg, *gt_depth, dpartials, terms, dLd);
+        backward_camera(rp, cam, R, B, radii, dL, dLd, g, camg.data_ptr<float>());
         if (terms_out) *terms_out = terms;
         torch::Tensor hc = camg.to(torch::kCPU), hv = cam.world_view_transform.to(torch::kCPU).contiguous(), hp = cam.full_proj_transform.to(torch::kCPU).contiguous();
         return se3_pose_gradient(hv.data_ptr<float>(), hp.data_ptr<float>(), hc.data_ptr<float>(), hc.data_ptr<float>() + 16, hc.data_ptr<float>() + 32);
@@ -757,11 +718,7 @@ private:
         const gslic_raster_params rp = raster_params(cam, true, false);
         ensure_image_buffers(cam.image_height, cam.image_width);
         ensure_rows(prm_[0].size(0));
-        check(gslic_rasterize_forward(&rp, grow_cb, &scratch_[0], grow_cb, &scratch_[1], grow_cb, &scratch_[2], grow_cb, &scratch_[3], f(bg_), f(prm_[0]),
-                                      f(prm_[1]), f(prm_[2]), nullptr, f(prm_[3]), f(prm_[4]), f(prm_[5]), nullptr, f(cam.world_view_transform),
-                                      f(cam.full_proj_transform), f(cam.camera_center), image_.data_ptr<float>(), final_T_.data_ptr<float>(),
-                                      radii_.data_ptr<int32_t>(), &R, &B, current_stream()),
-              "gslic_rasterize_forward");
+        forward(rp, cam, f(prm_[3]), f(prm_[4]), f(prm_[5]), image_, final_T_, nullptr, radii_, R, B);
         return rp;
     }
     // GaussianModel._rows_appended's rule: the appended tail has grown past resort_fraction of the map
@@ -770,32 +727,61 @@ private:
         const int64_t P = prm_[0].size(0);
         if (tie_.defined() && resort_fraction_ && (double)(P - sorted_P_) > *resort_fraction_ * (double)P) resort(stats);
     }
-    // the statistics' arrays, created zero-filled and grown (zero-extended) to `cap` rows; err_sum only once a view brought an error image,
-    // free_sum / meas_sum only once one brought a near-bound image
-    void fit_stats(ContributionStats& stats, int64_t cap, bool with_err, bool with_free = false)
+    // ---- The statistics objects that follow the rows, and the four operations the row changes apply to their row lists: the counterpart of the Python
+    // host's _RowStatistics.  The invariant all of them keep: in every statistics array the rows behind size() are zero — so zero-extending an array
+    // to capacity(), or zeroing rows that were just appended, never changes what an existing row holds.
+    // carried: the ContributionStats handed to the row change when it holds anything, and the attached GradientStats
+    std::vector<std::vector<StatRow>> carried(ContributionStats* stats) const
     {
-        auto io = prm_[0].options().requires_grad(false).dtype(torch::kInt32);
-        auto fit = [&](torch::Tensor& t, torch::ScalarType dt) {
-            if (t.defined() && t.size(0) >= cap) return;
-            torch::Tensor n = torch::zeros({cap}, io.dtype(dt));
-            if (t.defined()) n.narrow(0, 0, t.size(0)).copy_(t);
-            t = n;
-        };
-        fit(stats.max_w, torch::kInt32); fit(stats.n_pix, torch::kInt32); fit(stats.sum_w, torch::kInt64);
-        if (with_err || stats.err_sum.defined()) fit(stats.err_sum, torch::kInt64);
-        if (with_free || stats.free_sum.defined()) { fit(stats.free_sum, torch::kInt64); fit(stats.meas_sum, torch::kInt64); }
+        std::vector<std::vector<StatRow>> lists;
+        if (stats && stats->defined()) lists.push_back(stats->rows());
+        if (gstats_) lists.push_back(gstats_->rows());
+        return lists;
     }
-    // the gradient statistics' arrays, created zero-filled and grown (zero-extended) to `cap` rows
-    void fit_gradient_stats(int64_t cap)
+    // fit to capacity: every array created zero-filled, or zero-extended, to capacity() rows; a lazy array that does not exist only when it is `wanted`
+    void fit_rows(const std::vector<StatRow>& rows, std::initializer_list<const torch::Tensor*> wanted = {})
     {
-        auto io = prm_[0].options().requires_grad(false).dtype(torch::kInt32);
-        auto fit = [&](torch::Tensor& t, torch::ScalarType dt) {
-            if (t.defined() && t.size(0) >= cap) return;
-            torch::Tensor n = torch::zeros({cap}, io.dtype(dt));
+        const int64_t cap = capacity();
+        for (const StatRow& r : rows) {
+            torch::Tensor& t = *r.array;
+            if (t.defined() ? t.size(0) >= cap : (r.lazy && std::find(wanted.begin(), wanted.end(), r.array) == wanted.end())) continue;
+            torch::Tensor n = torch::zeros({cap}, prm_[0].options().requires_grad(false).dtype(r.type));
             if (t.defined()) n.narrow(0, 0, t.size(0)).copy_(t);
             t = n;
-        };
-        fit(gstats_->grad_sum, torch::kFloat32); fit(gstats_->n_seen, torch::kInt32); fit(gstats_->max_radius, torch::kInt32);
+        }
+    }
+    // gather (prune): fresh zero arrays of capacity(), rows [0, count) <- the old rows kept[0 .. count) in ONE gslic_gather_rows; P = the rows before
+    void gather_rows(const std::vector<StatRow>& rows, const torch::Tensor& kept, int64_t P, int32_t count)
+    {
+        std::vector<torch::Tensor> old;
+        std::vector<gslic_row_array> list;
+        for (const StatRow& r : rows) TORCH_CHECK(!r.array->defined() || r.array->size(0) >= P, "FusedStep::prune: the statistics hold fewer rows than the map");
+        for (const StatRow& r : rows) {
+            if (!r.array->defined()) continue;
+            old.push_back(*r.array);   // (alive until the launch is issued)
+            *r.array = torch::zeros({capacity()}, old.back().options());
+            list.push_back({old.back().data_ptr(), r.array->data_ptr(), r.width});
+        }
+        if (count > 0 && !list.empty())
+            check(gslic_gather_rows(list.data(), (int32_t)list.size(), reinterpret_cast<const uint32_t*>(kept.data_ptr<int32_t>()), count, current_stream()),
+                  "gslic_gather_rows (statistics)");
+    }
+    // appended / zero rows (extend, densify): rows [P, P + k) and, when given, the rows `also` (densify's split parents) start from zero
+    void zero_rows(const std::vector<StatRow>& rows, int64_t P, int64_t k, const torch::Tensor& also = torch::Tensor())
+    {
+        fit_rows(rows);
+        for (const StatRow& r : rows) {
+            if (!r.array->defined()) continue;
+            r.array->narrow(0, P, k).zero_();
+            if (also.defined()) r.array->index_fill_(0, also, 0);
+        }
+    }
+    // append to a permute list (resort): the arrays, in place
+    void permute_rows(const std::vector<StatRow>& rows, std::vector<gslic_row_array>& list)
+    {
+        fit_rows(rows);
+        for (const StatRow& r : rows)
+            if (r.array->defined()) list.push_back({r.array->data_ptr(), r.array->data_ptr(), r.width});
     }
     // capacity storage: created by the first extend(); until then the tensors handed to the constructor are used in place
     void reserve(int64_t newP)

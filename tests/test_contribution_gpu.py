@@ -303,7 +303,7 @@ def test_fused_contribution_cpp_host(tmp_path):
     spec = importlib.util.spec_from_file_location("build_shim", path)
     build_shim = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_contribution_check()
+    exe = build_shim.build_fused_check("fused_contribution")
     assert os.path.exists(exe)
     m, cam = _model("a", order="morton")
     d = str(tmp_path)

@@ -670,7 +670,7 @@ def test_fused_densify_cpp_host(tmp_path, order):
     spec = importlib.util.spec_from_file_location("build_shim", path)
     build_shim = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_densify_check()
+    exe = build_shim.build_fused_check("fused_densify")
     assert os.path.exists(exe)
     iters, seed = 2, 11
     m, cam, gt, bg = _trained(_scene(), order, steps=0, resort_fraction=None)

@@ -374,7 +374,7 @@ def test_fused_cpp_host_depth_pose_gradient(tmp_path):
     spec = importlib.util.spec_from_file_location("build_shim", path)
     build_shim = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_depth_pose_check()
+    exe = build_shim.build_fused_check("fused_depth_pose")
     assert os.path.exists(exe)
     P, W, H, deg = 20000, 320, 240, 3
     raw, sc, cam, model, gt, gtd, bg = _pose_case(7, P, W, H)

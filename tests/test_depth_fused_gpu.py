@@ -322,7 +322,7 @@ def test_fused_depth_cpp_host(tmp_path, deg):
     spec = importlib.util.spec_from_file_location("build_shim", path)
     build_shim = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_depth_check()
+    exe = build_shim.build_fused_check("fused_depth")
     assert os.path.exists(exe)
     P, W, H, iters = 30000, 320, 240, 4
     raw, cam, gt, gtd, bg = _setup("random", P, W, H, deg, 44)

@@ -453,7 +453,7 @@ def test_fused_free_space_cpp_host(tmp_path, monkeypatch):
     spec = importlib.util.spec_from_file_location("build_shim", path)
     build_shim = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_free_space_check()
+    exe = build_shim.build_fused_check("fused_free_space")
     assert os.path.exists(exe)
     monkeypatch.delenv("GSLIC_RESORT", raising=False)
     dev = _dev()

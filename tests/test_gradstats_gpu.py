@@ -387,7 +387,7 @@ def test_fused_gradient_stats_cpp_host(tmp_path, order):
     spec = importlib.util.spec_from_file_location("build_shim", path)
     build_shim = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_gradient_stats_check()
+    exe = build_shim.build_fused_check("fused_gradient_stats")
     assert os.path.exists(exe)
     P, iters, seed = 600, 2, 11
     m = _model(P, 3, order, resort_fraction=None)

@@ -422,7 +422,7 @@ def test_fused_prune_cpp_host(tmp_path):
     spec = importlib.util.spec_from_file_location("build_shim", path)
     build_shim = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_prune_check()
+    exe = build_shim.build_fused_check("fused_prune")
     assert os.path.exists(exe)
     iters, min_opacity, max_scale = 2, 0.3, 1.0
     m, cam, gt, bg = _model(_scene("random"), "morton", steps=0)

@@ -396,7 +396,7 @@ def test_fused_weighted_cpp_host(tmp_path, with_depth):
     spec = importlib.util.spec_from_file_location("build_shim", path)
     build_shim = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_weighted_check()
+    exe = build_shim.build_fused_check("fused_weighted")
     assert os.path.exists(exe)
     P, W, H, deg, iters = 5000, 160, 120, 3, 3
     raw, cam, gt, gtd, bg = _setup(P, W, H, deg, 44)

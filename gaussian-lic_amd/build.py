@@ -38,6 +38,7 @@ SOURCES = {
     "morton.hip": ["-ffp-contract=off"],   # the key rule of gslic_morton_order: every float32 step rounded on its own, tested on bits
     "contrib.hip": ["-ffp-contract=off"],  # replays the strict blend: every product of the power and of w = alpha T is rounded on its own
     "densify.hip": ["-ffp-contract=off"],  # the split children's positions: every product and sum rounded on its own, as the header writes them
+    "lidar_depth.hip": ["-ffp-contract=off"],  # pixel assignment decides integers, and the near bound is tested on bits: every step rounded on its own
 }
 COMMON = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-Wno-inline-asm",
           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]

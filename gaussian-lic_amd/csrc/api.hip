@@ -1396,6 +1396,44 @@ int gslic_morton_order(int32_t P, const float* xyz, const float* box, gslic_allo
     return morton_order(P, xyz, box, scratch_alloc, scratch_ctx, perm, keys_sorted, (hipStream_t)stream);
 }
 
+int gslic_lidar_zbuffer_add(int32_t n, const float* points, const float* R_cw, const float* t_cw, float fx, float fy, float cx, float cy,
+                            int32_t width, int32_t height, uint64_t* zbuf, int32_t clear, int32_t index_base, void* stream)
+{
+    if (n < 0) return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer add: n=%d is negative", n);
+    if (width <= 0 || height <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer add: width=%d height=%d must be positive", width, height);
+    if (!zbuf) return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer add: zbuf is NULL");
+    if (n > 0 && !points) return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer add: points is NULL");
+    if (n > 0 && !R_cw) return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer add: R_cw is NULL");
+    if (n > 0 && !t_cw) return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer add: t_cw is NULL");
+    if (index_base < 0 || (int64_t)index_base + (int64_t)n > 0x7fffffffLL)
+        return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer add: index_base=%d with n=%d leaves [0, 2^31 - 1]", index_base, n);
+    return lidar_zbuffer_add(n, points, R_cw, t_cw, fx, fy, cx, cy, width, height, reinterpret_cast<unsigned long long*>(zbuf), clear != 0,
+                             index_base, (hipStream_t)stream);
+}
+
+int gslic_lidar_zbuffer_resolve(int32_t width, int32_t height, const uint64_t* zbuf, int32_t footprint, float margin_abs, float margin_rel,
+                                float* depth_out, int32_t* index_out, float* near_out, uint32_t* n_measured_out, void* stream)
+{
+    if (width <= 0 || height <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer resolve: width=%d height=%d must be positive", width, height);
+    if (!zbuf) return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer resolve: zbuf is NULL");
+    if (footprint < 0 || footprint > 8) return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer resolve: footprint=%d outside [0, 8]", footprint);
+    if (!(margin_abs >= 0.0f)) return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer resolve: margin_abs=%g is negative or NaN", (double)margin_abs);
+    if (!(margin_rel >= 0.0f)) return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer resolve: margin_rel=%g is negative or NaN", (double)margin_rel);
+    if (!depth_out && !index_out && !near_out)
+        return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer resolve: depth_out, index_out and near_out are all NULL");
+    const size_t N = (size_t)width * (size_t)height;
+    const uintptr_t z0 = reinterpret_cast<uintptr_t>(zbuf), z1 = z0 + N * sizeof(uint64_t);
+    const struct { const void* p; size_t bytes; const char* name; } outs[4] = {
+        {depth_out, N * sizeof(float), "depth_out"}, {index_out, N * sizeof(int32_t), "index_out"}, {near_out, N * sizeof(float), "near_out"},
+        {n_measured_out, sizeof(uint32_t), "n_measured_out"}};
+    for (const auto& o : outs) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(o.p);
+        if (o.p && a < z1 && z0 < a + o.bytes) return set_error(GSLIC_ERR_INVALID_ARG, "lidar zbuffer resolve: %s overlaps zbuf", o.name);
+    }
+    return lidar_zbuffer_resolve(width, height, reinterpret_cast<const unsigned long long*>(zbuf), footprint, margin_abs, margin_rel, depth_out,
+                                 index_out, near_out, n_measured_out, (hipStream_t)stream);
+}
+
 size_t gslic_permute_rows_staging_bytes(const gslic_row_array* arrays, int32_t n_arrays, int32_t n_rows)
 {
     if (!arrays || n_arrays <= 0 || n_rows <= 0) return 0;

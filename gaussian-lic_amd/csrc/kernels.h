@@ -183,6 +183,13 @@ int morton_order(int P, const float* xyz, const float* box, gslic_alloc_fn alloc
 size_t permute_rows_bytes(const gslic_row_array* arrays, int n_arrays, int n_rows);   // the sum of row_dwords * 4 * n_rows, not rounded
 int permute_rows(const gslic_row_array* arrays, int n_arrays, const uint32_t* perm, int n_rows, void* staging, hipStream_t s);
 
+// lidar_depth.hip: the LiDAR z-buffer of gslic_lidar_zbuffer_add (optional clear, then one 64-bit atomicMin per point) and its resolution into
+// depth / index / near-bound images and the measured-pixel count by gslic_lidar_zbuffer_resolve (arguments validated by the caller)
+int lidar_zbuffer_add(int n, const float* points, const float* Rcw, const float* tcw, float fx, float fy, float cx, float cy, int W, int H,
+                      unsigned long long* zbuf, bool clear, int32_t index_base, hipStream_t s);
+int lidar_zbuffer_resolve(int W, int H, const unsigned long long* zbuf, int footprint, float margin_abs, float margin_rel, float* depth_out,
+                          int32_t* index_out, float* near_out, uint32_t* n_measured_out, hipStream_t s);
+
 // contrib.hip: the per-Gaussian contribution statistics of gslic_contribution_accumulate from a completed forward's lists (one workgroup per tile;
 // arguments validated by the caller; any of the three accumulators may be NULL)
 struct ContribArgs {

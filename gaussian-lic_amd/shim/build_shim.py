@@ -113,6 +113,7 @@ FUSED_CHECKS = {name: (os.path.join(HERE, name + "_check.cpp"), os.path.join(PKG
     "fused_gradient_stats",   # gradient statistics, carried through densify, prune and resort
     "fused_free_space",       # free-space statistics, carried through prune and resort
     "fused_rows",             # both statistics objects at once through densify, extend, prune and resort
+    "fused_lidar_depth",      # the LiDAR range image (gslic::LidarDepth) feeding a depth-supervised step and the free-space statistics
 )}
 
 

@@ -100,6 +100,78 @@ struct GradientStats {
     torch::Tensor big_mask(int64_t P, int32_t max_screen_radius) const { return max_radius.narrow(0, 0, P).gt(max_screen_radius); }
 };
 
+// The per-pixel LiDAR range image of one camera, built by the library (gslic_lidar_zbuffer_add / _resolve, include/gslic_hip.h) — the Python host's
+// trainer.LidarDepth: it owns the z-buffer of width * height 64-bit keys on `device`.  The reference's host builds the image on the CPU
+// (gaussian.cpp:554-572).  resolve()'s depth is usable as it is as the gt_depth of FusedStep::step and pose_gradient, its near_bound as the near_bound of
+// FusedStep::accumulate_free_space.  Every call runs on the current stream, allocates only its result tensors and reads nothing back.
+struct LidarImages {
+    torch::Tensor depth;        // float32 [H,W]: nearest return of the pixel's window, 0 = none
+    torch::Tensor near_bound;   // float32 [H,W]: depth - (margin_abs + margin_rel * depth) where measured, 0 elsewhere (only with margins)
+    torch::Tensor index;        // int32 [H,W]: the winning point, -1 = none (only when asked for)
+    torch::Tensor n_measured;   // int32 scalar on the device: measured pixels (only when asked for)
+};
+class LidarDepth {
+public:
+    LidarDepth(int width, int height, torch::Device device = torch::kCUDA) : W_(width), H_(height)
+    {
+        TORCH_CHECK(width > 0 && height > 0, "LidarDepth: the image must not be empty");
+        zbuf_ = torch::empty({(int64_t)height * width}, torch::TensorOptions().dtype(torch::kInt64).device(device));
+    }
+    // empties the image: the next add() clears the z-buffer inside its call
+    void clear() { pending_clear_ = true; n_points_ = 0; }
+    // One sweep: points_world [n,3] (device), the world-to-camera pose R_cw [3,3] row-major and t_cw [3] (float32, rounded from the host's pose as
+    // Camera.project_depth rounds it) and the intrinsics.  The nearest return wins a pixel, equal depths go to the lowest index.  Returns the
+    // sweep's index_base: its point i is index base + i in resolve()'s index image.  Several sweeps, each with its own pose, accumulate.
+    int64_t add(const torch::Tensor& points_world, const torch::Tensor& R_cw, const torch::Tensor& t_cw, float fx, float fy, float cx, float cy)
+    {
+        torch::NoGradGuard ng;
+        TORCH_CHECK(points_world.dim() == 2 && points_world.size(1) == 3 && points_world.device() == zbuf_.device(),
+                    "LidarDepth::add: points_world must be [n, 3] on the image's device");
+        TORCH_CHECK(R_cw.numel() == 9 && t_cw.numel() == 3, "LidarDepth::add: R_cw must hold 9 and t_cw 3 values");
+        const torch::Tensor pts = points_world.detach().to(torch::kFloat32).contiguous();
+        const torch::Tensor R = R_cw.detach().to(zbuf_.device(), torch::kFloat32).contiguous(), t = t_cw.detach().to(zbuf_.device(), torch::kFloat32).contiguous();
+        const int64_t n = pts.size(0);
+        TORCH_CHECK(n_points_ + n <= std::numeric_limits<int32_t>::max(), "LidarDepth::add: more than 2^31 - 1 points in one image");
+        return add_raw((int32_t)n, n ? pts.data_ptr<float>() : nullptr, R.data_ptr<float>(), t.data_ptr<float>(), fx, fy, cx, cy);
+    }
+    // The images of what was added since the last clear().  footprint r in [0, 8]: every pixel takes the nearest return of its (2r+1) x (2r+1)
+    // window clipped to the image (0: its own).  margins: when set, near_bound is written too.
+    LidarImages resolve(int footprint = 0, std::optional<std::array<float, 2>> margins = std::nullopt, bool index = false, bool count = false)
+    {
+        torch::NoGradGuard ng;
+        if (pending_clear_) add_raw(0, nullptr, nullptr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f);
+        const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(zbuf_.device()), i32 = f32.dtype(torch::kInt32);
+        LidarImages out;
+        out.depth = torch::empty({H_, W_}, f32);
+        if (margins) out.near_bound = torch::empty({H_, W_}, f32);
+        if (index) out.index = torch::empty({H_, W_}, i32);
+        if (count) out.n_measured = torch::empty({}, i32);
+        const int rc = gslic_lidar_zbuffer_resolve(W_, H_, reinterpret_cast<const uint64_t*>(zbuf_.data_ptr<int64_t>()), footprint, margins ? (*margins)[0] : 0.0f,
+                                                   margins ? (*margins)[1] : 0.0f, out.depth.data_ptr<float>(), index ? out.index.data_ptr<int32_t>() : nullptr,
+                                                   margins ? out.near_bound.data_ptr<float>() : nullptr,
+                                                   count ? reinterpret_cast<uint32_t*>(out.n_measured.data_ptr<int32_t>()) : nullptr, current_stream());
+        TORCH_CHECK(rc == GSLIC_OK, "gslic_lidar_zbuffer_resolve failed (", rc, "): ", gslic_last_error());
+        return out;
+    }
+    int64_t points() const { return n_points_; }   // points added since the last clear: the next sweep's index_base
+
+private:
+    int64_t add_raw(int32_t n, const float* pts, const float* R, const float* t, float fx, float fy, float cx, float cy)
+    {
+        const int64_t base = n_points_;
+        const int rc = gslic_lidar_zbuffer_add(n, pts, R, t, fx, fy, cx, cy, W_, H_, reinterpret_cast<uint64_t*>(zbuf_.data_ptr<int64_t>()), pending_clear_ ? 1 : 0,
+                                               (int32_t)base, current_stream());
+        TORCH_CHECK(rc == GSLIC_OK, "gslic_lidar_zbuffer_add failed (", rc, "): ", gslic_last_error());
+        pending_clear_ = false;
+        n_points_ = base + n;
+        return base;
+    }
+    int W_, H_;
+    torch::Tensor zbuf_;
+    bool pending_clear_ = true;
+    int64_t n_points_ = 0;
+};
+
 class FusedStep {
 public:
     // params: the six raw leaf tensors in the group order of trainingSetup (gaussian.cpp:399-418); updated IN PLACE.

@@ -571,6 +571,96 @@ def free_space_bound(depth, margin_abs, margin_rel):
     return torch.where(d > 0, d - (ma + mr * d), torch.zeros((), dtype=torch.float32, device=d.device))
 
 
+class LidarDepth:
+    """The per-pixel LiDAR range image of one camera, built by the library (gslic_lidar_zbuffer_add / _resolve, include/gslic_hip.h): it owns the
+    z-buffer of width * height 64-bit keys {float bits of camera z, point index} on `device`.
+
+        ld = LidarDepth(W, H, device);  ld.add(camera, points_world);  out = ld.resolve(footprint=0, margins=(0.1, 0.02))
+        training_step_fused(..., gt_depth=out["depth"], lambda_depth=...);  stats.accumulate(camera, free_space=out["near"])
+
+    At footprint 0, depth is camera.project_depth(points) and near is free_space_bound(depth, *margins), bit for bit; a footprint r > 0 gives
+    every pixel the NEAREST return of its (2r+1) x (2r+1) window (clipped to the image): a conservative footprint for sparse returns.  Which
+    footprint and margins to use, and when to trust a sweep, is the host's policy.  Every call runs on the current stream, allocates only its
+    result tensors and reads nothing back."""
+
+    MAX_FOOTPRINT = 8
+
+    def __init__(self, width, height, device):
+        self.width, self.height = int(width), int(height)
+        if self.width <= 0 or self.height <= 0:
+            raise ValueError(f"LidarDepth: the image must not be empty, got {width!r} x {height!r}")
+        self.device = torch.device(device)
+        self._zbuf = torch.empty(self.height * self.width, dtype=torch.int64, device=self.device)
+        self._pending_clear = True   # the first add clears (one memset inside the call)
+        self.n_points = 0            # the running index_base: points added since the last clear
+
+    def clear(self):
+        """Empties the image: the next add() clears the z-buffer inside its call; a resolve() before any add() gives the empty image."""
+        self._pending_clear = True
+        self.n_points = 0
+
+    def _add_raw(self, n, points, R_cw, t_cw, fx, fy, cx, cy):
+        from . import _lib
+        base = self.n_points
+        _lib.check(_lib.lib().gslic_lidar_zbuffer_add(n, _lib.ptr(points), _lib.ptr(R_cw), _lib.ptr(t_cw), fx, fy, cx, cy, self.width, self.height,
+                                                      _lib.ptr(self._zbuf), int(self._pending_clear), base, _lib.current_stream_ptr()))
+        self._pending_clear = False
+        self.n_points = base + n
+        return base
+
+    @torch.no_grad()
+    def add(self, camera, points_world):
+        """Adds one sweep: points_world [n,3] (world frame, on the device) seen from `camera` (its pose as project_depth forms it: R_cw = R_wc^T and
+        t_cw = -R_wc^T t_wc rounded to float32; its intrinsics).  The nearest return wins a pixel, equal depths go to the lowest index.  Returns the
+        index_base of this sweep: its point i is index base + i in resolve()'s index image.  Several sweeps, each with its own pose, accumulate."""
+        import numpy as np
+        if camera.image_width != self.width or camera.image_height != self.height:
+            raise ValueError(f"LidarDepth.add: the camera is {camera.image_width} x {camera.image_height}, the image {self.width} x {self.height}")
+        pts = torch.as_tensor(points_world)
+        if pts.dim() != 2 or pts.shape[1] != 3 or pts.device != self.device:
+            raise ValueError(f"LidarDepth.add: points_world must be [n, 3] on {self.device}, got {tuple(pts.shape)} on {pts.device}")
+        pts = pts.detach().to(torch.float32).contiguous()
+        R_cw = torch.from_numpy(np.ascontiguousarray(camera.R_wc.T.astype(np.float32))).to(self.device)
+        t_cw = torch.from_numpy((-camera.R_wc.T @ camera.t_wc).astype(np.float32)).to(self.device)
+        return self._add_raw(int(pts.shape[0]), pts, R_cw, t_cw, float(camera.fx), float(camera.fy), float(camera.cx), float(camera.cy))
+
+    @torch.no_grad()
+    def resolve(self, footprint=0, margins=None, index=False, count=False):
+        """The images of what was added since the last clear(), as a dict: "depth" float32 [H,W] (0 = no return in the window); with
+        margins=(margin_abs, margin_rel) also "near" = depth - (margin_abs + margin_rel * depth) where measured and 0 elsewhere
+        (free_space_bound's arithmetic; a bound <= 0 is kept as it is); with index=True "index" int32 [H,W] (the winning point, -1 = none); with
+        count=True "n_measured", a device int32 scalar tensor holding the number of measured pixels (no read-back here)."""
+        from . import _lib
+        r = int(footprint)
+        if not 0 <= r <= self.MAX_FOOTPRINT:
+            raise ValueError(f"LidarDepth.resolve: footprint must be in [0, {self.MAX_FOOTPRINT}], got {footprint!r}")
+        ma, mr = (0.0, 0.0) if margins is None else (float(margins[0]), float(margins[1]))
+        if not (ma >= 0.0 and mr >= 0.0):   # (a NaN fails)
+            raise ValueError(f"LidarDepth.resolve: the margins must be >= 0, got {margins!r}")
+        if self._pending_clear:
+            self._add_raw(0, None, None, None, 0.0, 0.0, 0.0, 0.0)
+        H, W, dev = self.height, self.width, self.device
+        out = {"depth": torch.empty(H, W, dtype=torch.float32, device=dev)}
+        if margins is not None:
+            out["near"] = torch.empty(H, W, dtype=torch.float32, device=dev)
+        if index:
+            out["index"] = torch.empty(H, W, dtype=torch.int32, device=dev)
+        if count:
+            out["n_measured"] = torch.empty((), dtype=torch.int32, device=dev)
+        p = lambda k: _lib.ptr(out.get(k))
+        _lib.check(_lib.lib().gslic_lidar_zbuffer_resolve(W, H, _lib.ptr(self._zbuf), r, ma, mr, p("depth"), p("index"), p("near"), p("n_measured"),
+                                                          _lib.current_stream_ptr()))
+        return out
+
+
+def lidar_depth_image(camera, points, footprint=0):
+    """camera.project_depth(points) through the library, for points on a GPU: one sweep into a fresh LidarDepth, its depth image [H,W] at the given
+    footprint (0: bit for bit project_depth's image)."""
+    ld = LidarDepth(camera.image_width, camera.image_height, torch.as_tensor(points).device)
+    ld.add(camera, points)
+    return ld.resolve(footprint=footprint)["depth"]
+
+
 class _RowStatistics:
     """What GaussianModel's row changes walk on an attached per-row statistics object (a weak reference in model._stats): _gather (prune), _appended
     (extend / densify), _zero_rows (densify's split parents), _permute (resort), on the arrays a subclass lists in _arrays() and creates, zero-filled

@@ -645,6 +645,50 @@ int gslic_extend_emit(
     float* xyz, float* dc, float* rest, float* opacity, float* scaling, float* rotation, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * gslic_lidar_zbuffer_add / gslic_lidar_zbuffer_resolve — the per-pixel LiDAR range image on the device: what gt_depth (depth supervision, the
+ * pose gradient under depth) and near_bound (gslic_contribution_accumulate_free_space) are made from.  The reference's host builds it on the CPU
+ * (a device-to-host copy of every point and an unordered_map keyed by "x_y" strings, gaussian.cpp:554-572); a LibTorch host needs about twenty
+ * elementwise launches and scatter_reduce_(amin).  Both calls work on a CALLER-OWNED z-buffer zbuf of width * height uint64 on the DEVICE, one
+ * key per pixel (row-major, pixel (x, y) at y * width + x): the all-ones word = empty, otherwise (float bits of z) << 32 | point index.
+ *
+ *  add:     with clear != 0 the buffer is first set to all ones.  Then one thread per point i < n; the rule is EXACT — every step below is ONE
+ *           IEEE float32 operation rounded on its own (no contraction, true divisions), left to right, so the same steps in any IEEE float32
+ *           arithmetic give the same image bit for bit.  points [n,3] world, R_cw [9] row-major and t_cw [3] on the DEVICE:
+ *
+ *             c_k = p_0 * R_cw[3k] + p_1 * R_cw[3k+1] + p_2 * R_cw[3k+2] + t_cw[k]      (k = 0, 1, 2;  z = c_2)
+ *             the point is dropped unless z > 0 and z < +inf                             (z <= 0, NaN and +inf are dropped)
+ *             xf = floor((c_0 * fx) / z + cx);   yf = floor((c_1 * fy) / z + cy)
+ *             the point is dropped unless 0 <= xf < width and 0 <= yf < height           (compared as floats; a NaN fails)
+ *             zbuf[yf * width + xf] = min(zbuf[...], (uint64) bits(z) << 32 | (uint32) (index_base + i))       (one 64-bit integer atomic)
+ *
+ *           The bits of a positive float order like its value, so the smallest z wins a pixel and equal z goes to the lowest index, whatever
+ *           order the points arrive in.  Calls with clear == 0 accumulate further sweeps (each with its own pose) into the same image;
+ *           index_base keeps their indices apart.  n == 0 with clear != 0 is valid and leaves an empty image.
+ *  resolve: per pixel, key = the minimum of zbuf over the (2 footprint + 1) x (2 footprint + 1) window around the pixel, clipped to the image
+ *           (footprint in [0, 8]; 0 reads the pixel's own key): the nearest return inside the window, a CONSERVATIVE footprint of sparse
+ *           returns (how wide to make it is the host's policy).  Outputs on the DEVICE, [height, width] row-major, each may be NULL, at
+ *           least one must not be:
+ *             depth_out float32   the float whose bits are key >> 32;                          0 where key is empty
+ *             index_out int32     (int32) (uint32) key;                                        -1 where key is empty
+ *             near_out  float32   d - (margin_abs + margin_rel * d) of that depth d — one product, one add, one subtraction, each rounded on
+ *                                 its own; a bound <= 0 is written as it is;                   0 where key is empty
+ *           n_measured_out: optional DEVICE uint32; the call zeroes it on the stream and every workgroup adds its number of non-empty
+ *           resolved pixels with one integer atomic (exact, independent of order).  zbuf is only read.
+ *  Neither call allocates, synchronises or reads anything back (graph-capturable); no float atomics.  Refused with GSLIC_ERR_INVALID_ARG before
+ *  any device work, the message naming the argument: n < 0; width <= 0 or height <= 0; a NULL zbuf; NULL points, R_cw or t_cw with n > 0;
+ *  index_base < 0 or index_base + n > 2^31 - 1; footprint outside [0, 8]; a margin that is negative or NaN; depth_out, index_out and near_out
+ *  all NULL; an output (n_measured_out included) whose bytes overlap zbuf's.  With N > 1 GPUs every rank calls both with identical arguments.
+ */
+int gslic_lidar_zbuffer_add(
+    int32_t n, const float* points /*[n,3]*/, const float* R_cw /*[9]*/, const float* t_cw /*[3]*/,
+    float fx, float fy, float cx, float cy, int32_t width, int32_t height,
+    uint64_t* zbuf /*[height*width]*/, int32_t clear, int32_t index_base, void* stream);
+int gslic_lidar_zbuffer_resolve(
+    int32_t width, int32_t height, const uint64_t* zbuf /*[height*width]*/, int32_t footprint, float margin_abs, float margin_rel,
+    float* depth_out /*[H,W] or NULL*/, int32_t* index_out /*[H,W] or NULL*/, float* near_out /*[H,W] or NULL*/,
+    uint32_t* n_measured_out /*[1] or NULL*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * gslic_prune_select / gslic_gather_rows — removing rows from the map (no reference counterpart: its map only grows; a LibTorch host
  * would run 19 boolean-index launches with 19 temporaries: 6 groups x {parameter, exp_avg, exp_avg_sq} + tie_rank).
  *

@@ -1,9 +1,119 @@
-"""Helpers shared by the -m gpu tests: run the HIP path through the C-ABI front-end on seeded scenes."""
+"""Helpers shared by the -m gpu tests: run the HIP path through the C-ABI front-end on seeded scenes, build the small models the statistics
+tests share, and compare tensors, model states, maps and guard words.  Importable without a GPU: whatever touches the device or loads
+libgslic_hip.so happens inside the functions."""
+import types
+
 import numpy as np
 import torch
 
 from gaussian_lic_amd import rasterizer as rz
 from gaussian_lic_amd.synthetic import activate
+
+SENTINEL = 0x5A5A5A5A   # the guard word of guarded(), and what the tests fill rows with that no kernel may write
+GUARD = 64              # guard words on either side of a guarded() buffer
+
+
+def gpu():
+    return torch.device("cuda:0")
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def same_tensors(a, b):
+    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def guarded(n, dtype=torch.int32, fill=None, device=None, sentinel=SENTINEL):
+    """A buffer of n words of `dtype` between two runs of GUARD guard words: (whole buffer, the n words as a view, set to `fill` if given)."""
+    buf = torch.full((n + 2 * GUARD,), sentinel, dtype=dtype, device=gpu() if device is None else device)
+    words = buf[GUARD:GUARD + n]
+    if fill is not None:
+        words.fill_(fill)
+    return buf, words
+
+
+def guards_intact(buf, n, sentinel=SENTINEL):
+    return bool((buf[:GUARD] == sentinel).all()) and bool((buf[GUARD + n:] == sentinel).all())
+
+
+def scene_model(name, order="insertion", **kw):
+    """(GaussianModel of contribution_ref.scene(name), its synthetic camera on the device)."""
+    import contribution_ref as cr
+    from gaussian_lic_amd import trainer
+    from gaussian_lic_amd.camera import synthetic_camera
+    raw, W, H = cr.scene(name)
+    m = trainer.GaussianModel(cr._clone(raw), gpu(), order=order, **kw)
+    return m, synthetic_camera(W, H).to_device(gpu())
+
+
+def training_model(raw):
+    """A GaussianModel of a copy of the raw parameters on the device, with its optimizer set up."""
+    from gaussian_lic_amd import trainer
+    m = trainer.GaussianModel({k: (v.clone() if torch.is_tensor(v) else v) for k, v in raw.items()}, gpu())
+    m.training_setup()
+    return m
+
+
+def raw_forward(m, cam, depth=False, bufs=None):
+    """A trainer._RawRaster of the model after its forward (black background, no autograd)."""
+    from gaussian_lic_amd import trainer
+    fwd = trainer._RawRaster(m, cam, torch.zeros(3, device=gpu()), depth=depth)
+    with torch.no_grad():
+        fwd.forward(bufs)
+    return fwd
+
+
+def export_lists(m, cam, fwd, what):
+    """rasterizer.debug_export of the lists a raw_forward left behind: the dict of the arrays named in `what`."""
+    H, W = fwd.hw
+    rs = types.SimpleNamespace(image_height=H, image_width=W, sh_degree=m.sh_degree, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, limx_neg=cam.limx_neg,
+                               limx_pos=cam.limx_pos, limy_neg=cam.limy_neg, limy_pos=cam.limy_pos, scale_modifier=1.0, no_color=False)
+    R, B, _radii, geom, binning, img, sample = fwd.state
+    return rz.debug_export(rs, m.P, 0, R, B, geom, binning, img, sample, what=tuple(what))
+
+
+def model_state(m):
+    """Parameters and both Adam moments of every group, as host copies."""
+    out = {}
+    for i, n in enumerate(m.NAMES):
+        out[n] = getattr(m, n).detach().cpu().clone()
+        st = m.optimizer.state[i]
+        if st is not None:
+            out[n + ".m"] = st["exp_avg"].cpu().clone()
+            out[n + ".v"] = st["exp_avg_sq"].cpu().clone()
+    return out
+
+
+def assert_same_state(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+
+
+def map_snapshot(m, order=None, tie=False):
+    """Copies of the map's rows [0, P): parameters and both moments per group (rows listed by `order` when given), with tie=True also the
+    tie rank as int64 (None for an insertion-order map)."""
+    P = m.P
+    pick = (lambda t: t[:P].clone()) if order is None else (lambda t: t[:P][order].clone())
+    out = {}
+    for n in m.NAMES:
+        out[n] = pick(m._buf[n]); out[n + ".m"] = pick(m._m[n]); out[n + ".v"] = pick(m._v[n])
+    if tie:
+        out["tie"] = None if m._tie is None else m._tie[:P].clone().long()
+    return out
+
+
+def same_map(a, b, view=bits):
+    """Asserts that the Morton-ordered model b holds the insertion-order model a's map: parameters and both moments, b's rows taken in their
+    original order.  `view` is what torch.equal sees: the bits, or (view=None) the floats themselves."""
+    view = view or (lambda t: t)
+    order = b.original_order()
+    for n in a.NAMES:
+        assert torch.equal(view(getattr(a, n).detach()), view(getattr(b, n).detach()[order])), n
+    for n in a.NAMES:
+        assert torch.equal(view(a._m[n][:a.P]), view(b._m[n][:b.P][order])) and torch.equal(view(a._v[n][:a.P]), view(b._v[n][:b.P][order])), n
 
 
 def settings_from(cam, deg, dev, no_color=False, lambda_erank=0.0, debug=False, scale_modifier=1.0):

@@ -10,7 +10,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _model(P, order):
+def _model(P, order):   # (a map on the CPU, for bench.py's own functions: not gpu_helpers.scene_model, which builds on the GPU)
     import gaussian_lic_amd  # noqa: F401
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.synthetic import random_scene

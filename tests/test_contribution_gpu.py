@@ -6,43 +6,20 @@ and plain torch indexing for everything that moves rows.  All forwards run in st
   a  96 Gaussians, SH degree 0, 40 x 24: 3 x 2 tiles, right column and bottom row partial        b  400 Gaussians on the one tile of 16 x 16, high
   c  scene a behind the camera: R = 0                                                               opacities: three staging batches, early stops
   d  scene a in a Morton-ordered model (tie_rank): storage rows, equal to a's after un-permuting"""
-import importlib.util
-import os
-import subprocess
-import types
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import contribution_ref as cr
+import fused_check_io as fio
 from conftest import rel_err
+from gpu_helpers import SENTINEL, export_lists, gpu, guarded, raw_forward, same_tensors, scene_model
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4          # the bar the project applies to gradients (tests/refcompare.py: TOL; conftest.rel_err)
-SENTINEL = 0x5A5A5A5A
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _model(name, order="insertion", **kw):
-    import gaussian_lic_amd  # noqa: F401
-    from gaussian_lic_amd import trainer
-    from gaussian_lic_amd.camera import synthetic_camera
-    raw, W, H = cr.scene(name)
-    m = trainer.GaussianModel(cr._clone(raw), _dev(), order=order, **kw)
-    return m, synthetic_camera(W, H).to_device(_dev())
-
-
-def _forward(m, cam, depth=False, bufs=None):
-    from gaussian_lic_amd import trainer
-    fwd = trainer._RawRaster(m, cam, torch.zeros(3, device=_dev()), depth=depth)
-    with torch.no_grad():
-        fwd.forward(bufs)
-    return fwd
 
 
 def _stats(m, fwds=(), cams=(), w_min=cr.W_MIN):
@@ -61,21 +38,12 @@ def _arrays(st):
     return st.max_weight().view(torch.int32).cpu().clone(), st.pixels().cpu().clone(), st.sum_fixed().cpu().clone()
 
 
-def _same(a, b):
-    return all(torch.equal(x, y) for x, y in zip(a, b))
-
-
 def _replay(m, cam, fwd, **kw):
-    from gaussian_lic_amd import rasterizer as rz
-    H, W = fwd.hw
-    rs = types.SimpleNamespace(image_height=H, image_width=W, sh_degree=m.sh_degree, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, limx_neg=cam.limx_neg,
-                               limx_pos=cam.limx_pos, limy_neg=cam.limy_neg, limy_pos=cam.limy_pos, scale_modifier=1.0, no_color=False)
-    R, B, _radii, geom, binning, img, sample = fwd.state
-    P = m.P
+    (H, W), R, P = fwd.hw, fwd.state[0], m.P
     if R == 0:
         z = np.zeros
         return cr.replay(z((P, 2)), z((P, 4)), z(0, np.int64), z((((W + 15) // 16) * ((H + 15) // 16), 2), np.int64), z((H, W), np.int64), W, H, P, **kw)
-    d = rz.debug_export(rs, P, 0, R, B, geom, binning, img, sample, what=("means2D", "conic_opacity", "point_list", "ranges", "n_contrib"))
+    d = export_lists(m, cam, fwd, ("means2D", "conic_opacity", "point_list", "ranges", "n_contrib"))
     n = lambda k: d[k].cpu().numpy()
     return cr.replay(n("means2D"), n("conic_opacity"), n("point_list"), n("ranges"), n("n_contrib"), W, H, P, **kw)
 
@@ -102,14 +70,14 @@ def _check_against_replay(st, rep, what):
 @pytest.mark.parametrize("name", ["a", "b"])
 def test_sum_of_weights_is_the_backwards_colour_gradient(name):
     from gaussian_lic_amd.rasterizer import render
-    m, cam = _model(name)
-    fwd = _forward(m, cam)
+    m, cam = scene_model(name)
+    fwd = raw_forward(m, cam)
     H, W = fwd.hw
-    dL = torch.zeros(3, H, W, device=_dev())
+    dL = torch.zeros(3, H, W, device=gpu())
     dL[0] = 1.0
     with torch.no_grad():
         grads = fwd.backward(dL)
-        final_T = render(cam, m, torch.zeros(3, device=_dev()))[1]
+        final_T = render(cam, m, torch.zeros(3, device=gpu()))[1]
     dL_dcolor = grads[1]
     st = _stats(m, fwds=[fwd])
     sw = st.sum_weight().cpu().numpy()
@@ -125,8 +93,8 @@ def test_sum_of_weights_is_the_backwards_colour_gradient(name):
 # ---------------------------------------------------------------------------------------------------- 2. against a replay
 @pytest.mark.parametrize("name", ["a", "b"])
 def test_statistics_match_the_float64_replay(name):
-    m, cam = _model(name)
-    fwd = _forward(m, cam)
+    m, cam = scene_model(name)
+    fwd = raw_forward(m, cam)
     rep = _replay(m, cam, fwd)
     if name == "b":   # the list crosses staging batches and every pixel stops well before its end
         R, nc = fwd.state[0], rep["pairs"].sum()
@@ -136,40 +104,35 @@ def test_statistics_match_the_float64_replay(name):
 
 
 def _ncontrib_max(m, cam, fwd):
-    from gaussian_lic_amd import rasterizer as rz
-    H, W = fwd.hw
-    rs = types.SimpleNamespace(image_height=H, image_width=W, sh_degree=0, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, limx_neg=cam.limx_neg,
-                               limx_pos=cam.limx_pos, limy_neg=cam.limy_neg, limy_pos=cam.limy_pos, scale_modifier=1.0, no_color=False)
-    R, B, _r, geom, binning, img, sample = fwd.state
-    return rz.debug_export(rs, m.P, 0, R, B, geom, binning, img, sample, what=("n_contrib",))["n_contrib"].max()
+    return export_lists(m, cam, fwd, ("n_contrib",))["n_contrib"].max()
 
 
 def test_nothing_in_view_leaves_zeros():
-    m, cam = _model("c")
-    fwd = _forward(m, cam)
+    m, cam = scene_model("c")
+    fwd = raw_forward(m, cam)
     assert fwd.state[0] == 0
     st = _stats(m, fwds=[fwd], cams=[cam])
     assert st.views == 2 and all(not bool(t.any()) for t in _arrays(st))
 
 
 def test_morton_order_indexes_storage_rows():
-    a, cam = _model("a")
-    d, _cam = _model("a", order="morton")
+    a, cam = scene_model("a")
+    d, _cam = scene_model("a", order="morton")
     assert not torch.equal(d.tie_rank.long().cpu(), torch.arange(d.P))      # the rows really are permuted
     sa, sd = _arrays(_stats(a, cams=[cam])), _arrays(_stats(d, cams=[cam]))
     order = d.original_order().cpu()
-    assert _same(sa, [t[order] for t in sd])
+    assert same_tensors(sa, [t[order] for t in sd])
     assert bool(sa[0].any())
 
 
 # ---------------------------------------------------------------------------------------------------- 3. determinism and accumulation
 def test_runs_repeat_and_views_accumulate_bit_for_bit():
     from gaussian_lic_amd.camera import synthetic_camera
-    m, cam1 = _model("a")
-    cam2 = synthetic_camera(cr.W_A, cr.H_A, 5).to_device(_dev())
+    m, cam1 = scene_model("a")
+    cam2 = synthetic_camera(cr.W_A, cr.H_A, 5).to_device(gpu())
     one, again, two = _arrays(_stats(m, cams=[cam1])), _arrays(_stats(m, cams=[cam1])), _arrays(_stats(m, cams=[cam2]))
-    assert _same(one, again)
-    assert bool(two[0].any()) and not _same(one, two)
+    assert same_tensors(one, again)
+    assert bool(two[0].any()) and not same_tensors(one, two)
     both = _stats(m, cams=[cam1, cam2])
     got = _arrays(both)
     assert both.views == 2
@@ -183,43 +146,37 @@ def test_runs_repeat_and_views_accumulate_bit_for_bit():
 def test_every_forward_and_binning_path_gives_the_same_statistics(name):
     from gaussian_lic_amd import _lib
     from gaussian_lic_amd.rasterizer import CapacityBuffers
-    m, cam = _model(name)
+    m, cam = scene_model(name)
     H, W = int(cam.image_height), int(cam.image_width)
-    want = _arrays(_stats(m, fwds=[_forward(m, cam)]))
+    want = _arrays(_stats(m, fwds=[raw_forward(m, cam)]))
     assert bool(want[0].any())
     old = _lib.set_binning_mode("radix")
     try:
         for mode in ("radix", "atomic"):
             _lib.set_binning_mode(mode)
-            assert _same(want, _arrays(_stats(m, fwds=[_forward(m, cam)]))), mode
+            assert same_tensors(want, _arrays(_stats(m, fwds=[raw_forward(m, cam)]))), mode
     finally:
         _lib.set_binning_mode(old)
-    assert _same(want, _arrays(_stats(m, fwds=[_forward(m, cam, depth=True)]))), "depth forward"
+    assert same_tensors(want, _arrays(_stats(m, fwds=[raw_forward(m, cam, depth=True)]))), "depth forward"
     for depth in (False, True):
-        bufs = CapacityBuffers(m.P, W, H, 4096, 256, _dev(), depth=depth)
-        _forward(m, cam, depth=depth, bufs=bufs)
+        bufs = CapacityBuffers(m.P, W, H, 4096, 256, gpu(), depth=depth)
+        raw_forward(m, cam, depth=depth, bufs=bufs)
         assert bufs.read_status()[2] == 0
-        assert _same(want, _arrays(_stats(m, fwds=[bufs]))), f"capacity forward, depth={depth}"
+        assert same_tensors(want, _arrays(_stats(m, fwds=[bufs]))), f"capacity forward, depth={depth}"
 
 
 # ---------------------------------------------------------------------------------------------------- 4. capacity mode
-def _guarded(P, dtype, fill):
-    g = torch.full((P + 128,), SENTINEL, dtype=dtype, device=_dev())
-    g[64:64 + P] = fill
-    return g, g[64:64 + P]
-
-
 def test_capacity_overflow_accumulates_nothing_and_guards_stay():
     from gaussian_lic_amd import rasterizer as rz
     from gaussian_lic_amd.rasterizer import CapacityBuffers
-    m, cam = _model("a")
+    m, cam = scene_model("a")
     H, W, P = cr.H_A, cr.W_A, m.P
-    R = _forward(m, cam).state[0]
+    R = raw_forward(m, cam).state[0]
     for cap_R, fits in ((R // 3, False), (4096, True)):
-        bufs = CapacityBuffers(P, W, H, cap_R, 256, _dev())
-        _forward(m, cam, bufs=bufs)
+        bufs = CapacityBuffers(P, W, H, cap_R, 256, gpu())
+        raw_forward(m, cam, bufs=bufs)
         assert (bufs.read_status()[2] == 0) == fits
-        g = [_guarded(P, torch.int32, 7), _guarded(P, torch.int32, 7), _guarded(P, torch.int64, 7)]
+        g = [guarded(P, torch.int32, 7), guarded(P, torch.int32, 7), guarded(P, torch.int64, 7)]
         rz.contribution_accumulate(P, H, W, bufs.cap_R, bufs.cap_B, bufs.geom, bufs.binning, bufs.img, cr.W_MIN, g[0][1], g[1][1], g[2][1])
         torch.cuda.synchronize()
         for whole, _view in g:
@@ -227,10 +184,10 @@ def test_capacity_overflow_accumulates_nothing_and_guards_stay():
         changed = [bool((view != 7).any()) for _whole, view in g]
         assert changed == [fits] * 3, (cap_R, changed)
     # any subset of the outputs may be absent
-    fwd = _forward(m, cam)
+    fwd = raw_forward(m, cam)
     full = _arrays(_stats(m, fwds=[fwd]))
     R, B, _r, geom, binning, img, _s = fwd.state
-    only = torch.zeros(P, dtype=torch.int32, device=_dev())
+    only = torch.zeros(P, dtype=torch.int32, device=gpu())
     rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, cr.W_MIN, None, only, None)
     rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, cr.W_MIN, None, None, None)
     assert torch.equal(only.cpu().long(), full[1])
@@ -240,8 +197,8 @@ def test_capacity_overflow_accumulates_nothing_and_guards_stay():
 def test_statistics_follow_the_rows_through_prune_extend_resort():
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.synthetic import lidar_scene
-    dev = _dev()
-    m, cam = _model("a", order="morton", capacity=4 * cr.P_A, resort_fraction=None)
+    dev = gpu()
+    m, cam = scene_model("a", order="morton", capacity=4 * cr.P_A, resort_fraction=None)
     st = _stats(m, cams=[cam])
     old = _arrays(st)
     # drop_mask is the torch expression on the returned arrays
@@ -256,14 +213,14 @@ def test_statistics_follow_the_rows_through_prune_extend_resort():
     detached.detach()
     n, kept = m.prune(drop=mask)
     assert n == int(mask.sum()) and m.P == cr.P_A - n
-    assert _same(_arrays(st), [t[kept.cpu()] for t in old]) and st.views == 1
+    assert same_tensors(_arrays(st), [t[kept.cpu()] for t in old]) and st.views == 1
     assert not bool(st._max[m.P:].any()) and not bool(st._npix[m.P:].any()) and not bool(st._sum[m.P:].any())
     with pytest.raises(RuntimeError, match="rows changed"):
         detached.max_weight()
     with pytest.raises(RuntimeError, match="rows changed"):
         detached.accumulate(cam)
     # a fresh accumulate on the pruned map equals the replay on the pruned map
-    fwd = _forward(m, cam)
+    fwd = raw_forward(m, cam)
     _check_against_replay(_stats(m, fwds=[fwd]), _replay(m, cam, fwd), "scene a, pruned")
     # extend: appended rows are zero, the others stay
     before = _arrays(st)
@@ -275,14 +232,14 @@ def test_statistics_follow_the_rows_through_prune_extend_resort():
     k = m.extend(cam, frame["xyz"].to(dev), col, frame["xyz"][:, 2].contiguous().to(dev), Rcw, tcw, (float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy)))
     assert k > 0 and m.P == P0 + k
     after = _arrays(st)
-    assert _same([t[:P0] for t in after], before) and all(not bool(t[P0:].any()) for t in after)
+    assert same_tensors([t[:P0] for t in after], before) and all(not bool(t[P0:].any()) for t in after)
     # ... also when the storage had to grow
-    small, _c = _model("a")
+    small, _c = scene_model("a")
     st_small = _stats(small, cams=[cam])
     b_small = _arrays(st_small)
     k2 = small.extend(cam, frame["xyz"].to(dev), col, frame["xyz"][:, 2].contiguous().to(dev), Rcw, tcw, (float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy)))
     a_small = _arrays(st_small)
-    assert k2 > 0 and small.capacity > cr.P_A and _same([t[:cr.P_A] for t in a_small], b_small) and all(not bool(t[cr.P_A:].any()) for t in a_small)
+    assert k2 > 0 and small.capacity > cr.P_A and same_tensors([t[:cr.P_A] for t in a_small], b_small) and all(not bool(t[cr.P_A:].any()) for t in a_small)
     # resort: the statistics follow the permutation
     st.accumulate(cam)
     before = _arrays(st)
@@ -290,7 +247,7 @@ def test_statistics_follow_the_rows_through_prune_extend_resort():
     stale.detach()
     perm = m.resort().cpu()
     assert not torch.equal(perm, torch.arange(m.P))
-    assert _same(_arrays(st), [t[perm] for t in before]) and st.views == 2
+    assert same_tensors(_arrays(st), [t[perm] for t in before]) and st.views == 2
     with pytest.raises(RuntimeError, match="rows changed"):
         stale.pixels()
 
@@ -299,20 +256,11 @@ def test_statistics_follow_the_rows_through_prune_extend_resort():
 def test_fused_contribution_cpp_host(tmp_path):
     """gslic::FusedStep::accumulate_contribution and the statistics carried through gslic::FusedStep::prune give the Python host's arrays bit
     for bit: scene (a) in Morton order, one view, a prune by drop_mask(pixels_below=1), the same view again on the pruned map."""
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussian-lic_amd", "shim", "build_shim.py")
-    spec = importlib.util.spec_from_file_location("build_shim", path)
-    build_shim = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_check("fused_contribution")
-    assert os.path.exists(exe)
-    m, cam = _model("a", order="morton")
+    exe = fio.build("fused_contribution")
+    m, cam = scene_model("a", order="morton")
     d = str(tmp_path)
-    w = lambda name, t, dt=np.float32, ext="f32": np.ascontiguousarray(t, dt).tofile(os.path.join(d, f"{name}.{ext}"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc")):
-        w(n, getattr(m, k).detach().cpu().numpy())
-    w("tie_rank", m.tie_rank.cpu().numpy())
-    w("view", cam.world_view_transform); w("proj", cam.full_proj_transform); w("campos", cam.camera_center)
-    w("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos], np.float32))
+    w = functools.partial(fio.write, d)
+    fio.write_inputs(d, m, cam, tie_rank=m.tie_rank)
     st = _stats(m, cams=[cam])
 
     def dump(tag):
@@ -325,6 +273,5 @@ def test_fused_contribution_cpp_host(tmp_path):
     w("exp_kept", kept.cpu().numpy(), np.int32, "i32")
     st.accumulate(cam)
     dump(2)
-    r = subprocess.run([exe, d, str(cr.P_A), str(cr.W_A), str(cr.H_A), "0", repr(cr.W_MIN), "1"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = fio.run(exe, d, str(cr.P_A), str(cr.W_A), str(cr.H_A), "0", repr(cr.W_MIN), "1")
     assert f"contribution check ok rows {cr.P_A} kept {m.P}" in r.stdout

@@ -6,9 +6,8 @@ the float64 replay of the forward's lists and the backward (dL_dcolor[:, 0] unde
 restatement of the selection rule, plain torch indexing for every copied field, and the numpy / float64 restatement of the counter generator and
 the split children (tests/densify_ref.py).  Scenes "a", "b", "c" are contribution_ref's.  All forwards run in strict arithmetic."""
 import ctypes
-import importlib.util
+import functools
 import os
-import subprocess
 import types
 
 import numpy as np
@@ -17,46 +16,22 @@ import torch
 
 import contribution_ref as cr
 import densify_ref as dr
+import fused_check_io as fio
+from gpu_helpers import SENTINEL, bits, export_lists, gpu, guarded, map_snapshot, raw_forward, scene_model
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A
 SENT_F = float(np.array([SENTINEL], np.uint32).view(np.float32)[0])
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _bits(x):
-    return x.contiguous().view(torch.int32)
-
-
 # ==================================================================================================== 1. the error accumulator
-def _model(name, order="insertion", **kw):
-    import gaussian_lic_amd  # noqa: F401
-    from gaussian_lic_amd import trainer
-    from gaussian_lic_amd.camera import synthetic_camera
-    raw, W, H = cr.scene(name)
-    m = trainer.GaussianModel(cr._clone(raw), _dev(), order=order, **kw)
-    return m, synthetic_camera(W, H).to_device(_dev())
-
-
-def _forward(m, cam, depth=False, bufs=None):
-    from gaussian_lic_amd import trainer
-    fwd = trainer._RawRaster(m, cam, torch.zeros(3, device=_dev()), depth=depth)
-    with torch.no_grad():
-        fwd.forward(bufs)
-    return fwd
-
-
 def _err_image(name, kind="random"):
     W, H = (cr.W_B, cr.H_B) if name == "b" else (cr.W_A, cr.H_A)
     if kind == "random":
         e = 2.0 * torch.rand(H, W, generator=torch.Generator().manual_seed(41))
     else:
         e = torch.full((H, W), float(kind))
-    return e.to(_dev())
+    return e.to(gpu())
 
 
 def _four(m, fwd, err, plain=False):
@@ -75,8 +50,8 @@ def views():
     """Per scene: the model, the camera, one plain forward and the plain entry point's three arrays — computed once, left unchanged."""
     out = {}
     for name in ("a", "b"):
-        m, cam = _model(name)
-        fwd = _forward(m, cam)
+        m, cam = scene_model(name)
+        fwd = raw_forward(m, cam)
         out[name] = (m, cam, fwd, _four(m, fwd, None, plain=True))
     return out
 
@@ -103,12 +78,7 @@ def test_guard_words_and_subsets_of_the_outputs(views):
     P, (H, W) = m.P, fwd.hw
     R, B, _r, geom, binning, img, _s = fwd.state
     err = _err_image("a")
-
-    def guarded(dtype):
-        g = torch.full((P + 128,), SENTINEL, dtype=dtype, device=_dev())
-        g[64:64 + P] = 0
-        return g, g[64:64 + P]
-    g = [guarded(torch.int32), guarded(torch.int32), guarded(torch.int64), guarded(torch.int64)]
+    g = [guarded(P, torch.int32, 0), guarded(P, torch.int32, 0), guarded(P, torch.int64, 0), guarded(P, torch.int64, 0)]
     rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, cr.W_MIN, g[0][1], g[1][1], g[2][1], error=err, err_sum=g[3][1])
     torch.cuda.synchronize()
     for whole, _v in g:
@@ -116,7 +86,7 @@ def test_guard_words_and_subsets_of_the_outputs(views):
     assert torch.equal(g[0][1].cpu(), plain[0]) and torch.equal(g[1][1].cpu().long() & 0xffffffff, plain[1]) and torch.equal(g[2][1].cpu(), plain[2])
     full = g[3][1].cpu().clone()
     assert bool(full.any())
-    only = torch.zeros(P, dtype=torch.int64, device=_dev())
+    only = torch.zeros(P, dtype=torch.int64, device=gpu())
     rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, cr.W_MIN, None, None, None, error=err, err_sum=only)   # the three may be absent
     assert torch.equal(only.cpu(), full)
     with pytest.raises(ValueError, match="go together"):
@@ -127,11 +97,11 @@ def test_runs_repeat_and_views_add_as_integers(views):
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.camera import synthetic_camera
     m, cam1, fwd, _plain = views["a"]
-    cam2 = synthetic_camera(cr.W_A, cr.H_A, 5).to_device(_dev())
+    cam2 = synthetic_camera(cr.W_A, cr.H_A, 5).to_device(gpu())
     err = _err_image("a")
     one, again = _four(m, fwd, err), _four(m, fwd, err)
     assert all(torch.equal(a, b) for a, b in zip(one, again)) and bool(one[3].any())
-    two = _four(m, _forward(m, cam2), err)
+    two = _four(m, raw_forward(m, cam2), err)
     assert not torch.equal(one[3], two[3])
     st = trainer.ContributionStats(m)
     st.accumulate(cam1, w_min=cr.W_MIN, error=err)
@@ -156,32 +126,28 @@ def test_every_forward_and_binning_path_gives_the_same_error_sums(views, name):
     try:
         for mode in ("radix", "atomic"):
             _lib.set_binning_mode(mode)
-            assert same(_four(m, _forward(m, cam), err)), mode
+            assert same(_four(m, raw_forward(m, cam), err)), mode
     finally:
         _lib.set_binning_mode(old)
-    assert same(_four(m, _forward(m, cam, depth=True), err)), "depth forward"
-    bufs = CapacityBuffers(m.P, W, H, 4096, 256, _dev())
-    _forward(m, cam, bufs=bufs)
+    assert same(_four(m, raw_forward(m, cam, depth=True), err)), "depth forward"
+    bufs = CapacityBuffers(m.P, W, H, 4096, 256, gpu())
+    raw_forward(m, cam, bufs=bufs)
     assert bufs.read_status()[2] == 0 and same(_four(m, bufs, err)), "capacity forward"
-    small = CapacityBuffers(m.P, W, H, max(fwd.state[0] // 3, 1), 256, _dev())       # the lists do not fit: nothing is accumulated
-    _forward(m, cam, bufs=small)
+    small = CapacityBuffers(m.P, W, H, max(fwd.state[0] // 3, 1), 256, gpu())       # the lists do not fit: nothing is accumulated
+    raw_forward(m, cam, bufs=small)
     assert small.read_status()[2] != 0 and not any(bool(t.any()) for t in _four(m, small, err))
 
 
 def test_nothing_in_view_leaves_zeros():
-    m, cam = _model("c")
-    fwd = _forward(m, cam)
+    m, cam = scene_model("c")
+    fwd = raw_forward(m, cam)
     assert fwd.state[0] == 0
     assert not any(bool(t.any()) for t in _four(m, fwd, _err_image("a")))
 
 
 def _replay_error(m, cam, fwd, err):
-    from gaussian_lic_amd import rasterizer as rz
     H, W = fwd.hw
-    rs = types.SimpleNamespace(image_height=H, image_width=W, sh_degree=m.sh_degree, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, limx_neg=cam.limx_neg,
-                               limx_pos=cam.limx_pos, limy_neg=cam.limy_neg, limy_pos=cam.limy_pos, scale_modifier=1.0, no_color=False)
-    R, B, _radii, geom, binning, img, sample = fwd.state
-    d = rz.debug_export(rs, m.P, 0, R, B, geom, binning, img, sample, what=("means2D", "conic_opacity", "point_list", "ranges", "n_contrib"))
+    d = export_lists(m, cam, fwd, ("means2D", "conic_opacity", "point_list", "ranges", "n_contrib"))
     n = lambda k: d[k].cpu().numpy()
     return dr.replay_error(n("means2D"), n("conic_opacity"), n("point_list"), n("ranges"), n("n_contrib"), W, H, m.P, err.cpu().numpy())
 
@@ -194,7 +160,7 @@ def test_random_error_against_the_replay_and_the_backward(views, name):
     err = _err_image(name)
     got = trainer.fixed_to_weight(_four(m, fwd, err)[3]).numpy()
     ref = _replay_error(m, cam, fwd, err)
-    dL = torch.zeros(3, H, W, device=_dev())
+    dL = torch.zeros(3, H, W, device=gpu())
     dL[0] = err
     with torch.no_grad():
         bwd = fwd.backward(dL)[1][:, 0].double().cpu().numpy()
@@ -210,7 +176,7 @@ def _rows(P, M, seed):
     g = torch.Generator().manual_seed(seed)
     r = lambda *s: torch.randn(*s, generator=g)
     t = dict(xyz=3.0 * r(P, 3), features_dc=r(P, 3), features_rest=r(P, 3 * M), opacity=r(P, 1), scaling=1.5 * r(P, 3) - 1.0, rotation=r(P, 4))
-    return {k: v.to(_dev()).contiguous() for k, v in t.items()}
+    return {k: v.to(gpu()).contiguous() for k, v in t.items()}
 
 
 NAMES = ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation")
@@ -220,9 +186,9 @@ def _select(t, grow, protect, tie, thr):
     from gaussian_lic_amd import _lib
     L, p = _lib.lib(), _lib.ptr
     P = t["xyz"].shape[0]
-    parent = torch.full((P + 16,), SENTINEL, dtype=torch.int32, device=_dev())
+    parent = torch.full((P + 16,), SENTINEL, dtype=torch.int32, device=gpu())
     count, split = ctypes.c_int32(-1), ctypes.c_int32(-1)
-    scratch = _lib.TensorAllocator(_dev())
+    scratch = _lib.TensorAllocator(gpu())
     u8 = lambda x: None if x is None else x.to(torch.uint8).contiguous()
     grow8, protect8, tie32 = u8(grow), u8(protect), (None if tie is None else tie.to(torch.int32).contiguous())   # (kept alive across the call)
     _lib.check(L.gslic_densify_select(P, p(t["xyz"]), p(t["features_dc"]), p(t["opacity"]), p(t["scaling"]), p(t["rotation"]), p(grow8), p(protect8),
@@ -249,10 +215,10 @@ def test_selection_equals_the_torch_rule(P):
     t["scaling"][::5, 0] = -1.0
     t["scaling"][::5, 2] = -2.0                                               # ... with nothing above it: they clone
     g = torch.Generator().manual_seed(P)
-    protect = (torch.rand(P, generator=g) < 0.2).to(_dev())
-    tie = torch.randperm(P, generator=g).to(_dev())
+    protect = (torch.rand(P, generator=g) < 0.2).to(gpu())
+    tie = torch.randperm(P, generator=g).to(gpu())
     for mname, grow in _masks(P, 7 * P).items():
-        grow = grow.to(_dev())
+        grow = grow.to(gpu())
         for prot in (None, protect):
             for ti in (None, tie):
                 parent, count, split = _select(t, grow, prot, ti, thr)
@@ -276,7 +242,7 @@ def test_non_finite_rows_and_zero_quaternions_are_not_eligible():
     t["rotation"][23] = 0.0
     t["rotation"][29] = torch.tensor([0.0, 0.0, -0.0, 1e-30])                 # not zero, but its float32 squared norm underflows to 0: no direction
     t["rotation"][31] = torch.tensor([0.0, 3e-19, -0.0, 1e-18])               # tiny with a float32 squared norm > 0: eligible
-    grow = torch.ones(P, dtype=torch.bool, device=_dev())
+    grow = torch.ones(P, dtype=torch.bool, device=gpu())
     parent, count, split = _select(t, grow, None, None, 0.0)
     out = {3, 7, 11, 13, 17, 23, 29}
     assert count == P - len(out) and sorted(parent[:count].tolist()) == [i for i in range(P) if i not in out]
@@ -290,21 +256,21 @@ def _emit_case(P, M, with_tie, seed, thr=0.0, mask="random"):
     from gaussian_lic_amd import _lib
     L, p = _lib.lib(), _lib.ptr
     t = _rows(P, M, 300 + P + M)
-    grow = _masks(P, 11 * P)[mask].to(_dev())
+    grow = _masks(P, 11 * P)[mask].to(gpu())
     g = torch.Generator().manual_seed(P + 1)
-    tie = torch.randperm(P, generator=g).to(_dev()) if with_tie else None
+    tie = torch.randperm(P, generator=g).to(gpu()) if with_tie else None
     parent, k, n_split = _select(t, grow, None, tie, thr)
     cap = P + k + 8
     buf, m1, m2 = {}, {}, {}
     for i, n in enumerate(NAMES):
         w = t[n].shape[1]
-        buf[n] = torch.full((cap, w), SENT_F, device=_dev())
+        buf[n] = torch.full((cap, w), SENT_F, device=gpu())
         buf[n][:P] = t[n]
-        m1[n] = torch.full((cap, w), 0.25 + i, device=_dev())
-        m2[n] = torch.full((cap, w), 0.5 + i, device=_dev())
+        m1[n] = torch.full((cap, w), 0.25 + i, device=gpu())
+        m2[n] = torch.full((cap, w), 0.5 + i, device=gpu())
     tie_buf = None
     if with_tie:
-        tie_buf = torch.full((cap,), SENTINEL, dtype=torch.int32, device=_dev())
+        tie_buf = torch.full((cap,), SENTINEL, dtype=torch.int32, device=gpu())
         tie_buf[:P] = tie.to(torch.int32)
     before = {n: (buf[n].clone(), m1[n].clone(), m2[n].clone()) for n in NAMES}
     tie_before = None if tie_buf is None else tie_buf.clone()
@@ -312,14 +278,14 @@ def _emit_case(P, M, with_tie, seed, thr=0.0, mask="random"):
     _lib.check(L.gslic_densify_emit(P, k, p(parent), M, six(buf), six(m1), six(m2), p(tie_buf), thr, seed, _lib.current_stream_ptr()))
     torch.cuda.synchronize()
     return types.SimpleNamespace(P=P, k=k, n_split=n_split, parent=parent[:k].long(), buf=buf, m1=m1, m2=m2, tie=tie_buf, before=before, tie_before=tie_before,
-                                 orig=t, o=(tie if with_tie else torch.arange(P, device=_dev())), thr=thr, seed=seed)
+                                 orig=t, o=(tie if with_tie else torch.arange(P, device=gpu())), thr=thr, seed=seed)
 
 
 def _xyz_gap(c):
     """Largest gap of the split children's xyz from the float64 restatement, relative to the parent's largest activated scale."""
     split = (c.orig["scaling"][c.parent] > c.thr).any(1)
     par = c.parent[split]
-    new = (c.P + torch.arange(c.k, device=_dev()))[split]
+    new = (c.P + torch.arange(c.k, device=gpu()))[split]
     if par.numel() == 0:
         return 0.0
     n = lambda x: x.cpu().numpy()
@@ -338,33 +304,33 @@ def _check_emission(P, M):
         c = _emit_case(P, M, with_tie, seed=9, mask=mask)
         k, par = c.k, c.parent
         assert k > 0
-        new = P + torch.arange(k, device=_dev())
+        new = P + torch.arange(k, device=gpu())
         split = (c.orig["scaling"][par] > c.thr).any(1)
         assert int(split.sum()) == c.n_split
         sp, cl = par[split], par[~split]
-        touched = torch.zeros(P + k + 8, dtype=torch.bool, device=_dev())
+        touched = torch.zeros(P + k + 8, dtype=torch.bool, device=gpu())
         for n in NAMES:
             b0, m10, m20 = c.before[n]
             b, m1, m2 = c.buf[n], c.m1[n], c.m2[n]
             # rows >= P + k and every row that is not a (split) parent are untouched
-            keep = torch.ones(P + k + 8, dtype=torch.bool, device=_dev())
+            keep = torch.ones(P + k + 8, dtype=torch.bool, device=gpu())
             keep[new] = False
             keep_m = keep.clone()
             keep_m[sp] = False
             if n in ("xyz", "scaling"):
                 keep[sp] = False
-            assert torch.equal(_bits(b[keep]), _bits(b0[keep])), n
-            assert torch.equal(_bits(m1[keep_m]), _bits(m10[keep_m])) and torch.equal(_bits(m2[keep_m]), _bits(m20[keep_m])), n
+            assert torch.equal(bits(b[keep]), bits(b0[keep])), n
+            assert torch.equal(bits(m1[keep_m]), bits(m10[keep_m])) and torch.equal(bits(m2[keep_m]), bits(m20[keep_m])), n
             # moments: zero on the new rows and the split parents
             for mm in (m1, m2):
-                assert not bool(_bits(mm[new]).any()) and not bool(_bits(mm[sp]).any()), n
+                assert not bool(bits(mm[new]).any()) and not bool(bits(mm[sp]).any()), n
             # copied fields
             if n in ("features_dc", "features_rest", "opacity", "rotation"):
-                assert torch.equal(_bits(b[new]), _bits(b0[par])), n
+                assert torch.equal(bits(b[new]), bits(b0[par])), n
             else:
-                assert torch.equal(_bits(b[new][~split]), _bits(b0[cl])), n            # clone: bit copy of xyz and scaling too
-        shr = c.orig["scaling"][sp] - torch.tensor(float(dr.SHRINK), device=_dev())    # ONE float32 subtraction
-        assert torch.equal(_bits(c.buf["scaling"][sp]), _bits(shr)) and torch.equal(_bits(c.buf["scaling"][new[split]]), _bits(shr))
+                assert torch.equal(bits(b[new][~split]), bits(b0[cl])), n            # clone: bit copy of xyz and scaling too
+        shr = c.orig["scaling"][sp] - torch.tensor(float(dr.SHRINK), device=gpu())    # ONE float32 subtraction
+        assert torch.equal(bits(c.buf["scaling"][sp]), bits(shr)) and torch.equal(bits(c.buf["scaling"][new[split]]), bits(shr))
         if with_tie:
             assert torch.equal(c.tie[:P], c.tie_before[:P]) and torch.equal(c.tie[P:P + k].long(), new) and bool((c.tie[P + k:] == SENTINEL).all())
             assert torch.equal(torch.sort(c.o[par]).values, c.o[par])                   # new rows in the order of the parents' original indices
@@ -377,11 +343,11 @@ def _check_emission(P, M):
         # the same seed gives the same bits, another seed other positions (and nothing else)
         again, other = _emit_case(P, M, with_tie, seed=9, mask=mask), _emit_case(P, M, with_tie, seed=10, mask=mask)
         for n in NAMES:
-            assert torch.equal(_bits(again.buf[n]), _bits(c.buf[n])), n
+            assert torch.equal(bits(again.buf[n]), bits(c.buf[n])), n
             if n != "xyz":
-                assert torch.equal(_bits(other.buf[n]), _bits(c.buf[n])), n
+                assert torch.equal(bits(other.buf[n]), bits(c.buf[n])), n
         if c.n_split:
-            assert not torch.equal(other.buf["xyz"][sp], c.buf["xyz"][sp]) and torch.equal(_bits(other.buf["xyz"][cl]), _bits(c.buf["xyz"][cl]))
+            assert not torch.equal(other.buf["xyz"][sp], c.buf["xyz"][sp]) and torch.equal(bits(other.buf["xyz"][cl]), bits(c.buf["xyz"][cl]))
 
 
 @pytest.mark.parametrize("M", [15, 0])
@@ -413,12 +379,12 @@ def test_a_parent_index_outside_the_map_is_never_an_address():
         cap = P + count + 8
         st = []
         for fill in (SENT_F, 0.25, 0.5):                                       # parameters, exp_avg, exp_avg_sq: sentinels beyond P, non-zero moments
-            d = {n: torch.full((cap, t[n].shape[1]), SENT_F, device=_dev()) for n in NAMES}
+            d = {n: torch.full((cap, t[n].shape[1]), SENT_F, device=gpu()) for n in NAMES}
             for n in NAMES:
                 d[n][:P] = t[n] if fill == SENT_F else fill
             st.append(d)
         before = [{n: d[n].clone() for n in NAMES} for d in st]
-        index = torch.tensor(parents, dtype=torch.int32, device=_dev())
+        index = torch.tensor(parents, dtype=torch.int32, device=gpu())
         _lib.check(L.gslic_densify_emit(P, count, p(index), M, six(st[0]), six(st[1]), six(st[2]), None, thr, seed, _lib.current_stream_ptr()))
         torch.cuda.synchronize()
         return st, before
@@ -427,18 +393,18 @@ def test_a_parent_index_outside_the_map_is_never_an_address():
     for g, b, w in zip(got, before, want):
         for n in NAMES:
             what = (n, g is got[0])
-            assert torch.equal(_bits(g[n][P + 0]), _bits(w[n][P + 0])) and torch.equal(_bits(g[n][P + 2]), _bits(w[n][P + 1])), what   # as without them
-            assert not bool((_bits(w[n][P:P + 2]) == SENTINEL).any()), what                                                            # (and written)
-            assert bool((_bits(g[n][P + 1]) == SENTINEL).all()) and bool((_bits(g[n][P + 3]) == SENTINEL).all()), what                 # left alone
-            assert bool((_bits(g[n][P + 4:]) == SENTINEL).all()), what                                                                 # the guard rows
-            rest = torch.arange(P, device=_dev()) != 2
-            assert torch.equal(_bits(g[n][:P][rest]), _bits(b[n][:P][rest])), what                                                     # every other old row
-            assert torch.equal(_bits(g[n][2]), _bits(w[n][2])), what                                                                   # the split parent
+            assert torch.equal(bits(g[n][P + 0]), bits(w[n][P + 0])) and torch.equal(bits(g[n][P + 2]), bits(w[n][P + 1])), what   # as without them
+            assert not bool((bits(w[n][P:P + 2]) == SENTINEL).any()), what                                                            # (and written)
+            assert bool((bits(g[n][P + 1]) == SENTINEL).all()) and bool((bits(g[n][P + 3]) == SENTINEL).all()), what                 # left alone
+            assert bool((bits(g[n][P + 4:]) == SENTINEL).all()), what                                                                 # the guard rows
+            rest = torch.arange(P, device=gpu()) != 2
+            assert torch.equal(bits(g[n][:P][rest]), bits(b[n][:P][rest])), what                                                     # every other old row
+            assert torch.equal(bits(g[n][2]), bits(w[n][2])), what                                                                   # the split parent
     for d in got[1:]:
         for n in NAMES:
-            assert not bool(_bits(d[n][2]).any()) and not bool(_bits(d[n][P + 0]).any()) and not bool(_bits(d[n][P + 2]).any()), n     # zero moments
+            assert not bool(bits(d[n][2]).any()) and not bool(bits(d[n][P + 0]).any()) and not bool(bits(d[n][P + 2]).any()), n     # zero moments
     for n in ("features_dc", "features_rest", "opacity", "rotation"):
-        assert torch.equal(_bits(got[0][n][2]), _bits(before[0][n][2])), n                                                             # no thread writes these
+        assert torch.equal(bits(got[0][n][2]), bits(before[0][n][2])), n                                                             # no thread writes these
 
 
 def test_tiny_quaternions_split_to_finite_children():
@@ -451,19 +417,19 @@ def test_tiny_quaternions_split_to_finite_children():
     t["rotation"][::4] = t["rotation"][::4] * 1e-18                            # squared norm about 1e-36: a normal float32
     dead = torch.arange(1, P, 8)
     t["rotation"][dead] = t["rotation"][dead] * 1e-30                          # squared norm underflows to 0
-    grow = torch.ones(P, dtype=torch.bool, device=_dev())
+    grow = torch.ones(P, dtype=torch.bool, device=gpu())
     parent, k, n_split = _select(t, grow, None, None, thr)
     want, wk, ws, _s = dr.select(t["xyz"], t["features_dc"], t["opacity"], t["scaling"], t["rotation"], grow, None, None, thr)
     assert k == wk == n_split == ws == P - dead.numel() and torch.equal(parent[:k].long(), want)
-    buf = {n: torch.cat([t[n], torch.full((k, t[n].shape[1]), SENT_F, device=_dev())]) for n in NAMES}
+    buf = {n: torch.cat([t[n], torch.full((k, t[n].shape[1]), SENT_F, device=gpu())]) for n in NAMES}
     m1 = {n: torch.ones_like(buf[n]) for n in NAMES}
     m2 = {n: torch.ones_like(buf[n]) for n in NAMES}
     six = lambda d: (ctypes.c_void_p * 6)(*[(d[n].data_ptr() if d[n].numel() else None) for n in NAMES])
     _lib.check(L.gslic_densify_emit(P, k, p(parent), M, six(buf), six(m1), six(m2), None, thr, seed, _lib.current_stream_ptr()))
     torch.cuda.synchronize()
     assert bool(torch.isfinite(buf["xyz"]).all()) and bool(torch.isfinite(buf["scaling"]).all())
-    assert torch.equal(_bits(buf["xyz"][dead.to(_dev())]), _bits(t["xyz"][dead.to(_dev())]))          # ineligible rows are untouched
-    c = types.SimpleNamespace(P=P, k=k, parent=parent[:k].long(), buf=buf, orig=t, o=torch.arange(P, device=_dev()), thr=thr, seed=seed)
+    assert torch.equal(bits(buf["xyz"][dead.to(gpu())]), bits(t["xyz"][dead.to(gpu())]))          # ineligible rows are untouched
+    c = types.SimpleNamespace(P=P, k=k, parent=parent[:k].long(), buf=buf, orig=t, o=torch.arange(P, device=gpu()), thr=thr, seed=seed)
     gap = _xyz_gap(c)
     print(f"[densify gap] split xyz, tiny quaternions: splits {n_split} gap / largest scale {gap:.3e} (bar {dr.XYZ_MARGIN})")
     assert gap <= dr.XYZ_MARGIN
@@ -475,8 +441,8 @@ def test_all_clone_and_all_split_thresholds():
         assert c.k == 257 and c.n_split == int(frac * 257)
         if frac == 0.0:
             for n in NAMES:
-                assert torch.equal(_bits(c.buf[n][257:514]), _bits(c.orig[n][c.parent])), n
-                assert torch.equal(_bits(c.buf[n][:257]), _bits(c.orig[n])), n
+                assert torch.equal(bits(c.buf[n][257:514]), bits(c.orig[n][c.parent])), n
+                assert torch.equal(bits(c.buf[n][:257]), bits(c.orig[n])), n
 
 
 # ==================================================================================================== 4. the model
@@ -493,7 +459,7 @@ def _trained(raw, order, steps=2, **kw):
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.camera import synthetic_camera
     from gaussian_lic_amd.synthetic import gt_image
-    dev = _dev()
+    dev = gpu()
     m = trainer.GaussianModel({k: (v.clone() if torch.is_tensor(v) else v) for k, v in raw.items()}, dev, order=order, **kw)
     m.training_setup()
     cam = synthetic_camera(W, H).to_device(dev)
@@ -501,15 +467,6 @@ def _trained(raw, order, steps=2, **kw):
     for _ in range(steps):
         trainer.training_step_fused(m, cam, gt, bg)
     return m, cam, gt, bg
-
-
-def _snapshot(m, order=None):
-    P = m.P
-    idx = torch.arange(P, device=_dev()) if order is None else order
-    out = {}
-    for n in m.NAMES:
-        out[n] = m._buf[n][:P][idx].clone(); out[n + ".m"] = m._m[n][:P][idx].clone(); out[n + ".v"] = m._v[n][:P][idx].clone()
-    return out
 
 
 def _median_scale(m):
@@ -521,45 +478,45 @@ def test_both_row_orders_densify_to_the_same_map():
     raw = _scene()
     a, cam, gt, bg = _trained(raw, "insertion", capacity=2 * NP)
     d, _c, _g, _b = _trained(raw, "morton", capacity=2 * NP, resort_fraction=None)
-    grow = torch.rand(NP, generator=torch.Generator().manual_seed(1)).to(_dev()) < 0.3      # in ORIGINAL order
+    grow = torch.rand(NP, generator=torch.Generator().manual_seed(1)).to(gpu()) < 0.3      # in ORIGINAL order
     s = _median_scale(a)
     ka, sa, _pa = a.densify(grow, s, seed=5)
     kd, sd, pd = d.densify(grow[d.tie_rank[:NP].long()], s, seed=5)
     assert (ka, sa) == (kd, sd) and 0 < sa < ka == int(grow.sum())
     assert a.P == d.P == NP + ka and a.layout_version == 1
-    assert torch.equal(torch.sort(d.tie_rank.long()).values, torch.arange(d.P, device=_dev()))
+    assert torch.equal(torch.sort(d.tie_rank.long()).values, torch.arange(d.P, device=gpu()))
     assert torch.equal(d.tie_rank[pd].long(), torch.sort(d.tie_rank[pd].long()).values)
-    sa_, sd_ = _snapshot(a), _snapshot(d, d.original_order())
+    sa_, sd_ = map_snapshot(a), map_snapshot(d, d.original_order())
     for k in sa_:
-        assert torch.equal(_bits(sa_[k]), _bits(sd_[k])), k
+        assert torch.equal(bits(sa_[k]), bits(sd_[k])), k
     with torch.no_grad():
         ia, id_ = render(cam, a, bg)[0], render(cam, d, bg)[0]
-    assert torch.equal(_bits(ia), _bits(id_)) and bool(torch.isfinite(ia).all())
+    assert torch.equal(bits(ia), bits(id_)) and bool(torch.isfinite(ia).all())
 
 
 @pytest.mark.parametrize("order", ["insertion", "morton"])
 def test_clone_then_prune_restores_the_map_and_training_goes_on(order):
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.synthetic import lidar_scene
-    dev = _dev()
+    dev = gpu()
     m, cam, gt, bg = _trained(_scene(), order, resort_fraction=None)             # no spare capacity: the storage grows
-    before, tie0 = _snapshot(m), (None if m._tie is None else m._tie[:NP].clone())
+    before, tie0 = map_snapshot(m), (None if m._tie is None else m._tie[:NP].clone())
     grow = torch.rand(NP, generator=torch.Generator().manual_seed(2)).to(dev) < 0.25
     with pytest.raises(ValueError, match="max_new"):
         m.densify(grow, None, max_new=int(grow.sum()) - 1)
-    assert m.P == NP and m.layout_version == 0 and all(torch.equal(_bits(v), _bits(_snapshot(m)[k])) for k, v in before.items())   # untouched
+    assert m.P == NP and m.layout_version == 0 and all(torch.equal(bits(v), bits(map_snapshot(m)[k])) for k, v in before.items())   # untouched
     k, n_split, parents = m.densify(grow, None, max_new=int(grow.sum()))         # split_scale None: every row clones
     assert k == int(grow.sum()) and n_split == 0 and m.P == NP + k and m.capacity >= NP + k
     assert torch.equal(torch.sort(parents).values, grow.nonzero().squeeze(1))
     for n in m.NAMES:
-        assert torch.equal(_bits(m._buf[n][NP:NP + k]), _bits(m._buf[n][parents])) and not bool(m._m[n][NP:NP + k].any()) and not bool(m._v[n][NP:NP + k].any())
+        assert torch.equal(bits(m._buf[n][NP:NP + k]), bits(m._buf[n][parents])) and not bool(m._m[n][NP:NP + k].any()) and not bool(m._v[n][NP:NP + k].any())
     drop = torch.zeros(m.P, dtype=torch.bool, device=dev)
     drop[NP:] = True
     n_removed, _kept = m.prune(drop=drop)
     assert n_removed == k and m.P == NP
-    after = _snapshot(m)
+    after = map_snapshot(m)
     for key in before:
-        assert torch.equal(_bits(before[key]), _bits(after[key])), key
+        assert torch.equal(bits(before[key]), bits(after[key])), key
     if tie0 is not None:
         assert torch.equal(m._tie[:NP], tie0)
     # a split densify, a fused step, then extend: ties stay a permutation of 0..P-1
@@ -619,7 +576,7 @@ def test_graphed_step_refuses_a_stale_layout_after_densify():
     gs = trainer.GraphedStep(m, cam, gt, bg, check_every=0)
     gs.step()
     assert gs.check() == 0
-    k, _s, _p = m.densify(torch.arange(m.P, device=_dev()) % 7 == 0, _median_scale(m))
+    k, _s, _p = m.densify(torch.arange(m.P, device=gpu()) % 7 == 0, _median_scale(m))
     assert k > 0
     with pytest.raises(RuntimeError, match="rows changed since this step was built"):
         gs.step()
@@ -633,12 +590,12 @@ def test_densify_before_training_setup():
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.camera import synthetic_camera
     from gaussian_lic_amd.synthetic import gt_image
-    dev = _dev()
+    dev = gpu()
     raw = _scene()
     for order in ("insertion", "morton"):
         m = trainer.GaussianModel({k: (v.clone() if torch.is_tensor(v) else v) for k, v in raw.items()}, dev, order=order, resort_fraction=None)
         assert m.optimizer is None
-        before = _snapshot(m)
+        before = map_snapshot(m)
         grow = torch.arange(NP, device=dev) % 3 == 0
         k, n_split, parents = m.densify(grow, _median_scale(m), seed=2)
         assert m.optimizer is None and k == int(grow.sum()) and 0 < n_split < k and m.P == NP + k and m.xyz.shape[0] == m.P
@@ -647,8 +604,8 @@ def test_densify_before_training_setup():
         for n in m.NAMES:
             assert not bool(m._m[n][:m.P].any()) and not bool(m._v[n][:m.P].any()), n
             if n not in ("xyz", "scaling"):
-                assert torch.equal(_bits(m._buf[n][:NP]), _bits(before[n])) and torch.equal(_bits(m._buf[n][NP:m.P]), _bits(before[n][parents])), n
-        assert torch.equal(_bits(m._buf["xyz"][NP:m.P][~split]), _bits(before["xyz"][parents[~split]]))
+                assert torch.equal(bits(m._buf[n][:NP]), bits(before[n])) and torch.equal(bits(m._buf[n][NP:m.P]), bits(before[n][parents])), n
+        assert torch.equal(bits(m._buf["xyz"][NP:m.P][~split]), bits(before["xyz"][parents[~split]]))
         m.training_setup()
         cam = synthetic_camera(W, H).to_device(dev)
         terms, _ = trainer.training_step_fused(m, cam, gt_image(H, W).to(dev), torch.zeros(3, device=dev))
@@ -666,27 +623,16 @@ def test_fused_densify_cpp_host(tmp_path, order):
     view accumulated with an error image, a densify of the rows above the median error sum (clones and splits) and two more steps, all 19 arrays
     (6 parameters, 12 moments, the tie rank) and err_sum are bit-identical to the Python model's, on both row orders."""
     from gaussian_lic_amd import trainer
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussian-lic_amd", "shim", "build_shim.py")
-    spec = importlib.util.spec_from_file_location("build_shim", path)
-    build_shim = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_check("fused_densify")
-    assert os.path.exists(exe)
+    exe = fio.build("fused_densify")
     iters, seed = 2, 11
     m, cam, gt, bg = _trained(_scene(), order, steps=0, resort_fraction=None)
     d = str(tmp_path)
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"), ("features_rest", "rest")):
-        w(n, getattr(m, k).detach().cpu().numpy())
-    if order == "morton":
-        w("tie_rank", m.tie_rank.cpu().numpy())
-    w("view", cam.world_view_transform); w("proj", cam.full_proj_transform); w("campos", cam.camera_center); w("gt", gt.cpu().numpy())
-    w("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos], np.float32))
+    fio.write_inputs(d, m, cam, gt=gt, tie_rank=m.tie_rank)
     for _ in range(iters):
         trainer.training_step_fused(m, cam, gt, bg)
     with torch.no_grad():
         err = (trainer.render(cam, m, bg)[0] - gt).abs().mean(0).contiguous()
-    w("err", err.cpu().numpy())
+    fio.write(d, "err", err)
     st = trainer.ContributionStats(m)
     st.accumulate(cam, w_min=cr.W_MIN, error=err)
     error_above = float(st.error_sum()[st.error_fixed() > 0].median())
@@ -696,15 +642,13 @@ def test_fused_densify_cpp_host(tmp_path, order):
     assert 0 < n_split < k < NP
     for _ in range(iters):
         trainer.training_step_fused(m, cam, gt, bg)
-    r = subprocess.run([exe, d, str(NP), str(W), str(H), "3", str(iters), repr(cr.W_MIN), str(lim), repr(split_scale), str(seed)], capture_output=True,
-                       text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = fio.run(exe, d, str(NP), str(W), str(H), "3", str(iters), repr(cr.W_MIN), str(lim), repr(split_scale), str(seed))
     assert f"densify added {k} splits {n_split} size {m.P}" in r.stdout
-    rd = lambda name, dt: torch.from_numpy(np.fromfile(os.path.join(d, "out_" + name), dt))
+    rd = functools.partial(fio.read, d)
     P = m.P
     for n, f in (("xyz", "xyz"), ("features_dc", "dc"), ("features_rest", "rest"), ("opacity", "opacity"), ("scaling", "scaling"), ("rotation", "rotation")):
         for pre, src in (("", m._buf), ("m_", m._m), ("v_", m._v)):
-            assert torch.equal(rd(pre + f + ".f32", np.int32), _bits(src[n][:P]).cpu().reshape(-1)), pre + f
+            assert torch.equal(rd(pre + f + ".f32", np.int32), bits(src[n][:P]).cpu().reshape(-1)), pre + f
     if order == "morton":
         assert torch.equal(rd("tie.i32", np.int32), m.tie_rank.cpu())
     else:

@@ -1,16 +1,14 @@
 """-m gpu: the camera-pose gradient under LiDAR depth supervision — gslic_rasterize_backward_depth_camera against the composed oracle
 (depth_camera_helpers), its degenerate cases, trainer.pose_gradient / training_step_with_pose with gt_depth, and the C++ host's
 gslic::FusedStep::pose_gradient(cam, gt, gt_depth, lambda_depth)."""
-import importlib.util
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
+import fused_check_io as fio
 from conftest import make_scene
 from depth_camera_helpers import CAM, GRADS, oracle_backward_depth_camera, oracle_depth
+from gpu_helpers import gpu
 from test_depth_gpu import DEPTH_CASES, POSE
 
 pytestmark = pytest.mark.gpu
@@ -25,10 +23,6 @@ CAM_TOL = 2e-4      # of max-abs per output: the bar test_camera_grad.py holds t
 # dL_dcampos 3.5e-7 / 2.4e-7 / 0 / 6.0e-7  ->  largest 2.775e-6; the bound is twice that.
 FAST_GAP_MEASURED = 2.775e-6
 FAST_TOL = 2 * FAST_GAP_MEASURED
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 class _mode:
@@ -50,7 +44,7 @@ def _fwd_depth(raw, cam):
     from gpu_helpers import settings_from
     from gaussian_lic_amd import rasterizer as rz
     from gaussian_lic_amd.synthetic import activate
-    dev = _dev()
+    dev = gpu()
     t = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in activate(raw).items()}
     rs = settings_from(cam, t["D"], dev)
     out = rz.rasterize_gaussians_depth(rs.bg, t["means"], t["opac"], t["scales"], t["rots"], rs.scale_modifier, rs.viewmatrix, rs.projmatrix,
@@ -66,7 +60,7 @@ def _bwd(f, dL_dpix, dL_ddepth, camera=True):
     gslic_rasterize_backward_camera.  Returns the tuple of device tensors."""
     from gaussian_lic_amd import rasterizer as rz
     t, rs = f["t"], f["rs"]
-    dev = _dev()
+    dev = gpu()
     geom, binning, img, sample = f["bufs"]
     if dL_ddepth is None:
         e = torch.empty(0, device=dev)
@@ -172,7 +166,7 @@ def test_depth_only_gradient_reaches_view_and_projection_not_campos():
 
 def test_empty_map_gives_zero_camera_gradients():
     from gaussian_lic_amd import rasterizer as rz
-    dev = _dev()
+    dev = gpu()
     W, H = 64, 48
     z = lambda *s: torch.zeros(*s, device=dev)
     e8 = torch.empty(0, dtype=torch.uint8, device=dev)
@@ -210,7 +204,7 @@ def test_overflowed_depth_forward_leaves_zero_camera_gradients():
     gslic_rasterize_backward_camera zeroes its outputs the same way and then adds whatever rows the scratch holds: zeros on a fresh scratch.)"""
     from gaussian_lic_amd import rasterizer as rz
     from gaussian_lic_amd.synthetic import activate
-    dev = _dev()
+    dev = gpu()
     P, W, H = 20000, 320, 240
     raw, sc, camd, cam = make_scene("random", P, W, H, 3, 6, view=POSE)
     cam.to_device(dev)
@@ -263,7 +257,7 @@ def _pose_case(view, P, W, H):
     from gaussian_lic_amd.rasterizer import render
     from gaussian_lic_amd.synthetic import gt_image
     raw, sc, _camd, _cam = make_scene("random", P, W, H, 3, 12)
-    dev = _dev()
+    dev = gpu()
     cam = synthetic_camera(W, H, view).to_device(dev)
     model = trainer.GaussianModel(raw, dev)
     gt, bg = gt_image(H, W).to(dev), torch.zeros(3, device=dev)
@@ -286,7 +280,7 @@ def test_depth_pose_gradient_matches_oracle_and_descends(oracle32, view, P, W, H
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.camera import synthetic_camera
     raw, sc, cam, model, gt, gtd, bg = _pose_case(view, P, W, H)
-    dev = _dev()
+    dev = gpu()
     camd = cam.as_dict()
     g, terms = trainer.pose_gradient(model, cam, gt, bg, gt_depth=gtd, lambda_depth=LAMBDA_D)
     g_col, terms_col = trainer.pose_gradient(model, cam, gt, bg)
@@ -343,7 +337,7 @@ def test_pose_gradient_without_depth_is_the_colour_only_path():
     raw, sc, cam, model, gt, gtd, bg = _pose_case(7, 3000, 160, 120)
     g_none, t_none = trainer.pose_gradient(model, cam, gt, bg, gt_depth=None, lambda_depth=LAMBDA_D)
     g_zero, t_zero = trainer.pose_gradient(model, cam, gt, bg, gt_depth=gtd, lambda_depth=0.0)
-    e = torch.empty(0, device=_dev())
+    e = torch.empty(0, device=gpu())
     fl = trainer._default_fused_loss()
     with torch.no_grad():
         xyz, dc, rest = model.xyz.detach(), model.features_dc.detach(), model.features_rest.detach()
@@ -370,23 +364,12 @@ def test_fused_cpp_host_depth_pose_gradient(tmp_path):
     1e-5 of max-abs, the bar test_shim_gpu.py::test_fused_cpp_host_pose_gradient holds the colour-only pair to; the three terms to float printing.
     The driver is built when missing (a build failure fails)."""
     from gaussian_lic_amd import trainer
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussian-lic_amd", "shim", "build_shim.py")
-    spec = importlib.util.spec_from_file_location("build_shim", path)
-    build_shim = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_check("fused_depth_pose")
-    assert os.path.exists(exe)
+    exe = fio.build("fused_depth_pose")
     P, W, H, deg = 20000, 320, 240, 3
     raw, sc, cam, model, gt, gtd, bg = _pose_case(7, P, W, H)
     d = str(tmp_path)
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"), ("features_rest", "rest")):
-        w(n, raw[k].numpy())
-    w("view", cam.world_view_transform); w("proj", cam.full_proj_transform); w("campos", cam.camera_center)
-    w("gt", gt.cpu().numpy()); w("gt_depth", gtd.cpu().numpy())
-    w("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos], np.float32))
-    r = subprocess.run([exe, d, str(P), str(W), str(H), str(deg), repr(LAMBDA_D)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    fio.write_inputs(d, raw, cam, gt=gt, gt_depth=gtd)
+    r = fio.run(exe, d, str(P), str(W), str(H), str(deg), repr(LAMBDA_D))
     line = lambda key: np.array([float(v) for v in [l for l in r.stdout.splitlines() if l.startswith(key)][-1].split()[1:]])
     got, got_terms = line("pose_gradient"), line("terms")
     want, terms = trainer.pose_gradient(model, cam, gt, bg, gt_depth=gtd, lambda_depth=LAMBDA_D)

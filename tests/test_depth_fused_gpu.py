@@ -1,24 +1,19 @@
 """-m gpu: LiDAR depth supervision on the fused single-GPU step — the depth loss kernel (gslic_depth_l1_loss_forward_backward), the fused-Adam
 depth backward (gslic_rasterize_backward_depth_adam), the capacity-mode depth forward (gslic_rasterize_forward_depth_capacity),
 trainer.training_step_fused / GraphedStep with gt_depth, and the C++ host's gslic::FusedStep::step with a depth target."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
+import fused_check_io as fio
 from conftest import make_scene
+from gpu_helpers import assert_same_state, gpu, model_state, training_model
 
 pytestmark = pytest.mark.gpu
 
 # a general SE(3) pose (scene moved rigidly into its frame): row 2 of the view matrix is not its column 2
 POSE = dict(ypr=(25.0, -12.0, 8.0), t=(0.4, -0.3, 0.6), place=True)
 LAMBDA_D = 0.5
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 class _mode:
@@ -39,50 +34,25 @@ class _mode:
 def _lidar_target(raw, cam, scale=1.1, stride=5):
     """A sparse LiDAR depth image: every stride-th point of the scene, pushed out to `scale` times its distance, projected (Camera.project_depth)."""
     pts = raw["xyz"][::stride].float() * scale
-    return cam.project_depth(pts).to(_dev())
+    return cam.project_depth(pts).to(gpu())
 
 
 def _setup(kind, P, W, H, deg, seed, view=None):
     import gaussian_lic_amd  # noqa: F401
     from gaussian_lic_amd.synthetic import gt_image
     raw, sc, camd, cam = make_scene(kind, P, W, H, deg, seed, view=view)
-    dev = _dev()
+    dev = gpu()
     cam.to_device(dev)
     gtd = _lidar_target(raw, cam)
     assert int((gtd > 0).sum()) > 100
     return raw, cam, gt_image(H, W, seed=seed).to(dev), gtd, torch.zeros(3, device=dev)
 
 
-def _model(raw):
-    from gaussian_lic_amd import trainer
-    m = trainer.GaussianModel({k: (v.clone() if torch.is_tensor(v) else v) for k, v in raw.items()}, _dev())
-    m.training_setup()
-    return m
-
-
-def _state(m):
-    """Parameters and both Adam moments of every group, as host copies."""
-    out = {}
-    for i, n in enumerate(m.NAMES):
-        out[n] = getattr(m, n).detach().cpu().clone()
-        st = m.optimizer.state[i]
-        if st is not None:
-            out[n + ".m"] = st["exp_avg"].cpu().clone()
-            out[n + ".v"] = st["exp_avg_sq"].cpu().clone()
-    return out
-
-
-def _assert_same_state(a, b):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert torch.equal(a[k], b[k]), k
-
-
 # ---------------------------------------------------------------------------------------------------- 1. the loss kernel
 @pytest.mark.parametrize("H,W", [(240, 320), (77, 131), (1, 5000)])
 def test_depth_loss_kernel_matches_autograd(H, W):
     from gaussian_lic_amd import loss
-    dev = _dev()
+    dev = gpu()
     g = torch.Generator().manual_seed(H * 7 + W)
     depth = (torch.rand(H, W, generator=g) * 10.0).to(dev)
     gt = (torch.rand(H, W, generator=g) * 10.0)
@@ -115,13 +85,13 @@ def test_fused_depth_adam_is_bit_identical(strict, kind, P, W, H, deg, seed, vie
     from gaussian_lic_amd import trainer
     raw, cam, gt, gtd, bg = _setup(kind, P, W, H, deg, seed, view)
     with _mode(strict):
-        a, b = _model(raw), _model(raw)
+        a, b = training_model(raw), training_model(raw)
         for _ in range(4):
             ta, va = trainer.training_step_fused(a, cam, gt, bg, gt_depth=gtd, lambda_depth=LAMBDA_D, adam_in_backward=True)
             tb, vb = trainer.training_step_fused(b, cam, gt, bg, gt_depth=gtd, lambda_depth=LAMBDA_D, adam_in_backward=False)
             assert torch.equal(va, vb) and bool(va.any())
             assert ta.numel() == 3 and torch.equal(ta, tb)
-    _assert_same_state(_state(a), _state(b))
+    assert_same_state(model_state(a), model_state(b))
 
 
 # ---------------------------------------------------------------------------------------------------- 3. against the autograd depth step
@@ -130,7 +100,7 @@ def test_fused_depth_step_matches_autograd_depth_step(strict):
     from gaussian_lic_amd import trainer
     raw, cam, gt, gtd, bg = _setup("random", 30000, 320, 240, 3, 61)
     with _mode(strict):
-        a, b = _model(raw), _model(raw)
+        a, b = training_model(raw), training_model(raw)
         loss, vis = trainer.training_step(a, cam, gt, bg, do_step=False, raw_render=False, gt_depth=gtd, lambda_depth=LAMBDA_D)
         ref = [p.grad.clone() for p in a.parameters()]
         captured = {}
@@ -153,16 +123,16 @@ def test_fused_depth_step_matches_autograd_depth_step(strict):
 def test_depth_off_is_the_colour_only_fused_step(adam_in_backward):
     from gaussian_lic_amd import trainer
     raw, cam, gt, gtd, bg = _setup("random", 20000, 320, 240, 3, 62)
-    ref, none_, zero = _model(raw), _model(raw), _model(raw)
+    ref, none_, zero = training_model(raw), training_model(raw), training_model(raw)
     for _ in range(3):
         t0, v0 = trainer.training_step_fused(ref, cam, gt, bg, adam_in_backward=adam_in_backward)
         t1, v1 = trainer.training_step_fused(none_, cam, gt, bg, adam_in_backward=adam_in_backward, gt_depth=None, lambda_depth=LAMBDA_D)
         t2, v2 = trainer.training_step_fused(zero, cam, gt, bg, adam_in_backward=adam_in_backward, gt_depth=gtd, lambda_depth=0.0)
         assert t0.numel() == t1.numel() == t2.numel() == 2
         assert torch.equal(v0, v1) and torch.equal(v0, v2)
-    s = _state(ref)
-    _assert_same_state(s, _state(none_))
-    _assert_same_state(s, _state(zero))
+    s = model_state(ref)
+    assert_same_state(s, model_state(none_))
+    assert_same_state(s, model_state(zero))
 
 
 # ---------------------------------------------------------------------------------------------------- 5. capacity-mode depth forward
@@ -178,13 +148,13 @@ def _fwd_args(m, cam):
 def test_capacity_depth_forward_is_the_depth_forward(strict, kind, P, W, H, deg, seed, view):
     from gaussian_lic_amd import rasterizer as rz
     raw, cam, gt, gtd, bg = _setup(kind, P, W, H, deg, seed, view)
-    m = _model(raw)
+    m = training_model(raw)
     xyz, dc, rest, op, sc, rot, scal = _fwd_args(m, cam)
     with _mode(strict), torch.no_grad():
         R, B, color, final_T, depth, radii = rz.rasterize_gaussians_depth(
             bg, xyz, op, sc, rot, 1.0, cam.d_world_view_transform, cam.d_full_proj_transform, scal[0], scal[1], H, W, *scal[2:], dc, rest, deg,
             cam.d_camera_center, raw_params=True)[:6]
-        bufs = rz.CapacityBuffers(P, W, H, R + 1000, B + 100, _dev(), depth=True)
+        bufs = rz.CapacityBuffers(P, W, H, R + 1000, B + 100, gpu(), depth=True)
         cR, cB, c2, T2, d2, r2 = rz.rasterize_gaussians_depth_capacity(bufs, bg, xyz, op, sc, rot, 1.0, cam.d_world_view_transform,
                                                                        cam.d_full_proj_transform, *scal, dc, rest, deg, cam.d_camera_center,
                                                                        raw_params=True)[:6]
@@ -202,9 +172,9 @@ def test_capacity_depth_overflow_is_a_noop():
     from gaussian_lic_amd.loss import FusedLoss
     raw, cam, gt, gtd, bg = _setup("random", 25000, 320, 240, 3, 83)
     P, W, H = 25000, 320, 240
-    m = _model(raw)
+    m = training_model(raw)
     m.optimizer.fused_descriptor()   # (creates the zero moments)
-    before = _state(m)
+    before = model_state(m)
     xyz, dc, rest, op, sc, rot, scal = _fwd_args(m, cam)
     fl = FusedLoss(0.2)
     with torch.no_grad():
@@ -212,7 +182,7 @@ def test_capacity_depth_overflow_is_a_noop():
                                             *scal[2:], dc, rest, 3, cam.d_camera_center, raw_params=True)[:2]
     assert R > 4000 and B > 8
     for cap_R, cap_B, bit in ((R // 4, B + 100, 1), (R + 1000, B // 4, 2)):
-        bufs = rz.CapacityBuffers(P, W, H, cap_R, cap_B, _dev(), depth=True)
+        bufs = rz.CapacityBuffers(P, W, H, cap_R, cap_B, gpu(), depth=True)
         with torch.no_grad():
             (cR, cB, image, _T, depth, radii, geom, binning, img, sample) = rz.rasterize_gaussians_depth_capacity(
                 bufs, bg, xyz, op, sc, rot, 1.0, cam.d_world_view_transform, cam.d_full_proj_transform, *scal, dc, rest, 3, cam.d_camera_center,
@@ -224,7 +194,7 @@ def test_capacity_depth_overflow_is_a_noop():
                                                   adam=m.optimizer.fused_descriptor())
         _r, _b, bits, good = bufs.read_status()
         assert bits & bit and good == 0, (cap_R, cap_B, bits)
-        _assert_same_state(before, _state(m))
+        assert_same_state(before, model_state(m))
 
 
 # ---------------------------------------------------------------------------------------------------- 6. GraphedStep with depth
@@ -235,10 +205,10 @@ def test_graphed_depth_step_equals_eager_depth_steps(use_graph):
     from gaussian_lic_amd.synthetic import gt_image
     raw, cam, gt, gtd, bg = _setup("random", 30000, 320, 240, 3, 91)
     W, H = 320, 240
-    cams = [synthetic_camera(W, H, k).to_device(_dev()) for k in range(3)]
-    gts = [gt_image(H, W, seed=40 + k).to(_dev()) for k in range(3)]
+    cams = [synthetic_camera(W, H, k).to_device(gpu()) for k in range(3)]
+    gts = [gt_image(H, W, seed=40 + k).to(gpu()) for k in range(3)]
     gtds = [_lidar_target(raw, c, scale=1.05 + 0.05 * k) for k, c in enumerate(cams)]
-    a, b = _model(raw), _model(raw)
+    a, b = training_model(raw), training_model(raw)
     gs = trainer.GraphedStep(a, cams[0], gts[0], bg, use_graph=use_graph, gt_depth=gtds[0], lambda_depth=LAMBDA_D)
     eager_terms, graphed_terms = [], []
     for k in (0, 1, 2, 1):
@@ -247,7 +217,7 @@ def test_graphed_depth_step_equals_eager_depth_steps(use_graph):
     assert gs.check() == 0
     for x, y in zip(graphed_terms, eager_terms):
         assert x.numel() == 3 and torch.equal(x, y)
-    _assert_same_state(_state(a), _state(b))
+    assert_same_state(model_state(a), model_state(b))
 
 
 @pytest.mark.parametrize("use_graph", [False, True])
@@ -256,14 +226,14 @@ def test_graphed_depth_step_repeats_overflowed_steps_with_their_own_targets(use_
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.camera import synthetic_camera
     from gaussian_lic_amd.synthetic import gt_image
-    dev = _dev()
+    dev = gpu()
     P, W, H = 40000, 320, 240
     raw, sc, camd, cam0 = make_scene("random", P, W, H, 3, 8)
     cams = [synthetic_camera(W, H, k).to_device(dev) for k in range(8)]
     gts = [gt_image(H, W, seed=10 + k).to(dev) for k in range(8)]
     gtds = [_lidar_target(raw, c) for c in cams]
     bg = torch.zeros(3, device=dev)
-    probe, e, Rs = _model(raw), torch.empty(0, device=dev), []
+    probe, e, Rs = training_model(raw), torch.empty(0, device=dev), []
     with torch.no_grad():
         for c in cams:
             Rs.append(rz.rasterize_gaussians(bg, probe.xyz.detach(), e, probe.opacity.detach(), probe.scaling.detach(), probe.rotation.detach(), 1.0, e,
@@ -273,7 +243,7 @@ def test_graphed_depth_step_repeats_overflowed_steps_with_their_own_targets(use_
     cap_R = (max(Rs) + sorted(Rs)[len(Rs) // 2]) // 2      # the larger views do not fit
     fits = [r <= cap_R - 64 for r in Rs]
     assert any(fits) and not all(fits)
-    model = _model(raw)
+    model = training_model(raw)
     first = fits.index(True)
     gs = trainer.GraphedStep(model, cams[first], gts[first], bg, check_every=0, cap_R=cap_R, use_graph=use_graph, gt_depth=gtds[first],
                              lambda_depth=LAMBDA_D)
@@ -283,13 +253,13 @@ def test_graphed_depth_step_repeats_overflowed_steps_with_their_own_targets(use_
     failed = [k for k in range(8) if (mask >> k) & 1]
     assert issued == 8 and failed
     assert gs.check() == len(failed) and gs.recaptures >= 1
-    eager = _model(raw)
+    eager = training_model(raw)
     for k in [k for k in range(8) if k not in failed] + failed:
         trainer.training_step_fused(eager, cams[k], gts[k], bg, gt_depth=gtds[k], lambda_depth=LAMBDA_D)
-    _assert_same_state(_state(model), _state(eager))
+    assert_same_state(model_state(model), model_state(eager))
 
     # a depth target modified in place after its (overflowed) step was issued: the repeat refuses
-    model2 = _model(raw)
+    model2 = training_model(raw)
     gs2 = trainer.GraphedStep(model2, cams[first], gts[first], bg, check_every=0, cap_R=cap_R, use_graph=use_graph, gt_depth=gtds[first],
                               lambda_depth=LAMBDA_D)
     k_bad = int(np.argmax(Rs))
@@ -301,42 +271,25 @@ def test_graphed_depth_step_repeats_overflowed_steps_with_their_own_targets(use_
 
 
 # ---------------------------------------------------------------------------------------------------- 7. the C++ host
-def _write_case(d, raw, cam, gt, gtd):
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"),
-                 ("features_rest", "rest")):
-        w(n, raw[k].numpy())
-    w("view", cam.world_view_transform); w("proj", cam.full_proj_transform); w("campos", cam.camera_center)
-    w("gt", gt.cpu().numpy()); w("gt_depth", gtd.cpu().numpy())
-    w("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos], np.float32))
-
-
 @pytest.mark.parametrize("deg", [3, 0])
 def test_fused_depth_cpp_host(tmp_path, deg):
     """gslic::FusedStep::step(cam, gt, gt_depth, lambda_depth) issues the C-ABI calls of training_step_fused(gt_depth=, lambda_depth=): image, depth,
     terms and parameters after four steps are bit-identical to the Python host's.  The driver is built when missing (a build failure fails)."""
-    import importlib.util
     import gaussian_lic_amd  # noqa: F401
     from gaussian_lic_amd import trainer
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussian-lic_amd", "shim", "build_shim.py")
-    spec = importlib.util.spec_from_file_location("build_shim", path)
-    build_shim = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_check("fused_depth")
-    assert os.path.exists(exe)
+    exe = fio.build("fused_depth")
     P, W, H, iters = 30000, 320, 240, 4
     raw, cam, gt, gtd, bg = _setup("random", P, W, H, deg, 44)
     d = str(tmp_path)
-    _write_case(d, raw, cam, gt, gtd)
-    r = subprocess.run([exe, d, str(P), str(W), str(H), str(deg), str(iters), repr(LAMBDA_D)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    model = _model(raw)
+    fio.write_inputs(d, raw, cam, gt=gt, gt_depth=gtd)
+    r = fio.run(exe, d, str(P), str(W), str(H), str(deg), str(iters), repr(LAMBDA_D))
+    model = training_model(raw)
     fl = trainer._default_fused_loss()
     losses = []
     for _ in range(iters):
         terms, _vis = trainer.training_step_fused(model, cam, gt, bg, gt_depth=gtd, lambda_depth=LAMBDA_D)
         losses.append(float(fl.value(terms, LAMBDA_D)))
-    rd = lambda name, shape: np.fromfile(os.path.join(d, f"out_{name}.f32"), np.float32).reshape(shape)
+    rd = lambda name, shape: fio.read(d, name + ".f32", np.float32).numpy().reshape(shape)
     np.testing.assert_array_equal(rd("terms", (3,)), terms.cpu().numpy())
     names = [("xyz", model.xyz), ("scaling", model.scaling), ("rotation", model.rotation), ("opacity", model.opacity), ("dc", model.features_dc)]
     if deg > 0:
@@ -353,7 +306,7 @@ def test_fused_depth_supervision_pulls_the_map_toward_the_target_depth():
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.loss import depth_l1
     from gaussian_lic_amd.rasterizer import render
-    dev = _dev()
+    dev = gpu()
     W, H = 160, 120
     raw, sc, camd, cam = make_scene("random", 3000, W, H, 3, 10)
     cam.to_device(dev)
@@ -365,7 +318,7 @@ def test_fused_depth_supervision_pulls_the_map_toward_the_target_depth():
         gt, _, _, _, _, gtd = render(cam, trainer.GaussianModel(tgt, dev), bg, return_depth=True)
 
     def run(lam):
-        m = _model(raw)
+        m = training_model(raw)
         with torch.no_grad():
             d0 = float(depth_l1(render(cam, m, bg, return_depth=True)[5], gtd))
         for _ in range(50):
@@ -384,9 +337,9 @@ def test_fused_depth_supervision_pulls_the_map_toward_the_target_depth():
 def test_fused_depth_step_refuses_multi_gpu(monkeypatch):
     from gaussian_lic_amd import trainer
     raw, cam, gt, gtd, bg = _setup("random", 5000, 160, 120, 3, 5)
-    m = _model(raw)
-    before = _state(m)
+    m = training_model(raw)
+    before = model_state(m)
     monkeypatch.setattr(trainer, "_dist_on", lambda: True)
     with pytest.raises(NotImplementedError, match="N > 1"):
         trainer.training_step_fused(m, cam, gt, bg, gt_depth=gtd, lambda_depth=LAMBDA_D)
-    _assert_same_state(before, _state(m))
+    assert_same_state(before, model_state(m))

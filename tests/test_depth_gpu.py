@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import assert_close_flips, make_scene, rel_err
+from gpu_helpers import gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -23,10 +24,6 @@ DEPTH_CASES = [
 # (V[8], V[9], V[10]) and V[2], V[6] are non-zero, so a transposed or mis-indexed view-row chain cannot pass
 POSE = dict(ypr=(25.0, -12.0, 8.0), t=(0.4, -0.3, 0.6), place=True)
 GRADS = ("dL_dmean2D", "dL_dcolor", "dL_dopacity", "dL_dmean3D", "dL_dcov3D", "dL_ddc", "dL_dsh", "dL_dscale", "dL_drot")
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 class _mode:
@@ -47,7 +44,7 @@ class _mode:
 def _inputs(raw, cam, raw_params=False):
     from gpu_helpers import settings_from
     from gaussian_lic_amd.synthetic import activate
-    dev = _dev()
+    dev = gpu()
     act = {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in activate(raw).items()}
     rs = settings_from(cam, act["D"], dev)
     if raw_params:
@@ -72,7 +69,7 @@ def fwd_depth(raw, cam, raw_params=False):
 def fwd_plain(raw, cam, raw_params=False):
     from gaussian_lic_amd import rasterizer as rz
     t, rs = _inputs(raw, cam, raw_params)
-    e = torch.empty(0, device=_dev())
+    e = torch.empty(0, device=gpu())
     out = rz.rasterize_gaussians(rs.bg, t["means"], e, t["opac"], t["scales"], t["rots"], rs.scale_modifier, e, rs.viewmatrix, rs.projmatrix,
                                  rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.limx_neg, rs.limx_pos, rs.limy_neg, rs.limy_pos,
                                  t["dc"], t["shs"], t["D"], rs.campos, False, False, False, raw_params=raw_params)
@@ -85,7 +82,7 @@ def bwd(f, dL_dpix, dL_ddepth=None):
     """dL_ddepth None: the colour-only gslic_rasterize_backward on f's buffers; else gslic_rasterize_backward_depth."""
     from gaussian_lic_amd import rasterizer as rz
     t, rs = f["t"], f["rs"]
-    dev = _dev()
+    dev = gpu()
     geom, binning, img, sample = f["bufs"]
     if dL_ddepth is None:
         e = torch.empty(0, device=dev)
@@ -361,7 +358,7 @@ def test_render_return_depth_autograd_matches_the_c_abi(raw_path):
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.rasterizer import render
     from gaussian_lic_amd.synthetic import activate, pixel_grad
-    dev = _dev()
+    dev = gpu()
     W, H = 200, 150
     raw, sc, camd, cam = make_scene("random", 8000, W, H, 3, 6)
     cam.to_device(dev)
@@ -394,7 +391,7 @@ def test_morton_model_depth_is_bit_identical():
     from gaussian_lic_amd.camera import synthetic_camera
     from gaussian_lic_amd.rasterizer import render
     from gaussian_lic_amd.synthetic import random_scene
-    dev = _dev()
+    dev = gpu()
     W, H = 320, 192
     raw = random_scene(30000, W, H, sh_degree=3, seed=5)
     z = raw["xyz"][:, 2]
@@ -418,7 +415,7 @@ def _params(m):
 def test_training_step_lambda_depth_zero_is_the_colour_step():
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.synthetic import gt_image
-    dev = _dev()
+    dev = gpu()
     W, H = 160, 120
     raw, sc, camd, cam = make_scene("random", 5000, W, H, 3, 9)
     cam.to_device(dev)
@@ -441,7 +438,7 @@ def test_depth_supervision_pulls_the_map_toward_the_target_depth():
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.loss import depth_l1
     from gaussian_lic_amd.rasterizer import render
-    dev = _dev()
+    dev = gpu()
     W, H = 160, 120
     raw, sc, camd, cam = make_scene("random", 3000, W, H, 3, 10)
     cam.to_device(dev)
@@ -493,7 +490,7 @@ def test_depth_edge_cases(oracle32):
     from gaussian_lic_amd import rasterizer as rz
     from gaussian_lic_amd.synthetic import pixel_grad
     from gpu_helpers import npy
-    dev = _dev()
+    dev = gpu()
     # P = 0
     e3 = torch.empty(0, 3, device=dev)
     out = rz.rasterize_gaussians_depth(torch.zeros(3, device=dev), e3, torch.empty(0, 1, device=dev), e3, torch.empty(0, 4, device=dev), 1.0,

@@ -5,10 +5,7 @@ References, none of them the code under test: the plain and the error-weighted e
 test_contribution_gpu.py / test_densify_gpu.py) for everything that is bit for bit, torch comparisons on the exported float32 depths for the
 predicate, torch indexing for everything that moves rows, and the float64 replay of tests/freespace_ref.py for the one toleranced test.  All
 forwards run in strict arithmetic.  Scenes a, b, c and the Morton twin d: contribution_ref.scene."""
-import importlib.util
-import os
-import subprocess
-import types
+import functools
 
 import numpy as np
 import pytest
@@ -16,41 +13,17 @@ import torch
 
 import contribution_ref as cr
 import freespace_ref as fr
+import fused_check_io as fio
+from gpu_helpers import SENTINEL, bits, export_lists, gpu, guarded, raw_forward, same_tensors, scene_model
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A
 INF, NAN = float("inf"), float("nan")
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _bits(x):
-    return x.contiguous().view(torch.int32)
-
-
-def _model(name, order="insertion", **kw):
-    import gaussian_lic_amd  # noqa: F401
-    from gaussian_lic_amd import trainer
-    from gaussian_lic_amd.camera import synthetic_camera
-    raw, W, H = cr.scene(name)
-    m = trainer.GaussianModel(cr._clone(raw), _dev(), order=order, **kw)
-    return m, synthetic_camera(W, H).to_device(_dev())
-
-
-def _forward(m, cam, depth=False, bufs=None):
-    from gaussian_lic_amd import trainer
-    fwd = trainer._RawRaster(m, cam, torch.zeros(3, device=_dev()), depth=depth)
-    with torch.no_grad():
-        fwd.forward(bufs)
-    return fwd
 
 
 def _const(fwd_or_hw, value):
     H, W = fwd_or_hw if isinstance(fwd_or_hw, tuple) else fwd_or_hw.hw
-    return torch.full((int(H), int(W)), float(value), device=_dev())
+    return torch.full((int(H), int(W)), float(value), device=gpu())
 
 
 def _five(m, fwd, near=None, error=None):
@@ -68,28 +41,15 @@ def _five(m, fwd, near=None, error=None):
     return out
 
 
-def _same(a, b):
-    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
-
-
-def _export(m, cam, fwd, what):
-    from gaussian_lic_amd import rasterizer as rz
-    H, W = fwd.hw
-    rs = types.SimpleNamespace(image_height=H, image_width=W, sh_degree=m.sh_degree, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, limx_neg=cam.limx_neg,
-                               limx_pos=cam.limx_pos, limy_neg=cam.limy_neg, limy_pos=cam.limy_pos, scale_modifier=1.0, no_color=False)
-    R, B, _radii, geom, binning, img, sample = fwd.state
-    return rz.debug_export(rs, m.P, 0, R, B, geom, binning, img, sample, what=what)
-
-
 @pytest.fixture(scope="module")
 def views():
     """Per scene: the model, the camera, one plain forward, the plain entry point's arrays and the exported float32 depths — computed once, left
     unchanged."""
     out = {}
     for name in ("a", "b"):
-        m, cam = _model(name)
-        fwd = _forward(m, cam)
-        z = _export(m, cam, fwd, ("depths",))["depths"].cpu().clone()
+        m, cam = scene_model(name)
+        fwd = raw_forward(m, cam)
+        z = export_lists(m, cam, fwd, ("depths",))["depths"].cpu().clone()
         out[name] = (m, cam, fwd, _five(m, fwd), z)
     return out
 
@@ -101,13 +61,13 @@ def test_constant_bounds(views, name):
     assert bool(plain[2].any()) and not bool(plain[3].any()) and not bool(plain[4].any())       # zeros before the first use
     inf = _five(m, fwd, _const(fwd, INF))
     assert torch.equal(inf[3], inf[2]) and torch.equal(inf[4], inf[2])                           # +inf: free == meas == sum_w, bits
-    assert _same(inf[:3], plain[:3])                                                             # the base three: the plain entry point's bits
+    assert same_tensors(inf[:3], plain[:3])                                                             # the base three: the plain entry point's bits
     for v in (0.0, NAN, -1.0):
         got = _five(m, fwd, _const(fwd, v))
         assert not bool(got[3].any()) and not bool(got[4].any()), v
-        assert _same(got[:3], plain[:3]), v
+        assert same_tensors(got[:3], plain[:3]), v
     tiny = _five(m, fwd, _const(fwd, 1e-30))                                                     # measured, and in front of everything
-    assert torch.equal(tiny[4], plain[2]) and not bool(tiny[3].any()) and _same(tiny[:3], plain[:3])
+    assert torch.equal(tiny[4], plain[2]) and not bool(tiny[3].any()) and same_tensors(tiny[:3], plain[:3])
 
 
 @pytest.mark.parametrize("name", ["a", "b"])
@@ -141,13 +101,13 @@ def _mask_images(H, W, busiest):
 def test_zero_inf_masks_equal_the_error_entry_point(views, name):
     m, cam, fwd, plain, _z = views[name]
     H, W = fwd.hw
-    busiest = int(_export(m, cam, fwd, ("n_contrib",))["n_contrib"].reshape(-1).argmax())
+    busiest = int(export_lists(m, cam, fwd, ("n_contrib",))["n_contrib"].reshape(-1).argmax())
     for kind, mask in _mask_images(int(H), int(W), busiest).items():
-        near = torch.where(mask, torch.tensor(INF), torch.tensor(0.0)).to(_dev())
+        near = torch.where(mask, torch.tensor(INF), torch.tensor(0.0)).to(gpu())
         got = _five(m, fwd, near)
-        err = _five(m, fwd, None, error=mask.float().to(_dev()))[5]
+        err = _five(m, fwd, None, error=mask.float().to(gpu()))[5]
         assert torch.equal(got[3], err) and torch.equal(got[4], err), kind
-        assert _same(got[:3], plain[:3]), kind
+        assert same_tensors(got[:3], plain[:3]), kind
         assert bool(err.any()) and not torch.equal(err, plain[2]), kind
 
 
@@ -156,14 +116,9 @@ def test_guard_words_and_absent_base_outputs(views):
     m, _cam, fwd, plain, _z = views["a"]
     P, (H, W) = m.P, fwd.hw
     R, B, _r, geom, binning, img, _s = fwd.state
-    near = fr.bound_image("a").to(_dev())
+    near = fr.bound_image("a").to(gpu())
     want = _five(m, fwd, near)
-
-    def guarded(dtype):
-        g = torch.full((P + 128,), SENTINEL, dtype=dtype, device=_dev())
-        g[64:64 + P] = 0
-        return g, g[64:64 + P]
-    g = [guarded(torch.int32), guarded(torch.int32), guarded(torch.int64), guarded(torch.int64), guarded(torch.int64)]
+    g = [guarded(P, torch.int32, 0), guarded(P, torch.int32, 0), guarded(P, torch.int64, 0), guarded(P, torch.int64, 0), guarded(P, torch.int64, 0)]
     rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, cr.W_MIN, g[0][1], g[1][1], g[2][1], near_bound=near, free_sum=g[3][1], meas_sum=g[4][1])
     torch.cuda.synchronize()
     for whole, _v in g:
@@ -172,11 +127,11 @@ def test_guard_words_and_absent_base_outputs(views):
     assert torch.equal(g[3][1].cpu(), want[3]) and torch.equal(g[4][1].cpu(), want[4]) and bool(want[3].any())
     assert not torch.equal(want[3], want[4]) and not torch.equal(want[4], plain[2])
     # the base three all absent: the two sums are still accumulated
-    f2, m2 = torch.zeros(P, dtype=torch.int64, device=_dev()), torch.zeros(P, dtype=torch.int64, device=_dev())
+    f2, m2 = torch.zeros(P, dtype=torch.int64, device=gpu()), torch.zeros(P, dtype=torch.int64, device=gpu())
     rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, cr.W_MIN, None, None, None, near_bound=near, free_sum=f2, meas_sum=m2)
     assert torch.equal(f2.cpu(), want[3]) and torch.equal(m2.cpu(), want[4])
     # any one of them absent
-    only = torch.zeros(P, dtype=torch.int32, device=_dev())
+    only = torch.zeros(P, dtype=torch.int32, device=gpu())
     f3, m3 = torch.zeros_like(f2), torch.zeros_like(m2)
     rz.contribution_accumulate(P, H, W, R, B, geom, binning, img, cr.W_MIN, None, only, None, near_bound=near, free_sum=f3, meas_sum=m3)
     assert torch.equal(only.cpu().long(), plain[1]) and torch.equal(f3.cpu(), want[3]) and torch.equal(m3.cpu(), want[4])
@@ -186,11 +141,11 @@ def test_runs_repeat_and_views_add_as_integers(views):
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.camera import synthetic_camera
     m, cam1, fwd, _plain, _z = views["a"]
-    cam2 = synthetic_camera(cr.W_A, cr.H_A, 5).to_device(_dev())
-    near = fr.bound_image("a").to(_dev())
+    cam2 = synthetic_camera(cr.W_A, cr.H_A, 5).to_device(gpu())
+    near = fr.bound_image("a").to(gpu())
     one, again = _five(m, fwd, near), _five(m, fwd, near)
-    assert _same(one, again) and bool(one[3].any())
-    two = _five(m, _forward(m, cam2), near)
+    assert same_tensors(one, again) and bool(one[3].any())
+    two = _five(m, raw_forward(m, cam2), near)
     assert not torch.equal(one[3], two[3]) and not torch.equal(one[4], two[4])
     st = trainer.ContributionStats(m)
     st.accumulate(cam1, w_min=cr.W_MIN, free_space=near)
@@ -211,51 +166,51 @@ def test_every_forward_and_binning_path_gives_the_same_sums(views, name):
     from gaussian_lic_amd.rasterizer import CapacityBuffers
     m, cam, fwd, _plain, _z = views[name]
     H, W = fwd.hw
-    near = fr.bound_image(name).to(_dev())
+    near = fr.bound_image(name).to(gpu())
     want = _five(m, fwd, near)
     assert bool(want[3].any())
     old = _lib.set_binning_mode("radix")
     try:
         for mode in ("radix", "atomic"):
             _lib.set_binning_mode(mode)
-            assert _same(want, _five(m, _forward(m, cam), near)), mode
+            assert same_tensors(want, _five(m, raw_forward(m, cam), near)), mode
     finally:
         _lib.set_binning_mode(old)
-    assert _same(want, _five(m, _forward(m, cam, depth=True), near)), "depth forward"
+    assert same_tensors(want, _five(m, raw_forward(m, cam, depth=True), near)), "depth forward"
     for depth in (False, True):
-        bufs = CapacityBuffers(m.P, W, H, 4096, 256, _dev(), depth=depth)
-        _forward(m, cam, depth=depth, bufs=bufs)
-        assert bufs.read_status()[2] == 0 and _same(want, _five(m, bufs, near)), f"capacity forward, depth={depth}"
-    small = CapacityBuffers(m.P, W, H, max(fwd.state[0] // 3, 1), 256, _dev())                   # the lists do not fit: nothing is touched
-    _forward(m, cam, bufs=small)
+        bufs = CapacityBuffers(m.P, W, H, 4096, 256, gpu(), depth=depth)
+        raw_forward(m, cam, depth=depth, bufs=bufs)
+        assert bufs.read_status()[2] == 0 and same_tensors(want, _five(m, bufs, near)), f"capacity forward, depth={depth}"
+    small = CapacityBuffers(m.P, W, H, max(fwd.state[0] // 3, 1), 256, gpu())                   # the lists do not fit: nothing is touched
+    raw_forward(m, cam, bufs=small)
     assert small.read_status()[2] != 0 and not any(bool(t.any()) for t in _five(m, small, near))
 
 
 def test_nothing_in_view_leaves_zeros():
-    m, cam = _model("c")
-    fwd = _forward(m, cam)
+    m, cam = scene_model("c")
+    fwd = raw_forward(m, cam)
     assert fwd.state[0] == 0
     assert not any(bool(t.any()) for t in _five(m, fwd, _const(fwd, INF)))
 
 
 def test_both_row_orders_give_the_same_statistics(views):
     a, cam, fwd, _plain, _z = views["a"]
-    d, _cam = _model("a", order="morton")
+    d, _cam = scene_model("a", order="morton")
     assert not torch.equal(d.tie_rank.long().cpu(), torch.arange(d.P))                           # the rows really are permuted
-    near = fr.bound_image("a").to(_dev())
-    sa, sd = _five(a, fwd, near), _five(d, _forward(d, cam), near)
+    near = fr.bound_image("a").to(gpu())
+    sa, sd = _five(a, fwd, near), _five(d, raw_forward(d, cam), near)
     order = d.original_order().cpu()
-    assert _same(sa, [t[order] for t in sd]) and bool(sa[3].any())
+    assert same_tensors(sa, [t[order] for t in sd]) and bool(sa[3].any())
 
 
 def test_both_images_in_one_call(views):
     from gaussian_lic_amd import trainer
     m, cam, fwd, plain, _z = views["a"]
-    near = fr.bound_image("a").to(_dev())
-    err = (2.0 * torch.rand(cr.H_A, cr.W_A, generator=torch.Generator().manual_seed(41))).to(_dev())
+    near = fr.bound_image("a").to(gpu())
+    err = (2.0 * torch.rand(cr.H_A, cr.W_A, generator=torch.Generator().manual_seed(41))).to(gpu())
     free_only, err_only = _five(m, fwd, near), _five(m, fwd, None, error=err)
     both = _five(m, fwd, near, error=err)                                                        # (_five asserts views == 1)
-    assert _same(both[:3], plain[:3])                                                            # nothing is counted twice
+    assert same_tensors(both[:3], plain[:3])                                                            # nothing is counted twice
     assert torch.equal(both[3], free_only[3]) and torch.equal(both[4], free_only[4]) and torch.equal(both[5], err_only[5])
     st = trainer.ContributionStats(m)
     st.accumulate(cam, w_min=cr.W_MIN, error=err, free_space=near)
@@ -278,8 +233,8 @@ def test_random_bound_against_the_float64_replay(views, name):
     m, cam, fwd, _plain, z = views[name]
     H, W = fwd.hw
     near = fr.bound_image(name)
-    got = _five(m, fwd, near.to(_dev()))
-    d = _export(m, cam, fwd, ("means2D", "conic_opacity", "point_list", "ranges", "n_contrib"))
+    got = _five(m, fwd, near.to(gpu()))
+    d = export_lists(m, cam, fwd, ("means2D", "conic_opacity", "point_list", "ranges", "n_contrib"))
     n = lambda k: d[k].cpu().numpy()
     rep = fr.replay(n("means2D"), n("conic_opacity"), n("point_list"), n("ranges"), n("n_contrib"), W, H, m.P, z.numpy(), near.numpy())
     shares = fr.class_shares(rep)
@@ -304,7 +259,7 @@ def _trained(order, steps=1, **kw):
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.camera import synthetic_camera
     from gaussian_lic_amd.synthetic import gt_image, random_scene
-    dev = _dev()
+    dev = gpu()
     m = trainer.GaussianModel(random_scene(NP, W, H, sh_degree=3, seed=3), dev, order=order, **kw)
     m.training_setup()
     cam = synthetic_camera(W, H).to_device(dev)
@@ -319,13 +274,13 @@ def _near_for(cam, m, seed=7):
     g = torch.Generator().manual_seed(seed)
     near = 1.0 + 29.0 * torch.rand(H, W, generator=g)
     near[torch.rand(H, W, generator=g) < 0.25] = 0.0
-    return near.to(_dev())
+    return near.to(gpu())
 
 
 def test_attached_statistics_follow_prune_extend_densify_resort():
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.synthetic import lidar_scene
-    dev = _dev()
+    dev = gpu()
     m, cam, gt, bg = _trained("morton", capacity=3 * NP, resort_fraction=None)
     near = _near_for(cam, m)
     st = trainer.ContributionStats(m)
@@ -352,14 +307,14 @@ def test_attached_statistics_follow_prune_extend_densify_resort():
     before = arrays()
     perm = m.resort()
     assert not torch.equal(perm.cpu(), torch.arange(m.P))
-    assert _same(arrays(), [t[perm] for t in before]) and st.views == 2
+    assert same_tensors(arrays(), [t[perm] for t in before]) and st.views == 2
     # prune by the floater mask: the kept rows
     before = arrays()
     mask = st.floater_mask(0.5, min_measured=0.01)
     assert torch.equal(mask, trainer.contribution_floater_mask(st.free_fixed(), st.measured_fixed(), 0.5, 0.01)) and 0 < int(mask.sum()) < m.P
     removed, kept = m.prune(drop=mask)
     assert removed == int(mask.sum())
-    assert _same(arrays(), [t[kept] for t in before])
+    assert same_tensors(arrays(), [t[kept] for t in before])
     assert not bool(st._free[m.P:].any()) and not bool(st._meas[m.P:].any())
     # extend: appended rows are zero
     before, P0 = arrays(), m.P
@@ -374,7 +329,7 @@ def test_attached_statistics_follow_prune_extend_densify_resort():
     k3 = m.extend(cam, frame["xyz"].to(dev), col, frame["xyz"][:, 2].contiguous().to(dev), Rcw, tcw, (float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy)))
     assert k3 > 0 and m.P == P0 + k3
     after = arrays()
-    assert _same([t[:P0] for t in after], before) and all(not bool(t[P0:].any()) for t in after)
+    assert same_tensors([t[:P0] for t in after], before) and all(not bool(t[P0:].any()) for t in after)
     st.reset()
     assert not any(bool(t.any()) for t in arrays())
 
@@ -411,7 +366,7 @@ def test_planted_floaters_are_found_and_pruned_and_training_goes_on():
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.camera import synthetic_camera
     from gaussian_lic_amd.synthetic import gt_image
-    dev = _dev()
+    dev = gpu()
     raw, points, n_wall = _wall_scene()
     m = trainer.GaussianModel(raw, dev)
     m.training_setup()
@@ -449,28 +404,17 @@ def test_fused_free_space_cpp_host(tmp_path, monkeypatch):
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.camera import synthetic_camera
     from gaussian_lic_amd.synthetic import gt_image, random_scene
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussian-lic_amd", "shim", "build_shim.py")
-    spec = importlib.util.spec_from_file_location("build_shim", path)
-    build_shim = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_check("fused_free_space")
-    assert os.path.exists(exe)
+    exe = fio.build("fused_free_space")
     monkeypatch.delenv("GSLIC_RESORT", raising=False)
-    dev = _dev()
+    dev = gpu()
     cam1, cam2 = synthetic_camera(W, H).to_device(dev), synthetic_camera(W, H, 5).to_device(dev)
     gt, bg = gt_image(H, W).to(dev), torch.zeros(3, device=dev)
     iters, w_min, fraction, min_measured = 2, trainer.ContributionStats.W_MIN, 0.6, 0.05
     m = trainer.GaussianModel(random_scene(NP, W, H, sh_degree=3, seed=9), dev)
     m.training_setup()
     d = str(tmp_path)
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"), ("features_rest", "rest")):
-        w(n, getattr(m, k).detach().cpu().numpy())
-    w("view", cam1.world_view_transform); w("proj", cam1.full_proj_transform); w("campos", cam1.camera_center); w("gt", gt.cpu().numpy())
-    w("view2", cam2.world_view_transform); w("proj2", cam2.full_proj_transform); w("campos2", cam2.camera_center)
-    w("scalars", np.array([cam1.tanfovx, cam1.tanfovy, cam1.limx_neg, cam1.limx_pos, cam1.limy_neg, cam1.limy_pos], np.float32))
     near1, near2 = _near_for(cam1, m, 7), _near_for(cam2, m, 8)
-    w("near1", near1.cpu().numpy()); w("near2", near2.cpu().numpy())
+    fio.write_inputs(d, m, (cam1, cam2), gt=gt, near1=near1, near2=near2)
 
     def steps():
         for _ in range(iters):
@@ -485,11 +429,9 @@ def test_fused_free_space_cpp_host(tmp_path, monkeypatch):
     st.accumulate(cam1, w_min=w_min, free_space=near1)
     perm = m.to_morton_order(resort_fraction=None)
     steps()
-    r = subprocess.run([exe, d, str(NP), str(W), str(H), "3", str(iters), repr(w_min), repr(fraction), repr(min_measured)], capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = fio.run(exe, d, str(NP), str(W), str(H), "3", str(iters), repr(w_min), repr(fraction), repr(min_measured))
     assert f"free space pruned {removed} size {m.P}" in r.stdout
-    rd = lambda name, dt: torch.from_numpy(np.fromfile(os.path.join(d, "out_" + name), dt))
+    rd = functools.partial(fio.read, d)
     P = m.P
     assert torch.equal(rd("mask.u8", np.uint8), mask.cpu()) and torch.equal(rd("kept.i64", np.int64), kept.cpu()) and torch.equal(rd("perm.i64", np.int64), perm.cpu())
     assert torch.equal(rd("max_w.i32", np.int32), st._max[:P].cpu()) and torch.equal(rd("n_pix.i32", np.int32), st._npix[:P].cpu())
@@ -498,5 +440,5 @@ def test_fused_free_space_cpp_host(tmp_path, monkeypatch):
     assert bool(st.free_fixed().any()) and st.views == 3
     for n, f in (("xyz", "xyz"), ("features_dc", "dc"), ("features_rest", "rest"), ("opacity", "opacity"), ("scaling", "scaling"), ("rotation", "rotation")):
         for pre, src in (("", m._buf), ("m_", m._m), ("v_", m._v)):
-            assert torch.equal(rd(pre + f + ".f32", np.int32), _bits(src[n][:P]).cpu().reshape(-1)), pre + f
+            assert torch.equal(rd(pre + f + ".f32", np.int32), bits(src[n][:P]).cpu().reshape(-1)), pre + f
     assert torch.equal(rd("tie.i32", np.int32), m.tie_rank.cpu())

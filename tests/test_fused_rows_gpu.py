@@ -2,20 +2,19 @@
 error and free-space arrays and the attached gslic::GradientStats — through all four row changes (densify, extend, prune, resort), held against the
 Python model with a trainer.ContributionStats and a trainer.GradientStats attached.  What the single-feature C++-host tests leave out: gradient
 statistics through extend(), the free-space arrays through densify(), and the two objects side by side.  Every comparison is on the bits."""
-import importlib.util
-import os
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 import torch
 
+import fused_check_io as fio
 import gradstats_ref as gr
 
 pytestmark = pytest.mark.gpu
 
 
-def _bits(t):
+def _flat_bits(t):   # (detached, on the host and flat, as fio.read gives the files: not gpu_helpers.bits, which keeps device and shape)
     return t.detach().contiguous().view(torch.int32).cpu().reshape(-1)
 
 
@@ -30,12 +29,7 @@ def test_fused_rows_cpp_host(tmp_path, monkeypatch):
     from gaussian_lic_amd.camera import synthetic_camera
     from gaussian_lic_amd.rasterizer import render
     from gaussian_lic_amd.synthetic import gt_image, lidar_scene
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussian-lic_amd", "shim", "build_shim.py")
-    spec = importlib.util.spec_from_file_location("build_shim", path)
-    build_shim = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_check("fused_rows")
-    assert os.path.exists(exe)
+    exe = fio.build("fused_rows")
     monkeypatch.delenv("GSLIC_RESORT", raising=False)
     dev = torch.device("cuda:0")
     W, H, P0, iters, seed, fraction, n_pts, w_min = gr.W, gr.H, 600, 2, 11, 0.05, 400, trainer.ContributionStats.W_MIN
@@ -44,23 +38,17 @@ def test_fused_rows_cpp_host(tmp_path, monkeypatch):
     m = trainer.GaussianModel(gr.scene(P0, 3), dev)
     m.training_setup()
     d = str(tmp_path)
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"), ("features_rest", "rest")):
-        w(n, getattr(m, k).detach().cpu().numpy())
     # the LiDAR frame inputs of tests/test_resort_gpu.py
     frame = lidar_scene(n_pts, W, H, sh_degree=3, seed=77)
     pts, rsp = frame["xyz"].to(dev), frame["xyz"][:, 2].contiguous().to(dev)
     col = (frame["features_dc"].reshape(-1, 3) * 0.28209479177387814 + 0.5).to(dev)
     Rcw, tcw = torch.from_numpy(cam.world_view_transform[:3, :3].T.copy()), torch.from_numpy(cam.world_view_transform[3, :3].copy())
     intr = (float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy))
-    w("pts", pts.cpu().numpy()); w("col", col.cpu().numpy()); w("rsp", rsp.cpu().numpy()); w("Rcw", Rcw.numpy()); w("tcw", tcw.numpy())
-    w("view", cam.world_view_transform); w("proj", cam.full_proj_transform); w("campos", cam.camera_center); w("gt", gt.cpu().numpy())
-    w("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos, *intr], np.float32))
     g = torch.Generator().manual_seed(7)                                # a bound image that splits the map's depth range, a quarter unmeasured
     near = 1.0 + 29.0 * torch.rand(H, W, generator=g)
     near[torch.rand(H, W, generator=g) < 0.25] = 0.0
     near = near.to(dev)
-    w("near", near.cpu().numpy())
+    fio.write_inputs(d, m, cam, scalars_extra=intr, gt=gt, pts=pts, col=col, rsp=rsp, Rcw=Rcw, tcw=tcw, near=near)
 
     gst = trainer.GradientStats(m)
 
@@ -70,7 +58,7 @@ def test_fused_rows_cpp_host(tmp_path, monkeypatch):
     steps()
     with torch.no_grad():
         err = (render(cam, m, bg)[0] - gt).abs().mean(0).contiguous()
-    w("err", err.cpu().numpy())
+    fio.write(d, "err", err)
     st = trainer.ContributionStats(m)
     st.accumulate(cam, w_min=w_min, error=err)
     st.accumulate(cam, w_min=w_min, free_space=near)
@@ -100,20 +88,19 @@ def test_fused_rows_cpp_host(tmp_path, monkeypatch):
     assert bool(st.free_fixed().any()) and bool(st.error_fixed().any()) and st.views == 3
     assert int(gst.n_seen().max()) == 4 * iters                         # a row of the initial map that every step saw and no event reset
 
-    r = subprocess.run([exe, d, str(P0), str(W), str(H), "3", str(iters), str(n_pts), repr(fraction), repr(w_min), repr(grad_above), repr(split_scale),
-                        str(seed), str(rlim)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = fio.run(exe, d, str(P0), str(W), str(H), "3", str(iters), str(n_pts), repr(fraction), repr(w_min), repr(grad_above), repr(split_scale),
+                str(seed), str(rlim))
     assert f"rows densified {k} splits {n_split} extended {k2} resorts 2 pruned {removed} size {P} views 3" in r.stdout, r.stdout[-500:]
     torch.cuda.synchronize()
-    rd = lambda name, dt: torch.from_numpy(np.fromfile(os.path.join(d, "out_" + name), dt))
+    rd = functools.partial(fio.read, d)
     for n, f in (("xyz", "xyz"), ("features_dc", "dc"), ("features_rest", "rest"), ("opacity", "opacity"), ("scaling", "scaling"), ("rotation", "rotation")):
         for pre, src in (("", m._buf), ("m_", m._m), ("v_", m._v)):
-            assert torch.equal(rd(pre + f + ".f32", np.int32), _bits(src[n][:P])), pre + f
+            assert torch.equal(rd(pre + f + ".f32", np.int32), _flat_bits(src[n][:P])), pre + f
     assert torch.equal(rd("tie.i32", np.int32), m.tie_rank.cpu())
     assert torch.equal(rd("max_w.i32", np.int32), st._max[:P].cpu()) and torch.equal(rd("n_pix.i32", np.int32), st._npix[:P].cpu())
     assert torch.equal(rd("sum_w.i64", np.int64), st.sum_fixed().cpu()) and torch.equal(rd("err_sum.i64", np.int64), st.error_fixed().cpu())
     assert torch.equal(rd("free_sum.i64", np.int64), st.free_fixed().cpu()) and torch.equal(rd("meas_sum.i64", np.int64), st.measured_fixed().cpu())
-    assert torch.equal(rd("grad_sum.f32", np.int32), _bits(gst.grad_sum())) and bool((gst.grad_sum() > 0).any())
+    assert torch.equal(rd("grad_sum.f32", np.int32), _flat_bits(gst.grad_sum())) and bool((gst.grad_sum() > 0).any())
     assert torch.equal(rd("n_seen.i32", np.int32), gst._seen_n[:P].cpu()) and torch.equal(rd("max_radius.i32", np.int32), gst.max_radius().cpu())
     assert torch.equal(rd("perm0.i64", np.int64), perm0.cpu()) and perm0.numel() == P0 + k
     assert torch.equal(rd("perm1.i64", np.int64), seen[0].cpu()) and seen[0].numel() == P0 + k + k2

@@ -4,21 +4,17 @@ trainer.GradientStats).
 The yardstick is never the code under test: the existing ten-gradient backward (gslic_rasterize_backward / _depth) on a bit-identical second
 forward of the same parameters gives dL_dmean2D, which tests/gradstats_ref.py pushes through a numpy float32 transcription of the rule.  Every
 comparison is on bits.  Row moves are held against plain torch indexing."""
-import importlib.util
-import os
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 import torch
 
+import fused_check_io as fio
 import gradstats_ref as gr
+from gpu_helpers import gpu
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _mods():
@@ -29,12 +25,12 @@ def _mods():
 
 def _cams(views=gr.VIEWS):
     from gaussian_lic_amd.camera import synthetic_camera
-    return [synthetic_camera(gr.W, gr.H, v).to_device(_dev()) for v in views]
+    return [synthetic_camera(gr.W, gr.H, v).to_device(gpu()) for v in views]
 
 
-def _model(P, degree, order="insertion", **kw):
+def _map(P, degree, order="insertion", **kw):
     trainer, _rz = _mods()
-    m = trainer.GaussianModel(gr.scene(P, degree), _dev(), order=order, **kw)
+    m = trainer.GaussianModel(gr.scene(P, degree), gpu(), order=order, **kw)
     m.training_setup()
     return m
 
@@ -48,9 +44,9 @@ class Guarded:
         s, n, r = gr.sentinels(P)
         self.bufs, self.views = [], []
         for init, dt in ((s, torch.float32), (n.view(np.int32), torch.int32), (r, torch.int32)):
-            b = torch.full((P + 2 * self.G,), gr.GUARD, dtype=torch.int32, device=_dev())
+            b = torch.full((P + 2 * self.G,), gr.GUARD, dtype=torch.int32, device=gpu())
             v = b[self.G:self.G + P].view(dt)
-            v.copy_(torch.from_numpy(init.copy()).to(_dev()))
+            v.copy_(torch.from_numpy(init.copy()).to(gpu()))
             self.bufs.append(b)
             self.views.append(v)
 
@@ -65,24 +61,24 @@ class Guarded:
         return [v.cpu().numpy().view(np.uint32).copy() for v in self.views]
 
 
-def _bits(ref):
+def _u32(ref):   # (numpy reference arrays as uint32 words: not gpu_helpers.bits, which views one tensor)
     return [np.ascontiguousarray(a).view(np.uint32) for a in ref]
 
 
-def _same(got, want):
+def _same(got, want):   # (lists of numpy arrays: not gpu_helpers.same_tensors, which compares tensors)
     return all(np.array_equal(g, w) for g, w in zip(got, want))
 
 
 def _dL(k, depth=False):
     from gaussian_lic_amd.synthetic import pixel_grad
-    g = pixel_grad(gr.H, gr.W, seed=31 + k).to(_dev())
-    return (g, (0.1 * pixel_grad(gr.H, gr.W, seed=77 + k)[0]).contiguous().to(_dev())) if depth else (g, None)
+    g = pixel_grad(gr.H, gr.W, seed=31 + k).to(gpu())
+    return (g, (0.1 * pixel_grad(gr.H, gr.W, seed=77 + k)[0]).contiguous().to(gpu())) if depth else (g, None)
 
 
 def _view_reference(m, cam, dL, dLd):
     """dL_dmean2D and radii of the ten-gradient backward on a forward of its own (CPU numpy)."""
     trainer, _rz = _mods()
-    fwd = trainer._RawRaster(m, cam, torch.zeros(3, device=_dev()), depth=dLd is not None)
+    fwd = trainer._RawRaster(m, cam, torch.zeros(3, device=gpu()), depth=dLd is not None)
     with torch.no_grad():
         fwd.forward()
         g = fwd.backward(dL, dLd)
@@ -92,7 +88,7 @@ def _view_reference(m, cam, dL, dLd):
 def _fused_view(m, cam, dL, dLd, stats):
     """The fused Adam backward with statistics on a second forward of the same parameters (updates the map)."""
     trainer, _rz = _mods()
-    fwd = trainer._RawRaster(m, cam, torch.zeros(3, device=_dev()), depth=dLd is not None)
+    fwd = trainer._RawRaster(m, cam, torch.zeros(3, device=gpu()), depth=dLd is not None)
     with torch.no_grad():
         fwd.forward()
         fwd.backward(dL, dLd, adam=m.optimizer.fused_descriptor(), grad_stats=stats)
@@ -101,7 +97,7 @@ def _fused_view(m, cam, dL, dLd, stats):
 
 
 def _three_views(P, degree, depth):
-    m = _model(P, degree)
+    m = _map(P, degree)
     g = Guarded(P)
     ref = gr.sentinels(P)
     vis = []
@@ -120,7 +116,7 @@ def _three_views(P, degree, depth):
     if P > 1:
         assert (~vis.any(0)).any() and vis.sum(1).max() > 1      # a row no view sees keeps its sentinels
     assert not torch.equal(before, m.xyz.detach())               # Adam did move the map between the views
-    want = _bits(ref)
+    want = _u32(ref)
     assert _same(got, want), [int((a != b).sum()) for a, b in zip(got, want)]
     never = ~vis.any(0)
     assert (got[0][never] == np.float32(gr.SENT_SUM).view(np.uint32)).all() and (got[1][never] == gr.SENT_SEEN).all() and (got[2][never] == 7).all()
@@ -141,12 +137,12 @@ def test_rule_on_the_depth_variant(P, degree):
 def test_stand_alone_kernel_equals_the_fused_route_and_keeps_to_its_rows():
     _trainer, rz = _mods()
     P = 257
-    m = _model(P, 3)
+    m = _map(P, 3)
     cam = _cams()[0]
     dL, _ = _dL(0)
     m2d, radii = _view_reference(m, cam, dL, None)
     fused, alone, part = Guarded(P), Guarded(P), Guarded(P)
-    t_m2d, t_r = torch.from_numpy(m2d).to(_dev()), torch.from_numpy(radii).to(_dev())
+    t_m2d, t_r = torch.from_numpy(m2d).to(gpu()), torch.from_numpy(radii).to(gpu())
     rz.gradient_stats_accumulate(t_m2d, t_r, *alone.views)
     rz.gradient_stats_accumulate(t_m2d, t_r, *part.views, rows=(64, P))
     _fused_view(m, cam, dL, None, fused.descriptor())
@@ -155,18 +151,18 @@ def test_stand_alone_kernel_equals_the_fused_route_and_keeps_to_its_rows():
     gr.apply_rule(*ref_part, m2d, radii, rows=(64, P))
     a, f, p = alone.numpy(), fused.numpy(), part.numpy()
     assert (radii[:64] > 0).any() and (radii[64:] > 0).any()
-    assert _same(a, f) and _same(a, _bits(ref)) and _same(p, _bits(ref_part))
-    assert _same([x[:64] for x in p], _bits([x[:64] for x in gr.sentinels(P)])) and not _same(p, a)
+    assert _same(a, f) and _same(a, _u32(ref)) and _same(p, _u32(ref_part))
+    assert _same([x[:64] for x in p], _u32([x[:64] for x in gr.sentinels(P)])) and not _same(p, a)
 
 
 @pytest.mark.parametrize("depth", [False, True])
 def test_capacity_overflow_touches_nothing(depth):
     trainer, rz = _mods()
     P = 257
-    m = _model(P, 3)
+    m = _map(P, 3)
     cam = _cams()[0]
     dL, dLd = _dL(0, depth)
-    sizing = trainer._RawRaster(m, cam, torch.zeros(3, device=_dev()), depth=depth)
+    sizing = trainer._RawRaster(m, cam, torch.zeros(3, device=gpu()), depth=depth)
     with torch.no_grad():
         sizing.forward()
     R, B = sizing.state[:2]
@@ -174,8 +170,8 @@ def test_capacity_overflow_touches_nothing(depth):
     start = g.numpy()
     params = [p.detach().clone() for p in m.parameters()]
     for cap_R, fits in ((R // 3, False), (R + 4096, True)):
-        bufs = rz.CapacityBuffers(P, gr.W, gr.H, cap_R, B + 64, _dev(), depth=depth)
-        fwd = trainer._RawRaster(m, cam, torch.zeros(3, device=_dev()), depth=depth)
+        bufs = rz.CapacityBuffers(P, gr.W, gr.H, cap_R, B + 64, gpu(), depth=depth)
+        fwd = trainer._RawRaster(m, cam, torch.zeros(3, device=gpu()), depth=depth)
         with torch.no_grad():
             fwd.forward(bufs)
             fwd.backward(dL, dLd, adam=m.optimizer.fused_descriptor(), grad_stats=g.descriptor())
@@ -186,7 +182,7 @@ def test_capacity_overflow_touches_nothing(depth):
         assert all(torch.equal(a, b.detach()) for a, b in zip(params, m.parameters())) == (not fits)
 
 
-def _state(m):
+def _state(m):   # (the 18 row arrays on the device, as a list: not gpu_helpers.model_state, which reads the optimizer's state)
     torch.cuda.synchronize()
     return [t[:m.P].clone() for d in (m._buf, m._m, m._v) for t in (d[n] for n in m.NAMES)]
 
@@ -197,9 +193,9 @@ def test_training_is_unchanged_by_the_statistics(order):
     from gaussian_lic_amd.synthetic import gt_image
     P = 4097
     cams = _cams()
-    gts = [gt_image(gr.H, gr.W, seed=5 + k).to(_dev()) for k in range(3)]
-    bg = torch.zeros(3, device=_dev())
-    plain, with_st, plain_u, unfused = (_model(P, 3, order) for _ in range(4))
+    gts = [gt_image(gr.H, gr.W, seed=5 + k).to(gpu()) for k in range(3)]
+    bg = torch.zeros(3, device=gpu())
+    plain, with_st, plain_u, unfused = (_map(P, 3, order) for _ in range(4))
     st, st_u = trainer.GradientStats(with_st), trainer.GradientStats(unfused)
     for k in range(4):
         trainer.training_step_fused(plain, cams[k % 3], gts[k % 3], bg)
@@ -223,9 +219,9 @@ def test_graphed_step_with_statistics(use_graph, order):
     from gaussian_lic_amd.synthetic import gt_image
     P = 4097
     cams = _cams()[:2]
-    gts = [gt_image(gr.H, gr.W, seed=5 + k).to(_dev()) for k in range(2)]
-    bg = torch.zeros(3, device=_dev())
-    eager, plain, graphed = _model(P, 3, order), _model(P, 3, order), _model(P, 3, order)
+    gts = [gt_image(gr.H, gr.W, seed=5 + k).to(gpu()) for k in range(2)]
+    bg = torch.zeros(3, device=gpu())
+    eager, plain, graphed = _map(P, 3, order), _map(P, 3, order), _map(P, 3, order)
     st_e, st_g = trainer.GradientStats(eager), trainer.GradientStats(graphed)
     st_g._maxr[:P] = 3                                       # what is there when the step is built stays (warm-up and capture are undone)
     st_e._maxr[:P] = 3
@@ -262,11 +258,11 @@ def test_other_paths_feed_the_same_statistics():
     from gaussian_lic_amd.synthetic import gt_image
     P = 257
     cam = _cams()[1]
-    gt = gt_image(gr.H, gr.W, seed=5).to(_dev())
-    bg = torch.zeros(3, device=_dev())
+    gt = gt_image(gr.H, gr.W, seed=5).to(gpu())
+    bg = torch.zeros(3, device=gpu())
     got = []
     for kind in ("fused", "autograd", "pose"):
-        m = _model(P, 3)
+        m = _map(P, 3)
         st = trainer.GradientStats(m)
         if kind == "fused":
             trainer.training_step_fused(m, cam, gt, bg, grad_stats=st)
@@ -279,7 +275,7 @@ def test_other_paths_feed_the_same_statistics():
     assert all(torch.equal(x, y) for x, y in zip(got[0], got[2]))          # the same loss kernels, the same backward sums
     assert torch.equal(got[0][1], got[1][1]) and torch.equal(got[0][2], got[1][2])   # (autograd's loss differs in rounding: counts and radii only)
     # the operator renderer leaves the gradient in screenspace_points.grad
-    m = _model(P, 3)
+    m = _map(P, 3)
     st = trainer.GradientStats(m)
     trainer.training_step(m, cam, gt, bg, raw_render=False, grad_stats=st)
     s = _snap(st)
@@ -289,12 +285,12 @@ def test_other_paths_feed_the_same_statistics():
 def test_statistics_follow_the_rows():
     trainer, _rz = _mods()
     from gaussian_lic_amd.synthetic import gt_image, lidar_scene
-    dev = _dev()
+    dev = gpu()
     P = 600
     cams = _cams()[:2]
     gts = [gt_image(gr.H, gr.W, seed=5 + k).to(dev) for k in range(2)]
     bg = torch.zeros(3, device=dev)
-    a, d = _model(P, 3), _model(P, 3, "morton", resort_fraction=None)
+    a, d = _map(P, 3), _map(P, 3, "morton", resort_fraction=None)
     assert not torch.equal(d.tie_rank.long().cpu(), torch.arange(P))
     sa, sd = trainer.GradientStats(a), trainer.GradientStats(d)
     for k in range(2):
@@ -357,7 +353,7 @@ def test_statistics_follow_the_rows():
 def test_non_finite_gradient_rows():
     trainer, _rz = _mods()
     P = 257
-    m = _model(P, 3)
+    m = _map(P, 3)
     cam = _cams()[0]
     dL, _ = _dL(0)
     dL = dL.clone()
@@ -371,7 +367,7 @@ def test_non_finite_gradient_rows():
     g = Guarded(P)
     _fused_view(m, cam, dL, None, g.descriptor())
     got = g.numpy()
-    assert _same(got, _bits(ref))
+    assert _same(got, _u32(ref))
     assert (got[0][bad] == np.float32(gr.SENT_SUM).view(np.uint32)).all() and (got[1][bad] == gr.SENT_SEEN).all()
     assert (got[2][bad].view(np.int32) == np.maximum(radii[bad], 7)).all() and (got[1][fine] == gr.SENT_SEEN + 1).all()
 
@@ -383,25 +379,14 @@ def test_fused_gradient_stats_cpp_host(tmp_path, order):
     12 moments, the tie rank) are bit-identical to the Python model's, on both row orders."""
     trainer, _rz = _mods()
     from gaussian_lic_amd.synthetic import gt_image
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussian-lic_amd", "shim", "build_shim.py")
-    spec = importlib.util.spec_from_file_location("build_shim", path)
-    build_shim = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_check("fused_gradient_stats")
-    assert os.path.exists(exe)
+    exe = fio.build("fused_gradient_stats")
     P, iters, seed = 600, 2, 11
-    m = _model(P, 3, order, resort_fraction=None)
+    m = _map(P, 3, order, resort_fraction=None)
     cam = _cams()[1]
-    gt = gt_image(gr.H, gr.W, seed=5).to(_dev())
-    bg = torch.zeros(3, device=_dev())
+    gt = gt_image(gr.H, gr.W, seed=5).to(gpu())
+    bg = torch.zeros(3, device=gpu())
     d = str(tmp_path)
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"), ("features_rest", "rest")):
-        w(n, getattr(m, k).detach().cpu().numpy())
-    if order == "morton":
-        w("tie_rank", m.tie_rank.cpu().numpy())
-    w("view", cam.world_view_transform); w("proj", cam.full_proj_transform); w("campos", cam.camera_center); w("gt", gt.cpu().numpy())
-    w("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos], np.float32))
+    fio.write_inputs(d, m, cam, gt=gt, tie_rank=m.tie_rank)
     st = trainer.GradientStats(m)
 
     def steps():
@@ -420,12 +405,10 @@ def test_fused_gradient_stats_cpp_host(tmp_path, order):
     perm = m.to_morton_order(resort_fraction=None) if order == "insertion" else m.resort()
     assert not torch.equal(perm.cpu(), torch.arange(m.P))
     steps()
-    r = subprocess.run([exe, d, str(P), str(gr.W), str(gr.H), "3", str(iters), repr(grad_above), str(rlim), repr(split_scale), str(seed)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = fio.run(exe, d, str(P), str(gr.W), str(gr.H), "3", str(iters), repr(grad_above), str(rlim), repr(split_scale), str(seed))
     assert f"densify added {k} splits {n_split} pruned {n} size {m.P}" in r.stdout, r.stdout
     torch.cuda.synchronize()
-    rd = lambda name, dt: torch.from_numpy(np.fromfile(os.path.join(d, "out_" + name), dt))
+    rd = functools.partial(fio.read, d)
     bits = lambda t: t.detach().contiguous().view(torch.int32).cpu().reshape(-1)
     Pn = m.P
     for name, f in (("xyz", "xyz"), ("features_dc", "dc"), ("features_rest", "rest"), ("opacity", "opacity"), ("scaling", "scaling"), ("rotation", "rotation")):

@@ -4,32 +4,23 @@ Every comparison is on bits; the rule has no tolerance.  References, none of the
 trainer.free_space_bound (merged torch code) at footprint 0, the numpy transcription of tests/lidar_depth_ref.py (held against project_depth by
 test_lidar_depth_cpu.py) for the index image and the footprints, and torch's max_pool2d as an independent route for the windowed minimum."""
 import ctypes
-import importlib.util
-import os
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 import torch
 
+import fused_check_io as fio
 import lidar_depth_ref as lr
+from gpu_helpers import SENTINEL as SENTINEL32, bits, gpu
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL64 = 0x5A5A5A5A5A5A5A5A
-SENTINEL32 = 0x5A5A5A5A
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _bits(x):
-    return x.contiguous().view(torch.int32)
 
 
 def _same_bits(a, b):
-    return torch.equal(_bits(a).cpu(), _bits(torch.as_tensor(b)).cpu())
+    return torch.equal(bits(a).cpu(), bits(torch.as_tensor(b)).cpu())
 
 
 def _trainer():
@@ -41,8 +32,8 @@ def _trainer():
 def _image(W, H, view, pts, footprint=0, margins=None, index=True, count=True):
     """(LidarDepth, resolve dict) of one sweep of `pts` (numpy [n,3]) seen from synthetic_camera(W, H, view)."""
     trainer = _trainer()
-    ld = trainer.LidarDepth(W, H, _dev())
-    base = ld.add(lr.camera(W, H, view), torch.from_numpy(np.array(pts)).to(_dev()))
+    ld = trainer.LidarDepth(W, H, gpu())
+    base = ld.add(lr.camera(W, H, view), torch.from_numpy(np.array(pts)).to(gpu()))
     assert base == 0 and ld.n_points == len(pts)
     return ld, ld.resolve(footprint=footprint, margins=margins, index=index, count=count)
 
@@ -56,7 +47,7 @@ def test_footprint_0_equals_project_depth_and_free_space_bound(W, H):
         cam = lr.camera(W, H, view)
         for n in lr.COUNTS:
             pts, _notes = lr.cloud(W, H, n, view)
-            want = cam.project_depth(torch.from_numpy(pts.copy()).to(_dev()))
+            want = cam.project_depth(torch.from_numpy(pts.copy()).to(gpu()))
             ref = lr.images_of(W, H, n, view)
             for ma, mr in lr.MARGINS:
                 _ld, out = _image(W, H, view, pts, margins=(ma, mr))
@@ -70,7 +61,7 @@ def test_footprint_0_equals_project_depth_and_free_space_bound(W, H):
                     nonpositive += int(((out["near"] <= 0) & (depth > 0)).sum())
                     assert not bool((out["near"] > 0).any())
             measured += ref["n_measured"]
-            assert _same_bits(trainer.lidar_depth_image(cam, torch.from_numpy(pts.copy()).to(_dev())), want)
+            assert _same_bits(trainer.lidar_depth_image(cam, torch.from_numpy(pts.copy()).to(gpu())), want)
     assert measured > 0 and nonpositive > 0
 
 
@@ -90,7 +81,7 @@ def test_footprints_equal_the_windowed_minimum_of_the_keys(W, H, r):
             assert _same_bits(out["near"], torch.from_numpy(ref["near"])), (view, n)
             assert int(out["n_measured"]) == ref["n_measured"], (view, n)
             # the independent torch route: min-pool of the footprint-0 depth with +inf for empty
-            d0 = torch.from_numpy(ref0["depth"]).to(_dev())
+            d0 = torch.from_numpy(ref0["depth"]).to(gpu())
             d_inf = torch.where(d0 > 0, d0, torch.full_like(d0, float("inf")))
             pooled = -torch.nn.functional.max_pool2d(-d_inf[None, None], 2 * r + 1, 1, r)[0, 0]
             assert _same_bits(out["depth"], torch.where(torch.isinf(pooled), torch.zeros_like(pooled), pooled)), (view, n)
@@ -104,9 +95,9 @@ def test_sweeps_accumulate_and_clear_empties():
     W, H, view = 37, 23, "se3_c"
     cam = lr.camera(W, H, view)
     a, b = lr.cloud(W, H, 257, view)[0], lr.cloud(W, H, 65, view, seed=1, plant=False)[0]   # (no planted rows in b: they would tie with a's)
-    ta, tb = torch.from_numpy(a.copy()).to(_dev()), torch.from_numpy(b.copy()).to(_dev())
+    ta, tb = torch.from_numpy(a.copy()).to(gpu()), torch.from_numpy(b.copy()).to(gpu())
     _ld, whole = _image(W, H, view, np.concatenate([a, b]))
-    ld = trainer.LidarDepth(W, H, _dev())
+    ld = trainer.LidarDepth(W, H, gpu())
     assert ld.add(cam, ta) == 0 and ld.add(cam, tb) == 257 and ld.n_points == 322
     ab = ld.resolve(index=True, count=True)
     assert _same_bits(ab["depth"], whole["depth"]) and torch.equal(ab["index"], whole["index"]) and int(ab["n_measured"]) == int(whole["n_measured"])
@@ -134,7 +125,7 @@ def test_repeats_shuffles_guard_words_on_a_side_stream():
     import gaussian_lic_amd  # noqa: F401
     from gaussian_lic_amd import _lib
     L = _lib.lib()
-    dev = _dev()
+    dev = gpu()
     W, H, n, view, r, margins = 37, 23, 4097, "se3_d", 3, lr.MARGINS[1]
     cam = lr.camera(W, H, view)
     pts, notes = lr.cloud(W, H, n, view)
@@ -198,7 +189,7 @@ def _scene():
     trainer = _trainer()
     from gaussian_lic_amd.camera import synthetic_camera
     from gaussian_lic_amd.synthetic import gt_image, lidar_scene, random_scene
-    dev = _dev()
+    dev = gpu()
     m = trainer.GaussianModel(random_scene(NP, SW, SH, sh_degree=3, seed=3), dev)
     m.training_setup()
     cam = synthetic_camera(SW, SH).to_device(dev)
@@ -207,7 +198,7 @@ def _scene():
 
 
 def _rows(m):
-    return {pre + n: _bits(src[n][:m.P]).cpu().reshape(-1).clone() for n in m.NAMES for pre, src in (("", m._buf), ("m_", m._m), ("v_", m._v))}
+    return {pre + n: bits(src[n][:m.P]).cpu().reshape(-1).clone() for n in m.NAMES for pre, src in (("", m._buf), ("m_", m._m), ("v_", m._v))}
 
 
 def _five(st):
@@ -231,8 +222,8 @@ def _consume(depth, near):
 def test_library_images_feed_the_step_and_the_statistics_like_the_torch_ones():
     trainer = _trainer()
     _m, cam, _gt, _bg, points = _scene()
-    d_pts = points.to(_dev())
-    ld = trainer.LidarDepth(SW, SH, _dev())
+    d_pts = points.to(gpu())
+    ld = trainer.LidarDepth(SW, SH, gpu())
     ld.add(cam, d_pts)
     lib = ld.resolve(margins=MARGINS)
     torch_depth = cam.project_depth(d_pts)
@@ -253,42 +244,31 @@ def test_fused_lidar_depth_cpp_host(tmp_path):
     """gslic::LidarDepth feeding FusedStep::step and accumulate_free_space gives the Python host's four images, its 18 parameter and moment arrays
     and its five accumulators, bit for bit."""
     trainer = _trainer()
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussian-lic_amd", "shim", "build_shim.py")
-    spec = importlib.util.spec_from_file_location("build_shim", path)
-    build_shim = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_check("fused_lidar_depth")
-    assert os.path.exists(exe)
+    exe = fio.build("fused_lidar_depth")
     footprint, w_min = 0, trainer.ContributionStats.W_MIN   # test 5's setting
     m, cam, gt, bg, points = _scene()
     R, t = lr.pose_f32(cam)
     d = str(tmp_path)
-    w = lambda name, x: np.ascontiguousarray(x, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"), ("features_rest", "rest")):
-        w(n, getattr(m, k).detach().cpu().numpy())
-    w("view", cam.world_view_transform); w("proj", cam.full_proj_transform); w("campos", cam.camera_center); w("gt", gt.cpu().numpy())
-    w("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos], np.float32))
-    w("points", points.numpy())
-    w("lidar", np.concatenate([R, t, np.array([cam.fx, cam.fy, cam.cx, cam.cy, MARGINS[0], MARGINS[1], LAMBDA_DEPTH, w_min], np.float32)]))
+    fio.write_inputs(d, m, cam, gt=gt, points=points,
+                     lidar=np.concatenate([R, t, np.array([cam.fx, cam.fy, cam.cx, cam.cy, MARGINS[0], MARGINS[1], LAMBDA_DEPTH, w_min], np.float32)]))
 
-    ld = trainer.LidarDepth(SW, SH, _dev())
-    ld.add(cam, points.to(_dev()))
+    ld = trainer.LidarDepth(SW, SH, gpu())
+    ld.add(cam, points.to(gpu()))
     im = ld.resolve(footprint=footprint, margins=MARGINS, index=True, count=True)
     trainer.training_step_fused(m, cam, gt, bg, gt_depth=im["depth"], lambda_depth=LAMBDA_DEPTH)
     st = trainer.ContributionStats(m)
     st.accumulate(cam, w_min=w_min, free_space=im["near"])
-    r = subprocess.run([exe, d, str(NP), str(SW), str(SH), "3", str(NPTS), str(footprint)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = fio.run(exe, d, str(NP), str(SW), str(SH), "3", str(NPTS), str(footprint))
     assert f"lidar measured {int(im['n_measured'])} base 0" in r.stdout
-    rd = lambda name, dt: torch.from_numpy(np.fromfile(os.path.join(d, "out_" + name), dt))
-    assert torch.equal(rd("lidar_depth.f32", np.int32), _bits(im["depth"]).cpu().reshape(-1)) and bool(im["depth"].any())
-    assert torch.equal(rd("lidar_near.f32", np.int32), _bits(im["near"]).cpu().reshape(-1))
+    rd = functools.partial(fio.read, d)
+    assert torch.equal(rd("lidar_depth.f32", np.int32), bits(im["depth"]).cpu().reshape(-1)) and bool(im["depth"].any())
+    assert torch.equal(rd("lidar_near.f32", np.int32), bits(im["near"]).cpu().reshape(-1))
     assert torch.equal(rd("lidar_index.i32", np.int32), im["index"].cpu().reshape(-1))
     assert int(rd("lidar_count.i32", np.int32)[0]) == int(im["n_measured"]) > 0
     P = m.P
     for n, f in (("xyz", "xyz"), ("features_dc", "dc"), ("features_rest", "rest"), ("opacity", "opacity"), ("scaling", "scaling"), ("rotation", "rotation")):
         for pre, src in (("", m._buf), ("m_", m._m), ("v_", m._v)):
-            assert torch.equal(rd(pre + f + ".f32", np.int32), _bits(src[n][:P]).cpu().reshape(-1)), pre + f
+            assert torch.equal(rd(pre + f + ".f32", np.int32), bits(src[n][:P]).cpu().reshape(-1)), pre + f
     assert torch.equal(rd("max_w.i32", np.int32), st._max[:P].cpu()) and torch.equal(rd("n_pix.i32", np.int32), st._npix[:P].cpu())
     assert torch.equal(rd("sum_w.i64", np.int64), st.sum_fixed().cpu())
     assert torch.equal(rd("free_sum.i64", np.int64), st.free_fixed().cpu()) and torch.equal(rd("meas_sum.i64", np.int64), st.measured_fixed().cpu())

@@ -3,9 +3,12 @@ kernels) renders, trains, grows and exports exactly as the same map in insertion
 rule of the sort — the reference lists Gaussians of equal (tile, depth bits) by ascending index (stable sort of the index-ordered emission,
 rasterizer_impl.cu:395-424) — and the forward applies it on the rows' ORIGINAL indices (gslic_raster_params.tie_rank).  The scenes here have
 their depths quantised so that thousands of Gaussians tie."""
-import numpy as np
+import functools
+
 import pytest
 import torch
+
+import gpu_helpers
 
 pytestmark = pytest.mark.gpu
 
@@ -30,13 +33,7 @@ def _models(raw, dev, **kw):
     return a, b
 
 
-def _same_map(a, b):
-    order = b.original_order()
-    for n in a.NAMES:
-        x, y = getattr(a, n).detach(), getattr(b, n).detach()[order]
-        assert torch.equal(x, y), n
-    for n in a.NAMES:
-        assert torch.equal(a._m[n][:a.P], b._m[n][:b.P][order]) and torch.equal(a._v[n][:a.P], b._v[n][:b.P][order]), n
+_same_map = functools.partial(gpu_helpers.same_map, view=None)   # the floats as torch.equal compares them, as this file always did: not the bits
 
 
 def test_morton_order_is_a_nontrivial_permutation_with_ties_in_the_scene():

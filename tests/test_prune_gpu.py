@@ -5,23 +5,19 @@ The reference of every comparison is plain torch on the same tensors (x[keep_mas
 exact (indices, or int32 views of the rows, so NaN payloads count)."""
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
+
+import fused_check_io as fio
+from gpu_helpers import SENTINEL, bits, gpu, map_snapshot
 
 pytestmark = pytest.mark.gpu
 
 SCAN_TILE = 256 * 16       # elements one workgroup of scan_u32 covers (scan.hip: SCAN_THREADS x SCAN_ITEMS)
 SHAPES = [1, 63, 64, 65, 257, SCAN_TILE + 1, 100003]
 PATTERNS = ["all", "none", "first", "last", "alternating", "random30"]
-SENTINEL = 0x5A5A5A5A
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _libs():
@@ -122,7 +118,7 @@ def _to(t, dev):
 @pytest.mark.parametrize("pattern", PATTERNS)
 @pytest.mark.parametrize("P", SHAPES)
 def test_selection_is_exact_and_ties_stay_dense(P, pattern):
-    dev = _dev()
+    dev = gpu()
     lo, hi = _thresholds()
     keep = _pattern(pattern, P)
     g = torch.Generator().manual_seed(31 * P)
@@ -146,7 +142,7 @@ def test_selection_is_exact_and_ties_stay_dense(P, pattern):
 
 @pytest.mark.parametrize("which", ["xyz", "dc", "opacity", "scaling", "rotation"])
 def test_nonfinite_rows_go_even_when_protected(which):
-    dev = _dev()
+    dev = gpu()
     lo, hi = _thresholds()
     P = 257
     rows, _d, _p = _rows_for(torch.ones(P, dtype=torch.bool), False)
@@ -175,7 +171,7 @@ def test_nonfinite_rows_go_even_when_protected(which):
 # ---------------------------------------------------------------------------------------------------- 3. the gather
 def _sources(P, M):
     """The map's 19 row arrays as random BIT patterns (int32 views; NaN payloads included): 6 groups x {parameter, exp_avg, exp_avg_sq} + tie_rank."""
-    dev = _dev()
+    dev = gpu()
     g = torch.Generator(device=dev).manual_seed(P + 17 * M)
     widths = [3, 3, 3 * M, 1, 3, 4] * 3 + [1]
     return [torch.randint(-2 ** 31, 2 ** 31 - 1, (P, w), dtype=torch.int64, device=dev, generator=g).to(torch.int32) for w in widths]
@@ -201,7 +197,7 @@ def _check_gather(srcs, index, cap):
 @pytest.mark.parametrize("M", [15, 0])
 @pytest.mark.parametrize("P", SHAPES)
 def test_gather_is_exact(P, M):
-    dev = _dev()
+    dev = gpu()
     srcs = _sources(P, M)
     for pattern in PATTERNS:
         index = _pattern(pattern, P).nonzero().squeeze(1).to(dev)          # ("none": n_rows = 0 returns at once, nothing is written)
@@ -213,7 +209,7 @@ def test_gather_is_exact(P, M):
 def test_gather_other_widths_and_more_arrays_than_one_launch_takes():
     """Widths without a compile-time divisor (2, 9, 4096 = one workgroup's chunk exactly), a row wider than a chunk (5000 dwords: the lanes walk
     the row), and 40 arrays (two launches of at most 32)."""
-    dev = _dev()
+    dev = gpu()
     g = torch.Generator(device=dev).manual_seed(5)
     P = 301
     rnd = lambda w: torch.randint(-2 ** 31, 2 ** 31 - 1, (P, w), dtype=torch.int64, device=dev, generator=g).to(torch.int32)
@@ -233,11 +229,11 @@ def _scene(kind):
     return (random_scene if kind == "random" else lidar_scene)(NP, W, H, sh_degree=3, seed=3)
 
 
-def _model(raw, order, steps=3, **kw):
+def _trained(raw, order, steps=3, **kw):
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.camera import synthetic_camera
     from gaussian_lic_amd.synthetic import gt_image
-    dev = _dev()
+    dev = gpu()
     m = trainer.GaussianModel({k: (v.clone() if torch.is_tensor(v) else v) for k, v in raw.items()}, dev, order=order, **kw)
     m.training_setup()
     cam = synthetic_camera(W, H).to_device(dev)
@@ -245,19 +241,6 @@ def _model(raw, order, steps=3, **kw):
     for _ in range(steps):
         trainer.training_step_fused(m, cam, gt, bg)
     return m, cam, gt, bg
-
-
-def _snapshot(m):
-    P = m.P
-    out = {}
-    for n in m.NAMES:
-        out[n] = m._buf[n][:P].clone(); out[n + ".m"] = m._m[n][:P].clone(); out[n + ".v"] = m._v[n][:P].clone()
-    out["tie"] = None if m._tie is None else m._tie[:P].clone().long()
-    return out
-
-
-def _bits(x):
-    return x.contiguous().view(torch.int32)
 
 
 def _limits(m):
@@ -279,14 +262,14 @@ def _model_mask(m, min_opacity, max_scale, drop, protect):
 @pytest.mark.parametrize("order", ["insertion", "morton"])
 @pytest.mark.parametrize("kind", ["random", "lidar"])
 def test_model_after_prune_equals_torch_indexing(kind, order):
-    dev = _dev()
-    m, _cam, _gt, _bg = _model(_scene(kind), order)
+    dev = gpu()
+    m, _cam, _gt, _bg = _trained(_scene(kind), order)
     assert any(float(m._m[n][:m.P].abs().max()) > 0 for n in m.NAMES)          # (the moments are non-zero: the steps did something)
     g = torch.Generator().manual_seed(11)
     drop = (torch.rand(NP, generator=g) < 0.1).to(dev)
     protect = (torch.rand(NP, generator=g) < 0.05).to(dev)
     lim = _limits(m)
-    before = _snapshot(m)
+    before = map_snapshot(m, tie=True)
     mask = _model_mask(m, lim[0], lim[1], drop, protect)
     sorted_before, version, cap = m._sorted_P, m.layout_version, m.capacity
     n_removed, kept = m.prune(lim[0], lim[1], drop=drop, protect=protect)
@@ -295,9 +278,9 @@ def test_model_after_prune_equals_torch_indexing(kind, order):
     assert kept.dtype == torch.int64 and torch.equal(kept, mask.nonzero().squeeze(1))
     assert m._sorted_P == int(mask[:sorted_before].sum())
     for i, n in enumerate(m.NAMES):
-        assert torch.equal(_bits(getattr(m, n).detach()), _bits(before[n][mask])), n
+        assert torch.equal(bits(getattr(m, n).detach()), bits(before[n][mask])), n
         st = m.optimizer.state[i]
-        assert torch.equal(_bits(st["exp_avg"]), _bits(before[n + ".m"][mask])) and torch.equal(_bits(st["exp_avg_sq"]), _bits(before[n + ".v"][mask])), n
+        assert torch.equal(bits(st["exp_avg"]), bits(before[n + ".m"][mask])) and torch.equal(bits(st["exp_avg_sq"]), bits(before[n + ".v"][mask])), n
         assert getattr(m, n).data_ptr() == m._buf[n].data_ptr() == m.optimizer.params[i].data_ptr()        # the optimizer sees the new tensors
     if order == "insertion":
         assert m.tie_rank is None and m.original_order() is None
@@ -314,15 +297,15 @@ def test_model_after_prune_equals_torch_indexing(kind, order):
 
 def test_prune_before_training_setup_and_to_nothing():
     from gaussian_lic_amd import trainer
-    dev = _dev()
+    dev = gpu()
     raw = _scene("random")
     m = trainer.GaussianModel({k: (v.clone() if torch.is_tensor(v) else v) for k, v in raw.items()}, dev, order="morton")
-    before = _snapshot(m)
+    before = map_snapshot(m, tie=True)
     mask = _model_mask(m, 0.5, None, None, None)
     n, kept = m.prune(min_opacity=0.5)
     assert n == NP - int(mask.sum()) and torch.equal(kept, mask.nonzero().squeeze(1))
     for name in m.NAMES:
-        assert torch.equal(_bits(getattr(m, name).detach()), _bits(before[name][mask])), name
+        assert torch.equal(bits(getattr(m, name).detach()), bits(before[name][mask])), name
     m.training_setup()
     n, kept = m.prune(drop=torch.ones(m.P, dtype=torch.bool, device=dev))      # every row: an empty map
     assert m.P == 0 and kept.numel() == 0 and m.xyz.shape == (0, 3) and m.tie_rank.numel() == 0 and m._sorted_P == 0
@@ -333,10 +316,10 @@ def test_pruned_orders_export_and_render_alike(kind, tmp_path):
     """The same ORIGINAL rows pruned from an insertion-order and a Morton model: byte-identical save_map, bit-identical strict render."""
     from gaussian_lic_amd import io_ply
     from gaussian_lic_amd.rasterizer import render
-    dev = _dev()
+    dev = gpu()
     raw = _scene(kind)
-    a, cam, gt, bg = _model(raw, "insertion")
-    b, _c, _g, _b = _model(raw, "morton")
+    a, cam, gt, bg = _trained(raw, "insertion")
+    b, _c, _g, _b = _trained(raw, "morton")
     lim = _limits(a)
     g = torch.Generator().manual_seed(12)
     drop_orig = (torch.rand(NP, generator=g) < 0.1).to(dev)                    # by ORIGINAL index
@@ -352,7 +335,7 @@ def test_pruned_orders_export_and_render_alike(kind, tmp_path):
         ia, Ta, _, va, ra = render(cam, a, bg)
         ib, Tb, _, vb, rb = render(cam, b, bg)
     order = b.original_order()
-    assert torch.equal(_bits(ia), _bits(ib)) and torch.equal(_bits(Ta), _bits(Tb)) and torch.equal(ra, rb[order])
+    assert torch.equal(bits(ia), bits(ib)) and torch.equal(bits(Ta), bits(Tb)) and torch.equal(ra, rb[order])
 
 
 @pytest.mark.parametrize("order", ["insertion", "morton"])
@@ -362,10 +345,10 @@ def test_training_goes_on_bit_for_bit_and_extend_keeps_ties_dense(order):
     from gaussian_lic_amd import trainer
     from gaussian_lic_amd.rasterizer import render
     from gaussian_lic_amd.synthetic import lidar_scene
-    dev = _dev()
+    dev = gpu()
     raw = _scene("random")
-    full, cam, gt, bg = _model(raw, order, capacity=2 * NP, resort_fraction=None)
-    cut, _c, _g, _b = _model(raw, order, capacity=2 * NP, resort_fraction=None)
+    full, cam, gt, bg = _trained(raw, order, capacity=2 * NP, resort_fraction=None)
+    cut, _c, _g, _b = _trained(raw, order, capacity=2 * NP, resort_fraction=None)
     with torch.no_grad():
         radii = render(cam, cut, bg)[4]
     invisible = radii == 0
@@ -374,11 +357,11 @@ def test_training_goes_on_bit_for_bit_and_extend_keeps_ties_dense(order):
     assert n == int(invisible.sum()) and torch.equal(kept, (~invisible).nonzero().squeeze(1))
     ta, _ = trainer.training_step_fused(full, cam, gt, bg)
     tb, _ = trainer.training_step_fused(cut, cam, gt, bg)
-    assert torch.equal(_bits(ta), _bits(tb))
+    assert torch.equal(bits(ta), bits(tb))
     for name in full.NAMES:
-        assert torch.equal(_bits(cut._buf[name][:cut.P]), _bits(full._buf[name][:NP][kept])), name
-        assert torch.equal(_bits(cut._m[name][:cut.P]), _bits(full._m[name][:NP][kept])), name + ".m"
-        assert torch.equal(_bits(cut._v[name][:cut.P]), _bits(full._v[name][:NP][kept])), name + ".v"
+        assert torch.equal(bits(cut._buf[name][:cut.P]), bits(full._buf[name][:NP][kept])), name
+        assert torch.equal(bits(cut._m[name][:cut.P]), bits(full._m[name][:NP][kept])), name + ".m"
+        assert torch.equal(bits(cut._v[name][:cut.P]), bits(full._v[name][:NP][kept])), name + ".v"
     # extend() behind a prune that emptied the right half of the image: the new rows' ties P0..P0+k-1 collide with nothing
     u_pix = cut.xyz.detach()[:, 0] * (0.675 * W) / cut.xyz.detach()[:, 2].abs().clamp_min(0.2) + 0.4857 * W
     cut.prune(drop=u_pix > 0.5 * W)
@@ -399,7 +382,7 @@ def test_training_goes_on_bit_for_bit_and_extend_keeps_ties_dense(order):
 
 def test_graphed_step_refuses_a_stale_layout():
     from gaussian_lic_amd import trainer
-    m, cam, gt, bg = _model(_scene("random"), "morton", steps=1)
+    m, cam, gt, bg = _trained(_scene("random"), "morton", steps=1)
     gs = trainer.GraphedStep(m, cam, gt, bg, check_every=0)
     gs.step()
     assert gs.check() == 0
@@ -416,32 +399,20 @@ def test_graphed_step_refuses_a_stale_layout():
 def test_fused_prune_cpp_host(tmp_path):
     """gslic::FusedStep::prune issues the calls of GaussianModel.prune: after two steps, a prune with the same limits and two more steps on a map
     handed over in Morton order (tie_rank), kept indices, parameters and the position moments are bit-identical to the Python host's."""
-    import importlib.util
     from gaussian_lic_amd import trainer
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussian-lic_amd", "shim", "build_shim.py")
-    spec = importlib.util.spec_from_file_location("build_shim", path)
-    build_shim = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_check("fused_prune")
-    assert os.path.exists(exe)
+    exe = fio.build("fused_prune")
     iters, min_opacity, max_scale = 2, 0.3, 1.0
-    m, cam, gt, bg = _model(_scene("random"), "morton", steps=0)
+    m, cam, gt, bg = _trained(_scene("random"), "morton", steps=0)
     d = str(tmp_path)
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"), ("features_rest", "rest")):
-        w(n, getattr(m, k).detach().cpu().numpy())
-    w("tie_rank", m.tie_rank.cpu().numpy())
-    w("view", cam.world_view_transform); w("proj", cam.full_proj_transform); w("campos", cam.camera_center); w("gt", gt.cpu().numpy())
-    w("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos], np.float32))
-    r = subprocess.run([exe, d, str(NP), str(W), str(H), "3", str(iters), repr(min_opacity), repr(max_scale)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    fio.write_inputs(d, m, cam, gt=gt, tie_rank=m.tie_rank)
+    r = fio.run(exe, d, str(NP), str(W), str(H), "3", str(iters), repr(min_opacity), repr(max_scale))
     for _ in range(iters):
         trainer.training_step_fused(m, cam, gt, bg)
     n_removed, kept = m.prune(min_opacity, max_scale)
     assert 0 < n_removed < NP and f"prune removed {n_removed} size {m.P}" in r.stdout
     for _ in range(iters):
         trainer.training_step_fused(m, cam, gt, bg)
-    rd = lambda name, shape: np.fromfile(os.path.join(d, f"out_{name}.f32"), np.float32).reshape(shape)
+    rd = lambda name, shape: fio.read(d, name + ".f32", np.float32).numpy().reshape(shape)
     np.testing.assert_array_equal(rd("kept", (m.P,)).astype(np.int64), kept.cpu().numpy())
     for name, t in (("xyz", m.xyz), ("scaling", m.scaling), ("rotation", m.rotation), ("opacity", m.opacity), ("dc", m.features_dc), ("rest", m.features_rest),
                     ("m_xyz", m._m["xyz"][:m.P]), ("v_xyz", m._v["xyz"][:m.P])):

@@ -4,25 +4,19 @@ row array re-ordered in place), trainer.GaussianModel.resort / to_morton_order o
 The yardstick of the keys and of the permutation is tests/resort_ref.py: the header's rule in numpy float32 and a stable np.argsort.  The
 yardstick of the row move is torch indexing on the same tensors.  Every comparison is exact (integers, or int32 views of the rows)."""
 import ctypes
-import importlib.util
-import os
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 import torch
 
+import fused_check_io as fio
 import resort_ref as ref
+from gpu_helpers import bits, gpu, guarded, guards_intact, same_map
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [1, 63, 64, 65, 257, 4097, 70001]     # a partial wave, one wave and one over, more than one sort tile of 4096, many workgroups
-SENTINEL = 0x5A5A5A5A
-GUARD = 64                                     # guard words on either side of an output
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _libs():
@@ -31,31 +25,17 @@ def _libs():
     return _lib, _lib.lib()
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _guarded(n, dev):
-    """An int32 buffer of n words between two runs of guard words: (whole buffer, the n words as a view)."""
-    buf = torch.full((n + 2 * GUARD,), SENTINEL, dtype=torch.int32, device=dev)
-    return buf, buf[GUARD:GUARD + n]
-
-
-def _guards_intact(buf, n):
-    return bool((buf[:GUARD] == SENTINEL).all()) and bool((buf[GUARD + n:] == SENTINEL).all())
-
-
 def _order(xyz, box):
     """gslic_morton_order with guard words around both outputs -> (perm, keys_sorted) as uint32 numpy arrays."""
     _l, L = _libs()
     P, dev = int(xyz.shape[0]), xyz.device
-    pbuf, perm = _guarded(P, dev)
-    kbuf, keys = _guarded(P, dev)
+    pbuf, perm = guarded(P, device=dev)
+    kbuf, keys = guarded(P, device=dev)
     scratch = _l.TensorAllocator(dev)
     _l.check(L.gslic_morton_order(P, _l.ptr(xyz), _l.ptr(box), scratch.cb, None, ctypes.c_void_p(perm.data_ptr()), ctypes.c_void_p(keys.data_ptr()),
                                   _l.current_stream_ptr()))
     torch.cuda.synchronize()
-    assert _guards_intact(pbuf, P) and _guards_intact(kbuf, P)
+    assert guards_intact(pbuf, P) and guards_intact(kbuf, P)
     return perm.cpu().numpy().view(np.uint32), keys.cpu().numpy().view(np.uint32)
 
 
@@ -84,7 +64,7 @@ def _cloud(kind, P):
 @pytest.mark.parametrize("kind", ["lattice", "wild"])
 @pytest.mark.parametrize("P", SIZES)
 def test_keys_and_permutation_match_the_rule_on_bits(P, kind):
-    dev = _dev()
+    dev = gpu()
     xyz_c, boxes = _cloud(kind, P)
     xyz = xyz_c.to(dev)
     for box_c in boxes:
@@ -102,11 +82,11 @@ def test_keys_and_permutation_match_the_rule_on_bits(P, kind):
         assert np.array_equal(perm3, np.arange(P, dtype=np.uint32)) and np.array_equal(keys3, keys)
     # keys_sorted is optional
     _l, L = _libs()
-    pbuf, only = _guarded(P, dev)
+    pbuf, only = guarded(P, device=dev)
     scratch = _l.TensorAllocator(dev)
     _l.check(L.gslic_morton_order(P, _l.ptr(xyz), _l.ptr(box), scratch.cb, None, ctypes.c_void_p(only.data_ptr()), None, _l.current_stream_ptr()))
     torch.cuda.synchronize()
-    assert _guards_intact(pbuf, P) and np.array_equal(only.cpu().numpy().view(np.uint32), perm)
+    assert guards_intact(pbuf, P) and np.array_equal(only.cpu().numpy().view(np.uint32), perm)
 
 
 @pytest.mark.parametrize("copy", ["memcpy", "kernel"])     # the way back: one copy per array (the default), or the one launch of the A/B switch
@@ -114,7 +94,7 @@ def test_keys_and_permutation_match_the_rule_on_bits(P, kind):
 def test_permute_rows_matches_torch_indexing_in_place(which, copy, monkeypatch):
     monkeypatch.setenv("GSLIC_PERMUTE_COPY", copy)
     _l, L = _libs()
-    dev = _dev()
+    dev = gpu()
     cap, n = 8300, 8200                       # width 1: three workgroups of 4096 rows; width 45: 91 rows per workgroup; rows behind n stay
     widths = [1, 2, 3, 4, 45]
     g = torch.Generator().manual_seed(5)
@@ -126,10 +106,10 @@ def test_permute_rows_matches_torch_indexing_in_place(which, copy, monkeypatch):
     arr = (_l.RowArray * len(widths))(*[_l.RowArray(a.data_ptr(), a.data_ptr(), w) for a, w in zip(arrays, widths)])
     need = 4 * n * sum(widths)
     assert L.gslic_permute_rows_staging_bytes(arr, len(widths), n) == L.gslic_scratch_round_up(need)
-    sbuf, staging = _guarded(need // 4, dev)                           # exactly the sum: the rounding is advice for an allocator
+    sbuf, staging = guarded(need // 4, device=dev)                    # exactly the sum: the rounding is advice for an allocator
     _l.check(L.gslic_permute_rows(arr, len(widths), _l.ptr(perm32), n, ctypes.c_void_p(staging.data_ptr()), need, _l.current_stream_ptr()))
     torch.cuda.synchronize()
-    assert _guards_intact(sbuf, need // 4)
+    assert guards_intact(sbuf, need // 4)
     for a, b, p, w in zip(arrays, before, ptrs, widths):
         assert a.data_ptr() == p
         assert torch.equal(a[:n], b[:n][perm]), w
@@ -191,14 +171,7 @@ def _grown(raw, order, cam, gt, bg, dev, steps=2):
 
 
 def _storage(m):
-    return [(n, _bits(t[:m.P]).clone()) for _d, n, t, _w, _z in m._row_arrays()]
-
-
-def _same_map(a, b):
-    order = b.original_order()
-    for n in a.NAMES:
-        assert torch.equal(_bits(getattr(a, n).detach()), _bits(getattr(b, n).detach()[order])), n
-        assert torch.equal(_bits(a._m[n][:a.P]), _bits(b._m[n][:b.P][order])) and torch.equal(_bits(a._v[n][:a.P]), _bits(b._v[n][:b.P][order])), n
+    return [(n, bits(t[:m.P]).clone()) for _d, n, t, _w, _z in m._row_arrays()]
 
 
 def test_model_resort_is_the_reference_permutation_in_place_and_the_map_is_unchanged(monkeypatch):
@@ -206,13 +179,13 @@ def test_model_resort_is_the_reference_permutation_in_place_and_the_map_is_uncha
     from gaussian_lic_amd.camera import synthetic_camera
     from gaussian_lic_amd.rasterizer import render
     from gaussian_lic_amd.synthetic import gt_image
-    dev = _dev()
+    dev = gpu()
     cam = synthetic_camera(W, H).to_device(dev)
     gt, bg = gt_image(H, W).to(dev), torch.zeros(3, device=dev)
     raw = _scene()
     monkeypatch.delenv("GSLIC_RESORT", raising=False)
     a, b, c = (_grown(raw, o, cam, gt, bg, dev) for o in ("insertion", "morton", "morton"))
-    _same_map(a, b)
+    same_map(a, b)
     assert all(torch.equal(x, y) for (_n, x), (_n2, y) in zip(_storage(b), _storage(c)))     # (c is b again: it takes the torch route below)
     st = trainer.ContributionStats(b)
     with torch.no_grad():
@@ -245,7 +218,7 @@ def test_model_resort_is_the_reference_permutation_in_place_and_the_map_is_uncha
     for (n, x), (_n, y) in zip(_storage(b), _storage(c)):
         assert torch.equal(x, y), n
     # still the insertion-order twin's map: the image, and fused steps after the re-sort
-    _same_map(a, b)
+    same_map(a, b)
     with torch.no_grad():
         ia, ib = render(cam, a, bg)[0], render(cam, b, bg)[0]
     assert torch.equal(ia, ib)
@@ -253,7 +226,7 @@ def test_model_resort_is_the_reference_permutation_in_place_and_the_map_is_uncha
         la, _x = trainer.training_step_fused(a, cam, gt, bg)
         lb, _y = trainer.training_step_fused(b, cam, gt, bg)
     assert torch.equal(torch.as_tensor(la), torch.as_tensor(lb))
-    _same_map(a, b)
+    same_map(a, b)
     # to_morton_order(): the insertion-order twin becomes a Morton model with b's storage (b re-sorted on the same positions first)
     b.resort()
     with pytest.raises(AssertionError, match="insertion order"):
@@ -289,14 +262,9 @@ def test_fused_resort_cpp_host(tmp_path, monkeypatch):
     from gaussian_lic_amd.camera import synthetic_camera
     from gaussian_lic_amd.rasterizer import render
     from gaussian_lic_amd.synthetic import gt_image
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussian-lic_amd", "shim", "build_shim.py")
-    spec = importlib.util.spec_from_file_location("build_shim", path)
-    build_shim = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_check("fused_resort")
-    assert os.path.exists(exe)
+    exe = fio.build("fused_resort")
     monkeypatch.delenv("GSLIC_RESORT", raising=False)
-    dev = _dev()
+    dev = gpu()
     cam = synthetic_camera(W, H).to_device(dev)
     gt, bg = gt_image(H, W).to(dev), torch.zeros(3, device=dev)
     raw = _scene(seed=9)
@@ -305,13 +273,8 @@ def test_fused_resort_cpp_host(tmp_path, monkeypatch):
     m = trainer.GaussianModel({k: (v.clone() if torch.is_tensor(v) else v) for k, v in raw.items()}, dev)
     m.training_setup()
     d = str(tmp_path)
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"), ("features_rest", "rest")):
-        w(n, getattr(m, k).detach().cpu().numpy())
     pts, col, rsp, Rcw, tcw, intr = _frame(cam, dev, n=n_pts)
-    w("pts", pts.cpu().numpy()); w("col", col.cpu().numpy()); w("rsp", rsp.cpu().numpy()); w("Rcw", Rcw.numpy()); w("tcw", tcw.numpy())
-    w("view", cam.world_view_transform); w("proj", cam.full_proj_transform); w("campos", cam.camera_center); w("gt", gt.cpu().numpy())
-    w("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos, *intr], np.float32))
+    fio.write_inputs(d, m, cam, scalars_extra=intr, gt=gt, pts=pts, col=col, rsp=rsp, Rcw=Rcw, tcw=tcw)
 
     def steps():
         for _ in range(iters):
@@ -319,7 +282,7 @@ def test_fused_resort_cpp_host(tmp_path, monkeypatch):
     steps()
     with torch.no_grad():
         err = (render(cam, m, bg)[0] - gt).abs().mean(0).contiguous()
-    w("err", err.cpu().numpy())
+    fio.write(d, "err", err)
     st = trainer.ContributionStats(m)
     st.accumulate(cam, w_min=w_min, error=err)
     perm0 = m.to_morton_order(resort_fraction=fraction)                 # the first sort, from insertion order
@@ -337,15 +300,13 @@ def test_fused_resort_cpp_host(tmp_path, monkeypatch):
     assert removed > 0 and m._sorted_P == m.P > 1000                    # (a compaction keeps the sorted block sorted)
     perm2 = m.resort()
     steps()
-    r = subprocess.run([exe, d, str(P0), str(W), str(H), "3", str(iters), str(n_pts), repr(fraction), repr(min_opacity), repr(max_scale), repr(w_min)],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = fio.run(exe, d, str(P0), str(W), str(H), "3", str(iters), str(n_pts), repr(fraction), repr(min_opacity), repr(max_scale), repr(w_min))
     assert f"resort extended {k} resorts 2 pruned {removed} size {m.P}" in r.stdout
-    rd = lambda name, dt: torch.from_numpy(np.fromfile(os.path.join(d, "out_" + name), dt))
+    rd = functools.partial(fio.read, d)
     P = m.P
     for n, f in (("xyz", "xyz"), ("features_dc", "dc"), ("features_rest", "rest"), ("opacity", "opacity"), ("scaling", "scaling"), ("rotation", "rotation")):
         for pre, src in (("", m._buf), ("m_", m._m), ("v_", m._v)):
-            assert torch.equal(rd(pre + f + ".f32", np.int32), _bits(src[n][:P]).cpu().reshape(-1)), pre + f
+            assert torch.equal(rd(pre + f + ".f32", np.int32), bits(src[n][:P]).cpu().reshape(-1)), pre + f
     assert torch.equal(rd("tie.i32", np.int32), m.tie_rank.cpu())
     assert torch.equal(rd("err_sum.i64", np.int64), st.error_fixed().cpu())
     assert torch.equal(rd("perm0.i64", np.int64), perm0.cpu()) and torch.equal(rd("perm2.i64", np.int64), perm2.cpu())

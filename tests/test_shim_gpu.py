@@ -1,4 +1,5 @@
 """-m gpu: the C++ LibTorch shim (reference L2 signatures) and the reference's own host code on top of it."""
+import functools
 import os
 import subprocess
 
@@ -6,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import fused_check_io as fio
 from conftest import make_scene, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -72,16 +74,9 @@ def test_reference_host_code_drives_the_hip_kernels(tmp_path):
     P, W, H, iters = 30000, 320, 240, 3
     raw, sc, camd, cam = make_scene("random", P, W, H, 3, 41)
     d = str(tmp_path)
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"),
-                 ("features_rest", "rest")):
-        w(n, raw[k].numpy())
-    w("view", cam.world_view_transform); w("proj", cam.full_proj_transform); w("campos", cam.camera_center)
     gt = gt_image(H, W)
-    w("gt", gt.numpy())
-    w("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos], np.float32))
-    r = subprocess.run([CHECK, d, str(P), str(W), str(H), "3", str(iters)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    fio.write_inputs(d, raw, cam, gt=gt)
+    fio.run(CHECK, d, str(P), str(W), str(H), "3", str(iters))
     dev = torch.device("cuda:0")
     model = trainer.GaussianModel(raw, dev)
     model.training_setup()
@@ -89,7 +84,7 @@ def test_reference_host_code_drives_the_hip_kernels(tmp_path):
     bg = torch.zeros(3, device=dev)
     for _ in range(iters):
         trainer.training_step(model, cam, gt.to(dev), bg, raw_render=False)   # (the C++ program runs renderer.cpp as written)
-    rd = lambda name, shape: np.fromfile(os.path.join(d, f"out_{name}.f32"), np.float32).reshape(shape)
+    rd = lambda name, shape: fio.read(d, name + ".f32", np.float32).numpy().reshape(shape)
     for name, t in (("xyz", model.xyz), ("scaling", model.scaling), ("rotation", model.rotation), ("opacity", model.opacity),
                     ("dc", model.features_dc), ("rest", model.features_rest)):
         got = rd(name, tuple(t.shape))
@@ -98,8 +93,7 @@ def test_reference_host_code_drives_the_hip_kernels(tmp_path):
     # grad.clone()) instead of the reference's (six adamUpdate launches): bit-identical parameters and image
     if os.path.exists(CHECK_GROUPS):
         first = {n: rd(n, (-1,)).copy() for n in ("image", "xyz", "scaling", "rotation", "opacity", "dc", "rest")}
-        r = subprocess.run([CHECK_GROUPS, d, str(P), str(W), str(H), "3", str(iters)], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        fio.run(CHECK_GROUPS, d, str(P), str(W), str(H), "3", str(iters))
         for n, a in first.items():
             np.testing.assert_array_equal(rd(n, (-1,)), a, err_msg=n)
         # and with the N > 1 exchange step compiled in (shim/include/gslic_dist.h: c10d ProcessGroupNCCL = RCCL, all-reduce of the
@@ -108,8 +102,7 @@ def test_reference_host_code_drives_the_hip_kernels(tmp_path):
         if os.path.exists(CHECK_DIST):
             for sparse, port in (("0", "29601"), ("1", "29603")):
                 env = dict(os.environ, RANK="0", WORLD_SIZE="1", MASTER_PORT=port, GSLIC_SPARSE_EXCHANGE=sparse, HSA_ENABLE_IPC_MODE_LEGACY="0")
-                r = subprocess.run([CHECK_DIST, d, str(P), str(W), str(H), "3", str(iters)], capture_output=True, text=True, timeout=300, env=env)
-                assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+                fio.run(CHECK_DIST, d, str(P), str(W), str(H), "3", str(iters), env=env)
                 for n, a in first.items():
                     np.testing.assert_array_equal(rd(n, (-1,)), a, err_msg=f"{n} (dist, sparse={sparse})")
             # rank-1 exchange (gslic_dist.h exchange_gradients_rank1: 11 floats all-reduced, dL_ddc all-gathered, dL_ddc / dL_dsh rebuilt by
@@ -117,20 +110,9 @@ def test_reference_host_code_drives_the_hip_kernels(tmp_path):
             # autograd rows it replaces, equal to fp32 rounding (Adam's normalised update turns a last-bit change of a near-zero gradient into a
             # visible change of that element's step, hence 1e-4 of max-abs after three steps rather than 1e-6)
             env = dict(os.environ, RANK="0", WORLD_SIZE="1", MASTER_PORT="29605", GSLIC_EXCHANGE="rank1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-            r = subprocess.run([CHECK_DIST, d, str(P), str(W), str(H), "3", str(iters)], capture_output=True, text=True, timeout=300, env=env)
-            assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+            fio.run(CHECK_DIST, d, str(P), str(W), str(H), "3", str(iters), env=env)
             for n, a in first.items():
                 assert rel_err(rd(n, (-1,)), a) < 1e-4, f"{n} (dist, rank1)"
-
-
-def _write_case(d, raw, cam, gt):
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"),
-                 ("features_rest", "rest")):
-        w(n, raw[k].numpy())
-    w("view", cam.world_view_transform); w("proj", cam.full_proj_transform); w("campos", cam.camera_center)
-    w("gt", gt.numpy())
-    w("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos], np.float32))
 
 
 @pytest.mark.parametrize("deg", [3, 0])
@@ -147,9 +129,8 @@ def test_fused_cpp_host(tmp_path, deg):
     raw, sc, camd, cam = make_scene("random", P, W, H, deg, 43)
     d = str(tmp_path)
     gt = gt_image(H, W)
-    _write_case(d, raw, cam, gt)
-    r = subprocess.run([CHECK_FUSED, d, str(P), str(W), str(H), str(deg), str(iters)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    fio.write_inputs(d, raw, cam, gt=gt)
+    r = fio.run(CHECK_FUSED, d, str(P), str(W), str(H), str(deg), str(iters))
     dev = torch.device("cuda:0")
     model = trainer.GaussianModel(raw, dev)
     model.training_setup()
@@ -159,7 +140,7 @@ def test_fused_cpp_host(tmp_path, deg):
     for _ in range(iters):
         terms, _vis = trainer.training_step_fused(model, cam, gt.to(dev), bg)
         losses.append(float(0.8 * terms[0] + 0.2 * (1.0 - terms[1])))
-    rd = lambda name, shape: np.fromfile(os.path.join(d, f"out_{name}.f32"), np.float32).reshape(shape)
+    rd = lambda name, shape: fio.read(d, name + ".f32", np.float32).numpy().reshape(shape)
     names = [("xyz", model.xyz), ("scaling", model.scaling), ("rotation", model.rotation), ("opacity", model.opacity), ("dc", model.features_dc)]
     if deg > 0:
         names.append(("rest", model.features_rest))
@@ -187,7 +168,6 @@ def test_fused_cpp_host_extend(tmp_path):
     P = int(raw["xyz"].shape[0])
     d = str(tmp_path)
     gt = gt_image(H, W)
-    _write_case(d, raw, cam, gt)
     frame = lidar_scene(4000, W, H, sh_degree=3, seed=101)
     f_pts = frame["xyz"].contiguous()
     f_col = (frame["features_dc"].reshape(-1, 3) * 0.28209479177387814 + 0.5).contiguous()
@@ -195,12 +175,9 @@ def test_fused_cpp_host_extend(tmp_path):
     Rcw = np.ascontiguousarray(cam.world_view_transform[:3, :3].T, np.float32)
     tcw = np.ascontiguousarray(cam.world_view_transform[3, :3], np.float32)
     intr = np.array([cam.fx, cam.fy, cam.cx, cam.cy], np.float32)
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    w("frame_pts", f_pts.numpy()); w("frame_col", f_col.numpy()); w("frame_rsp", f_rsp.numpy())
-    w("frame_pose", np.concatenate([Rcw.reshape(-1), tcw.reshape(-1), intr]))
-    w("frame_n", np.array([f_pts.shape[0]], np.float32))
-    r = subprocess.run([CHECK_FUSED, d, str(P), str(W), str(H), str(deg), str(iters)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    fio.write_inputs(d, raw, cam, gt=gt, frame_pts=f_pts, frame_col=f_col, frame_rsp=f_rsp,
+                     frame_pose=np.concatenate([Rcw.reshape(-1), tcw.reshape(-1), intr]), frame_n=np.array([f_pts.shape[0]], np.float32))
+    r = fio.run(CHECK_FUSED, d, str(P), str(W), str(H), str(deg), str(iters))
     ins = [l for l in r.stdout.splitlines() if l.startswith("extend inserted")]
     assert ins, r.stdout[-1000:]
     k_cpp, size_cpp = int(ins[0].split()[2]), int(ins[0].split()[4])
@@ -215,7 +192,7 @@ def test_fused_cpp_host_extend(tmp_path):
     for _ in range(iters):
         trainer.training_step_fused(model, cam, gt.to(dev), bg)
     assert k_cpp == k_py and k_py > 100 and size_cpp == model.P
-    rd = lambda name, shape: np.fromfile(os.path.join(d, f"out_{name}.f32"), np.float32).reshape(shape)
+    rd = lambda name, shape: fio.read(d, name + ".f32", np.float32).numpy().reshape(shape)
     for name, t in (("xyz", model.xyz), ("scaling", model.scaling), ("rotation", model.rotation), ("opacity", model.opacity),
                     ("dc", model.features_dc), ("rest", model.features_rest)):
         np.testing.assert_array_equal(rd(name, tuple(t.shape)), t.detach().cpu().numpy(), err_msg=name)
@@ -258,9 +235,9 @@ def test_reference_host_two_ranks_rccl(tmp_path):
     P, W, H, iters = 30000, 320, 240, 3
     raw, sc, camd, cam = make_scene("random", P, W, H, 3, 41)
     d = str(tmp_path)
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"), ("features_rest", "rest")):
-        w(n, raw[k].numpy())
+    w = functools.partial(fio.write, d)   # (per-rank files view_<k> / gt_<k> and no untagged camera: not fio.write_inputs' layout)
+    for k, n in fio.GROUPS:
+        w(n, raw[k])
     cams, gts = [synthetic_camera(W, H, k) for k in range(2)], [gt_image(H, W, seed=2 + k) for k in range(2)]
     for k in range(2):
         w(f"view_{k}", cams[k].world_view_transform); w(f"proj_{k}", cams[k].full_proj_transform); w(f"campos_{k}", cams[k].camera_center)
@@ -289,7 +266,7 @@ def test_reference_host_two_ranks_rccl(tmp_path):
             vis = v if vis is None else (vis | v)
         model.optimizer.set_visibility_and_N(vis, model.P)
         model.optimizer.step(acc)
-    rd = lambda name, shape: np.fromfile(os.path.join(d, f"out_{name}.f32"), np.float32).reshape(shape)
+    rd = lambda name, shape: fio.read(d, name + ".f32", np.float32).numpy().reshape(shape)
     for name, t in (("xyz", model.xyz), ("scaling", model.scaling), ("rotation", model.rotation), ("opacity", model.opacity),
                     ("dc", model.features_dc), ("rest", model.features_rest)):
         assert rel_err(rd(name, tuple(t.shape)), t.detach().cpu().numpy()) < 1e-5, name
@@ -312,19 +289,13 @@ def test_dropin_renderer_cpp(tmp_path):
     P, W, H, iters = 30000, 320, 240, 3
     raw, sc, camd, cam = make_scene("random", P, W, H, 3, 43)
     d = str(tmp_path)
-    w = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"), ("features_rest", "rest")):
-        w(n, raw[k].numpy())
-    w("view", cam.world_view_transform); w("proj", cam.full_proj_transform); w("campos", cam.camera_center)
-    w("gt", gt_image(H, W).numpy())
-    w("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos], np.float32))
+    fio.write_inputs(d, raw, cam, gt=gt_image(H, W))
     names = ("image", "xyz", "scaling", "rotation", "opacity", "dc", "rest")
-    rd = lambda name: np.fromfile(os.path.join(d, f"out_{name}.f32"), np.float32)
+    rd = lambda name: fio.read(d, name + ".f32", np.float32).numpy()
     lrs = dict(xyz=1.6e-4, dc=2.5e-3, rest=2.5e-3 / 20.0, opacity=5e-2, scaling=5e-3, rotation=1e-3)
 
     def run(exe):
-        r = subprocess.run([exe, d, str(P), str(W), str(H), "3", str(iters)], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        r = fio.run(exe, d, str(P), str(W), str(H), "3", str(iters))
         losses = [float(l.split()[3]) for l in r.stdout.splitlines() if l.startswith("iter ")]
         return {n: rd(n).copy() for n in names}, losses
 
@@ -357,9 +328,8 @@ def test_fused_cpp_host_pose_gradient(tmp_path):
     cam = synthetic_camera(W, H, 7)
     d = str(tmp_path)
     gt = gt_image(H, W)
-    _write_case(d, raw, cam, gt)
-    r = subprocess.run([CHECK_FUSED, d, str(P), str(W), str(H), str(deg), "1"], capture_output=True, text=True, timeout=300, env=dict(os.environ, GSLIC_CHECK_POSE="1"))   # (the gradient is printed before the one step)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    fio.write_inputs(d, raw, cam, gt=gt)
+    r = fio.run(CHECK_FUSED, d, str(P), str(W), str(H), str(deg), "1", env=dict(os.environ, GSLIC_CHECK_POSE="1"))   # (the gradient is printed before the one step)
     got = np.array([float(v) for v in [l for l in r.stdout.splitlines() if l.startswith("pose_gradient")][-1].split()[1:]])
     dev = torch.device("cuda:0")
     model = trainer.GaussianModel(raw, dev)

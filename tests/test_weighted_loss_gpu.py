@@ -2,22 +2,21 @@
 the pinned operators (bit for bit) and a float64 reference, FusedLoss / training_step_fused / GraphedStep / pose_gradient with weight=..., and the
 C++ host's gslic::FusedStep with a weight image."""
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import fused_check_io as fio
 import weighted_loss_ref as wr
 from conftest import make_scene
+from gpu_helpers import assert_same_state, bits, gpu, guarded, guards_intact, model_state, training_model
 
 pytestmark = pytest.mark.gpu
 
 LAM = 0.2
 SHAPES = [(1, 1), (32, 32), (31, 33), (33, 65), (70, 45), (130, 40)]
-GUARD = 64                      # guard words on both sides of every output buffer
-GUARD_BITS = 0x7FC0FFEE         # (a NaN pattern no kernel produces)
+GUARD_BITS = 0x7FC0FFEE         # the guard words here: a NaN pattern no kernel produces (the outputs are floats)
 LAMBDA_D = 0.5
 
 # S against the float64 sum of the clamped weights.  The kernels add non-negative float32 numbers along a fixed tree: at most 7 additions in a
@@ -28,21 +27,12 @@ S_TREE_DEPTH = 7 + 6 + 2 + 1 + 6 + 2
 S_BAR = (1.0 + 2.0 ** -24) ** S_TREE_DEPTH - 1.0
 
 
-def _dev():
-    return torch.device("cuda:0")
+def _nan_guarded(n):
+    buf, words = guarded(n, sentinel=GUARD_BITS)
+    return buf, words.view(torch.float32)
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _guarded(n):
-    buf = torch.full((n + 2 * GUARD,), GUARD_BITS, dtype=torch.int32, device=_dev())
-    return buf, buf[GUARD:GUARD + n].view(torch.float32)
-
-
-def _guards_intact(buf, n):
-    return bool((buf[:GUARD] == GUARD_BITS).all()) and bool((buf[GUARD + n:] == GUARD_BITS).all())
+_nan_guards_intact = functools.partial(guards_intact, sentinel=GUARD_BITS)
 
 
 def _weighted(img, gt, w, lam=LAM):
@@ -51,16 +41,16 @@ def _weighted(img, gt, w, lam=LAM):
     L, p = _lib.lib(), _lib.ptr
     CH, H, W = img.shape
     n_part = int(L.gslic_l1_ssim_loss_weighted_partials_count(CH, H, W))
-    gb_dL, dL = _guarded(CH * H * W)
-    gb_p, partials = _guarded(n_part)
-    gb_t, terms = _guarded(3)
+    gb_dL, dL = _nan_guarded(CH * H * W)
+    gb_p, partials = _nan_guarded(n_part)
+    gb_t, terms = _nan_guarded(3)
     d = [torch.empty_like(img) for _ in range(3)]
     _lib.check(L.gslic_l1_ssim_loss_weighted_forward_backward(CH, H, W, loss.C1, loss.C2, lam, p(img), p(gt), p(w), p(d[0]), p(d[1]), p(d[2]), p(partials),
                                                               p(terms), p(dL), _lib.current_stream_ptr()))
     torch.cuda.synchronize()
-    assert _guards_intact(gb_dL, CH * H * W), "dL_dimg guard"
-    assert _guards_intact(gb_p, n_part), "partials guard"
-    assert _guards_intact(gb_t, 3), "terms guard"
+    assert _nan_guards_intact(gb_dL, CH * H * W), "dL_dimg guard"
+    assert _nan_guards_intact(gb_p, n_part), "partials guard"
+    assert _nan_guards_intact(gb_t, 3), "terms guard"
     return dL.view(CH, H, W).clone(), terms.clone()
 
 
@@ -89,7 +79,7 @@ def _case(H, W):
     """Images of a shape on the device, the existing unweighted kernels' result on them, and the float64 reference at w == 1 (computed once)."""
     from gaussian_lic_amd import loss
     img_h, gt_h = wr.images(H, W, 11 + H)
-    img, gt = img_h.to(_dev()), gt_h.to(_dev())
+    img, gt = img_h.to(gpu()), gt_h.to(gpu())
     fl = loss.FusedLoss(LAM)
     dL, terms = fl.forward_backward(img, gt)
     ssim_map = loss.fusedssim(loss.C1, loss.C2, img.unsqueeze(0), gt.unsqueeze(0), False)[0][0]
@@ -108,9 +98,9 @@ def _grad_gap(got, ref64, S):
 @pytest.mark.parametrize("H,W", SHAPES)
 def test_unit_weight_reproduces_the_unweighted_entry_point_bit_for_bit(H, W):
     c = _case(H, W)
-    dL, terms = _weighted(c["img"], c["gt"], torch.ones(H, W, device=_dev()))
-    assert torch.equal(_bits(dL), _bits(c["dL"]))
-    assert torch.equal(_bits(terms[:2]), _bits(c["terms"]))
+    dL, terms = _weighted(c["img"], c["gt"], torch.ones(H, W, device=gpu()))
+    assert torch.equal(bits(dL), bits(c["dL"]))
+    assert torch.equal(bits(terms[:2]), bits(c["terms"]))
     assert float(terms[2]) == float(H * W)
 
 
@@ -122,7 +112,7 @@ def test_gradient_is_the_chain_of_the_pinned_operators_bit_for_bit(H, W):
     for name in wr.PATTERNS:
         w_h = wr.weight_pattern(name, H, W, seed=H)
         clean_h = wr.clamp_weight(w_h)
-        w, clean = w_h.to(_dev()), clean_h.to(_dev())
+        w, clean = w_h.to(gpu()), clean_h.to(gpu())
         dL, terms = _weighted(img, gt, w)                                   # (8: the guard words are checked inside)
         S = float(terms[2])
         S64 = float(clean_h.double().sum())
@@ -142,10 +132,10 @@ def test_gradient_is_the_chain_of_the_pinned_operators_bit_for_bit(H, W):
         # 6. the sanitised pattern is its clamped copy
         if name == "dirty":
             dL_c, terms_c = _weighted(img, gt, clean)
-            assert torch.equal(_bits(dL), _bits(dL_c)) and torch.equal(_bits(terms), _bits(terms_c))
+            assert torch.equal(bits(dL), bits(dL_c)) and torch.equal(bits(terms), bits(terms_c))
         # 7. repeats
         dL2, terms2 = _weighted(img, gt, w)
-        assert torch.equal(_bits(dL), _bits(dL2)) and torch.equal(_bits(terms), _bits(terms2)), name
+        assert torch.equal(bits(dL), bits(dL2)) and torch.equal(bits(terms), bits(terms2)), name
 
 
 # ---------------------------------------------------------------------------------------------------- 4. against the float64 reference
@@ -166,7 +156,7 @@ def test_terms_and_gradient_against_the_float64_reference():
         c = _case(H, W)
         for name in wr.PATTERNS:
             w_h = wr.weight_pattern(name, H, W, seed=H)
-            dL, terms = _weighted(c["img"], c["gt"], w_h.to(_dev()))
+            dL, terms = _weighted(c["img"], c["gt"], w_h.to(gpu()))
             ref_t, ref_g = wr.weighted_reference(c["img_h"], c["gt_h"], w_h, LAM)
             gt_, gg_ = float(np.abs(terms[:2].double().cpu().numpy() - ref_t[:2]).max()), _grad_gap(dL, ref_g, float(ref_t[2]))
             print(f"[weighted loss gap] {H}x{W} {name}: terms {gt_:.3e}  gradient {gg_:.3e}")
@@ -183,10 +173,10 @@ def test_fused_loss_with_a_weight_keeps_terms3_and_exposes_the_sum():
     from gaussian_lic_amd import loss
     H, W = 70, 45
     c = _case(H, W)
-    w = wr.weight_pattern("uniform", H, W, seed=H).to(_dev())
+    w = wr.weight_pattern("uniform", H, W, seed=H).to(gpu())
     ref_dL, ref_terms = _weighted(c["img"], c["gt"], w)
     fl = loss.FusedLoss(LAM)
-    depth, gtd = torch.rand(H, W, device=_dev()) + 0.5, torch.rand(H, W, device=_dev())
+    depth, gtd = torch.rand(H, W, device=gpu()) + 0.5, torch.rand(H, W, device=gpu())
     _dLd, term_d = fl.depth_forward_backward(depth, gtd, LAMBDA_D)
     L_d = term_d.clone()
     dL, terms = fl.forward_backward(c["img"], c["gt"], w)
@@ -203,7 +193,7 @@ def test_fused_loss_with_a_weight_keeps_terms3_and_exposes_the_sum():
     (2.0 * v).backward()
     assert torch.equal(v.detach(), fl.value(ref_terms[:2])) and torch.equal(x.grad, ref_dL * 2.0)
     # evaluation: the weighted PSNR / SSIM leave out what the weight leaves out
-    m = wr.weight_pattern("frame", H, W).to(_dev())
+    m = wr.weight_pattern("frame", H, W).to(gpu())
     ps = float(loss.psnr(c["img"], c["gt"], m))
     mse = float(((c["img_h"].double() - c["gt_h"].double()) ** 2 * m.cpu().double()).sum() / (3 * m.cpu().double().sum()))
     assert abs(ps - 10.0 * np.log10(1.0 / mse)) < 1e-3
@@ -214,33 +204,9 @@ def _setup(P=5000, W=160, H=120, deg=3, seed=5):
     import gaussian_lic_amd  # noqa: F401
     from gaussian_lic_amd.synthetic import gt_image
     raw, sc, camd, cam = make_scene("random", P, W, H, deg, seed)
-    cam.to_device(_dev())
-    gtd = cam.project_depth(raw["xyz"][::5].float() * 1.1).to(_dev())
-    return raw, cam, gt_image(H, W, seed=seed).to(_dev()), gtd, torch.zeros(3, device=_dev())
-
-
-def _model(raw):
-    from gaussian_lic_amd import trainer
-    m = trainer.GaussianModel({k: (v.clone() if torch.is_tensor(v) else v) for k, v in raw.items()}, _dev())
-    m.training_setup()
-    return m
-
-
-def _state(m):
-    out = {}
-    for i, n in enumerate(m.NAMES):
-        out[n] = getattr(m, n).detach().cpu().clone()
-        st = m.optimizer.state[i]
-        if st is not None:
-            out[n + ".m"] = st["exp_avg"].cpu().clone()
-            out[n + ".v"] = st["exp_avg_sq"].cpu().clone()
-    return out
-
-
-def _assert_same_state(a, b):
-    assert a.keys() == b.keys()
-    for k in a:
-        assert torch.equal(a[k], b[k]), k
+    cam.to_device(gpu())
+    gtd = cam.project_depth(raw["xyz"][::5].float() * 1.1).to(gpu())
+    return raw, cam, gt_image(H, W, seed=seed).to(gpu()), gtd, torch.zeros(3, device=gpu())
 
 
 def _assembled_step(model, cam, gt, bg, w, gtd, camera_grads=False):
@@ -257,8 +223,8 @@ def _assembled_step(model, cam, gt, bg, w, gtd, camera_grads=False):
             dLd = loss.FusedLoss(LAM).depth_forward_backward(depth, gtd, LAMBDA_D)[0]
         if camera_grads:
             return rr.backward(dL, dLd, camera_grads=True)
-        xg = torch.empty(model.P, 3, device=_dev()) if gtd is not None else None
-        vis = torch.empty(model.P, dtype=torch.uint8, device=_dev())
+        xg = torch.empty(model.P, 3, device=gpu()) if gtd is not None else None
+        vis = torch.empty(model.P, dtype=torch.uint8, device=gpu())
         rr.backward(dL, dLd, adam=model.optimizer.fused_descriptor(visible_out=vis), xyz_grad=xg)
         model.optimizer.count_step()
 
@@ -268,25 +234,25 @@ def test_fused_step_with_a_weight_is_the_assembled_step_bit_for_bit(with_depth):
     from gaussian_lic_amd import loss, trainer
     raw, cam, gt, gtd, bg = _setup()
     H, W = gt.shape[1:]
-    w = wr.weight_pattern("frame", H, W).to(_dev()) * wr.weight_pattern("mask", H, W).to(_dev())      # a 0/1 mask: its sum is exact in any order
+    w = wr.weight_pattern("frame", H, W).to(gpu()) * wr.weight_pattern("mask", H, W).to(gpu())      # a 0/1 mask: its sum is exact in any order
     kw = dict(gt_depth=gtd, lambda_depth=LAMBDA_D) if with_depth else {}
-    a, b = _model(raw), _model(raw)
+    a, b = training_model(raw), training_model(raw)
     fl = loss.FusedLoss(LAM)
     for _ in range(3):
         terms, vis = trainer.training_step_fused(a, cam, gt, bg, fused_loss=fl, weight=w, **kw)
         _assembled_step(b, cam, gt, bg, w, gtd if with_depth else None)
         assert terms.numel() == (3 if with_depth else 2) and bool(vis.any())
         assert float(fl.weight_sum) == float(w.sum())
-    _assert_same_state(_state(a), _state(b))
+    assert_same_state(model_state(a), model_state(b))
     # weight = ones is weight = None
-    c, d = _model(raw), _model(raw)
-    ones = torch.ones(H, W, device=_dev())
+    c, d = training_model(raw), training_model(raw)
+    ones = torch.ones(H, W, device=gpu())
     for _ in range(3):
         tc, _v = trainer.training_step_fused(c, cam, gt, bg, weight=ones, **kw)
         td, _v = trainer.training_step_fused(d, cam, gt, bg, **kw)
         assert torch.equal(tc, td)
-    _assert_same_state(_state(c), _state(d))
-    assert not torch.equal(_state(a)["xyz"], _state(d)["xyz"])            # the mask changed the step
+    assert_same_state(model_state(c), model_state(d))
+    assert not torch.equal(model_state(a)["xyz"], model_state(d)["xyz"])            # the mask changed the step
 
 
 def test_fused_step_with_a_weight_matches_the_autograd_step():
@@ -295,8 +261,8 @@ def test_fused_step_with_a_weight_matches_the_autograd_step():
     from gaussian_lic_amd import loss, trainer
     raw, cam, gt, gtd, bg = _setup(P=30000, W=320, H=240, seed=61)
     H, W = gt.shape[1:]
-    w = wr.weight_pattern("uniform", H, W).to(_dev()) * wr.weight_pattern("frame", H, W).to(_dev())
-    a, b = _model(raw), _model(raw)
+    w = wr.weight_pattern("uniform", H, W).to(gpu()) * wr.weight_pattern("frame", H, W).to(gpu())
+    a, b = training_model(raw), training_model(raw)
     lossv, vis = trainer.training_step(a, cam, gt, bg, do_step=False, raw_render=False, weight=w)
     ref = [p.grad.clone() for p in a.parameters()]
     captured = {}
@@ -312,7 +278,7 @@ def test_fused_step_with_a_weight_matches_the_autograd_step():
         err = float((g.reshape(g_ref.shape) - g_ref).abs().max()) / max(scale, 1e-30)
         assert err < 5e-5, (name, err)
     # the one-node loss on the same step
-    c = _model(raw)
+    c = training_model(raw)
     loss1, _v = trainer.training_step(c, cam, gt, bg, do_step=False, raw_render=False, one_node_loss=True, weight=w)
     assert abs(float(loss1) - float(lossv)) < 2e-6
 
@@ -325,10 +291,10 @@ def test_graphed_step_with_a_weight_equals_eager_steps(use_graph):
     from gaussian_lic_amd.synthetic import gt_image
     raw, cam, gt, gtd, bg = _setup(P=20000, W=320, H=240, seed=91)
     W, H = 320, 240
-    cams = [synthetic_camera(W, H, k).to_device(_dev()) for k in range(3)]
-    gts = [gt_image(H, W, seed=40 + k).to(_dev()) for k in range(3)]
-    ws = [wr.weight_pattern(n, H, W, seed=k).to(_dev()) for k, n in enumerate(("mask", "frame", "uniform"))]
-    a, b = _model(raw), _model(raw)
+    cams = [synthetic_camera(W, H, k).to_device(gpu()) for k in range(3)]
+    gts = [gt_image(H, W, seed=40 + k).to(gpu()) for k in range(3)]
+    ws = [wr.weight_pattern(n, H, W, seed=k).to(gpu()) for k, n in enumerate(("mask", "frame", "uniform"))]
+    a, b = training_model(raw), training_model(raw)
     gs = trainer.GraphedStep(a, cams[0], gts[0], bg, use_graph=use_graph, weight=ws[0])
     eager_terms, graphed_terms = [], []
     for k in (0, 1, 2, 1):
@@ -337,16 +303,16 @@ def test_graphed_step_with_a_weight_equals_eager_steps(use_graph):
     assert gs.check() == 0
     for x, y in zip(graphed_terms, eager_terms):
         assert x.numel() == 2 and torch.equal(x, y)
-    _assert_same_state(_state(a), _state(b))
+    assert_same_state(model_state(a), model_state(b))
 
 
 def test_graphed_step_weight_mismatches_raise():
     from gaussian_lic_amd import trainer
     raw, cam, gt, gtd, bg = _setup()
     H, W = gt.shape[1:]
-    w = wr.weight_pattern("mask", H, W).to(_dev())
-    m = _model(raw)
-    before = _state(m)
+    w = wr.weight_pattern("mask", H, W).to(gpu())
+    m = training_model(raw)
+    before = model_state(m)
     plain = trainer.GraphedStep(m, cam, gt, bg)
     with pytest.raises(ValueError, match="built without"):
         plain.step(cam, gt, weight=w)                       # built without a weight, handed one
@@ -355,7 +321,7 @@ def test_graphed_step_weight_mismatches_raise():
         weighted.step(cam, gt, weight=False)                # built with a weight, told to run without one
     with pytest.raises(ValueError, match="shape"):
         weighted.step(cam, gt, weight=w[:-1])
-    _assert_same_state(before, _state(m))
+    assert_same_state(before, model_state(m))
 
 
 # ---------------------------------------------------------------------------------------------------- 11. the pose gradient
@@ -364,25 +330,25 @@ def test_pose_gradient_with_a_weight_is_the_chain_fed_backward(with_depth):
     from gaussian_lic_amd import trainer
     raw, cam, gt, gtd, bg = _setup()
     H, W = gt.shape[1:]
-    w = wr.weight_pattern("mask", H, W).to(_dev())
+    w = wr.weight_pattern("mask", H, W).to(gpu())
     kw = dict(gt_depth=gtd, lambda_depth=LAMBDA_D) if with_depth else {}
-    m = _model(raw)
-    before = _state(m)
+    m = training_model(raw)
+    before = model_state(m)
     g, terms = trainer.pose_gradient(m, cam, gt, bg, weight=w, **kw)
     out = _assembled_step(m, cam, gt, bg, w, gtd if with_depth else None, camera_grads=True)
     ref = cam.pose_gradient(out[9], out[10], out[11])
     assert np.array_equal(np.asarray(g), np.asarray(ref)) and np.abs(np.asarray(g)).max() > 0
     g0, _t = trainer.pose_gradient(m, cam, gt, bg, **kw)
     assert not np.array_equal(np.asarray(g), np.asarray(g0))
-    _assert_same_state(before, _state(m))
+    assert_same_state(before, model_state(m))
     # the joint map + pose step under the same weight: the terms and the visible set of training_step_fused(weight=...), the same camera gradient
     # (to 1e-5 of max-abs, the bar tests/test_depth_camera_gpu.py holds the two backward instantiations to)
-    a, b = _model(raw), _model(raw)
+    a, b = training_model(raw), training_model(raw)
     t_a, v_a, g_joint = trainer.training_step_with_pose(a, cam, gt, bg, pose_lr=0.0, weight=w, **kw)
     t_b, v_b = trainer.training_step_fused(b, cam, gt, bg, weight=w, **kw)
     assert torch.equal(t_a, t_b) and torch.equal(v_a, v_b)
     assert float(np.abs(np.asarray(g_joint) - np.asarray(g)).max()) <= 1e-5 * float(np.abs(np.asarray(g)).max())
-    assert not torch.equal(_state(a)["xyz"], before["xyz"])
+    assert not torch.equal(model_state(a)["xyz"], before["xyz"])
 
 
 # ---------------------------------------------------------------------------------------------------- 12. the C++ host
@@ -390,41 +356,29 @@ def test_pose_gradient_with_a_weight_is_the_chain_fed_backward(with_depth):
 def test_fused_weighted_cpp_host(tmp_path, with_depth):
     """gslic::FusedStep::step / pose_gradient with a weight issue the C-ABI calls of training_step_fused / pose_gradient(weight=...): terms, the weight
     sum, the pose gradient and the parameters after three steps are bit-identical to the Python host's.  The driver is built when missing."""
-    import importlib.util
     from gaussian_lic_amd import loss, trainer
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussian-lic_amd", "shim", "build_shim.py")
-    spec = importlib.util.spec_from_file_location("build_shim", path)
-    build_shim = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build_shim)
-    exe = build_shim.build_fused_check("fused_weighted")
-    assert os.path.exists(exe)
+    exe = fio.build("fused_weighted")
     P, W, H, deg, iters = 5000, 160, 120, 3, 3
     raw, cam, gt, gtd, bg = _setup(P, W, H, deg, 44)
-    w = wr.weight_pattern("uniform", H, W).to(_dev()) * wr.weight_pattern("frame", H, W).to(_dev())
+    w = wr.weight_pattern("uniform", H, W).to(gpu()) * wr.weight_pattern("frame", H, W).to(gpu())
     d = str(tmp_path)
-    wf = lambda name, t: np.ascontiguousarray(t, np.float32).tofile(os.path.join(d, name + ".f32"))
-    for k, n in (("xyz", "xyz"), ("scaling", "scaling"), ("rotation", "rotation"), ("opacity", "opacity"), ("features_dc", "dc"), ("features_rest", "rest")):
-        wf(n, raw[k].numpy())
-    wf("view", cam.world_view_transform); wf("proj", cam.full_proj_transform); wf("campos", cam.camera_center)
-    wf("gt", gt.cpu().numpy()); wf("gt_depth", gtd.cpu().numpy()); wf("weight", w.cpu().numpy())
-    wf("scalars", np.array([cam.tanfovx, cam.tanfovy, cam.limx_neg, cam.limx_pos, cam.limy_neg, cam.limy_pos], np.float32))
+    fio.write_inputs(d, raw, cam, gt=gt, gt_depth=gtd, weight=w)
     lam_d = LAMBDA_D if with_depth else 0.0
-    r = subprocess.run([exe, d, str(P), str(W), str(H), str(deg), str(iters), repr(lam_d)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = fio.run(exe, d, str(P), str(W), str(H), str(deg), str(iters), repr(lam_d))
     kw = dict(gt_depth=gtd, lambda_depth=LAMBDA_D) if with_depth else {}
-    model = _model(raw)
+    model = training_model(raw)
     fl = loss.FusedLoss(LAM)
     g, _t = trainer.pose_gradient(model, cam, gt, bg, fused_loss=fl, weight=w, **kw)
     for _ in range(iters):
         terms, _vis = trainer.training_step_fused(model, cam, gt, bg, fused_loss=fl, weight=w, **kw)
-    rd = lambda name, shape: np.fromfile(os.path.join(d, f"out_{name}.f32"), np.float32).reshape(shape)
+    rd = lambda name, shape: fio.read(d, name + ".f32", np.float32).numpy().reshape(shape)
     np.testing.assert_array_equal(rd("terms", (3 if with_depth else 2,)), terms.cpu().numpy())
     np.testing.assert_array_equal(rd("weight_sum", (1,)), fl.weight_sum.cpu().numpy())
     for name, t in [("xyz", model.xyz), ("scaling", model.scaling), ("rotation", model.rotation), ("opacity", model.opacity), ("dc", model.features_dc),
                     ("rest", model.features_rest)]:
         np.testing.assert_array_equal(rd(name, tuple(t.shape)), t.detach().cpu().numpy(), err_msg=name)
     # the C++ one-node autograd loss (loss_utils_fused.h) on the last image against the Python one
-    x = torch.from_numpy(rd("image", (3, H, W))).to(_dev()).requires_grad_(True)
+    x = torch.from_numpy(rd("image", (3, H, W))).to(gpu()).requires_grad_(True)
     one = loss.l1_ssim_loss(x, gt, LAM, weight=w)
     (2.0 * one).backward()
     np.testing.assert_array_equal(rd("onenode", (1,)), one.detach().reshape(1).cpu().numpy())

@@ -61,6 +61,7 @@ EXPORTS = [
     "gslic_morton_order", "gslic_permute_rows", "gslic_permute_rows_staging_bytes",
     "gslic_rasterize_backward_adam_stats", "gslic_rasterize_backward_depth_adam_stats", "gslic_gradient_stats_accumulate",
     "gslic_lidar_zbuffer_add", "gslic_lidar_zbuffer_resolve",
+    "gslic_depth_loss_weighted_partials_count", "gslic_depth_loss_weighted_forward_backward",
 ]
 
 _lib = None
@@ -97,6 +98,9 @@ def lib():
     L.gslic_depth_l1_loss_partials_count.restype = ctypes.c_int64
     L.gslic_depth_l1_loss_partials_count.argtypes = [i32, i32]
     L.gslic_depth_l1_loss_forward_backward.argtypes = [i32, i32, f32, vp, vp, vp, vp, vp, vp]
+    L.gslic_depth_loss_weighted_partials_count.restype = ctypes.c_int64
+    L.gslic_depth_loss_weighted_partials_count.argtypes = [i32, i32]
+    L.gslic_depth_loss_weighted_forward_backward.argtypes = [i32, i32, f32, f32] + [vp] * 6 + [vp]   # H, W, lambda_depth, delta, depth, gt_depth, weight, partials, terms, dL_ddepth, stream
     # the rasterize entry points, from the pieces their signatures share (include/gslic_hip.h)
     prm, counts, adam = ctypes.POINTER(RasterParams), [ctypes.POINTER(i32), ctypes.POINTER(i32)], ctypes.POINTER(AdamFused)
     inputs = [vp] * 12                                 # background ... cam_pos (the backward: radii in place of opacities)

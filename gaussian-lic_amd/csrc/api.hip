@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <mutex>
 
 #include <stdarg.h>
@@ -280,6 +281,8 @@ int loss_weighted_forward_backward(int, int, int, float, float, float, const flo
 int64_t loss_weighted_partials_count(int, int, int);
 int depth_loss_forward_backward(int, int, float, const float*, const float*, float*, float*, float*, hipStream_t);
 int64_t depth_loss_partials_count(int, int);
+int depth_loss_weighted_forward_backward(int, int, float, float, const float*, const float*, const float*, float*, float*, float*, hipStream_t);
+int64_t depth_loss_weighted_partials_count(int, int);
 int extend_select(int, const float*, const float*, const float*, const float*, float, float, float, float, int, int, const float*,
                   gslic_alloc_fn, void*, uint32_t**, uint32_t**, int32_t*, hipStream_t);
 int extend_emit(int, const uint32_t*, const uint32_t*, const float*, const float*, const float*, float, float, int, float*, float*, float*,
@@ -1313,6 +1316,34 @@ int gslic_depth_l1_loss_forward_backward(int32_t H, int32_t W, float lambda_dept
     if (H <= 0 || W <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "depth loss: empty image");
     if (!depth || !gt_depth || !partials || !term || !dL_ddepth) return set_error(GSLIC_ERR_INVALID_ARG, "depth loss: NULL pointer");
     return depth_loss_forward_backward(H, W, lambda_depth, depth, gt_depth, partials, term, dL_ddepth, (hipStream_t)stream);
+}
+
+int64_t gslic_depth_loss_weighted_partials_count(int32_t H, int32_t W) { return (H <= 0 || W <= 0) ? 8 : depth_loss_weighted_partials_count(H, W); }
+
+int gslic_depth_loss_weighted_forward_backward(int32_t H, int32_t W, float lambda_depth, float delta, const float* depth, const float* gt_depth,
+                                               const float* weight, float* partials, float* terms, float* dL_ddepth, void* stream)
+{
+    const char* fn = "weighted depth loss";
+    if (H <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: H = %d is not positive", fn, H);
+    if (W <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: W = %d is not positive", fn, W);
+    const struct { const void* p; const char* name; } ptrs[5] = {{depth, "depth"}, {gt_depth, "gt_depth"}, {partials, "partials"}, {terms, "terms"},
+                                                                 {dL_ddepth, "dL_ddepth"}};
+    for (const auto& a : ptrs)
+        if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, a.name);
+    if (!(delta >= 0.0f) || std::isinf(delta)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: delta = %g must be finite and >= 0", fn, (double)delta);
+    if (std::isnan(lambda_depth)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: lambda_depth is NaN", fn);
+    const size_t img = (size_t)H * (size_t)W * sizeof(float);
+    auto overlap = [](const void* x, size_t xn, const void* y, size_t yn) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(x), b = reinterpret_cast<uintptr_t>(y);
+        return a < b + yn && b < a + xn;
+    };
+    const struct { const void* p; const char* name; } in[3] = {{depth, "depth"}, {gt_depth, "gt_depth"}, {weight, "weight"}};
+    for (const auto& a : in) {
+        if (!a.p) continue;   // (weight may be NULL: every pixel weighs 1)
+        if (overlap(dL_ddepth, img, a.p, img)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: dL_ddepth overlaps %s", fn, a.name);
+        if (overlap(terms, 2 * sizeof(float), a.p, img)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: terms overlaps %s", fn, a.name);
+    }
+    return depth_loss_weighted_forward_backward(H, W, lambda_depth, delta, depth, gt_depth, weight, partials, terms, dL_ddepth, (hipStream_t)stream);
 }
 
 int gslic_knn_mean_dist2(int32_t P, const float* points, float* mean_dists, gslic_alloc_fn scratch_alloc, void* scratch_ctx,

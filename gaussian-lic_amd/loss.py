@@ -61,13 +61,57 @@ def l1_loss(network_output, gt):
     return torch.abs(network_output - gt).mean()
 
 
-def depth_l1(depth, gt_depth):
+def depth_weight(weight):
+    """A per-pixel depth weight as the weighted depth loss kernels read it: NaN, negative and +inf values are 0; NO clamp at 1 (inverse-variance
+    weights are not bounded by 1, and the loss divides by their sum)."""
+    return torch.where((weight > 0) & (weight < float("inf")), weight, torch.zeros_like(weight))
+
+
+def depth_l1(depth, gt_depth, weight=None, huber=0.0):
     """Masked L1 for LiDAR depth supervision: mean |depth - gt_depth| over the pixels where gt_depth > 0 (a sparse projected depth image,
-    Camera.project_depth); 0 when there are none (still a tensor connected to `depth`, so backward() works)."""
+    Camera.project_depth); 0 when there are none (still a tensor connected to `depth`, so backward() works).
+    weight [H,W] (no gradient to it; depth_weight's reading) and huber = delta >= 0: the rule of gslic_depth_loss_weighted_forward_backward in
+    torch ops — sum_m w rho / sum_m w over m = gt_depth > 0 and w > 0, rho the smooth-L1 of the residual with beta = delta (delta = 0: |r|);
+    0 when the weights sum to 0.  With the defaults the graph and the bits are the ones above."""
+    huber = float(huber)
+    if not (0.0 <= huber < float("inf")):
+        raise ValueError(f"depth_l1: huber = {huber} must be finite and >= 0")
+    if weight is None and huber == 0.0:
+        mask = gt_depth > 0
+        n = mask.sum()
+        diff = torch.where(mask, (depth - gt_depth).abs(), torch.zeros_like(depth))
+        return diff.sum() / n.clamp_min(1).to(depth.dtype)
     mask = gt_depth > 0
-    n = mask.sum()
-    diff = torch.where(mask, (depth - gt_depth).abs(), torch.zeros_like(depth))
-    return diff.sum() / n.clamp_min(1).to(depth.dtype)
+    if weight is None:
+        w = mask.to(depth.dtype)
+    else:
+        w = depth_weight(weight.detach().to(depth.dtype))
+        mask = mask & (w > 0)
+        w = torch.where(mask, w, torch.zeros_like(w))
+    r = torch.where(mask, depth - gt_depth, torch.zeros_like(depth))   # (an unmeasured pixel's depth, NaN included, reaches neither value nor gradient)
+    a = r.abs()
+    rho = a if huber == 0.0 else torch.where(a < huber, ((0.5 * a) * a) / huber, a - 0.5 * huber)
+    S = w.sum()
+    T = (w * rho).sum()
+    return torch.where(S > 0, T / S.clamp_min(torch.finfo(depth.dtype).tiny), torch.zeros_like(T))
+
+
+def depth_metrics(depth, gt_depth, weight=None):
+    """Depth evaluation over the measured pixels (gt_depth > 0; with weight [H,W], depth_weight's reading: the pixels of positive weight, each counted
+    by its weight), accumulated in float64: dict of device scalars mae = mean |D - d|, rmse = sqrt(mean (D - d)^2), abs_rel = mean |D - d| / d,
+    delta1 = share with max(D / d, d / D) < 1.25, n = the sum of the weights (the number of pixels without one).  All 0 when n == 0."""
+    D, d = depth.detach().double(), gt_depth.detach().double()
+    m = d > 0
+    w = m.double() if weight is None else torch.where(m, depth_weight(weight.detach().double()), torch.zeros_like(d))
+    m = w > 0
+    one = torch.ones_like(d)
+    D, d = torch.where(m, D, one), torch.where(m, d, one)
+    e = (D - d).abs()
+    S = w.sum()
+    n = S.clamp_min(torch.finfo(torch.float64).tiny)
+    ratio = torch.maximum(D / d, d / D)
+    ok = ((ratio < 1.25) & (D > 0)).double()   # (a NaN or non-positive rendered depth fails)
+    return dict(mae=(w * e).sum() / n, rmse=((w * e * e).sum() / n).sqrt(), abs_rel=(w * e / d).sum() / n, delta1=(w * ok).sum() / n, n=S)
 
 
 def clamp_weight(weight):
@@ -118,19 +162,28 @@ def ssim(img1, img2, window_size=11, size_average=True):
     return ssim_map.mean() if size_average else ssim_map.mean(1).mean(1).mean(1)
 
 
-def evaluate_visual_quality(model, cameras, gt_images, bg, fused=True, weights=None):
+def evaluate_visual_quality(model, cameras, gt_images, bg, fused=True, weights=None, gt_depths=None, depth_weights=None):
     """PSNR / SSIM over a set of views — the metric part of evaluateVisualQuality (gaussian.cpp:751-789): render, clamp to [0,1],
     psnr + SSIM per image, averaged over the views.  fused=True evaluates the SSIM map with the fused-SSIM kernel
     (gslic_fusedssim_forward, train = 0: the same 11-tap sigma-1.5 window with zero padding as loss_utils.h:41-128, separable, one
     launch) instead of five LibTorch conv2d calls; fused=False is the reference's formulation verbatim.  Returns device scalars
     (mean PSNR, mean SSIM).  (LPIPS needs the TorchScript AlexNet blob the reference does not ship.)
     weights: one [H,W] weight image per view (or None per view): PSNR from the weighted MSE and SSIM as the weighted mean of the SSIM map
-    (window statistics over all pixels, as in the weighted training loss), in plain torch on top of the same map."""
+    (window statistics over all pixels, as in the weighted training loss), in plain torch on top of the same map.
+    gt_depths: one [H,W] depth target per view (or None per view; depth_weights likewise, optional): the views that have one are rendered with
+    their depth and the result gains a third element, the dict of depth_metrics averaged over those views (float64 device scalars).  Without
+    gt_depths the result is the pair it always was."""
     from .rasterizer import render
-    ps, ss = [], []
+    ps, ss, dm = [], [], []
     with torch.no_grad():
         for i, (cam, gt) in enumerate(zip(cameras, gt_images)):
-            img = torch.clamp(render(cam, model, bg)[0], 0.0, 1.0)
+            gtd = None if gt_depths is None else gt_depths[i]
+            if gtd is None:
+                img = torch.clamp(render(cam, model, bg)[0], 0.0, 1.0)
+            else:
+                out = render(cam, model, bg, return_depth=True)
+                img = torch.clamp(out[0], 0.0, 1.0)
+                dm.append(depth_metrics(out[5], gtd, None if depth_weights is None else depth_weights[i]))
             gt = torch.clamp(gt, 0.0, 1.0)                      # gaussian.cpp:759
             w = None if weights is None else weights[i]
             ps.append(psnr(img, gt, w))
@@ -143,7 +196,13 @@ def evaluate_visual_quality(model, cameras, gt_images, bg, fused=True, weights=N
                 ss.append(fusedssim(C1, C2, img.unsqueeze(0).contiguous(), gt.unsqueeze(0).contiguous(), False)[0].mean())
             else:
                 ss.append(ssim(img.unsqueeze(0), gt.unsqueeze(0)))
-    return torch.stack(ps).mean(), torch.stack(ss).mean()
+    if gt_depths is None:
+        return torch.stack(ps).mean(), torch.stack(ss).mean()
+    if depth_weights is not None and not dm:
+        raise ValueError("evaluate_visual_quality: depth_weights without a depth target in gt_depths")
+    keys = ("mae", "rmse", "abs_rel", "delta1", "n")
+    depth_result = {k: torch.stack([m[k] for m in dm]).mean() for k in keys} if dm else {}
+    return torch.stack(ps).mean(), torch.stack(ss).mean(), depth_result
 
 
 class _L1SsimLoss(torch.autograd.Function):
@@ -187,6 +246,7 @@ class FusedLoss:
         self._dshape, self._dbuf = None, None
         self._terms = None
         self._wshape, self._wbuf = None, None
+        self._dwshape, self._dwbuf = None, None
 
     def _terms_buf(self, device):
         if self._terms is None or self._terms.device != device:
@@ -212,17 +272,46 @@ class FusedLoss:
             self._dshape = tuple(depth.shape)
         return self._dbuf
 
-    def depth_forward_backward(self, depth, gt_depth, lambda_depth):
+    def depth_forward_backward(self, depth, gt_depth, lambda_depth, weight=None, huber=0.0):
         """depth, gt_depth: [H,W] (gt_depth 0 = no measurement).  Returns (dL/ddepth of lambda_depth * L_d, term) with term = device [1] view of
-        L_d = depth_l1(depth, gt_depth) — gslic_depth_l1_loss_forward_backward, two launches; dL/ddepth equals autograd's bit for bit."""
+        L_d = depth_l1(depth, gt_depth) — gslic_depth_l1_loss_forward_backward, two launches; dL/ddepth equals autograd's bit for bit.
+        weight [H,W] float32 (NaN, negative and +inf read as 0; NOT clamped at 1) and / or huber = delta > 0 (the smooth-L1 threshold, in the unit
+        of depth): L_d = depth_l1(depth, gt_depth, weight, huber) and its gradient by gslic_depth_loss_weighted_forward_backward — two launches and
+        a 4-byte copy into `terms3`; `depth_weight_sum` is then S, the sum of the weights over the measured pixels.  S == 0: L_d 0 and a zero
+        gradient.  weight=None with huber == 0 is the call above, launch for launch."""
         depth, gt_depth = depth.contiguous(), gt_depth.contiguous()
         H, W = depth.shape
         assert tuple(gt_depth.shape) == (H, W), "gt_depth must have the depth image's shape [H,W]"
-        dL, partials, term = self._depth_scratch(depth)
+        huber = float(huber)
         p = _lib.ptr
+        if weight is not None or huber != 0.0:
+            if weight is not None:
+                if tuple(weight.shape) != (H, W) or weight.dtype != torch.float32 or weight.device != depth.device:
+                    raise ValueError(f"depth weight must be a float32 [H,W] = [{H},{W}] tensor on the depth image's device")
+                weight = weight.contiguous()
+            dL, _partials, term = self._depth_scratch(depth)
+            wpartials, wterms = self._depth_weighted_scratch(depth)
+            _lib.check(_lib.lib().gslic_depth_loss_weighted_forward_backward(H, W, float(lambda_depth), huber, p(depth), p(gt_depth), p(weight),
+                                                                             p(wpartials), p(wterms), p(dL), _lib.current_stream_ptr()))
+            term.copy_(wterms[:1])   # terms3 stays [L1, SSIM, L_d]; S is `depth_weight_sum`
+            return dL, term
+        dL, partials, term = self._depth_scratch(depth)
         _lib.check(_lib.lib().gslic_depth_l1_loss_forward_backward(H, W, float(lambda_depth), p(depth), p(gt_depth), p(partials), p(term), p(dL),
                                                                    _lib.current_stream_ptr()))
         return dL, term
+
+    @property
+    def depth_weight_sum(self):
+        """S = sum of the depth weights over the measured pixels of the last depth_forward_backward(weight= / huber=): a device [1] view; None
+        before the first such call."""
+        return None if self._dwbuf is None else self._dwbuf[1][1:2]
+
+    def _depth_weighted_scratch(self, depth):
+        if self._dwshape != tuple(depth.shape) or self._dwbuf[0].device != depth.device:
+            n = int(_lib.lib().gslic_depth_loss_weighted_partials_count(depth.shape[0], depth.shape[1]))
+            self._dwbuf = [torch.empty(n, device=depth.device), torch.zeros(2, device=depth.device)]
+            self._dwshape = tuple(depth.shape)
+        return self._dwbuf
 
     @property
     def weight_sum(self):

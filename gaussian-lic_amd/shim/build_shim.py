@@ -109,6 +109,7 @@ FUSED_CHECKS = {name: (os.path.join(HERE, name + "_check.cpp"), os.path.join(PKG
     "fused_contribution",     # contribution statistics, carried through prune
     "fused_densify",          # the error score and densify between steps
     "fused_weighted",         # the step and the pose gradient under a per-pixel weight image
+    "fused_depth_weighted",   # ... under a per-pixel depth weight image and a Huber threshold on the depth loss
     "fused_resort",           # resort and the set_resort_fraction rule, through extend and prune
     "fused_gradient_stats",   # gradient statistics, carried through densify, prune and resort
     "fused_free_space",       # free-space statistics, carried through prune and resort

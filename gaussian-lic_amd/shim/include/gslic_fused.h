@@ -20,6 +20,8 @@
 //   float loss = fs.loss_value(terms, lambda_depth);
 // issues gslic_rasterize_forward_depth, the two loss calls, gslic_depth_l1_loss_forward_backward and gslic_rasterize_backward_depth_adam — the
 // calls of the Python host's training_step_fused(gt_depth=, lambda_depth=), so the two agree bit for bit (tests/test_depth_fused_gpu.py).
+// With a depth weight image [H,W] and / or a Huber threshold (fs.step(cam, gt, gt_depth, lambda_depth, weight, depth_weight, depth_huber)) the depth
+// loss call is gslic_depth_loss_weighted_forward_backward, as training_step_fused(depth_weight=, depth_huber=)'s (tests/test_depth_weighted_gpu.py).
 //
 // Per-row statistics (ContributionStats, GradientStats) follow the map's rows the way the Python host's _RowStatistics do: each object lists its
 // arrays ONCE (rows(): tensor, scalar type, row width in dwords, created only when asked for), and the four row changes — prune, extend, densify,
@@ -509,18 +511,26 @@ public:
     int64_t capacity() const { return buf_[0].defined() ? buf_[0].size(0) : prm_[0].size(0); }
 
     // One optimisation step on one view.  Returns the device tensor [mean |image - gt|, mean ssim]; nothing synchronises.
-    torch::Tensor step(const FusedCamera& cam, const torch::Tensor& gt_image) { return step_body(cam, gt_image, nullptr, 0.0f, nullptr); }
+    torch::Tensor step(const FusedCamera& cam, const torch::Tensor& gt_image) { return step_body(cam, gt_image, nullptr, 0.0f, nullptr, DepthLossOptions{}); }
 
     // One optimisation step on one view with LiDAR depth supervision.  Returns the device tensor [mean |image - gt|, mean ssim, L_d]; nothing
     // synchronises.  An undefined gt_depth or lambda_depth == 0 is the colour-only step above (two terms).
     // weight (optional, fp32 [H,W]; a mask is the 0/1 case): the colour loss becomes the weighted one — gslic_l1_ssim_loss_weighted_forward_backward,
     // the calls of the Python host's training_step_fused(weight=...); terms[0:2] are the weighted means and weight_sum() the sum of the weights.  An
     // undefined weight is the unweighted step, the same calls as ever.
+    // depth_weight (optional, fp32 [H,W]) and depth_huber (the smooth-L1 threshold, 0 = L1): the depth loss becomes the weighted one —
+    // gslic_depth_loss_weighted_forward_backward, the call of the Python host's training_step_fused(depth_weight=, depth_huber=): NaN, negative and
+    // +inf weights read as 0, NO clamp at 1; depth_weight_sum() is the sum of the weights over the measured pixels.  An undefined depth_weight with
+    // depth_huber == 0 is the unweighted depth loss, the same calls as ever.  Either of them without a depth target is an error.
     torch::Tensor step(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor& gt_depth, float lambda_depth,
-                       const torch::Tensor& weight = torch::Tensor())
+                       const torch::Tensor& weight = torch::Tensor(), const torch::Tensor& depth_weight = torch::Tensor(), float depth_huber = 0.0f)
     {
-        return step_body(cam, gt_image, gt_depth.defined() && lambda_depth != 0.0f ? &gt_depth : nullptr, lambda_depth, weight.defined() ? &weight : nullptr);
+        TORCH_CHECK(gt_depth.defined() || (!depth_weight.defined() && depth_huber == 0.0f), "depth_weight / depth_huber given without gt_depth");
+        const DepthLossOptions dlo{depth_weight.defined() ? &depth_weight : nullptr, depth_huber};
+        return step_body(cam, gt_image, gt_depth.defined() && lambda_depth != 0.0f ? &gt_depth : nullptr, lambda_depth, weight.defined() ? &weight : nullptr, dlo);
     }
+    // S = the sum of the depth weights over the measured pixels of the last weighted / Huber depth loss: a device [1] view (undefined before the first)
+    torch::Tensor depth_weight_sum() const { return dwterms_.defined() ? dwterms_.slice(0, 1, 2) : torch::Tensor(); }
     // S = the sum of the (clamped) weights of the last weighted step / pose gradient: a device [1] view (undefined before the first)
     torch::Tensor weight_sum() const { return wterms_.defined() ? wterms_.slice(0, 2, 3) : torch::Tensor(); }
 
@@ -529,17 +539,20 @@ public:
     // gslic_rasterize_backward_camera (the map is NOT updated), then the chain of gaussian-lic_amd/camera.py:Camera.pose_gradient:
     //   G = dL/dV + Proj^T dL/d(Proj V) (top three rows; Proj = (Proj V) V^-1),  G_R = G[:, :3] - t g_c^T,  G_t = G[:, 3] - R g_c,
     //   dL/drho = G_t,  dL/dphi = vee(M - M^T) + t x G_t,  M = G_R R^T.          Returns {d/drho[3], d/dphi[3]}; synchronises (35 floats to the host).
-    std::array<double, 6> pose_gradient(const FusedCamera& cam, const torch::Tensor& gt_image) { return pose_gradient_body(cam, gt_image, nullptr, 0.0f, nullptr, nullptr); }
+    std::array<double, 6> pose_gradient(const FusedCamera& cam, const torch::Tensor& gt_image) { return pose_gradient_body(cam, gt_image, nullptr, 0.0f, nullptr, nullptr, DepthLossOptions{}); }
     // The same gradient under LiDAR depth supervision: loss = (1 - lambda) L1 + lambda (1 - SSIM) + lambda_depth L_d.  gslic_rasterize_forward_depth, the
     // colour and depth loss calls of step(cam, gt_image, gt_depth, lambda_depth), gslic_rasterize_backward_depth_camera, the same chain — the calls
     // gaussian-lic_amd/trainer.py:pose_gradient(gt_depth=...) issues.  terms_out (optional): the device tensor [mean L1, mean SSIM, L_d].  An undefined
     // gt_depth or lambda_depth == 0 is the colour-only gradient above.  weight (optional, fp32 [H,W]): the weighted colour loss, as step()'s.
+    // depth_weight / depth_huber: the weighted / Huber depth loss, as step()'s.
     std::array<double, 6> pose_gradient(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor& gt_depth, float lambda_depth,
-                                        torch::Tensor* terms_out = nullptr, const torch::Tensor& weight = torch::Tensor())
+                                        torch::Tensor* terms_out = nullptr, const torch::Tensor& weight = torch::Tensor(),
+                                        const torch::Tensor& depth_weight = torch::Tensor(), float depth_huber = 0.0f)
     {
+        TORCH_CHECK(gt_depth.defined() || (!depth_weight.defined() && depth_huber == 0.0f), "depth_weight / depth_huber given without gt_depth");
         const torch::Tensor* w = weight.defined() ? &weight : nullptr;
-        if (!gt_depth.defined() || lambda_depth == 0.0f) return w ? pose_gradient_body(cam, gt_image, nullptr, 0.0f, terms_out, w) : pose_gradient(cam, gt_image);
-        return pose_gradient_body(cam, gt_image, &gt_depth, lambda_depth, terms_out, w);
+        if (!gt_depth.defined() || lambda_depth == 0.0f) return w ? pose_gradient_body(cam, gt_image, nullptr, 0.0f, terms_out, w, DepthLossOptions{}) : pose_gradient(cam, gt_image);
+        return pose_gradient_body(cam, gt_image, &gt_depth, lambda_depth, terms_out, w, DepthLossOptions{depth_weight.defined() ? &depth_weight : nullptr, depth_huber});
     }
     // the chain alone, on host arrays in the element order of the kernels' inputs (float[16] with (r, c) at [4c + r])
     static std::array<double, 6> se3_pose_gradient(const float* view16, const float* fullproj16, const float* dview16, const float* dproj16, const float* dcampos3)
@@ -582,6 +595,11 @@ public:
     const torch::Tensor& exp_avg_sq(int group) const { return v_[group]; }
 
 private:
+    // what shapes the depth loss beyond its target: the per-pixel weight image (nullptr: none) and the Huber threshold (0: L1)
+    struct DepthLossOptions {
+        const torch::Tensor* weight = nullptr;
+        float huber = 0.0f;
+    };
     // the params of one view: raw = the six tensors are the RAW parameters (activated inside the kernels); no_color = transmittance only
     gslic_raster_params raster_params(const FusedCamera& cam, bool raw, bool no_color) const
     {
@@ -648,10 +666,25 @@ private:
                   "gslic_l1_ssim_loss_forward_backward");
         }
     }
-    // the depth loss of a view, forward and backward: terms[2] and dLd
+    // the depth loss of a view, forward and backward: terms[2] and dLd.  With a weight image or a Huber threshold the weighted call (its two launches,
+    // then terms[2] <- L_d; S stays in dwterms_[1]: depth_weight_sum()), otherwise the unweighted call as it always ran.
     void depth_loss(int H, int W, float lambda_depth, const torch::Tensor& depth, const torch::Tensor& gt_depth, torch::Tensor& partials, torch::Tensor& terms,
-                    torch::Tensor& dLd)
+                    torch::Tensor& dLd, const DepthLossOptions& dlo)
     {
+        if (dlo.weight || dlo.huber != 0.0f) {
+            const torch::Tensor* w = dlo.weight;
+            TORCH_CHECK(!w || (w->is_contiguous() && w->scalar_type() == torch::kFloat32 && w->dim() == 2 && w->size(0) == H && w->size(1) == W),
+                        "depth_weight must be contiguous fp32 [H,W]");
+            auto fo = prm_[0].options().requires_grad(false);
+            const int64_t n = gslic_depth_loss_weighted_partials_count(H, W);
+            if (!dwpartials_.defined() || dwpartials_.size(0) != n) dwpartials_ = torch::empty({n}, fo);
+            if (!dwterms_.defined()) dwterms_ = torch::zeros({2}, fo);
+            check(gslic_depth_loss_weighted_forward_backward(H, W, lambda_depth, dlo.huber, f(depth), f(gt_depth), w ? f(*w) : nullptr,
+                                                             dwpartials_.data_ptr<float>(), dwterms_.data_ptr<float>(), dLd.data_ptr<float>(), current_stream()),
+                  "gslic_depth_loss_weighted_forward_backward");
+            terms.slice(0, 2, 3).copy_(dwterms_.slice(0, 0, 1));
+            return;
+        }
         check(gslic_depth_l1_loss_forward_backward(H, W, lambda_depth, f(depth), f(gt_depth), partials.data_ptr<float>(), terms.data_ptr<float>() + 2,
                                                    dLd.data_ptr<float>(), current_stream()),
               "gslic_depth_l1_loss_forward_backward");
@@ -733,7 +766,7 @@ private:
 
     // the step: forward, loss, depth loss, backward.  gt_depth != nullptr: under depth supervision
     torch::Tensor step_body(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor* gt_depth, float lambda_depth,
-                            const torch::Tensor* weight)
+                            const torch::Tensor* weight, const DepthLossOptions& dlo)
     {
         torch::NoGradGuard ng;
         const bool depth = gt_depth != nullptr;
@@ -750,7 +783,7 @@ private:
         int32_t R = 0, B = 0;
         forward(rp, cam, f(prm_[3]), f(prm_[4]), f(prm_[5]), image_, final_T_, depth ? &depth_ : nullptr, radii_, R, B);
         colour_loss(H, W, image_, gt_image, weight, dm_, partials_, terms, dL_dimage_);
-        if (depth) depth_loss(H, W, lambda_depth, depth_, *gt_depth, depth_partials_, terms, dL_ddepth_);
+        if (depth) depth_loss(H, W, lambda_depth, depth_, *gt_depth, depth_partials_, terms, dL_ddepth_, dlo);
         backward_adam(rp, cam, R, B, depth);
         return terms;
     }
@@ -758,7 +791,7 @@ private:
     // the pose gradient: forward, loss, depth loss, camera backward, the chain on the host.  gt_depth != nullptr: under depth supervision.  (The
     // colour-only path runs the unweighted loss as gslic_l1_ssim_loss_forward + _backward, every other path as the fused pair: both as they were.)
     std::array<double, 6> pose_gradient_body(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor* gt_depth, float lambda_depth,
-                                             torch::Tensor* terms_out, const torch::Tensor* weight)
+                                             torch::Tensor* terms_out, const torch::Tensor* weight, const DepthLossOptions& dlo)
     {
         torch::NoGradGuard ng;
         const bool depth = gt_depth != nullptr;
@@ -777,7 +810,7 @@ private:
         int32_t R = 0, B = 0;
         forward(rp, cam, f(prm_[3]), f(prm_[4]), f(prm_[5]), image, final_T, depth ? &zimg : nullptr, radii, R, B);
         colour_loss(H, W, image, gt_image, weight, dm, partials, terms, dL, /*two_calls=*/!depth);
-        if (depth) depth_loss(H, W, lambda_depth, zimg, *gt_depth, dpartials, terms, dLd);
+        if (depth) depth_loss(H, W, lambda_depth, zimg, *gt_depth, dpartials, terms, dLd, dlo);
         backward_camera(rp, cam, R, B, radii, dL, dLd, g, camg.data_ptr<float>());
         if (terms_out) *terms_out = terms;
         torch::Tensor hc = camg.to(torch::kCPU), hv = cam.world_view_transform.to(torch::kCPU).contiguous(), hp = cam.full_proj_transform.to(torch::kCPU).contiguous();
@@ -919,6 +952,7 @@ private:
     torch::Tensor bg_, image_, final_T_, radii_, dm_[3], dL_dimage_, partials_, tie_;
     torch::Tensor depth_, dL_ddepth_, depth_partials_, xyz_grad_;   // depth steps
     torch::Tensor wpartials_, wterms_;                              // weighted loss: scratch and {L1_w, SSIM_w, S}
+    torch::Tensor dwpartials_, dwterms_;                            // weighted / Huber depth loss: scratch and {L_d, S}
     std::optional<double> resort_fraction_;                         // the re-sort rule (off by default)
     int64_t sorted_P_ = 0, n_resorts_ = 0;                          // rows [0, sorted_P_) are in Morton order; resort() calls so far
     torch::Tensor last_perm_;                                       // the last resort()'s permutation

@@ -571,6 +571,19 @@ def free_space_bound(depth, margin_abs, margin_rel):
     return torch.where(d > 0, d - (ma + mr * d), torch.zeros((), dtype=torch.float32, device=d.device))
 
 
+def range_weight(depth, sigma_abs, sigma_rel):
+    """A relative-error weight image for the depth loss (depth_weight= of the training steps), from a depth image such as LidarDepth.resolve's:
+    float32 [H, W], sigma_abs / (sigma_abs + sigma_rel * d) where d > 0 and 0 elsewhere (d <= 0, NaN) — one product, one add, one division, each a
+    float32 torch operation in that order.  1 at the sensor, falling with range as a range noise sigma_abs + sigma_rel * d grows: it keeps the far
+    returns of a sweep from outvoting the near structure.  sigma_abs > 0, sigma_rel >= 0.  Plain torch; which weight to use is the host's policy."""
+    if not (float(sigma_abs) > 0.0 and float(sigma_rel) >= 0.0 and float(sigma_abs) < float("inf") and float(sigma_rel) < float("inf")):   # (a NaN fails)
+        raise ValueError(f"range_weight: sigma_abs must be > 0 and sigma_rel >= 0, both finite, got {sigma_abs!r} and {sigma_rel!r}")
+    d = torch.as_tensor(depth).detach().to(torch.float32)
+    sa = torch.tensor(float(sigma_abs), dtype=torch.float32, device=d.device)
+    sr = torch.tensor(float(sigma_rel), dtype=torch.float32, device=d.device)
+    return torch.where(d > 0, sa / (sa + sr * d), torch.zeros((), dtype=torch.float32, device=d.device))
+
+
 class LidarDepth:
     """The per-pixel LiDAR range image of one camera, built by the library (gslic_lidar_zbuffer_add / _resolve, include/gslic_hip.h): it owns the
     z-buffer of width * height 64-bit keys {float bits of camera z, point index} on `device`.
@@ -1254,14 +1267,25 @@ class _RawRaster:
                             sample, self.lambda_erank, **modes)
 
 
-def _fused_losses(fl, image, gt_image, depth, gt_depth, lambda_depth, weight=None):
-    """The colour loss kernels (weight [H,W]: the weighted ones) and, for a depth image, the depth loss kernels: (dL/dimage, dL/ddepth or None, terms)."""
+def _fused_losses(fl, image, gt_image, depth, gt_depth, lambda_depth, weight=None, depth_weight=None, depth_huber=0.0):
+    """The colour loss kernels (weight [H,W]: the weighted ones) and, for a depth image, the depth loss kernels (depth_weight [H,W] / depth_huber:
+    the weighted ones): (dL/dimage, dL/ddepth or None, terms)."""
     if depth is None:
         dL_dimage, terms = fl.forward_backward(image, gt_image, weight)
         return dL_dimage, None, terms
     dL_dimage, _ = fl.forward_backward(image, gt_image, weight)
-    dL_ddepth, _ = fl.depth_forward_backward(depth, gt_depth, lambda_depth)
+    dL_ddepth, _ = fl.depth_forward_backward(depth, gt_depth, lambda_depth, depth_weight, depth_huber)
     return dL_dimage, dL_ddepth, fl.terms3
+
+
+def _use_depth(who, gt_depth, lambda_depth, depth_weight, depth_huber):
+    """Whether a step runs depth supervision, and the checks every step shares: a depth weight or Huber threshold needs a depth target, and the
+    threshold is finite and >= 0.  (gt_depth with lambda_depth == 0 is the colour-only step; the two arguments are then not used.)"""
+    if not (0.0 <= float(depth_huber) < float("inf")):   # (a NaN fails)
+        raise ValueError(f"{who}: depth_huber = {depth_huber!r} must be finite and >= 0")
+    if gt_depth is None and (depth_weight is not None or float(depth_huber) != 0.0):
+        raise ValueError(f"{who}: depth_weight / depth_huber given without gt_depth (they shape the depth term of the loss: pass gt_depth and lambda_depth)")
+    return gt_depth is not None and lambda_depth != 0.0
 
 
 def _grad_slab(model):
@@ -1361,7 +1385,7 @@ def allreduce_gradients(grads, visible):
 
 
 def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_step=True, raw_render=None, one_node_loss=False, gt_depth=None,
-                  lambda_depth=0.0, weight=None, grad_stats=None):
+                  lambda_depth=0.0, weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0):
     """One iteration of optimize()'s loop (gaussian.cpp:674-716) the way the reference's host writes it: render -> 0.8*L1 + 0.2*(1-SSIM) ->
     loss.backward() -> sparse Adam, on LibTorch autograd.  Returns (loss tensor, visible mask).
     raw_render: passed to render() — None = its default (the drop-in renderer: activations inside the kernels), False = renderer.cpp as written
@@ -1373,8 +1397,11 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
     weight [H,W] (not in the reference; a mask is the 0/1 case, clamped to [0,1]): the colour terms become the weighted means
     (w |d|).sum() / (3 S) and (FusedSSIMMap w).sum() / (3 S), S = w.sum() (both 0 when S == 0), from the existing operators; None = the plain means.
     grad_stats (a GradientStats of this model; single GPU): this view's dL_dmeans2D — screenspace_points.grad, or on the raw path what its backward
-    node writes out — and radii are added to it by one small kernel (GradientStats.accumulate_from); the step itself is unchanged."""
-    use_depth = gt_depth is not None and lambda_depth != 0.0
+    node writes out — and radii are added to it by one small kernel (GradientStats.accumulate_from); the step itself is unchanged.
+    depth_weight [H,W] / depth_huber (with gt_depth; not in the reference): the depth term becomes depth_l1(depth, gt_depth, depth_weight, depth_huber),
+    the per-pixel weighted mean (NaN, negative and +inf weights read as 0, no clamp at 1) of the smooth-L1 of the residual with threshold depth_huber
+    (0 = L1); None and 0 are exactly the unweighted term."""
+    use_depth = _use_depth("training_step", gt_depth, lambda_depth, depth_weight, depth_huber)
     grad_stats = _grad_stats_for_step(grad_stats, model)
     m2d = {} if grad_stats is None else dict(mean2d_grad_out=grad_stats._mean2d_buffer())
     if use_depth:
@@ -1394,7 +1421,7 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
         ssim_value = loss_utils.fused_ssim(image.unsqueeze(0), gt_image.unsqueeze(0))
         loss = (1.0 - lambda_dssim) * Ll1 + lambda_dssim * (1.0 - ssim_value)
     if use_depth:
-        loss = loss + lambda_depth * loss_utils.depth_l1(depth, gt_depth)
+        loss = loss + lambda_depth * loss_utils.depth_l1(depth, gt_depth, depth_weight, depth_huber)
     loss.backward()
     if grad_stats is not None:
         grad_stats.accumulate_from(_pts.grad if _pts.grad is not None else m2d["mean2d_grad_out"], _radii)
@@ -1409,34 +1436,37 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
     return loss.detach(), visible
 
 
-def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None):
+def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None, depth_weight=None, depth_huber=0.0):
     """dL/dxi of the training loss w.r.t. a left se(3) increment of the camera pose (Camera.pose_gradient) for the current map: forward -> loss
     kernels -> gslic_rasterize_backward_camera -> the chain.  The map is not touched.  Returns (float64 [6] = (d/drho, d/dphi), terms).
     One step of pose refinement is `camera.apply_pose_increment(-lr * g); camera.to_device(dev)`.
     gt_depth [H,W] with lambda_depth != 0 (LiDAR depth supervision, as training_step_fused's): the loss gains lambda_depth * depth_l1 and the
     gradient its share — depth forward -> colour and depth loss kernels -> gslic_rasterize_backward_depth_camera -> the same chain; terms is
     then [mean L1, mean SSIM, L_d].  gt_depth=None or lambda_depth=0 is exactly the colour-only path.
-    weight [H,W]: the weighted colour loss (FusedLoss.forward_backward); it combines freely with gt_depth."""
+    weight [H,W]: the weighted colour loss (FusedLoss.forward_backward); it combines freely with gt_depth.
+    depth_weight [H,W] / depth_huber: the weighted / Huber depth term, as training_step_fused's."""
     fl = fused_loss or _default_fused_loss()
-    use_depth = gt_depth is not None and lambda_depth != 0.0
+    use_depth = _use_depth("pose_gradient", gt_depth, lambda_depth, depth_weight, depth_huber)
     with torch.no_grad():
         rr = _RawRaster(model, camera, bg, use_depth)
         image, depth, _radii = rr.forward()
-        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight)
+        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber)
         out = rr.backward(dL_dimage, dL_ddepth, camera_grads=True)
     return camera.pose_gradient(out[9], out[10], out[11]), terms
 
 
-def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None, grad_stats=None):
+def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None, grad_stats=None,
+                            depth_weight=None, depth_huber=0.0):
     """One joint map + pose iteration: forward -> loss kernels -> gslic_rasterize_backward_camera (parameter gradients AND the camera gradient in
     one pass) -> masked Adam on the map -> `camera` moved by -pose_lr * dL/dxi (left se(3) increment; 35 floats cross to the host, which is the
     step's only synchronisation).  Returns (terms, visible, dL/dxi).
     gt_depth [H,W] with lambda_depth != 0: the same step under LiDAR depth supervision (depth forward, colour and depth loss kernels,
     gslic_rasterize_backward_depth_camera); the map update equals training_step_fused(gt_depth=...)'s, terms is [mean L1, mean SSIM, L_d].
     gt_depth=None or lambda_depth=0 is exactly the colour-only step.  weight [H,W]: the weighted colour loss, as training_step_fused's.
-    grad_stats (a GradientStats of this model): the backward also writes dL_dmeans2D, which one small kernel adds to the statistics."""
+    grad_stats (a GradientStats of this model): the backward also writes dL_dmeans2D, which one small kernel adds to the statistics.
+    depth_weight [H,W] / depth_huber: the weighted / Huber depth term, as training_step_fused's."""
     fl = fused_loss or _default_fused_loss()
-    use_depth = gt_depth is not None and lambda_depth != 0.0
+    use_depth = _use_depth("training_step_with_pose", gt_depth, lambda_depth, depth_weight, depth_huber)
     grad_stats = _grad_stats_for_step(grad_stats, model)
     cam = camera
     with torch.no_grad():
@@ -1444,7 +1474,7 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
             _grad_slab(model)   # (the depth step sets the slab up ahead of its forward, the colour step behind its loss: both as they were)
         rr = _RawRaster(model, cam, bg, use_depth)
         image, depth, radii = rr.forward()
-        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight)
+        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber)
         slab = _grad_slab(model)
         if grad_stats is None:
             out = rr.backward(dL_dimage, dL_ddepth, out=slab.views, camera_grads=True)
@@ -1461,7 +1491,7 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
 
 
 def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=True, adam_in_backward=True, gt_depth=None, lambda_depth=0.0,
-                        weight=None, grad_stats=None):
+                        weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0):
     """The same iteration as training_step — identical arithmetic up to fp32 rounding — on the fused entry points
     (SURVEY.md §8f row 2): sigmoid / exp / normalize and their backward run inside preprocess / preprocess_bwd (raw_params),
     the loss and dL/dimage come from two loss kernels, and there is no autograd graph: 0 LibTorch elementwise launches per step
@@ -1477,9 +1507,18 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
     grad_stats (a GradientStats of this model; single GPU): the view is added to the densification statistics — with the Adam update inside the
     backward by that kernel itself (gslic_rasterize_backward_adam_stats / _depth_adam_stats: the gradient never leaves it), otherwise from the
     dL_dmeans2D the backward then also writes (one small kernel).  Parameters and moments are bit-identical with and without it; None is today's
-    step, launch for launch."""
+    step, launch for launch.
+    depth_weight [H,W] float32 and / or depth_huber > 0 (with gt_depth): the depth term becomes the weighted mean, over the measured pixels, of the
+    smooth-L1 of the residual with threshold depth_huber (0 = L1) — FusedLoss.depth_forward_backward(weight=, huber=), the two launches of
+    gslic_depth_loss_weighted_forward_backward in place of the two of the unweighted call, plus a 4-byte copy.  NaN, negative and +inf weights read
+    as 0 and there is NO clamp at 1 (unlike `weight`); a pixel of weight 0 is an unmeasured pixel; FusedLoss.depth_weight_sum is the sum of the
+    weights.  `weight` does not reach the depth term and depth_weight does not reach the colour terms.  depth_weight=None with depth_huber=0 is
+    exactly today's depth step, launch for launch.  Without gt_depth they raise; single GPU only, like gt_depth."""
     fl = fused_loss or _default_fused_loss()
-    use_depth = gt_depth is not None and lambda_depth != 0.0
+    if (depth_weight is not None or depth_huber) and _dist_on():
+        raise NotImplementedError("training_step_fused with depth supervision is single-GPU only: the N > 1 gradient exchange (rank1 / slab "
+                                  "all-reduce) carries no depth gradient; use training_step(gt_depth=...) or run on one GPU")
+    use_depth = _use_depth("training_step_fused", gt_depth, lambda_depth, depth_weight, depth_huber)
     grad_stats = _grad_stats_for_step(grad_stats, model)
     if use_depth and _dist_on():
         raise NotImplementedError("training_step_fused with depth supervision is single-GPU only: the N > 1 gradient exchange (rank1 / slab "
@@ -1491,7 +1530,7 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
     with torch.no_grad():
         rr = _RawRaster(model, cam, bg, use_depth)
         image, depth, radii = rr.forward()
-        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight)
+        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber)
         if do_step and adam_in_backward and not _dist_on():
             # single GPU: nothing to exchange, so the Adam update runs inside the per-Gaussian backward kernel while the
             # gradients are still in registers / LDS (bit-identical to backward + SparseGaussianAdam.step, ~2 GB less HBM traffic);
@@ -1597,10 +1636,15 @@ class GraphedStep:
 
     weight [H,W]: the step runs the weighted colour loss (training_step_fused(weight=...)).  Whether it does is baked into the step; the weight
     image lives in a static buffer like the depth target and is passed to step() the same way (None = the one that is loaded), under the same
-    checks when a step is repeated.  A step built without a weight raises when it is handed one; a step built with one raises on weight=False."""
+    checks when a step is repeated.  A step built without a weight raises when it is handed one; a step built with one raises on weight=False.
+
+    depth_weight [H,W] / depth_huber (with gt_depth and lambda_depth != 0): the step runs the weighted / Huber depth loss
+    (training_step_fused(depth_weight=, depth_huber=)).  depth_weight lives in a static buffer exactly as `weight` does and is replaced through
+    step(depth_weight=...) under the same checks; a step built without one raises when it is handed one.  depth_huber is an argument of the kernels
+    inside the step and so fixed when the step is built."""
 
     def __init__(self, model, camera, gt_image, bg, headroom=1.25, check_every=16, cap_R=None, cap_B=None, use_graph=False, gt_depth=None,
-                 lambda_depth=0.0, weight=None, grad_stats=None):
+                 lambda_depth=0.0, weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0):
         """use_graph=False (default since round 5): the capacity-mode step (caller-owned scratch, no host round trip, overflow checks and repeats as
         below) issued as eager launches; use_graph=True: captured in a hipGraph and replayed with one launch per step.  The two are equally fast at
         2M Gaussians (bench.py: `capacity_eager` / `graphed`; the host runs ahead of the device either way), and the eager form has no hazard:
@@ -1620,8 +1664,11 @@ class GraphedStep:
         self.proj = camera.d_full_proj_transform.clone()
         self.campos = camera.d_camera_center.clone()
         self.gt = gt_image.clone()
-        self.use_depth = gt_depth is not None and lambda_depth != 0.0
+        self.use_depth = _use_depth("GraphedStep", gt_depth, lambda_depth, depth_weight, depth_huber)
         self.lambda_depth = float(lambda_depth) if self.use_depth else 0.0
+        self.use_depth_weight = self.use_depth and depth_weight is not None
+        self.depth_weight = depth_weight.detach().float().contiguous().clone() if self.use_depth_weight else None
+        self.depth_huber = float(depth_huber) if self.use_depth else 0.0
         self.gt_depth = gt_depth.detach().float().contiguous().clone() if self.use_depth else None
         self.use_weight = weight is not None
         self.weight = weight.detach().float().contiguous().clone() if self.use_weight else None
@@ -1647,7 +1694,8 @@ class GraphedStep:
     def _eager(self):
         rr = _RawRaster(self.model, self.cam, self.bg, self.use_depth, e=self.e, pose=(self.view, self.proj, self.campos))
         image, depth, _radii = rr.forward(self.bufs)
-        dL_dimage, dL_ddepth, self.terms = _fused_losses(self.fl, image, self.gt, depth, self.gt_depth, self.lambda_depth, self.weight)
+        dL_dimage, dL_ddepth, self.terms = _fused_losses(self.fl, image, self.gt, depth, self.gt_depth, self.lambda_depth, self.weight, self.depth_weight,
+                                                         self.depth_huber)
         if self._gstat is None:
             rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad)
         else:
@@ -1697,7 +1745,7 @@ class GraphedStep:
         device between two replays)."""
         return (camera.world_view_transform.copy(), camera.full_proj_transform.copy(), camera.camera_center.copy())
 
-    def _load(self, camera, gt_image, gt_depth=None, weight=None):
+    def _load(self, camera, gt_image, gt_depth=None, weight=None, depth_weight=None):
         """Refresh the static buffers the captured step reads.  The pose is copied on every call that names a camera (the same Camera object
         may have been moved in place since it was loaded last)."""
         if weight is False:   # "this step runs without a weight": true only of a step that was built without one
@@ -1713,6 +1761,14 @@ class GraphedStep:
             if weight.data_ptr() != self.weight.data_ptr():
                 self.weight.copy_(weight)
                 self._w_serial = getattr(self, "_w_serial", 0) + 1
+        if depth_weight is not None:
+            if not self.use_depth_weight:
+                raise ValueError("GraphedStep: depth_weight given to a step built without one (pass depth_weight to the constructor)")
+            if tuple(depth_weight.shape) != tuple(self.depth_weight.shape):
+                raise ValueError(f"GraphedStep: depth_weight of shape {tuple(depth_weight.shape)} given to a step built for {tuple(self.depth_weight.shape)}")
+            if depth_weight.data_ptr() != self.depth_weight.data_ptr():
+                self.depth_weight.copy_(depth_weight)
+                self._dw_serial = getattr(self, "_dw_serial", 0) + 1
         if gt_depth is not None:
             if not self.use_depth:
                 raise ValueError("GraphedStep: gt_depth given to a step built without depth supervision (pass gt_depth / lambda_depth to the constructor)")
@@ -1729,7 +1785,7 @@ class GraphedStep:
             self.gt.copy_(gt_image)
             self._gt_serial = getattr(self, "_gt_serial", 0) + 1
 
-    def _snapshot(self, gt_image, gt_depth=None, weight=None):
+    def _snapshot(self, gt_image, gt_depth=None, weight=None, depth_weight=None):
         """What a repeat of this step needs, independent of what the caller does to its objects afterwards: the pose by VALUE (host copies of the
         35 floats that are loaded now) and the target by reference together with the evidence that it is still the same data (the tensor's
         version counter; for gt_image=None — "the target that is loaded" — the serial number of the load)."""
@@ -1737,7 +1793,8 @@ class GraphedStep:
             self._pose_host = self._pose_of(self.cam)
         return dict(pose=self._pose_host, gt=gt_image, gt_version=None if gt_image is None else gt_image._version, gt_serial=getattr(self, "_gt_serial", 0),
                     gtd=gt_depth, gtd_version=None if gt_depth is None else gt_depth._version, gtd_serial=getattr(self, "_gtd_serial", 0),
-                    w=weight, w_version=None if weight is None else weight._version, w_serial=getattr(self, "_w_serial", 0))
+                    w=weight, w_version=None if weight is None else weight._version, w_serial=getattr(self, "_w_serial", 0),
+                    dw=depth_weight, dw_version=None if depth_weight is None else depth_weight._version, dw_serial=getattr(self, "_dw_serial", 0))
 
     def _load_snapshot(self, snap):
         dev = self.view.device
@@ -1767,6 +1824,18 @@ class GraphedStep:
                 if w.data_ptr() != self.weight.data_ptr():
                     self.weight.copy_(w)
                     self._w_serial = getattr(self, "_w_serial", 0) + 1
+        if self.use_depth_weight:
+            dw = snap.get("dw")
+            if dw is None:
+                if snap.get("dw_serial", 0) != getattr(self, "_dw_serial", 0):
+                    raise RuntimeError("GraphedStep: a step that has to be repeated ran on a depth weight image that has been replaced since (it was "
+                                       "issued with depth_weight=None); pass the depth weight explicitly to step() when it changes between checks")
+            else:
+                if dw._version != snap["dw_version"]:
+                    raise RuntimeError("GraphedStep: the depth weight image of a step that has to be repeated was modified in place after the step was issued")
+                if dw.data_ptr() != self.depth_weight.data_ptr():
+                    self.depth_weight.copy_(dw)
+                    self._dw_serial = getattr(self, "_dw_serial", 0) + 1
         if not self.use_depth:
             return
         gtd = snap.get("gtd")
@@ -1798,14 +1867,15 @@ class GraphedStep:
             with torch.no_grad():
                 self._eager()
 
-    def step(self, camera=None, gt_image=None, gt_depth=None, weight=None):
+    def step(self, camera=None, gt_image=None, gt_depth=None, weight=None, depth_weight=None):
         """One optimiser step (replay).  Returns the device tensor [mean L1, mean SSIM] of this step's loss terms ([mean L1, mean SSIM, L_d]
-        with depth supervision; gt_depth: this step's depth target, None = the one that is loaded; weight: this step's weight image, likewise)."""
-        self._load(camera, gt_image, gt_depth, weight)
+        with depth supervision; gt_depth: this step's depth target, None = the one that is loaded; weight: this step's weight image, likewise;
+        depth_weight: this step's depth weight image, likewise)."""
+        self._load(camera, gt_image, gt_depth, weight, depth_weight)
         self._issue()
         self.steps_issued += 1
         if len(self.window) < 32:
-            self.window.append(self._snapshot(gt_image, gt_depth, None if weight is False else weight))
+            self.window.append(self._snapshot(gt_image, gt_depth, None if weight is False else weight, depth_weight))
         self.model.optimizer.count_step()
         if self.check_every and self.steps_issued >= self.check_every:
             self.check()

@@ -609,6 +609,35 @@ int gslic_depth_l1_loss_forward_backward(
     int32_t H, int32_t W, float lambda_depth, const float* depth, const float* gt_depth, float* partials, float* term /*[1] device*/,
     float* dL_ddepth, void* stream);
 
+/* gslic_depth_loss_weighted_forward_backward — the depth loss under a per-pixel weight image and a Huber (smooth-L1) threshold, and its gradient,
+ * in TWO launches (additive, ABI 8; no reference counterpart).  depth, gt_depth [H,W] float DEVICE; weight [H,W] float DEVICE or NULL (every
+ * pixel weighs 1); delta = the smooth-L1 `beta` in the unit of depth, 0 = plain L1.  Every step below is ONE IEEE float32 operation rounded on its
+ * own (no contraction; the divisions are true divisions):
+ *   w_p  = weight == NULL ? 1 : (weight_p > 0 && weight_p < +inf ? weight_p : 0)          NaN, negative and +inf weights read as 0
+ *   m_p  = gt_p > 0 && w_p > 0                        (a NaN fails: unmeasured; a pixel with w_p = 0 IS an unmeasured pixel, whatever depth_p holds)
+ *   r_p  = depth_p - gt_p,  a_p = |r_p|
+ *   delta == 0:  rho_p = a_p                                             rho'_p = r_p > 0 ? 1 : (r_p < 0 ? -1 : 0)
+ *   delta  > 0:  a_p <  delta:       rho_p = ((0.5 * a_p) * a_p) / delta    rho'_p = r_p / delta
+ *                otherwise:          rho_p = a_p - 0.5 * delta              rho'_p = +-1 (0 for r_p = 0 or NaN) as above
+ *   S = sum over m_p of w_p,  T = sum over m_p of w_p * rho_p           (float32, in the fixed order below; weight == NULL adds rho_p itself)
+ *   terms[0] = L_d = S > 0 ? T / S : 0,   terms[1] = S
+ *   k = S > 0 ? lambda_depth / S : 0
+ *   dL_ddepth_p = m_p ? (k * w_p) * rho'_p : 0       where rho'_p = +-1: +-(k * w_p), and +0 where it is 0; weight == NULL: k in place of k * w_p
+ * The gradient of lambda_depth * L_d; its magnitude never exceeds the L1's.  UNLIKE the colour weight above there is NO clamp at 1: inverse-variance
+ * weights are not bounded by 1, and the division by S makes the scale of the weights irrelevant — the difference is deliberate.
+ * Order of the sums: workgroups of 2048 consecutive pixels; thread t of 256 adds its pixels t, t + 256, ... in that order, the 256 thread sums go
+ * through a xor-shuffle tree (distances 32 ... 1) per 64 lanes and (r0 + r1) + (r2 + r3) over the four; the per-workgroup partials b are added
+ * the same way (thread t takes b = t, t + 256, ...).  That is the order of gslic_depth_l1_loss_forward_backward: with weight == NULL or all ones
+ * and delta == 0, S is a sum of ones (exact below 2^24 pixels) and terms[0] and dL_ddepth have the bits of that entry point.
+ * No atomics, no allocation, no host synchronisation: graph-capturable and bit-reproducible.  `partials`: DEVICE scratch of
+ * gslic_depth_loss_weighted_partials_count(H, W) floats.  GSLIC_ERR_INVALID_ARG before any device work, naming the argument, for H or W <= 0, a
+ * NULL depth / gt_depth / partials / terms / dL_ddepth, a delta that is negative, NaN or +inf, a NaN lambda_depth, and a dL_ddepth or terms that
+ * overlaps depth, gt_depth or weight. */
+int64_t gslic_depth_loss_weighted_partials_count(int32_t H, int32_t W);
+int gslic_depth_loss_weighted_forward_backward(
+    int32_t H, int32_t W, float lambda_depth, float delta, const float* depth, const float* gt_depth, const float* weight /*or NULL*/,
+    float* partials, float* terms /*[2] device*/, float* dL_ddepth, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * gslic_knn_mean_dist2 — replaces SimpleKNN::knn (src/simple-knn/simple_knn.cu:185-221) behind distCUDA2
  * (src/simple-knn/spatial.cu:15-26): mean_dists[i] = mean of the 3 smallest squared distances from point i

@@ -29,8 +29,8 @@ SOURCES = {
     "preprocess_bwd.hip": [],
     "preprocess_bwd_gstat.hip": [],   # the gradient-statistics variants of preprocess_bwd.hip's kernels, in a module of their own (their rule pins its own rounding: fp contract(off))
     "adam.hip": [],
-    "ssim.hip": ["-ffp-contract=off"],
-    "depth_loss.hip": [],    # the maps are held bit-exact to the reference kernels under the same flag (tests/golden/ssim_*.npz)
+    "ssim.hip": ["-ffp-contract=off"],   # the maps are held bit-exact to the reference kernels under the same flag (tests/golden/ssim_*.npz)
+    "depth_loss.hip": [],    # its two kernels pin their own rounding (fp contract(off)): the gradient is held to autograd's bits
     "knn.hip": [],
     "extend.hip": ["-ffp-contract=off"],  # pixel assignment decides integers: canonical order like preprocess.hip
     "prune.hip": [],         # comparisons and copies only: no arithmetic a flag could change

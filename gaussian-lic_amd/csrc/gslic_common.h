@@ -319,6 +319,20 @@ __device__ __forceinline__ uint32_t block256_exclusive_prefix(uint32_t thread_su
     block_total = total;
     return wave_base + inc - thread_sum;
 }
+// Sum of one value per thread over a 256-thread block, the same in every thread: a xor-shuffle tree 32 ... 1 inside each wave, the four wave
+// results through LDS, (r0 + r1) + (r2 + r3).  The order of the additions is part of the loss kernels' bit contract (ssim.hip, depth_loss.hip).
+// red: 4 elements, reusable after return (two barriers).
+template <typename T>
+__device__ __forceinline__ T block256_sum(T v, T* red /*[4]*/)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const T r = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return r;
+}
 __device__ __forceinline__ float readlane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 __device__ __forceinline__ uint32_t readlane_u(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 // Streaming accesses: data that is read once or written once per launch (Adam moments, per-instance partial gradients) goes past the

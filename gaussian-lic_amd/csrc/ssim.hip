@@ -176,20 +176,24 @@ __device__ __forceinline__ SsimTerms ssim_terms(const FwdStats& st, float C1, fl
     return t;
 }
 
-__global__ __launch_bounds__(256) void ssim_fwd_kernel(SsimGrid grid, int H, int W, float C1, float C2, const float* __restrict__ img1,
-                                                       const float* __restrict__ img2, float* __restrict__ ssim_map,
-                                                       float* __restrict__ dm_dmu1, float* __restrict__ dm_dsigma1_sq,
-                                                       float* __restrict__ dm_dsigma12)
+// The forward of one 32 x 32 tile, the one body of the three forward kernels: stage, column pass, terms, the three derivative maps.
+//   STORE_MAP  the drop-in kernel: the SSIM map is stored, and the derivative maps only when the caller passed them (train)
+//   SUMS       the loss kernels: the tile's sums of |a - b| and of the SSIM values go to partials[2 tile], [2 tile + 1] (fixed order, no atomics)
+//   WEIGHTED   both sums under w = loss_weight(weight[pixel]), and the tile's sum of w to partials_w[tile] (written by plane 0)
+template <bool STORE_MAP, bool SUMS, bool WEIGHTED>
+__device__ __forceinline__ void ssim_fwd_body(FwdLds& L, float* red /*[4], SUMS only*/, SsimGrid grid, int H, int W, float C1, float C2,
+                                              const float* img1, const float* img2, const float* weight,
+                                              float* ssim_map, float* dm_dmu1, float* dm_dsigma1_sq,
+                                              float* dm_dsigma12, float* partials, float* partials_w)
 {
-    __shared__ FwdLds L;
     int tile_x, tile_y, plane_i;
     size_t tile_linear;
     if (!ssim_tile(grid, tile_x, tile_y, plane_i, tile_linear)) return;   // (whole workgroup: before any barrier)
     const size_t plane = (size_t)plane_i * H * W;
     const int x0 = tile_x * ST, y0 = tile_y * ST;
     const int tid = threadIdx.x;
-    float l1_unused = 0.f;
-    ssim_fwd_stage(L, img1 + plane, img2 + plane, H, W, x0, y0, l1_unused);
+    float sum_l1 = 0.f, sum_ssim = 0.f, sum_w = 0.f;
+    ssim_fwd_stage<WEIGHTED>(L, img1 + plane, img2 + plane, H, W, x0, y0, sum_l1, weight, &sum_w);
     const int lx = tid & 31;
     FwdStats st4[4];
     ssim_fwd_column4(L, 4 * (tid >> 5), lx, st4);
@@ -201,14 +205,36 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(SsimGrid grid, int H, int
         if (px < W && py < H) {
             const SsimTerms t = ssim_terms(st, C1, C2);
             const size_t o = plane + (size_t)py * W + px;
-            ssim_map[o] = t.map;
-            if (dm_dmu1) {
+            if constexpr (STORE_MAP) ssim_map[o] = t.map;
+            if constexpr (SUMS) sum_ssim += WEIGHTED ? loss_weight(weight[(size_t)py * W + px]) * t.map : t.map;
+            if (!STORE_MAP || dm_dmu1) {
                 dm_dmu1[o] = t.d_mu1;
                 dm_dsigma1_sq[o] = t.d_sigma1_sq;
                 dm_dsigma12[o] = t.d_sigma12;
             }
         }
     }
+    if constexpr (SUMS) {
+        const float bl1 = block256_sum(sum_l1, red);
+        const float bss = block256_sum(sum_ssim, red);
+        float bw = 0.f;
+        if constexpr (WEIGHTED) bw = block256_sum(sum_w, red);
+        if (tid == 0) {
+            const size_t blk = tile_linear;
+            partials[2 * blk] = bl1;
+            partials[2 * blk + 1] = bss;
+            if (WEIGHTED && plane_i == 0) partials_w[blk] = bw;   // (plane 0 holds tiles 0 .. gx gy - 1)
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ssim_fwd_kernel(SsimGrid grid, int H, int W, float C1, float C2, const float* __restrict__ img1,
+                                                       const float* __restrict__ img2, float* __restrict__ ssim_map,
+                                                       float* __restrict__ dm_dmu1, float* __restrict__ dm_dsigma1_sq,
+                                                       float* __restrict__ dm_dsigma12)
+{
+    __shared__ FwdLds L;
+    ssim_fwd_body<true, false, false>(L, nullptr, grid, H, W, C1, C2, img1, img2, nullptr, ssim_map, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, nullptr, nullptr);
 }
 
 // The backward keeps three separate LDS arrays and scalar arithmetic: the interleaved / packed variant of the forward was measured slower here
@@ -297,17 +323,6 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(SsimGrid grid, int H, int
 // Loss of optimize() (gaussian.cpp:685-691) with l1_loss (loss_utils.h:30-33) folded into the SSIM passes.
 // loss_fwd_kernel = ssim_fwd_kernel without the ssim_map store, plus per-block sums of |a-b| and of the SSIM values;
 // loss_reduce_kernel adds the per-block partials in a fixed order (bit-reproducible, no float atomics).
-__device__ __forceinline__ float block256_sum(float v, float* red /*[4]*/)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float r = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(256) void loss_fwd_kernel(SsimGrid grid, int H, int W, float C1, float C2, const float* __restrict__ img1,
                                                        const float* __restrict__ img2, float* __restrict__ dm_dmu1,
                                                        float* __restrict__ dm_dsigma1_sq, float* __restrict__ dm_dsigma12,
@@ -315,38 +330,7 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(SsimGrid grid, int H, int
 {
     __shared__ FwdLds L;
     __shared__ float red[4];
-    int tile_x, tile_y, plane_i;
-    size_t tile_linear;
-    if (!ssim_tile(grid, tile_x, tile_y, plane_i, tile_linear)) return;   // (whole workgroup: before any barrier)
-    const size_t plane = (size_t)plane_i * H * W;
-    const int x0 = tile_x * ST, y0 = tile_y * ST;
-    const int tid = threadIdx.x;
-    float sum_l1 = 0.f, sum_ssim = 0.f;
-    ssim_fwd_stage(L, img1 + plane, img2 + plane, H, W, x0, y0, sum_l1);
-    const int lx = tid & 31;
-    FwdStats st4[4];
-    ssim_fwd_column4(L, 4 * (tid >> 5), lx, st4);
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int ly = 4 * (tid >> 5) + q;
-        const FwdStats st = st4[q];
-        const int px = x0 + lx, py = y0 + ly;
-        if (px < W && py < H) {
-            const SsimTerms t = ssim_terms(st, C1, C2);
-            const size_t o = plane + (size_t)py * W + px;
-            sum_ssim += t.map;
-            dm_dmu1[o] = t.d_mu1;
-            dm_dsigma1_sq[o] = t.d_sigma1_sq;
-            dm_dsigma12[o] = t.d_sigma12;
-        }
-    }
-    const float bl1 = block256_sum(sum_l1, red);
-    const float bss = block256_sum(sum_ssim, red);
-    if (tid == 0) {
-        const size_t blk = tile_linear;
-        partials[2 * blk] = bl1;
-        partials[2 * blk + 1] = bss;
-    }
+    ssim_fwd_body<false, true, false>(L, red, grid, H, W, C1, C2, img1, img2, nullptr, nullptr, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, partials, nullptr);
 }
 
 __global__ __launch_bounds__(256) void loss_reduce_kernel(size_t nblk, const float* __restrict__ partials, float inv_n, float* __restrict__ terms)
@@ -403,40 +387,7 @@ __global__ __launch_bounds__(256) void loss_weighted_fwd_kernel(SsimGrid grid, i
 {
     __shared__ FwdLds L;
     __shared__ float red[4];
-    int tile_x, tile_y, plane_i;
-    size_t tile_linear;
-    if (!ssim_tile(grid, tile_x, tile_y, plane_i, tile_linear)) return;   // (whole workgroup: before any barrier)
-    const size_t plane = (size_t)plane_i * H * W;
-    const int x0 = tile_x * ST, y0 = tile_y * ST;
-    const int tid = threadIdx.x;
-    float sum_l1 = 0.f, sum_ssim = 0.f, sum_w = 0.f;
-    ssim_fwd_stage<true>(L, img1 + plane, img2 + plane, H, W, x0, y0, sum_l1, weight, &sum_w);
-    const int lx = tid & 31;
-    FwdStats st4[4];
-    ssim_fwd_column4(L, 4 * (tid >> 5), lx, st4);
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int ly = 4 * (tid >> 5) + q;
-        const FwdStats st = st4[q];
-        const int px = x0 + lx, py = y0 + ly;
-        if (px < W && py < H) {
-            const SsimTerms t = ssim_terms(st, C1, C2);
-            const size_t o = plane + (size_t)py * W + px;
-            sum_ssim += loss_weight(weight[(size_t)py * W + px]) * t.map;
-            dm_dmu1[o] = t.d_mu1;
-            dm_dsigma1_sq[o] = t.d_sigma1_sq;
-            dm_dsigma12[o] = t.d_sigma12;
-        }
-    }
-    const float bl1 = block256_sum(sum_l1, red);
-    const float bss = block256_sum(sum_ssim, red);
-    const float bw = block256_sum(sum_w, red);
-    if (tid == 0) {
-        const size_t blk = tile_linear;
-        partials[2 * blk] = bl1;
-        partials[2 * blk + 1] = bss;
-        if (plane_i == 0) partials_w[blk] = bw;   // (plane 0 holds tiles 0 .. gx gy - 1)
-    }
+    ssim_fwd_body<false, true, true>(L, red, grid, H, W, C1, C2, img1, img2, weight, nullptr, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, partials, partials_w);
 }
 
 // One workgroup: the three sums in loss_reduce_kernel's order (bit-reproducible), then terms = {L1_w, SSIM_w, S} and the backward's coefficients

@@ -60,7 +60,7 @@ EXPORTS = [
     "gslic_l1_ssim_loss_weighted_partials_count", "gslic_l1_ssim_loss_weighted_forward_backward",
     "gslic_morton_order", "gslic_permute_rows", "gslic_permute_rows_staging_bytes",
     "gslic_rasterize_backward_adam_stats", "gslic_rasterize_backward_depth_adam_stats", "gslic_gradient_stats_accumulate",
-    "gslic_lidar_zbuffer_add", "gslic_lidar_zbuffer_resolve",
+    "gslic_lidar_zbuffer_add", "gslic_lidar_zbuffer_resolve", "gslic_lidar_zbuffer_resolve_weighted",
     "gslic_depth_loss_weighted_partials_count", "gslic_depth_loss_weighted_forward_backward",
 ]
 
@@ -142,6 +142,7 @@ def lib():
     L.gslic_gather_rows.argtypes = [ctypes.POINTER(RowArray), i32, vp, i32, vp]
     L.gslic_lidar_zbuffer_add.argtypes = [i32, vp, vp, vp, f32, f32, f32, f32, i32, i32, vp, i32, i32, vp]   # n, points, R_cw, t_cw, fx fy cx cy, W, H, zbuf, clear, index_base, stream
     L.gslic_lidar_zbuffer_resolve.argtypes = [i32, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp]   # W, H, zbuf, footprint, margin_abs, margin_rel, depth, index, near, n_measured, stream
+    L.gslic_lidar_zbuffer_resolve_weighted.argtypes = [i32, i32, vp, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp]   # W, H, zbuf, footprint, margin_abs, margin_rel, sigma_abs, sigma_rel, falloff, depth, index, near, n_measured, weight, dist2, stream
     L.gslic_morton_order.argtypes = [i32, vp, vp, ALLOC_FN, vp, vp, vp, vp]   # P, xyz, box, allocator + context, perm, keys_sorted, stream
     L.gslic_permute_rows.argtypes = [ctypes.POINTER(RowArray), i32, vp, i32, vp, ctypes.c_size_t, vp]   # arrays, n, perm, n_rows, staging + bytes, stream
     L.gslic_permute_rows_staging_bytes.restype = ctypes.c_size_t

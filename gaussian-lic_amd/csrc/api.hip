@@ -1465,6 +1465,42 @@ int gslic_lidar_zbuffer_resolve(int32_t width, int32_t height, const uint64_t* z
                                  index_out, near_out, n_measured_out, (hipStream_t)stream);
 }
 
+int gslic_lidar_zbuffer_resolve_weighted(int32_t width, int32_t height, const uint64_t* zbuf, int32_t footprint, float margin_abs, float margin_rel,
+                                         float sigma_abs, float sigma_rel, float falloff, float* depth_out, int32_t* index_out, float* near_out,
+                                         uint32_t* n_measured_out, float* weight_out, int32_t* dist2_out, void* stream)
+{
+    static const char* const who = "lidar zbuffer resolve weighted";
+    if (width <= 0 || height <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: width=%d height=%d must be positive", who, width, height);
+    if (!zbuf) return set_error(GSLIC_ERR_INVALID_ARG, "%s: zbuf is NULL", who);
+    if (footprint < 0 || footprint > 8) return set_error(GSLIC_ERR_INVALID_ARG, "%s: footprint=%d outside [0, 8]", who, footprint);
+    if (!(margin_abs >= 0.0f)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: margin_abs=%g is negative or NaN", who, (double)margin_abs);
+    if (!(margin_rel >= 0.0f)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: margin_rel=%g is negative or NaN", who, (double)margin_rel);
+    if (!depth_out && !index_out && !near_out && !weight_out && !dist2_out)
+        return set_error(GSLIC_ERR_INVALID_ARG, "%s: depth_out, index_out, near_out, weight_out and dist2_out are all NULL", who);
+    if (weight_out) {
+        const float inf = __builtin_inff();
+        if (!(sigma_abs > 0.0f && sigma_abs < inf))
+            return set_error(GSLIC_ERR_INVALID_ARG, "%s: sigma_abs=%g must be > 0 and finite", who, (double)sigma_abs);
+        if (!(sigma_rel >= 0.0f && sigma_rel < inf))
+            return set_error(GSLIC_ERR_INVALID_ARG, "%s: sigma_rel=%g is negative, NaN or infinite", who, (double)sigma_rel);
+        if (!(falloff >= 0.0f && falloff < inf))
+            return set_error(GSLIC_ERR_INVALID_ARG, "%s: falloff=%g is negative, NaN or infinite", who, (double)falloff);
+    }
+    const size_t N = (size_t)width * (size_t)height;
+    const uintptr_t z0 = reinterpret_cast<uintptr_t>(zbuf), z1 = z0 + N * sizeof(uint64_t);
+    const struct { const void* p; size_t bytes; const char* name; } outs[6] = {
+        {depth_out, N * sizeof(float), "depth_out"}, {index_out, N * sizeof(int32_t), "index_out"}, {near_out, N * sizeof(float), "near_out"},
+        {n_measured_out, sizeof(uint32_t), "n_measured_out"}, {weight_out, N * sizeof(float), "weight_out"},
+        {dist2_out, N * sizeof(int32_t), "dist2_out"}};
+    for (const auto& o : outs) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(o.p);
+        if (o.p && a < z1 && z0 < a + o.bytes) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s overlaps zbuf", who, o.name);
+    }
+    return lidar_zbuffer_resolve_weighted(width, height, reinterpret_cast<const unsigned long long*>(zbuf), footprint, margin_abs, margin_rel, sigma_abs,
+                                          sigma_rel, falloff, depth_out, index_out, near_out, n_measured_out, weight_out, dist2_out,
+                                          (hipStream_t)stream);
+}
+
 size_t gslic_permute_rows_staging_bytes(const gslic_row_array* arrays, int32_t n_arrays, int32_t n_rows)
 {
     if (!arrays || n_arrays <= 0 || n_rows <= 0) return 0;

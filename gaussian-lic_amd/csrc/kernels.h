@@ -189,6 +189,10 @@ int lidar_zbuffer_add(int n, const float* points, const float* Rcw, const float*
                       unsigned long long* zbuf, bool clear, int32_t index_base, hipStream_t s);
 int lidar_zbuffer_resolve(int W, int H, const unsigned long long* zbuf, int footprint, float margin_abs, float margin_rel, float* depth_out,
                           int32_t* index_out, float* near_out, uint32_t* n_measured_out, hipStream_t s);
+// ... and gslic_lidar_zbuffer_resolve_weighted: the same images plus the weight and dist2 images, in one launch of a kernel of its own
+int lidar_zbuffer_resolve_weighted(int W, int H, const unsigned long long* zbuf, int footprint, float margin_abs, float margin_rel, float sigma_abs,
+                                   float sigma_rel, float falloff, float* depth_out, int32_t* index_out, float* near_out, uint32_t* n_measured_out,
+                                   float* weight_out, int32_t* dist2_out, hipStream_t s);
 
 // contrib.hip: the per-Gaussian contribution statistics of gslic_contribution_accumulate from a completed forward's lists (one workgroup per tile;
 // arguments validated by the caller; any of the three accumulators may be NULL)

@@ -115,6 +115,7 @@ FUSED_CHECKS = {name: (os.path.join(HERE, name + "_check.cpp"), os.path.join(PKG
     "fused_free_space",       # free-space statistics, carried through prune and resort
     "fused_rows",             # both statistics objects at once through densify, extend, prune and resort
     "fused_lidar_depth",      # the LiDAR range image (gslic::LidarDepth) feeding a depth-supervised step and the free-space statistics
+    "fused_lidar_weight",     # ... its weight and dist2 images feeding the weighted depth step
 )}
 
 

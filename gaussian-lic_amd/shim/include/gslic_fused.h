@@ -111,6 +111,8 @@ struct LidarImages {
     torch::Tensor near_bound;   // float32 [H,W]: depth - (margin_abs + margin_rel * depth) where measured, 0 elsewhere (only with margins)
     torch::Tensor index;        // int32 [H,W]: the winning point, -1 = none (only when asked for)
     torch::Tensor n_measured;   // int32 scalar on the device: measured pixels (only when asked for)
+    torch::Tensor weight;       // float32 [H,W]: range weight times 1 / (1 + falloff * dist2), 0 = none; a depth_weight as it is (only with weight)
+    torch::Tensor dist2;        // int32 [H,W]: squared pixel distance to the return the pixel was given, -1 = none (only when asked for)
 };
 class LidarDepth {
 public:
@@ -137,10 +139,20 @@ public:
         return add_raw((int32_t)n, n ? pts.data_ptr<float>() : nullptr, R.data_ptr<float>(), t.data_ptr<float>(), fx, fy, cx, cy);
     }
     // The images of what was added since the last clear().  footprint r in [0, 8]: every pixel takes the nearest return of its (2r+1) x (2r+1)
-    // window clipped to the image (0: its own).  margins: when set, near_bound is written too.
-    LidarImages resolve(int footprint = 0, std::optional<std::array<float, 2>> margins = std::nullopt, bool index = false, bool count = false)
+    // window clipped to the image (0: its own).  margins: when set, near_bound is written too.  weight = {sigma_abs, sigma_rel, falloff}: when
+    // set, the weight image sigma_abs / (sigma_abs + sigma_rel d) * 1 / (1 + falloff * dist2) is written too (sigma_abs > 0, sigma_rel >= 0,
+    // falloff >= 0, all finite); dist2: the squared pixel distance to the return each pixel was given.  Both come from the same single launch
+    // (gslic_lidar_zbuffer_resolve_weighted); with neither, the call is gslic_lidar_zbuffer_resolve's.
+    LidarImages resolve(int footprint = 0, std::optional<std::array<float, 2>> margins = std::nullopt, bool index = false, bool count = false,
+                        std::optional<std::array<float, 3>> weight = std::nullopt, bool dist2 = false)
     {
         torch::NoGradGuard ng;
+        if (weight) {
+            const float inf = std::numeric_limits<float>::infinity();
+            TORCH_CHECK((*weight)[0] > 0.0f && (*weight)[0] < inf && (*weight)[1] >= 0.0f && (*weight)[1] < inf,
+                        "LidarDepth::resolve: sigma_abs must be > 0 and sigma_rel >= 0, both finite");
+            TORCH_CHECK((*weight)[2] >= 0.0f && (*weight)[2] < inf, "LidarDepth::resolve: the falloff must be >= 0 and finite");
+        }
         if (pending_clear_) add_raw(0, nullptr, nullptr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f);
         const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(zbuf_.device()), i32 = f32.dtype(torch::kInt32);
         LidarImages out;
@@ -148,6 +160,18 @@ public:
         if (margins) out.near_bound = torch::empty({H_, W_}, f32);
         if (index) out.index = torch::empty({H_, W_}, i32);
         if (count) out.n_measured = torch::empty({}, i32);
+        if (weight || dist2) {
+            if (weight) out.weight = torch::empty({H_, W_}, f32);
+            if (dist2) out.dist2 = torch::empty({H_, W_}, i32);
+            const int rc = gslic_lidar_zbuffer_resolve_weighted(
+                W_, H_, reinterpret_cast<const uint64_t*>(zbuf_.data_ptr<int64_t>()), footprint, margins ? (*margins)[0] : 0.0f,
+                margins ? (*margins)[1] : 0.0f, weight ? (*weight)[0] : 1.0f, weight ? (*weight)[1] : 0.0f, weight ? (*weight)[2] : 0.0f,
+                out.depth.data_ptr<float>(), index ? out.index.data_ptr<int32_t>() : nullptr, margins ? out.near_bound.data_ptr<float>() : nullptr,
+                count ? reinterpret_cast<uint32_t*>(out.n_measured.data_ptr<int32_t>()) : nullptr, weight ? out.weight.data_ptr<float>() : nullptr,
+                dist2 ? out.dist2.data_ptr<int32_t>() : nullptr, current_stream());
+            TORCH_CHECK(rc == GSLIC_OK, "gslic_lidar_zbuffer_resolve_weighted failed (", rc, "): ", gslic_last_error());
+            return out;
+        }
         const int rc = gslic_lidar_zbuffer_resolve(W_, H_, reinterpret_cast<const uint64_t*>(zbuf_.data_ptr<int64_t>()), footprint, margins ? (*margins)[0] : 0.0f,
                                                    margins ? (*margins)[1] : 0.0f, out.depth.data_ptr<float>(), index ? out.index.data_ptr<int32_t>() : nullptr,
                                                    margins ? out.near_bound.data_ptr<float>() : nullptr,

@@ -638,11 +638,17 @@ class LidarDepth:
         return self._add_raw(int(pts.shape[0]), pts, R_cw, t_cw, float(camera.fx), float(camera.fy), float(camera.cx), float(camera.cy))
 
     @torch.no_grad()
-    def resolve(self, footprint=0, margins=None, index=False, count=False):
+    def resolve(self, footprint=0, margins=None, index=False, count=False, weight=None, dist2=False):
         """The images of what was added since the last clear(), as a dict: "depth" float32 [H,W] (0 = no return in the window); with
         margins=(margin_abs, margin_rel) also "near" = depth - (margin_abs + margin_rel * depth) where measured and 0 elsewhere
         (free_space_bound's arithmetic; a bound <= 0 is kept as it is); with index=True "index" int32 [H,W] (the winning point, -1 = none); with
-        count=True "n_measured", a device int32 scalar tensor holding the number of measured pixels (no read-back here)."""
+        count=True "n_measured", a device int32 scalar tensor holding the number of measured pixels (no read-back here).
+
+        With dist2=True also "dist2" int32 [H,W]: the squared pixel distance from the pixel to the return it was given (0 = its own, at most
+        2 footprint^2; -1 = none).  With weight=(sigma_abs, sigma_rel) or (sigma_abs, sigma_rel, falloff) (falloff defaults to 0) also "weight"
+        float32 [H,W], usable as it is as depth_weight= of the training steps: range_weight(depth, sigma_abs, sigma_rel) times
+        1 / (1 + falloff * dist2), 0 where nothing was measured (the rule of gslic_lidar_zbuffer_resolve_weighted; where dist2 is 0, and everywhere
+        at falloff 0, range_weight's bits).  Both come out of the same single launch; with neither, the call is gslic_lidar_zbuffer_resolve's."""
         from . import _lib
         r = int(footprint)
         if not 0 <= r <= self.MAX_FOOTPRINT:
@@ -650,6 +656,15 @@ class LidarDepth:
         ma, mr = (0.0, 0.0) if margins is None else (float(margins[0]), float(margins[1]))
         if not (ma >= 0.0 and mr >= 0.0):   # (a NaN fails)
             raise ValueError(f"LidarDepth.resolve: the margins must be >= 0, got {margins!r}")
+        sa, sr, fo = 1.0, 0.0, 0.0
+        if weight is not None:
+            if not isinstance(weight, (tuple, list)) or len(weight) not in (2, 3):
+                raise ValueError(f"LidarDepth.resolve: weight must be (sigma_abs, sigma_rel) or (sigma_abs, sigma_rel, falloff), got {weight!r}")
+            sa, sr, fo = float(weight[0]), float(weight[1]), (float(weight[2]) if len(weight) == 3 else 0.0)
+            if not (sa > 0.0 and sr >= 0.0 and sa < float("inf") and sr < float("inf")):   # (a NaN fails; range_weight's check and words)
+                raise ValueError(f"LidarDepth.resolve: sigma_abs must be > 0 and sigma_rel >= 0, both finite, got {weight[0]!r} and {weight[1]!r}")
+            if not (fo >= 0.0 and fo < float("inf")):
+                raise ValueError(f"LidarDepth.resolve: the falloff must be >= 0 and finite, got {weight[2]!r}")
         if self._pending_clear:
             self._add_raw(0, None, None, None, 0.0, 0.0, 0.0, 0.0)
         H, W, dev = self.height, self.width, self.device
@@ -660,9 +675,18 @@ class LidarDepth:
             out["index"] = torch.empty(H, W, dtype=torch.int32, device=dev)
         if count:
             out["n_measured"] = torch.empty((), dtype=torch.int32, device=dev)
+        if weight is not None:
+            out["weight"] = torch.empty(H, W, dtype=torch.float32, device=dev)
+        if dist2:
+            out["dist2"] = torch.empty(H, W, dtype=torch.int32, device=dev)
         p = lambda k: _lib.ptr(out.get(k))
-        _lib.check(_lib.lib().gslic_lidar_zbuffer_resolve(W, H, _lib.ptr(self._zbuf), r, ma, mr, p("depth"), p("index"), p("near"), p("n_measured"),
-                                                          _lib.current_stream_ptr()))
+        if weight is None and not dist2:
+            _lib.check(_lib.lib().gslic_lidar_zbuffer_resolve(W, H, _lib.ptr(self._zbuf), r, ma, mr, p("depth"), p("index"), p("near"), p("n_measured"),
+                                                              _lib.current_stream_ptr()))
+        else:
+            _lib.check(_lib.lib().gslic_lidar_zbuffer_resolve_weighted(W, H, _lib.ptr(self._zbuf), r, ma, mr, sa, sr, fo, p("depth"), p("index"),
+                                                                       p("near"), p("n_measured"), p("weight"), p("dist2"),
+                                                                       _lib.current_stream_ptr()))
         return out
 
 

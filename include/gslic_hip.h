@@ -674,8 +674,9 @@ int gslic_extend_emit(
     float* xyz, float* dc, float* rest, float* opacity, float* scaling, float* rotation, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * gslic_lidar_zbuffer_add / gslic_lidar_zbuffer_resolve — the per-pixel LiDAR range image on the device: what gt_depth (depth supervision, the
- * pose gradient under depth) and near_bound (gslic_contribution_accumulate_free_space) are made from.  The reference's host builds it on the CPU
+ * gslic_lidar_zbuffer_add / gslic_lidar_zbuffer_resolve / gslic_lidar_zbuffer_resolve_weighted — the per-pixel LiDAR range image on the device:
+ * what gt_depth (depth supervision, the pose gradient under depth), depth_weight (the weighted depth loss) and near_bound
+ * (gslic_contribution_accumulate_free_space) are made from.  The reference's host builds it on the CPU
  * (a device-to-host copy of every point and an unordered_map keyed by "x_y" strings, gaussian.cpp:554-572); a LibTorch host needs about twenty
  * elementwise launches and scatter_reduce_(amin).  Both calls work on a CALLER-OWNED z-buffer zbuf of width * height uint64 on the DEVICE, one
  * key per pixel (row-major, pixel (x, y) at y * width + x): the all-ones word = empty, otherwise (float bits of z) << 32 | point index.
@@ -707,6 +708,34 @@ int gslic_extend_emit(
  *  any device work, the message naming the argument: n < 0; width <= 0 or height <= 0; a NULL zbuf; NULL points, R_cw or t_cw with n > 0;
  *  index_base < 0 or index_base + n > 2^31 - 1; footprint outside [0, 8]; a margin that is negative or NaN; depth_out, index_out and near_out
  *  all NULL; an output (n_measured_out included) whose bytes overlap zbuf's.  With N > 1 GPUs every rank calls both with identical arguments.
+ *
+ *  resolve_weighted (gslic_lidar_zbuffer_resolve_weighted): resolve with two more optional images from the SAME launch — how far away the return a
+ *           pixel was given fell, and a weight for the depth loss (depth_weight) that says so.  A footprint r > 0 fills most of a sparse image with
+ *           depths borrowed from up to r sqrt(2) pixels away; resolve hands back only the winning point's index, so without this call a host
+ *           would have to re-project every point to learn the distance.  Every argument of resolve keeps its meaning and the four outputs of
+ *           resolve are written as resolve writes them.  Per pixel (x, y), also EXACT:
+ *
+ *             key = the minimum of zbuf over the clipped (2r+1) x (2r+1) window                       (as resolve)
+ *             s2  = the smallest dx^2 + dy^2 over the cells (x+dx, y+dy) of that same clipped window whose OWN zbuf key equals key
+ *                   (an integer in 0 .. 2 r^2; one such cell always exists when key is not empty.  Keys are normally unique per pixel; "smallest"
+ *                   makes the rule total when a caller reused an index_base.  s2 = 0: the pixel itself was measured and its own return is the
+ *                   nearest of its window.  s2 > 0 on a measured pixel: its own return was overruled by a nearer neighbour's)
+ *             dist2_out  int32    s2;                                                                  -1 where key is empty
+ *             weight_out float32  with d the depth of key, four steps, each ONE float32 operation rounded on its own, true divisions:
+ *                                   a  = sigma_abs + sigma_rel * d          (one product, one add)
+ *                                   rw = sigma_abs / a
+ *                                   f  = 1.0f / (1.0f + falloff * (float) s2)
+ *                                   w  = rw * f;                                                      0 where key is empty
+ *
+ *           So at s2 = 0, f is exactly 1 and w is the host's range weight sigma_abs / (sigma_abs + sigma_rel d) bit for bit (the Python host's
+ *           trainer.range_weight); at footprint 0 the whole weight image is that range weight of the depth image; at falloff 0 it is at any
+ *           footprint.  A product that overflows to +inf gives weight 0 (a = +inf makes rw = 0; 1 + inf makes f = 0), which the depth loss reads as
+ *           unmeasured.  The falloff is rational, not an exponential, so that any IEEE float32 arithmetic reproduces it.  Which sigmas, falloff and
+ *           footprint to use is the host's policy.  n_measured_out as in resolve.  Same promises: no allocation, synchronisation, read-back or float
+ *           atomics; graph-capturable.  Refused with GSLIC_ERR_INVALID_ARG before any device work, the message naming the argument: everything
+ *           resolve refuses, "all NULL" now meaning depth_out, index_out, near_out, weight_out and dist2_out; with a weight_out, a sigma_abs
+ *           that is not > 0 or not finite, a sigma_rel or a falloff that is negative, NaN or infinite (without one the three are not looked at);
+ *           weight_out or dist2_out overlapping zbuf.
  */
 int gslic_lidar_zbuffer_add(
     int32_t n, const float* points /*[n,3]*/, const float* R_cw /*[9]*/, const float* t_cw /*[3]*/,
@@ -716,6 +745,11 @@ int gslic_lidar_zbuffer_resolve(
     int32_t width, int32_t height, const uint64_t* zbuf /*[height*width]*/, int32_t footprint, float margin_abs, float margin_rel,
     float* depth_out /*[H,W] or NULL*/, int32_t* index_out /*[H,W] or NULL*/, float* near_out /*[H,W] or NULL*/,
     uint32_t* n_measured_out /*[1] or NULL*/, void* stream);
+int gslic_lidar_zbuffer_resolve_weighted(
+    int32_t width, int32_t height, const uint64_t* zbuf /*[height*width]*/, int32_t footprint, float margin_abs, float margin_rel,
+    float sigma_abs, float sigma_rel, float falloff,
+    float* depth_out /*[H,W] or NULL*/, int32_t* index_out /*[H,W] or NULL*/, float* near_out /*[H,W] or NULL*/,
+    uint32_t* n_measured_out /*[1] or NULL*/, float* weight_out /*[H,W] or NULL*/, int32_t* dist2_out /*[H,W] or NULL*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * gslic_prune_select / gslic_gather_rows — removing rows from the map (no reference counterpart: its map only grows; a LibTorch host

@@ -62,6 +62,7 @@ EXPORTS = [
     "gslic_rasterize_backward_adam_stats", "gslic_rasterize_backward_depth_adam_stats", "gslic_gradient_stats_accumulate",
     "gslic_lidar_zbuffer_add", "gslic_lidar_zbuffer_resolve", "gslic_lidar_zbuffer_resolve_weighted",
     "gslic_depth_loss_weighted_partials_count", "gslic_depth_loss_weighted_forward_backward",
+    "gslic_geometry_images",
 ]
 
 _lib = None
@@ -150,6 +151,7 @@ def lib():
     L.gslic_contribution_accumulate.argtypes = [prm, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp]   # params, R, B, geom / binning / img, w_min, 3 outputs, stream
     L.gslic_contribution_accumulate_error.argtypes = [prm, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]   # ... 3 outputs, err, err_sum, stream
     L.gslic_contribution_accumulate_free_space.argtypes = [prm, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]   # ... 3 outputs, near_bound, free_sum, meas_sum, stream
+    L.gslic_geometry_images.argtypes = [prm, i32, i32, vp, vp, vp, f32] + [vp] * 7 + [vp]   # params, R, B, geom / binning / img, a_min, 7 images, stream
     L.gslic_densify_select.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, ALLOC_FN, vp, vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     six_ptrs = ctypes.POINTER(vp)   # HOST array of six device base pointers
     L.gslic_densify_emit.argtypes = [i32, i32, vp, i32, six_ptrs, six_ptrs, six_ptrs, vp, f32, u32, vp]

@@ -1590,6 +1590,33 @@ int gslic_contribution_accumulate_free_space(const gslic_raster_params* prm, int
                                    near_bound, free_sum, meas_sum);
 }
 
+int gslic_geometry_images(const gslic_raster_params* prm, int32_t R, int32_t B, const char* geom_buffer, const char* binning_buffer,
+                          const char* img_buffer, float a_min, float* transmittance, float* opacity, float* depth_sum, float* depth_norm,
+                          float* depth_median, int32_t* top_row, float* top_weight, void* stream)
+{
+    GS_TRY(check_params(prm));
+    if (R < 0 || B < 0) return set_error(GSLIC_ERR_INVALID_ARG, "geometry images: negative R / B");
+    if (prm->no_color) return set_error(GSLIC_ERR_INVALID_ARG, "geometry images: a no_color forward stores no n_contrib (nothing says where a pixel stopped)");
+    if (depth_norm && !(a_min > 0.0f)) return set_error(GSLIC_ERR_INVALID_ARG, "geometry images: a_min must be > 0 for depth_norm (it guards the division)");
+    const bool any = transmittance || opacity || depth_sum || depth_norm || depth_median || top_row || top_weight;
+    const bool lists = prm->P != 0 && R != 0;
+    if (lists && (!geom_buffer || !binning_buffer || !img_buffer)) return set_error(GSLIC_ERR_INVALID_ARG, "geometry images: NULL forward buffer");
+    if (!any) return GSLIC_OK;
+    int gx, gy;
+    GeometryArgs ga = {};
+    ga.W = prm->width; ga.H = prm->height; ga.T = tile_grid(prm->width, prm->height, gx, gy); ga.gx = gx; ga.P = prm->P; ga.R = (uint32_t)R;
+    if (lists) {   // the colour-only carve, as the contribution launches
+        GeomState geom = GeomState::carve(align256(const_cast<char*>(geom_buffer)), (size_t)prm->P, nullptr);
+        ImageState img = ImageState::carve(align256(const_cast<char*>(img_buffer)), (size_t)ga.T, nullptr);
+        BinningState bin = BinningState::carve(align256(const_cast<char*>(binning_buffer)), (size_t)R, sort_end_bit(ga.T), false, nullptr);
+        ga.ranges = img.ranges; ga.point_list = bin.point_list(); ga.rec = geom.rec; ga.pix_final = img.pix_final; ga.status = geom.flags;
+    }
+    ga.a_min = a_min;
+    ga.transmittance = transmittance; ga.opacity = opacity; ga.depth_sum = depth_sum; ga.depth_norm = depth_norm; ga.depth_median = depth_median;
+    ga.top_row = top_row; ga.top_weight = top_weight;
+    return launch_geometry_images(ga, lists, (hipStream_t)stream);
+}
+
 int gslic_densify_select(int32_t P, const float* xyz, const float* dc, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw,
                          const uint8_t* grow, const uint8_t* protect, const uint32_t* tie_rank, float scaling_raw_split, gslic_alloc_fn scratch_alloc,
                          void* scratch_ctx, uint32_t* parent_index, int32_t* count, int32_t* count_split, void* stream)

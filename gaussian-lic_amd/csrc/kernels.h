@@ -214,6 +214,28 @@ struct ContribArgs {
 int launch_contribution(const ContribArgs& a, hipStream_t s, const float* err = nullptr, unsigned long long* err_sum = nullptr,
                         const float* near_bound = nullptr, unsigned long long* free_sum = nullptr, unsigned long long* meas_sum = nullptr);
 
+// contrib.hip: the per-pixel geometry images of gslic_geometry_images from a completed forward's lists (the same replay, one workgroup per tile, the
+// per-pixel results kept instead of reduced per Gaussian; arguments validated by the caller; any of the seven images may be NULL)
+struct GeometryArgs {
+    int W, H, gx, T, P;
+    uint32_t R;                       // as ContribArgs
+    const uint2* ranges;
+    const uint32_t* point_list;
+    const float4* rec;
+    const float4* pix_final;
+    const uint32_t* status;
+    float a_min;
+    float* transmittance;             // each [H*W] row-major
+    float* opacity;
+    float* depth_sum;
+    float* depth_norm;
+    float* depth_median;
+    int32_t* top_row;
+    float* top_weight;
+};
+// lists = false (P == 0 or R == 0: no list exists, the forward's buffers are not read): every pixel gets the rule's initial values
+int launch_geometry_images(const GeometryArgs& a, bool lists, hipStream_t s);
+
 // densify.hip: the clone / split rule of gslic_densify_select on the raw parameters -> parent_index / the two counts (one stream synchronisation),
 // and the new rows of gslic_densify_emit: the wide launch (copied fields, zeroed moments) and then one thread per parent (arguments validated by
 // the caller)

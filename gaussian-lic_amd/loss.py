@@ -162,7 +162,8 @@ def ssim(img1, img2, window_size=11, size_average=True):
     return ssim_map.mean() if size_average else ssim_map.mean(1).mean(1).mean(1)
 
 
-def evaluate_visual_quality(model, cameras, gt_images, bg, fused=True, weights=None, gt_depths=None, depth_weights=None):
+def evaluate_visual_quality(model, cameras, gt_images, bg, fused=True, weights=None, gt_depths=None, depth_weights=None, depth_kind="sum",
+                            depth_a_min=0.05):
     """PSNR / SSIM over a set of views — the metric part of evaluateVisualQuality (gaussian.cpp:751-789): render, clamp to [0,1],
     psnr + SSIM per image, averaged over the views.  fused=True evaluates the SSIM map with the fused-SSIM kernel
     (gslic_fusedssim_forward, train = 0: the same 11-tap sigma-1.5 window with zero padding as loss_utils.h:41-128, separable, one
@@ -172,14 +173,26 @@ def evaluate_visual_quality(model, cameras, gt_images, bg, fused=True, weights=N
     (window statistics over all pixels, as in the weighted training loss), in plain torch on top of the same map.
     gt_depths: one [H,W] depth target per view (or None per view; depth_weights likewise, optional): the views that have one are rendered with
     their depth and the result gains a third element, the dict of depth_metrics averaged over those views (float64 device scalars).  Without
-    gt_depths the result is the pair it always was."""
+    gt_depths the result is the pair it always was.
+    depth_kind: which rendered depth the metrics are taken of.  "sum" (the default): D = sum T alpha z, the image the depth loss trains on — biased
+    low wherever the accumulated opacity is below 1.  "normalised": D / A where the accumulated opacity A >= depth_a_min, 0 elsewhere; "median": the
+    view depth of the entry that takes the transmittance below one half (0: never reached) — both from trainer.geometry_images of the same view (one
+    more forward and one replay launch per view with a depth target; a pixel whose depth is 0 fails delta1 and counts its full error)."""
     from .rasterizer import render
+    kinds = {"sum": None, "normalised": "depth_norm", "median": "depth_median"}
+    if depth_kind not in kinds:
+        raise ValueError(f"evaluate_visual_quality: depth_kind must be one of {tuple(kinds)}, got {depth_kind!r}")
     ps, ss, dm = [], [], []
     with torch.no_grad():
         for i, (cam, gt) in enumerate(zip(cameras, gt_images)):
             gtd = None if gt_depths is None else gt_depths[i]
             if gtd is None:
                 img = torch.clamp(render(cam, model, bg)[0], 0.0, 1.0)
+            elif kinds[depth_kind] is not None:
+                from .trainer import geometry_images
+                img = torch.clamp(render(cam, model, bg)[0], 0.0, 1.0)
+                geo = geometry_images(model, cam, bg, a_min=depth_a_min, what=(kinds[depth_kind],))
+                dm.append(depth_metrics(geo[kinds[depth_kind]], gtd, None if depth_weights is None else depth_weights[i]))
             else:
                 out = render(cam, model, bg, return_depth=True)
                 img = torch.clamp(out[0], 0.0, 1.0)

@@ -603,6 +603,31 @@ def contribution_accumulate(P, H, W, R, B, geom, binning, img, w_min, max_w=None
                                                         bp(n_pix), bp(sum_w), _lib.current_stream_ptr()))
 
 
+GEOMETRY_IMAGES = ("transmittance", "opacity", "depth_sum", "depth_norm", "depth_median", "top_row", "top_weight")   # the argument order of the export
+
+
+def geometry_images(P, H, W, R, B, geom, binning, img, a_min, out):
+    """gslic_geometry_images: ONE view's per-pixel geometry, replayed from the buffers of a completed forward (rasterize_gaussians / _depth /
+    _capacity / _depth_capacity; R, B as that forward returned them), written into the caller's images.  out: a dict of contiguous device tensors
+    of H * W elements keyed by the names of GEOMETRY_IMAGES — float32, top_row int32; a name that is absent (or None) is not computed.  Every
+    pixel of every image given is written (a capacity forward whose status reports an overflow writes nothing).  The rule is written out in
+    include/gslic_hip.h.  One launch on the current stream, no allocation, no synchronisation."""
+    unknown = set(out) - set(GEOMETRY_IMAGES)
+    if unknown:
+        raise ValueError(f"geometry_images: unknown image(s) {sorted(unknown)}; the images are {GEOMETRY_IMAGES}")
+    ptrs = []
+    for name in GEOMETRY_IMAGES:
+        t = out.get(name)
+        dt = torch.int32 if name == "top_row" else torch.float32
+        if t is not None and not (torch.is_tensor(t) and t.is_contiguous() and t.dtype == dt and t.numel() == int(H) * int(W) and t.numel() > 0):
+            raise ValueError(f"geometry_images: {name} must be a contiguous {dt} tensor of {int(H)} x {int(W)} elements")
+        ptrs.append(None if t is None else ctypes.c_void_p(t.data_ptr()))
+    prm = _params(P, 0, 0, H, W, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, False, False, False)   # (only P, W and H are read)
+    bp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    _lib.check(_lib.lib().gslic_geometry_images(ctypes.byref(prm), int(R), int(B), bp(geom), bp(binning), bp(img), float(a_min), *ptrs,
+                                                _lib.current_stream_ptr()))
+
+
 def debug_export(settings, P, M, R, B, geom, binning, img, sample, what=("tiles_touched", "point_list", "ranges")):
     """Test-only: copy stage boundaries out of the opaque scratch buffers (gslic_debug_export)."""
     L = _lib.lib()

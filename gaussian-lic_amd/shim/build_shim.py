@@ -116,16 +116,17 @@ FUSED_CHECKS = {name: (os.path.join(HERE, name + "_check.cpp"), os.path.join(PKG
     "fused_rows",             # both statistics objects at once through densify, extend, prune and resort
     "fused_lidar_depth",      # the LiDAR range image (gslic::LidarDepth) feeding a depth-supervised step and the free-space statistics
     "fused_lidar_weight",     # ... its weight and dist2 images feeding the weighted depth step
+    "fused_geometry",         # the per-pixel geometry images (gslic::FusedStep::geometry_images)
 )}
 
 
 def build_fused_check(name="fused", force=False):
     """Builds the program `name` of FUSED_CHECKS (stale when its source, shim/fused_check_io.h, gslic_fused.h, gslic_hip.h or libgslic_hip.so is
-    newer) and returns the binary's path."""
+    newer) and returns the binary's path.  The "fused_" prefix may be left out: build_fused_check("geometry")."""
     import sysconfig
     import torch
     from torch.utils import cpp_extension
-    src, CHECK_FUSED = FUSED_CHECKS[name]
+    src, CHECK_FUSED = FUSED_CHECKS[name if name in FUSED_CHECKS else "fused_" + name]
     deps = [src, os.path.join(HERE, "fused_check_io.h"), os.path.join(HERE, "include", "gslic_fused.h"), os.path.join(PKG, "..", "include", "gslic_hip.h"),
             os.path.join(PKG, "libgslic_hip.so")]
     if not force and os.path.exists(CHECK_FUSED) and os.path.getmtime(CHECK_FUSED) > max(os.path.getmtime(p) for p in deps):

@@ -114,6 +114,31 @@ struct LidarImages {
     torch::Tensor weight;       // float32 [H,W]: range weight times 1 / (1 + falloff * dist2), 0 = none; a depth_weight as it is (only with weight)
     torch::Tensor dist2;        // int32 [H,W]: squared pixel distance to the return the pixel was given, -1 = none (only when asked for)
 };
+// The per-pixel geometry images of one view (gslic_geometry_images, include/gslic_hip.h) — what the Python host's trainer.geometry_images
+// returns: FusedStep::geometry_images writes the tensors that are DEFINED, each [H,W] on the map's device (float32, top_row int32); make()
+// allocates the ones asked for.  Tensors a caller keeps are reused by the next call of the same size: no allocation, capturable in a graph.
+struct GeometryImages {
+    torch::Tensor transmittance;   // the forward's final_T
+    torch::Tensor opacity;         // A = sum of w = alpha T
+    torch::Tensor depth_sum;       // D = sum of T alpha z (the depth the loss trains on)
+    torch::Tensor depth_norm;      // D / A where A >= a_min, 0 elsewhere
+    torch::Tensor depth_median;    // the view depth of the entry that takes T below one half, 0: never reached
+    torch::Tensor top_row;         // int32: the STORAGE row of the largest w, -1: no contributor
+    torch::Tensor top_weight;      // that w
+    std::array<torch::Tensor*, 7> all() { return {&transmittance, &opacity, &depth_sum, &depth_norm, &depth_median, &top_row, &top_weight}; }
+    // allocates (on demand: a tensor of the right size stays) the images whose flag is set, in the order of all()
+    void make(int64_t H, int64_t W, torch::Device device, std::array<bool, 7> want = {false, true, false, true, true, true, false})
+    {
+        const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(device);
+        const auto imgs = all();
+        for (int i = 0; i < 7; i++) {
+            torch::Tensor& t = *imgs[i];
+            if (!want[i]) { t = torch::Tensor(); continue; }
+            if (!t.defined() || t.size(0) != H || t.size(1) != W) t = torch::empty({H, W}, i == 5 ? f32.dtype(torch::kInt32) : f32);
+        }
+    }
+};
+
 class LidarDepth {
 public:
     LidarDepth(int width, int height, torch::Device device = torch::kCUDA) : W_(width), H_(height)
@@ -470,6 +495,33 @@ public:
                                                        reinterpret_cast<uint64_t*>(stats.free_sum.data_ptr<int64_t>()),
                                                        reinterpret_cast<uint64_t*>(stats.meas_sum.data_ptr<int64_t>()), current_stream()),
               "gslic_contribution_accumulate_free_space");
+    }
+    // The per-pixel geometry images of ONE view — the Python host's trainer.geometry_images: the statistics passes' raw-parameter forward (it
+    // reuses the step's scratch; call it between steps) and one gslic_geometry_images on its buffers.  The images written are the tensors of `out`
+    // that are defined (float32 [H,W] on the map's device, top_row int32, contiguous); an `out` with none gets the default set (opacity,
+    // depth_norm, depth_median, top_row) from GeometryImages::make.  a_min > 0 guards depth_norm's division.  The map and its moments are not touched.
+    void geometry_images(const FusedCamera& cam, GeometryImages& out, float a_min = 0.05f)
+    {
+        torch::NoGradGuard ng;
+        const int64_t P = prm_[0].size(0);
+        const int W = cam.image_width, H = cam.image_height;
+        auto imgs = out.all();
+        if (std::none_of(imgs.begin(), imgs.end(), [](const torch::Tensor* t) { return t->defined(); })) out.make(H, W, prm_[0].device());
+        void* ptr[7];
+        for (int i = 0; i < 7; i++) {
+            const torch::Tensor& t = *imgs[i];
+            TORCH_CHECK(!t.defined() || (t.numel() == (int64_t)H * W && t.is_contiguous() && t.device() == prm_[0].device() &&
+                                         t.scalar_type() == (i == 5 ? torch::kInt32 : torch::kFloat32)),
+                        "FusedStep::geometry_images: image ", i, " must be a contiguous ", i == 5 ? "int32" : "float32", " [", H, ", ", W, "] tensor on the map's device");
+            ptr[i] = t.defined() ? t.data_ptr() : nullptr;
+        }
+        TORCH_CHECK(!out.depth_norm.defined() || a_min > 0.0f, "FusedStep::geometry_images: a_min must be > 0 for depth_norm");
+        int32_t R = 0, B = 0;
+        const gslic_raster_params rp = P > 0 ? statistics_forward(cam, R, B) : raster_params(cam, true, false);
+        check(gslic_geometry_images(&rp, R, B, P > 0 ? cptr(scratch_[0]) : nullptr, P > 0 ? cptr(scratch_[1]) : nullptr, P > 0 ? cptr(scratch_[2]) : nullptr,
+                                    a_min, (float*)ptr[0], (float*)ptr[1], (float*)ptr[2], (float*)ptr[3], (float*)ptr[4], (int32_t*)ptr[5], (float*)ptr[6],
+                                    current_stream()),
+              "gslic_geometry_images");
     }
     // Clone / split densification on the device — the Python host's GaussianModel.densify (gaussian-lic_amd/trainer.py), same calls, same result:
     // ONE gslic_densify_select (which rows grow, and where their new rows go) and ONE gslic_densify_emit (the new rows of the 18 parameter and

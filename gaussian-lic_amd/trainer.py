@@ -942,6 +942,87 @@ class ContributionStats(_RowStatistics):
         return contribution_drop_mask(self.max_weight(), self.pixels(), max_weight_below, pixels_below)
 
 
+GEOMETRY_DEFAULT = ("opacity", "depth_norm", "depth_median", "top_row")
+
+
+@torch.no_grad()
+def geometry_images(model, camera, bg=None, a_min=0.05, what=GEOMETRY_DEFAULT, out=None):
+    """Per-pixel geometry of one view (gslic_geometry_images, include/gslic_hip.h) as a dict of [H, W] device tensors: renders `camera` (a forward
+    of its own, raw parameters, no autograd — the training step is not touched) and replays its lists.  what: any of "transmittance" (the
+    forward's final_T), "opacity" (A = sum of w = alpha T), "depth_sum" (render(return_depth=True)'s D = sum T alpha z), "depth_norm" (D / A where
+    A >= a_min, 0 elsewhere), "depth_median" (the view depth of the entry that takes T below one half; 0: never reached), "top_row" (int32: the
+    STORAGE row of the largest w, -1: no contributor) and "top_weight" (that w).  out: see geometry_images_from.  Which a_min to use and what to
+    do with the images is the host's policy."""
+    H, W = int(camera.image_height), int(camera.image_width)
+    if model.P == 0:   # nothing to render: the rule's initial values, from the same launch
+        from . import rasterizer as rz
+        res = _geometry_out(H, W, model.device, what, out)
+        rz.geometry_images(0, H, W, 0, 0, None, None, None, _geometry_a_min(a_min, res), res)
+        return res
+    bg = torch.zeros(3, device=model.device) if bg is None else bg
+    fwd = _RawRaster(model, camera, bg)
+    fwd.forward()
+    return geometry_images_from(fwd, a_min=a_min, what=what, out=out)
+
+
+def _geometry_a_min(a_min, res):
+    a_min = float(a_min)
+    if "depth_norm" in res and not a_min > 0.0:   # (a NaN fails)
+        raise ValueError(f"geometry_images: a_min must be > 0 for depth_norm, got {a_min!r}")
+    return a_min
+
+
+def _geometry_out(H, W, device, what, out):
+    """The dict of images a geometry call writes, one per name in `what`: out's tensors, or fresh ones."""
+    from . import rasterizer as rz
+    names = tuple(what)
+    unknown = set(names) - set(rz.GEOMETRY_IMAGES)
+    if unknown:
+        raise ValueError(f"geometry_images: unknown image(s) {sorted(unknown)}; the images are {rz.GEOMETRY_IMAGES}")
+    if out is not None:
+        missing = [n for n in names if out.get(n) is None]
+        if missing:
+            raise ValueError(f"geometry_images: out= has no tensor for {missing}")
+        return {n: out[n] for n in names}
+    return {n: torch.empty(H, W, dtype=torch.int32 if n == "top_row" else torch.float32, device=device) for n in names}
+
+
+@torch.no_grad()
+def geometry_images_from(fwd, a_min=0.05, what=GEOMETRY_DEFAULT, out=None):
+    """geometry_images of a forward the caller already has: a _RawRaster after forward() (training_step_fused's pieces) or the
+    rasterizer.CapacityBuffers a capacity forward filled (GraphedStep.bufs: the launch is sized from the capacities, stops at the real counts on
+    the device and writes NOTHING when the forward's status says the lists did not fit).  A colour-only and a depth forward give the same images.
+    out: a dict of preallocated contiguous [H, W] device tensors (float32, top_row int32) keyed by image name — the call then allocates nothing
+    and can sit in a captured graph; `what` names the images computed (each must be in out).  Returns the dict of images."""
+    from . import rasterizer as rz
+    if isinstance(fwd, rz.CapacityBuffers):
+        if fwd.no_color:
+            raise ValueError("geometry_images: a no_color forward stores no n_contrib")
+        P, H, W, R, B, geom, binning, img = fwd.P, fwd.H, fwd.W, fwd.cap_R, fwd.cap_B, fwd.geom, fwd.binning, fwd.img
+    else:
+        if fwd.state is None:
+            raise ValueError("geometry_images: run forward() on the _RawRaster first")
+        R, B, _radii, geom, binning, img, _sample = fwd.state
+        P, (H, W) = fwd.xyz.shape[0], fwd.hw
+    res = _geometry_out(int(H), int(W), geom.device, what, out)
+    rz.geometry_images(P, H, W, R, B, geom, binning, img, _geometry_a_min(a_min, res), res)
+    return res
+
+
+def rows_under(top_row, mask, P=None):
+    """bool [P]: the storage rows that own at least one pixel where `mask` is true — top_row: geometry_images' int32 [H, W] image, mask: bool (or
+    any tensor read as != 0) [H, W] on the same device; a pixel without a contributor (-1) names no row.  P: the number of rows (the model's P;
+    default: the largest row named + 1).  Plain torch; usable as it is as drop= / protect= of prune() and grow= / protect= of densify()."""
+    top_row, mask = torch.as_tensor(top_row), torch.as_tensor(mask)
+    if top_row.shape != mask.shape:
+        raise ValueError(f"rows_under: top_row is {tuple(top_row.shape)}, mask {tuple(mask.shape)}")
+    rows = top_row[(mask != 0) & (top_row >= 0)].long()
+    n = int(P) if P is not None else (int(top_row.max()) + 1 if top_row.numel() else 0)
+    owned = torch.zeros(max(n, 0), dtype=torch.bool, device=top_row.device)
+    owned[rows] = True
+    return owned
+
+
 def gradient_grow_mask(grad_sum, n_seen, grad_above, min_seen=1):
     """uint8 [P]: 1 where n_seen >= max(min_seen, 1) and grad_sum >= float32(grad_above) * float32(n_seen) — the 3DGS test "mean gradient >=
     threshold" without the division: comparisons and ONE float32 product, so the same expression in torch or numpy gives the same mask.  3DGS's

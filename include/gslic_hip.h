@@ -935,6 +935,46 @@ int gslic_contribution_accumulate_free_space(
     const float* near_bound /*[H,W]*/, uint64_t* free_sum /*[P]*/, uint64_t* meas_sum /*[P]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * gslic_geometry_images — per-PIXEL geometry of ONE view, from the buffers a completed forward filled (no reference counterpart): the
+ * accumulated opacity, the opacity-normalised and the median depth, and which Gaussian owns the pixel — what evaluation, mesh / TSDF export,
+ * occlusion tests of LiDAR points and 2-D masks turned into row masks need, none of which needs a gradient.  The same replay as
+ * gslic_contribution_accumulate, which keeps the per-pixel results instead of reducing them per Gaussian.  One launch, a pass of its own: the
+ * training step is not touched.  geom / binning / img, R and B: the contract of gslic_contribution_accumulate (colour or depth forwards, plain
+ * or capacity; a no_color forward stores no n_contrib: GSLIC_ERR_INVALID_ARG).
+ *
+ *  The rule.  For every pixel p of the image, with its tile's list e_0, e_1, ... (front to back) and its stored n_contrib[p]:
+ *      T = 1;  A = 0;  D = 0;  zmed = 0;  found = false;  top = -1;  wtop = 0
+ *      for the CONTRIBUTING pairs (p, e_k), k < n_contrib[p]   (the rule of gslic_contribution_accumulate: skip power > 0 and alpha < 1/255):
+ *          z = the float32 view depth in e_k's record (what the depth blend reads);   w = alpha T
+ *          D = D + (z alpha) T                                    (the strict depth forward's operation order)
+ *          A = A + w
+ *          if w > wtop:  wtop = w;  top = storage row of e_k      (strict >: the frontmost wins a tie)
+ *          T = T (1 - alpha)
+ *          if !found and T < 0.5:  zmed = z;  found = true        (the entry whose blending takes T below one half)
+ *      transmittance[p] = T;   opacity[p] = A;   depth_sum[p] = D;   depth_median[p] = zmed   (0: one half was never reached)
+ *      depth_norm[p] = A >= a_min ? D / A : 0                     (ONE IEEE float32 division; a_min > 0)
+ *      top_row[p] = top   (-1: no contributor);   top_weight[p] = wtop
+ *  The arithmetic is the strict forward's (absolute pixel coordinates, every product rounded on its own, hipcc's expf): on a strict forward's
+ *  buffers transmittance is that forward's final_T and depth_sum its depth image (gslic_rasterize_forward_depth), bit for bit, and the buffers
+ *  of a colour-only and of a depth forward give the same seven images.  There is NO fast-math variant: on the buffers of a fast-mode forward
+ *  (gslic_set_math_mode(0)) the kernel still replays in the strict arithmetic and honours that forward's n_contrib; the two arithmetics differ
+ *  by rounding, so a few pairs per million sit on the other side of alpha < 1/255 and are classified differently from what that forward did.
+ *  Outputs (DEVICE, each [H*W] row-major, each may be NULL): EVERY pixel of the image is written by the launch — no memset is needed — and a
+ *  pixel no list reaches gets the initial values (1, 0, 0, 0, 0, -1, 0).  top_row indexes STORAGE rows, like the contribution statistics.
+ *  Deterministic: a pixel's values depend on its own list only; no atomics, no cross-pixel arithmetic.
+ *  Capacity mode: the launch is sized from the image, the lists end at the real counts on the device, and NOTHING is written when the
+ *  forward's status words say the lists did not fit (what the backward does).  No host synchronisation, no allocation; capturable in a graph.
+ *  All seven outputs NULL returns at once.  P == 0 or R == 0: no list exists, the forward's buffers are not read (they may be NULL) and the
+ *  outputs given get the initial values.  Negative R / B, no_color, NULL buffers (P > 0 and R > 0) and — with a non-NULL depth_norm — an
+ *  a_min that is NaN or not > 0 are reported before any device work (GSLIC_ERR_INVALID_ARG, gslic_last_error).
+ */
+int gslic_geometry_images(
+    const gslic_raster_params* prm, int32_t R, int32_t B,
+    const char* geom_buffer, const char* binning_buffer, const char* img_buffer, float a_min,
+    float* transmittance, float* opacity, float* depth_sum, float* depth_norm, float* depth_median,
+    int32_t* top_row, float* top_weight /*each [H*W] or NULL*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * gslic_densify_select / gslic_densify_emit — clone / split densification on the device (no reference counterpart: its map grows from
  * LiDAR returns only; a LibTorch host would run 18 index + cat launches plus the rewrite of the split parents).  Which rows to grow
  * (`grow`, e.g. a threshold on err_sum) and when is the host's policy.

@@ -43,6 +43,13 @@ class GradStats(ctypes.Structure):
     _fields_ = [("grad_sum", ctypes.c_void_p), ("n_seen", ctypes.c_void_p), ("max_radius", ctypes.c_void_p)]
 
 
+class ExposureAdam(ctypes.Structure):
+    """gslic_exposure_adam: the [V,12] / [V] arrays of trainer.Exposure, the device word that names the view, torch.optim.Adam's scalars, and the
+    optional device word that turns the update off (device pointers)."""
+    _fields_ = [("param", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("step_count", ctypes.c_void_p), ("view", ctypes.c_void_p),
+                ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("skip", ctypes.c_void_p)]
+
+
 EXPORTS = [
     "gslic_rasterize_forward", "gslic_rasterize_backward", "gslic_rasterize_backward_adam", "gslic_rasterize_backward_camera", "gslic_adam_update", "gslic_adam_update_groups",
     "gslic_fusedssim_forward", "gslic_fusedssim_backward", "gslic_knn_mean_dist2", "gslic_abi_version",
@@ -63,6 +70,7 @@ EXPORTS = [
     "gslic_lidar_zbuffer_add", "gslic_lidar_zbuffer_resolve", "gslic_lidar_zbuffer_resolve_weighted",
     "gslic_depth_loss_weighted_partials_count", "gslic_depth_loss_weighted_forward_backward",
     "gslic_geometry_images",
+    "gslic_exposure_partials_count", "gslic_exposure_apply", "gslic_exposure_backward",
 ]
 
 _lib = None
@@ -102,6 +110,10 @@ def lib():
     L.gslic_depth_loss_weighted_partials_count.restype = ctypes.c_int64
     L.gslic_depth_loss_weighted_partials_count.argtypes = [i32, i32]
     L.gslic_depth_loss_weighted_forward_backward.argtypes = [i32, i32, f32, f32] + [vp] * 6 + [vp]   # H, W, lambda_depth, delta, depth, gt_depth, weight, partials, terms, dL_ddepth, stream
+    L.gslic_exposure_partials_count.restype = ctypes.c_int64
+    L.gslic_exposure_partials_count.argtypes = [i32, i32]
+    L.gslic_exposure_apply.argtypes = [i32, i32, vp, vp, vp, vp]   # H, W, E, image, out, stream
+    L.gslic_exposure_backward.argtypes = [i32, i32] + [vp] * 6 + [ctypes.POINTER(ExposureAdam), vp]   # H, W, E, image, dL_dout, dL_dimage, partials, dL_dE, adam, stream
     # the rasterize entry points, from the pieces their signatures share (include/gslic_hip.h)
     prm, counts, adam = ctypes.POINTER(RasterParams), [ctypes.POINTER(i32), ctypes.POINTER(i32)], ctypes.POINTER(AdamFused)
     inputs = [vp] * 12                                 # background ... cam_pos (the backward: radii in place of opacities)

@@ -1346,6 +1346,65 @@ int gslic_depth_loss_weighted_forward_backward(int32_t H, int32_t W, float lambd
     return depth_loss_weighted_forward_backward(H, W, lambda_depth, delta, depth, gt_depth, weight, partials, terms, dL_ddepth, (hipStream_t)stream);
 }
 
+int64_t gslic_exposure_partials_count(int32_t H, int32_t W) { return (H <= 0 || W <= 0) ? 12 : exposure_partials_count(H, W); }
+
+namespace {
+struct NamedRange { const void* p; size_t bytes; const char* name; };
+bool ranges_overlap(const NamedRange& x, const NamedRange& y)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
+    return a < b + y.bytes && b < a + x.bytes;
+}
+}  // namespace
+
+int gslic_exposure_apply(int32_t H, int32_t W, const float* E, const float* image, float* out, void* stream)
+{
+    const char* fn = "exposure apply";
+    if (H <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: H = %d is not positive", fn, H);
+    if (W <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: W = %d is not positive", fn, W);
+    const size_t img = 3 * (size_t)H * (size_t)W * sizeof(float);
+    const NamedRange o = {out, img, "out"}, in[2] = {{E, 12 * sizeof(float), "E"}, {image, img, "image"}};
+    for (const auto& a : {in[0], in[1], o})
+        if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, a.name);
+    for (const auto& a : in)
+        if (ranges_overlap(o, a)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: out overlaps %s", fn, a.name);
+    return exposure_apply(H, W, E, image, out, (hipStream_t)stream);
+}
+
+int gslic_exposure_backward(int32_t H, int32_t W, const float* E, const float* image, const float* dL_dout, float* dL_dimage, float* partials,
+                            float* dL_dE, const gslic_exposure_adam* adam, void* stream)
+{
+    const char* fn = "exposure backward";
+    if (H <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: H = %d is not positive", fn, H);
+    if (W <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: W = %d is not positive", fn, W);
+    const size_t img = 3 * (size_t)H * (size_t)W * sizeof(float), row = 12 * sizeof(float);
+    const NamedRange in[3] = {{E, row, "E"}, {image, img, "image"}, {dL_dout, img, "dL_dout"}};
+    const NamedRange outs[3] = {{dL_dimage, img, "dL_dimage"}, {dL_dE, row, "dL_dE"}, {partials, (size_t)exposure_partials_count(H, W) * sizeof(float), "partials"}};
+    for (const auto& a : in)
+        if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, a.name);
+    for (const auto& a : outs)
+        if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, a.name);
+    for (int i = 0; i < 3; i++) {
+        for (const auto& a : in)
+            if (ranges_overlap(outs[i], a)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s overlaps %s", fn, outs[i].name, a.name);
+        for (int j = 0; j < i; j++)
+            if (ranges_overlap(outs[i], outs[j])) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s overlaps %s", fn, outs[i].name, outs[j].name);
+    }
+    if (adam) {
+        const struct { const void* p; const char* name; } members[5] = {{adam->param, "param"}, {adam->m, "m"}, {adam->v, "v"}, {adam->step_count, "step_count"},
+                                                                        {adam->view, "view"}};
+        for (const auto& a : members)
+            if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: adam->%s is NULL", fn, a.name);
+        const struct { float x; const char* name; bool below_one; } values[4] = {{adam->lr, "lr", false}, {adam->beta1, "beta1", true}, {adam->beta2, "beta2", true},
+                                                                                 {adam->eps, "eps", false}};
+        for (const auto& a : values) {
+            if (!(a.x >= 0.0f)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: adam->%s = %g is NaN or negative", fn, a.name, (double)a.x);
+            if (a.below_one && !(a.x < 1.0f)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: adam->%s = %g must be below 1", fn, a.name, (double)a.x);
+        }
+    }
+    return exposure_backward(H, W, E, image, dL_dout, dL_dimage, partials, dL_dE, adam, (hipStream_t)stream);
+}
+
 int gslic_knn_mean_dist2(int32_t P, const float* points, float* mean_dists, gslic_alloc_fn scratch_alloc, void* scratch_ctx,
                          void* stream)
 {

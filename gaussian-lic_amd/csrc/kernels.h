@@ -245,4 +245,12 @@ int densify_select(int P, const float* xyz, const float* dc, const float* opacit
 int densify_emit(int P, int count, const uint32_t* parent_index, int M, float* const param[6], float* const exp_avg[6], float* const exp_avg_sq[6],
                  uint32_t* tie_rank, float split_above, uint32_t seed, hipStream_t s);
 
+// exposure.hip: the 3x4 affine exposure model of gslic_exposure_apply / gslic_exposure_backward (arguments validated by the caller).  The backward is
+// two launches: dL_dimage and one row of twelve partial sums per workgroup, then one workgroup that adds the rows, writes dL_dE and — adam != NULL —
+// applies the bias-corrected Adam update to the row *adam->view of the [V,12] arrays
+int64_t exposure_partials_count(int H, int W);
+int exposure_apply(int H, int W, const float* E, const float* image, float* out, hipStream_t s);
+int exposure_backward(int H, int W, const float* E, const float* image, const float* dL_dout, float* dL_dimage, float* partials, float* dL_dE,
+                      const gslic_exposure_adam* adam, hipStream_t s);
+
 }  // namespace gslic

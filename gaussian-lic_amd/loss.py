@@ -163,7 +163,7 @@ def ssim(img1, img2, window_size=11, size_average=True):
 
 
 def evaluate_visual_quality(model, cameras, gt_images, bg, fused=True, weights=None, gt_depths=None, depth_weights=None, depth_kind="sum",
-                            depth_a_min=0.05):
+                            depth_a_min=0.05, exposures=None, views=None):
     """PSNR / SSIM over a set of views — the metric part of evaluateVisualQuality (gaussian.cpp:751-789): render, clamp to [0,1],
     psnr + SSIM per image, averaged over the views.  fused=True evaluates the SSIM map with the fused-SSIM kernel
     (gslic_fusedssim_forward, train = 0: the same 11-tap sigma-1.5 window with zero padding as loss_utils.h:41-128, separable, one
@@ -177,8 +177,21 @@ def evaluate_visual_quality(model, cameras, gt_images, bg, fused=True, weights=N
     depth_kind: which rendered depth the metrics are taken of.  "sum" (the default): D = sum T alpha z, the image the depth loss trains on — biased
     low wherever the accumulated opacity is below 1.  "normalised": D / A where the accumulated opacity A >= depth_a_min, 0 elsewhere; "median": the
     view depth of the entry that takes the transmittance below one half (0: never reached) — both from trainer.geometry_images of the same view (one
-    more forward and one replay launch per view with a depth target; a pixel whose depth is 0 fails delta1 and counts its full error)."""
+    more forward and one replay launch per view with a depth target; a pixel whose depth is 0 fails delta1 and counts its full error).
+    exposures (a trainer.Exposure) with views (one row index per camera): the image that is scored is the exposure-compensated one,
+    clamp(E_view applied to the render) — what the training loss saw; the depth metrics are not touched.  By default the raw render is scored."""
     from .rasterizer import render
+    if (exposures is None) != (views is None):
+        raise ValueError("evaluate_visual_quality: exposures and views go together (one row index per camera)")
+    if views is not None and len(views) != len(cameras):
+        raise ValueError(f"evaluate_visual_quality: {len(views)} views for {len(cameras)} cameras")
+
+    def shown(rendered, i):
+        if exposures is None:
+            return torch.clamp(rendered, 0.0, 1.0)
+        rendered = rendered.contiguous()
+        return torch.clamp(exposure_apply(rendered, exposures.matrix(views[i]), torch.empty_like(rendered)), 0.0, 1.0)
+
     kinds = {"sum": None, "normalised": "depth_norm", "median": "depth_median"}
     if depth_kind not in kinds:
         raise ValueError(f"evaluate_visual_quality: depth_kind must be one of {tuple(kinds)}, got {depth_kind!r}")
@@ -187,15 +200,15 @@ def evaluate_visual_quality(model, cameras, gt_images, bg, fused=True, weights=N
         for i, (cam, gt) in enumerate(zip(cameras, gt_images)):
             gtd = None if gt_depths is None else gt_depths[i]
             if gtd is None:
-                img = torch.clamp(render(cam, model, bg)[0], 0.0, 1.0)
+                img = shown(render(cam, model, bg)[0], i)
             elif kinds[depth_kind] is not None:
                 from .trainer import geometry_images
-                img = torch.clamp(render(cam, model, bg)[0], 0.0, 1.0)
+                img = shown(render(cam, model, bg)[0], i)
                 geo = geometry_images(model, cam, bg, a_min=depth_a_min, what=(kinds[depth_kind],))
                 dm.append(depth_metrics(geo[kinds[depth_kind]], gtd, None if depth_weights is None else depth_weights[i]))
             else:
                 out = render(cam, model, bg, return_depth=True)
-                img = torch.clamp(out[0], 0.0, 1.0)
+                img = shown(out[0], i)
                 dm.append(depth_metrics(out[5], gtd, None if depth_weights is None else depth_weights[i]))
             gt = torch.clamp(gt, 0.0, 1.0)                      # gaussian.cpp:759
             w = None if weights is None else weights[i]
@@ -247,6 +260,63 @@ def l1_ssim_loss(image, gt, lambda_dssim=0.2, weight=None):
     return _L1SsimLoss.apply(image, gt, float(lambda_dssim), weight.detach())
 
 
+def _exposure_args(image, E):
+    if image.dim() != 3 or image.size(0) != 3 or image.dtype != torch.float32 or not image.is_contiguous():
+        raise ValueError("exposure: the image must be a contiguous float32 [3,H,W] tensor")
+    if E.numel() != 12 or E.dtype != torch.float32 or E.device != image.device or not E.is_contiguous():
+        raise ValueError("exposure: E must be 12 contiguous float32 values ([3,4]) on the image's device")
+    return int(image.size(1)), int(image.size(2))
+
+
+def exposure_apply(image, E, out):
+    """gslic_exposure_apply: out_c = ((E[c,0] r + E[c,1] g) + E[c,2] b) + E[c,3] on a planar [3,H,W] image, every step one float32 operation."""
+    H, W = _exposure_args(image, E)
+    p = _lib.ptr
+    _lib.check(_lib.lib().gslic_exposure_apply(H, W, p(E), p(image), p(out), _lib.current_stream_ptr()))
+    return out
+
+
+def exposure_backward(image, E, dL_dout, dL_dimage, partials, dL_dE, adam=None):
+    """gslic_exposure_backward: dL_dimage = E^T dL_dout and dL_dE [3,4] (twelve fixed-order sums over the pixels of dL_dout x [image | 1]) in two
+    launches; adam (a _lib.ExposureAdam or None): the second launch also applies torch-style Adam to the row the descriptor names."""
+    H, W = _exposure_args(image, E)
+    if tuple(dL_dout.shape) != tuple(image.shape) or dL_dout.dtype != torch.float32 or not dL_dout.is_contiguous():
+        raise ValueError("exposure: dL_dout must be a contiguous float32 tensor of the image's shape")
+    import ctypes
+    p = _lib.ptr
+    _lib.check(_lib.lib().gslic_exposure_backward(H, W, p(E), p(image), p(dL_dout), p(dL_dimage), p(partials), p(dL_dE),
+                                                  None if adam is None else ctypes.byref(adam), _lib.current_stream_ptr()))
+    return dL_dimage
+
+
+class _ApplyExposure(torch.autograd.Function):
+    """gslic_exposure_apply / gslic_exposure_backward as one autograd node with gradients to the image and to E."""
+
+    @staticmethod
+    def forward(ctx, image, E):
+        img3 = image.detach().reshape(image.shape[-3:]).contiguous()
+        E12 = E.detach().contiguous()
+        ctx.save_for_backward(img3, E12)
+        ctx.shapes = (image.shape, E.shape)
+        return exposure_apply(img3, E12, torch.empty_like(img3)).reshape(image.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        img3, E12 = ctx.saved_tensors
+        g3 = g.reshape(img3.shape).contiguous()
+        dL_dimage, dL_dE = torch.empty_like(img3), torch.empty(12, device=img3.device)
+        partials = torch.empty(int(_lib.lib().gslic_exposure_partials_count(img3.shape[1], img3.shape[2])), device=img3.device)
+        exposure_backward(img3, E12, g3, dL_dimage, partials, dL_dE)
+        return dL_dimage.reshape(ctx.shapes[0]), dL_dE.reshape(ctx.shapes[1])
+
+
+def apply_exposure(image, E):
+    """The exposure-compensated image E[:, :3] @ rgb + E[:, 3] of a rendered [3,H,W] (or [1,3,H,W]) image, differentiable in both arguments: for the
+    autograd training_step and for a host that builds its own graph (`E` its own [3,4] leaf with its own optimiser, as the reference's exposure_
+    and exposure_optimizer_).  Forward and backward are the two exports; the values are theirs bit for bit."""
+    return _ApplyExposure.apply(image, E)
+
+
 class FusedLoss:
     """loss = (1-lambda) * L1 + lambda * (1 - SSIM) of optimize() (gaussian.cpp:685-691) computed by two kernels
     (gslic_l1_ssim_loss_forward / _backward) with no LibTorch elementwise ops and no autograd graph; with LiDAR depth supervision
@@ -260,6 +330,7 @@ class FusedLoss:
         self._terms = None
         self._wshape, self._wbuf = None, None
         self._dwshape, self._dwbuf = None, None
+        self._eshape, self._ebuf = None, None
 
     def _terms_buf(self, device):
         if self._terms is None or self._terms.device != device:
@@ -363,6 +434,29 @@ class FusedLoss:
         _lib.check(L.gslic_l1_ssim_loss_forward_backward(1, CH, H, W, C1, C2, self.lambda_dssim, p(image), p(gt), p(d1), p(d2), p(d3), p(partials),
                                                          p(terms), p(dL), _lib.current_stream_ptr()))
         return dL, terms
+
+    def _exposure_scratch(self, img):
+        if self._eshape != tuple(img.shape) or self._ebuf[0].device != img.device:
+            n = int(_lib.lib().gslic_exposure_partials_count(img.shape[1], img.shape[2]))
+            self._ebuf = [torch.empty_like(img), torch.empty_like(img), torch.empty(n, device=img.device)]
+            self._eshape = tuple(img.shape)
+        return self._ebuf
+
+    def exposure_apply(self, image, E):
+        """image [3,H,W], E 12 device floats ([3,4], e.g. a row of trainer.Exposure.params): the exposure-compensated image, in a scratch image kept
+        here (gslic_exposure_apply, one launch)."""
+        image = image.contiguous()
+        out = self._exposure_scratch(image)[0]
+        exposure_apply(image, E, out)
+        return out
+
+    def exposure_backward(self, image, E, dL_dout, dL_dE, adam=None):
+        """The other half: dL/dimage = E^T dL_dout into a scratch image kept here (returned), dL/dE into dL_dE [3,4]; adam: a _lib.ExposureAdam —
+        the second launch then also updates the row it names (gslic_exposure_backward, two launches)."""
+        image = image.contiguous()
+        _out, dL_dimage, partials = self._exposure_scratch(image)
+        exposure_backward(image, E, dL_dout, dL_dimage, partials, dL_dE, adam)
+        return dL_dimage
 
     def value(self, terms, lambda_depth=0.0):
         """The loss from the terms: [mean L1, mean SSIM] or, with lambda_depth != 0, [mean L1, mean SSIM, L_d]."""

@@ -139,6 +139,45 @@ struct GeometryImages {
     }
 };
 
+// Trainable per-view exposure — the Python host's trainer.Exposure: one 3x4 affine colour transform per view (which views share a row is the
+// host's policy), applied to the rendered image before the loss (gslic_exposure_apply / gslic_exposure_backward, include/gslic_hip.h).  The
+// reference's host owns such a tensor with an Adam of its own (gaussian.cpp:287-291, :419-422, :708-711) and never applies it; n_views = 1 is
+// that tensor.  params [V,3,4] starts at [I | 0]; m, v and steps [V] int32 are torch::optim::Adam's state (bias-corrected), grad [3,4] the last
+// dL/dE.  Handed to FusedStep::set_exposure, step() updates the view's row inside the exposure backward's second launch.
+struct Exposure {
+    torch::Tensor params, m, v;   // float32 [V,3,4]
+    torch::Tensor steps;          // int32 [V]
+    torch::Tensor grad;           // float32 [3,4]
+    torch::Tensor views;          // int32 [V] = 0 .. V-1: the device word that names view i is views[i]
+    float lr, beta1, beta2, eps;
+    Exposure(int64_t n_views, torch::Device device = torch::kCUDA, float lr_ = 0.01f, float beta1_ = 0.9f, float beta2_ = 0.999f, float eps_ = 1e-8f)
+        : lr(lr_), beta1(beta1_), beta2(beta2_), eps(eps_)
+    {
+        TORCH_CHECK(n_views >= 1, "Exposure: n_views must be at least 1");
+        const auto fo = torch::TensorOptions().dtype(torch::kFloat32).device(device);
+        params = torch::eye(3, 4, fo).unsqueeze(0).repeat({n_views, 1, 1}).contiguous();
+        m = torch::zeros_like(params); v = torch::zeros_like(params);
+        steps = torch::zeros({n_views}, fo.dtype(torch::kInt32));
+        grad = torch::zeros({3, 4}, fo);
+        views = torch::arange(n_views, fo.dtype(torch::kInt32));
+    }
+    int64_t n_views() const { return params.size(0); }
+    torch::Tensor matrix(int64_t view) const   // the [3,4] transform of a view: a view into params
+    {
+        TORCH_CHECK(view >= 0 && view < n_views(), "Exposure: view ", view, " is outside [0, ", n_views(), ")");
+        return params[view];
+    }
+    gslic_exposure_adam descriptor(int64_t view) const
+    {
+        matrix(view);
+        gslic_exposure_adam ad{};
+        ad.param = params.data_ptr<float>(); ad.m = m.data_ptr<float>(); ad.v = v.data_ptr<float>(); ad.step_count = steps.data_ptr<int32_t>();
+        ad.view = views.data_ptr<int32_t>() + view;
+        ad.lr = lr; ad.beta1 = beta1; ad.beta2 = beta2; ad.eps = eps;
+        return ad;
+    }
+};
+
 class LidarDepth {
 public:
     LidarDepth(int width, int height, torch::Device device = torch::kCUDA) : W_(width), H_(height)
@@ -262,6 +301,17 @@ public:
     {
         gstats_ = stats;
         if (gstats_) fit_rows(gstats_->rows());
+    }
+    // From here on step() and pose_gradient() take the loss of the exposure-compensated image: E = exposure->matrix(view) applied into a scratch
+    // image (gslic_exposure_apply), the loss calls unchanged on that image, then gslic_exposure_backward, which hands the rasteriser's backward
+    // E^T dL/dout and leaves dL/dE in exposure->grad; step() also updates the row by torch-style Adam in that call's second launch, pose_gradient()
+    // updates nothing.  The calls of the Python host's training_step_fused(exposure=, view=).  The depth image is not touched.  The object must
+    // outlive the step or be taken off with nullptr, which is the step as it always was.
+    void set_exposure(Exposure* exposure, int view = 0)
+    {
+        if (exposure) exposure->matrix(view);
+        exposure_ = exposure;
+        exposure_view_ = view;
     }
     // A host that keeps the map's rows in a PERMUTED order (e.g. sorted along a space-filling curve so that what a view sees is contiguous in
     // memory) passes the rows' ORIGINAL indices (device int32 [P]): the forward then lists Gaussians of equal depth in the original order, as the
@@ -765,6 +815,26 @@ private:
                                                    dLd.data_ptr<float>(), current_stream()),
               "gslic_depth_l1_loss_forward_backward");
     }
+    // the exposure model around the colour loss: E of the attached view applied into ex_image_ (returned), and the backward that turns the loss's
+    // dL/dout into dL (= E^T dL/dout) and exposure_->grad, with the row's Adam update when asked for
+    const torch::Tensor& exposure_apply(int H, int W, const torch::Tensor& image)
+    {
+        if (!ex_image_.defined() || ex_image_.size(1) != H || ex_image_.size(2) != W) {
+            auto fo = prm_[0].options().requires_grad(false);
+            ex_image_ = torch::empty({3, H, W}, fo);
+            ex_dL_ = torch::empty({3, H, W}, fo);
+            ex_partials_ = torch::empty({gslic_exposure_partials_count(H, W)}, fo);
+        }
+        check(gslic_exposure_apply(H, W, f(exposure_->matrix(exposure_view_)), f(image), ex_image_.data_ptr<float>(), current_stream()), "gslic_exposure_apply");
+        return ex_image_;
+    }
+    void exposure_backward(int H, int W, const torch::Tensor& image, const torch::Tensor& dL_dout, torch::Tensor& dL, bool adam)
+    {
+        const gslic_exposure_adam ad = exposure_->descriptor(exposure_view_);
+        check(gslic_exposure_backward(H, W, f(exposure_->matrix(exposure_view_)), f(image), f(dL_dout), dL.data_ptr<float>(), ex_partials_.data_ptr<float>(),
+                                      exposure_->grad.data_ptr<float>(), adam ? &ad : nullptr, current_stream()),
+              "gslic_exposure_backward");
+    }
     static void check_targets(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor* gt_depth)
     {
         const int W = cam.image_width, H = cam.image_height;
@@ -858,7 +928,12 @@ private:
         torch::Tensor terms = torch::empty({depth ? 3 : 2}, fo);
         int32_t R = 0, B = 0;
         forward(rp, cam, f(prm_[3]), f(prm_[4]), f(prm_[5]), image_, final_T_, depth ? &depth_ : nullptr, radii_, R, B);
-        colour_loss(H, W, image_, gt_image, weight, dm_, partials_, terms, dL_dimage_);
+        if (exposure_) {
+            colour_loss(H, W, exposure_apply(H, W, image_), gt_image, weight, dm_, partials_, terms, ex_dL_);
+            exposure_backward(H, W, image_, ex_dL_, dL_dimage_, /*adam=*/true);
+        } else {
+            colour_loss(H, W, image_, gt_image, weight, dm_, partials_, terms, dL_dimage_);
+        }
         if (depth) depth_loss(H, W, lambda_depth, depth_, *gt_depth, depth_partials_, terms, dL_ddepth_, dlo);
         backward_adam(rp, cam, R, B, depth);
         return terms;
@@ -885,7 +960,13 @@ private:
         for (int i = 0; i < 6; i++) g[i] = torch::empty_like(prm_[i], fo);
         int32_t R = 0, B = 0;
         forward(rp, cam, f(prm_[3]), f(prm_[4]), f(prm_[5]), image, final_T, depth ? &zimg : nullptr, radii, R, B);
-        colour_loss(H, W, image, gt_image, weight, dm, partials, terms, dL, /*two_calls=*/!depth);
+        if (exposure_) {
+            torch::Tensor dLo = torch::empty({3, H, W}, fo);
+            colour_loss(H, W, exposure_apply(H, W, image), gt_image, weight, dm, partials, terms, dLo);   // (the fused pair, as the Python host's)
+            exposure_backward(H, W, image, dLo, dL, /*adam=*/false);
+        } else {
+            colour_loss(H, W, image, gt_image, weight, dm, partials, terms, dL, /*two_calls=*/!depth);
+        }
         if (depth) depth_loss(H, W, lambda_depth, zimg, *gt_depth, dpartials, terms, dLd, dlo);
         backward_camera(rp, cam, R, B, radii, dL, dLd, g, camg.data_ptr<float>());
         if (terms_out) *terms_out = terms;
@@ -1033,6 +1114,9 @@ private:
     int64_t sorted_P_ = 0, n_resorts_ = 0;                          // rows [0, sorted_P_) are in Morton order; resort() calls so far
     torch::Tensor last_perm_;                                       // the last resort()'s permutation
     GradientStats* gstats_ = nullptr;                               // set_gradient_stats: accumulated by step(), carried by the row changes
+    Exposure* exposure_ = nullptr;                                  // set_exposure: applied and updated by step(), applied by pose_gradient()
+    int exposure_view_ = 0;
+    torch::Tensor ex_image_, ex_dL_, ex_partials_;                  // exposure: the compensated image, the loss's gradient w.r.t. it, the partial sums
 };
 
 }  // namespace gslic

@@ -11,7 +11,10 @@
 // Differences a caller could observe, both deliberate:
 //   * std::get<2> (screenspace_points) is a zero-stride [P,3] view of one zero row, not a fresh requires_grad tensor: no caller of render()
 //     reads it or its gradient (gaussian.cpp:506,683,757,797).  -DGSLIC_RENDER_SCREENSPACE_TENSOR restores the dense zeros.
-//   * use_trained_exposure is ignored exactly as in the reference (renderer.cpp never reads it).
+//   * use_trained_exposure = true with a defined pc->exposure_ ([3,4], gaussian.cpp:287-291) APPLIES it: the image returned is
+//     exposure_[:, :3] @ rgb + exposure_[:, 3] (gslic_exposure_apply) and loss.backward() leaves dL/dexposure in exposure_.grad() for the host's
+//     exposure_optimizer_ (gslic_exposure_backward) — what the reference's host asks for and its render() never does (renderer.cpp:25).  The
+//     default, false, and an undefined exposure_ are the render without it, call for call.
 // Image, final_T, radii and the six parameter gradients equal the reference path's up to fp32 rounding of the activation chain
 // (tests/test_shim_gpu.py::test_dropin_renderer_cpp).
 #include "renderer.h"   // the reference's header (src/rasterizer/renderer.h): Camera, GaussianModel, the render() declaration
@@ -111,6 +114,33 @@ struct RawRasterize : public torch::autograd::Function<RawRasterize> {
     }
 };
 
+// gslic_exposure_apply / gslic_exposure_backward as one autograd node: gradients to the image and to the [3,4] exposure
+struct ApplyExposure : public torch::autograd::Function<ApplyExposure> {
+    static torch::Tensor forward(AutogradContext* ctx, torch::Tensor image, torch::Tensor E)
+    {
+        TORCH_CHECK(image.dim() == 3 && image.size(0) == 3 && E.numel() == 12, "exposure: image [3,H,W] and a [3,4] exposure expected");
+        image = image.contiguous(); E = E.contiguous();
+        torch::Tensor out = torch::empty_like(image, image.options().requires_grad(false));
+        check(gslic_exposure_apply((int32_t)image.size(1), (int32_t)image.size(2), fp(E), fp(image), out.data_ptr<float>(), gslic::current_stream()),
+              "gslic_exposure_apply");
+        ctx->save_for_backward({image, E});
+        return out;
+    }
+    static tensor_list backward(AutogradContext* ctx, tensor_list grad_outputs)
+    {
+        auto sv = ctx->get_saved_variables();
+        const torch::Tensor &image = sv[0], &E = sv[1];
+        const int32_t H = (int32_t)image.size(1), W = (int32_t)image.size(2);
+        auto fo = image.options().requires_grad(false);
+        torch::Tensor g = grad_outputs[0].contiguous(), dL = torch::empty_like(image, fo), dE = torch::empty({3, 4}, fo);
+        torch::Tensor partials = torch::empty({gslic_exposure_partials_count(H, W)}, fo);
+        check(gslic_exposure_backward(H, W, fp(E), fp(image), fp(g), dL.data_ptr<float>(), partials.data_ptr<float>(), dE.data_ptr<float>(), nullptr,
+                                      gslic::current_stream()),
+              "gslic_exposure_backward");
+        return {dL, dE.reshape(E.sizes())};
+    }
+};
+
 }  // namespace
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
@@ -121,7 +151,6 @@ render(const std::shared_ptr<Camera>& viewpoint_camera,
        bool no_color,
        float scaling_modifier)
 {
-    (void)use_trained_exposure;
     const float tanfovx = std::tan(viewpoint_camera->FoVx_ * 0.5f);   // renderer.cpp:31-32
     const float tanfovy = std::tan(viewpoint_camera->FoVy_ * 0.5f);
     auto res = RawRasterize::apply(pc->xyz_, pc->features_dc_, pc->features_rest_, pc->opacity_, pc->scaling_, pc->rotation_, bg_color,
@@ -130,6 +159,8 @@ render(const std::shared_ptr<Camera>& viewpoint_camera,
                                    (double)viewpoint_camera->limx_neg_, (double)viewpoint_camera->limx_pos_, (double)viewpoint_camera->limy_neg_,
                                    (double)viewpoint_camera->limy_pos_, (double)scaling_modifier, (int64_t)pc->sh_degree_, no_color, (double)pc->lambda_erank_);
     torch::Tensor rendered_image = res[0], radii = res[1], rendered_final_T = res[2];
+    // (the reference's model holds an EMPTY exposure_ until its training setup has run, gaussian.h:100: that is "no exposure" too)
+    if (use_trained_exposure && pc->exposure_.defined() && pc->exposure_.numel() == 12 && !no_color) rendered_image = ApplyExposure::apply(rendered_image, pc->exposure_);
 #ifdef GSLIC_RENDER_SCREENSPACE_TENSOR
     torch::Tensor screenspace_points = torch::zeros_like(pc->xyz_, pc->xyz_.options().requires_grad(true));
 #else

@@ -16,4 +16,5 @@ public:
     double lambda_dssim_ = 0.2;
     bool apply_exposure_ = false;
     torch::Tensor xyz_, features_dc_, features_rest_, scaling_, rotation_, opacity_;
+    torch::Tensor exposure_;   // [3,4], [I | 0] with requires_grad in the reference (gaussian.cpp:287-291); undefined here unless a program sets it
 };

@@ -1372,9 +1372,126 @@ class _RawRaster:
                             sample, self.lambda_erank, **modes)
 
 
-def _fused_losses(fl, image, gt_image, depth, gt_depth, lambda_depth, weight=None, depth_weight=None, depth_huber=0.0):
+class Exposure:
+    """Trainable per-view exposure: one 3x4 affine colour transform per view (or per group of views — which views share a row is the host's
+    policy), applied to the rendered image before the loss: out_c = E[c,:3] . rgb + E[c,3] (gslic_exposure_apply; the rule is written out in
+    include/gslic_hip.h).  The reference's host owns such a tensor — [I | 0] with an Adam of its own at exposure_lr, stepped after every view
+    (gaussian.cpp:287-291, :419-422, :708-711) — and never applies it; n_views=1 is that single tensor.
+    params [V,3,4] starts at [I | 0]; m, v [V,3,4] and steps [V] int32 are torch.optim.Adam's state (WITH bias correction, unlike the map's sparse
+    Adam); grad [3,4] holds the last dL/dE a step computed.  The fused steps update the row inside the exposure backward's second launch
+    (gslic_exposure_backward with its Adam descriptor); nothing here allocates or synchronises per step."""
+
+    def __init__(self, n_views, device, lr=0.01, betas=(0.9, 0.999), eps=1e-8):
+        V = int(n_views)
+        if V < 1:
+            raise ValueError(f"Exposure: n_views = {n_views} must be at least 1")
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        if not (self.lr >= 0.0 and 0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0 and self.eps >= 0.0):
+            raise ValueError(f"Exposure: lr = {lr}, betas = {betas}, eps = {eps} must be >= 0 and the betas below 1")
+        self.device = torch.device(device)
+        self.params = torch.zeros(V, 3, 4, dtype=torch.float32, device=self.device)
+        self.m, self.v = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        self.steps = torch.zeros(V, dtype=torch.int32, device=self.device)
+        self.grad = torch.zeros(3, 4, dtype=torch.float32, device=self.device)
+        self._views = torch.arange(V, dtype=torch.int32, device=self.device)   # the device word that names view i is _views[i]: no copy per step
+        self.reset()
+
+    @property
+    def n_views(self):
+        return self.params.size(0)
+
+    def _index(self, view):
+        v = int(view)
+        if not 0 <= v < self.n_views:
+            raise IndexError(f"Exposure: view {view} is outside [0, {self.n_views})")
+        return v
+
+    def matrix(self, view=0):
+        """The [3,4] transform of a view: a view into `params` (no copy)."""
+        return self.params[self._index(view)]
+
+    def reset(self, view=None):
+        """Back to [I | 0] with zero moments and step count: one view, or all of them."""
+        rows = slice(None) if view is None else slice(self._index(view), self._index(view) + 1)
+        self.params[rows] = torch.eye(3, 4, dtype=torch.float32, device=self.device)
+        self.m[rows] = 0
+        self.v[rows] = 0
+        self.steps[rows] = 0
+        if view is None:
+            self.grad.zero_()
+
+    def state_dict(self):
+        return dict(params=self.params.clone(), m=self.m.clone(), v=self.v.clone(), steps=self.steps.clone(), lr=self.lr, betas=self.betas, eps=self.eps)
+
+    def load_state_dict(self, state):
+        if tuple(state["params"].shape) != tuple(self.params.shape):
+            raise ValueError(f"Exposure: the state holds {tuple(state['params'].shape)}, this object {tuple(self.params.shape)}")
+        self.params.copy_(state["params"]); self.m.copy_(state["m"]); self.v.copy_(state["v"]); self.steps.copy_(state["steps"])
+        self.lr, self.betas, self.eps = float(state["lr"]), (float(state["betas"][0]), float(state["betas"][1])), float(state["eps"])
+
+    def clone(self):
+        other = Exposure(self.n_views, self.device, self.lr, self.betas, self.eps)
+        other.load_state_dict(self.state_dict())
+        other.grad.copy_(self.grad)
+        return other
+
+    def _descriptor(self, view_word, skip=None):
+        """gslic_exposure_adam on this object's arrays; view_word: a device int32 [1] that names the row, skip: the optional device word."""
+        from . import _lib
+        p = lambda t: t.data_ptr()
+        return _lib.ExposureAdam(p(self.params), p(self.m), p(self.v), p(self.steps), p(view_word), self.lr, self.betas[0], self.betas[1], self.eps,
+                                 None if skip is None else p(skip))
+
+    def adam_step(self, view, grad):
+        """torch.optim.Adam's step on one row from a gradient the caller has (the autograd training_step, as the reference's torch::optim::Adam
+        of exposure_ does it: LibTorch ops, bias terms in double).  The fused steps do not come here: their update is inside the backward kernel."""
+        i = self._index(view)
+        t = int(self.steps[i].item()) + 1
+        b1, b2 = self.betas
+        g = grad.detach().to(self.params.dtype).reshape(3, 4)
+        self.m[i].mul_(b1).add_(g, alpha=1.0 - b1)
+        self.v[i].mul_(b2).addcmul_(g, g, value=1.0 - b2)
+        denom = (self.v[i].sqrt() / math.sqrt(1.0 - b2 ** t)).add_(self.eps)
+        self.params[i].addcdiv_(self.m[i], denom, value=-self.lr / (1.0 - b1 ** t))
+        self.steps[i] = t
+
+
+def _check_exposure(who, exposure, view):
+    """The checks every step makes on its exposure= argument (None passes): an Exposure on the image's device, one GPU, a view it has."""
+    if exposure is None:
+        return None
+    if not isinstance(exposure, Exposure):
+        raise ValueError(f"{who}: exposure must be a trainer.Exposure")
+    if _dist_on():
+        raise NotImplementedError(f"{who}: exposure is single-GPU only: the N > 1 gradient exchange carries no exposure gradient (every rank would "
+                                  "update its own copy of E from its own view)")
+    exposure._index(view)
+    return exposure
+
+
+def _exposure_losses(fl, image, gt_image, depth, gt_depth, lambda_depth, weight, depth_weight, depth_huber, exposure, view, exposure_step):
+    """_fused_losses under an exposure model: E applied into a scratch image of the FusedLoss, the loss calls — unchanged — on that image, then
+    the exposure backward on their dL/dimage, which hands the rasteriser E^T g, leaves dL/dE in exposure.grad and (exposure_step) updates the
+    view's row by Adam in its second launch.  The depth image is not touched.  view: the row's index, or GraphedStep's (E [12], the device word
+    that names the row, the device word that turns the update off)."""
+    if isinstance(view, tuple):
+        E, word, skip = view
+    else:
+        i = exposure._index(view)
+        E, word, skip = exposure.params[i], exposure._views[i:i + 1], None
+    out = fl.exposure_apply(image, E)
+    dL_dout, dL_ddepth, terms = _fused_losses(fl, out, gt_image, depth, gt_depth, lambda_depth, weight, depth_weight, depth_huber)
+    dL_dimage = fl.exposure_backward(image, E, dL_dout, exposure.grad, exposure._descriptor(word, skip) if exposure_step else None)
+    return dL_dimage, dL_ddepth, terms
+
+
+def _fused_losses(fl, image, gt_image, depth, gt_depth, lambda_depth, weight=None, depth_weight=None, depth_huber=0.0, exposure=None, view=0,
+                  exposure_step=True):
     """The colour loss kernels (weight [H,W]: the weighted ones) and, for a depth image, the depth loss kernels (depth_weight [H,W] / depth_huber:
-    the weighted ones): (dL/dimage, dL/ddepth or None, terms)."""
+    the weighted ones): (dL/dimage, dL/ddepth or None, terms).  exposure (a trainer.Exposure) / view: the same calls on the exposure-compensated
+    image, between gslic_exposure_apply and gslic_exposure_backward (_exposure_losses); None is exactly the calls below."""
+    if exposure is not None:
+        return _exposure_losses(fl, image, gt_image, depth, gt_depth, lambda_depth, weight, depth_weight, depth_huber, exposure, view, exposure_step)
     if depth is None:
         dL_dimage, terms = fl.forward_backward(image, gt_image, weight)
         return dL_dimage, None, terms
@@ -1490,7 +1607,7 @@ def allreduce_gradients(grads, visible):
 
 
 def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_step=True, raw_render=None, one_node_loss=False, gt_depth=None,
-                  lambda_depth=0.0, weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0):
+                  lambda_depth=0.0, weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0, exposure=None, view=0):
     """One iteration of optimize()'s loop (gaussian.cpp:674-716) the way the reference's host writes it: render -> 0.8*L1 + 0.2*(1-SSIM) ->
     loss.backward() -> sparse Adam, on LibTorch autograd.  Returns (loss tensor, visible mask).
     raw_render: passed to render() — None = its default (the drop-in renderer: activations inside the kernels), False = renderer.cpp as written
@@ -1505,14 +1622,22 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
     node writes out — and radii are added to it by one small kernel (GradientStats.accumulate_from); the step itself is unchanged.
     depth_weight [H,W] / depth_huber (with gt_depth; not in the reference): the depth term becomes depth_l1(depth, gt_depth, depth_weight, depth_huber),
     the per-pixel weighted mean (NaN, negative and +inf weights read as 0, no clamp at 1) of the smooth-L1 of the residual with threshold depth_huber
-    (0 = L1); None and 0 are exactly the unweighted term."""
+    (0 = L1); None and 0 are exactly the unweighted term.
+    exposure (a trainer.Exposure; single GPU) / view: the loss is taken of loss.apply_exposure(image, E_view) — one more autograd node, on
+    gslic_exposure_apply / _backward — which is what the reference's host asks for with apply_exposure and never gets; exposure.grad is then dL/dE
+    and do_step also steps E_view by torch.optim.Adam's rule (Exposure.adam_step, as the reference's exposure_optimizer_).  The depth image is not
+    touched.  None is exactly the step without it."""
     use_depth = _use_depth("training_step", gt_depth, lambda_depth, depth_weight, depth_huber)
+    exposure = _check_exposure("training_step", exposure, view)
     grad_stats = _grad_stats_for_step(grad_stats, model)
     m2d = {} if grad_stats is None else dict(mean2d_grad_out=grad_stats._mean2d_buffer())
     if use_depth:
         image, _final_T, _pts, visible, _radii, depth = render(camera, model, bg, raw=raw_render, return_depth=True, **m2d)
     else:
         image, _final_T, _pts, visible, _radii = render(camera, model, bg, raw=raw_render, **m2d)
+    if exposure is not None:
+        E = exposure.matrix(view).detach().clone().requires_grad_(True)
+        image = loss_utils.apply_exposure(image, E)
     if one_node_loss:
         loss = loss_utils.l1_ssim_loss(image, gt_image, lambda_dssim, weight)
     elif weight is not None:
@@ -1528,6 +1653,10 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
     if use_depth:
         loss = loss + lambda_depth * loss_utils.depth_l1(depth, gt_depth, depth_weight, depth_huber)
     loss.backward()
+    if exposure is not None:
+        exposure.grad.copy_(E.grad)
+        if do_step:
+            exposure.adam_step(view, E.grad)
     if grad_stats is not None:
         grad_stats.accumulate_from(_pts.grad if _pts.grad is not None else m2d["mean2d_grad_out"], _radii)
     if do_step:
@@ -1541,7 +1670,8 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
     return loss.detach(), visible
 
 
-def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None, depth_weight=None, depth_huber=0.0):
+def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None, depth_weight=None, depth_huber=0.0,
+                  exposure=None, view=0):
     """dL/dxi of the training loss w.r.t. a left se(3) increment of the camera pose (Camera.pose_gradient) for the current map: forward -> loss
     kernels -> gslic_rasterize_backward_camera -> the chain.  The map is not touched.  Returns (float64 [6] = (d/drho, d/dphi), terms).
     One step of pose refinement is `camera.apply_pose_increment(-lr * g); camera.to_device(dev)`.
@@ -1549,19 +1679,22 @@ def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, l
     gradient its share — depth forward -> colour and depth loss kernels -> gslic_rasterize_backward_depth_camera -> the same chain; terms is
     then [mean L1, mean SSIM, L_d].  gt_depth=None or lambda_depth=0 is exactly the colour-only path.
     weight [H,W]: the weighted colour loss (FusedLoss.forward_backward); it combines freely with gt_depth.
-    depth_weight [H,W] / depth_huber: the weighted / Huber depth term, as training_step_fused's."""
+    depth_weight [H,W] / depth_huber: the weighted / Huber depth term, as training_step_fused's.
+    exposure / view: the loss of the exposure-compensated image, as training_step_fused's; exposure.grad is written, E is not updated."""
     fl = fused_loss or _default_fused_loss()
     use_depth = _use_depth("pose_gradient", gt_depth, lambda_depth, depth_weight, depth_huber)
+    exposure = _check_exposure("pose_gradient", exposure, view)
     with torch.no_grad():
         rr = _RawRaster(model, camera, bg, use_depth)
         image, depth, _radii = rr.forward()
-        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber)
+        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber,
+                                                    exposure, view, False)
         out = rr.backward(dL_dimage, dL_ddepth, camera_grads=True)
     return camera.pose_gradient(out[9], out[10], out[11]), terms
 
 
 def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None, grad_stats=None,
-                            depth_weight=None, depth_huber=0.0):
+                            depth_weight=None, depth_huber=0.0, exposure=None, view=0):
     """One joint map + pose iteration: forward -> loss kernels -> gslic_rasterize_backward_camera (parameter gradients AND the camera gradient in
     one pass) -> masked Adam on the map -> `camera` moved by -pose_lr * dL/dxi (left se(3) increment; 35 floats cross to the host, which is the
     step's only synchronisation).  Returns (terms, visible, dL/dxi).
@@ -1569,9 +1702,11 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
     gslic_rasterize_backward_depth_camera); the map update equals training_step_fused(gt_depth=...)'s, terms is [mean L1, mean SSIM, L_d].
     gt_depth=None or lambda_depth=0 is exactly the colour-only step.  weight [H,W]: the weighted colour loss, as training_step_fused's.
     grad_stats (a GradientStats of this model): the backward also writes dL_dmeans2D, which one small kernel adds to the statistics.
-    depth_weight [H,W] / depth_huber: the weighted / Huber depth term, as training_step_fused's."""
+    depth_weight [H,W] / depth_huber: the weighted / Huber depth term, as training_step_fused's.
+    exposure / view: the exposure model of the view, applied and updated as training_step_fused's."""
     fl = fused_loss or _default_fused_loss()
     use_depth = _use_depth("training_step_with_pose", gt_depth, lambda_depth, depth_weight, depth_huber)
+    exposure = _check_exposure("training_step_with_pose", exposure, view)
     grad_stats = _grad_stats_for_step(grad_stats, model)
     cam = camera
     with torch.no_grad():
@@ -1579,7 +1714,8 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
             _grad_slab(model)   # (the depth step sets the slab up ahead of its forward, the colour step behind its loss: both as they were)
         rr = _RawRaster(model, cam, bg, use_depth)
         image, depth, radii = rr.forward()
-        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber)
+        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber,
+                                                    exposure, view)
         slab = _grad_slab(model)
         if grad_stats is None:
             out = rr.backward(dL_dimage, dL_ddepth, out=slab.views, camera_grads=True)
@@ -1596,7 +1732,7 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
 
 
 def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=True, adam_in_backward=True, gt_depth=None, lambda_depth=0.0,
-                        weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0):
+                        weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0, exposure=None, view=0):
     """The same iteration as training_step — identical arithmetic up to fp32 rounding — on the fused entry points
     (SURVEY.md §8f row 2): sigmoid / exp / normalize and their backward run inside preprocess / preprocess_bwd (raw_params),
     the loss and dL/dimage come from two loss kernels, and there is no autograd graph: 0 LibTorch elementwise launches per step
@@ -1618,7 +1754,16 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
     gslic_depth_loss_weighted_forward_backward in place of the two of the unweighted call, plus a 4-byte copy.  NaN, negative and +inf weights read
     as 0 and there is NO clamp at 1 (unlike `weight`); a pixel of weight 0 is an unmeasured pixel; FusedLoss.depth_weight_sum is the sum of the
     weights.  `weight` does not reach the depth term and depth_weight does not reach the colour terms.  depth_weight=None with depth_huber=0 is
-    exactly today's depth step, launch for launch.  Without gt_depth they raise; single GPU only, like gt_depth."""
+    exactly today's depth step, launch for launch.  Without gt_depth they raise; single GPU only, like gt_depth.
+    exposure (a trainer.Exposure) / view (the row of it this view uses): the loss is taken of the exposure-compensated image — gslic_exposure_apply
+    into a scratch image of the FusedLoss, the loss calls above unchanged on that image, then gslic_exposure_backward, which hands the rasteriser's
+    backward E^T dL/dout, leaves dL/dE in exposure.grad and, in its second launch, steps the view's row by torch-style Adam (bias-corrected, as the
+    reference's exposure optimiser): three more launches per step.  It combines freely with weight, gt_depth, depth_weight, depth_huber and
+    grad_stats; the depth image is not touched, and the SSIM statistics see the compensated image.  do_step=False computes exposure.grad and
+    updates nothing.  Single GPU only: under the N > 1 exchange it raises NotImplementedError, because the exchange carries no exposure gradient
+    (each rank would step its own copy of E from its own view and the replicas would part).  exposure=None is exactly today's step, launch for
+    launch."""
+    exposure = _check_exposure("training_step_fused", exposure, view)
     fl = fused_loss or _default_fused_loss()
     if (depth_weight is not None or depth_huber) and _dist_on():
         raise NotImplementedError("training_step_fused with depth supervision is single-GPU only: the N > 1 gradient exchange (rank1 / slab "
@@ -1635,7 +1780,8 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
     with torch.no_grad():
         rr = _RawRaster(model, cam, bg, use_depth)
         image, depth, radii = rr.forward()
-        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber)
+        dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber,
+                                                    exposure, view, do_step)
         if do_step and adam_in_backward and not _dist_on():
             # single GPU: nothing to exchange, so the Adam update runs inside the per-Gaussian backward kernel while the
             # gradients are still in registers / LDS (bit-identical to backward + SparseGaussianAdam.step, ~2 GB less HBM traffic);
@@ -1746,10 +1892,16 @@ class GraphedStep:
     depth_weight [H,W] / depth_huber (with gt_depth and lambda_depth != 0): the step runs the weighted / Huber depth loss
     (training_step_fused(depth_weight=, depth_huber=)).  depth_weight lives in a static buffer exactly as `weight` does and is replaced through
     step(depth_weight=...) under the same checks; a step built without one raises when it is handed one.  depth_huber is an argument of the kernels
-    inside the step and so fixed when the step is built."""
+    inside the step and so fixed when the step is built.
+
+    exposure (a trainer.Exposure) / view: the step runs training_step_fused(exposure=, view=)'s calls.  Which row a step uses is a device int32 that
+    step(view=...) fills (None = the one that is loaded), so a captured graph changes views without being re-captured: the step first gathers the
+    row into a fixed 12-float buffer (one index_select launch, inside the step), applies it from there, and the exposure backward's second launch
+    updates the row the word names.  A step that did not fit its buffers updates no row either (the descriptor's skip word is the forward's
+    status word) and is repeated with its own view.  Eager and captured runs issue the same calls."""
 
     def __init__(self, model, camera, gt_image, bg, headroom=1.25, check_every=16, cap_R=None, cap_B=None, use_graph=False, gt_depth=None,
-                 lambda_depth=0.0, weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0):
+                 lambda_depth=0.0, weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0, exposure=None, view=0):
         """use_graph=False (default since round 5): the capacity-mode step (caller-owned scratch, no host round trip, overflow checks and repeats as
         below) issued as eager launches; use_graph=True: captured in a hipGraph and replayed with one launch per step.  The two are equally fast at
         2M Gaussians (bench.py: `capacity_eager` / `graphed`; the host runs ahead of the device either way), and the eager form has no hazard:
@@ -1778,6 +1930,11 @@ class GraphedStep:
         self.use_weight = weight is not None
         self.weight = weight.detach().float().contiguous().clone() if self.use_weight else None
         self.fl = loss_utils.FusedLoss(LAMBDA_DSSIM)
+        self.exposure = _check_exposure("GraphedStep", exposure, view)
+        if self.exposure is not None:
+            self._ex_E = torch.empty(1, 12, dtype=torch.float32, device=dev)                  # the row the step applies, gathered inside the step
+            self._ex_view = torch.full((1,), int(view), dtype=torch.int32, device=dev)       # which row: filled by _load
+            self._ex_view_host = int(view)
         self.e = torch.empty(0, device=dev)
         # sizes from one eager forward of the current state
         with torch.no_grad():
@@ -1799,8 +1956,13 @@ class GraphedStep:
     def _eager(self):
         rr = _RawRaster(self.model, self.cam, self.bg, self.use_depth, e=self.e, pose=(self.view, self.proj, self.campos))
         image, depth, _radii = rr.forward(self.bufs)
+        if self.exposure is None:
+            ex_view = 0
+        else:
+            torch.index_select(self.exposure.params.view(-1, 12), 0, self._ex_view, out=self._ex_E)
+            ex_view = (self._ex_E.view(12), self._ex_view, self.bufs.status[2:3])
         dL_dimage, dL_ddepth, self.terms = _fused_losses(self.fl, image, self.gt, depth, self.gt_depth, self.lambda_depth, self.weight, self.depth_weight,
-                                                         self.depth_huber)
+                                                         self.depth_huber, self.exposure, ex_view)
         if self._gstat is None:
             rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad)
         else:
@@ -1820,6 +1982,8 @@ class GraphedStep:
         saved = [(self.model._buf[n][:self.model.P].clone(), self.model._m[n][:self.model.P].clone(), self.model._v[n][:self.model.P].clone())
                  for n in names]
         saved_stats = [] if self.grad_stats is None else [a.clone() for a, _w in self.grad_stats._arrays()]   # (the two passes are no views of the host's)
+        ex = self.exposure
+        saved_ex = None if ex is None else [(a, a.clone()) for a in (ex.params, ex.m, ex.v, ex.steps, ex.grad)]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s), torch.no_grad():
@@ -1836,6 +2000,8 @@ class GraphedStep:
             self.model._buf[n][:self.model.P].copy_(p); self.model._m[n][:self.model.P].copy_(m1); self.model._v[n][:self.model.P].copy_(m2)
         for (a, _w), keep in zip(self.grad_stats._arrays() if saved_stats else (), saved_stats):
             a.copy_(keep)
+        for a, keep in saved_ex or ():
+            a.copy_(keep)
         self.bufs.status.zero_()
         self.graph = g
         self.steps_issued = 0
@@ -1850,9 +2016,15 @@ class GraphedStep:
         device between two replays)."""
         return (camera.world_view_transform.copy(), camera.full_proj_transform.copy(), camera.camera_center.copy())
 
-    def _load(self, camera, gt_image, gt_depth=None, weight=None, depth_weight=None):
+    def _load(self, camera, gt_image, gt_depth=None, weight=None, depth_weight=None, view=None):
         """Refresh the static buffers the captured step reads.  The pose is copied on every call that names a camera (the same Camera object
         may have been moved in place since it was loaded last)."""
+        if view is not None:
+            if self.exposure is None:
+                raise ValueError("GraphedStep: view given to a step built without an exposure (pass exposure to the constructor)")
+            if self.exposure._index(view) != self._ex_view_host:
+                self._ex_view_host = self.exposure._index(view)
+                self._ex_view.fill_(self._ex_view_host)
         if weight is False:   # "this step runs without a weight": true only of a step that was built without one
             if self.use_weight:
                 raise ValueError("GraphedStep: this step was built with a weight and always runs the weighted loss (pass ones to weigh every pixel "
@@ -1890,13 +2062,13 @@ class GraphedStep:
             self.gt.copy_(gt_image)
             self._gt_serial = getattr(self, "_gt_serial", 0) + 1
 
-    def _snapshot(self, gt_image, gt_depth=None, weight=None, depth_weight=None):
+    def _snapshot(self, gt_image, gt_depth=None, weight=None, depth_weight=None, view=None):
         """What a repeat of this step needs, independent of what the caller does to its objects afterwards: the pose by VALUE (host copies of the
         35 floats that are loaded now) and the target by reference together with the evidence that it is still the same data (the tensor's
         version counter; for gt_image=None — "the target that is loaded" — the serial number of the load)."""
         if getattr(self, "_pose_host", None) is None:
             self._pose_host = self._pose_of(self.cam)
-        return dict(pose=self._pose_host, gt=gt_image, gt_version=None if gt_image is None else gt_image._version, gt_serial=getattr(self, "_gt_serial", 0),
+        return dict(view=getattr(self, "_ex_view_host", None), pose=self._pose_host, gt=gt_image, gt_version=None if gt_image is None else gt_image._version, gt_serial=getattr(self, "_gt_serial", 0),
                     gtd=gt_depth, gtd_version=None if gt_depth is None else gt_depth._version, gtd_serial=getattr(self, "_gtd_serial", 0),
                     w=weight, w_version=None if weight is None else weight._version, w_serial=getattr(self, "_w_serial", 0),
                     dw=depth_weight, dw_version=None if depth_weight is None else depth_weight._version, dw_serial=getattr(self, "_dw_serial", 0))
@@ -1906,6 +2078,8 @@ class GraphedStep:
         v, p, c = snap["pose"]
         self.view.copy_(torch.from_numpy(v).to(dev)); self.proj.copy_(torch.from_numpy(p).to(dev)); self.campos.copy_(torch.from_numpy(c).to(dev))
         self._pose_host = snap["pose"]
+        if self.exposure is not None and snap.get("view") is not None:
+            self._load(None, None, view=snap["view"])
         gt = snap["gt"]
         if gt is None:
             if snap["gt_serial"] != getattr(self, "_gt_serial", 0):
@@ -1972,11 +2146,11 @@ class GraphedStep:
             with torch.no_grad():
                 self._eager()
 
-    def step(self, camera=None, gt_image=None, gt_depth=None, weight=None, depth_weight=None):
+    def step(self, camera=None, gt_image=None, gt_depth=None, weight=None, depth_weight=None, view=None):
         """One optimiser step (replay).  Returns the device tensor [mean L1, mean SSIM] of this step's loss terms ([mean L1, mean SSIM, L_d]
         with depth supervision; gt_depth: this step's depth target, None = the one that is loaded; weight: this step's weight image, likewise;
-        depth_weight: this step's depth weight image, likewise)."""
-        self._load(camera, gt_image, gt_depth, weight, depth_weight)
+        depth_weight: this step's depth weight image, likewise; view: the row of the exposure this step applies and updates, likewise)."""
+        self._load(camera, gt_image, gt_depth, weight, depth_weight, view)
         self._issue()
         self.steps_issued += 1
         if len(self.window) < 32:

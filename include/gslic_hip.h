@@ -638,6 +638,53 @@ int gslic_depth_loss_weighted_forward_backward(
     int32_t H, int32_t W, float lambda_depth, float delta, const float* depth, const float* gt_depth, const float* weight /*or NULL*/,
     float* partials, float* terms /*[2] device*/, float* dL_ddepth, void* stream);
 
+/* gslic_exposure_apply / gslic_exposure_backward — the per-view exposure model: a 3x4 affine colour transform E applied to the rendered image before
+ * the loss, and its gradient (additive, ABI 8; the reference creates, optimises and never applies such a tensor: gaussian.cpp:287-291, renderer.cpp:25).
+ * image, out, dL_dout, dL_dimage: planar [3,H,W] float DEVICE; E: 12 floats DEVICE, row-major [3,4] (E[c,k] at 4 c + k).  Every product and sum
+ * below is ONE IEEE float32 operation rounded on its own, in the order the parentheses give (no contraction).  With x = (r, g, b) the pixel of `image`
+ * and g_c the pixel of dL_dout in channel c:
+ *   out_c       = ((E[c,0] * r + E[c,1] * g) + E[c,2] * b) + E[c,3]                                    gslic_exposure_apply
+ *   dL_dimage_k = ((E[0,k] * g_0 + E[1,k] * g_1) + E[2,k] * g_2)                                        gslic_exposure_backward, k = 0..2
+ *   dL_dE[c,k]  = sum over the pixels p of g_c(p) * x_k(p)  (k < 3),   dL_dE[c,3] = sum over p of g_c(p)     x is `image`, the model's INPUT
+ * Order of the twelve sums, a function of H * W alone (not of the device's CU count, not of the pointers): workgroups of 2048 consecutive pixels;
+ * thread t of 256 adds, onto +0, the products of its pixels 4 (t + 256 j) + e in the order j = 0, 1 and e = 0 .. 3 within j (pixels at or past
+ * H * W add nothing); the 256 thread sums go through a xor-shuffle tree (distances 32 ... 1) per 64 lanes and (r0 + r1) + (r2 + r3) over the four
+ * waves; workgroup b stores its twelve sums as row b of `partials`.  A second launch of ONE workgroup adds the rows: thread t takes the rows t,
+ * t + 256, ... in that order, then the same tree.  No atomics: dL_dE has the same bits on every run and every device, whatever `partials` held
+ * before.  `partials`: DEVICE scratch of gslic_exposure_partials_count(H, W) floats (12 per workgroup).  Each call reads and writes every pixel
+ * once — 24 and 36 bytes per pixel — with 16-byte accesses (dword-aligned ones unless H * W % 4 == 0 and the images are 16-byte aligned; the one
+ * group of four that crosses the end of the image pixel by pixel); apply is one launch, backward two; no allocation, no host synchronisation, no
+ * read-back: capturable in a graph.
+ *
+ * adam (optional): the second launch also updates E in place — row *view of the [V,12] / [V] DEVICE arrays, *view read ON THE DEVICE so that a
+ * captured graph can change views — by torch.optim.Adam's rule WITH bias correction (what the reference's torch::optim::Adam of exposure_ applies;
+ * NOT the map's uncorrected sparse Adam), per element with g = dL_dE[c,k]:
+ *   t = step_count[view] + 1, stored back;   b1 = 1 - beta1^t,  b2 = 1 - beta2^t      in DOUBLE from the integer t (beta as the float given)
+ *   s = (float)(lr / b1),  q = (float)sqrt(b2)                                        in double, each rounded to float once
+ *   m = beta1 * m + (1 - beta1) * g,   v = beta2 * v + ((1 - beta2) * g) * g,   p = p - (s * m) / (sqrtf(v) / q + eps)       float32, as written
+ * A host that applies E of the row the update will change passes E = param + 12 * view to both calls (a POINTER, not a view index: the first
+ * launch of the backward reads E before the second one updates it).  skip (optional): a DEVICE word, e.g. &status[2] of the capacity-mode forward
+ * whose image this is — when one of its bits 1 | 2 | 8 | 16 is set (that forward did not complete, the step is a no-op) nothing is updated; dL_dE
+ * is still written.
+ * GSLIC_ERR_INVALID_ARG before any device work, naming the argument, for H or W <= 0, a NULL E / image / out (apply) or E / image / dL_dout /
+ * dL_dimage / partials / dL_dE (backward), an `out` that overlaps image or E, a dL_dimage or dL_dE that overlaps E, image or dL_dout (or each
+ * other), an Adam descriptor with a NULL param / m / v / step_count / view, and one whose lr, beta1, beta2 or eps is NaN or negative or whose
+ * beta1 or beta2 is >= 1. */
+typedef struct gslic_exposure_adam {
+    float* param;              /* [V,12] */
+    float* m;                  /* [V,12] exp_avg */
+    float* v;                  /* [V,12] exp_avg_sq */
+    int32_t* step_count;       /* [V] */
+    const int32_t* view;       /* [1] the row to update */
+    float lr, beta1, beta2, eps;
+    const uint32_t* skip;      /* optional [1]: see above */
+} gslic_exposure_adam;
+int64_t gslic_exposure_partials_count(int32_t H, int32_t W);
+int gslic_exposure_apply(int32_t H, int32_t W, const float* E /*[12] device*/, const float* image, float* out, void* stream);
+int gslic_exposure_backward(
+    int32_t H, int32_t W, const float* E /*[12] device*/, const float* image, const float* dL_dout, float* dL_dimage, float* partials,
+    float* dL_dE /*[12] device*/, const gslic_exposure_adam* adam /*or NULL*/, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * gslic_knn_mean_dist2 — replaces SimpleKNN::knn (src/simple-knn/simple_knn.cu:185-221) behind distCUDA2
  * (src/simple-knn/spatial.cu:15-26): mean_dists[i] = mean of the 3 smallest squared distances from point i

@@ -71,6 +71,7 @@ EXPORTS = [
     "gslic_depth_loss_weighted_partials_count", "gslic_depth_loss_weighted_forward_backward",
     "gslic_geometry_images",
     "gslic_exposure_partials_count", "gslic_exposure_apply", "gslic_exposure_backward",
+    "gslic_keyframe_decode", "gslic_keyframe_encode",
 ]
 
 _lib = None
@@ -114,6 +115,8 @@ def lib():
     L.gslic_exposure_partials_count.argtypes = [i32, i32]
     L.gslic_exposure_apply.argtypes = [i32, i32, vp, vp, vp, vp]   # H, W, E, image, out, stream
     L.gslic_exposure_backward.argtypes = [i32, i32] + [vp] * 6 + [ctypes.POINTER(ExposureAdam), vp]   # H, W, E, image, dL_dout, dL_dimage, partials, dL_dE, adam, stream
+    L.gslic_keyframe_decode.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp]   # W, H, level, color_slab, mask_slab, frame, n_frames, out, weight_out, stream
+    L.gslic_keyframe_encode.argtypes = [i32, i32, vp, vp, vp, vp, i32, i32, vp]        # W, H, image, mask, color_slab, mask_slab, capacity, slot, stream
     # the rasterize entry points, from the pieces their signatures share (include/gslic_hip.h)
     prm, counts, adam = ctypes.POINTER(RasterParams), [ctypes.POINTER(i32), ctypes.POINTER(i32)], ctypes.POINTER(AdamFused)
     inputs = [vp] * 12                                 # background ... cam_pos (the backward: radii in place of opacities)

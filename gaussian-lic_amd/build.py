@@ -32,6 +32,7 @@ SOURCES = {
     "ssim.hip": ["-ffp-contract=off"],   # the maps are held bit-exact to the reference kernels under the same flag (tests/golden/ssim_*.npz)
     "depth_loss.hip": [],    # its two kernels pin their own rounding (fp contract(off)): the gradient is held to autograd's bits
     "exposure.hip": ["-ffp-contract=off"],   # the 3x4 exposure model: every product and sum of the rule rounded on its own, apply and dL_dimage tested on bits
+    "keyframes.hip": ["-ffp-contract=off"],  # the keyframe store: integer sums and one float multiply (decode), one product rounded on its own (encode), tested on bits
     "knn.hip": [],
     "extend.hip": ["-ffp-contract=off"],  # pixel assignment decides integers: canonical order like preprocess.hip
     "prune.hip": [],         # comparisons and copies only: no arithmetic a flag could change

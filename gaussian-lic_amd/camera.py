@@ -106,6 +106,25 @@ class Camera:
         self.set_pose(R_new.T, -R_new.T @ t_new)
         return self
 
+    MAX_LEVEL = 4   # GSLIC_KEYFRAME_MAX_LEVEL of include/gslic_hip.h
+
+    def at_level(self, level):
+        """This camera at pyramid level l of the keyframe store (the rule is written out in include/gslic_hip.h): a NEW Camera of W >> l by H >> l
+        pixels with fx, fy, cx, cy divided by 2^l (exact in float32) and the same pose, znear and zfar.  The continuous image coordinate
+        u = fx x / z + cx spans [0, W), so it is halved with the image: a point's level-l pixel is floor(pixel_0 / 2^l).  A camera that has device
+        copies (to_device) hands the new one copies on the same device.  Level 0 is a copy."""
+        l = int(level)
+        if not 0 <= l <= self.MAX_LEVEL:
+            raise ValueError(f"Camera.at_level: level = {level} is outside [0, {self.MAX_LEVEL}]")
+        W, H = self.image_width >> l, self.image_height >> l
+        if W < 1 or H < 1:
+            raise ValueError(f"Camera.at_level: a {self.image_width} x {self.image_height} image has no level {l}")
+        s = np.float32(2.0 ** -l)
+        cam = Camera(W, H, self.fx * s, self.fy * s, self.cx * s, self.cy * s, self.R_wc, self.t_wc, self.znear, self.zfar)
+        if hasattr(self, "d_world_view_transform"):
+            cam.to_device(self.d_world_view_transform.device)
+        return cam
+
     def to_device(self, device):
         """Attach device copies of the three tensors the rasterizer reads (camera.h:86,109,60-61 keep them on CUDA)."""
         import torch

@@ -1405,6 +1405,50 @@ int gslic_exposure_backward(int32_t H, int32_t W, const float* E, const float* i
     return exposure_backward(H, W, E, image, dL_dout, dL_dimage, partials, dL_dE, adam, (hipStream_t)stream);
 }
 
+static bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
+
+int gslic_keyframe_decode(int32_t W, int32_t H, int32_t level, const uint8_t* color_slab, const uint8_t* mask_slab, const int32_t* frame,
+                          int32_t n_frames, float* out, float* weight_out, void* stream)
+{
+    const char* fn = "keyframe decode";
+    if (W <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: W = %d is not positive", fn, W);
+    if (H <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: H = %d is not positive", fn, H);
+    if (level < 0 || level > GSLIC_KEYFRAME_MAX_LEVEL)
+        return set_error(GSLIC_ERR_INVALID_ARG, "%s: level = %d is outside [0, %d]", fn, level, GSLIC_KEYFRAME_MAX_LEVEL);
+    if ((W >> level) == 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: W_l = %d >> %d is 0", fn, W, level);
+    if ((H >> level) == 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: H_l = %d >> %d is 0", fn, H, level);
+    if (n_frames < 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: n_frames = %d is negative", fn, n_frames);
+    const struct { const void* p; const char* name; } ptrs[3] = {{color_slab, "color_slab"}, {frame, "frame"}, {out, "out"}};
+    for (const auto& a : ptrs)
+        if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, a.name);
+    if (mask_slab && !weight_out) return set_error(GSLIC_ERR_INVALID_ARG, "%s: weight_out is NULL (a mask_slab was given)", fn);
+    const struct { const void* p; const char* name; } al[4] = {{out, "out"}, {mask_slab ? weight_out : nullptr, "weight_out"}, {color_slab, "color_slab"},
+                                                               {mask_slab, "mask_slab"}};
+    for (const auto& a : al)
+        if (!aligned_to(a.p, 16)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is not 16-byte aligned", fn, a.name);
+    return keyframe_decode(W, H, level, color_slab, mask_slab, frame, n_frames, out, weight_out, (hipStream_t)stream);
+}
+
+int gslic_keyframe_encode(int32_t W, int32_t H, const float* image, const float* mask, uint8_t* color_slab, uint8_t* mask_slab, int32_t capacity,
+                          int32_t slot, void* stream)
+{
+    const char* fn = "keyframe encode";
+    if (W <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: W = %d is not positive", fn, W);
+    if (H <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: H = %d is not positive", fn, H);
+    if (capacity <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: capacity = %d is not positive", fn, capacity);
+    if (slot < 0 || slot >= capacity) return set_error(GSLIC_ERR_INVALID_ARG, "%s: slot = %d is outside [0, %d)", fn, slot, capacity);
+    if (!image && !mask) return set_error(GSLIC_ERR_INVALID_ARG, "%s: image and mask are both NULL", fn);
+    if (image && !color_slab) return set_error(GSLIC_ERR_INVALID_ARG, "%s: color_slab is NULL (an image was given)", fn);
+    if (mask && !mask_slab) return set_error(GSLIC_ERR_INVALID_ARG, "%s: mask_slab is NULL (a mask was given)", fn);
+    if (!aligned_to(image, 4)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: image is not 4-byte aligned", fn);
+    if (!aligned_to(mask, 4)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: mask is not 4-byte aligned", fn);
+    if (image && !aligned_to(color_slab, 16)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: color_slab is not 16-byte aligned", fn);
+    if (mask && !aligned_to(mask_slab, 16)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: mask_slab is not 16-byte aligned", fn);
+    const size_t pix = (size_t)H * (size_t)W;
+    return keyframe_encode(W, H, image, mask, image ? color_slab + (size_t)slot * pix * 3 : nullptr, mask ? mask_slab + (size_t)slot * pix : nullptr,
+                           (hipStream_t)stream);
+}
+
 int gslic_knn_mean_dist2(int32_t P, const float* points, float* mean_dists, gslic_alloc_fn scratch_alloc, void* scratch_ctx,
                          void* stream)
 {

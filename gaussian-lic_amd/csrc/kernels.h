@@ -253,4 +253,11 @@ int exposure_apply(int H, int W, const float* E, const float* image, float* out,
 int exposure_backward(int H, int W, const float* E, const float* image, const float* dL_dout, float* dL_dimage, float* partials, float* dL_dE,
                       const gslic_exposure_adam* adam, hipStream_t s);
 
+// keyframes.hip: the keyframe store's decode (one launch: colour and, with a mask slab, the weight; the slot index read from the device word
+// `frame`, a word outside [0, n_frames) writes nothing) and encode (one launch per image given) of gslic_keyframe_decode / gslic_keyframe_encode
+// (arguments validated by the caller; color_slot / mask_slot: the first byte of the slot written)
+int keyframe_decode(int W, int H, int level, const uint8_t* color, const uint8_t* mask, const int32_t* frame, int n_frames, float* out, float* weight,
+                    hipStream_t s);
+int keyframe_encode(int W, int H, const float* image, const float* mask, uint8_t* color_slot, uint8_t* mask_slot, hipStream_t s);
+
 }  // namespace gslic

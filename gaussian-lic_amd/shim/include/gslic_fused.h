@@ -178,6 +178,116 @@ struct Exposure {
     }
 };
 
+// The keyframes' ground-truth images on the device as 8-bit pixels — the Python host's trainer.KeyframeStore (gslic_keyframe_encode /
+// gslic_keyframe_decode; storage, decode and encode rules in include/gslic_hip.h).  color: uint8 [capacity,H,W,3] interleaved RGB; mask (masks =
+// true): uint8 [capacity,H,W], decoded into the float32 weight image the weighted loss takes.  target() is usable as it is as the gt_image (and weight)
+// of FusedStep::step.  The reference keeps every keyframe as a float32 CPU tensor and uploads it at every step (gaussian.cpp:49, :80, :678).
+struct KeyframeTarget {
+    torch::Tensor image;    // float32 [3,H_l,W_l]
+    torch::Tensor weight;   // float32 [H_l,W_l] (a store with masks), undefined otherwise
+};
+class KeyframeStore {
+public:
+    torch::Tensor color, mask;   // the slabs
+    KeyframeStore(int width, int height, int capacity, torch::Device device = torch::kCUDA, bool masks = false) : W_(width), H_(height), cap_(capacity)
+    {
+        TORCH_CHECK(width >= 1 && height >= 1 && capacity >= 1, "KeyframeStore: width, height and capacity must all be at least 1");
+        const auto u8 = torch::TensorOptions().dtype(torch::kByte).device(device);
+        color = torch::zeros({capacity, height, width, 3}, u8);
+        if (masks) mask = torch::zeros({capacity, height, width}, u8);
+        frames_ = torch::arange(capacity, u8.dtype(torch::kInt32));
+        serial_.assign((size_t)capacity, 0);
+    }
+    int n() const { return n_; }
+    int64_t nbytes() const { return color.numel() + (mask.defined() ? mask.numel() : 0); }
+    int64_t serial(int slot) const { return serial_[(size_t)index(slot)]; }
+    // encodes a float32 [3,H,W] image (and, on a store with masks, a float32 [H,W] mask; undefined: weight 1 everywhere) into the next slot
+    int add(const torch::Tensor& image, const torch::Tensor& mask_image = torch::Tensor())
+    {
+        TORCH_CHECK(n_ < cap_, "KeyframeStore: all ", cap_, " slots are filled");
+        write(n_, image, mask_image);
+        return n_++;
+    }
+    // copies a uint8 [H,W,3] image (bgr: the channels flipped, in LibTorch) and a uint8 [H,W] mask into the next slot
+    int add_u8(const torch::Tensor& hwc, const torch::Tensor& mask_u8 = torch::Tensor(), bool bgr = false)
+    {
+        TORCH_CHECK(n_ < cap_, "KeyframeStore: all ", cap_, " slots are filled");
+        write_u8(n_, hwc, mask_u8, bgr);
+        return n_++;
+    }
+    // replaces a filled slot by a float image (as add) and bumps the slot's serial number
+    void put(int slot, const torch::Tensor& image, const torch::Tensor& mask_image = torch::Tensor())
+    {
+        write(index(slot), image, mask_image);
+        serial_[(size_t)slot]++;
+    }
+    void put_u8(int slot, const torch::Tensor& hwc, const torch::Tensor& mask_u8 = torch::Tensor(), bool bgr = false)
+    {
+        write_u8(index(slot), hwc, mask_u8, bgr);
+        serial_[(size_t)slot]++;
+    }
+    // the float32 target of a slot at a pyramid level (one launch; the slot index is read from a device word the store keeps)
+    KeyframeTarget target(int slot, int level = 0)
+    {
+        torch::NoGradGuard ng;
+        index(slot);
+        TORCH_CHECK(level >= 0 && level <= GSLIC_KEYFRAME_MAX_LEVEL && (W_ >> level) >= 1 && (H_ >> level) >= 1, "KeyframeStore: a ", W_, " x ", H_,
+                    " image has no level ", level);
+        const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(color.device());
+        KeyframeTarget out;
+        out.image = torch::empty({3, H_ >> level, W_ >> level}, f32);
+        if (mask.defined()) out.weight = torch::empty({H_ >> level, W_ >> level}, f32);
+        const int rc = gslic_keyframe_decode(W_, H_, level, color.data_ptr<uint8_t>(), mask.defined() ? mask.data_ptr<uint8_t>() : nullptr,
+                                             frames_.data_ptr<int32_t>() + slot, n_, out.image.data_ptr<float>(),
+                                             mask.defined() ? out.weight.data_ptr<float>() : nullptr, current_stream());
+        TORCH_CHECK(rc == GSLIC_OK, "gslic_keyframe_decode failed (", rc, "): ", gslic_last_error());
+        return out;
+    }
+
+private:
+    int index(int slot) const
+    {
+        TORCH_CHECK(slot >= 0 && slot < n_, "KeyframeStore: slot ", slot, " is outside [0, ", n_, ")");
+        return slot;
+    }
+    void write(int slot, const torch::Tensor& image, const torch::Tensor& mask_image)
+    {
+        torch::NoGradGuard ng;
+        TORCH_CHECK(!mask_image.defined() || mask.defined(), "KeyframeStore: mask given to a store built without masks");
+        const torch::Tensor img = image.detach().to(color.device(), torch::kFloat32).contiguous();
+        TORCH_CHECK(img.dim() == 3 && img.size(0) == 3 && img.size(1) == H_ && img.size(2) == W_, "KeyframeStore: the image must be [3, ", H_, ", ", W_, "]");
+        torch::Tensor m;
+        if (mask_image.defined()) {
+            m = mask_image.detach().to(color.device(), torch::kFloat32).contiguous();
+            TORCH_CHECK(m.dim() == 2 && m.size(0) == H_ && m.size(1) == W_, "KeyframeStore: the mask must be [", H_, ", ", W_, "]");
+        } else if (mask.defined()) {
+            mask[slot].fill_(255);
+        }
+        const int rc = gslic_keyframe_encode(W_, H_, img.data_ptr<float>(), m.defined() ? m.data_ptr<float>() : nullptr, color.data_ptr<uint8_t>(),
+                                             m.defined() ? mask.data_ptr<uint8_t>() : nullptr, cap_, slot, current_stream());
+        TORCH_CHECK(rc == GSLIC_OK, "gslic_keyframe_encode failed (", rc, "): ", gslic_last_error());
+    }
+    void write_u8(int slot, const torch::Tensor& hwc, const torch::Tensor& mask_u8, bool bgr)
+    {
+        torch::NoGradGuard ng;
+        TORCH_CHECK(!mask_u8.defined() || mask.defined(), "KeyframeStore: mask given to a store built without masks");
+        TORCH_CHECK(hwc.scalar_type() == torch::kByte && hwc.dim() == 3 && hwc.size(0) == H_ && hwc.size(1) == W_ && hwc.size(2) == 3,
+                    "KeyframeStore: add_u8 takes a uint8 [", H_, ", ", W_, ", 3] tensor");
+        color[slot].copy_(bgr ? hwc.flip({-1}) : hwc);
+        if (!mask.defined()) return;
+        if (mask_u8.defined()) {
+            TORCH_CHECK(mask_u8.scalar_type() == torch::kByte && mask_u8.dim() == 2 && mask_u8.size(0) == H_ && mask_u8.size(1) == W_,
+                        "KeyframeStore: the mask of add_u8 is a uint8 [", H_, ", ", W_, "] tensor");
+            mask[slot].copy_(mask_u8);
+        } else {
+            mask[slot].fill_(255);
+        }
+    }
+    int W_, H_, cap_, n_ = 0;
+    torch::Tensor frames_;            // int32 [capacity] = 0 .. capacity-1: the device word that names slot i is frames_[i]
+    std::vector<int64_t> serial_;
+};
+
 class LidarDepth {
 public:
     LidarDepth(int width, int height, torch::Device device = torch::kCUDA) : W_(width), H_(height)

@@ -1372,6 +1372,158 @@ class _RawRaster:
                             sample, self.lambda_erank, **modes)
 
 
+class KeyframeStore:
+    """The keyframes' ground-truth images on the device as the 8-bit pixels the camera delivered, decoded into the float32 target of a pyramid
+    level by one launch (gslic_keyframe_encode / gslic_keyframe_decode; the three rules — storage, decode, encode — are written out in
+    include/gslic_hip.h).  The reference keeps every keyframe as a float32 CPU tensor and uploads it at every step (gaussian.cpp:49, :80, :678).
+    color: uint8 [capacity, H, W, 3] interleaved RGB; mask (masks=True): uint8 [capacity, H, W], decoded into the float32 [H_l, W_l] weight image
+    the weighted loss takes (255 = weight 1).  Slots are handed out in order; `n` of them are filled.  Every slot has a serial number that put()
+    bumps: a GraphedStep that has to repeat a step checks it.  Nothing here synchronises; add_u8 is a plain copy."""
+
+    MAX_LEVEL = 4   # GSLIC_KEYFRAME_MAX_LEVEL
+
+    def __init__(self, width, height, capacity, device, masks=False):
+        W, H, C = int(width), int(height), int(capacity)
+        if W < 1 or H < 1 or C < 1:
+            raise ValueError(f"KeyframeStore: width = {width}, height = {height}, capacity = {capacity} must all be at least 1")
+        self.width, self.height, self.capacity = W, H, C
+        self.device = torch.device(device)
+        self.color = torch.zeros(C, H, W, 3, dtype=torch.uint8, device=self.device)
+        self.mask = torch.zeros(C, H, W, dtype=torch.uint8, device=self.device) if masks else None
+        self._frames = torch.arange(C, dtype=torch.int32, device=self.device)   # the device word that names slot i is _frames[i]: no copy per decode
+        self._serial = [0] * C
+        self._n = 0
+
+    @property
+    def n(self):
+        """Slots filled."""
+        return self._n
+
+    @property
+    def nbytes(self):
+        """Device bytes of the slabs (all `capacity` slots)."""
+        return self.color.numel() + (0 if self.mask is None else self.mask.numel())
+
+    @property
+    def has_masks(self):
+        return self.mask is not None
+
+    def _index(self, slot):
+        s = int(slot)
+        if not 0 <= s < self._n:
+            raise IndexError(f"KeyframeStore: slot {slot} is outside [0, {self._n})")
+        return s
+
+    def serial(self, slot):
+        return self._serial[self._index(slot)]
+
+    def level_size(self, level):
+        """(W_l, H_l) of a level; raises for a level the image does not have."""
+        l = int(level)
+        if not 0 <= l <= self.MAX_LEVEL:
+            raise ValueError(f"KeyframeStore: level = {level} is outside [0, {self.MAX_LEVEL}]")
+        if (self.width >> l) < 1 or (self.height >> l) < 1:
+            raise ValueError(f"KeyframeStore: a {self.width} x {self.height} image has no level {l}")
+        return self.width >> l, self.height >> l
+
+    def _check_mask(self, mask):
+        if mask is not None and self.mask is None:
+            raise ValueError("KeyframeStore: mask given to a store built without masks (pass masks=True to the constructor)")
+
+    def _next(self):
+        if self._n >= self.capacity:
+            raise RuntimeError(f"KeyframeStore: all {self.capacity} slots are filled")
+        return self._n
+
+    def _write(self, slot, image, mask):
+        """gslic_keyframe_encode of a float image [3,H,W] (and a float mask [H,W]; None on a store with masks: weight 1 everywhere) into `slot`."""
+        from . import _lib
+        H, W = self.height, self.width
+        self._check_mask(mask)
+        img = image.detach().to(self.device, torch.float32).contiguous()
+        if tuple(img.shape) != (3, H, W):
+            raise ValueError(f"KeyframeStore: image of shape {tuple(image.shape)} given to a store of [3, {H}, {W}]")
+        m = None
+        if mask is not None:
+            m = mask.detach().to(self.device, torch.float32).contiguous()
+            if tuple(m.shape) != (H, W):
+                raise ValueError(f"KeyframeStore: mask of shape {tuple(mask.shape)} given to a store of [{H}, {W}]")
+        elif self.mask is not None:
+            self.mask[slot].fill_(255)
+        _lib.check(_lib.lib().gslic_keyframe_encode(W, H, _lib.ptr(img), _lib.ptr(m), _lib.ptr(self.color), _lib.ptr(self.mask) if m is not None else None,
+                                                    self.capacity, slot, _lib.current_stream_ptr()))
+
+    def _write_u8(self, slot, hwc_uint8, mask, bgr):
+        H, W = self.height, self.width
+        self._check_mask(mask)
+        if hwc_uint8.dtype != torch.uint8 or tuple(hwc_uint8.shape) != (H, W, 3):
+            raise ValueError(f"KeyframeStore: add_u8 takes a uint8 [{H}, {W}, 3] tensor, not {hwc_uint8.dtype} {tuple(hwc_uint8.shape)}")
+        if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W)):
+            raise ValueError(f"KeyframeStore: the mask of add_u8 is a uint8 [{H}, {W}] tensor, not {mask.dtype} {tuple(mask.shape)}")
+        self.color[slot].copy_(hwc_uint8.flip(-1) if bgr else hwc_uint8)
+        if self.mask is not None:
+            if mask is None:
+                self.mask[slot].fill_(255)
+            else:
+                self.mask[slot].copy_(mask)
+
+    def add(self, image, mask=None):
+        """Encodes a float32 [3,H,W] image (values clamped to [0, 1], NaN as 0) and, on a store with masks, a float32 [H,W] mask into the next
+        slot; returns the slot."""
+        slot = self._next()
+        self._write(slot, image, mask)
+        self._n += 1
+        return slot
+
+    def add_u8(self, hwc_uint8, mask=None, bgr=False):
+        """Copies a uint8 [H,W,3] image (any device; bgr=True: the channels are flipped, in torch) and a uint8 [H,W] mask into the next slot;
+        returns the slot."""
+        slot = self._next()
+        self._write_u8(slot, hwc_uint8, mask, bgr)
+        self._n += 1
+        return slot
+
+    def put(self, slot, image=None, mask=None, u8=None, bgr=False):
+        """Replaces a filled slot — by a float image (as add) or, u8=, a uint8 [H,W,3] one (as add_u8) — and bumps the slot's serial number."""
+        s = self._index(slot)
+        if (image is None) == (u8 is None):
+            raise ValueError("KeyframeStore.put: pass exactly one of image and u8")
+        if u8 is None:
+            self._write(s, image, mask)
+        else:
+            self._write_u8(s, u8, mask, bgr)
+        self._serial[s] += 1
+        return s
+
+    def _decode(self, word, level, out, weight_out, n_frames=None):
+        """gslic_keyframe_decode of the slot the device word names: one launch, colour and (with masks) weight."""
+        from . import _lib
+        _lib.check(_lib.lib().gslic_keyframe_decode(self.width, self.height, int(level), _lib.ptr(self.color), _lib.ptr(self.mask), _lib.ptr(word),
+                                                    self._n if n_frames is None else int(n_frames), _lib.ptr(out),
+                                                    None if self.mask is None else _lib.ptr(weight_out), _lib.current_stream_ptr()))
+
+    def target_buffers(self, level=0):
+        """Uninitialised (image [3,H_l,W_l], weight [H_l,W_l] or None) of a level, as target(out=) takes them."""
+        Wl, Hl = self.level_size(level)
+        image = torch.empty(3, Hl, Wl, dtype=torch.float32, device=self.device)
+        return image, (torch.empty(Hl, Wl, dtype=torch.float32, device=self.device) if self.mask is not None else None)
+
+    def target(self, slot, level=0, out=None):
+        """The float32 target of a slot at a level: image [3,H_l,W_l], or (image, weight [H_l,W_l]) on a store with masks — usable as they are as
+        gt_image / weight of every training_step*.  out: the tensor (the pair, with masks) to write into instead of allocating."""
+        s = self._index(slot)
+        Wl, Hl = self.level_size(level)
+        if out is None:
+            image, weight = self.target_buffers(level)
+        else:
+            image, weight = out if self.mask is not None else (out, None)
+            for t, shape, name in ((image, (3, Hl, Wl), "image"), (weight, (Hl, Wl), "weight")):
+                if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.color.device):
+                    raise ValueError(f"KeyframeStore.target: out's {name} must be a contiguous float32 {list(shape)} tensor on the store's device")
+        self._decode(self._frames[s:s + 1], level, image, weight)
+        return image if self.mask is None else (image, weight)
+
+
 class Exposure:
     """Trainable per-view exposure: one 3x4 affine colour transform per view (or per group of views — which views share a row is the host's
     policy), applied to the rendered image before the loss: out_c = E[c,:3] . rgb + E[c,3] (gslic_exposure_apply; the rule is written out in
@@ -1898,10 +2050,20 @@ class GraphedStep:
     step(view=...) fills (None = the one that is loaded), so a captured graph changes views without being re-captured: the step first gathers the
     row into a fixed 12-float buffer (one index_select launch, inside the step), applies it from there, and the exposure backward's second launch
     updates the row the word names.  A step that did not fit its buffers updates no row either (the descriptor's skip word is the forward's
-    status word) and is repeated with its own view.  Eager and captured runs issue the same calls."""
+    status word) and is repeated with its own view.  Eager and captured runs issue the same calls.
+
+    keyframes (a trainer.KeyframeStore) / frame / level, with gt_image=None: the step's static target is filled INSIDE the step by the store's
+    decode launch (gslic_keyframe_decode at `level`) from the slot a device int32 names; step(camera, frame=j) fills that word (None = the one that
+    is loaded) and that is all a change of target costs — no 25 MB copy, no re-capture.  The step is built at camera.at_level(level) resolution: a
+    camera of the store's full size is converted, one that already has the level's size is used as it is.  A store with masks feeds the step's
+    weight buffer from the same launch: the step is then a weighted step.  The launch is given the store's CAPACITY as its frame count (frames
+    added after a capture stay reachable); the index is validated against the filled slots on the host before the word is written.  A repeated step
+    uses its own frame index and the slot's serial number: a slot replaced (put) since the step was issued fails loudly.  gt_image together with
+    a store, or frame given to a step built without one, raises.  Without keyframes the step is what it was, launch for launch."""
 
     def __init__(self, model, camera, gt_image, bg, headroom=1.25, check_every=16, cap_R=None, cap_B=None, use_graph=False, gt_depth=None,
-                 lambda_depth=0.0, weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0, exposure=None, view=0):
+                 lambda_depth=0.0, weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0, exposure=None, view=0, keyframes=None,
+                 frame=None, level=0):
         """use_graph=False (default since round 5): the capacity-mode step (caller-owned scratch, no host round trip, overflow checks and repeats as
         below) issued as eager launches; use_graph=True: captured in a hipGraph and replayed with one launch per step.  The two are equally fast at
         2M Gaussians (bench.py: `capacity_eager` / `graphed`; the host runs ahead of the device either way), and the eager form has no hazard:
@@ -1915,20 +2077,40 @@ class GraphedStep:
         self.use_graph = bool(use_graph)
         self.model, self.bg, self.headroom, self.check_every = model, bg, float(headroom), int(check_every)
         dev = model.device
+        self.keyframes, self.level = keyframes, int(level)
+        if keyframes is None:
+            if frame is not None or self.level != 0:
+                raise ValueError("GraphedStep: frame / level given without keyframes (pass a trainer.KeyframeStore)")
+        else:
+            if not isinstance(keyframes, KeyframeStore):
+                raise ValueError("GraphedStep: keyframes must be a trainer.KeyframeStore")
+            if gt_image is not None:
+                raise ValueError("GraphedStep: gt_image given together with keyframes (the step decodes its target from the store: pass gt_image=None "
+                                 "and frame=)")
+            if weight is not None and keyframes.has_masks:
+                raise ValueError("GraphedStep: weight given together with a keyframe store that has masks (the store's mask is the step's weight)")
+            self._kf_size = keyframes.level_size(self.level)
+            self._kf_host = keyframes._index(0 if frame is None else frame)
+            self._kf_word = torch.full((1,), self._kf_host, dtype=torch.int32, device=dev)
+            camera = self._kf_camera(camera)
         self.H, self.W = int(camera.image_height), int(camera.image_width)
         self.cam = camera
         self.view = camera.d_world_view_transform.clone()
         self.proj = camera.d_full_proj_transform.clone()
         self.campos = camera.d_camera_center.clone()
-        self.gt = gt_image.clone()
+        kf_weight = None
+        if keyframes is None:
+            self.gt = gt_image.clone()
+        else:
+            self.gt, kf_weight = keyframes.target_buffers(self.level)   # filled by the decode launch inside the step
         self.use_depth = _use_depth("GraphedStep", gt_depth, lambda_depth, depth_weight, depth_huber)
         self.lambda_depth = float(lambda_depth) if self.use_depth else 0.0
         self.use_depth_weight = self.use_depth and depth_weight is not None
         self.depth_weight = depth_weight.detach().float().contiguous().clone() if self.use_depth_weight else None
         self.depth_huber = float(depth_huber) if self.use_depth else 0.0
         self.gt_depth = gt_depth.detach().float().contiguous().clone() if self.use_depth else None
-        self.use_weight = weight is not None
-        self.weight = weight.detach().float().contiguous().clone() if self.use_weight else None
+        self.use_weight = weight is not None or kf_weight is not None
+        self.weight = kf_weight if kf_weight is not None else (weight.detach().float().contiguous().clone() if self.use_weight else None)
         self.fl = loss_utils.FusedLoss(LAMBDA_DSSIM)
         self.exposure = _check_exposure("GraphedStep", exposure, view)
         if self.exposure is not None:
@@ -1953,7 +2135,19 @@ class GraphedStep:
         self.recaptures = 0
         self._capture()
 
+    def _kf_camera(self, camera):
+        """The camera a step on a keyframe store runs at: one of the level's size as it is, one of the store's full size through at_level."""
+        size = (int(camera.image_width), int(camera.image_height))
+        if size == self._kf_size:
+            return camera
+        if size != (self.keyframes.width, self.keyframes.height):
+            raise ValueError(f"GraphedStep: a {size[0]} x {size[1]} camera given to a step on {self.keyframes.width} x {self.keyframes.height} keyframes "
+                             f"at level {self.level} ({self._kf_size[0]} x {self._kf_size[1]})")
+        return camera.at_level(self.level)
+
     def _eager(self):
+        if self.keyframes is not None:
+            self.keyframes._decode(self._kf_word, self.level, self.gt, self.weight, n_frames=self.keyframes.capacity)
         rr = _RawRaster(self.model, self.cam, self.bg, self.use_depth, e=self.e, pose=(self.view, self.proj, self.campos))
         image, depth, _radii = rr.forward(self.bufs)
         if self.exposure is None:
@@ -2016,9 +2210,22 @@ class GraphedStep:
         device between two replays)."""
         return (camera.world_view_transform.copy(), camera.full_proj_transform.copy(), camera.camera_center.copy())
 
-    def _load(self, camera, gt_image, gt_depth=None, weight=None, depth_weight=None, view=None):
+    def _load(self, camera, gt_image, gt_depth=None, weight=None, depth_weight=None, view=None, frame=None):
         """Refresh the static buffers the captured step reads.  The pose is copied on every call that names a camera (the same Camera object
         may have been moved in place since it was loaded last)."""
+        if self.keyframes is None:
+            if frame is not None:
+                raise ValueError("GraphedStep: frame given to a step built without a keyframe store (pass keyframes to the constructor)")
+        else:
+            if gt_image is not None:
+                raise ValueError("GraphedStep: gt_image given to a step built on a keyframe store (its target is decoded inside the step: pass frame=)")
+            if weight is not None and weight is not False and self.keyframes.has_masks:
+                raise ValueError("GraphedStep: weight given to a step whose keyframe store has masks (the store's mask is the step's weight)")
+            if frame is not None and self.keyframes._index(frame) != self._kf_host:
+                self._kf_host = self.keyframes._index(frame)
+                self._kf_word.fill_(self._kf_host)
+            if camera is not None:
+                camera = self._kf_camera(camera)
         if view is not None:
             if self.exposure is None:
                 raise ValueError("GraphedStep: view given to a step built without an exposure (pass exposure to the constructor)")
@@ -2068,7 +2275,9 @@ class GraphedStep:
         version counter; for gt_image=None — "the target that is loaded" — the serial number of the load)."""
         if getattr(self, "_pose_host", None) is None:
             self._pose_host = self._pose_of(self.cam)
-        return dict(view=getattr(self, "_ex_view_host", None), pose=self._pose_host, gt=gt_image, gt_version=None if gt_image is None else gt_image._version, gt_serial=getattr(self, "_gt_serial", 0),
+        kf = self.keyframes
+        return dict(frame=None if kf is None else self._kf_host, frame_serial=None if kf is None else kf.serial(self._kf_host),
+                    view=getattr(self, "_ex_view_host", None), pose=self._pose_host, gt=gt_image, gt_version=None if gt_image is None else gt_image._version, gt_serial=getattr(self, "_gt_serial", 0),
                     gtd=gt_depth, gtd_version=None if gt_depth is None else gt_depth._version, gtd_serial=getattr(self, "_gtd_serial", 0),
                     w=weight, w_version=None if weight is None else weight._version, w_serial=getattr(self, "_w_serial", 0),
                     dw=depth_weight, dw_version=None if depth_weight is None else depth_weight._version, dw_serial=getattr(self, "_dw_serial", 0))
@@ -2080,6 +2289,11 @@ class GraphedStep:
         self._pose_host = snap["pose"]
         if self.exposure is not None and snap.get("view") is not None:
             self._load(None, None, view=snap["view"])
+        if self.keyframes is not None:
+            if self.keyframes.serial(snap["frame"]) != snap["frame_serial"]:
+                raise RuntimeError(f"GraphedStep: slot {snap['frame']} of the keyframe store was replaced (put) after a step that has to be repeated "
+                                   "was issued on it")
+            self._load(None, None, frame=snap["frame"])
         gt = snap["gt"]
         if gt is None:
             if snap["gt_serial"] != getattr(self, "_gt_serial", 0):
@@ -2146,11 +2360,12 @@ class GraphedStep:
             with torch.no_grad():
                 self._eager()
 
-    def step(self, camera=None, gt_image=None, gt_depth=None, weight=None, depth_weight=None, view=None):
+    def step(self, camera=None, gt_image=None, gt_depth=None, weight=None, depth_weight=None, view=None, frame=None):
         """One optimiser step (replay).  Returns the device tensor [mean L1, mean SSIM] of this step's loss terms ([mean L1, mean SSIM, L_d]
         with depth supervision; gt_depth: this step's depth target, None = the one that is loaded; weight: this step's weight image, likewise;
-        depth_weight: this step's depth weight image, likewise; view: the row of the exposure this step applies and updates, likewise)."""
-        self._load(camera, gt_image, gt_depth, weight, depth_weight, view)
+        depth_weight: this step's depth weight image, likewise; view: the row of the exposure this step applies and updates, likewise; frame: the
+        slot of the keyframe store this step trains on, likewise)."""
+        self._load(camera, gt_image, gt_depth, weight, depth_weight, view, frame)
         self._issue()
         self.steps_issued += 1
         if len(self.window) < 32:

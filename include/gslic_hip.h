@@ -685,6 +685,48 @@ int gslic_exposure_backward(
     int32_t H, int32_t W, const float* E /*[12] device*/, const float* image, const float* dL_dout, float* dL_dimage, float* partials,
     float* dL_dE /*[12] device*/, const gslic_exposure_adam* adam /*or NULL*/, void* stream);
 
+/* gslic_keyframe_encode / gslic_keyframe_decode — the keyframe store: ground-truth images kept on the device as the 8-bit pixels the camera
+ * delivered, decoded into the float32 target of a pyramid level (additive, ABI 8; the reference keeps every keyframe as a float32 CPU tensor and
+ * uploads it at every step: gaussian.cpp:49, :80, :678).  Three rules, each reproducible bit for bit from numpy (tests/keyframe_ref.py):
+ *
+ * STORAGE.  color_slab: uint8 [capacity, H, W, 3] DEVICE, interleaved RGB (pixel (x, y) of slot s, channel c at ((s H + y) W + x) 3 + c: what a
+ * camera driver or OpenCV delivers, up to the channel order).  mask_slab (optional): uint8 [capacity, H, W] DEVICE.
+ *
+ * DECODE at level l, 0 <= l <= GSLIC_KEYFRAME_MAX_LEVEL: W_l = W >> l, H_l = H >> l (either 0: GSLIC_ERR_INVALID_ARG); the remainder columns on the
+ * right and the remainder rows at the bottom are dropped.  Output pixel (X, Y) of channel c:
+ *   out[c, Y, X] = (float)S * c_l,   S = the INTEGER sum of the 4^l bytes of channel c in the block [X 2^l, (X+1) 2^l) x [Y 2^l, (Y+1) 2^l),
+ *   c_l = (1.0f / 255.0f) * 2^(-2 l)          (the float32 quotient, scaled exactly)
+ * S <= 255 * 256 is exact in float32, so the rule is ONE float32 multiply per value.  The mask decodes by the same rule into weight_out, float32
+ * [H_l, W_l]: a per-pixel weight image as gslic_l1_ssim_loss_weighted_forward_backward takes it.  out: planar float32 [3, H_l, W_l].  The slot is
+ * read from the DEVICE word *frame, so a captured graph changes targets without a host copy; a word outside [0, n_frames) makes the launch write
+ * NOTHING (a host validates the index before it fills the word).  One launch writes colour and, with mask_slab != NULL, the weight.  A lane owns
+ * four consecutive output pixels where W % (4 << l) == 0 (aligned 4- / 8- / 16-byte non-temporal loads of the slab, one 16-byte store per plane),
+ * one pixel otherwise.  No atomics, no allocation, no read-back: capturable in a graph.
+ *
+ * ENCODE.  image: planar float32 [3, H, W] DEVICE -> slot `slot` of color_slab; mask: float32 [H, W] DEVICE -> slot `slot` of mask_slab (either
+ * pair may be NULL, not both).  Per value x:
+ *   x' = x > 0 ? (x < 1 ? x : 1) : 0          (NaN reads as 0, -0 as 0, +inf as 1)
+ *   q  = (uint8) floorf((x' * 255.0f) + 0.5f)  the product rounded to float32 on its own (never contracted into the add), then the add, then floor
+ * Round trip: with d(v) = (float)v * c_0 the decoded value of byte v, encode(d(v)) == v for all 256 values, and so does encode of the float32
+ * quotient v / 255.0f (which differs from d(v) in the last bit for 126 of them): decode(encode(x)) == d(v) bit for bit for either x.
+ *
+ * CAMERA at level l (the host's part; Camera.at_level in camera.py): width W_l, height H_l, fx / 2^l, fy / 2^l, cx / 2^l, cy / 2^l — all four exact
+ * in float32 — and the pose, znear and zfar unchanged.  The continuous image coordinate u = fx x / z + cx spans [0, W) in this library's convention
+ * (P[0,2] = (2 cx - W) / W; the floor of gslic_lidar_zbuffer_add), so halving u is the whole change: a point's level-l pixel is
+ * floor(pixel_0 / 2^l) exactly, and it is dropped exactly when that lands in a remainder column or row.
+ *
+ * GSLIC_ERR_INVALID_ARG before any device work, naming the argument: W or H <= 0, a level outside [0, GSLIC_KEYFRAME_MAX_LEVEL], W_l or H_l of 0,
+ * a NULL color_slab / frame / out (decode), mask_slab != NULL with weight_out == NULL, n_frames < 0, an out / weight_out / color_slab / mask_slab
+ * that is not 16-byte aligned, an image that is not 4-byte aligned; (encode) capacity <= 0, a slot outside [0, capacity), image and mask both
+ * NULL, an image without color_slab or a mask without mask_slab. */
+#define GSLIC_KEYFRAME_MAX_LEVEL 4
+int gslic_keyframe_decode(
+    int32_t W, int32_t H, int32_t level, const uint8_t* color_slab, const uint8_t* mask_slab /*or NULL*/, const int32_t* frame /*[1] device*/,
+    int32_t n_frames, float* out /*[3,H_l,W_l]*/, float* weight_out /*[H_l,W_l], with mask_slab*/, void* stream);
+int gslic_keyframe_encode(
+    int32_t W, int32_t H, const float* image /*[3,H,W] or NULL*/, const float* mask /*[H,W] or NULL*/, uint8_t* color_slab, uint8_t* mask_slab,
+    int32_t capacity, int32_t slot, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * gslic_knn_mean_dist2 — replaces SimpleKNN::knn (src/simple-knn/simple_knn.cu:185-221) behind distCUDA2
  * (src/simple-knn/spatial.cu:15-26): mean_dists[i] = mean of the 3 smallest squared distances from point i

@@ -1869,10 +1869,8 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
         dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber,
                                                     exposure, view)
         slab = _grad_slab(model)
-        if grad_stats is None:
-            out = rr.backward(dL_dimage, dL_ddepth, out=slab.views, camera_grads=True)
-        else:
-            out = rr.backward(dL_dimage, dL_ddepth, out=slab.views, camera_grads=True, mean2d_out=grad_stats._mean2d_buffer())
+        out = rr.backward(dL_dimage, dL_ddepth, out=slab.views, camera_grads=True, mean2d_out=None if grad_stats is None else grad_stats._mean2d_buffer())
+        if grad_stats is not None:
             grad_stats.accumulate_from(out[0], radii)
         visible = radii > 0
         model.optimizer.set_visibility_and_N(visible, model.P)
@@ -1917,14 +1915,12 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
     launch."""
     exposure = _check_exposure("training_step_fused", exposure, view)
     fl = fused_loss or _default_fused_loss()
-    if (depth_weight is not None or depth_huber) and _dist_on():
+    # (ahead of _use_depth: under the exchange a depth weight or threshold is refused as depth supervision is, with or without a depth target)
+    if ((gt_depth is not None and lambda_depth != 0.0) or depth_weight is not None or depth_huber) and _dist_on():
         raise NotImplementedError("training_step_fused with depth supervision is single-GPU only: the N > 1 gradient exchange (rank1 / slab "
                                   "all-reduce) carries no depth gradient; use training_step(gt_depth=...) or run on one GPU")
     use_depth = _use_depth("training_step_fused", gt_depth, lambda_depth, depth_weight, depth_huber)
     grad_stats = _grad_stats_for_step(grad_stats, model)
-    if use_depth and _dist_on():
-        raise NotImplementedError("training_step_fused with depth supervision is single-GPU only: the N > 1 gradient exchange (rank1 / slab "
-                                  "all-reduce) carries no depth gradient; use training_step(gt_depth=...) or run on one GPU")
     dev = model.device
     cam = camera
     if DIST_TIMING is not None and do_step and _dist_on():
@@ -1944,10 +1940,8 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
                 if xg is None or xg.shape[0] != model.P or xg.device != rr.xyz.device:
                     xg = model._depth_xyz_grad = torch.empty(model.P, 3, dtype=torch.float32, device=dev)
             vis_u8 = torch.empty(model.P, dtype=torch.uint8, device=dev)
-            if grad_stats is None:
-                rr.backward(dL_dimage, dL_ddepth, adam=model.optimizer.fused_descriptor(visible_out=vis_u8), xyz_grad=xg)
-            else:
-                rr.backward(dL_dimage, dL_ddepth, adam=model.optimizer.fused_descriptor(visible_out=vis_u8), xyz_grad=xg, grad_stats=grad_stats._descriptor())
+            rr.backward(dL_dimage, dL_ddepth, adam=model.optimizer.fused_descriptor(visible_out=vis_u8), xyz_grad=xg,
+                        grad_stats=None if grad_stats is None else grad_stats._descriptor())
             model.optimizer.count_step()
             return terms, vis_u8.view(torch.bool)   # `radii > 0` (renderer.cpp:85), written by the backward kernel: no compare launch
         slab = _grad_slab(model)
@@ -1968,10 +1962,9 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
                 model.optimizer.step(grads, only=idx)
             _dist_mark("end")
             return terms, visible
-        if grad_stats is None:
-            rr.backward(dL_dimage, dL_ddepth, out=slab.views)
-        else:
-            grad_stats.accumulate_from(rr.backward(dL_dimage, dL_ddepth, out=slab.views, mean2d_out=grad_stats._mean2d_buffer())[0], radii)
+        out = rr.backward(dL_dimage, dL_ddepth, out=slab.views, mean2d_out=None if grad_stats is None else grad_stats._mean2d_buffer())
+        if grad_stats is not None:
+            grad_stats.accumulate_from(out[0], radii)
         visible = radii > 0
         if do_step:
             if _dist_on():
@@ -2016,6 +2009,40 @@ def render_fwd_bwd(model, camera, dL_dimage, bg):
     for p in model.parameters():
         p.grad = None
     return visible
+
+
+class _StepInput:
+    """One static input image of GraphedStep — the buffer the step reads and the serial number of its loads — and the rule all four live by.
+    load(t) copies a tensor that lives in other storage and counts the copy.  snapshot(t) is what a repeat of a step issued with t needs: the
+    tensor by reference with its version counter, or, for t=None ("the one that is loaded"), the serial of the load.  restore(snap) loads it
+    again, and refuses when that evidence says the data is no longer what the step ran on.  Tensor operations only."""
+
+    def __init__(self, noun, arg, buffer, loaded_noun=None, check_shape=False):
+        """noun: what the messages call the image; arg: step()'s name for it; loaded_noun: the noun of "the one that is loaded" where it
+        differs; check_shape: load() refuses a tensor of another shape (else that is copy_'s business)."""
+        self.noun, self.loaded_noun, self.arg, self.buffer, self.check_shape = noun, loaded_noun or noun, arg, buffer, check_shape
+        self.serial = 0
+
+    def load(self, t):
+        if self.check_shape and tuple(t.shape) != tuple(self.buffer.shape):
+            raise ValueError(f"GraphedStep: {self.arg} of shape {tuple(t.shape)} given to a step built for {tuple(self.buffer.shape)}")
+        if t.data_ptr() != self.buffer.data_ptr():
+            self.buffer.copy_(t)
+            self.serial += 1
+
+    def snapshot(self, t):
+        return (t, None if t is None else t._version, self.serial)
+
+    def restore(self, snap):
+        t, version, serial = snap
+        if t is None:
+            if serial != self.serial:
+                raise RuntimeError(f"GraphedStep: a step that has to be repeated ran on a {self.loaded_noun} that has been replaced since (it was "
+                                   f"issued with {self.arg}=None); pass it explicitly to step() when it changes between checks")
+            return
+        if t._version != version:
+            raise RuntimeError(f"GraphedStep: the {self.noun} of a step that has to be repeated was modified in place after the step was issued")
+        self.load(t)
 
 
 class GraphedStep:
@@ -2081,6 +2108,7 @@ class GraphedStep:
         if keyframes is None:
             if frame is not None or self.level != 0:
                 raise ValueError("GraphedStep: frame / level given without keyframes (pass a trainer.KeyframeStore)")
+            self._kf_host = None
         else:
             if not isinstance(keyframes, KeyframeStore):
                 raise ValueError("GraphedStep: keyframes must be a trainer.KeyframeStore")
@@ -2098,6 +2126,7 @@ class GraphedStep:
         self.view = camera.d_world_view_transform.clone()
         self.proj = camera.d_full_proj_transform.clone()
         self.campos = camera.d_camera_center.clone()
+        self._pose_host = self._pose_of(camera)
         kf_weight = None
         if keyframes is None:
             self.gt = gt_image.clone()
@@ -2105,18 +2134,26 @@ class GraphedStep:
             self.gt, kf_weight = keyframes.target_buffers(self.level)   # filled by the decode launch inside the step
         self.use_depth = _use_depth("GraphedStep", gt_depth, lambda_depth, depth_weight, depth_huber)
         self.lambda_depth = float(lambda_depth) if self.use_depth else 0.0
-        self.use_depth_weight = self.use_depth and depth_weight is not None
-        self.depth_weight = depth_weight.detach().float().contiguous().clone() if self.use_depth_weight else None
+        self.depth_weight = depth_weight.detach().float().contiguous().clone() if self.use_depth and depth_weight is not None else None
         self.depth_huber = float(depth_huber) if self.use_depth else 0.0
         self.gt_depth = gt_depth.detach().float().contiguous().clone() if self.use_depth else None
         self.use_weight = weight is not None or kf_weight is not None
         self.weight = kf_weight if kf_weight is not None else (weight.detach().float().contiguous().clone() if self.use_weight else None)
+
+        def slot(buffer, noun, arg, **kw):
+            return None if buffer is None else _StepInput(noun, arg, buffer, **kw)
+        # the four images the step reads from static buffers, under step()'s names for them and in the order a repeat restores them; None: the
+        # step was built without that input.  self.gt, .weight, .depth_weight and .gt_depth stay the buffers themselves.
+        self._slots = dict(gt_image=slot(self.gt, "ground-truth tensor", "gt_image", loaded_noun="target"),
+                           weight=slot(self.weight, "weight image", "weight", check_shape=True),
+                           depth_weight=slot(self.depth_weight, "depth weight image", "depth_weight", check_shape=True),
+                           gt_depth=slot(self.gt_depth, "depth target", "gt_depth"))
         self.fl = loss_utils.FusedLoss(LAMBDA_DSSIM)
         self.exposure = _check_exposure("GraphedStep", exposure, view)
+        self._ex_view_host = None if self.exposure is None else int(view)                    # the row that is loaded
         if self.exposure is not None:
             self._ex_E = torch.empty(1, 12, dtype=torch.float32, device=dev)                  # the row the step applies, gathered inside the step
             self._ex_view = torch.full((1,), int(view), dtype=torch.int32, device=dev)       # which row: filled by _load
-            self._ex_view_host = int(view)
         self.e = torch.empty(0, device=dev)
         # sizes from one eager forward of the current state
         with torch.no_grad():
@@ -2157,10 +2194,7 @@ class GraphedStep:
             ex_view = (self._ex_E.view(12), self._ex_view, self.bufs.status[2:3])
         dL_dimage, dL_ddepth, self.terms = _fused_losses(self.fl, image, self.gt, depth, self.gt_depth, self.lambda_depth, self.weight, self.depth_weight,
                                                          self.depth_huber, self.exposure, ex_view)
-        if self._gstat is None:
-            rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad)
-        else:
-            rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad, grad_stats=self._gstat)
+        rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad, grad_stats=self._gstat)
 
     def _capture(self):
         from . import rasterizer as rz
@@ -2237,111 +2271,45 @@ class GraphedStep:
                 raise ValueError("GraphedStep: this step was built with a weight and always runs the weighted loss (pass ones to weigh every pixel "
                                  "alike, or build a step without a weight)")
             weight = None
-        if weight is not None:
-            if not self.use_weight:
-                raise ValueError("GraphedStep: weight given to a step built without one (pass weight to the constructor)")
-            if tuple(weight.shape) != tuple(self.weight.shape):
-                raise ValueError(f"GraphedStep: weight of shape {tuple(weight.shape)} given to a step built for {tuple(self.weight.shape)}")
-            if weight.data_ptr() != self.weight.data_ptr():
-                self.weight.copy_(weight)
-                self._w_serial = getattr(self, "_w_serial", 0) + 1
-        if depth_weight is not None:
-            if not self.use_depth_weight:
-                raise ValueError("GraphedStep: depth_weight given to a step built without one (pass depth_weight to the constructor)")
-            if tuple(depth_weight.shape) != tuple(self.depth_weight.shape):
-                raise ValueError(f"GraphedStep: depth_weight of shape {tuple(depth_weight.shape)} given to a step built for {tuple(self.depth_weight.shape)}")
-            if depth_weight.data_ptr() != self.depth_weight.data_ptr():
-                self.depth_weight.copy_(depth_weight)
-                self._dw_serial = getattr(self, "_dw_serial", 0) + 1
-        if gt_depth is not None:
-            if not self.use_depth:
-                raise ValueError("GraphedStep: gt_depth given to a step built without depth supervision (pass gt_depth / lambda_depth to the constructor)")
-            if gt_depth.data_ptr() != self.gt_depth.data_ptr():
-                self.gt_depth.copy_(gt_depth)
-                self._gtd_serial = getattr(self, "_gtd_serial", 0) + 1
+        for arg, t, without, ctor in (("weight", weight, "one", "weight"), ("depth_weight", depth_weight, "one", "depth_weight"),
+                                      ("gt_depth", gt_depth, "depth supervision", "gt_depth / lambda_depth")):
+            if t is not None:
+                if self._slots[arg] is None:
+                    raise ValueError(f"GraphedStep: {arg} given to a step built without {without} (pass {ctor} to the constructor)")
+                self._slots[arg].load(t)
         if camera is not None:
             for k in self._BAKED:
                 assert float(getattr(camera, k)) == float(getattr(self.cam, k)), f"{k} is baked into the graph"
             self.view.copy_(camera.d_world_view_transform); self.proj.copy_(camera.d_full_proj_transform); self.campos.copy_(camera.d_camera_center)
             self.cam = camera
             self._pose_host = self._pose_of(camera)
-        if gt_image is not None and gt_image.data_ptr() != self.gt.data_ptr():
-            self.gt.copy_(gt_image)
-            self._gt_serial = getattr(self, "_gt_serial", 0) + 1
+        if gt_image is not None:
+            self._slots["gt_image"].load(gt_image)
 
-    def _snapshot(self, gt_image, gt_depth=None, weight=None, depth_weight=None, view=None):
+    def _snapshot(self, gt_image=None, gt_depth=None, weight=None, depth_weight=None):
         """What a repeat of this step needs, independent of what the caller does to its objects afterwards: the pose by VALUE (host copies of the
-        35 floats that are loaded now) and the target by reference together with the evidence that it is still the same data (the tensor's
-        version counter; for gt_image=None — "the target that is loaded" — the serial number of the load)."""
-        if getattr(self, "_pose_host", None) is None:
-            self._pose_host = self._pose_of(self.cam)
+        35 floats that are loaded now), the exposure row and keyframe slot that are loaded (the slot with its serial number), and every image by
+        reference together with the evidence that it is still the same data (_StepInput.snapshot: the tensor's version counter; for None — "the
+        one that is loaded" — the serial number of the load)."""
+        given = dict(gt_image=gt_image, gt_depth=gt_depth, weight=weight, depth_weight=depth_weight)
         kf = self.keyframes
-        return dict(frame=None if kf is None else self._kf_host, frame_serial=None if kf is None else kf.serial(self._kf_host),
-                    view=getattr(self, "_ex_view_host", None), pose=self._pose_host, gt=gt_image, gt_version=None if gt_image is None else gt_image._version, gt_serial=getattr(self, "_gt_serial", 0),
-                    gtd=gt_depth, gtd_version=None if gt_depth is None else gt_depth._version, gtd_serial=getattr(self, "_gtd_serial", 0),
-                    w=weight, w_version=None if weight is None else weight._version, w_serial=getattr(self, "_w_serial", 0),
-                    dw=depth_weight, dw_version=None if depth_weight is None else depth_weight._version, dw_serial=getattr(self, "_dw_serial", 0))
+        return dict(frame=self._kf_host, frame_serial=None if kf is None else kf.serial(self._kf_host), view=self._ex_view_host, pose=self._pose_host,
+                    images={arg: slot.snapshot(given[arg]) for arg, slot in self._slots.items() if slot is not None})
 
     def _load_snapshot(self, snap):
         dev = self.view.device
         v, p, c = snap["pose"]
         self.view.copy_(torch.from_numpy(v).to(dev)); self.proj.copy_(torch.from_numpy(p).to(dev)); self.campos.copy_(torch.from_numpy(c).to(dev))
         self._pose_host = snap["pose"]
-        if self.exposure is not None and snap.get("view") is not None:
+        if snap["view"] is not None:
             self._load(None, None, view=snap["view"])
         if self.keyframes is not None:
             if self.keyframes.serial(snap["frame"]) != snap["frame_serial"]:
                 raise RuntimeError(f"GraphedStep: slot {snap['frame']} of the keyframe store was replaced (put) after a step that has to be repeated "
                                    "was issued on it")
             self._load(None, None, frame=snap["frame"])
-        gt = snap["gt"]
-        if gt is None:
-            if snap["gt_serial"] != getattr(self, "_gt_serial", 0):
-                raise RuntimeError("GraphedStep: a step that has to be repeated ran on a target that has been replaced since (it was issued with "
-                                   "gt_image=None); pass the target explicitly to step() when targets change between checks")
-        else:
-            if gt._version != snap["gt_version"]:
-                raise RuntimeError("GraphedStep: the ground-truth tensor of a step that has to be repeated was modified in place after the step was issued")
-            if gt.data_ptr() != self.gt.data_ptr():
-                self.gt.copy_(gt)
-                self._gt_serial = getattr(self, "_gt_serial", 0) + 1
-        if self.use_weight:
-            w = snap.get("w")
-            if w is None:
-                if snap.get("w_serial", 0) != getattr(self, "_w_serial", 0):
-                    raise RuntimeError("GraphedStep: a step that has to be repeated ran on a weight image that has been replaced since (it was issued "
-                                       "with weight=None); pass the weight explicitly to step() when it changes between checks")
-            else:
-                if w._version != snap["w_version"]:
-                    raise RuntimeError("GraphedStep: the weight image of a step that has to be repeated was modified in place after the step was issued")
-                if w.data_ptr() != self.weight.data_ptr():
-                    self.weight.copy_(w)
-                    self._w_serial = getattr(self, "_w_serial", 0) + 1
-        if self.use_depth_weight:
-            dw = snap.get("dw")
-            if dw is None:
-                if snap.get("dw_serial", 0) != getattr(self, "_dw_serial", 0):
-                    raise RuntimeError("GraphedStep: a step that has to be repeated ran on a depth weight image that has been replaced since (it was "
-                                       "issued with depth_weight=None); pass the depth weight explicitly to step() when it changes between checks")
-            else:
-                if dw._version != snap["dw_version"]:
-                    raise RuntimeError("GraphedStep: the depth weight image of a step that has to be repeated was modified in place after the step was issued")
-                if dw.data_ptr() != self.depth_weight.data_ptr():
-                    self.depth_weight.copy_(dw)
-                    self._dw_serial = getattr(self, "_dw_serial", 0) + 1
-        if not self.use_depth:
-            return
-        gtd = snap.get("gtd")
-        if gtd is None:
-            if snap.get("gtd_serial", 0) != getattr(self, "_gtd_serial", 0):
-                raise RuntimeError("GraphedStep: a step that has to be repeated ran on a depth target that has been replaced since (it was issued with "
-                                   "gt_depth=None); pass the depth target explicitly to step() when targets change between checks")
-        else:
-            if gtd._version != snap["gtd_version"]:
-                raise RuntimeError("GraphedStep: the depth target of a step that has to be repeated was modified in place after the step was issued")
-            if gtd.data_ptr() != self.gt_depth.data_ptr():
-                self.gt_depth.copy_(gtd)
-                self._gtd_serial = getattr(self, "_gtd_serial", 0) + 1
+        for arg, image in snap["images"].items():
+            self._slots[arg].restore(image)
 
     def _issue(self):
         now = (self.model.P, getattr(self.model, "layout_version", 0))
@@ -2388,7 +2356,7 @@ class GraphedStep:
                 break
             # which steps: one bit per issue index while the window is at most 32 steps long; a longer unchecked run (check_every = 0)
             # can only be repeated on the view that is loaded now
-            todo = [self.window[i] for i in range(min(issued, len(self.window))) if (failed_mask >> i) & 1] if issued <= 32 else [self._snapshot(None)] * missed
+            todo = [self.window[i] for i in range(min(issued, len(self.window))) if (failed_mask >> i) & 1] if issued <= 32 else [self._snapshot()] * missed
             self.cap_R = max(self.cap_R, int(max_R * self.headroom) + 65536)
             self.cap_B = max(self.cap_B, int(max_B * self.headroom) + 1024)
             if max_R > 0x7fffffff // 2 or bits & 16:

@@ -221,3 +221,107 @@ def test_graphed_step_repeats_with_the_pose_of_the_step_when_one_camera_object_m
     staging.add_(1.0)
     with pytest.raises(RuntimeError, match="modified in place"):
         gs2.check()
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_graphed_step_repeats_overflowed_steps_with_their_own_weights_and_view(use_graph):
+    """Every per-step input at once — camera, target, depth target, colour weight, depth weight, exposure view — on a step whose buffers hold some
+    views and not others: every view is trained exactly once, the ones that fitted in issue order and then the ones that did not, each on the
+    inputs it was ISSUED with, so the map and the exposure equal a training_step_fused run over that order bit for bit.  The last two steps pass
+    weight=None and depth_weight=None ("the one that is loaded"): such a step can only be repeated while nothing has been loaded since it was
+    issued, so they are the views that do not fit, issued last.  Both models train at a tenth of the default rates: at the default ones the
+    counts of those two views (119 735 on the initial map, cap_R 117 161) have fallen to 117 109 and 116 267 after the six steps before them and
+    they fit; at a tenth they are 119 532 and 119 385, and the largest of the six that fit is 114 956.  Then a repeat that has to put a weight
+    and a depth weight back which a later step replaced, and the refusals of a repeat: a weight or depth weight image modified in place after its
+    step, and a weight replaced after a step that was issued with weight=None."""
+    from gpu_helpers import assert_same_state, bits, model_state, training_model
+    from gaussian_lic_amd import rasterizer as rz
+    from gaussian_lic_amd import trainer
+    from gaussian_lic_amd.camera import synthetic_camera
+    from gaussian_lic_amd.synthetic import gt_image
+    dev = torch.device("cuda:0")
+    P, W, H, LAMBDA_D, HUBER = 40000, 320, 240, 0.5, 0.3
+    raw, sc, camd, cam0 = make_scene("random", P, W, H, 3, 8)
+    cams = [synthetic_camera(W, H, k).to_device(dev) for k in range(8)]
+    gts = [gt_image(H, W, seed=10 + k).to(dev) for k in range(8)]
+    gtds = [c.project_depth(raw["xyz"][::5].float() * 1.1).to(dev) for c in cams]
+    ws = [(torch.rand(H, W, generator=torch.Generator().manual_seed(100 + k)) * 1.2).to(dev) for k in range(8)]
+    dws = [trainer.range_weight(gtds[k], 0.05, 0.02 * (k + 1)) * (1.0 + 0.5 * k) for k in range(8)]
+    bg = torch.zeros(3, device=dev)
+    ex_g = trainer.Exposure(8, dev, lr=0.01)
+    ex_g.params.add_(torch.from_numpy(np.random.default_rng(3).uniform(-0.1, 0.1, (8, 3, 4)).astype(np.float32)).to(dev))
+    ex_e = ex_g.clone()
+    probe, e, Rs = training_model(raw), torch.empty(0, device=dev), []
+    with torch.no_grad():
+        for c in cams:
+            Rs.append(rz.rasterize_gaussians(bg, probe.xyz.detach(), e, probe.opacity.detach(), probe.scaling.detach(), probe.rotation.detach(), 1.0, e,
+                                             c.d_world_view_transform, c.d_full_proj_transform, float(c.tanfovx), float(c.tanfovy), H, W,
+                                             float(c.limx_neg), float(c.limx_pos), float(c.limy_neg), float(c.limy_pos), probe.features_dc.detach(),
+                                             probe.features_rest.detach(), 3, c.d_camera_center, False, False, False, raw_params=True)[0])
+    cap_R = (max(Rs) + sorted(Rs)[len(Rs) // 2]) // 2      # the larger views do not fit
+    fits = [r <= cap_R - 64 for r in Rs]
+    assert any(fits) and not all(fits)
+    print(f"Rs {Rs} cap_R {cap_R} fits {fits}")
+
+    def fresh():
+        m = trainer.GaussianModel({k: (v.clone() if torch.is_tensor(v) else v) for k, v in raw.items()}, dev)
+        m.training_setup({name: 0.1 * lr for name, lr in trainer.DEFAULT_LRS.items()})
+        return m
+
+    def graphed(model, k, exposure=None):
+        return trainer.GraphedStep(model, cams[k], gts[k], bg, check_every=0, cap_R=cap_R, use_graph=use_graph, gt_depth=gtds[k], lambda_depth=LAMBDA_D,
+                                   weight=ws[k], depth_weight=dws[k], depth_huber=HUBER, exposure=exposure, view=k)
+    # the views in issue order: the ones that fit, then the ones that do not; the last two steps name no weight and no depth weight
+    order = [k for k in range(8) if fits[k]] + [k for k in range(8) if not fits[k]]
+    unnamed = (6, 7)
+    model = fresh()
+    gs = graphed(model, order[0], ex_g)
+    used = []                                               # (weight, depth weight) every step ran on
+    for i, k in enumerate(order):
+        if i in unnamed:
+            gs.step(cams[k], gts[k], gtds[k], view=k)
+            used.append(used[-1])
+        else:
+            gs.step(cams[k], gts[k], gtds[k], weight=ws[k], depth_weight=dws[k], view=k)
+            used.append((ws[k], dws[k]))
+    issued, mask, _max_R, _max_B = gs.bufs.read_window()
+    failed = [i for i in range(8) if (mask >> i) & 1]
+    print(f"order {order} failed steps {failed}")
+    assert issued == 8 and failed and any(i in failed for i in unnamed)
+    assert gs.check() == len(failed) and gs.recaptures >= 1
+    eager = fresh()
+    for i in [i for i in range(8) if i not in failed] + failed:
+        k = order[i]
+        trainer.training_step_fused(eager, cams[k], gts[k], bg, gt_depth=gtds[k], lambda_depth=LAMBDA_D, weight=used[i][0], depth_weight=used[i][1],
+                                    depth_huber=HUBER, exposure=ex_e, view=k)
+    assert_same_state(model_state(model), model_state(eager))
+    for a, b in ((ex_g.params, ex_e.params), (ex_g.m, ex_e.m), (ex_g.v, ex_e.v), (ex_g.steps, ex_e.steps)):
+        assert torch.equal(bits(a), bits(b))
+    assert ex_g.steps.tolist() == [1] * 8                   # every view's row was stepped once: a no-op step updates no row
+
+    # an overflowed step whose weight and depth weight a later step replaced: the repeat puts its own back
+    first, k_bad = fits.index(True), int(np.argmax(Rs))
+    step_kw = lambda k: dict(gt_depth=gtds[k], weight=ws[k], depth_weight=dws[k])
+    model1, eager1 = fresh(), fresh()
+    gs1 = graphed(model1, first)
+    for k in (k_bad, first):
+        gs1.step(cams[k], gts[k], **step_kw(k))
+    assert gs1.bufs.read_window()[:2] == (2, 1) and gs1.check() == 1
+    for k in (first, k_bad):
+        trainer.training_step_fused(eager1, cams[k], gts[k], bg, lambda_depth=LAMBDA_D, depth_huber=HUBER, **step_kw(k))
+    assert_same_state(model_state(model1), model_state(eager1))
+    # an image modified in place after its (overflowed) step was issued: the repeat refuses
+    for name, match in (("weight", "weight image .* modified in place"), ("depth_weight", "depth weight image .* modified in place")):
+        gs2 = graphed(fresh(), first)
+        images = dict(weight=ws[k_bad], depth_weight=dws[k_bad])
+        images[name] = images[name].clone()
+        gs2.step(cams[k_bad], gts[k_bad], gtds[k_bad], **images)
+        images[name].mul_(0.5)
+        with pytest.raises(RuntimeError, match=match):
+            gs2.check()
+    # a weight replaced after an (overflowed) step that was issued with weight=None: the repeat refuses
+    gs3 = graphed(fresh(), first)
+    gs3.step(cams[k_bad], gts[k_bad], gtds[k_bad])
+    gs3.step(cams[first], gts[first], gtds[first], weight=ws[k_bad])
+    with pytest.raises(RuntimeError, match="ran on a weight image .* replaced since"):
+        gs3.check()

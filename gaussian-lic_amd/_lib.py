@@ -50,6 +50,15 @@ class ExposureAdam(ctypes.Structure):
                 ("lr", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("skip", ctypes.c_void_p)]
 
 
+class PoseAdam(ctypes.Structure):
+    """gslic_pose_adam: the [V,16] / [V,16] / [V,3] pose arrays, [V,6] moments and [V] step counts of trainer.PoseSet, the shared projection, the
+    device word that names the view, V, the two rates and torch.optim.Adam's scalars, and the optional device word that turns the step off."""
+    _fields_ = [("view_all", ctypes.c_void_p), ("proj_all", ctypes.c_void_p), ("campos_all", ctypes.c_void_p), ("m", ctypes.c_void_p),
+                ("v", ctypes.c_void_p), ("step_count", ctypes.c_void_p), ("projection", ctypes.c_void_p), ("view", ctypes.c_void_p),
+                ("n_views", ctypes.c_int32), ("lr_trans", ctypes.c_float), ("lr_rot", ctypes.c_float), ("beta1", ctypes.c_float),
+                ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("skip", ctypes.c_void_p)]
+
+
 EXPORTS = [
     "gslic_rasterize_forward", "gslic_rasterize_backward", "gslic_rasterize_backward_adam", "gslic_rasterize_backward_camera", "gslic_adam_update", "gslic_adam_update_groups",
     "gslic_fusedssim_forward", "gslic_fusedssim_backward", "gslic_knn_mean_dist2", "gslic_abi_version",
@@ -72,6 +81,7 @@ EXPORTS = [
     "gslic_geometry_images",
     "gslic_exposure_partials_count", "gslic_exposure_apply", "gslic_exposure_backward",
     "gslic_keyframe_decode", "gslic_keyframe_encode",
+    "gslic_pose_step", "gslic_pose_load",
 ]
 
 _lib = None
@@ -117,6 +127,8 @@ def lib():
     L.gslic_exposure_backward.argtypes = [i32, i32] + [vp] * 6 + [ctypes.POINTER(ExposureAdam), vp]   # H, W, E, image, dL_dout, dL_dimage, partials, dL_dE, adam, stream
     L.gslic_keyframe_decode.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp]   # W, H, level, color_slab, mask_slab, frame, n_frames, out, weight_out, stream
     L.gslic_keyframe_encode.argtypes = [i32, i32, vp, vp, vp, vp, i32, i32, vp]        # W, H, image, mask, color_slab, mask_slab, capacity, slot, stream
+    L.gslic_pose_step.argtypes = [ctypes.POINTER(PoseAdam), vp, vp, vp, vp, vp]   # descriptor, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, grad_out, stream
+    L.gslic_pose_load.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp]            # view_all, proj_all, campos_all, view_word, n_views, 3 outputs, stream
     # the rasterize entry points, from the pieces their signatures share (include/gslic_hip.h)
     prm, counts, adam = ctypes.POINTER(RasterParams), [ctypes.POINTER(i32), ctypes.POINTER(i32)], ctypes.POINTER(AdamFused)
     inputs = [vp] * 12                                 # background ... cam_pos (the backward: radii in place of opacities)

@@ -33,6 +33,7 @@ SOURCES = {
     "depth_loss.hip": [],    # its two kernels pin their own rounding (fp contract(off)): the gradient is held to autograd's bits
     "exposure.hip": ["-ffp-contract=off"],   # the 3x4 exposure model: every product and sum of the rule rounded on its own, apply and dL_dimage tested on bits
     "keyframes.hip": ["-ffp-contract=off"],  # the keyframe store: integer sums and one float multiply (decode), one product rounded on its own (encode), tested on bits
+    "pose.hip": ["-ffp-contract=off"],       # the pose set's step: every float32 product and sum of the rule rounded on its own, in the header's order
     "knn.hip": [],
     "extend.hip": ["-ffp-contract=off"],  # pixel assignment decides integers: canonical order like preprocess.hip
     "prune.hip": [],         # comparisons and copies only: no arithmetic a flag could change

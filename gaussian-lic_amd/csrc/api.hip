@@ -1449,6 +1449,58 @@ int gslic_keyframe_encode(int32_t W, int32_t H, const float* image, const float*
                            (hipStream_t)stream);
 }
 
+int gslic_pose_step(const gslic_pose_adam* d, const float* dL_dviewmatrix, const float* dL_dprojmatrix, const float* dL_dcampos, float* grad_out,
+                    void* stream)
+{
+    const char* fn = "pose step";
+    if (!d) return set_error(GSLIC_ERR_INVALID_ARG, "%s: the descriptor is NULL", fn);
+    if (d->n_views <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: n_views = %d is not positive", fn, d->n_views);
+    const size_t V = (size_t)d->n_views, f = sizeof(float);
+    const NamedRange state[8] = {{d->view_all, 16 * V * f, "view_all"}, {d->proj_all, 16 * V * f, "proj_all"}, {d->campos_all, 3 * V * f, "campos_all"},
+                                 {d->m, 6 * V * f, "m"}, {d->v, 6 * V * f, "v"}, {d->step_count, V * sizeof(int32_t), "step_count"},
+                                 {d->projection, 16 * f, "projection"}, {d->view, sizeof(int32_t), "view"}};
+    const NamedRange grads[4] = {{dL_dviewmatrix, 16 * f, "dL_dviewmatrix"}, {dL_dprojmatrix, 16 * f, "dL_dprojmatrix"}, {dL_dcampos, 3 * f, "dL_dcampos"},
+                                 {grad_out, 6 * f, "grad_out"}};
+    for (const auto& a : state)
+        if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, a.name);
+    for (const auto& a : grads)
+        if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, a.name);
+    for (const auto& g : grads)
+        for (const auto& a : state)
+            if (ranges_overlap(g, a)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s overlaps %s", fn, g.name, a.name);
+    for (int i = 0; i < 3; i++)
+        if (ranges_overlap(grads[3], grads[i])) return set_error(GSLIC_ERR_INVALID_ARG, "%s: grad_out overlaps %s", fn, grads[i].name);
+    const struct { float x; const char* name; bool below_one; } values[5] = {{d->lr_trans, "lr_trans", false}, {d->lr_rot, "lr_rot", false},
+                                                                             {d->beta1, "beta1", true}, {d->beta2, "beta2", true}, {d->eps, "eps", false}};
+    for (const auto& a : values) {
+        if (!(a.x >= 0.0f)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s = %g is NaN or negative", fn, a.name, (double)a.x);
+        if (a.below_one && !(a.x < 1.0f)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s = %g must be below 1", fn, a.name, (double)a.x);
+    }
+    return pose_step(d, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, grad_out, (hipStream_t)stream);
+}
+
+int gslic_pose_load(const float* view_all, const float* proj_all, const float* campos_all, const int32_t* view_word, int32_t n_views, float* view_out,
+                    float* proj_out, float* campos_out, void* stream)
+{
+    const char* fn = "pose load";
+    if (n_views <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: n_views = %d is not positive", fn, n_views);
+    const size_t V = (size_t)n_views, f = sizeof(float);
+    const NamedRange in[4] = {{view_all, 16 * V * f, "view_all"}, {proj_all, 16 * V * f, "proj_all"}, {campos_all, 3 * V * f, "campos_all"},
+                              {view_word, sizeof(int32_t), "view_word"}};
+    const NamedRange outs[3] = {{view_out, 16 * f, "view_out"}, {proj_out, 16 * f, "proj_out"}, {campos_out, 3 * f, "campos_out"}};
+    for (const auto& a : in)
+        if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, a.name);
+    for (const auto& a : outs)
+        if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, a.name);
+    for (int i = 0; i < 3; i++) {
+        for (const auto& a : in)
+            if (ranges_overlap(outs[i], a)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s overlaps %s", fn, outs[i].name, a.name);
+        for (int j = 0; j < i; j++)
+            if (ranges_overlap(outs[i], outs[j])) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s overlaps %s", fn, outs[i].name, outs[j].name);
+    }
+    return pose_load(view_all, proj_all, campos_all, view_word, n_views, view_out, proj_out, campos_out, (hipStream_t)stream);
+}
+
 int gslic_knn_mean_dist2(int32_t P, const float* points, float* mean_dists, gslic_alloc_fn scratch_alloc, void* scratch_ctx,
                          void* stream)
 {

@@ -260,4 +260,10 @@ int keyframe_decode(int W, int H, int level, const uint8_t* color, const uint8_t
                     hipStream_t s);
 int keyframe_encode(int W, int H, const float* image, const float* mask, uint8_t* color_slot, uint8_t* mask_slot, hipStream_t s);
 
+// pose.hip: the trainable pose set of gslic_pose_step / gslic_pose_load (arguments validated by the caller), one launch of one wave each: the
+// se(3) chain, Adam, retraction, Gram-Schmidt and recomposition on row *d->view; the copy of row *view_word into three caller-owned buffers
+int pose_step(const gslic_pose_adam* d, const float* dL_dviewmatrix, const float* dL_dprojmatrix, const float* dL_dcampos, float* grad_out, hipStream_t s);
+int pose_load(const float* view_all, const float* proj_all, const float* campos_all, const int32_t* view_word, int n_views, float* view_out,
+              float* proj_out, float* campos_out, hipStream_t s);
+
 }  // namespace gslic

@@ -178,6 +178,109 @@ struct Exposure {
     }
 };
 
+// Trainable keyframe poses on the device — the Python host's trainer.PoseSet: per view the three arrays the rasteriser reads (view, proj [V,16],
+// campos [V,3], the layout of FusedCamera's tensors), torch::optim::Adam's state on the six coordinates of a left se(3) increment (m, v [V,6],
+// steps [V] int32, bias-corrected, one rate for the translation and one for the rotation) and the shared projection [16].  gslic_pose_step — one
+// launch — chains the three camera gradients, steps the row and retracts the pose (the rule is written out in include/gslic_hip.h); grad [6] is
+// the last gradient.  load() takes a camera's three arrays as they are; row_camera() hands the row back as views (no copy, no synchronisation).
+struct PoseSet {
+    torch::Tensor view, proj;     // float32 [V,16]
+    torch::Tensor campos;         // float32 [V,3]
+    torch::Tensor m, v;           // float32 [V,6]
+    torch::Tensor steps;          // int32 [V]
+    torch::Tensor projection;     // float32 [16]: Camera.projection_matrix, element (r, c) at [4 c + r]
+    torch::Tensor grad;           // float32 [6]
+    torch::Tensor views;          // int32 [V] = 0 .. V-1: the device word that names view i is views[i]
+    torch::Tensor no_step;        // int32 [1] = 1: a skip word that is set (the chain alone)
+    float lr_trans, lr_rot, beta1, beta2, eps;
+    // projection16: the pose-independent projection the views share, 16 floats in any float32 tensor (host or device)
+    PoseSet(int64_t n_views, const torch::Tensor& projection16, torch::Device device = torch::kCUDA, float lr_rot_ = 1e-3f, float lr_trans_ = 1e-3f,
+            float beta1_ = 0.9f, float beta2_ = 0.999f, float eps_ = 1e-8f)
+        : lr_trans(lr_trans_), lr_rot(lr_rot_), beta1(beta1_), beta2(beta2_), eps(eps_)
+    {
+        TORCH_CHECK(n_views >= 1, "PoseSet: n_views must be at least 1");
+        TORCH_CHECK(projection16.numel() == 16 && projection16.scalar_type() == torch::kFloat32, "PoseSet: projection must be 16 float32 values");
+        const auto fo = torch::TensorOptions().dtype(torch::kFloat32).device(device);
+        view = torch::zeros({n_views, 16}, fo); proj = torch::zeros({n_views, 16}, fo); campos = torch::zeros({n_views, 3}, fo);
+        m = torch::zeros({n_views, 6}, fo); v = torch::zeros({n_views, 6}, fo);
+        steps = torch::zeros({n_views}, fo.dtype(torch::kInt32));
+        projection = projection16.reshape({16}).to(device).contiguous().clone();
+        grad = torch::zeros({6}, fo);
+        views = torch::arange(n_views, fo.dtype(torch::kInt32));
+        no_step = torch::ones({1}, fo.dtype(torch::kInt32));
+    }
+    int64_t n_views() const { return view.size(0); }
+    int64_t index(int64_t i) const
+    {
+        TORCH_CHECK(i >= 0 && i < n_views(), "PoseSet: view ", i, " is outside [0, ", n_views(), ")");
+        return i;
+    }
+    void load(int64_t i, const FusedCamera& cam)   // bit copies of the camera's three arrays; zero moments and step count
+    {
+        index(i);
+        view[i].copy_(cam.world_view_transform.reshape({16})); proj[i].copy_(cam.full_proj_transform.reshape({16})); campos[i].copy_(cam.camera_center.reshape({3}));
+        m[i].zero_(); v[i].zero_(); steps[i].zero_();
+    }
+    // The row as the camera a render takes: device VIEWS into the set (no copy, no synchronisation) with the image size and scalars of
+    // `intrinsics` — the Python host's pose(view), not its camera(view), which reads the row back into a host Camera.
+    FusedCamera row_camera(int64_t i, const FusedCamera& intrinsics) const
+    {
+        index(i);
+        FusedCamera cam = intrinsics;
+        cam.world_view_transform = view[i].view({4, 4}); cam.full_proj_transform = proj[i].view({4, 4}); cam.camera_center = campos[i];
+        return cam;
+    }
+    void reset_moments(int64_t i = -1)   // zero moments and step count: one view, or (i < 0) all of them and the last gradient
+    {
+        if (i < 0) { m.zero_(); v.zero_(); steps.zero_(); grad.zero_(); return; }
+        index(i);
+        m[i].zero_(); v[i].zero_(); steps[i].zero_();
+    }
+    // The set's state by value — what the Python host's state_dict / load_state_dict / clone carry: the rows, the moments, the step counts, the
+    // scalars and (clone) the last gradient.  copy_from refuses a set of another size or another projection.
+    void copy_from(const PoseSet& o)
+    {
+        TORCH_CHECK(o.n_views() == n_views(), "PoseSet: the state holds ", o.n_views(), " views, this object ", n_views());
+        TORCH_CHECK(torch::equal(o.projection.to(projection.device()), projection), "PoseSet: the state was saved under another projection");
+        view.copy_(o.view); proj.copy_(o.proj); campos.copy_(o.campos); m.copy_(o.m); v.copy_(o.v); steps.copy_(o.steps);
+        lr_trans = o.lr_trans; lr_rot = o.lr_rot; beta1 = o.beta1; beta2 = o.beta2; eps = o.eps;
+    }
+    PoseSet clone() const
+    {
+        PoseSet other(n_views(), projection, projection.device(), lr_rot, lr_trans, beta1, beta2, eps);
+        other.copy_from(*this);
+        other.grad.copy_(grad);
+        return other;
+    }
+    gslic_pose_adam descriptor(int64_t i, bool do_step = true) const
+    {
+        index(i);
+        gslic_pose_adam d{};
+        d.view_all = view.data_ptr<float>(); d.proj_all = proj.data_ptr<float>(); d.campos_all = campos.data_ptr<float>();
+        d.m = m.data_ptr<float>(); d.v = v.data_ptr<float>(); d.step_count = steps.data_ptr<int32_t>(); d.projection = projection.data_ptr<float>();
+        d.view = views.data_ptr<int32_t>() + i; d.n_views = (int32_t)n_views();
+        d.lr_trans = lr_trans; d.lr_rot = lr_rot; d.beta1 = beta1; d.beta2 = beta2; d.eps = eps;
+        d.skip = do_step ? nullptr : reinterpret_cast<const uint32_t*>(no_step.data_ptr<int32_t>());
+        return d;
+    }
+    // gslic_pose_step on gradients the caller holds: camg = dL_dviewmatrix [16], dL_dprojmatrix [16], dL_dcampos [3] in one device tensor of 35 floats
+    void adam_step(int64_t i, const torch::Tensor& camg, bool do_step = true)
+    {
+        TORCH_CHECK(camg.numel() == 35 && camg.scalar_type() == torch::kFloat32 && camg.is_contiguous(), "PoseSet: camg must be 35 contiguous float32 values");
+        const gslic_pose_adam d = descriptor(i, do_step);
+        const float* g = camg.data_ptr<float>();
+        const int rc = gslic_pose_step(&d, g, g + 16, g + 32, grad.data_ptr<float>(), current_stream());
+        TORCH_CHECK(rc == GSLIC_OK, "gslic_pose_step failed (", rc, "): ", gslic_last_error());
+    }
+    // gslic_pose_load: the row the device word names into three buffers (how a captured step reads its pose)
+    void load_row(const torch::Tensor& view_word, torch::Tensor& view_out, torch::Tensor& proj_out, torch::Tensor& campos_out) const
+    {
+        const int rc = gslic_pose_load(view.data_ptr<float>(), proj.data_ptr<float>(), campos.data_ptr<float>(), view_word.data_ptr<int32_t>(),
+                                       (int32_t)n_views(), view_out.data_ptr<float>(), proj_out.data_ptr<float>(), campos_out.data_ptr<float>(), current_stream());
+        TORCH_CHECK(rc == GSLIC_OK, "gslic_pose_load failed (", rc, "): ", gslic_last_error());
+    }
+};
+
 // The keyframes' ground-truth images on the device as 8-bit pixels — the Python host's trainer.KeyframeStore (gslic_keyframe_encode /
 // gslic_keyframe_decode; storage, decode and encode rules in include/gslic_hip.h).  color: uint8 [capacity,H,W,3] interleaved RGB; mask (masks =
 // true): uint8 [capacity,H,W], decoded into the float32 weight image the weighted loss takes.  target() is usable as it is as the gt_image (and weight)
@@ -790,6 +893,26 @@ public:
         if (!gt_depth.defined() || lambda_depth == 0.0f) return w ? pose_gradient_body(cam, gt_image, nullptr, 0.0f, terms_out, w, DepthLossOptions{}) : pose_gradient(cam, gt_image);
         return pose_gradient_body(cam, gt_image, &gt_depth, lambda_depth, terms_out, w, DepthLossOptions{depth_weight.defined() ? &depth_weight : nullptr, depth_huber});
     }
+    // The same gradient for row `view` of a PoseSet, with the chain on the DEVICE: the render is from the row (`cam` supplies the image size and the
+    // scalars), gslic_pose_step runs one launch behind the camera backward and leaves dL/d(rho, phi) in poses->grad — returned, a device [6]
+    // tensor; no synchronisation, no host copy.  do_step: the same launch also steps the row (Adam on the six coordinates, the retraction).  The
+    // calls gaussian-lic_amd/trainer.py:pose_gradient(poses=, view=, do_step=) issues.  gt_depth / lambda_depth / weight / depth_weight /
+    // depth_huber as above; with set_exposure, the exposure row that call named.
+    torch::Tensor pose_gradient(const FusedCamera& cam, const torch::Tensor& gt_image, PoseSet* poses, int view, bool do_step,
+                                const torch::Tensor& gt_depth = torch::Tensor(), float lambda_depth = 0.0f, torch::Tensor* terms_out = nullptr,
+                                const torch::Tensor& weight = torch::Tensor(), const torch::Tensor& depth_weight = torch::Tensor(), float depth_huber = 0.0f)
+    {
+        TORCH_CHECK(poses != nullptr, "pose_gradient: poses is NULL");
+        TORCH_CHECK(gt_depth.defined() || (!depth_weight.defined() && depth_huber == 0.0f), "depth_weight / depth_huber given without gt_depth");
+        const FusedCamera row = poses->row_camera(view, cam);
+        const torch::Tensor* w = weight.defined() ? &weight : nullptr;
+        const bool depth = gt_depth.defined() && lambda_depth != 0.0f;
+        torch::Tensor camg;
+        pose_gradient_body(row, gt_image, depth ? &gt_depth : nullptr, depth ? lambda_depth : 0.0f, terms_out, w,
+                           depth ? DepthLossOptions{depth_weight.defined() ? &depth_weight : nullptr, depth_huber} : DepthLossOptions{}, &camg);
+        poses->adam_step(view, camg, do_step);
+        return poses->grad;
+    }
     // the chain alone, on host arrays in the element order of the kernels' inputs (float[16] with (r, c) at [4c + r])
     static std::array<double, 6> se3_pose_gradient(const float* view16, const float* fullproj16, const float* dview16, const float* dproj16, const float* dcampos3)
     {
@@ -1052,7 +1175,8 @@ private:
     // the pose gradient: forward, loss, depth loss, camera backward, the chain on the host.  gt_depth != nullptr: under depth supervision.  (The
     // colour-only path runs the unweighted loss as gslic_l1_ssim_loss_forward + _backward, every other path as the fused pair: both as they were.)
     std::array<double, 6> pose_gradient_body(const FusedCamera& cam, const torch::Tensor& gt_image, const torch::Tensor* gt_depth, float lambda_depth,
-                                             torch::Tensor* terms_out, const torch::Tensor* weight, const DepthLossOptions& dlo)
+                                             torch::Tensor* terms_out, const torch::Tensor* weight, const DepthLossOptions& dlo,
+                                             torch::Tensor* camg_out = nullptr)   // camg_out: the 35 camera gradient floats stay on the device, no chain here
     {
         torch::NoGradGuard ng;
         const bool depth = gt_depth != nullptr;
@@ -1075,11 +1199,12 @@ private:
             colour_loss(H, W, exposure_apply(H, W, image), gt_image, weight, dm, partials, terms, dLo);   // (the fused pair, as the Python host's)
             exposure_backward(H, W, image, dLo, dL, /*adam=*/false);
         } else {
-            colour_loss(H, W, image, gt_image, weight, dm, partials, terms, dL, /*two_calls=*/!depth);
+            colour_loss(H, W, image, gt_image, weight, dm, partials, terms, dL, /*two_calls=*/!depth && !camg_out);   // (the pose-set route: the fused pair, as the Python host's)
         }
         if (depth) depth_loss(H, W, lambda_depth, zimg, *gt_depth, dpartials, terms, dLd, dlo);
         backward_camera(rp, cam, R, B, radii, dL, dLd, g, camg.data_ptr<float>());
         if (terms_out) *terms_out = terms;
+        if (camg_out) { *camg_out = camg; return {}; }
         torch::Tensor hc = camg.to(torch::kCPU), hv = cam.world_view_transform.to(torch::kCPU).contiguous(), hp = cam.full_proj_transform.to(torch::kCPU).contiguous();
         return se3_pose_gradient(hv.data_ptr<float>(), hp.data_ptr<float>(), hc.data_ptr<float>(), hc.data_ptr<float>() + 16, hc.data_ptr<float>() + 32);
     }

@@ -9,6 +9,7 @@ sparse-Adam update, so replicas stay bit-identical without a broadcast (SURVEY.m
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import loss as loss_utils
@@ -1621,6 +1622,170 @@ def _check_exposure(who, exposure, view):
     return exposure
 
 
+class PoseSet:
+    """Trainable keyframe poses on the device, the pose counterpart of Exposure: one row per view with the three arrays the rasteriser reads —
+    view [V,16], proj [V,16], campos [V,3], in the layout and meaning of Camera.world_view_transform, full_proj_transform and camera_center —
+    torch.optim.Adam's state on the six coordinates (rho, phi) of a LEFT se(3) increment (m, v [V,6], steps [V] int32, WITH bias correction, a
+    rate for the translation and one for the rotation) and, once per set, the pose-independent projection [16].  gslic_pose_step — one launch —
+    chains the three camera gradients of the backward to dL/d(rho, phi), steps the row by Adam and moves the pose by the exact retraction
+    T_cw <- exp(delta^) T_cw, with R re-orthonormalised (the rule is written out in include/gslic_hip.h, restated in float64 by tests/pose_ref.py);
+    grad [6] holds the last gradient.  Nothing here allocates or synchronises per step; camera() is the one call that reads back.
+
+    `camera` supplies what the views share: the projection_matrix and the scalars a step bakes in (tanfov, the four limits).  All of them
+    depend only on fx / W, cx / W, fy / H, cy / H (and the depth range), not on the image size, so one set serves every pyramid level l of a
+    KeyframeStore whose width and height are divisible by 2^l (Camera.at_level halves W, H and the four intrinsics exactly; an odd size drops a
+    column and changes cx / W): a step takes the image size from ITS camera and the pose from the set, and matches(camera.at_level(l)) says
+    whether the set serves that camera.  Nothing the kernels read from the set depends on the image size."""
+
+    _BAKED = ("tanfovx", "tanfovy", "limx_neg", "limx_pos", "limy_neg", "limy_pos")   # (level-invariant, like the projection)
+
+    def __init__(self, n_views, camera, device, lr_rot=1e-3, lr_trans=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        V = int(n_views)
+        if V < 1:
+            raise ValueError(f"PoseSet: n_views = {n_views} must be at least 1")
+        self.lr_rot, self.lr_trans = float(lr_rot), float(lr_trans)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        if not (self.lr_rot >= 0.0 and self.lr_trans >= 0.0 and 0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0 and self.eps >= 0.0):
+            raise ValueError(f"PoseSet: lr_rot = {lr_rot}, lr_trans = {lr_trans}, betas = {betas}, eps = {eps} must be >= 0 and the betas below 1")
+        self.device = dev = torch.device(device)
+        self._intrinsics = camera   # (fx, fy, cx, cy, znear, zfar and the image size of the cameras camera() returns)
+        self._projection_host = np.array(camera.projection_matrix, np.float32).reshape(16)
+        self._baked = tuple(float(getattr(camera, k)) for k in self._BAKED)
+        self.projection = torch.from_numpy(self._projection_host.copy()).to(dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.view, self.proj, self.campos = torch.zeros(V, 16, **f32), torch.zeros(V, 16, **f32), torch.zeros(V, 3, **f32)
+        self.m, self.v = torch.zeros(V, 6, **f32), torch.zeros(V, 6, **f32)
+        self.steps = torch.zeros(V, dtype=torch.int32, device=dev)
+        self.grad = torch.zeros(6, **f32)
+        self._views = torch.arange(V, dtype=torch.int32, device=dev)    # the device word that names view i is _views[i]: no copy per step
+        self._no_step = torch.ones(1, dtype=torch.int32, device=dev)    # a skip word that is set: the chain alone (do_step=False)
+        for i in range(V):   # every row starts as the camera's own pose
+            self.load(i, camera)
+
+    @property
+    def n_views(self):
+        return self.view.size(0)
+
+    def _index(self, view):
+        v = int(view)
+        if not 0 <= v < self.n_views:
+            raise IndexError(f"PoseSet: view {view} is outside [0, {self.n_views})")
+        return v
+
+    def matches(self, camera):
+        """Whether the set serves `camera`: the set's projection_matrix and baked scalars (tanfov, the four limits) bit for bit.  The image size
+        is not compared: a camera of another pyramid level of the same intrinsics matches."""
+        same = np.array_equal(np.asarray(camera.projection_matrix, np.float32).reshape(16).view(np.int32), self._projection_host.view(np.int32))
+        return same and tuple(float(getattr(camera, k)) for k in self._BAKED) == self._baked
+
+    def _check_camera(self, who, camera):
+        if not self.matches(camera):
+            raise ValueError(f"{who}: the camera's projection_matrix or baked scalars (tanfov, limits) differ from the pose set's")
+
+    def load(self, view, camera):
+        """Row `view` becomes a bit copy of the camera's three arrays, with zero moments and step count."""
+        i = self._index(view)
+        self._check_camera("PoseSet.load", camera)
+        put = lambda dst, a, n: dst.copy_(torch.from_numpy(np.ascontiguousarray(a, np.float32).reshape(n)))
+        put(self.view[i], camera.world_view_transform, 16); put(self.proj[i], camera.full_proj_transform, 16); put(self.campos[i], camera.camera_center, 3)
+        self.reset_moments(i)
+
+    def pose(self, view):
+        """(view [16], proj [16], campos [3]) of a row: device views into the set (no copy), usable as _RawRaster(..., pose=...)."""
+        i = self._index(view)
+        return self.view[i], self.proj[i], self.campos[i]
+
+    def camera(self, view, level=0):
+        """A new host Camera at the row's pose (this call synchronises: it is for saving trajectories): the intrinsics of the set's camera — at
+        pyramid level `level` of it (Camera.at_level) — set_pose from the row's R, t, and then the row's own bits as its three arrays, host and
+        device, so that it renders exactly what the row renders."""
+        from .camera import Camera
+        i, c = self._index(view), self._intrinsics.at_level(level)
+        V = self.view[i].cpu().numpy().astype(np.float64).reshape(4, 4).T
+        R, t = V[:3, :3], V[:3, 3]
+        cam = Camera(c.image_width, c.image_height, c.fx, c.fy, c.cx, c.cy, R.T, -R.T @ t, c.znear, c.zfar)
+        cam.world_view_transform = self.view[i].cpu().numpy().reshape(4, 4).copy()
+        cam.full_proj_transform = self.proj[i].cpu().numpy().reshape(4, 4).copy()
+        cam.camera_center = self.campos[i].cpu().numpy().copy()
+        return cam.to_device(self.view.device)
+
+    def reset_moments(self, view=None):
+        """Zero moments and step count: one view, or all of them (then the last gradient too)."""
+        rows = slice(None) if view is None else slice(self._index(view), self._index(view) + 1)
+        self.m[rows] = 0
+        self.v[rows] = 0
+        self.steps[rows] = 0
+        if view is None:
+            self.grad.zero_()
+
+    def state_dict(self):
+        return dict(view=self.view.clone(), proj=self.proj.clone(), campos=self.campos.clone(), projection=self.projection.clone(), m=self.m.clone(),
+                    v=self.v.clone(), steps=self.steps.clone(), lr_rot=self.lr_rot, lr_trans=self.lr_trans, betas=self.betas, eps=self.eps)
+
+    def load_state_dict(self, state):
+        if tuple(state["view"].shape) != tuple(self.view.shape):
+            raise ValueError(f"PoseSet: the state holds {tuple(state['view'].shape)}, this object {tuple(self.view.shape)}")
+        if not torch.equal(state["projection"].to(self.device).view(torch.int32), self.projection.view(torch.int32)):
+            raise ValueError("PoseSet: the state was saved under another projection_matrix")
+        for k in ("view", "proj", "campos", "m", "v", "steps"):
+            getattr(self, k).copy_(state[k])
+        self.lr_rot, self.lr_trans, self.eps = float(state["lr_rot"]), float(state["lr_trans"]), float(state["eps"])
+        self.betas = (float(state["betas"][0]), float(state["betas"][1]))
+
+    def clone(self):
+        other = PoseSet(self.n_views, self._intrinsics, self.device, self.lr_rot, self.lr_trans, self.betas, self.eps)
+        other.load_state_dict(self.state_dict())
+        other.grad.copy_(self.grad)
+        return other
+
+    def _descriptor(self, view_word, skip=None):
+        """gslic_pose_adam on this object's arrays; view_word: a device int32 [1] that names the row, skip: the optional device word."""
+        from . import _lib
+        p = lambda t: t.data_ptr()
+        return _lib.PoseAdam(p(self.view), p(self.proj), p(self.campos), p(self.m), p(self.v), p(self.steps), p(self.projection), p(view_word),
+                             self.n_views, self.lr_trans, self.lr_rot, self.betas[0], self.betas[1], self.eps, None if skip is None else p(skip))
+
+    def _step(self, view, cam_grads, do_step=True):
+        """gslic_pose_step on row `view`: grad <- the chain of the three camera gradients; do_step: the row moves (else the skip word is set)."""
+        import ctypes
+        from . import _lib
+        i = self._index(view)
+        gv, gp, gc = cam_grads
+        for t, n, name in ((gv, 16, "dL_dviewmatrix"), (gp, 16, "dL_dprojmatrix"), (gc, 3, "dL_dcampos")):
+            if t.numel() != n or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.view.device:
+                raise ValueError(f"PoseSet: {name} must be {n} contiguous float32 values on the set's device")
+        d = self._descriptor(self._views[i:i + 1], None if do_step else self._no_step)
+        _lib.check(_lib.lib().gslic_pose_step(ctypes.byref(d), _lib.ptr(gv), _lib.ptr(gp), _lib.ptr(gc), _lib.ptr(self.grad), _lib.current_stream_ptr()))
+        return self.grad
+
+    def adam_step(self, view, cam_grads):
+        """The kernel on gradients the caller already holds: cam_grads = (dL_dviewmatrix [16], dL_dprojmatrix [16], dL_dcampos [3]) device tensors,
+        as a backward with camera_grads=True returns them.  Returns grad."""
+        return self._step(view, cam_grads, True)
+
+    def _load_row(self, view_word, view_out, proj_out, campos_out):
+        """gslic_pose_load: the row the device word names into three buffers (GraphedStep's static pose), one launch."""
+        from . import _lib
+        p = _lib.ptr
+        _lib.check(_lib.lib().gslic_pose_load(p(self.view), p(self.proj), p(self.campos), p(view_word), self.n_views, p(view_out), p(proj_out),
+                                              p(campos_out), _lib.current_stream_ptr()))
+
+
+def _check_poses(who, poses, view, camera=None):
+    """The checks every step makes on its poses= argument (None passes): a PoseSet, one GPU, a view it has, a camera of the set's intrinsics."""
+    if poses is None:
+        return None
+    if not isinstance(poses, PoseSet):
+        raise ValueError(f"{who}: poses must be a trainer.PoseSet")
+    if _dist_on():
+        raise NotImplementedError(f"{who}: poses is single-GPU only: the N > 1 gradient exchange carries no camera gradient (every rank would "
+                                  "step its own copy of the pose from its own view)")
+    poses._index(view)
+    if camera is not None:
+        poses._check_camera(who, camera)
+    return poses
+
+
 def _exposure_losses(fl, image, gt_image, depth, gt_depth, lambda_depth, weight, depth_weight, depth_huber, exposure, view, exposure_step):
     """_fused_losses under an exposure model: E applied into a scratch image of the FusedLoss, the loss calls — unchanged — on that image, then
     the exposure backward on their dL/dimage, which hands the rasteriser E^T g, leaves dL/dE in exposure.grad and (exposure_step) updates the
@@ -1823,7 +1988,7 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
 
 
 def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None, depth_weight=None, depth_huber=0.0,
-                  exposure=None, view=0):
+                  exposure=None, view=0, poses=None, do_step=False):
     """dL/dxi of the training loss w.r.t. a left se(3) increment of the camera pose (Camera.pose_gradient) for the current map: forward -> loss
     kernels -> gslic_rasterize_backward_camera -> the chain.  The map is not touched.  Returns (float64 [6] = (d/drho, d/dphi), terms).
     One step of pose refinement is `camera.apply_pose_increment(-lr * g); camera.to_device(dev)`.
@@ -1832,21 +1997,30 @@ def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, l
     then [mean L1, mean SSIM, L_d].  gt_depth=None or lambda_depth=0 is exactly the colour-only path.
     weight [H,W]: the weighted colour loss (FusedLoss.forward_backward); it combines freely with gt_depth.
     depth_weight [H,W] / depth_huber: the weighted / Huber depth term, as training_step_fused's.
-    exposure / view: the loss of the exposure-compensated image, as training_step_fused's; exposure.grad is written, E is not updated."""
+    exposure / view: the loss of the exposure-compensated image, as training_step_fused's; exposure.grad is written, E is not updated.
+    poses (a trainer.PoseSet) / view: the render is from row `view` of the set (`camera` supplies only the intrinsics and must match the set's) and
+    the chain runs on the device (gslic_pose_step, one launch behind the backward): returns (poses.grad [6] float32 DEVICE tensor, terms) with no
+    synchronisation and no host copy.  do_step=True also steps the row (Adam and the retraction, in the same launch); view names the exposure's
+    row as well when both are given."""
     fl = fused_loss or _default_fused_loss()
     use_depth = _use_depth("pose_gradient", gt_depth, lambda_depth, depth_weight, depth_huber)
     exposure = _check_exposure("pose_gradient", exposure, view)
+    poses = _check_poses("pose_gradient", poses, view, camera)
+    if poses is None and do_step:
+        raise ValueError("pose_gradient: do_step=True needs poses= (a trainer.PoseSet holds the optimiser's state)")
     with torch.no_grad():
-        rr = _RawRaster(model, camera, bg, use_depth)
+        rr = _RawRaster(model, camera, bg, use_depth, pose=None if poses is None else poses.pose(view))
         image, depth, _radii = rr.forward()
         dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber,
                                                     exposure, view, False)
         out = rr.backward(dL_dimage, dL_ddepth, camera_grads=True)
+        if poses is not None:
+            return poses._step(view, out[9:12], do_step), terms
     return camera.pose_gradient(out[9], out[10], out[11]), terms
 
 
 def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None, grad_stats=None,
-                            depth_weight=None, depth_huber=0.0, exposure=None, view=0):
+                            depth_weight=None, depth_huber=0.0, exposure=None, view=0, poses=None):
     """One joint map + pose iteration: forward -> loss kernels -> gslic_rasterize_backward_camera (parameter gradients AND the camera gradient in
     one pass) -> masked Adam on the map -> `camera` moved by -pose_lr * dL/dxi (left se(3) increment; 35 floats cross to the host, which is the
     step's only synchronisation).  Returns (terms, visible, dL/dxi).
@@ -1855,16 +2029,24 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
     gt_depth=None or lambda_depth=0 is exactly the colour-only step.  weight [H,W]: the weighted colour loss, as training_step_fused's.
     grad_stats (a GradientStats of this model): the backward also writes dL_dmeans2D, which one small kernel adds to the statistics.
     depth_weight [H,W] / depth_huber: the weighted / Huber depth term, as training_step_fused's.
-    exposure / view: the exposure model of the view, applied and updated as training_step_fused's."""
+    exposure / view: the exposure model of the view, applied and updated as training_step_fused's.
+    poses (a trainer.PoseSet) / view: the same joint iteration on row `view` of the set — the render is from the row (`camera` supplies only the
+    intrinsics and must match the set's), and the pose step is ONE launch behind the map's Adam (gslic_pose_step: chain, Adam on the six tangent
+    coordinates with the set's two rates, retraction): no host copy of the 35 floats, no numpy, no to_device, no synchronisation.  Returns
+    (terms, visible, poses.grad [6] float32 DEVICE tensor).  pose_lr != 0 together with poses= raises (the set has its own rates); with exposure=
+    as well, view names both rows."""
     fl = fused_loss or _default_fused_loss()
     use_depth = _use_depth("training_step_with_pose", gt_depth, lambda_depth, depth_weight, depth_huber)
     exposure = _check_exposure("training_step_with_pose", exposure, view)
+    poses = _check_poses("training_step_with_pose", poses, view, camera)
+    if poses is not None and pose_lr:
+        raise ValueError("training_step_with_pose: pose_lr != 0 given together with poses= (the pose set steps by its own lr_rot / lr_trans)")
     grad_stats = _grad_stats_for_step(grad_stats, model)
     cam = camera
     with torch.no_grad():
         if use_depth:
             _grad_slab(model)   # (the depth step sets the slab up ahead of its forward, the colour step behind its loss: both as they were)
-        rr = _RawRaster(model, cam, bg, use_depth)
+        rr = _RawRaster(model, cam, bg, use_depth, pose=None if poses is None else poses.pose(view))
         image, depth, radii = rr.forward()
         dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber,
                                                     exposure, view)
@@ -1875,6 +2057,8 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
         visible = radii > 0
         model.optimizer.set_visibility_and_N(visible, model.P)
         model.optimizer.step(slab.grads(model))
+        if poses is not None:
+            return terms, visible, poses._step(view, out[9:12])
         g = cam.pose_gradient(out[9], out[10], out[11])
         if pose_lr:
             cam.apply_pose_increment(-float(pose_lr) * g).to_device(model.device)
@@ -2086,11 +2270,19 @@ class GraphedStep:
     weight buffer from the same launch: the step is then a weighted step.  The launch is given the store's CAPACITY as its frame count (frames
     added after a capture stay reachable); the index is validated against the filled slots on the host before the word is written.  A repeated step
     uses its own frame index and the slot's serial number: a slot replaced (put) since the step was issued fails loudly.  gt_image together with
-    a store, or frame given to a step built without one, raises.  Without keyframes the step is what it was, launch for launch."""
+    a store, or frame given to a step built without one, raises.  Without keyframes the step is what it was, launch for launch.
+
+    poses (a trainer.PoseSet) / view: the step READS its pose from the set: one gslic_pose_load launch inside the step fills the static view / proj /
+    campos buffers from the row a device int32 names; step(view=j) fills that word (and the exposure's, when there is one: view names both rows),
+    so a captured graph changes keyframe pose without a host copy or a re-capture.  `camera` supplies the intrinsics and must match the set's;
+    step(camera=...) on such a step raises.  The step does NOT train the pose (the fused-Adam backward kernels have no camera variant): pose steps
+    are issued between graphed steps through pose_gradient(..., poses=, do_step=True) or training_step_with_pose(poses=).  A repeated step (the
+    overflow window) repeats with its view index and reads the row AS IT IS THEN — a pose step issued since moves the repeat with it.  poses=None
+    is the step as it was, launch for launch."""
 
     def __init__(self, model, camera, gt_image, bg, headroom=1.25, check_every=16, cap_R=None, cap_B=None, use_graph=False, gt_depth=None,
                  lambda_depth=0.0, weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0, exposure=None, view=0, keyframes=None,
-                 frame=None, level=0):
+                 frame=None, level=0, poses=None):
         """use_graph=False (default since round 5): the capacity-mode step (caller-owned scratch, no host round trip, overflow checks and repeats as
         below) issued as eager launches; use_graph=True: captured in a hipGraph and replayed with one launch per step.  The two are equally fast at
         2M Gaussians (bench.py: `capacity_eager` / `graphed`; the host runs ahead of the device either way), and the eager form has no hazard:
@@ -2127,6 +2319,12 @@ class GraphedStep:
         self.proj = camera.d_full_proj_transform.clone()
         self.campos = camera.d_camera_center.clone()
         self._pose_host = self._pose_of(camera)
+        self.poses = _check_poses("GraphedStep", poses, view, camera)
+        self._pose_view_host = None if self.poses is None else int(view)                     # the row that is loaded
+        if self.poses is not None:
+            self._pose_word = torch.full((1,), int(view), dtype=torch.int32, device=dev)     # which row: filled by _load
+            self.poses._load_row(self._pose_word, self.view, self.proj, self.campos)         # (the sizing forward below renders from the row)
+            self._pose_host = None                                                           # the pose is the row's, read inside the step
         kf_weight = None
         if keyframes is None:
             self.gt = gt_image.clone()
@@ -2185,6 +2383,8 @@ class GraphedStep:
     def _eager(self):
         if self.keyframes is not None:
             self.keyframes._decode(self._kf_word, self.level, self.gt, self.weight, n_frames=self.keyframes.capacity)
+        if self.poses is not None:
+            self.poses._load_row(self._pose_word, self.view, self.proj, self.campos)
         rr = _RawRaster(self.model, self.cam, self.bg, self.use_depth, e=self.e, pose=(self.view, self.proj, self.campos))
         image, depth, _radii = rr.forward(self.bufs)
         if self.exposure is None:
@@ -2260,12 +2460,17 @@ class GraphedStep:
                 self._kf_word.fill_(self._kf_host)
             if camera is not None:
                 camera = self._kf_camera(camera)
+        if camera is not None and self.poses is not None:
+            raise ValueError("GraphedStep: camera given to a step built on a pose set (its pose is read from the set inside the step: pass view=)")
         if view is not None:
-            if self.exposure is None:
-                raise ValueError("GraphedStep: view given to a step built without an exposure (pass exposure to the constructor)")
-            if self.exposure._index(view) != self._ex_view_host:
+            if self.exposure is None and self.poses is None:
+                raise ValueError("GraphedStep: view given to a step built without an exposure or a pose set (pass exposure or poses to the constructor)")
+            if self.exposure is not None and self.exposure._index(view) != self._ex_view_host:
                 self._ex_view_host = self.exposure._index(view)
                 self._ex_view.fill_(self._ex_view_host)
+            if self.poses is not None and self.poses._index(view) != self._pose_view_host:
+                self._pose_view_host = self.poses._index(view)
+                self._pose_word.fill_(self._pose_view_host)
         if weight is False:   # "this step runs without a weight": true only of a step that was built without one
             if self.use_weight:
                 raise ValueError("GraphedStep: this step was built with a weight and always runs the weighted loss (pass ones to weigh every pixel "
@@ -2293,14 +2498,16 @@ class GraphedStep:
         one that is loaded" — the serial number of the load)."""
         given = dict(gt_image=gt_image, gt_depth=gt_depth, weight=weight, depth_weight=depth_weight)
         kf = self.keyframes
-        return dict(frame=self._kf_host, frame_serial=None if kf is None else kf.serial(self._kf_host), view=self._ex_view_host, pose=self._pose_host,
+        view = self._ex_view_host if self.poses is None else self._pose_view_host   # (one index names both rows)
+        return dict(frame=self._kf_host, frame_serial=None if kf is None else kf.serial(self._kf_host), view=view, pose=self._pose_host,
                     images={arg: slot.snapshot(given[arg]) for arg, slot in self._slots.items() if slot is not None})
 
     def _load_snapshot(self, snap):
         dev = self.view.device
-        v, p, c = snap["pose"]
-        self.view.copy_(torch.from_numpy(v).to(dev)); self.proj.copy_(torch.from_numpy(p).to(dev)); self.campos.copy_(torch.from_numpy(c).to(dev))
-        self._pose_host = snap["pose"]
+        if snap["pose"] is not None:   # (None: a step on a pose set reads the row its view index names, inside the step)
+            v, p, c = snap["pose"]
+            self.view.copy_(torch.from_numpy(v).to(dev)); self.proj.copy_(torch.from_numpy(p).to(dev)); self.campos.copy_(torch.from_numpy(c).to(dev))
+            self._pose_host = snap["pose"]
         if snap["view"] is not None:
             self._load(None, None, view=snap["view"])
         if self.keyframes is not None:
@@ -2331,8 +2538,8 @@ class GraphedStep:
     def step(self, camera=None, gt_image=None, gt_depth=None, weight=None, depth_weight=None, view=None, frame=None):
         """One optimiser step (replay).  Returns the device tensor [mean L1, mean SSIM] of this step's loss terms ([mean L1, mean SSIM, L_d]
         with depth supervision; gt_depth: this step's depth target, None = the one that is loaded; weight: this step's weight image, likewise;
-        depth_weight: this step's depth weight image, likewise; view: the row of the exposure this step applies and updates, likewise; frame: the
-        slot of the keyframe store this step trains on, likewise)."""
+        depth_weight: this step's depth weight image, likewise; view: the row of the exposure this step applies and updates and / or the row of
+        the pose set it renders from, likewise; frame: the slot of the keyframe store this step trains on, likewise)."""
         self._load(camera, gt_image, gt_depth, weight, depth_weight, view, frame)
         self._issue()
         self.steps_issued += 1

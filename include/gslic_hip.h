@@ -727,6 +727,78 @@ int gslic_keyframe_encode(
     int32_t W, int32_t H, const float* image /*[3,H,W] or NULL*/, const float* mask /*[H,W] or NULL*/, uint8_t* color_slab, uint8_t* mask_slab,
     int32_t capacity, int32_t slot, void* stream);
 
+/* gslic_pose_step / gslic_pose_load — a set of trainable keyframe poses on the device (additive, ABI 8; the reference optimises no pose:
+ * rasterizer.cpp:171-182 drops the camera gradient).  Per view i the set holds view[i,16], proj[i,16] and campos[i,3] in exactly the layout and
+ * meaning of the viewmatrix, projmatrix and cam_pos arguments of the rasteriser (element (r, c) at [4 c + r]; V = [R | t; 0 0 0 1] the world-to-camera
+ * matrix, proj = Pm V, campos = -R^T t), the Adam moments m[i,6], v[i,6] and the step count steps[i]; once per set the pose-independent projection
+ * Pm[16] (same layout).  gslic_pose_step is ONE launch of one wave on row *view, read ON THE DEVICE so that a captured graph can change views.
+ * Every product and sum below is ONE IEEE float32 operation rounded on its own, in the order the parentheses give (no contraction; sums of
+ * products run over k ascending, ((p0 + p1) + p2) + p3), except where DOUBLE is named.  One lane runs the whole rule: no sum depends on a
+ * reduction order.  With Gv(r,c) = dL_dviewmatrix[4 c + r], Gp(r,c) = dL_dprojmatrix[4 c + r], gc = dL_dcampos:
+ *
+ * CHAIN (Camera.pose_gradient of camera.py, term by term), r = 0..2:
+ *   G(r,c)  = Gv(r,c) + (((Pm(0,r) Gp(0,c) + Pm(1,r) Gp(1,c)) + Pm(2,r) Gp(2,c)) + Pm(3,r) Gp(3,c))                    c = 0..3
+ *   GR(r,c) = G(r,c) - t_r gc_c   (c = 0..2),      Gt_r = G(r,3) - ((R(r,0) gc_0 + R(r,1) gc_1) + R(r,2) gc_2)
+ *   M(r,c)  = (GR(r,0) R(c,0) + GR(r,1) R(c,1)) + GR(r,2) R(c,2)
+ *   g = (Gt_0, Gt_1, Gt_2,  (M(2,1) - M(1,2)) + (t_1 Gt_2 - t_2 Gt_1),  (M(0,2) - M(2,0)) + (t_2 Gt_0 - t_0 Gt_2),  (M(1,0) - M(0,1)) + (t_0 Gt_1 - t_1 Gt_0))
+ * g — dL/d(rho, phi) of the LEFT increment T_cw <- exp((rho, phi)^) T_cw — is ALWAYS written to grad_out[6].
+ *
+ * ADAM (torch.optim.Adam WITH bias correction, as gslic_exposure_backward states it), per coordinate k with lr_k = lr_trans (k < 3) or lr_rot:
+ *   n = steps[view] + 1, stored back;   b1 = 1 - beta1^n,  b2 = 1 - beta2^n               in DOUBLE from the integer n (beta as the float given)
+ *   s_k = (float)(lr_k / b1),  q = (float)sqrt(b2)                                        in double, each rounded to float once
+ *   m = beta1 m + (1 - beta1) g,   v = beta2 v + ((1 - beta2) g) g,   delta_k = -((s_k m) / (sqrtf(v) / q + eps))
+ *
+ * RETRACTION T_cw <- exp(delta^) T_cw (se3_exp of camera.py), rho = delta[0..2], phi = delta[3..5] = (x, y, z):
+ *   theta^2 = (x x + y y) + z z,  theta = sqrt(theta^2)                                  in DOUBLE from the float phi
+ *   theta <  GSLIC_POSE_SERIES_THETA:  a = 1 - theta^2 / 6,  b = 1/2 - theta^2 / 24,  c = 1/6 - theta^2 / 120
+ *   otherwise:                         a = sin(theta) / theta,  b = (1 - cos(theta)) / theta^2,  c = (theta - sin(theta)) / (theta^2 theta)
+ *                                                                                        in DOUBLE, each rounded to float once
+ *   K = phi^ = [0 -z y; z 0 -x; -y x 0],   K2 = [-(y y + z z)  x y  x z;  x y  -(x x + z z)  y z;  x z  y z  -(x x + y y)]
+ *   Rm(r,c) = (I(r,c) + a K(r,c)) + b K2(r,c),   Vm(r,c) = (I(r,c) + b K(r,c)) + c K2(r,c),   Et_r = (Vm(r,0) rho_0 + Vm(r,1) rho_1) + Vm(r,2) rho_2
+ *   R'(r,c) = (Rm(r,0) R(0,c) + Rm(r,1) R(1,c)) + Rm(r,2) R(2,c),   t'_r = ((Rm(r,0) t_0 + Rm(r,1) t_1) + Rm(r,2) t_2) + Et_r
+ * RE-ORTHONORMALISATION (Gram-Schmidt on the rows of R' in the order 0, 1; row 2 is their cross product, so det R = +1 and thousands of steps
+ * accumulate no drift):
+ *   r0 = R'[0] / sqrtf((R'(0,0)^2 + R'(0,1)^2) + R'(0,2)^2)
+ *   u  = R'[1] - d r0,  d = (r0_0 R'(1,0) + r0_1 R'(1,1)) + r0_2 R'(1,2);     r1 = u / sqrtf((u_0^2 + u_1^2) + u_2^2)
+ *   r2 = (r0_1 r1_2 - r0_2 r1_1,  r0_2 r1_0 - r0_0 r1_2,  r0_0 r1_1 - r0_1 r1_0)
+ * RECOMPOSITION with V = [r0; r1; r2 | t'; 0 0 0 1]:
+ *   view[4 c + r] = V(r,c);   proj[4 c + r] = ((Pm(r,0) V(0,c) + Pm(r,1) V(1,c)) + Pm(r,2) V(2,c)) + Pm(r,3) V(3,c);
+ *   campos_c = -((V(0,c) t'_0 + V(1,c) t'_1) + V(2,c) t'_2)
+ * A row the host loaded and no step moved keeps the host's bits.
+ *
+ * NO-OPS.  skip (optional DEVICE word, the bits of gslic_exposure_adam.skip: one of 1 | 2 | 8 | 16 set): nothing but grad_out is written.  A
+ * coordinate of g that is not finite: nothing but grad_out is written, steps is not advanced.  delta zero in all six coordinates (a zero gradient
+ * on zero moments, or both rates 0), or a coordinate of delta that is not finite (eps = 0 on a zero second moment): m, v and steps are updated,
+ * view / proj / campos are not rewritten.  *view outside [0, n_views): nothing at all is written.
+ * No atomics, no allocation, no read-back: capturable in a graph.  All stores are vector stores.
+ * GSLIC_ERR_INVALID_ARG before any device work, naming the argument: a NULL descriptor, member (skip excepted), gradient or grad_out;
+ * n_views <= 0; a gradient array or grad_out that overlaps a state array (the [n_views, ...] extents), or grad_out one of the gradients; lr_trans,
+ * lr_rot, beta1, beta2 or eps NaN or negative; beta1 or beta2 >= 1.
+ *
+ * gslic_pose_load copies row *view_word — 35 floats — of the three pose arrays into three caller-owned DEVICE buffers in one launch: how a
+ * captured step reads "the pose of the view the word names".  A word outside [0, n_views) writes NOTHING.  GSLIC_ERR_INVALID_ARG for a NULL
+ * pointer, n_views <= 0, or an output that overlaps an input or another output. */
+#define GSLIC_POSE_SERIES_THETA 1e-4
+typedef struct gslic_pose_adam {
+    float* view_all;           /* [V,16] */
+    float* proj_all;           /* [V,16] */
+    float* campos_all;         /* [V,3]  */
+    float* m;                  /* [V,6] exp_avg of (rho, phi) */
+    float* v;                  /* [V,6] exp_avg_sq */
+    int32_t* step_count;       /* [V] */
+    const float* projection;   /* [16] Pm, shared by the views */
+    const int32_t* view;       /* [1] the row to step */
+    int32_t n_views;           /* V */
+    float lr_trans, lr_rot, beta1, beta2, eps;
+    const uint32_t* skip;      /* optional [1]: see above */
+} gslic_pose_adam;
+int gslic_pose_step(
+    const gslic_pose_adam* d, const float* dL_dviewmatrix /*[16]*/, const float* dL_dprojmatrix /*[16]*/, const float* dL_dcampos /*[3]*/,
+    float* grad_out /*[6]*/, void* stream);
+int gslic_pose_load(
+    const float* view_all, const float* proj_all, const float* campos_all, const int32_t* view_word /*[1] device*/, int32_t n_views,
+    float* view_out /*[16]*/, float* proj_out /*[16]*/, float* campos_out /*[3]*/, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * gslic_knn_mean_dist2 — replaces SimpleKNN::knn (src/simple-knn/simple_knn.cu:185-221) behind distCUDA2
  * (src/simple-knn/spatial.cu:15-26): mean_dists[i] = mean of the 3 smallest squared distances from point i

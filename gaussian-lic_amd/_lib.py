@@ -82,6 +82,7 @@ EXPORTS = [
     "gslic_exposure_partials_count", "gslic_exposure_apply", "gslic_exposure_backward",
     "gslic_keyframe_decode", "gslic_keyframe_encode",
     "gslic_pose_step", "gslic_pose_load",
+    "gslic_rasterize_backward_camera_adam", "gslic_rasterize_backward_depth_camera_adam",
 ]
 
 _lib = None
@@ -150,6 +151,8 @@ def lib():
     L.gslic_gradient_stats_accumulate.argtypes = [i32, vp, vp, gstats, i32, i32, vp]   # P, dL_dmean2D, radii, stats, row_begin, row_end, stream
     L.gslic_rasterize_backward_camera.argtypes = bwd_head + [vp] + ten + [vp] * 3 + [vp]
     L.gslic_rasterize_backward_depth_camera.argtypes = bwd_head + [vp, vp] + ten + [vp] * 3 + [vp]
+    L.gslic_rasterize_backward_camera_adam.argtypes = bwd_head + [vp] + six + [adam] + [vp] * 4 + [vp]   # + the three camera outputs, dL_dmean2D
+    L.gslic_rasterize_backward_depth_camera_adam.argtypes = bwd_head + [vp, vp] + six + [adam] + [vp] * 4 + [vp]
     L.gslic_rasterize_backward_rgb.argtypes = bwd_head + [vp] + five + [vp]
     L.gslic_rasterize_backward_rgb_rows.argtypes = bwd_head + [vp] + five + [i32, i32, i32, vp]
     L.gslic_rasterize_backward_rgb_payload.argtypes = bwd_head + [vp] + five + [vp, vp, vp]

@@ -28,6 +28,7 @@ SOURCES = {
     "render_bwd_scan.hip": ["-fno-slp-vectorize"],
     "preprocess_bwd.hip": [],
     "preprocess_bwd_gstat.hip": [],   # the gradient-statistics variants of preprocess_bwd.hip's kernels, in a module of their own (their rule pins its own rounding: fp contract(off))
+    "preprocess_bwd_cam_adam.hip": [],   # the camera gradient with the fused Adam (depth chain variant, its tail, the checked reduction), in a module of its own like the statistics variants
     "adam.hip": [],
     "ssim.hip": ["-ffp-contract=off"],   # the maps are held bit-exact to the reference kernels under the same flag (tests/golden/ssim_*.npz)
     "depth_loss.hip": [],    # its two kernels pin their own rounding (fp contract(off)): the gradient is held to autograd's bits

@@ -805,6 +805,8 @@ static int rasterize_backward_impl(const BackwardCall& c)
         if (adam->param[0] != c.means3D || adam->param[4] != c.scales || adam->param[5] != c.rotations || (prm->M > 0 && adam->param[2] != c.shs))
             return set_error(GSLIC_ERR_INVALID_ARG, "fused Adam: param[] must alias the tensors passed as means3D / shs / scales / rotations");
     }
+    if (dL_dcam && adam && (c.stats || c.row_begin != 0 || (c.row_end >= 0 && c.row_end != P)))
+        return set_error(GSLIC_ERR_INVALID_ARG, "camera gradient with the fused Adam: no statistics descriptor and no row range");
     {   // (checked before anything is enqueued: a bad row range must not leave a blend backward behind)
         const int re = c.row_end < 0 ? P : c.row_end;
         if (c.row_begin < 0 || re > P || c.row_begin > re || (c.row_begin & 63))
@@ -1202,6 +1204,48 @@ int gslic_rasterize_backward_depth_camera(const gslic_raster_params* prm, int32_
     if (prm->P == 0) return zero_camera_grads(c.dL_dcam, stream);
     GS_TRY(depth_backward_checks(prm, dL_ddepth, "gslic_rasterize_backward_camera", "camera "));
     if (!dL_dmean3D) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_camera: dL_dmean3D is NULL (the depth's share is added to it)");
+    return rasterize_backward_impl(c);
+}
+
+int gslic_rasterize_backward_camera_adam(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
+                                         const float* dc, const float* shs, const float* colors_precomp, const float* scales,
+                                         const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                         const float* cam_pos, const int32_t* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                                         char* sample_buffer, const float* dL_dpix, float* dL_dopacity, float* dL_dmean3D, float* dL_ddc,
+                                         float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_erank, const gslic_adam_fused* adam,
+                                         float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, float* dL_dmean2D, void* stream)
+{
+    if (!dL_dviewmatrix || !dL_dprojmatrix || !dL_dcampos)
+        return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_camera_adam: a camera-gradient output pointer is NULL");
+    if (!adam) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_camera_adam: adam descriptor is NULL");
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_ADAM(c); GS_BACKWARD_CAMERA(c);
+    c.dL_dmean2D = dL_dmean2D;
+    if (prm && prm->P == 0) return zero_camera_grads(c.dL_dcam, stream);
+    return rasterize_backward_impl(c);
+}
+
+int gslic_rasterize_backward_depth_camera_adam(const gslic_raster_params* prm, int32_t R, int32_t B, const float* background, const float* means3D,
+                                               const float* dc, const float* shs, const float* colors_precomp, const float* scales,
+                                               const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                               const float* cam_pos, const int32_t* radii, char* geom_buffer, char* binning_buffer, char* img_buffer,
+                                               char* sample_buffer, const float* dL_dpix, const float* dL_ddepth, float* dL_dopacity,
+                                               float* dL_dmean3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_erank,
+                                               const gslic_adam_fused* adam, float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos,
+                                               float* dL_dmean2D, void* stream)
+{
+    if (!dL_dviewmatrix || !dL_dprojmatrix || !dL_dcampos)
+        return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_camera_adam: a camera-gradient output pointer is NULL");
+    if (!adam) return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_camera_adam: adam descriptor is NULL");
+    GS_TRY(check_params(prm));   // (SH degree > 3 among them)
+    BackwardCall c{};
+    GS_BACKWARD_SHARED(c); GS_BACKWARD_ADAM(c); GS_BACKWARD_CAMERA(c);
+    c.dL_dmean2D = dL_dmean2D;
+    c.dL_ddepth = dL_ddepth;
+    if (prm->P == 0) return zero_camera_grads(c.dL_dcam, stream);
+    GS_TRY(depth_backward_checks(prm, dL_ddepth, "gslic_rasterize_backward_camera_adam", "camera "));
+    if (!dL_dmean3D)
+        return set_error(GSLIC_ERR_INVALID_ARG, "gslic_rasterize_backward_depth_camera_adam: dL_dmean3D is NULL (the xyz gradient is assembled there before its update)");
     return rasterize_backward_impl(c);
 }
 #undef GS_BACKWARD_SHARED

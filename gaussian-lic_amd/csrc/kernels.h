@@ -129,6 +129,12 @@ struct GradStatArgs {
 // gs != NULL (fused Adam only, no camera gradient): the *_gstat_kernel instantiations, which also apply the statistics rule to every visible row
 int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s, const GradStatArgs* gs = nullptr);
 int launch_preprocess_bwd_gstat(const PreprocessBwdArgs& a, const GradStatArgs& gs, bool lds_sh, bool defer, hipStream_t s);   // preprocess_bwd_gstat.hip
+// preprocess_bwd_cam_adam.hip: what launch_preprocess_bwd adds for the camera gradient WITH the fused Adam (a.cam_partials and a.adam.on) — under depth
+// the chain kernel (CAM and DEFER_XYZ; lds_sh as that function chose it) and the tail behind it, which forms the four direct view-matrix sums from
+// the means as they were and then steps xyz; colour-only the reduction of the partial rows that honours the forward's overflow word
+int launch_preprocess_bwd_cam_defer_xyz(const PreprocessBwdArgs& a, bool lds_sh, hipStream_t s);
+int launch_depth_mean3d_cam_adam(const PreprocessBwdArgs& a, hipStream_t s);
+int launch_cam_reduce_checked(size_t rows, const PreprocessBwdArgs& a, hipStream_t s);
 // the same rule on a dL_dmean2D [P,3] the caller already has, rows [row_begin, row_end): one thread per row
 int launch_gradient_stats(int row_begin, int row_end, const float* dL_dmean2D, const int32_t* radii, const GradStatArgs& gs, hipStream_t s);
 

@@ -48,37 +48,6 @@ __global__ __launch_bounds__(256) void cam_reduce_kernel(size_t rows, const floa
 // ADAM (gslic_rasterize_backward_depth_adam, behind preprocess_bwd_defer_xyz_kernel): dL_dmean3D holds the chain's xyz gradient, the sum is formed by
 // the same code and then consumed by the masked Adam update of group 0 (adam_scalar, as gslic_adam_update_groups applies it to visible rows): 12 B
 // per Gaussian read and 12 written more than the colour-only fused step, plus the dz gather.
-// depth_mean3d_row: the work per visible Gaussian, shared by depth_mean3d_kernel and its camera variant below.  Returns dL/dz.
-template <bool ADAM>
-__device__ __forceinline__ float depth_mean3d_row(const int idx, const uint32_t* __restrict__ gauss_start, const uint32_t* __restrict__ tiles_touched,
-                                                  const uint8_t* __restrict__ dead, const float* __restrict__ partials_z, const float* __restrict__ V,
-                                                  float* __restrict__ dL_dmean3D, const AdamFusedArgs& A)
-{
-    const uint32_t u0 = gauss_start[idx], u1 = u0 + tiles_touched[idx];
-    float dz = 0.f;
-    constexpr int UP = 4;   // four instances in flight per trip (masked adds: the same summation order as one at a time)
-    for (uint32_t u = u0; u < u1; u += UP) {
-        bool live[UP];
-        float q[UP];
-#pragma unroll
-        for (int j = 0; j < UP; j++) live[j] = (u + j < u1) && dead[u + j] == 0;
-#pragma unroll
-        for (int j = 0; j < UP; j++) q[j] = live[j] ? partials_z[u + j] : 0.f;
-#pragma unroll
-        for (int j = 0; j < UP; j++)
-            if (live[j]) dz += q[j];
-    }
-    dL_dmean3D[3 * idx] += dz * V[2];
-    dL_dmean3D[3 * idx + 1] += dz * V[6];
-    dL_dmean3D[3 * idx + 2] += dz * V[10];
-    if constexpr (ADAM) {
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-            adam_scalar(A.p[0][3 * idx + k], dL_dmean3D[3 * idx + k], A.m[0][3 * idx + k], A.v[0][3 * idx + k], A.lr[0], A.b1, A.b2, A.eps);
-    }
-    return dz;
-}
-
 template <bool ADAM>
 __global__ __launch_bounds__(256) void depth_mean3d_kernel(int row_begin, int row_end, const int32_t* __restrict__ radii,
                                                            const uint32_t* __restrict__ gauss_start, const uint32_t* __restrict__ tiles_touched,
@@ -170,8 +139,10 @@ int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s, const GradS
         return set_error(GSLIC_ERR_INVALID_ARG, "gradient statistics: the fused Adam backward only, without the camera gradient");
     if (a.partials_z && (a.dL_drgb || !a.dL_dmean3D))
         return set_error(GSLIC_ERR_INVALID_ARG, "depth backward: no dL_drgb output, and dL_dmean3D is required");
-    if (a.partials_z && a.cam_partials && (a.adam.on || a.row_begin != 0))
-        return set_error(GSLIC_ERR_INVALID_ARG, "depth camera backward: no fused Adam and no row range");
+    if (a.partials_z && a.cam_partials && a.row_begin != 0)
+        return set_error(GSLIC_ERR_INVALID_ARG, "depth camera backward: no row range");
+    if (a.cam_partials && a.adam.on && (a.row_begin != 0 || a.row_end != a.P))
+        return set_error(GSLIC_ERR_INVALID_ARG, "camera backward with the fused Adam: no row range");
     const bool defer = a.partials_z && a.adam.on;   // depth + fused Adam: xyz is updated by depth_mean3d_kernel<true> once dL/dz is in
     const bool cam = a.cam_partials != nullptr;
     const int nrows = a.row_end - a.row_begin;
@@ -180,17 +151,21 @@ int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s, const GradS
     if (a.M == 15 && a.shs && (a.dL_dsh || a.adam.on || a.dL_drgb)) {
         // one wave per workgroup: 64 Gaussians' SH rows (11.25 KiB) + small-group gradients in LDS, the phase barriers are wave-level,
         // and ten workgroups per CU sit in different phases (measured 0.72 ms against 0.75 at 128 and 0.88 at 256 threads)
-        if (cam) GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_kernel<true, 64, true>), dim3(div_up(nrows, 64)), dim3(64), 0, s, a);
+        if (cam && defer) GS_TRY(launch_preprocess_bwd_cam_defer_xyz(a, true, s));
+        else if (cam) GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_kernel<true, 64, true>), dim3(div_up(nrows, 64)), dim3(64), 0, s, a);
         else if (gs) GS_TRY(launch_preprocess_bwd_gstat(a, *gs, true, defer, s));
         else if (defer) GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_defer_xyz_kernel<true, 64>), dim3(div_up(nrows, 64)), dim3(64), 0, s, a);
         else GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_kernel<true, 64, false>), dim3(div_up(nrows, 64)), dim3(64), 0, s, a);
     } else {
-        if (cam) GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_kernel<false, 256, true>), dim3(div_up(nrows, 256)), dim3(256), 0, s, a);
+        if (cam && defer) GS_TRY(launch_preprocess_bwd_cam_defer_xyz(a, false, s));
+        else if (cam) GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_kernel<false, 256, true>), dim3(div_up(nrows, 256)), dim3(256), 0, s, a);
         else if (gs) GS_TRY(launch_preprocess_bwd_gstat(a, *gs, false, defer, s));
         else if (defer) GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_defer_xyz_kernel<false, 256>), dim3(div_up(nrows, 256)), dim3(256), 0, s, a);
         else GS_LAUNCH(K_PREPROCESS_BWD, (preprocess_bwd_kernel<false, 256, false>), dim3(div_up(nrows, 256)), dim3(256), 0, s, a);
     }
-    if (defer)
+    if (defer && cam)
+        GS_TRY(launch_depth_mean3d_cam_adam(a, s));   // the four direct view-matrix sums from the means as they were, then xyz's Adam
+    else if (defer)
         GS_LAUNCH(K_PREPROCESS_BWD, depth_mean3d_kernel<true>, dim3(div_up(nrows, 256)), dim3(256), 0, s, a.row_begin, a.row_end, a.radii, a.gauss_start,
                   a.tiles_touched, a.dead, a.partials_z, a.view, a.status, a.dL_dmean3D, a.adam);
     else if (a.partials_z && cam)
@@ -202,6 +177,7 @@ int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s, const GradS
     if (cam) {
         const size_t rows = (a.M == 15 && a.shs && (a.dL_dsh || a.adam.on || a.dL_drgb)) ? (size_t)div_up(a.P, 64) : (size_t)div_up(a.P, 256) * 4;
         if (a.partials_z) GS_LAUNCH(K_PREPROCESS_BWD, cam_reduce_depth_kernel, dim3(27), dim3(256), 0, s, rows, (const float*)a.cam_partials, a.status, a.cam_out);
+        else if (a.adam.on) GS_TRY(launch_cam_reduce_checked(rows, a, s));   // (the fused step runs behind capacity-mode forwards: the overflow word is honoured)
         else GS_LAUNCH(K_PREPROCESS_BWD, cam_reduce_kernel, dim3(27), dim3(256), 0, s, rows, (const float*)a.cam_partials, a.cam_out);
     }
     return GSLIC_OK;

@@ -625,3 +625,34 @@ __device__ __forceinline__ void bwd_rest(const PreprocessBwdArgs& a, const int i
     }
 }
 
+// depth_mean3d_row: the work per visible Gaussian, shared by depth_mean3d_kernel and its camera variants (preprocess_bwd.hip: the comment above depth_mean3d_kernel;
+// preprocess_bwd_cam_adam.hip).  Returns dL/dz.
+template <bool ADAM>
+__device__ __forceinline__ float depth_mean3d_row(const int idx, const uint32_t* __restrict__ gauss_start, const uint32_t* __restrict__ tiles_touched,
+                                                  const uint8_t* __restrict__ dead, const float* __restrict__ partials_z, const float* __restrict__ V,
+                                                  float* __restrict__ dL_dmean3D, const AdamFusedArgs& A)
+{
+    const uint32_t u0 = gauss_start[idx], u1 = u0 + tiles_touched[idx];
+    float dz = 0.f;
+    constexpr int UP = 4;   // four instances in flight per trip (masked adds: the same summation order as one at a time)
+    for (uint32_t u = u0; u < u1; u += UP) {
+        bool live[UP];
+        float q[UP];
+#pragma unroll
+        for (int j = 0; j < UP; j++) live[j] = (u + j < u1) && dead[u + j] == 0;
+#pragma unroll
+        for (int j = 0; j < UP; j++) q[j] = live[j] ? partials_z[u + j] : 0.f;
+#pragma unroll
+        for (int j = 0; j < UP; j++)
+            if (live[j]) dz += q[j];
+    }
+    dL_dmean3D[3 * idx] += dz * V[2];
+    dL_dmean3D[3 * idx + 1] += dz * V[6];
+    dL_dmean3D[3 * idx + 2] += dz * V[10];
+    if constexpr (ADAM) {
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            adam_scalar(A.p[0][3 * idx + k], dL_dmean3D[3 * idx + k], A.m[0][3 * idx + k], A.v[0][3 * idx + k], A.lr[0], A.b1, A.b2, A.eps);
+    }
+    return dz;
+}

@@ -200,19 +200,39 @@ def rasterize_gaussians_depth_capacity(bufs, background, means3D, opacity, scale
 def _backward(view, degree, debug, raw_params, background, means3D, radii, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
               dL_dout_color, dL_dout_depth, dc, sh, geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank, out=None, adam=None,
               camera_grads=False, rgb_out=None, rows=None, skip_blend=False, out_addr=None, payload=None, xyz_grad=None, grad_stats=None,
-              mean2d_out=None):
+              mean2d_out=None, cam_out=None):
     """The one backward behind the two public ones (see there for the modes).  dL_dout_depth: None = the colour-only entry points, a tensor =
     their depth twins.  view as _forward's.  grad_stats (a _lib.GradStats, with adam only): the *_adam_stats entry points; mean2d_out
-    (float32 [P,3], with out and no adam / rgb_out): dL_dmeans2D is written there instead of not being materialised."""
+    (float32 [P,3], with out and no adam / rgb_out): dL_dmeans2D is written there instead of not being materialised.
+    camera_grads with adam: gslic_rasterize_backward_camera_adam / _depth_camera_adam — the Adam update inside the backward AND the camera
+    gradient; returns (dL_dviewmatrix [16], dL_dprojmatrix [16], dL_dcampos [3]) — views of cam_out (a float32 [35] the caller keeps, e.g. a
+    captured step's static buffer) or of a new tensor.  mean2d_out is then written too; grad_stats / rows / rgb_out do not combine with it."""
     if grad_stats is not None and adam is None:
         raise ValueError("grad_stats goes with adam (the fused backward); the other backwards give dL_dmeans2D to gradient_stats_accumulate")
+    cam_adam = camera_grads and adam is not None
+    if cam_adam and (grad_stats is not None or rows is not None or rgb_out is not None):
+        raise ValueError("camera_grads with adam: no grad_stats (pass mean2d_out and use gradient_stats_accumulate), no rows, no rgb_out")
+    if cam_out is not None:
+        if not cam_adam:
+            raise ValueError("cam_out goes with camera_grads and adam")
+        if cam_out.numel() != 35 or cam_out.dtype != torch.float32 or not cam_out.is_contiguous() or cam_out.device != means3D.device:
+            raise ValueError("cam_out must be 35 contiguous float32 values on the model's device")
     L = _lib.lib()
     dev, P, M = means3D.device, means3D.size(0), _sh_width(sh)
     depth = dL_dout_depth is not None
     full = adam is None and rgb_out is None   # the nine gradient tensors are returned (else: None)
     if rgb_out is not None:
         assert out is not None   # the four other parameter gradients go into the caller's storage, nothing else is materialised
+    if cam_adam:
+        if mean2d_out is not None:
+            assert mean2d_out.is_contiguous() and mean2d_out.dtype == torch.float32 and mean2d_out.numel() >= 3 * P
+        if cam_out is None:
+            cam_out = torch.empty(35, dtype=torch.float32, device=dev)
+        cam = (cam_out[:16], cam_out[16:32], cam_out[32:35])
     if adam is not None and depth and P == 0:
+        if cam_adam:
+            cam_out.zero_()
+            return cam
         return None   # (the colour-only fused backward leaves P == 0 to the library, which returns at once)
     if full and out is not None:
         # caller-provided gradient storage (e.g. views of one flat slab for a zero-copy all-reduce); the tensors the host
@@ -251,6 +271,9 @@ def _backward(view, degree, debug, raw_params, background, means3D, radii, color
             if grad_stats is not None:   # the same call plus the statistics descriptor
                 fn = L.gslic_rasterize_backward_depth_adam_stats if depth else L.gslic_rasterize_backward_adam_stats
                 tail += (ctypes.byref(grad_stats),)
+            elif cam_adam:               # the same call plus the three camera outputs and the optional dL_dmean2D
+                fn = L.gslic_rasterize_backward_depth_camera_adam if depth else L.gslic_rasterize_backward_camera_adam
+                tail += (p(cam[0]), p(cam[1]), p(cam[2]), p(mean2d_out))
         elif rgb_out is not None and rows is not None:
             # chunked (gslic_rasterize_backward_rgb_rows): Gaussians [rows[0], rows[1]) only; the kernels index the gradient pointers by the
             # ABSOLUTE Gaussian index, so a caller that keeps its chunks in separate blocks passes `out_addr` = {name: address of row 0}
@@ -278,7 +301,7 @@ def _backward(view, degree, debug, raw_params, background, means3D, radii, color
     elif full and camera_grads:
         cam = (torch.zeros(16, device=dev), torch.zeros(16, device=dev), torch.zeros(3, device=dev))
     if not full:
-        return None
+        return cam if cam_adam else None
     res = (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscales, dL_drotations)
     return res + cam if camera_grads else res
 
@@ -287,7 +310,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  projmatrix, tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, dL_dout_color, dc, sh,
                                  degree, campos, geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank, debug,
                                  raw_params=False, out=None, adam=None, camera_grads=False, rgb_out=None, rows=None, skip_blend=False,
-                                 out_addr=None, payload=None, grad_stats=None, mean2d_out=None):
+                                 out_addr=None, payload=None, grad_stats=None, mean2d_out=None, cam_out=None):
     """RasterizeGaussiansBackwardCUDA (rasterize_points.cu:151-246): returns (dL_dmeans2D, dL_dcolors_precomp,
     dL_dopacities, dL_dmeans3D, dL_dcov3Ds_precomp, dL_ddc, dL_dsh, dL_dscales, dL_drotations).
     raw_params=True: scales / rotations are raw and dL_dopacities / dL_dscales / dL_drotations are w.r.t. the raw parameters.
@@ -296,19 +319,20 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     adam (a gslic_adam_fused descriptor, raw_params implied): gslic_rasterize_backward_adam, the Adam update inside the backward; returns None.
     rgb_out [P,3] (with out; returns None): gslic_rasterize_backward_rgb_payload, or with rows=(p0, p1) gslic_rasterize_backward_rgb_rows.
     camera_grads=True (gslic_rasterize_backward_camera; no reference counterpart): three more tensors are appended —
-    dL_dviewmatrix [16], dL_dprojmatrix [16], dL_dcampos [3], element order of the inputs.
+    dL_dviewmatrix [16], dL_dprojmatrix [16], dL_dcampos [3], element order of the inputs.  With adam as well
+    (gslic_rasterize_backward_camera_adam): the Adam update inside the backward, the three returned alone (views of cam_out [35] when given).
     grad_stats (a _lib.GradStats, with adam): gslic_rasterize_backward_adam_stats.  mean2d_out [P,3] (with out): dL_dmeans2D is written there."""
     view = (dL_dout_color.size(1), dL_dout_color.size(2), tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier)
     return _backward(view, degree, debug, raw_params, background, means3D, radii, colors, scales, rotations, cov3D_precomp, viewmatrix, projmatrix,
                      campos, dL_dout_color, None, dc, sh, geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank, out=out, adam=adam,
                      camera_grads=camera_grads, rgb_out=rgb_out, rows=rows, skip_blend=skip_blend, out_addr=out_addr, payload=payload,
-                     grad_stats=grad_stats, mean2d_out=mean2d_out)
+                     grad_stats=grad_stats, mean2d_out=mean2d_out, cam_out=cam_out)
 
 
 def rasterize_gaussians_backward_depth(background, means3D, radii, scales, rotations, scale_modifier, viewmatrix, projmatrix, tan_fovx,
                                        tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, dL_dout_color, dL_dout_depth, dc, sh, degree, campos,
                                        geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank=0.0, debug=False, raw_params=False,
-                                       out=None, adam=None, xyz_grad=None, camera_grads=False, grad_stats=None, mean2d_out=None):
+                                       out=None, adam=None, xyz_grad=None, camera_grads=False, grad_stats=None, mean2d_out=None, cam_out=None):
     """gslic_rasterize_backward_depth: rasterize_gaussians_backward with dL/d(out_depth) [H,W] as a second input, on the buffers of
     rasterize_gaussians_depth (or rasterize_gaussians_depth_capacity: pass its cap_R / cap_B as R / B).  Returns the same nine tensors
     (dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dmeans3D, dL_dcov3D, dL_ddc, dL_dsh, dL_dscales, dL_drotations); dL_dout_depth = 0 gives
@@ -319,14 +343,13 @@ def rasterize_gaussians_backward_depth(background, means3D, radii, scales, rotat
     bit-identical to this backward followed by the masked Adam step; returns None.  xyz_grad [P,3]: where the xyz gradient is assembled before
     its update (allocated when None; a graph-captured step passes a buffer of its own).
     camera_grads=True (gslic_rasterize_backward_depth_camera): three more tensors are appended — dL_dviewmatrix [16], dL_dprojmatrix [16],
-    dL_dcampos [3] of the colour AND depth loss, as rasterize_gaussians_backward(camera_grads=True) does; not with adam.
+    dL_dcampos [3] of the colour AND depth loss, as rasterize_gaussians_backward(camera_grads=True) does.  With adam as well
+    (gslic_rasterize_backward_depth_camera_adam): returns the three alone, views of cam_out [35] when given; mean2d_out is written too.
     grad_stats (with adam): gslic_rasterize_backward_depth_adam_stats.  mean2d_out [P,3] (with out): dL_dmeans2D is written there."""
-    if adam is not None and camera_grads:
-        raise ValueError("rasterize_gaussians_backward_depth: camera_grads with the fused Adam backward is not available")
     view = (dL_dout_color.size(1), dL_dout_color.size(2), tan_fovx, tan_fovy, limx_neg, limx_pos, limy_neg, limy_pos, scale_modifier)
     return _backward(view, degree, debug, raw_params, background, means3D, radii, None, scales, rotations, None, viewmatrix, projmatrix, campos,
                      dL_dout_color, dL_dout_depth, dc, sh, geomBuffer, R, binningBuffer, imageBuffer, B, sampleBuffer, lambda_erank, out=out, adam=adam,
-                     camera_grads=camera_grads, xyz_grad=xyz_grad, grad_stats=grad_stats, mean2d_out=mean2d_out)
+                     camera_grads=camera_grads, xyz_grad=xyz_grad, grad_stats=grad_stats, mean2d_out=mean2d_out, cam_out=cam_out)
 
 
 def _depth_grads(ctx, dL_dcolor, dL_ddepth, xyz, dc, sh, opacity, scaling, rotation, radii, geom, binning, img, sample, raw):

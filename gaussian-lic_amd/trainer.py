@@ -1747,14 +1747,18 @@ class PoseSet:
 
     def _step(self, view, cam_grads, do_step=True):
         """gslic_pose_step on row `view`: grad <- the chain of the three camera gradients; do_step: the row moves (else the skip word is set)."""
+        i = self._index(view)
+        return self._step_word(self._views[i:i + 1], cam_grads, None if do_step else self._no_step)
+
+    def _step_word(self, view_word, cam_grads, skip):
+        """gslic_pose_step on the row a device int32 names, with an optional device skip word (GraphedStep: the forward's overflow word)."""
         import ctypes
         from . import _lib
-        i = self._index(view)
         gv, gp, gc = cam_grads
         for t, n, name in ((gv, 16, "dL_dviewmatrix"), (gp, 16, "dL_dprojmatrix"), (gc, 3, "dL_dcampos")):
             if t.numel() != n or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.view.device:
                 raise ValueError(f"PoseSet: {name} must be {n} contiguous float32 values on the set's device")
-        d = self._descriptor(self._views[i:i + 1], None if do_step else self._no_step)
+        d = self._descriptor(view_word, skip)
         _lib.check(_lib.lib().gslic_pose_step(ctypes.byref(d), _lib.ptr(gv), _lib.ptr(gp), _lib.ptr(gc), _lib.ptr(self.grad), _lib.current_stream_ptr()))
         return self.grad
 
@@ -1825,6 +1829,14 @@ def _use_depth(who, gt_depth, lambda_depth, depth_weight, depth_huber):
     if gt_depth is None and (depth_weight is not None or float(depth_huber) != 0.0):
         raise ValueError(f"{who}: depth_weight / depth_huber given without gt_depth (they shape the depth term of the loss: pass gt_depth and lambda_depth)")
     return gt_depth is not None and lambda_depth != 0.0
+
+
+def _depth_xyz_grad(model):
+    """The [P,3] buffer, kept on the model, in which the fused depth backwards assemble the xyz gradient before its update."""
+    xg = getattr(model, "_depth_xyz_grad", None)
+    if xg is None or xg.shape[0] != model.P or xg.device != model.xyz.device:
+        xg = model._depth_xyz_grad = torch.empty(model.P, 3, dtype=torch.float32, device=model.device)
+    return xg
 
 
 def _grad_slab(model):
@@ -2020,7 +2032,7 @@ def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, l
 
 
 def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None, grad_stats=None,
-                            depth_weight=None, depth_huber=0.0, exposure=None, view=0, poses=None):
+                            depth_weight=None, depth_huber=0.0, exposure=None, view=0, poses=None, adam_in_backward=False):
     """One joint map + pose iteration: forward -> loss kernels -> gslic_rasterize_backward_camera (parameter gradients AND the camera gradient in
     one pass) -> masked Adam on the map -> `camera` moved by -pose_lr * dL/dxi (left se(3) increment; 35 floats cross to the host, which is the
     step's only synchronisation).  Returns (terms, visible, dL/dxi).
@@ -2034,16 +2046,44 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
     intrinsics and must match the set's), and the pose step is ONE launch behind the map's Adam (gslic_pose_step: chain, Adam on the six tangent
     coordinates with the set's two rates, retraction): no host copy of the 35 floats, no numpy, no to_device, no synchronisation.  Returns
     (terms, visible, poses.grad [6] float32 DEVICE tensor).  pose_lr != 0 together with poses= raises (the set has its own rates); with exposure=
-    as well, view names both rows."""
+    as well, view names both rows.
+    adam_in_backward=True: the map's Adam runs inside the backward that also returns the camera gradient (gslic_rasterize_backward_camera_adam /
+    _depth_camera_adam): the ten gradients are neither written to the slab nor read back and SparseGaussianAdam.step's launches go away.  The
+    camera gradient is that of the map before its update; parameters, moments, the mask and the pose step are bit-identical to the default's.
+    `visible` is the mask the kernel wrote; the pose step follows unchanged, through poses= or pose_lr.  It combines with gt_depth, weight,
+    depth_weight, depth_huber, exposure and grad_stats (the backward then writes dL_dmeans2D too, and the same small kernel adds it).  Single GPU
+    only (NotImplementedError under the N > 1 exchange).  False (the default) is the step as it was, launch for launch."""
     fl = fused_loss or _default_fused_loss()
     use_depth = _use_depth("training_step_with_pose", gt_depth, lambda_depth, depth_weight, depth_huber)
     exposure = _check_exposure("training_step_with_pose", exposure, view)
     poses = _check_poses("training_step_with_pose", poses, view, camera)
     if poses is not None and pose_lr:
         raise ValueError("training_step_with_pose: pose_lr != 0 given together with poses= (the pose set steps by its own lr_rot / lr_trans)")
+    if adam_in_backward and _dist_on():
+        raise NotImplementedError("training_step_with_pose(adam_in_backward=True) is single-GPU only: under the N > 1 exchange the gradients "
+                                  "travel between the backward and the Adam update")
     grad_stats = _grad_stats_for_step(grad_stats, model)
     cam = camera
     with torch.no_grad():
+        if adam_in_backward:
+            rr = _RawRaster(model, cam, bg, use_depth, pose=None if poses is None else poses.pose(view))
+            image, depth, radii = rr.forward()
+            dL_dimage, dL_ddepth, terms = _fused_losses(fl, image, gt_image, depth, gt_depth, float(lambda_depth), weight, depth_weight, depth_huber,
+                                                        exposure, view)
+            vis_u8 = torch.empty(model.P, dtype=torch.uint8, device=model.device)
+            m2d = None if grad_stats is None else grad_stats._mean2d_buffer()
+            out = rr.backward(dL_dimage, dL_ddepth, adam=model.optimizer.fused_descriptor(visible_out=vis_u8),
+                              xyz_grad=_depth_xyz_grad(model) if use_depth else None, camera_grads=True, mean2d_out=m2d)
+            if grad_stats is not None:
+                grad_stats.accumulate_from(m2d, radii)
+            model.optimizer.count_step()
+            visible = vis_u8.view(torch.bool)
+            if poses is not None:
+                return terms, visible, poses._step(view, out)
+            g = cam.pose_gradient(*out)
+            if pose_lr:
+                cam.apply_pose_increment(-float(pose_lr) * g).to_device(model.device)
+            return terms, visible, g
         if use_depth:
             _grad_slab(model)   # (the depth step sets the slab up ahead of its forward, the colour step behind its loss: both as they were)
         rr = _RawRaster(model, cam, bg, use_depth, pose=None if poses is None else poses.pose(view))
@@ -2118,11 +2158,7 @@ def training_step_fused(model, camera, gt_image, bg, fused_loss=None, do_step=Tr
             # single GPU: nothing to exchange, so the Adam update runs inside the per-Gaussian backward kernel while the
             # gradients are still in registers / LDS (bit-identical to backward + SparseGaussianAdam.step, ~2 GB less HBM traffic);
             # under depth supervision every group but xyz there, xyz once dL/dz is in (its gradient is assembled in a buffer kept on the model)
-            xg = None
-            if use_depth:
-                xg = getattr(model, "_depth_xyz_grad", None)
-                if xg is None or xg.shape[0] != model.P or xg.device != rr.xyz.device:
-                    xg = model._depth_xyz_grad = torch.empty(model.P, 3, dtype=torch.float32, device=dev)
+            xg = _depth_xyz_grad(model) if use_depth else None
             vis_u8 = torch.empty(model.P, dtype=torch.uint8, device=dev)
             rr.backward(dL_dimage, dL_ddepth, adam=model.optimizer.fused_descriptor(visible_out=vis_u8), xyz_grad=xg,
                         grad_stats=None if grad_stats is None else grad_stats._descriptor())
@@ -2275,14 +2311,23 @@ class GraphedStep:
     poses (a trainer.PoseSet) / view: the step READS its pose from the set: one gslic_pose_load launch inside the step fills the static view / proj /
     campos buffers from the row a device int32 names; step(view=j) fills that word (and the exposure's, when there is one: view names both rows),
     so a captured graph changes keyframe pose without a host copy or a re-capture.  `camera` supplies the intrinsics and must match the set's;
-    step(camera=...) on such a step raises.  The step does NOT train the pose (the fused-Adam backward kernels have no camera variant): pose steps
-    are issued between graphed steps through pose_gradient(..., poses=, do_step=True) or training_step_with_pose(poses=).  A repeated step (the
-    overflow window) repeats with its view index and reads the row AS IT IS THEN — a pose step issued since moves the repeat with it.  poses=None
-    is the step as it was, launch for launch."""
+    step(camera=...) on such a step raises.  A repeated step (the overflow window) repeats with its view index and reads the row AS IT IS THEN — a
+    pose step issued since moves the repeat with it.  poses=None is the step as it was, launch for launch.
+
+    train_pose=True (with poses): the step is the joint map + pose iteration, training_step_with_pose(poses=, adam_in_backward=True) in capacity
+    mode.  Its launches, in order: gslic_pose_load, the capacity forward, the loss kernels, gslic_rasterize_backward_camera_adam (or
+    _depth_camera_adam) into a static 35-float buffer, gslic_pose_step on the same device word — so step(view=j) changes the row that is rendered
+    from AND trained without a re-capture.  The skip word of the pose step is the forward's status word, exactly as the exposure backward's is: a
+    step that did not fit moves neither map nor pose (its camera gradient is zeros) and check() repeats it with its view index.  The warm-up and
+    capture passes run the step, so the set's state (view, proj, campos, m, v, steps, grad) is saved and restored around them like the map's.
+    train_pose=True without poses raises ValueError; with grad_stats it raises NotImplementedError (the camera kernel accumulates no statistics,
+    and the small statistics kernel has no overflow word: a step that did not fit would add stale gradients).  train_pose=False: the step does
+    not train the pose — pose steps are then issued between graphed steps through pose_gradient(..., poses=, do_step=True) or
+    training_step_with_pose(poses=) — and is the step as it was, launch for launch."""
 
     def __init__(self, model, camera, gt_image, bg, headroom=1.25, check_every=16, cap_R=None, cap_B=None, use_graph=False, gt_depth=None,
                  lambda_depth=0.0, weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0, exposure=None, view=0, keyframes=None,
-                 frame=None, level=0, poses=None):
+                 frame=None, level=0, poses=None, train_pose=False):
         """use_graph=False (default since round 5): the capacity-mode step (caller-owned scratch, no host round trip, overflow checks and repeats as
         below) issued as eager launches; use_graph=True: captured in a hipGraph and replayed with one launch per step.  The two are equally fast at
         2M Gaussians (bench.py: `capacity_eager` / `graphed`; the host runs ahead of the device either way), and the eager form has no hazard:
@@ -2320,6 +2365,13 @@ class GraphedStep:
         self.campos = camera.d_camera_center.clone()
         self._pose_host = self._pose_of(camera)
         self.poses = _check_poses("GraphedStep", poses, view, camera)
+        self.train_pose = bool(train_pose)
+        if self.train_pose and self.poses is None:
+            raise ValueError("GraphedStep: train_pose=True needs poses= (a trainer.PoseSet holds the rows and the optimiser's state)")
+        if self.train_pose and self.grad_stats is not None:
+            raise NotImplementedError("GraphedStep: train_pose=True together with grad_stats (the camera kernel accumulates no statistics, and the "
+                                      "small statistics kernel has no overflow word: a step that did not fit would add stale gradients)")
+        self._cam_grads = torch.zeros(35, dtype=torch.float32, device=dev) if self.train_pose else None   # the backward's three camera outputs
         self._pose_view_host = None if self.poses is None else int(view)                     # the row that is loaded
         if self.poses is not None:
             self._pose_word = torch.full((1,), int(view), dtype=torch.int32, device=dev)     # which row: filled by _load
@@ -2394,6 +2446,10 @@ class GraphedStep:
             ex_view = (self._ex_E.view(12), self._ex_view, self.bufs.status[2:3])
         dL_dimage, dL_ddepth, self.terms = _fused_losses(self.fl, image, self.gt, depth, self.gt_depth, self.lambda_depth, self.weight, self.depth_weight,
                                                          self.depth_huber, self.exposure, ex_view)
+        if self.train_pose:
+            cam = rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad, camera_grads=True, cam_out=self._cam_grads)
+            self.poses._step_word(self._pose_word, cam, self.bufs.status[2:3])   # (skip: the forward's overflow word, as the exposure's)
+            return
         rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad, grad_stats=self._gstat)
 
     def _capture(self):
@@ -2412,6 +2468,8 @@ class GraphedStep:
         saved_stats = [] if self.grad_stats is None else [a.clone() for a, _w in self.grad_stats._arrays()]   # (the two passes are no views of the host's)
         ex = self.exposure
         saved_ex = None if ex is None else [(a, a.clone()) for a in (ex.params, ex.m, ex.v, ex.steps, ex.grad)]
+        ps = self.poses if self.train_pose else None
+        saved_ps = None if ps is None else [(a, a.clone()) for a in (ps.view, ps.proj, ps.campos, ps.m, ps.v, ps.steps, ps.grad)]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s), torch.no_grad():
@@ -2428,7 +2486,7 @@ class GraphedStep:
             self.model._buf[n][:self.model.P].copy_(p); self.model._m[n][:self.model.P].copy_(m1); self.model._v[n][:self.model.P].copy_(m2)
         for (a, _w), keep in zip(self.grad_stats._arrays() if saved_stats else (), saved_stats):
             a.copy_(keep)
-        for a, keep in saved_ex or ():
+        for a, keep in (saved_ex or []) + (saved_ps or []):
             a.copy_(keep)
         self.bufs.status.zero_()
         self.graph = g

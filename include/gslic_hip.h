@@ -523,6 +523,45 @@ int gslic_rasterize_backward_depth_camera(
     float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot, float lambda_erank,
     float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* stream);
 
+/* The joint map + pose iteration on the single-GPU fast path (no reference counterpart; additive exports, ABI 8).
+ *
+ * gslic_rasterize_backward_camera_adam — gslic_rasterize_backward_adam plus the three camera gradients, in the same launches: the per-Gaussian
+ *  kernel forms the 27 camera sums from the parameters AS THEY WERE, then applies the Adam update while the gradients are still in registers / LDS.
+ * gslic_rasterize_backward_depth_camera_adam — gslic_rasterize_backward_depth_adam plus the same three, for a loss on colour AND depth: the fused
+ *  kernel updates every group but xyz and leaves xyz's chain gradient in dL_dmean3D (REQUIRED, [P,3], any contents: every row is written); a second
+ *  kernel adds dL/dz * row 2 of the view matrix, forms the four direct view-matrix sums dL/dz_i (x_i, y_i, z_i, 1) from the means as they were and
+ *  then updates xyz from the complete gradient.
+ *
+ * THE RULE.  Parameters, both moments and adam->visible_out are bit-identical to gslic_rasterize_backward_camera / _depth_camera with
+ * raw_params = 1 followed by gslic_adam_update_groups(visible = radii > 0) over the six groups; the three camera outputs are bit-identical to that
+ * call's (sums over the parameters before the update, reduced in the same fixed order: no atomics, every run gives the same bits).  dL_dmean2D
+ * (optional, [P,3]) receives what gslic_rasterize_backward writes there — the input of gslic_gradient_stats_accumulate; the six parameter-gradient
+ * pointers may be NULL (but dL_dmean3D of the depth entry) or receive the gradients.  After a capacity-mode forward that overflowed, nothing
+ * per-Gaussian is touched (no gradient, no moment, no parameter, no visible_out) and the three camera outputs are zeros.  Nothing allocates,
+ * synchronises or reads back: both calls can be captured in a graph.  P == 0: the three camera outputs are zeroed.
+ * GSLIC_ERR_INVALID_ARG before any device work: a NULL camera output, adam == NULL, raw_params = 0, everything gslic_rasterize_backward_adam
+ * (gslic_rasterize_backward_depth_adam) and gslic_rasterize_backward_camera (_depth_camera) refuse.  There is no row range and no statistics
+ * descriptor on these entries: the camera gradient combines with neither (the shared implementation refuses both).
+ */
+int gslic_rasterize_backward_camera_adam(
+    const gslic_raster_params* prm, int32_t R, int32_t B,
+    const float* background, const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+    const float* scales, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix, const float* cam_pos, const int32_t* radii,
+    char* geom_buffer, char* binning_buffer, char* img_buffer, char* sample_buffer, const float* dL_dpix,
+    float* dL_dopacity, float* dL_dmean3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot,
+    float lambda_erank, const gslic_adam_fused* adam,
+    float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, float* dL_dmean2D, void* stream);
+int gslic_rasterize_backward_depth_camera_adam(
+    const gslic_raster_params* prm, int32_t R, int32_t B,
+    const float* background, const float* means3D, const float* dc, const float* shs, const float* colors_precomp,
+    const float* scales, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix, const float* cam_pos, const int32_t* radii,
+    char* geom_buffer, char* binning_buffer, char* img_buffer, char* sample_buffer, const float* dL_dpix, const float* dL_ddepth,
+    float* dL_dopacity, float* dL_dmean3D, float* dL_ddc, float* dL_dsh, float* dL_dscale, float* dL_drot,
+    float lambda_erank, const gslic_adam_fused* adam,
+    float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, float* dL_dmean2D, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * gslic_adam_update — replaces ADAM::adamUpdate / adamUpdateCUDA (cuda_rasterizer/adam.cu:9-66), reached
  * from adamUpdate (rasterize_points.cu:248-273) <- SparseGaussianAdam::custom_step (optim_utils.h:102-137).

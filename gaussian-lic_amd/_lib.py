@@ -80,7 +80,7 @@ EXPORTS = [
     "gslic_depth_loss_weighted_partials_count", "gslic_depth_loss_weighted_forward_backward",
     "gslic_geometry_images",
     "gslic_exposure_partials_count", "gslic_exposure_apply", "gslic_exposure_backward",
-    "gslic_keyframe_decode", "gslic_keyframe_encode",
+    "gslic_keyframe_decode", "gslic_keyframe_encode", "gslic_keyframe_decode_depth", "gslic_keyframe_encode_depth",
     "gslic_pose_step", "gslic_pose_load",
     "gslic_rasterize_backward_camera_adam", "gslic_rasterize_backward_depth_camera_adam",
 ]
@@ -128,6 +128,8 @@ def lib():
     L.gslic_exposure_backward.argtypes = [i32, i32] + [vp] * 6 + [ctypes.POINTER(ExposureAdam), vp]   # H, W, E, image, dL_dout, dL_dimage, partials, dL_dE, adam, stream
     L.gslic_keyframe_decode.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp]   # W, H, level, color_slab, mask_slab, frame, n_frames, out, weight_out, stream
     L.gslic_keyframe_encode.argtypes = [i32, i32, vp, vp, vp, vp, i32, i32, vp]        # W, H, image, mask, color_slab, mask_slab, capacity, slot, stream
+    L.gslic_keyframe_decode_depth.argtypes = [i32, i32, i32, vp, vp, vp, i32, f32, vp, vp, vp]   # W, H, level, depth_slab, dweight_slab, frame, n_frames, step, depth_out, dweight_out, stream
+    L.gslic_keyframe_encode_depth.argtypes = [i32, i32, vp, vp, vp, vp, i32, i32, f32, vp]      # W, H, depth, weight, depth_slab, dweight_slab, capacity, slot, step, stream
     L.gslic_pose_step.argtypes = [ctypes.POINTER(PoseAdam), vp, vp, vp, vp, vp]   # descriptor, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, grad_out, stream
     L.gslic_pose_load.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp]            # view_all, proj_all, campos_all, view_word, n_views, 3 outputs, stream
     # the rasterize entry points, from the pieces their signatures share (include/gslic_hip.h)

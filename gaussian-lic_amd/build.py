@@ -34,6 +34,7 @@ SOURCES = {
     "depth_loss.hip": [],    # its two kernels pin their own rounding (fp contract(off)): the gradient is held to autograd's bits
     "exposure.hip": ["-ffp-contract=off"],   # the 3x4 exposure model: every product and sum of the rule rounded on its own, apply and dL_dimage tested on bits
     "keyframes.hip": ["-ffp-contract=off"],  # the keyframe store: integer sums and one float multiply (decode), one product rounded on its own (encode), tested on bits
+    "keyframes_depth.hip": ["-ffp-contract=off"],  # the store's depth slabs, in a module of their own: an integer minimum and one exact multiply (decode), one exact product, an add and a floor (encode)
     "pose.hip": ["-ffp-contract=off"],       # the pose set's step: every float32 product and sum of the rule rounded on its own, in the header's order
     "knn.hip": [],
     "extend.hip": ["-ffp-contract=off"],  # pixel assignment decides integers: canonical order like preprocess.hip
@@ -46,7 +47,7 @@ SOURCES = {
 }
 COMMON = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-Wno-inline-asm",
           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]
-HEADERS = ["gslic_common.h", "kernels.h", "render_fwd_body.inc", "preprocess_bwd_body.inc", "preprocess_bwd_device.inc", "contrib_body.inc", "loss_bwd_body.inc", "row_rules.h", os.path.join("..", "..", "include", "gslic_hip.h")]
+HEADERS = ["gslic_common.h", "kernels.h", "render_fwd_body.inc", "preprocess_bwd_body.inc", "preprocess_bwd_device.inc", "contrib_body.inc", "loss_bwd_body.inc", "row_rules.h", "keyframe_rows.h", os.path.join("..", "..", "include", "gslic_hip.h")]
 
 
 def _newer(a, b):

@@ -1493,6 +1493,59 @@ int gslic_keyframe_encode(int32_t W, int32_t H, const float* image, const float*
                            (hipStream_t)stream);
 }
 
+// step = 2^e with -16 <= e <= 0 (frexpf: 0.5 * 2^(e + 1))
+static bool keyframe_depth_step_ok(float step)
+{
+    int e = 0;
+    return step > 0.0f && step <= 1.0f && frexpf(step, &e) == 0.5f && e >= -15 && e <= 1;
+}
+
+int gslic_keyframe_decode_depth(int32_t W, int32_t H, int32_t level, const uint16_t* depth_slab, const uint8_t* dweight_slab, const int32_t* frame,
+                                int32_t n_frames, float step, float* depth_out, float* dweight_out, void* stream)
+{
+    const char* fn = "keyframe decode depth";
+    if (W <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: W = %d is not positive", fn, W);
+    if (H <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: H = %d is not positive", fn, H);
+    if (level < 0 || level > GSLIC_KEYFRAME_MAX_LEVEL)
+        return set_error(GSLIC_ERR_INVALID_ARG, "%s: level = %d is outside [0, %d]", fn, level, GSLIC_KEYFRAME_MAX_LEVEL);
+    if ((W >> level) == 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: W_l = %d >> %d is 0", fn, W, level);
+    if ((H >> level) == 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: H_l = %d >> %d is 0", fn, H, level);
+    if (n_frames < 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: n_frames = %d is negative", fn, n_frames);
+    if (!keyframe_depth_step_ok(step))
+        return set_error(GSLIC_ERR_INVALID_ARG, "%s: step = %g is not a power of two in [2^-16, 1]", fn, (double)step);
+    const struct { const void* p; const char* name; } ptrs[3] = {{depth_slab, "depth_slab"}, {frame, "frame"}, {depth_out, "depth_out"}};
+    for (const auto& a : ptrs)
+        if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, a.name);
+    if (dweight_slab && !dweight_out) return set_error(GSLIC_ERR_INVALID_ARG, "%s: dweight_out is NULL (a dweight_slab was given)", fn);
+    const struct { const void* p; const char* name; } al[4] = {{depth_out, "depth_out"}, {dweight_slab ? dweight_out : nullptr, "dweight_out"},
+                                                               {depth_slab, "depth_slab"}, {dweight_slab, "dweight_slab"}};
+    for (const auto& a : al)
+        if (!aligned_to(a.p, 16)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is not 16-byte aligned", fn, a.name);
+    return keyframe_decode_depth(W, H, level, depth_slab, dweight_slab, frame, n_frames, step, depth_out, dweight_out, (hipStream_t)stream);
+}
+
+int gslic_keyframe_encode_depth(int32_t W, int32_t H, const float* depth, const float* weight, uint16_t* depth_slab, uint8_t* dweight_slab,
+                                int32_t capacity, int32_t slot, float step, void* stream)
+{
+    const char* fn = "keyframe encode depth";
+    if (W <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: W = %d is not positive", fn, W);
+    if (H <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: H = %d is not positive", fn, H);
+    if (capacity <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: capacity = %d is not positive", fn, capacity);
+    if (slot < 0 || slot >= capacity) return set_error(GSLIC_ERR_INVALID_ARG, "%s: slot = %d is outside [0, %d)", fn, slot, capacity);
+    if (!keyframe_depth_step_ok(step))
+        return set_error(GSLIC_ERR_INVALID_ARG, "%s: step = %g is not a power of two in [2^-16, 1]", fn, (double)step);
+    if (!depth) return set_error(GSLIC_ERR_INVALID_ARG, "%s: depth is NULL", fn);
+    if (!depth_slab) return set_error(GSLIC_ERR_INVALID_ARG, "%s: depth_slab is NULL", fn);
+    if (weight && !dweight_slab) return set_error(GSLIC_ERR_INVALID_ARG, "%s: dweight_slab is NULL (a weight was given)", fn);
+    if (!aligned_to(depth, 4)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: depth is not 4-byte aligned", fn);
+    if (!aligned_to(weight, 4)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: weight is not 4-byte aligned", fn);
+    if (!aligned_to(depth_slab, 16)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: depth_slab is not 16-byte aligned", fn);
+    if (!aligned_to(dweight_slab, 16)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: dweight_slab is not 16-byte aligned", fn);
+    const size_t pix = (size_t)H * (size_t)W;
+    return keyframe_encode_depth(W, H, depth, weight, depth_slab + (size_t)slot * pix, dweight_slab ? dweight_slab + (size_t)slot * pix : nullptr, step,
+                                 (hipStream_t)stream);
+}
+
 int gslic_pose_step(const gslic_pose_adam* d, const float* dL_dviewmatrix, const float* dL_dprojmatrix, const float* dL_dcampos, float* grad_out,
                     void* stream)
 {

@@ -265,6 +265,10 @@ int exposure_backward(int H, int W, const float* E, const float* image, const fl
 int keyframe_decode(int W, int H, int level, const uint8_t* color, const uint8_t* mask, const int32_t* frame, int n_frames, float* out, float* weight,
                     hipStream_t s);
 int keyframe_encode(int W, int H, const float* image, const float* mask, uint8_t* color_slot, uint8_t* mask_slot, hipStream_t s);
+// the depth slabs of gslic_keyframe_decode_depth / gslic_keyframe_encode_depth: one launch each (depth and, with a weight slab, the depth weight)
+int keyframe_decode_depth(int W, int H, int level, const uint16_t* depth, const uint8_t* dweight, const int32_t* frame, int n_frames, float step,
+                          float* depth_out, float* dweight_out, hipStream_t s);
+int keyframe_encode_depth(int W, int H, const float* depth, const float* weight, uint16_t* depth_slot, uint8_t* dweight_slot, float step, hipStream_t s);
 
 // pose.hip: the trainable pose set of gslic_pose_step / gslic_pose_load (arguments validated by the caller), one launch of one wave each: the
 // se(3) chain, Adam, retraction, Gram-Schmidt and recomposition on row *d->view; the copy of row *view_word into three caller-owned buffers

@@ -14,36 +14,9 @@
 // allocation, no read-back: capturable in a graph.
 #include "gslic_common.h"
 #include "kernels.h"
+#include "keyframe_rows.h"
 
 namespace gslic {
-
-static constexpr int KF_THREADS = 256;
-
-typedef uint32_t kf_u2 __attribute__((ext_vector_type(2)));
-typedef uint32_t kf_u4 __attribute__((ext_vector_type(4)));
-
-// the CH << L dwords of one source row of a group (4 << L pixels of CH bytes), at an address aligned to min(16, 4 << L) bytes
-template <int L, int CH>
-__device__ __forceinline__ void kf_load_row(const uint8_t* __restrict__ p, uint32_t (&w)[CH << L])
-{
-    constexpr int ND = CH << L;
-    if constexpr (L == 0) {
-#pragma unroll
-        for (int k = 0; k < ND; k++) w[k] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p) + k);
-    } else if constexpr (L == 1) {
-#pragma unroll
-        for (int k = 0; k < ND / 2; k++) {
-            const kf_u2 v = __builtin_nontemporal_load(reinterpret_cast<const kf_u2*>(p) + k);
-            w[2 * k] = v.x; w[2 * k + 1] = v.y;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < ND / 4; k++) {
-            const kf_u4 v = __builtin_nontemporal_load(reinterpret_cast<const kf_u4*>(p) + k);
-            w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w;
-        }
-    }
-}
 
 // One group of the fast path: output pixels (X .. X + 3, Y) of a CH-channel slot [H, W, CH] -> planes out + c * plane (plane = H_l * W_l floats)
 template <int L, int CH>
@@ -133,14 +106,6 @@ __global__ __launch_bounds__(KF_THREADS) void keyframe_decode_scalar_kernel(Keyf
     }
 }
 
-// q = (uint8) floorf(x' * 255 + 0.5), x' = x clamped to [0, 1] with NaN -> 0 (saturate_f); the product rounded on its own
-__device__ __forceinline__ uint32_t kf_quantise(float x)
-{
-#pragma clang fp contract(off)
-    const float p = __fmul_rn(saturate_f(x), 255.0f);
-    return (uint32_t)floorf(p + 0.5f);
-}
-
 // planar float [CH, N] -> interleaved bytes [N, CH]; QUADS: N % 4 == 0 and the planes are 16-byte aligned: a lane takes four pixels, reads one quad per
 // plane and writes CH dwords; otherwise one pixel per lane
 template <int CH, bool QUADS>
@@ -171,9 +136,6 @@ __global__ __launch_bounds__(KF_THREADS) void keyframe_encode_kernel(size_t N, c
         for (int c = 0; c < CH; c++) slot[t * CH + c] = (uint8_t)kf_quantise(image[(size_t)c * N + t]);
     }
 }
-
-static bool kf_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-static bool kf_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }   // a slot of a 16-byte aligned slab when N % 4 == 0
 
 int keyframe_decode(int W, int H, int level, const uint8_t* color, const uint8_t* mask, const int32_t* frame, int n_frames, float* out, float* weight,
                     hipStream_t s)

@@ -119,6 +119,7 @@ FUSED_CHECKS = {name: (os.path.join(HERE, name + "_check.cpp"), os.path.join(PKG
     "fused_geometry",         # the per-pixel geometry images (gslic::FusedStep::geometry_images)
     "fused_exposure",         # the step and the pose gradient under a trainable per-view exposure (gslic::Exposure), two views
     "fused_keyframe",         # the keyframe store (gslic::KeyframeStore): add_u8, put, a decoded target at a pyramid level and one step on it
+    "fused_keyframe_depth",   # ... its depth slabs: add_u8 with depth, put_depth, decoded depth targets at two levels and one depth step on them
     "fused_pose",             # trainable keyframe poses (gslic::PoseSet): pose steps on two rows through FusedStep::pose_gradient
     "fused_pose_adam",        # the joint map + pose step with the Adam inside the camera backward (FusedStep::step_with_pose)
 )}

@@ -285,48 +285,92 @@ struct PoseSet {
 // gslic_keyframe_decode; storage, decode and encode rules in include/gslic_hip.h).  color: uint8 [capacity,H,W,3] interleaved RGB; mask (masks =
 // true): uint8 [capacity,H,W], decoded into the float32 weight image the weighted loss takes.  target() is usable as it is as the gt_image (and weight)
 // of FusedStep::step.  The reference keeps every keyframe as a float32 CPU tensor and uploads it at every step (gaussian.cpp:49, :80, :678).
+// depths = true: every slot also holds its LiDAR range image as 16-bit codes (depth: uint16 [capacity,H,W], 0 = not measured, k = depth k *
+// depth_step, depth_step a power of two in [2^-16, 1]) and, depth_weights = true, an 8-bit confidence weight (dweight: uint8 [capacity,H,W]) —
+// gslic_keyframe_encode_depth / gslic_keyframe_decode_depth.  depth_target() is usable as it is as the gt_depth (and depth_weight) of FusedStep::step.
 struct KeyframeTarget {
     torch::Tensor image;    // float32 [3,H_l,W_l]
     torch::Tensor weight;   // float32 [H_l,W_l] (a store with masks), undefined otherwise
 };
+struct KeyframeDepthTarget {
+    torch::Tensor depth;    // float32 [H_l,W_l], 0 = not measured
+    torch::Tensor weight;   // float32 [H_l,W_l] (a store with depth weights), undefined otherwise
+};
 class KeyframeStore {
 public:
     torch::Tensor color, mask;   // the slabs
-    KeyframeStore(int width, int height, int capacity, torch::Device device = torch::kCUDA, bool masks = false) : W_(width), H_(height), cap_(capacity)
+    torch::Tensor depth, dweight;   // the depth slabs (depths / depth_weights), undefined otherwise
+    KeyframeStore(int width, int height, int capacity, torch::Device device = torch::kCUDA, bool masks = false, bool depths = false,
+                  float depth_step = 0.001953125f /*2^-9*/, bool depth_weights = false)
+        : W_(width), H_(height), cap_(capacity), depth_step_(depth_step)
     {
         TORCH_CHECK(width >= 1 && height >= 1 && capacity >= 1, "KeyframeStore: width, height and capacity must all be at least 1");
+        TORCH_CHECK(depths || !depth_weights, "KeyframeStore: depth_weights needs depths (the weight is the depth's)");
+        int e = 0;
+        TORCH_CHECK(!depths || (depth_step > 0.0f && depth_step <= 1.0f && std::frexp(depth_step, &e) == 0.5f && e >= -15),
+                    "KeyframeStore: depth_step = ", depth_step, " must be a power of two in [2^-16, 1]");
         const auto u8 = torch::TensorOptions().dtype(torch::kByte).device(device);
         color = torch::zeros({capacity, height, width, 3}, u8);
         if (masks) mask = torch::zeros({capacity, height, width}, u8);
+        if (depths) depth = torch::zeros({capacity, height, width}, u8.dtype(torch::kUInt16));
+        if (depth_weights) dweight = torch::zeros({capacity, height, width}, u8);
         frames_ = torch::arange(capacity, u8.dtype(torch::kInt32));
         serial_.assign((size_t)capacity, 0);
     }
     int n() const { return n_; }
-    int64_t nbytes() const { return color.numel() + (mask.defined() ? mask.numel() : 0); }
+    int64_t nbytes() const
+    {
+        return color.numel() + (mask.defined() ? mask.numel() : 0) + (depth.defined() ? 2 * depth.numel() : 0) + (dweight.defined() ? dweight.numel() : 0);
+    }
+    bool has_depths() const { return depth.defined(); }
+    bool has_depth_weights() const { return dweight.defined(); }
+    float depth_step() const { return depth_step_; }
     int64_t serial(int slot) const { return serial_[(size_t)index(slot)]; }
     // encodes a float32 [3,H,W] image (and, on a store with masks, a float32 [H,W] mask; undefined: weight 1 everywhere) into the next slot
-    int add(const torch::Tensor& image, const torch::Tensor& mask_image = torch::Tensor())
+    // depth_image / depth_weight (a store with depths / depth weights): float32 [H,W], encoded into the slot's codes; a slot written without a
+    // depth image holds "nothing measured"
+    int add(const torch::Tensor& image, const torch::Tensor& mask_image = torch::Tensor(), const torch::Tensor& depth_image = torch::Tensor(),
+            const torch::Tensor& depth_weight = torch::Tensor())
     {
         TORCH_CHECK(n_ < cap_, "KeyframeStore: all ", cap_, " slots are filled");
+        check_depth(depth_image, depth_weight);
         write(n_, image, mask_image);
+        write_depth(n_, depth_image, depth_weight);
         return n_++;
     }
     // copies a uint8 [H,W,3] image (bgr: the channels flipped, in LibTorch) and a uint8 [H,W] mask into the next slot
-    int add_u8(const torch::Tensor& hwc, const torch::Tensor& mask_u8 = torch::Tensor(), bool bgr = false)
+    int add_u8(const torch::Tensor& hwc, const torch::Tensor& mask_u8 = torch::Tensor(), bool bgr = false,
+               const torch::Tensor& depth_image = torch::Tensor(), const torch::Tensor& depth_weight = torch::Tensor())
     {
         TORCH_CHECK(n_ < cap_, "KeyframeStore: all ", cap_, " slots are filled");
+        check_depth(depth_image, depth_weight);
         write_u8(n_, hwc, mask_u8, bgr);
+        write_depth(n_, depth_image, depth_weight);
         return n_++;
     }
     // replaces a filled slot by a float image (as add) and bumps the slot's serial number
-    void put(int slot, const torch::Tensor& image, const torch::Tensor& mask_image = torch::Tensor())
+    void put(int slot, const torch::Tensor& image, const torch::Tensor& mask_image = torch::Tensor(), const torch::Tensor& depth_image = torch::Tensor(),
+             const torch::Tensor& depth_weight = torch::Tensor())
     {
+        check_depth(depth_image, depth_weight);
         write(index(slot), image, mask_image);
+        write_depth(slot, depth_image, depth_weight);
         serial_[(size_t)slot]++;
     }
-    void put_u8(int slot, const torch::Tensor& hwc, const torch::Tensor& mask_u8 = torch::Tensor(), bool bgr = false)
+    void put_u8(int slot, const torch::Tensor& hwc, const torch::Tensor& mask_u8 = torch::Tensor(), bool bgr = false,
+                const torch::Tensor& depth_image = torch::Tensor(), const torch::Tensor& depth_weight = torch::Tensor())
     {
+        check_depth(depth_image, depth_weight);
         write_u8(index(slot), hwc, mask_u8, bgr);
+        write_depth(slot, depth_image, depth_weight);
+        serial_[(size_t)slot]++;
+    }
+    // replaces only the depth (and depth weight) of a filled slot — LiDAR that arrives after the image — and bumps the slot's serial number
+    void put_depth(int slot, const torch::Tensor& depth_image, const torch::Tensor& depth_weight = torch::Tensor())
+    {
+        TORCH_CHECK(depth.defined(), "KeyframeStore: put_depth on a store built without depths");
+        TORCH_CHECK(depth_image.defined(), "KeyframeStore: put_depth without a depth image");
+        write_depth(index(slot), depth_image, depth_weight);
         serial_[(size_t)slot]++;
     }
     // the float32 target of a slot at a pyramid level (one launch; the slot index is read from a device word the store keeps)
@@ -346,12 +390,59 @@ public:
         TORCH_CHECK(rc == GSLIC_OK, "gslic_keyframe_decode failed (", rc, "): ", gslic_last_error());
         return out;
     }
+    // the float32 depth target (and depth weight) of a slot at a pyramid level: the nearest return of every block (one launch)
+    KeyframeDepthTarget depth_target(int slot, int level = 0)
+    {
+        torch::NoGradGuard ng;
+        index(slot);
+        TORCH_CHECK(depth.defined(), "KeyframeStore: this store was built without depths");
+        TORCH_CHECK(level >= 0 && level <= GSLIC_KEYFRAME_MAX_LEVEL && (W_ >> level) >= 1 && (H_ >> level) >= 1, "KeyframeStore: a ", W_, " x ", H_,
+                    " image has no level ", level);
+        const auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(color.device());
+        KeyframeDepthTarget out;
+        out.depth = torch::empty({H_ >> level, W_ >> level}, f32);
+        if (dweight.defined()) out.weight = torch::empty({H_ >> level, W_ >> level}, f32);
+        const int rc = gslic_keyframe_decode_depth(W_, H_, level, static_cast<const uint16_t*>(depth.data_ptr()),
+                                                   dweight.defined() ? dweight.data_ptr<uint8_t>() : nullptr, frames_.data_ptr<int32_t>() + slot, n_,
+                                                   depth_step_, out.depth.data_ptr<float>(), dweight.defined() ? out.weight.data_ptr<float>() : nullptr,
+                                                   current_stream());
+        TORCH_CHECK(rc == GSLIC_OK, "gslic_keyframe_decode_depth failed (", rc, "): ", gslic_last_error());
+        return out;
+    }
 
 private:
     int index(int slot) const
     {
         TORCH_CHECK(slot >= 0 && slot < n_, "KeyframeStore: slot ", slot, " is outside [0, ", n_, ")");
         return slot;
+    }
+    void check_depth(const torch::Tensor& depth_image, const torch::Tensor& depth_weight) const
+    {
+        TORCH_CHECK(!depth_image.defined() || depth.defined(), "KeyframeStore: depth given to a store built without depths");
+        TORCH_CHECK(!depth_weight.defined() || dweight.defined(), "KeyframeStore: depth_weight given to a store built without depth weights");
+        TORCH_CHECK(!depth_weight.defined() || depth_image.defined(), "KeyframeStore: depth_weight given without depth");
+    }
+    void write_depth(int slot, const torch::Tensor& depth_image, const torch::Tensor& depth_weight)
+    {
+        torch::NoGradGuard ng;
+        check_depth(depth_image, depth_weight);
+        if (!depth.defined()) return;
+        if (!depth_image.defined()) {   // nothing measured
+            depth[slot].view(torch::kInt16).zero_();
+            if (dweight.defined()) dweight[slot].fill_(255);
+            return;
+        }
+        const torch::Tensor d = depth_image.detach().to(color.device(), torch::kFloat32).contiguous();
+        TORCH_CHECK(d.dim() == 2 && d.size(0) == H_ && d.size(1) == W_, "KeyframeStore: the depth image must be [", H_, ", ", W_, "]");
+        torch::Tensor w;
+        if (depth_weight.defined()) {
+            w = depth_weight.detach().to(color.device(), torch::kFloat32).contiguous();
+            TORCH_CHECK(w.dim() == 2 && w.size(0) == H_ && w.size(1) == W_, "KeyframeStore: the depth weight must be [", H_, ", ", W_, "]");
+        }
+        const int rc = gslic_keyframe_encode_depth(W_, H_, d.data_ptr<float>(), w.defined() ? w.data_ptr<float>() : nullptr,
+                                                   static_cast<uint16_t*>(depth.data_ptr()), dweight.defined() ? dweight.data_ptr<uint8_t>() : nullptr,
+                                                   cap_, slot, depth_step_, current_stream());
+        TORCH_CHECK(rc == GSLIC_OK, "gslic_keyframe_encode_depth failed (", rc, "): ", gslic_last_error());
     }
     void write(int slot, const torch::Tensor& image, const torch::Tensor& mask_image)
     {
@@ -387,6 +478,7 @@ private:
         }
     }
     int W_, H_, cap_, n_ = 0;
+    float depth_step_;
     torch::Tensor frames_;            // int32 [capacity] = 0 .. capacity-1: the device word that names slot i is frames_[i]
     std::vector<int64_t> serial_;
 };

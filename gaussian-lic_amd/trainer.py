@@ -1379,18 +1379,32 @@ class KeyframeStore:
     include/gslic_hip.h).  The reference keeps every keyframe as a float32 CPU tensor and uploads it at every step (gaussian.cpp:49, :80, :678).
     color: uint8 [capacity, H, W, 3] interleaved RGB; mask (masks=True): uint8 [capacity, H, W], decoded into the float32 [H_l, W_l] weight image
     the weighted loss takes (255 = weight 1).  Slots are handed out in order; `n` of them are filled.  Every slot has a serial number that put()
-    bumps: a GraphedStep that has to repeat a step checks it.  Nothing here synchronises; add_u8 is a plain copy."""
+    bumps: a GraphedStep that has to repeat a step checks it.  Nothing here synchronises; add_u8 is a plain copy.
+
+    depths=True: every slot also holds its LiDAR range image as 16-bit codes — depth: uint16 [capacity, H, W], 0 = not measured, k = depth
+    k * depth_step, depth_step a power of two in [2^-16, 1] (2^-9 m: 1.95 mm, 127.998 m) — and, depth_weights=True, a confidence weight —
+    dweight: uint8 [capacity, H, W] (gslic_keyframe_encode_depth / gslic_keyframe_decode_depth; the rules are in include/gslic_hip.h).  A level's
+    depth target is the nearest return of every 2^l x 2^l block, which is the code-rounded range image of camera.at_level(l): one stored image
+    serves every level.  A slot written without depth holds "nothing measured"."""
 
     MAX_LEVEL = 4   # GSLIC_KEYFRAME_MAX_LEVEL
 
-    def __init__(self, width, height, capacity, device, masks=False):
+    def __init__(self, width, height, capacity, device, masks=False, depths=False, depth_step=2.0 ** -9, depth_weights=False):
         W, H, C = int(width), int(height), int(capacity)
         if W < 1 or H < 1 or C < 1:
             raise ValueError(f"KeyframeStore: width = {width}, height = {height}, capacity = {capacity} must all be at least 1")
+        if depth_weights and not depths:
+            raise ValueError("KeyframeStore: depth_weights=True needs depths=True (the weight is the depth's)")
+        mant, exp = math.frexp(float(depth_step)) if 0.0 < float(depth_step) <= 1.0 else (0.0, 0)
+        if depths and not (mant == 0.5 and -15 <= exp <= 1):
+            raise ValueError(f"KeyframeStore: depth_step = {depth_step!r} must be a power of two in [2^-16, 1]")
         self.width, self.height, self.capacity = W, H, C
         self.device = torch.device(device)
         self.color = torch.zeros(C, H, W, 3, dtype=torch.uint8, device=self.device)
         self.mask = torch.zeros(C, H, W, dtype=torch.uint8, device=self.device) if masks else None
+        self.depth = torch.zeros(C, H, W, dtype=torch.uint16, device=self.device) if depths else None
+        self.dweight = torch.zeros(C, H, W, dtype=torch.uint8, device=self.device) if depth_weights else None
+        self.depth_step = float(depth_step) if depths else None
         self._frames = torch.arange(C, dtype=torch.int32, device=self.device)   # the device word that names slot i is _frames[i]: no copy per decode
         self._serial = [0] * C
         self._n = 0
@@ -1403,11 +1417,19 @@ class KeyframeStore:
     @property
     def nbytes(self):
         """Device bytes of the slabs (all `capacity` slots)."""
-        return self.color.numel() + (0 if self.mask is None else self.mask.numel())
+        return sum(t.numel() * t.element_size() for t in (self.color, self.mask, self.depth, self.dweight) if t is not None)
 
     @property
     def has_masks(self):
         return self.mask is not None
+
+    @property
+    def has_depths(self):
+        return self.depth is not None
+
+    @property
+    def has_depth_weights(self):
+        return self.dweight is not None
 
     def _index(self, slot):
         s = int(slot)
@@ -1468,31 +1490,81 @@ class KeyframeStore:
             else:
                 self.mask[slot].copy_(mask)
 
-    def add(self, image, mask=None):
+    def _check_depth(self, depth, depth_weight):
+        if depth is not None and self.depth is None:
+            raise ValueError("KeyframeStore: depth given to a store built without depths (pass depths=True to the constructor)")
+        if depth_weight is not None and self.dweight is None:
+            raise ValueError("KeyframeStore: depth_weight given to a store built without depth weights (pass depth_weights=True to the constructor)")
+        if depth_weight is not None and depth is None:
+            raise ValueError("KeyframeStore: depth_weight given without depth (the weight is the depth's)")
+
+    def _write_depth(self, slot, depth, depth_weight):
+        """gslic_keyframe_encode_depth of a float depth image [H,W] (and a float weight [H,W]; None on a store with depth weights: 255 everywhere)
+        into `slot`; depth None on a store with depths: the slot is cleared to "nothing measured"."""
+        from . import _lib
+        H, W = self.height, self.width
+        self._check_depth(depth, depth_weight)
+        if self.depth is None:
+            return
+        if depth is None:
+            self.depth[slot].view(torch.int16).zero_()
+            if self.dweight is not None:
+                self.dweight[slot].fill_(255)
+            return
+        d = depth.detach().to(self.device, torch.float32).contiguous()
+        if tuple(d.shape) != (H, W):
+            raise ValueError(f"KeyframeStore: depth of shape {tuple(depth.shape)} given to a store of [{H}, {W}]")
+        w = None
+        if depth_weight is not None:
+            w = depth_weight.detach().to(self.device, torch.float32).contiguous()
+            if tuple(w.shape) != (H, W):
+                raise ValueError(f"KeyframeStore: depth_weight of shape {tuple(depth_weight.shape)} given to a store of [{H}, {W}]")
+        _lib.check(_lib.lib().gslic_keyframe_encode_depth(W, H, _lib.ptr(d), _lib.ptr(w), _lib.ptr(self.depth), _lib.ptr(self.dweight), self.capacity,
+                                                          slot, self.depth_step, _lib.current_stream_ptr()))
+
+    def add(self, image, mask=None, depth=None, depth_weight=None):
         """Encodes a float32 [3,H,W] image (values clamped to [0, 1], NaN as 0) and, on a store with masks, a float32 [H,W] mask into the next
-        slot; returns the slot."""
+        slot; on a store with depths, a float32 [H,W] depth image (and depth weight) too; returns the slot."""
         slot = self._next()
+        self._check_depth(depth, depth_weight)
         self._write(slot, image, mask)
+        self._write_depth(slot, depth, depth_weight)
         self._n += 1
         return slot
 
-    def add_u8(self, hwc_uint8, mask=None, bgr=False):
+    def add_u8(self, hwc_uint8, mask=None, bgr=False, depth=None, depth_weight=None):
         """Copies a uint8 [H,W,3] image (any device; bgr=True: the channels are flipped, in torch) and a uint8 [H,W] mask into the next slot;
-        returns the slot."""
+        depth / depth_weight: float32 [H,W] images, encoded as add's; returns the slot."""
         slot = self._next()
+        self._check_depth(depth, depth_weight)
         self._write_u8(slot, hwc_uint8, mask, bgr)
+        self._write_depth(slot, depth, depth_weight)
         self._n += 1
         return slot
 
-    def put(self, slot, image=None, mask=None, u8=None, bgr=False):
-        """Replaces a filled slot — by a float image (as add) or, u8=, a uint8 [H,W,3] one (as add_u8) — and bumps the slot's serial number."""
+    def put(self, slot, image=None, mask=None, u8=None, bgr=False, depth=None, depth_weight=None):
+        """Replaces a filled slot — by a float image (as add) or, u8=, a uint8 [H,W,3] one (as add_u8), with its depth (None: nothing measured) —
+        and bumps the slot's serial number."""
         s = self._index(slot)
         if (image is None) == (u8 is None):
             raise ValueError("KeyframeStore.put: pass exactly one of image and u8")
+        self._check_depth(depth, depth_weight)
         if u8 is None:
             self._write(s, image, mask)
         else:
             self._write_u8(s, u8, mask, bgr)
+        self._write_depth(s, depth, depth_weight)
+        self._serial[s] += 1
+        return s
+
+    def put_depth(self, slot, depth, depth_weight=None):
+        """Replaces only the depth (and depth weight) of a filled slot — LiDAR that arrives after the image — and bumps the slot's serial number."""
+        s = self._index(slot)
+        if self.depth is None:
+            raise ValueError("KeyframeStore: put_depth on a store built without depths (pass depths=True to the constructor)")
+        if depth is None:
+            raise ValueError("KeyframeStore.put_depth: depth is None")
+        self._write_depth(s, depth, depth_weight)
         self._serial[s] += 1
         return s
 
@@ -1523,6 +1595,39 @@ class KeyframeStore:
                     raise ValueError(f"KeyframeStore.target: out's {name} must be a contiguous float32 {list(shape)} tensor on the store's device")
         self._decode(self._frames[s:s + 1], level, image, weight)
         return image if self.mask is None else (image, weight)
+
+    def _decode_depth(self, word, level, depth_out, dweight_out, n_frames=None):
+        """gslic_keyframe_decode_depth of the slot the device word names: one launch, depth and (with depth weights) its weight."""
+        from . import _lib
+        _lib.check(_lib.lib().gslic_keyframe_decode_depth(self.width, self.height, int(level), _lib.ptr(self.depth), _lib.ptr(self.dweight),
+                                                          _lib.ptr(word), self._n if n_frames is None else int(n_frames), self.depth_step,
+                                                          _lib.ptr(depth_out), None if self.dweight is None else _lib.ptr(dweight_out),
+                                                          _lib.current_stream_ptr()))
+
+    def depth_target_buffers(self, level=0):
+        """Uninitialised (depth [H_l,W_l], weight [H_l,W_l] or None) of a level, as depth_target(out=) takes them."""
+        if self.depth is None:
+            raise ValueError("KeyframeStore: this store was built without depths (pass depths=True to the constructor)")
+        Wl, Hl = self.level_size(level)
+        depth = torch.empty(Hl, Wl, dtype=torch.float32, device=self.device)
+        return depth, (torch.empty(Hl, Wl, dtype=torch.float32, device=self.device) if self.dweight is not None else None)
+
+    def depth_target(self, slot, level=0, out=None):
+        """The float32 depth target of a slot at a level: depth [H_l,W_l] (0 = not measured), or (depth, weight [H_l,W_l]) on a store with depth
+        weights — usable as they are as gt_depth / depth_weight of every training_step*.  out: the tensor (the pair) to write into."""
+        s = self._index(slot)
+        Wl, Hl = self.level_size(level)
+        if out is None:
+            depth, weight = self.depth_target_buffers(level)
+        else:
+            if self.depth is None:
+                raise ValueError("KeyframeStore: this store was built without depths (pass depths=True to the constructor)")
+            depth, weight = out if self.dweight is not None else (out, None)
+            for t, name in ((depth, "depth"), (weight, "weight")):
+                if t is not None and (tuple(t.shape) != (Hl, Wl) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.color.device):
+                    raise ValueError(f"KeyframeStore.depth_target: out's {name} must be a contiguous float32 {[Hl, Wl]} tensor on the store's device")
+        self._decode_depth(self._frames[s:s + 1], level, depth, weight)
+        return depth if self.dweight is None else (depth, weight)
 
 
 class Exposure:
@@ -2307,6 +2412,11 @@ class GraphedStep:
     added after a capture stay reachable); the index is validated against the filled slots on the host before the word is written.  A repeated step
     uses its own frame index and the slot's serial number: a slot replaced (put) since the step was issued fails loudly.  gt_image together with
     a store, or frame given to a step built without one, raises.  Without keyframes the step is what it was, launch for launch.
+    A store with depths under lambda_depth != 0: the step is the depth step, and its static gt_depth buffer — with depth weights its depth_weight
+    buffer too — is filled by ONE gslic_keyframe_decode_depth launch right behind the colour decode, from the same frame word: step(frame=j)
+    changes colour target, mask, depth target and depth weight together.  gt_depth= given to such a step (at construction or in step()) raises,
+    and so does depth_weight= on a store with depth weights; depth_weight= on a depth store without them is host-loaded as ever.  put_depth bumps
+    the slot's serial number like put.  lambda_depth == 0, or a store without depths, is the step as it was, launch for launch.
 
     poses (a trainer.PoseSet) / view: the step READS its pose from the set: one gslic_pose_load launch inside the step fills the static view / proj /
     campos buffers from the row a device int32 names; step(view=j) fills that word (and the exposure's, when there is one: view names both rows),
@@ -2342,6 +2452,8 @@ class GraphedStep:
         self.model, self.bg, self.headroom, self.check_every = model, bg, float(headroom), int(check_every)
         dev = model.device
         self.keyframes, self.level = keyframes, int(level)
+        # a store with depths under lambda_depth != 0: the depth target (and the store's depth weight) is decoded inside the step as well
+        self._kf_depth = isinstance(keyframes, KeyframeStore) and keyframes.has_depths and lambda_depth != 0.0
         if keyframes is None:
             if frame is not None or self.level != 0:
                 raise ValueError("GraphedStep: frame / level given without keyframes (pass a trainer.KeyframeStore)")
@@ -2354,6 +2466,12 @@ class GraphedStep:
                                  "and frame=)")
             if weight is not None and keyframes.has_masks:
                 raise ValueError("GraphedStep: weight given together with a keyframe store that has masks (the store's mask is the step's weight)")
+            if self._kf_depth and gt_depth is not None:
+                raise ValueError("GraphedStep: gt_depth given together with a keyframe store that has depths (the step decodes its depth target "
+                                 "from the store, from the same frame word)")
+            if self._kf_depth and depth_weight is not None and keyframes.has_depth_weights:
+                raise ValueError("GraphedStep: depth_weight given together with a keyframe store that has depth weights (the store's depth weight "
+                                 "is the step's)")
             self._kf_size = keyframes.level_size(self.level)
             self._kf_host = keyframes._index(0 if frame is None else frame)
             self._kf_word = torch.full((1,), self._kf_host, dtype=torch.int32, device=dev)
@@ -2382,11 +2500,12 @@ class GraphedStep:
             self.gt = gt_image.clone()
         else:
             self.gt, kf_weight = keyframes.target_buffers(self.level)   # filled by the decode launch inside the step
-        self.use_depth = _use_depth("GraphedStep", gt_depth, lambda_depth, depth_weight, depth_huber)
+        kf_gt_depth, kf_depth_weight = keyframes.depth_target_buffers(self.level) if self._kf_depth else (None, None)   # filled by the depth decode launch
+        self.use_depth = _use_depth("GraphedStep", kf_gt_depth if self._kf_depth else gt_depth, lambda_depth, depth_weight, depth_huber)
         self.lambda_depth = float(lambda_depth) if self.use_depth else 0.0
-        self.depth_weight = depth_weight.detach().float().contiguous().clone() if self.use_depth and depth_weight is not None else None
+        self.depth_weight = depth_weight.detach().float().contiguous().clone() if self.use_depth and depth_weight is not None else kf_depth_weight
         self.depth_huber = float(depth_huber) if self.use_depth else 0.0
-        self.gt_depth = gt_depth.detach().float().contiguous().clone() if self.use_depth else None
+        self.gt_depth = kf_gt_depth if self._kf_depth else (gt_depth.detach().float().contiguous().clone() if self.use_depth else None)
         self.use_weight = weight is not None or kf_weight is not None
         self.weight = kf_weight if kf_weight is not None else (weight.detach().float().contiguous().clone() if self.use_weight else None)
 
@@ -2435,6 +2554,8 @@ class GraphedStep:
     def _eager(self):
         if self.keyframes is not None:
             self.keyframes._decode(self._kf_word, self.level, self.gt, self.weight, n_frames=self.keyframes.capacity)
+            if self._kf_depth:
+                self.keyframes._decode_depth(self._kf_word, self.level, self.gt_depth, self.depth_weight, n_frames=self.keyframes.capacity)
         if self.poses is not None:
             self.poses._load_row(self._pose_word, self.view, self.proj, self.campos)
         rr = _RawRaster(self.model, self.cam, self.bg, self.use_depth, e=self.e, pose=(self.view, self.proj, self.campos))
@@ -2513,6 +2634,12 @@ class GraphedStep:
                 raise ValueError("GraphedStep: gt_image given to a step built on a keyframe store (its target is decoded inside the step: pass frame=)")
             if weight is not None and weight is not False and self.keyframes.has_masks:
                 raise ValueError("GraphedStep: weight given to a step whose keyframe store has masks (the store's mask is the step's weight)")
+            if gt_depth is not None and self._kf_depth:
+                raise ValueError("GraphedStep: gt_depth given to a step whose keyframe store has depths (its depth target is decoded inside the step: "
+                                 "pass frame=)")
+            if depth_weight is not None and self._kf_depth and self.keyframes.has_depth_weights:
+                raise ValueError("GraphedStep: depth_weight given to a step whose keyframe store has depth weights (the store's depth weight is the "
+                                 "step's)")
             if frame is not None and self.keyframes._index(frame) != self._kf_host:
                 self._kf_host = self.keyframes._index(frame)
                 self._kf_word.fill_(self._kf_host)

@@ -766,6 +766,54 @@ int gslic_keyframe_encode(
     int32_t W, int32_t H, const float* image /*[3,H,W] or NULL*/, const float* mask /*[H,W] or NULL*/, uint8_t* color_slab, uint8_t* mask_slab,
     int32_t capacity, int32_t slot, void* stream);
 
+/* gslic_keyframe_encode_depth / gslic_keyframe_decode_depth — the keyframe store's LiDAR depth: one range image per slot kept as 16-bit codes (and
+ * an optional 8-bit confidence weight), decoded into the float32 depth target (and depth weight) of a pyramid level (additive, ABI 8).  Three rules,
+ * each reproducible bit for bit from numpy (tests/keyframe_depth_ref.py):
+ *
+ * STORAGE.  depth_slab: uint16 [capacity, H, W] DEVICE.  Code 0 = not measured; code k >= 1 = depth k * step.  step: float32, a power of two 2^e
+ * with -16 <= e <= 0, the caller's choice and fixed per store (2^-9 m: 1.95 mm resolution, 127.998 m range); anything else is
+ * GSLIC_ERR_INVALID_ARG.  dweight_slab (optional): uint8 [capacity, H, W] DEVICE.
+ *
+ * ENCODE.  depth: float32 [H, W] DEVICE -> slot `slot` of depth_slab; weight: float32 [H, W] DEVICE or NULL -> slot `slot` of dweight_slab.
+ *   d is measured iff d > 0 and d is finite            (NaN, -x, +-0 and +inf are not)
+ *   t = d * (1 / step)                                  exact: 1 / step is a power of two
+ *   k = floorf(t + 0.5f)
+ *   code = k if 1 <= k <= 65535, else 0                 a depth below half a step and one beyond the range read as NOT MEASURED, never as a clamped depth
+ * A weight x is quantised by the mask's rule of gslic_keyframe_encode: x' = x clamped to [0, 1] (NaN -> 0), (uint8) floorf((x' * 255.0f) + 0.5f),
+ * the product rounded on its own.  With a dweight_slab and weight == NULL the slot's weights are all 255.
+ *
+ * DECODE at level l (levels, W_l, H_l, the block [X 2^l, (X+1) 2^l) x [Y 2^l, (Y+1) 2^l) and the dropped remainder columns and rows as for
+ * gslic_keyframe_decode).  Every block pixel with code c != 0 has the key
+ *   key = c                                 without a dweight_slab
+ *   key = (c << 8) | (255 - wcode)          with one
+ * and m = the UNSIGNED MINIMUM of the block's keys: the nearest return, and among pixels that share its code the one of the largest weight, so the
+ * result does not depend on a pixel's position inside its block.
+ *   depth_out[Y, X]   = (float)code(m) * step                             exact (16 bits times a power of two); code(m) = m, or m >> 8
+ *   dweight_out[Y, X] = (float)(255 - (m & 255)) * (1.0f / 255.0f)        the mask's level-0 value d(v)
+ * and both are 0 where the block holds no measured pixel.  The slot is read from the DEVICE word *frame as in gslic_keyframe_decode: a word outside
+ * [0, n_frames) writes NOTHING.
+ *
+ * PROPERTIES.  decode_0(encode(D)) == the code-rounded D.  decode_l(encode(D)) == positive_min_pool(decode_0(encode(D)), l): the minimum of codes is
+ * taken on integers, ahead of the one multiply, and k -> k * step is monotonic.  The level-l LiDAR range image of Camera.at_level(l) is the
+ * positive-minimum pool of the level-0 image (a point's level-l pixel is floor(pixel_0 / 2^l)), and rounding to codes is monotonic, so decode_l of an
+ * encoded level-0 range image equals the code-rounded range image of the level-l camera: ONE stored image serves every level.
+ *
+ * Both calls are one launch, shaped like the colour pair: where W % (4 << l) == 0 a lane of the decode owns four consecutive output pixels (per
+ * source row 8 << l bytes of codes and 4 << l bytes of weights in aligned 4- / 8- / 16-byte non-temporal loads, four running minima, one 16-byte
+ * store per plane), one pixel otherwise; the encode takes four pixels per lane where H W % 4 == 0 and the images are 16-byte aligned (one 8-byte
+ * store of codes, one dword of weights), one otherwise.  No atomics, no allocation, no read-back: capturable in a graph.
+ *
+ * GSLIC_ERR_INVALID_ARG before any device work, naming the argument: W or H <= 0, a level outside [0, GSLIC_KEYFRAME_MAX_LEVEL], W_l or H_l of 0,
+ * n_frames < 0, a step that is not such a power of two, a NULL depth_slab / frame / depth_out (decode), dweight_slab != NULL with dweight_out == NULL,
+ * a depth_out / dweight_out / depth_slab / dweight_slab that is not 16-byte aligned; (encode) capacity <= 0, a slot outside [0, capacity), a NULL
+ * depth or depth_slab, a weight without dweight_slab, a depth or weight that is not 4-byte aligned, a slab that is not 16-byte aligned. */
+int gslic_keyframe_decode_depth(
+    int32_t W, int32_t H, int32_t level, const uint16_t* depth_slab, const uint8_t* dweight_slab /*or NULL*/, const int32_t* frame /*[1] device*/,
+    int32_t n_frames, float step, float* depth_out /*[H_l,W_l]*/, float* dweight_out /*[H_l,W_l], with dweight_slab*/, void* stream);
+int gslic_keyframe_encode_depth(
+    int32_t W, int32_t H, const float* depth /*[H,W]*/, const float* weight /*[H,W] or NULL*/, uint16_t* depth_slab, uint8_t* dweight_slab /*or NULL*/,
+    int32_t capacity, int32_t slot, float step, void* stream);
+
 /* gslic_pose_step / gslic_pose_load — a set of trainable keyframe poses on the device (additive, ABI 8; the reference optimises no pose:
  * rasterizer.cpp:171-182 drops the camera gradient).  Per view i the set holds view[i,16], proj[i,16] and campos[i,3] in exactly the layout and
  * meaning of the viewmatrix, projmatrix and cam_pos arguments of the rasteriser (element (r, c) at [4 c + r]; V = [R | t; 0 0 0 1] the world-to-camera

@@ -59,6 +59,17 @@ class PoseAdam(ctypes.Structure):
                 ("beta2", ctypes.c_float), ("eps", ctypes.c_float), ("skip", ctypes.c_void_p)]
 
 
+class PoseShared(ctypes.Structure):
+    """gslic_pose_shared: the three pose arrays of trainer.PoseSet, the shared projection, the device word that names the view, V, the [V,6] twists,
+    the Adam state of (rho_x, phi_x, tau) (sm, sv [7], ssteps [1]), the accumulated correction X [12] and tau [1], the three rates and
+    torch.optim.Adam's scalars, and the optional device word that turns the step off."""
+    _fields_ = [("view_all", ctypes.c_void_p), ("proj_all", ctypes.c_void_p), ("campos_all", ctypes.c_void_p), ("projection", ctypes.c_void_p),
+                ("view", ctypes.c_void_p), ("n_views", ctypes.c_int32), ("twist", ctypes.c_void_p), ("sm", ctypes.c_void_p), ("sv", ctypes.c_void_p),
+                ("ssteps", ctypes.c_void_p), ("X", ctypes.c_void_p), ("tau", ctypes.c_void_p), ("lr_trans", ctypes.c_float),
+                ("lr_rot", ctypes.c_float), ("lr_time", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
+                ("skip", ctypes.c_void_p)]
+
+
 EXPORTS = [
     "gslic_rasterize_forward", "gslic_rasterize_backward", "gslic_rasterize_backward_adam", "gslic_rasterize_backward_camera", "gslic_adam_update", "gslic_adam_update_groups",
     "gslic_fusedssim_forward", "gslic_fusedssim_backward", "gslic_knn_mean_dist2", "gslic_abi_version",
@@ -81,7 +92,7 @@ EXPORTS = [
     "gslic_geometry_images",
     "gslic_exposure_partials_count", "gslic_exposure_apply", "gslic_exposure_backward",
     "gslic_keyframe_decode", "gslic_keyframe_encode", "gslic_keyframe_decode_depth", "gslic_keyframe_encode_depth",
-    "gslic_pose_step", "gslic_pose_load",
+    "gslic_pose_step", "gslic_pose_load", "gslic_pose_step_shared", "gslic_pose_calibrate_rows",
     "gslic_rasterize_backward_camera_adam", "gslic_rasterize_backward_depth_camera_adam",
 ]
 
@@ -132,6 +143,8 @@ def lib():
     L.gslic_keyframe_encode_depth.argtypes = [i32, i32, vp, vp, vp, vp, i32, i32, f32, vp]      # W, H, depth, weight, depth_slab, dweight_slab, capacity, slot, step, stream
     L.gslic_pose_step.argtypes = [ctypes.POINTER(PoseAdam), vp, vp, vp, vp, vp]   # descriptor, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, grad_out, stream
     L.gslic_pose_load.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp]            # view_all, proj_all, campos_all, view_word, n_views, 3 outputs, stream
+    L.gslic_pose_step_shared.argtypes = [ctypes.POINTER(PoseShared), vp, vp, vp, vp, vp]   # descriptor, the three camera gradients, grad_out [7], stream
+    L.gslic_pose_calibrate_rows.argtypes = [ctypes.POINTER(PoseShared), i32, i32, vp]      # descriptor, first, count, stream
     # the rasterize entry points, from the pieces their signatures share (include/gslic_hip.h)
     prm, counts, adam = ctypes.POINTER(RasterParams), [ctypes.POINTER(i32), ctypes.POINTER(i32)], ctypes.POINTER(AdamFused)
     inputs = [vp] * 12                                 # background ... cam_pos (the backward: radii in place of opacities)

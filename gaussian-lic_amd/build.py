@@ -36,6 +36,7 @@ SOURCES = {
     "keyframes.hip": ["-ffp-contract=off"],  # the keyframe store: integer sums and one float multiply (decode), one product rounded on its own (encode), tested on bits
     "keyframes_depth.hip": ["-ffp-contract=off"],  # the store's depth slabs, in a module of their own: an integer minimum and one exact multiply (decode), one exact product, an add and a floor (encode)
     "pose.hip": ["-ffp-contract=off"],       # the pose set's step: every float32 product and sum of the rule rounded on its own, in the header's order
+    "pose_shared.hip": ["-ffp-contract=off"],   # the shared extrinsic / time-offset step and the row calibration: the same rule, rounded the same way
     "knn.hip": [],
     "extend.hip": ["-ffp-contract=off"],  # pixel assignment decides integers: canonical order like preprocess.hip
     "prune.hip": [],         # comparisons and copies only: no arithmetic a flag could change

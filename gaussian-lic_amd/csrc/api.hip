@@ -1598,6 +1598,63 @@ int gslic_pose_load(const float* view_all, const float* proj_all, const float* c
     return pose_load(view_all, proj_all, campos_all, view_word, n_views, view_out, proj_out, campos_out, (hipStream_t)stream);
 }
 
+// the members of a gslic_pose_shared with their extents: the arrays a call writes or reads per set (`view`, the step's word, is listed apart)
+static int pose_shared_state(const gslic_pose_shared* d, NamedRange out[11])
+{
+    const size_t V = (size_t)d->n_views, f = sizeof(float);
+    const NamedRange state[11] = {{d->view_all, 16 * V * f, "view_all"}, {d->proj_all, 16 * V * f, "proj_all"}, {d->campos_all, 3 * V * f, "campos_all"},
+                                  {d->projection, 16 * f, "projection"}, {d->twist, 6 * V * f, "twist"}, {d->X, 12 * f, "X"}, {d->tau, f, "tau"},
+                                  {d->sm, 7 * f, "sm"}, {d->sv, 7 * f, "sv"}, {d->ssteps, sizeof(int32_t), "ssteps"}, {d->view, sizeof(int32_t), "view"}};
+    for (int i = 0; i < 11; i++) out[i] = state[i];
+    return 11;
+}
+
+int gslic_pose_step_shared(const gslic_pose_shared* d, const float* dL_dviewmatrix, const float* dL_dprojmatrix, const float* dL_dcampos,
+                           float* grad_out, void* stream)
+{
+    const char* fn = "pose step shared";
+    if (!d) return set_error(GSLIC_ERR_INVALID_ARG, "%s: the descriptor is NULL", fn);
+    if (d->n_views <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: n_views = %d is not positive", fn, d->n_views);
+    const size_t f = sizeof(float);
+    NamedRange state[11];
+    pose_shared_state(d, state);
+    const NamedRange grads[4] = {{dL_dviewmatrix, 16 * f, "dL_dviewmatrix"}, {dL_dprojmatrix, 16 * f, "dL_dprojmatrix"}, {dL_dcampos, 3 * f, "dL_dcampos"},
+                                 {grad_out, 7 * f, "grad_out"}};
+    for (const auto& a : state)
+        if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, a.name);
+    for (const auto& a : grads)
+        if (!a.p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, a.name);
+    for (const auto& g : grads)
+        for (const auto& a : state)
+            if (ranges_overlap(g, a)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s overlaps %s", fn, g.name, a.name);
+    for (int i = 0; i < 3; i++)
+        if (ranges_overlap(grads[3], grads[i])) return set_error(GSLIC_ERR_INVALID_ARG, "%s: grad_out overlaps %s", fn, grads[i].name);
+    const struct { float x; const char* name; bool below_one; } values[6] = {{d->lr_trans, "lr_trans", false}, {d->lr_rot, "lr_rot", false},
+                                                                             {d->lr_time, "lr_time", false}, {d->beta1, "beta1", true},
+                                                                             {d->beta2, "beta2", true}, {d->eps, "eps", false}};
+    for (const auto& a : values) {
+        if (!(a.x >= 0.0f)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s = %g is NaN or negative", fn, a.name, (double)a.x);
+        if (a.below_one && !(a.x < 1.0f)) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s = %g must be below 1", fn, a.name, (double)a.x);
+    }
+    return pose_step_shared(d, dL_dviewmatrix, dL_dprojmatrix, dL_dcampos, grad_out, (hipStream_t)stream);
+}
+
+int gslic_pose_calibrate_rows(const gslic_pose_shared* d, int32_t first, int32_t count, void* stream)
+{
+    const char* fn = "pose calibrate rows";
+    if (!d) return set_error(GSLIC_ERR_INVALID_ARG, "%s: the descriptor is NULL", fn);
+    if (d->n_views <= 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: n_views = %d is not positive", fn, d->n_views);
+    if (first < 0 || count < 0 || (int64_t)first + (int64_t)count > (int64_t)d->n_views)
+        return set_error(GSLIC_ERR_INVALID_ARG, "%s: rows [first = %d, first + count = %lld) are outside [0, n_views = %d)", fn, first,
+                         (long long)first + (long long)count, d->n_views);
+    NamedRange state[11];
+    pose_shared_state(d, state);
+    for (int i = 0; i < 7; i++)   // what this call reads or writes: the three pose arrays, projection, twist, X and tau
+        if (!state[i].p) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s is NULL", fn, state[i].name);
+    if (count == 0) return GSLIC_OK;
+    return pose_calibrate_rows(d, first, count, (hipStream_t)stream);
+}
+
 int gslic_knn_mean_dist2(int32_t P, const float* points, float* mean_dists, gslic_alloc_fn scratch_alloc, void* scratch_ctx,
                          void* stream)
 {

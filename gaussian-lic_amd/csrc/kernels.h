@@ -276,4 +276,11 @@ int pose_step(const gslic_pose_adam* d, const float* dL_dviewmatrix, const float
 int pose_load(const float* view_all, const float* proj_all, const float* campos_all, const int32_t* view_word, int n_views, float* view_out,
               float* proj_out, float* campos_out, hipStream_t s);
 
+// pose_shared.hip: the calibration the views of a pose set share (arguments validated by the caller).  gslic_pose_step_shared: one launch of one
+// workgroup — chain and Adam on seven coordinates by one thread, then one thread per row moves EVERY row, the accumulated correction X and tau;
+// gslic_pose_calibrate_rows: one thread per row of [first, first + count), T <- exp((tau xi_j)^) (X T)
+int pose_step_shared(const gslic_pose_shared* d, const float* dL_dviewmatrix, const float* dL_dprojmatrix, const float* dL_dcampos, float* grad_out,
+                     hipStream_t s);
+int pose_calibrate_rows(const gslic_pose_shared* d, int first, int count, hipStream_t s);
+
 }  // namespace gslic

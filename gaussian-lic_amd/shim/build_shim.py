@@ -122,6 +122,7 @@ FUSED_CHECKS = {name: (os.path.join(HERE, name + "_check.cpp"), os.path.join(PKG
     "fused_keyframe_depth",   # ... its depth slabs: add_u8 with depth, put_depth, decoded depth targets at two levels and one depth step on them
     "fused_pose",             # trainable keyframe poses (gslic::PoseSet): pose steps on two rows through FusedStep::pose_gradient
     "fused_pose_adam",        # the joint map + pose step with the Adam inside the camera backward (FusedStep::step_with_pose)
+    "fused_pose_shared",      # the shared extrinsic / time-offset calibration (gslic::PoseSet with shared): joint steps, a pose step, a calibrated load
 )}
 
 
@@ -167,5 +168,8 @@ if __name__ == "__main__":
     print(build_dropin_check(force="--force" in sys.argv, groups="dist"))
     for g in ("render_ref", "render", "render_loss", "render_refhost"):
         print(build_dropin_check(force="--force" in sys.argv, groups=g))
-    for name in FUSED_CHECKS:
-        print(build_fused_check(name, force="--force" in sys.argv))
+    # the check programs do not depend on one another: a few compilers at a time (each is one g++ process of about a quarter of a minute)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=max(1, min(8, os.cpu_count() or 1))) as pool:
+        for path in pool.map(lambda name: build_fused_check(name, force="--force" in sys.argv), list(FUSED_CHECKS)):
+            print(path)

@@ -183,6 +183,11 @@ struct Exposure {
 // steps [V] int32, bias-corrected, one rate for the translation and one for the rotation) and the shared projection [16].  gslic_pose_step — one
 // launch — chains the three camera gradients, steps the row and retracts the pose (the rule is written out in include/gslic_hip.h); grad [6] is
 // the last gradient.  load() takes a camera's three arrays as they are; row_camera() hands the row back as views (no copy, no synchronisation).
+// shared = true adds the calibration the views SHARE, as the Python host's PoseSet(shared=True): twist [V,6] (camera-frame (v, w) of each view),
+// Adam's state sm, sv [7], ssteps [1] on (rho_x, phi_x, tau) with the rates lr_trans, lr_rot, lr_time, the accumulated extrinsic correction X [12]
+// (rows of [R_x | t_x]), the accumulated time offset tau [1] and shared_grad [7].  gslic_pose_step_shared (shared_adam_step) steps the seven
+// coordinates from one view's gradient and moves EVERY row; gslic_pose_calibrate_rows (calibrate_rows, load(..., calibrated = true)) brings a row
+// loaded later to the calibration.  shared = false is the set as it is without.
 struct PoseSet {
     torch::Tensor view, proj;     // float32 [V,16]
     torch::Tensor campos;         // float32 [V,3]
@@ -193,11 +198,21 @@ struct PoseSet {
     torch::Tensor views;          // int32 [V] = 0 .. V-1: the device word that names view i is views[i]
     torch::Tensor no_step;        // int32 [1] = 1: a skip word that is set (the chain alone)
     float lr_trans, lr_rot, beta1, beta2, eps;
+    bool shared;                  // the tensors below are defined
+    float lr_time;
+    torch::Tensor twist;          // float32 [V,6]
+    torch::Tensor sm, sv;         // float32 [7]
+    torch::Tensor ssteps;         // int32 [1]
+    torch::Tensor X;              // float32 [12]: rows of [R_x | t_x]
+    torch::Tensor tau;            // float32 [1], seconds
+    torch::Tensor shared_grad;    // float32 [7]
     // projection16: the pose-independent projection the views share, 16 floats in any float32 tensor (host or device)
     PoseSet(int64_t n_views, const torch::Tensor& projection16, torch::Device device = torch::kCUDA, float lr_rot_ = 1e-3f, float lr_trans_ = 1e-3f,
-            float beta1_ = 0.9f, float beta2_ = 0.999f, float eps_ = 1e-8f)
-        : lr_trans(lr_trans_), lr_rot(lr_rot_), beta1(beta1_), beta2(beta2_), eps(eps_)
+            float beta1_ = 0.9f, float beta2_ = 0.999f, float eps_ = 1e-8f, bool shared_ = false, float lr_time_ = 0.0f)
+        : lr_trans(lr_trans_), lr_rot(lr_rot_), beta1(beta1_), beta2(beta2_), eps(eps_), shared(shared_), lr_time(lr_time_)
     {
+        TORCH_CHECK(lr_time_ >= 0.0f, "PoseSet: lr_time must be >= 0");
+        TORCH_CHECK(shared_ || lr_time_ == 0.0f, "PoseSet: lr_time given to a set built without shared");
         TORCH_CHECK(n_views >= 1, "PoseSet: n_views must be at least 1");
         TORCH_CHECK(projection16.numel() == 16 && projection16.scalar_type() == torch::kFloat32, "PoseSet: projection must be 16 float32 values");
         const auto fo = torch::TensorOptions().dtype(torch::kFloat32).device(device);
@@ -208,8 +223,62 @@ struct PoseSet {
         grad = torch::zeros({6}, fo);
         views = torch::arange(n_views, fo.dtype(torch::kInt32));
         no_step = torch::ones({1}, fo.dtype(torch::kInt32));
+        if (shared) {
+            twist = torch::zeros({n_views, 6}, fo);
+            sm = torch::zeros({7}, fo); sv = torch::zeros({7}, fo); ssteps = torch::zeros({1}, fo.dtype(torch::kInt32));
+            X = torch::eye(3, 4, fo).reshape({12}).contiguous();
+            tau = torch::zeros({1}, fo);
+            shared_grad = torch::zeros({7}, fo);
+        }
     }
     int64_t n_views() const { return view.size(0); }
+    void need_shared(const char* who) const { TORCH_CHECK(shared, who, ": the pose set was built without shared"); }
+    void set_twist(int64_t i, const torch::Tensor& xi)   // the camera-frame twist (v, w) of row i: six float32 values, host or device
+    {
+        need_shared("PoseSet::set_twist");
+        index(i);
+        TORCH_CHECK(xi.numel() == 6 && xi.scalar_type() == torch::kFloat32, "PoseSet: a twist is six float32 values");
+        twist[i].copy_(xi.reshape({6}));
+    }
+    // load, then (twist defined) set_twist, then (calibrated) gslic_pose_calibrate_rows on the row: T <- exp((tau xi)^) (X T)
+    void load(int64_t i, const FusedCamera& cam, const torch::Tensor& xi, bool calibrated = false)
+    {
+        need_shared("PoseSet::load");
+        load(i, cam);
+        if (xi.defined()) set_twist(i, xi);
+        if (calibrated) calibrate_rows(i, 1);
+    }
+    void reset_shared_moments() { need_shared("PoseSet::reset_shared_moments"); sm.zero_(); sv.zero_(); ssteps.zero_(); shared_grad.zero_(); }   // X and tau stay
+    torch::Tensor extrinsic() const { need_shared("PoseSet::extrinsic"); return X.to(torch::kCPU).reshape({3, 4}); }   // [R_x | t_x] on the host; synchronises
+    float time_offset() const { need_shared("PoseSet::time_offset"); return tau.to(torch::kCPU).item<float>(); }         // seconds; synchronises
+    gslic_pose_shared shared_descriptor(int64_t i, bool do_step = true) const
+    {
+        need_shared("PoseSet");
+        index(i);
+        gslic_pose_shared d{};
+        d.view_all = view.data_ptr<float>(); d.proj_all = proj.data_ptr<float>(); d.campos_all = campos.data_ptr<float>();
+        d.projection = projection.data_ptr<float>(); d.view = views.data_ptr<int32_t>() + i; d.n_views = (int32_t)n_views();
+        d.twist = twist.data_ptr<float>(); d.sm = sm.data_ptr<float>(); d.sv = sv.data_ptr<float>(); d.ssteps = ssteps.data_ptr<int32_t>();
+        d.X = X.data_ptr<float>(); d.tau = tau.data_ptr<float>();
+        d.lr_trans = lr_trans; d.lr_rot = lr_rot; d.lr_time = lr_time; d.beta1 = beta1; d.beta2 = beta2; d.eps = eps;
+        d.skip = do_step ? nullptr : reinterpret_cast<const uint32_t*>(no_step.data_ptr<int32_t>());
+        return d;
+    }
+    // gslic_pose_step_shared on gradients the caller holds (camg as adam_step's), taken as row i's: shared_grad <- (g, xi_i . g); do_step: every row moves
+    void shared_adam_step(int64_t i, const torch::Tensor& camg, bool do_step = true)
+    {
+        TORCH_CHECK(camg.numel() == 35 && camg.scalar_type() == torch::kFloat32 && camg.is_contiguous(), "PoseSet: camg must be 35 contiguous float32 values");
+        const gslic_pose_shared d = shared_descriptor(i, do_step);
+        const float* g = camg.data_ptr<float>();
+        const int rc = gslic_pose_step_shared(&d, g, g + 16, g + 32, shared_grad.data_ptr<float>(), current_stream());
+        TORCH_CHECK(rc == GSLIC_OK, "gslic_pose_step_shared failed (", rc, "): ", gslic_last_error());
+    }
+    void calibrate_rows(int64_t first, int64_t count)   // gslic_pose_calibrate_rows on rows [first, first + count)
+    {
+        const gslic_pose_shared d = shared_descriptor(0);
+        const int rc = gslic_pose_calibrate_rows(&d, (int32_t)first, (int32_t)count, current_stream());
+        TORCH_CHECK(rc == GSLIC_OK, "gslic_pose_calibrate_rows failed (", rc, "): ", gslic_last_error());
+    }
     int64_t index(int64_t i) const
     {
         TORCH_CHECK(i >= 0 && i < n_views(), "PoseSet: view ", i, " is outside [0, ", n_views(), ")");
@@ -244,12 +313,18 @@ struct PoseSet {
         TORCH_CHECK(torch::equal(o.projection.to(projection.device()), projection), "PoseSet: the state was saved under another projection");
         view.copy_(o.view); proj.copy_(o.proj); campos.copy_(o.campos); m.copy_(o.m); v.copy_(o.v); steps.copy_(o.steps);
         lr_trans = o.lr_trans; lr_rot = o.lr_rot; beta1 = o.beta1; beta2 = o.beta2; eps = o.eps;
+        TORCH_CHECK(o.shared == shared, "PoseSet: one of the two sets was built with shared, the other without");
+        if (shared) {
+            twist.copy_(o.twist); sm.copy_(o.sm); sv.copy_(o.sv); ssteps.copy_(o.ssteps); X.copy_(o.X); tau.copy_(o.tau);
+            lr_time = o.lr_time;
+        }
     }
     PoseSet clone() const
     {
-        PoseSet other(n_views(), projection, projection.device(), lr_rot, lr_trans, beta1, beta2, eps);
+        PoseSet other(n_views(), projection, projection.device(), lr_rot, lr_trans, beta1, beta2, eps, shared, lr_time);
         other.copy_from(*this);
         other.grad.copy_(grad);
+        if (shared) other.shared_grad.copy_(shared_grad);
         return other;
     }
     gslic_pose_adam descriptor(int64_t i, bool do_step = true) const
@@ -990,9 +1065,11 @@ public:
     // tensor; no synchronisation, no host copy.  do_step: the same launch also steps the row (Adam on the six coordinates, the retraction).  The
     // calls gaussian-lic_amd/trainer.py:pose_gradient(poses=, view=, do_step=) issues.  gt_depth / lambda_depth / weight / depth_weight /
     // depth_huber as above; with set_exposure, the exposure row that call named.
+    // shared (a set built with shared): gslic_pose_step_shared in place of gslic_pose_step — returns poses->shared_grad [7]; do_step moves every row.
     torch::Tensor pose_gradient(const FusedCamera& cam, const torch::Tensor& gt_image, PoseSet* poses, int view, bool do_step,
                                 const torch::Tensor& gt_depth = torch::Tensor(), float lambda_depth = 0.0f, torch::Tensor* terms_out = nullptr,
-                                const torch::Tensor& weight = torch::Tensor(), const torch::Tensor& depth_weight = torch::Tensor(), float depth_huber = 0.0f)
+                                const torch::Tensor& weight = torch::Tensor(), const torch::Tensor& depth_weight = torch::Tensor(), float depth_huber = 0.0f,
+                                bool shared = false)
     {
         TORCH_CHECK(poses != nullptr, "pose_gradient: poses is NULL");
         TORCH_CHECK(gt_depth.defined() || (!depth_weight.defined() && depth_huber == 0.0f), "depth_weight / depth_huber given without gt_depth");
@@ -1002,6 +1079,10 @@ public:
         torch::Tensor camg;
         pose_gradient_body(row, gt_image, depth ? &gt_depth : nullptr, depth ? lambda_depth : 0.0f, terms_out, w,
                            depth ? DepthLossOptions{depth_weight.defined() ? &depth_weight : nullptr, depth_huber} : DepthLossOptions{}, &camg);
+        if (shared) {
+            poses->shared_adam_step(view, camg, do_step);
+            return poses->shared_grad;
+        }
         poses->adam_step(view, camg, do_step);
         return poses->grad;
     }
@@ -1011,9 +1092,11 @@ public:
     // poses->grad.  The calls gaussian-lic_amd/trainer.py:training_step_with_pose(poses=, view=, adam_in_backward=True) issues; returns the terms
     // tensor; no synchronisation, no host copy.  gt_depth / lambda_depth / weight / depth_weight / depth_huber as step()'s; with set_exposure the
     // exposure row that call named is applied and updated as step() does.  Not with attached gradient statistics (the camera backward accumulates none).
+    // shared (a set built with shared): the pose launch is gslic_pose_step_shared — the view's gradient steps the shared extrinsic / time-offset
+    // coordinates and every row moves (trainer.training_step_with_pose(shared=True, adam_in_backward=True)); the gradient is poses->shared_grad.
     torch::Tensor step_with_pose(const FusedCamera& cam, const torch::Tensor& gt_image, PoseSet* poses, int view,
                                  const torch::Tensor& gt_depth = torch::Tensor(), float lambda_depth = 0.0f, const torch::Tensor& weight = torch::Tensor(),
-                                 const torch::Tensor& depth_weight = torch::Tensor(), float depth_huber = 0.0f)
+                                 const torch::Tensor& depth_weight = torch::Tensor(), float depth_huber = 0.0f, bool shared = false)
     {
         TORCH_CHECK(poses != nullptr, "step_with_pose: poses is NULL");
         TORCH_CHECK(!gstats_, "step_with_pose: gradient statistics are attached (the fused camera backward accumulates none)");
@@ -1023,7 +1106,8 @@ public:
         torch::Tensor camg;
         torch::Tensor terms = step_body(row, gt_image, depth ? &gt_depth : nullptr, depth ? lambda_depth : 0.0f, weight.defined() ? &weight : nullptr,
                                         depth ? DepthLossOptions{depth_weight.defined() ? &depth_weight : nullptr, depth_huber} : DepthLossOptions{}, &camg);
-        poses->adam_step(view, camg, /*do_step=*/true);
+        if (shared) poses->shared_adam_step(view, camg, /*do_step=*/true);
+        else poses->adam_step(view, camg, /*do_step=*/true);
         return terms;
     }
     // the chain alone, on host arrays in the element order of the kernels' inputs (float[16] with (r, c) at [4c + r])

@@ -1740,11 +1740,23 @@ class PoseSet:
     depend only on fx / W, cx / W, fy / H, cy / H (and the depth range), not on the image size, so one set serves every pyramid level l of a
     KeyframeStore whose width and height are divisible by 2^l (Camera.at_level halves W, H and the four intrinsics exactly; an odd size drops a
     column and changes cx / W): a step takes the image size from ITS camera and the pose from the set, and matches(camera.at_level(l)) says
-    whether the set serves that camera.  Nothing the kernels read from the set depends on the image size."""
+    whether the set serves that camera.  Nothing the kernels read from the set depends on the image size.
+
+    shared=True adds the calibration the views SHARE — a correction of the camera-body extrinsic and of the camera clock offset, the two errors
+    that move every keyframe the same way: twist [V,6] (the camera-frame twist (v, w) of each view in m/s and rad/s, T_cw(t + dt) ~
+    exp((dt xi)^) T_cw(t); zeros until set_twist / load(twist=) give it), Adam's state sm, sv [7] and ssteps [1] on (rho_x, phi_x, tau) with the
+    rates lr_trans, lr_rot and lr_time, the accumulated extrinsic correction X [12] (rows of [R_x | t_x], the identity at the start), the
+    accumulated time offset tau [1] in seconds and shared_grad [7], the last shared gradient.  gslic_pose_step_shared — one launch — chains the
+    rendered view's camera gradient to g, takes g_tau = xi_i . g, steps the seven coordinates and moves EVERY row by d_x + d_tau xi_j (the rule is
+    in include/gslic_hip.h, restated by tests/pose_shared_ref.py); steps reach it through shared=True / train_pose="shared".  extrinsic() and
+    time_offset() read X and tau back (they synchronise, like camera()).  load(view, camera, calibrated=True) brings a keyframe that arrives later
+    to the calibration the older rows were moved to (gslic_pose_calibrate_rows).  shared=False is the set as it is without, bit for bit."""
 
     _BAKED = ("tanfovx", "tanfovy", "limx_neg", "limx_pos", "limy_neg", "limy_pos")   # (level-invariant, like the projection)
 
-    def __init__(self, n_views, camera, device, lr_rot=1e-3, lr_trans=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    _SHARED = ("twist", "sm", "sv", "ssteps", "X", "tau")   # the arrays shared=True adds to the state (shared_grad beside them, like grad)
+
+    def __init__(self, n_views, camera, device, lr_rot=1e-3, lr_trans=1e-3, betas=(0.9, 0.999), eps=1e-8, shared=False, lr_time=0.0):
         V = int(n_views)
         if V < 1:
             raise ValueError(f"PoseSet: n_views = {n_views} must be at least 1")
@@ -1752,6 +1764,11 @@ class PoseSet:
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         if not (self.lr_rot >= 0.0 and self.lr_trans >= 0.0 and 0.0 <= self.betas[0] < 1.0 and 0.0 <= self.betas[1] < 1.0 and self.eps >= 0.0):
             raise ValueError(f"PoseSet: lr_rot = {lr_rot}, lr_trans = {lr_trans}, betas = {betas}, eps = {eps} must be >= 0 and the betas below 1")
+        self.shared, self.lr_time = bool(shared), float(lr_time)
+        if not self.lr_time >= 0.0:
+            raise ValueError(f"PoseSet: lr_time = {lr_time} must be >= 0")
+        if self.lr_time and not self.shared:
+            raise ValueError("PoseSet: lr_time given to a set built without shared=True")
         self.device = dev = torch.device(device)
         self._intrinsics = camera   # (fx, fy, cx, cy, znear, zfar and the image size of the cameras camera() returns)
         self._projection_host = np.array(camera.projection_matrix, np.float32).reshape(16)
@@ -1764,6 +1781,12 @@ class PoseSet:
         self.grad = torch.zeros(6, **f32)
         self._views = torch.arange(V, dtype=torch.int32, device=dev)    # the device word that names view i is _views[i]: no copy per step
         self._no_step = torch.ones(1, dtype=torch.int32, device=dev)    # a skip word that is set: the chain alone (do_step=False)
+        if self.shared:
+            self.twist = torch.zeros(V, 6, **f32)
+            self.sm, self.sv, self.ssteps = torch.zeros(7, **f32), torch.zeros(7, **f32), torch.zeros(1, dtype=torch.int32, device=dev)
+            self.X = torch.eye(3, 4, **f32).reshape(12).contiguous()
+            self.tau = torch.zeros(1, **f32)
+            self.shared_grad = torch.zeros(7, **f32)
         for i in range(V):   # every row starts as the camera's own pose
             self.load(i, camera)
 
@@ -1787,13 +1810,58 @@ class PoseSet:
         if not self.matches(camera):
             raise ValueError(f"{who}: the camera's projection_matrix or baked scalars (tanfov, limits) differ from the pose set's")
 
-    def load(self, view, camera):
-        """Row `view` becomes a bit copy of the camera's three arrays, with zero moments and step count."""
+    def load(self, view, camera, twist=None, calibrated=False):
+        """Row `view` becomes a bit copy of the camera's three arrays, with zero moments and step count.  On a shared set: twist [6] sets the row's
+        camera-frame twist as set_twist does (None leaves it), and calibrated=True then applies the set's calibration to the row — T <-
+        exp((tau xi)^) (X T), gslic_pose_calibrate_rows, one launch — so that a keyframe that arrives after the calibration has moved starts where
+        the older rows were moved to.  calibrated=False is the bit copy."""
         i = self._index(view)
         self._check_camera("PoseSet.load", camera)
+        if (twist is not None or calibrated) and not self.shared:
+            raise ValueError("PoseSet.load: twist / calibrated given to a set built without shared=True")
         put = lambda dst, a, n: dst.copy_(torch.from_numpy(np.ascontiguousarray(a, np.float32).reshape(n)))
         put(self.view[i], camera.world_view_transform, 16); put(self.proj[i], camera.full_proj_transform, 16); put(self.campos[i], camera.camera_center, 3)
         self.reset_moments(i)
+        if twist is not None:
+            self.set_twist(i, twist)
+        if calibrated:
+            self.calibrate_rows(i, 1)
+
+    def _need_shared(self, who):
+        if not self.shared:
+            raise ValueError(f"{who}: the pose set was built without shared=True")
+
+    def set_twist(self, view, xi):
+        """The camera-frame twist (v [m/s], w [rad/s]) of row `view`: six values."""
+        self._need_shared("PoseSet.set_twist")
+        i = self._index(view)
+        xi = np.ascontiguousarray(xi.detach().cpu().numpy() if torch.is_tensor(xi) else xi, np.float32).reshape(-1)
+        if xi.size != 6:
+            raise ValueError(f"PoseSet.set_twist: a twist is six values (v, w), got {xi.size}")
+        self.twist[i].copy_(torch.from_numpy(xi))
+
+    def calibrate_rows(self, first, count):
+        """gslic_pose_calibrate_rows on rows [first, first + count): T <- exp((tau xi_j)^) (X T), one launch."""
+        import ctypes
+        from . import _lib
+        self._need_shared("PoseSet.calibrate_rows")
+        first, count = int(first), int(count)
+        if first < 0 or count < 0 or first + count > self.n_views:
+            raise IndexError(f"PoseSet.calibrate_rows: rows [{first}, {first + count}) are outside [0, {self.n_views})")
+        d = self._shared_descriptor(self._views[0:1])
+        _lib.check(_lib.lib().gslic_pose_calibrate_rows(ctypes.byref(d), first, count, _lib.current_stream_ptr()))
+
+    def extrinsic(self):
+        """The accumulated extrinsic correction as a host float64 4x4 [R_x | t_x; 0 0 0 1] (this call synchronises)."""
+        self._need_shared("PoseSet.extrinsic")
+        X = np.eye(4)
+        X[:3, :] = self.X.cpu().numpy().astype(np.float64).reshape(3, 4)
+        return X
+
+    def time_offset(self):
+        """The accumulated time offset in seconds (this call synchronises)."""
+        self._need_shared("PoseSet.time_offset")
+        return float(self.tau.cpu()[0])
 
     def pose(self, view):
         """(view [16], proj [16], campos [3]) of a row: device views into the set (no copy), usable as _RawRaster(..., pose=...)."""
@@ -1814,8 +1882,14 @@ class PoseSet:
         cam.camera_center = self.campos[i].cpu().numpy().copy()
         return cam.to_device(self.view.device)
 
-    def reset_moments(self, view=None):
-        """Zero moments and step count: one view, or all of them (then the last gradient too)."""
+    def reset_moments(self, view=None, shared=False):
+        """Zero moments and step count: one view, or all of them (then the last gradient too).  shared=True: the shared state's instead — sm, sv,
+        ssteps and shared_grad; X and tau, the calibration itself, stay."""
+        if shared:
+            self._need_shared("PoseSet.reset_moments")
+            for a in (self.sm, self.sv, self.ssteps, self.shared_grad):
+                a.zero_()
+            return
         rows = slice(None) if view is None else slice(self._index(view), self._index(view) + 1)
         self.m[rows] = 0
         self.v[rows] = 0
@@ -1824,23 +1898,33 @@ class PoseSet:
             self.grad.zero_()
 
     def state_dict(self):
-        return dict(view=self.view.clone(), proj=self.proj.clone(), campos=self.campos.clone(), projection=self.projection.clone(), m=self.m.clone(),
-                    v=self.v.clone(), steps=self.steps.clone(), lr_rot=self.lr_rot, lr_trans=self.lr_trans, betas=self.betas, eps=self.eps)
+        state = dict(view=self.view.clone(), proj=self.proj.clone(), campos=self.campos.clone(), projection=self.projection.clone(), m=self.m.clone(),
+                     v=self.v.clone(), steps=self.steps.clone(), lr_rot=self.lr_rot, lr_trans=self.lr_trans, betas=self.betas, eps=self.eps)
+        if self.shared:
+            state.update({k: getattr(self, k).clone() for k in self._SHARED}, lr_time=self.lr_time)
+        return state
 
     def load_state_dict(self, state):
         if tuple(state["view"].shape) != tuple(self.view.shape):
             raise ValueError(f"PoseSet: the state holds {tuple(state['view'].shape)}, this object {tuple(self.view.shape)}")
         if not torch.equal(state["projection"].to(self.device).view(torch.int32), self.projection.view(torch.int32)):
             raise ValueError("PoseSet: the state was saved under another projection_matrix")
-        for k in ("view", "proj", "campos", "m", "v", "steps"):
+        if self.shared != ("X" in state):
+            raise ValueError("PoseSet: the state was saved by a set " + ("without" if self.shared else "with") + " shared=True, this object was built "
+                             + ("with" if self.shared else "without") + " it")
+        for k in ("view", "proj", "campos", "m", "v", "steps") + (self._SHARED if self.shared else ()):
             getattr(self, k).copy_(state[k])
         self.lr_rot, self.lr_trans, self.eps = float(state["lr_rot"]), float(state["lr_trans"]), float(state["eps"])
         self.betas = (float(state["betas"][0]), float(state["betas"][1]))
+        if self.shared:
+            self.lr_time = float(state["lr_time"])
 
     def clone(self):
-        other = PoseSet(self.n_views, self._intrinsics, self.device, self.lr_rot, self.lr_trans, self.betas, self.eps)
+        other = PoseSet(self.n_views, self._intrinsics, self.device, self.lr_rot, self.lr_trans, self.betas, self.eps, self.shared, self.lr_time)
         other.load_state_dict(self.state_dict())
         other.grad.copy_(self.grad)
+        if self.shared:
+            other.shared_grad.copy_(self.shared_grad)
         return other
 
     def _descriptor(self, view_word, skip=None):
@@ -1867,6 +1951,37 @@ class PoseSet:
         _lib.check(_lib.lib().gslic_pose_step(ctypes.byref(d), _lib.ptr(gv), _lib.ptr(gp), _lib.ptr(gc), _lib.ptr(self.grad), _lib.current_stream_ptr()))
         return self.grad
 
+    def _shared_descriptor(self, view_word, skip=None):
+        """gslic_pose_shared on this object's arrays; view_word / skip as _descriptor's."""
+        from . import _lib
+        p = lambda t: t.data_ptr()
+        return _lib.PoseShared(p(self.view), p(self.proj), p(self.campos), p(self.projection), p(view_word), self.n_views, p(self.twist), p(self.sm),
+                               p(self.sv), p(self.ssteps), p(self.X), p(self.tau), self.lr_trans, self.lr_rot, self.lr_time, self.betas[0],
+                               self.betas[1], self.eps, None if skip is None else p(skip))
+
+    def _step_shared(self, view, cam_grads, do_step=True):
+        """gslic_pose_step_shared with row `view`'s gradient: shared_grad <- (g, xi . g); do_step: the seven coordinates step and every row moves."""
+        i = self._index(view)
+        return self._step_shared_word(self._views[i:i + 1], cam_grads, None if do_step else self._no_step)
+
+    def _step_shared_word(self, view_word, cam_grads, skip):
+        """gslic_pose_step_shared on the row a device int32 names, with an optional device skip word (GraphedStep: the forward's overflow word)."""
+        import ctypes
+        from . import _lib
+        self._need_shared("PoseSet")
+        gv, gp, gc = cam_grads
+        for t, n, name in ((gv, 16, "dL_dviewmatrix"), (gp, 16, "dL_dprojmatrix"), (gc, 3, "dL_dcampos")):
+            if t.numel() != n or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.view.device:
+                raise ValueError(f"PoseSet: {name} must be {n} contiguous float32 values on the set's device")
+        d = self._shared_descriptor(view_word, skip)
+        _lib.check(_lib.lib().gslic_pose_step_shared(ctypes.byref(d), _lib.ptr(gv), _lib.ptr(gp), _lib.ptr(gc), _lib.ptr(self.shared_grad),
+                                                     _lib.current_stream_ptr()))
+        return self.shared_grad
+
+    def shared_adam_step(self, view, cam_grads):
+        """The shared kernel on gradients the caller already holds (cam_grads as adam_step's), taken as row `view`'s.  Returns shared_grad."""
+        return self._step_shared(view, cam_grads, True)
+
     def adam_step(self, view, cam_grads):
         """The kernel on gradients the caller already holds: cam_grads = (dL_dviewmatrix [16], dL_dprojmatrix [16], dL_dcampos [3]) device tensors,
         as a backward with camera_grads=True returns them.  Returns grad."""
@@ -1880,9 +1995,12 @@ class PoseSet:
                                               p(campos_out), _lib.current_stream_ptr()))
 
 
-def _check_poses(who, poses, view, camera=None):
-    """The checks every step makes on its poses= argument (None passes): a PoseSet, one GPU, a view it has, a camera of the set's intrinsics."""
+def _check_poses(who, poses, view, camera=None, shared=False):
+    """The checks every step makes on its poses= argument (None passes): a PoseSet, one GPU, a view it has, a camera of the set's intrinsics; shared:
+    the step trains the shared calibration, which needs a set built with shared=True."""
     if poses is None:
+        if shared:
+            raise ValueError(f"{who}: shared=True needs poses= (a trainer.PoseSet built with shared=True holds the calibration)")
         return None
     if not isinstance(poses, PoseSet):
         raise ValueError(f"{who}: poses must be a trainer.PoseSet")
@@ -1892,6 +2010,8 @@ def _check_poses(who, poses, view, camera=None):
     poses._index(view)
     if camera is not None:
         poses._check_camera(who, camera)
+    if shared and not poses.shared:
+        raise ValueError(f"{who}: shared=True on a pose set built without shared=True")
     return poses
 
 
@@ -2105,7 +2225,7 @@ def training_step(model, camera, gt_image, bg, lambda_dssim=LAMBDA_DSSIM, do_ste
 
 
 def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None, depth_weight=None, depth_huber=0.0,
-                  exposure=None, view=0, poses=None, do_step=False):
+                  exposure=None, view=0, poses=None, do_step=False, shared=False):
     """dL/dxi of the training loss w.r.t. a left se(3) increment of the camera pose (Camera.pose_gradient) for the current map: forward -> loss
     kernels -> gslic_rasterize_backward_camera -> the chain.  The map is not touched.  Returns (float64 [6] = (d/drho, d/dphi), terms).
     One step of pose refinement is `camera.apply_pose_increment(-lr * g); camera.to_device(dev)`.
@@ -2118,11 +2238,14 @@ def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, l
     poses (a trainer.PoseSet) / view: the render is from row `view` of the set (`camera` supplies only the intrinsics and must match the set's) and
     the chain runs on the device (gslic_pose_step, one launch behind the backward): returns (poses.grad [6] float32 DEVICE tensor, terms) with no
     synchronisation and no host copy.  do_step=True also steps the row (Adam and the retraction, in the same launch); view names the exposure's
-    row as well when both are given."""
+    row as well when both are given.
+    shared=True (with poses=, a set built with shared=True): gslic_pose_step_shared runs in place of gslic_pose_step — the same chain on row `view`,
+    then g_tau = xi_view . g; do_step=True steps the shared extrinsic / time-offset coordinates and moves EVERY row.  Returns
+    (poses.shared_grad [7] float32 DEVICE tensor, terms).  Per-view and shared training in one step are not offered."""
     fl = fused_loss or _default_fused_loss()
     use_depth = _use_depth("pose_gradient", gt_depth, lambda_depth, depth_weight, depth_huber)
     exposure = _check_exposure("pose_gradient", exposure, view)
-    poses = _check_poses("pose_gradient", poses, view, camera)
+    poses = _check_poses("pose_gradient", poses, view, camera, shared)
     if poses is None and do_step:
         raise ValueError("pose_gradient: do_step=True needs poses= (a trainer.PoseSet holds the optimiser's state)")
     with torch.no_grad():
@@ -2132,12 +2255,12 @@ def pose_gradient(model, camera, gt_image, bg, fused_loss=None, gt_depth=None, l
                                                     exposure, view, False)
         out = rr.backward(dL_dimage, dL_ddepth, camera_grads=True)
         if poses is not None:
-            return poses._step(view, out[9:12], do_step), terms
+            return (poses._step_shared if shared else poses._step)(view, out[9:12], do_step), terms
     return camera.pose_gradient(out[9], out[10], out[11]), terms
 
 
 def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss=None, gt_depth=None, lambda_depth=0.0, weight=None, grad_stats=None,
-                            depth_weight=None, depth_huber=0.0, exposure=None, view=0, poses=None, adam_in_backward=False):
+                            depth_weight=None, depth_huber=0.0, exposure=None, view=0, poses=None, adam_in_backward=False, shared=False):
     """One joint map + pose iteration: forward -> loss kernels -> gslic_rasterize_backward_camera (parameter gradients AND the camera gradient in
     one pass) -> masked Adam on the map -> `camera` moved by -pose_lr * dL/dxi (left se(3) increment; 35 floats cross to the host, which is the
     step's only synchronisation).  Returns (terms, visible, dL/dxi).
@@ -2157,11 +2280,15 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
     camera gradient is that of the map before its update; parameters, moments, the mask and the pose step are bit-identical to the default's.
     `visible` is the mask the kernel wrote; the pose step follows unchanged, through poses= or pose_lr.  It combines with gt_depth, weight,
     depth_weight, depth_huber, exposure and grad_stats (the backward then writes dL_dmeans2D too, and the same small kernel adds it).  Single GPU
-    only (NotImplementedError under the N > 1 exchange).  False (the default) is the step as it was, launch for launch."""
+    only (NotImplementedError under the N > 1 exchange).  False (the default) is the step as it was, launch for launch.
+    shared=True (with poses=, a set built with shared=True): the pose launch is gslic_pose_step_shared — the view's gradient steps the shared
+    extrinsic / time-offset coordinates and EVERY row of the set moves; the per-view moments are not touched.  Returns (terms, visible,
+    poses.shared_grad [7]).  It combines with everything the per-view step combines with, adam_in_backward included; False is the step as it was."""
     fl = fused_loss or _default_fused_loss()
     use_depth = _use_depth("training_step_with_pose", gt_depth, lambda_depth, depth_weight, depth_huber)
     exposure = _check_exposure("training_step_with_pose", exposure, view)
-    poses = _check_poses("training_step_with_pose", poses, view, camera)
+    poses = _check_poses("training_step_with_pose", poses, view, camera, shared)
+    pose_step = None if poses is None else (poses._step_shared if shared else poses._step)
     if poses is not None and pose_lr:
         raise ValueError("training_step_with_pose: pose_lr != 0 given together with poses= (the pose set steps by its own lr_rot / lr_trans)")
     if adam_in_backward and _dist_on():
@@ -2184,7 +2311,7 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
             model.optimizer.count_step()
             visible = vis_u8.view(torch.bool)
             if poses is not None:
-                return terms, visible, poses._step(view, out)
+                return terms, visible, pose_step(view, out)
             g = cam.pose_gradient(*out)
             if pose_lr:
                 cam.apply_pose_increment(-float(pose_lr) * g).to_device(model.device)
@@ -2203,7 +2330,7 @@ def training_step_with_pose(model, camera, gt_image, bg, pose_lr=0.0, fused_loss
         model.optimizer.set_visibility_and_N(visible, model.P)
         model.optimizer.step(slab.grads(model))
         if poses is not None:
-            return terms, visible, poses._step(view, out[9:12])
+            return terms, visible, pose_step(view, out[9:12])
         g = cam.pose_gradient(out[9], out[10], out[11])
         if pose_lr:
             cam.apply_pose_increment(-float(pose_lr) * g).to_device(model.device)
@@ -2431,7 +2558,12 @@ class GraphedStep:
     step that did not fit moves neither map nor pose (its camera gradient is zeros) and check() repeats it with its view index.  The warm-up and
     capture passes run the step, so the set's state (view, proj, campos, m, v, steps, grad) is saved and restored around them like the map's.
     train_pose=True without poses raises ValueError; with grad_stats it raises NotImplementedError (the camera kernel accumulates no statistics,
-    and the small statistics kernel has no overflow word: a step that did not fit would add stale gradients).  train_pose=False: the step does
+    and the small statistics kernel has no overflow word: a step that did not fit would add stale gradients).  train_pose="shared" (a set built with
+    shared=True): the same launches with the last one replaced by gslic_pose_step_shared — training_step_with_pose(shared=True,
+    adam_in_backward=True) in capacity mode: the view's gradient steps the shared extrinsic / time-offset coordinates and every row moves.  Its skip
+    word is the forward's status word too, so a step that did not fit moves nothing and is repeated; the set's shared state (sm, sv, ssteps, X, tau,
+    shared_grad) is saved and restored around the warm-up and capture passes with the rest.  On a set without shared=True it raises ValueError, with
+    grad_stats NotImplementedError, as True does.  train_pose=False: the step does
     not train the pose — pose steps are then issued between graphed steps through pose_gradient(..., poses=, do_step=True) or
     training_step_with_pose(poses=) — and is the step as it was, launch for launch."""
 
@@ -2483,9 +2615,14 @@ class GraphedStep:
         self.campos = camera.d_camera_center.clone()
         self._pose_host = self._pose_of(camera)
         self.poses = _check_poses("GraphedStep", poses, view, camera)
+        if isinstance(train_pose, str) and train_pose != "shared":
+            raise ValueError(f"GraphedStep: train_pose = {train_pose!r} must be False, True or \"shared\"")
         self.train_pose = bool(train_pose)
+        self._pose_shared = train_pose == "shared"   # the pose launch is gslic_pose_step_shared: every row moves
         if self.train_pose and self.poses is None:
             raise ValueError("GraphedStep: train_pose=True needs poses= (a trainer.PoseSet holds the rows and the optimiser's state)")
+        if self._pose_shared and not self.poses.shared:
+            raise ValueError("GraphedStep: train_pose=\"shared\" on a pose set built without shared=True")
         if self.train_pose and self.grad_stats is not None:
             raise NotImplementedError("GraphedStep: train_pose=True together with grad_stats (the camera kernel accumulates no statistics, and the "
                                       "small statistics kernel has no overflow word: a step that did not fit would add stale gradients)")
@@ -2569,7 +2706,8 @@ class GraphedStep:
                                                          self.depth_huber, self.exposure, ex_view)
         if self.train_pose:
             cam = rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad, camera_grads=True, cam_out=self._cam_grads)
-            self.poses._step_word(self._pose_word, cam, self.bufs.status[2:3])   # (skip: the forward's overflow word, as the exposure's)
+            step_word = self.poses._step_shared_word if self._pose_shared else self.poses._step_word
+            step_word(self._pose_word, cam, self.bufs.status[2:3])   # (skip: the forward's overflow word, as the exposure's)
             return
         rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad, grad_stats=self._gstat)
 
@@ -2591,6 +2729,8 @@ class GraphedStep:
         saved_ex = None if ex is None else [(a, a.clone()) for a in (ex.params, ex.m, ex.v, ex.steps, ex.grad)]
         ps = self.poses if self.train_pose else None
         saved_ps = None if ps is None else [(a, a.clone()) for a in (ps.view, ps.proj, ps.campos, ps.m, ps.v, ps.steps, ps.grad)]
+        if self._pose_shared:
+            saved_ps += [(a, a.clone()) for a in (ps.sm, ps.sv, ps.ssteps, ps.X, ps.tau, ps.shared_grad)]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s), torch.no_grad():

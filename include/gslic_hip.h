@@ -886,6 +886,74 @@ int gslic_pose_load(
     const float* view_all, const float* proj_all, const float* campos_all, const int32_t* view_word /*[1] device*/, int32_t n_views,
     float* view_out /*[16]*/, float* proj_out /*[16]*/, float* campos_out /*[3]*/, void* stream);
 
+/* gslic_pose_step_shared / gslic_pose_calibrate_rows — the calibration the views of a pose set SHARE (additive, ABI 8): a correction of the
+ * camera-body extrinsic and of the camera clock offset.  A left increment T_cw <- exp(d^) T_cw acts in the camera frame, so the gradient g of
+ * gslic_pose_step for the rendered view is, unchanged, the gradient of an extrinsic correction every view takes; with the camera-frame twist
+ * xi_j = (v, w) of view j (m/s, rad/s; T_cw(t + dt) ~ exp((dt xi)^) T_cw(t)) the product xi_i . g is the gradient of a common time offset.  Per set,
+ * beside the three pose arrays and Pm of gslic_pose_step: twist[V,6], the Adam moments sm[7], sv[7] and the step count ssteps[1] of
+ * (rho_x, phi_x, tau), the accumulated extrinsic correction X[12] (ROWS of [R_x | t_x]: element (r, c) at [4 r + c]; the identity at the start) and
+ * the accumulated time offset tau[1] in seconds.  The per-view moments of gslic_pose_adam are neither read nor written.
+ * gslic_pose_step_shared is ONE launch of ONE workgroup.  Every product and sum below is ONE IEEE float32 operation rounded on its own, in the order
+ * the parentheses give, except where DOUBLE is named.  One thread runs CHAIN and ADAM; then each thread runs the whole MOVE of the rows it takes,
+ * alone: no sum depends on a reduction order, and no row's result depends on V.
+ *
+ * CHAIN: gslic_pose_step's CHAIN on row i = *view, term for term, gives g[0..5]; then with xi = twist[i]
+ *   g_tau = ((((g_0 xi_0 + g_1 xi_1) + g_2 xi_2) + g_3 xi_3) + g_4 xi_4) + g_5 xi_5
+ * (g, g_tau) is ALWAYS written to grad_out[7].
+ *
+ * ADAM: gslic_pose_step's ADAM on the seven coordinates k of (g, g_tau), on sm, sv, with lr_k = lr_trans (k < 3), lr_rot (3 <= k < 6), lr_time (k = 6):
+ *   n = ssteps[0] + 1, stored back;   b1 = 1 - beta1^n,  b2 = 1 - beta2^n               in DOUBLE from the integer n (beta as the float given)
+ *   s_k = (float)(lr_k / b1),  q = (float)sqrt(b2)                                        in double, each rounded to float once
+ *   m = beta1 sm_k + (1 - beta1) g_k,   v = beta2 sv_k + ((1 - beta2) g_k) g_k,   delta_k = -((s_k m) / (sqrtf(v) / q + eps))
+ * d_x = delta[0..5], d_tau = delta[6].
+ *
+ * MOVE, for EVERY row j in [0, V):   d_j[k] = d_x[k] + d_tau xi_j[k]   (k = 0..5; one product, one sum), then gslic_pose_step's RETRACTION with
+ * delta = d_j, RE-ORTHONORMALISATION and RECOMPOSITION on row j — the same formulas, constants and GSLIC_POSE_SERIES_THETA.
+ *   X   <- the same RETRACTION by d_x and RE-ORTHONORMALISATION on the 3x4 [R_x | t_x] alone (no recomposition)
+ *   tau <- tau + d_tau
+ *
+ * NO-OPS, row by row those of gslic_pose_step.  skip set (its bits 1 | 2 | 8 | 16): nothing but grad_out is written.  A coordinate of g or g_tau
+ * that is not finite: nothing but grad_out is written, ssteps is not advanced.  Otherwise sm, sv and ssteps are updated, and: a row whose d_j is zero
+ * in all six coordinates keeps its bits; a row whose d_j has a coordinate that is not finite keeps its bits; X keeps its bits when d_x is zero in
+ * all six coordinates or has a coordinate that is not finite; tau keeps its bits when d_tau is zero or not finite.  *view outside [0, n_views):
+ * nothing at all is written.
+ * No atomics, no allocation, no read-back: capturable in a graph.  All stores are vector stores.
+ * GSLIC_ERR_INVALID_ARG before any device work, naming the argument: a NULL descriptor, member (skip excepted), gradient or grad_out;
+ * n_views <= 0; a gradient array or grad_out that overlaps a state array, or grad_out one of the gradients; lr_trans, lr_rot, lr_time, beta1, beta2
+ * or eps NaN or negative; beta1 or beta2 >= 1.
+ *
+ * gslic_pose_calibrate_rows brings freshly loaded rows to the calibration the older rows were moved to.  This is a DEFINITION, first order in tau:
+ * for every row j in [first, first + count), one thread per row,
+ *   A_R(r,c) = (X(r,0) R(0,c) + X(r,1) R(1,c)) + X(r,2) R(2,c),   A_t_r = ((X(r,0) t_0 + X(r,1) t_1) + X(r,2) t_2) + X(r,3)          A = X T
+ *   d[k] = tau xi_j[k]                                                                                                              k = 0..5
+ *   T <- RETRACTION of [A_R | A_t] by d, RE-ORTHONORMALISATION, RECOMPOSITION (always run: d = 0 is the exact identity exp)
+ * A row whose d has a coordinate that is not finite keeps its bits; rows outside the range are not touched.  With lr_time = 0 the result is, up to
+ * rounding, the pose a row loaded from the same camera before the steps was moved to (X is the ordered product of their exp(d_x^)).  With
+ * lr_time != 0 it composes ONE exp(tau xi_j) where the older rows took a product of exp(d_x + d_tau xi_j): equal to first order in the increments.
+ * Reads view_all / proj_all / campos_all, projection, twist, X and tau of the descriptor (the other members may be NULL).
+ * GSLIC_ERR_INVALID_ARG: a NULL descriptor or one of those members; n_views <= 0; first or count negative, or first + count > n_views.  count = 0 is
+ * a no-op. */
+typedef struct gslic_pose_shared {
+    float* view_all;           /* [V,16] */
+    float* proj_all;           /* [V,16] */
+    float* campos_all;         /* [V,3]  */
+    const float* projection;   /* [16] Pm, shared by the views */
+    const int32_t* view;       /* [1] the row whose gradient this is */
+    int32_t n_views;           /* V */
+    const float* twist;        /* [V,6] camera-frame twist (v, w) of each view */
+    float* sm;                 /* [7] exp_avg of (rho_x, phi_x, tau) */
+    float* sv;                 /* [7] exp_avg_sq */
+    int32_t* ssteps;           /* [1] */
+    float* X;                  /* [12] rows of [R_x | t_x] */
+    float* tau;                /* [1] seconds */
+    float lr_trans, lr_rot, lr_time, beta1, beta2, eps;
+    const uint32_t* skip;      /* optional [1]: as gslic_pose_adam.skip */
+} gslic_pose_shared;
+int gslic_pose_step_shared(
+    const gslic_pose_shared* d, const float* dL_dviewmatrix /*[16]*/, const float* dL_dprojmatrix /*[16]*/, const float* dL_dcampos /*[3]*/,
+    float* grad_out /*[7]*/, void* stream);
+int gslic_pose_calibrate_rows(const gslic_pose_shared* d, int32_t first, int32_t count, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * gslic_knn_mean_dist2 — replaces SimpleKNN::knn (src/simple-knn/simple_knn.cu:185-221) behind distCUDA2
  * (src/simple-knn/spatial.cu:15-26): mean_dists[i] = mean of the 3 smallest squared distances from point i

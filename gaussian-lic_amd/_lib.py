@@ -94,6 +94,7 @@ EXPORTS = [
     "gslic_keyframe_decode", "gslic_keyframe_encode", "gslic_keyframe_decode_depth", "gslic_keyframe_encode_depth",
     "gslic_pose_step", "gslic_pose_load", "gslic_pose_step_shared", "gslic_pose_calibrate_rows",
     "gslic_rasterize_backward_camera_adam", "gslic_rasterize_backward_depth_camera_adam",
+    "gslic_covis_record", "gslic_covis_pair_counts", "gslic_covis_frame_counts", "gslic_covis_row_counts",
 ]
 
 _lib = None
@@ -145,6 +146,10 @@ def lib():
     L.gslic_pose_load.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp]            # view_all, proj_all, campos_all, view_word, n_views, 3 outputs, stream
     L.gslic_pose_step_shared.argtypes = [ctypes.POINTER(PoseShared), vp, vp, vp, vp, vp]   # descriptor, the three camera gradients, grad_out [7], stream
     L.gslic_pose_calibrate_rows.argtypes = [ctypes.POINTER(PoseShared), i32, i32, vp]      # descriptor, first, count, stream
+    L.gslic_covis_record.argtypes = [i32, i32, vp, vp, vp, vp, vp, i32, i32, vp]   # P, F, bits, radii, visible, frame_word, skip, row_begin, row_end, stream
+    L.gslic_covis_pair_counts.argtypes = [i32, i32, vp, vp, vp]                    # P, F, bits, pair, stream
+    L.gslic_covis_frame_counts.argtypes = [i32, i32, vp, vp, vp, vp]               # P, F, bits, frame_word, out, stream
+    L.gslic_covis_row_counts.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp]        # P, F, bits, frame_mask, n_seen, min_others, redundant, stream
     # the rasterize entry points, from the pieces their signatures share (include/gslic_hip.h)
     prm, counts, adam = ctypes.POINTER(RasterParams), [ctypes.POINTER(i32), ctypes.POINTER(i32)], ctypes.POINTER(AdamFused)
     inputs = [vp] * 12                                 # background ... cam_pos (the backward: radii in place of opacities)

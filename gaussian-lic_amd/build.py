@@ -37,6 +37,7 @@ SOURCES = {
     "keyframes_depth.hip": ["-ffp-contract=off"],  # the store's depth slabs, in a module of their own: an integer minimum and one exact multiply (decode), one exact product, an add and a floor (encode)
     "pose.hip": ["-ffp-contract=off"],       # the pose set's step: every float32 product and sum of the rule rounded on its own, in the header's order
     "pose_shared.hip": ["-ffp-contract=off"],   # the shared extrinsic / time-offset step and the row calibration: the same rule, rounded the same way
+    "covis.hip": [],         # covisibility bits: integer loads, stores, popcounts and atomic adds only: no arithmetic a flag could change
     "knn.hip": [],
     "extend.hip": ["-ffp-contract=off"],  # pixel assignment decides integers: canonical order like preprocess.hip
     "prune.hip": [],         # comparisons and copies only: no arithmetic a flag could change

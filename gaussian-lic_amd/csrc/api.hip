@@ -1655,6 +1655,84 @@ int gslic_pose_calibrate_rows(const gslic_pose_shared* d, int32_t first, int32_t
     return pose_calibrate_rows(d, first, count, (hipStream_t)stream);
 }
 
+// what the four gslic_covis_* calls check alike: P, F (at most max_F) and bits; *bits_range is the [P, Wd] rows
+static int covis_common(const char* fn, int32_t P, int32_t F, int32_t max_F, const void* bits, NamedRange* bits_range)
+{
+    if (P < 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: P = %d is negative", fn, P);
+    if (F < 1 || F > max_F) return set_error(GSLIC_ERR_INVALID_ARG, "%s: F = %d is outside 1 .. %d", fn, F, max_F);
+    if (!bits) return set_error(GSLIC_ERR_INVALID_ARG, "%s: bits is NULL", fn);
+    *bits_range = {bits, (size_t)P * (size_t)((F + 31) / 32) * sizeof(uint32_t), "bits"};
+    return GSLIC_OK;
+}
+
+// every given range of outs against every given range of ins and against the outs before it
+static int covis_overlaps(const char* fn, const NamedRange* outs, int n_outs, const NamedRange* ins, int n_ins)
+{
+    for (int i = 0; i < n_outs; i++) {
+        if (!outs[i].p) continue;
+        for (int j = 0; j < n_ins; j++)
+            if (ins[j].p && ranges_overlap(outs[i], ins[j])) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s overlaps %s", fn, outs[i].name, ins[j].name);
+        for (int j = 0; j < i; j++)
+            if (outs[j].p && ranges_overlap(outs[i], outs[j])) return set_error(GSLIC_ERR_INVALID_ARG, "%s: %s overlaps %s", fn, outs[i].name, outs[j].name);
+    }
+    return GSLIC_OK;
+}
+
+int gslic_covis_record(int32_t P, int32_t F, uint32_t* bits, const int32_t* radii, const uint8_t* visible, const int32_t* frame_word, const int32_t* skip,
+                       int32_t row_begin, int32_t row_end, void* stream)
+{
+    const char* fn = "covis record";
+    NamedRange b;
+    GS_TRY(covis_common(fn, P, F, GSLIC_COVIS_MAX_FRAMES, bits, &b));
+    if (!frame_word) return set_error(GSLIC_ERR_INVALID_ARG, "%s: frame_word is NULL", fn);
+    if (radii && visible) return set_error(GSLIC_ERR_INVALID_ARG, "%s: radii and visible are both given (at most one; neither clears the column)", fn);
+    const int32_t re = row_end < 0 ? P : row_end;
+    if (row_begin < 0 || row_begin > re || re > P)
+        return set_error(GSLIC_ERR_INVALID_ARG, "%s: row range [%d, %d) of %d rows", fn, row_begin, re, P);
+    const NamedRange ins[4] = {{radii, (size_t)P * sizeof(int32_t), "radii"}, {visible, (size_t)P, "visible"},
+                               {frame_word, sizeof(int32_t), "frame_word"}, {skip, sizeof(int32_t), "skip"}};
+    GS_TRY(covis_overlaps(fn, &b, 1, ins, 4));
+    return covis_record(F, bits, radii, visible, frame_word, skip, row_begin, re, (hipStream_t)stream);
+}
+
+int gslic_covis_pair_counts(int32_t P, int32_t F, const uint32_t* bits, uint32_t* pair, void* stream)
+{
+    const char* fn = "covis pair counts";
+    NamedRange b;
+    GS_TRY(covis_common(fn, P, F, GSLIC_COVIS_MAX_PAIR_FRAMES, bits, &b));
+    if (!pair) return set_error(GSLIC_ERR_INVALID_ARG, "%s: pair is NULL", fn);
+    const NamedRange out = {pair, (size_t)F * (size_t)F * sizeof(uint32_t), "pair"};
+    GS_TRY(covis_overlaps(fn, &out, 1, &b, 1));
+    return covis_pair_counts(P, F, bits, pair, (hipStream_t)stream);
+}
+
+int gslic_covis_frame_counts(int32_t P, int32_t F, const uint32_t* bits, const int32_t* frame_word, uint32_t* out, void* stream)
+{
+    const char* fn = "covis frame counts";
+    NamedRange b;
+    GS_TRY(covis_common(fn, P, F, GSLIC_COVIS_MAX_FRAMES, bits, &b));
+    if (!frame_word) return set_error(GSLIC_ERR_INVALID_ARG, "%s: frame_word is NULL", fn);
+    if (!out) return set_error(GSLIC_ERR_INVALID_ARG, "%s: out is NULL", fn);
+    const NamedRange o = {out, (size_t)F * sizeof(uint32_t), "out"}, ins[2] = {b, {frame_word, sizeof(int32_t), "frame_word"}};
+    GS_TRY(covis_overlaps(fn, &o, 1, ins, 2));
+    return covis_frame_counts(P, F, bits, frame_word, out, (hipStream_t)stream);
+}
+
+int gslic_covis_row_counts(int32_t P, int32_t F, const uint32_t* bits, const uint32_t* frame_mask, int32_t* n_seen, int32_t min_others,
+                           uint32_t* redundant, void* stream)
+{
+    const char* fn = "covis row counts";
+    NamedRange b;
+    GS_TRY(covis_common(fn, P, F, GSLIC_COVIS_MAX_FRAMES, bits, &b));
+    if (!n_seen) return set_error(GSLIC_ERR_INVALID_ARG, "%s: n_seen is NULL", fn);
+    if (min_others < 0) return set_error(GSLIC_ERR_INVALID_ARG, "%s: min_others = %d is negative", fn, min_others);
+    const size_t wd = (size_t)((F + 31) / 32);
+    const NamedRange outs[2] = {{n_seen, (size_t)P * sizeof(int32_t), "n_seen"}, {redundant, (size_t)F * sizeof(uint32_t), "redundant"}};
+    const NamedRange ins[2] = {b, {frame_mask, wd * sizeof(uint32_t), "frame_mask"}};
+    GS_TRY(covis_overlaps(fn, outs, 2, ins, 2));
+    return covis_row_counts(P, F, bits, frame_mask, n_seen, min_others, redundant, (hipStream_t)stream);
+}
+
 int gslic_knn_mean_dist2(int32_t P, const float* points, float* mean_dists, gslic_alloc_fn scratch_alloc, void* scratch_ctx,
                          void* stream)
 {

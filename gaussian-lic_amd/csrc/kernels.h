@@ -283,4 +283,12 @@ int pose_step_shared(const gslic_pose_shared* d, const float* dL_dviewmatrix, co
                      hipStream_t s);
 int pose_calibrate_rows(const gslic_pose_shared* d, int first, int count, hipStream_t s);
 
+// covis.hip: covisibility bits uint32 [P, ceil(F / 32)] (arguments validated by the caller).  record: one thread per row of the range, one word
+// loaded and stored; the three queries zero their outputs on the stream, then one launch each (LDS counters, integer atomics per workgroup)
+int covis_record(int F, uint32_t* bits, const int32_t* radii, const uint8_t* visible, const int32_t* frame_word, const int32_t* skip, int row_begin,
+                 int row_end, hipStream_t s);
+int covis_pair_counts(int P, int F, const uint32_t* bits, uint32_t* pair, hipStream_t s);
+int covis_frame_counts(int P, int F, const uint32_t* bits, const int32_t* frame_word, uint32_t* out, hipStream_t s);
+int covis_row_counts(int P, int F, const uint32_t* bits, const uint32_t* frame_mask, int32_t* n_seen, int min_others, uint32_t* redundant, hipStream_t s);
+
 }  // namespace gslic

@@ -123,6 +123,7 @@ FUSED_CHECKS = {name: (os.path.join(HERE, name + "_check.cpp"), os.path.join(PKG
     "fused_pose",             # trainable keyframe poses (gslic::PoseSet): pose steps on two rows through FusedStep::pose_gradient
     "fused_pose_adam",        # the joint map + pose step with the Adam inside the camera backward (FusedStep::step_with_pose)
     "fused_pose_shared",      # the shared extrinsic / time-offset calibration (gslic::PoseSet with shared): joint steps, a pose step, a calibrated load
+    "fused_covis",            # covisibility sets (gslic::Covisibility): records behind steps, carried through densify, prune and resort, the queries
 )}
 
 

@@ -23,9 +23,10 @@
 // With a depth weight image [H,W] and / or a Huber threshold (fs.step(cam, gt, gt_depth, lambda_depth, weight, depth_weight, depth_huber)) the depth
 // loss call is gslic_depth_loss_weighted_forward_backward, as training_step_fused(depth_weight=, depth_huber=)'s (tests/test_depth_weighted_gpu.py).
 //
-// Per-row statistics (ContributionStats, GradientStats) follow the map's rows the way the Python host's _RowStatistics do: each object lists its
+// Per-row statistics (ContributionStats, GradientStats, Covisibility) follow the map's rows the way the Python host's _RowStatistics do: each object lists its
 // arrays ONCE (rows(): tensor, scalar type, row width in dwords, created only when asked for), and the four row changes — prune, extend, densify,
-// resort — walk the lists of the objects they carry (the ContributionStats* argument when it holds anything, the attached GradientStats) with four
+// resort — walk the lists of the objects they carry (the ContributionStats* argument when it holds anything, the attached GradientStats and
+// Covisibility) with four
 // operations: fit to capacity, gather, zero rows, append to the permute list.  A new array is a field, an entry in its list and its accumulate call.
 #pragma once
 #include <torch/torch.h>
@@ -51,10 +52,11 @@ struct FusedCamera {
 
 // One per-row array of a statistics object, as the row changes of FusedStep see it
 struct StatRow {
-    torch::Tensor* array;     // [capacity] on the map's device, indexed by storage row
+    torch::Tensor* array;     // [capacity] (cols == 0) or [capacity, cols] on the map's device, indexed by storage row
     torch::ScalarType type;
-    uint32_t width;           // row width in dwords: 1 or 2
+    uint32_t width;           // row width in dwords: 1 or 2 for a 1-D array, cols of an int32 [capacity, cols] array
     bool lazy;                // exists only once an accumulate call asked for it; until then the row changes pass over it
+    int64_t cols = 0;         // the trailing dimension of a 2-D array (0: the array is 1-D)
 };
 
 // Per-Gaussian contribution statistics accumulated over views (gslic_contribution_accumulate, include/gslic_hip.h) — the Python host's
@@ -100,6 +102,98 @@ struct GradientStats {
     }
     // bool [P] for FusedStep::prune(drop): max_radius > max_screen_radius (3DGS's screen-size prune)
     torch::Tensor big_mask(int64_t P, int32_t max_screen_radius) const { return max_radius.narrow(0, 0, P).gt(max_screen_radius); }
+};
+
+// Covisibility sets (gslic_covis_*, include/gslic_hip.h) — the Python host's trainer.Covisibility as plain data: one bit per (row, frame) in
+// int32 [capacity, Wd] rows, Wd = ceil(n_frames / 32); bit f of a row says "frame f, when last recorded, had radii > 0 on this row".  Handed to
+// FusedStep::set_covisibility, FusedStep::record_covisibility(frame) replaces the frame's column by the last step's radii > 0, and prune / extend /
+// densify / resort carry the rows (gathered, zero for new rows and split parents, permuted: one more row array of run-time width).  The queries
+// take the map's row count P (FusedStep::size()) and read nothing back; which keyframe to give up and which rows to protect is the host's policy.
+struct Covisibility {
+    int32_t n_frames;
+    torch::Tensor bits;    // int32 [capacity, Wd]
+    torch::Tensor word;    // int32 [1]: the frame word of the calls that name their frame by a host int
+    explicit Covisibility(int32_t frames) : n_frames(frames)
+    {
+        TORCH_CHECK(frames >= 1 && frames <= GSLIC_COVIS_MAX_FRAMES, "Covisibility: n_frames = ", frames, " is outside 1 .. ", GSLIC_COVIS_MAX_FRAMES);
+    }
+    int64_t words() const { return (n_frames + 31) / 32; }
+    bool defined() const { return bits.defined(); }
+    std::vector<StatRow> rows() { return {{&bits, torch::kInt32, (uint32_t)words(), false, words()}}; }
+    void reset() { if (defined()) bits.zero_(); }
+    // column `frame` <- seen: radii (int32 [P]: seen where > 0) or a visibility mask (bool / uint8 [P]); an undefined tensor clears the column
+    void record(int64_t P, int frame, const torch::Tensor& seen = torch::Tensor())
+    {
+        ready(P);
+        const bool radii = seen.defined() && seen.scalar_type() == torch::kInt32;
+        TORCH_CHECK(!seen.defined() || (seen.dim() == 1 && seen.size(0) == P && (radii || seen.scalar_type() == torch::kBool || seen.scalar_type() == torch::kByte)),
+                    "Covisibility::record: seen must be radii (int32) or a visibility mask (bool / uint8) of ", P, " rows");
+        if (P == 0) return;
+        const torch::Tensor s = seen.defined() ? seen.contiguous() : seen;
+        check(gslic_covis_record((int32_t)P, n_frames, u32(bits), radii ? s.data_ptr<int32_t>() : nullptr,
+                                 s.defined() && !radii ? static_cast<const uint8_t*>(s.data_ptr()) : nullptr, frame_word(frame), nullptr, 0, -1,
+                                 current_stream()), "gslic_covis_record");
+    }
+    void clear(int64_t P, int frame) { record(P, frame); }
+    torch::Tensor pair_counts(int64_t P)   // int64 [F, F]
+    {
+        ready(P);
+        torch::Tensor out = torch::zeros({n_frames, n_frames}, bits.options());
+        if (P) check(gslic_covis_pair_counts((int32_t)P, n_frames, u32(bits), u32(out), current_stream()), "gslic_covis_pair_counts");
+        return out.to(torch::kInt64);
+    }
+    torch::Tensor frame_counts(int64_t P, int frame)   // int64 [F]
+    {
+        ready(P);
+        torch::Tensor out = torch::zeros({n_frames}, bits.options());
+        if (P) check(gslic_covis_frame_counts((int32_t)P, n_frames, u32(bits), frame_word(frame), u32(out), current_stream()), "gslic_covis_frame_counts");
+        return out.to(torch::kInt64);
+    }
+    // int32 [P]: how many of the frames of frame_mask (int32 [Wd] device words; undefined: every frame) see each row
+    torch::Tensor seen_count(int64_t P, const torch::Tensor& frame_mask = torch::Tensor()) { return row_counts(P, frame_mask, 0, nullptr); }
+    // int64 [F]: [f] = the rows f sees that at least 1 + min_others frames (of frame_mask) see
+    torch::Tensor redundant(int64_t P, int min_others, const torch::Tensor& frame_mask = torch::Tensor())
+    {
+        torch::Tensor red;
+        row_counts(P, frame_mask, min_others, &red);
+        return red.to(torch::kInt64);
+    }
+    torch::Tensor rows_of(int64_t P, int frame)   // bool [P]
+    {
+        ready(P);
+        TORCH_CHECK(frame >= 0 && frame < n_frames, "Covisibility: frame ", frame, " is outside [0, ", n_frames, ")");
+        return bits.narrow(0, 0, P).select(1, frame >> 5).bitwise_right_shift(frame & 31).bitwise_and(1).to(torch::kBool);
+    }
+    torch::Tensor seen_by_fewer_than(int64_t P, int n, const torch::Tensor& frame_mask = torch::Tensor()) { return seen_count(P, frame_mask).lt(n); }   // bool [P]
+    torch::Tensor overlap(int64_t P, int frame)   // float32 [F]: frame_counts / the frame's own count, 0 where it sees nothing
+    {
+        const torch::Tensor fc = frame_counts(P, frame).to(torch::kFloat32), own = fc[frame];
+        return torch::where(own.gt(0), fc / own.clamp_min(1.0f), torch::zeros_like(fc));
+    }
+
+private:
+    static void check(int rc, const char* what) { TORCH_CHECK(rc == GSLIC_OK, what, " failed (", rc, "): ", gslic_last_error()); }
+    static uint32_t* u32(torch::Tensor& t) { return reinterpret_cast<uint32_t*>(t.data_ptr<int32_t>()); }
+    void ready(int64_t P) const { TORCH_CHECK(defined() && bits.size(0) >= P, "Covisibility: not attached to a map of ", P, " rows (FusedStep::set_covisibility)"); }
+    const int32_t* frame_word(int frame)
+    {
+        TORCH_CHECK(frame >= 0 && frame < n_frames, "Covisibility: frame ", frame, " is outside [0, ", n_frames, ")");
+        if (!word.defined()) word = torch::zeros({1}, bits.options());
+        word.fill_(frame);
+        return word.data_ptr<int32_t>();
+    }
+    torch::Tensor row_counts(int64_t P, const torch::Tensor& frame_mask, int min_others, torch::Tensor* red)
+    {
+        ready(P);
+        TORCH_CHECK(!frame_mask.defined() || (frame_mask.scalar_type() == torch::kInt32 && frame_mask.numel() == words() && frame_mask.is_contiguous()),
+                    "Covisibility: frame_mask must be ", words(), " contiguous int32 words");
+        torch::Tensor n_seen = torch::zeros({P}, bits.options());
+        if (red) *red = torch::zeros({n_frames}, bits.options());
+        if (P)
+            check(gslic_covis_row_counts((int32_t)P, n_frames, u32(bits), frame_mask.defined() ? reinterpret_cast<const uint32_t*>(frame_mask.data_ptr<int32_t>()) : nullptr,
+                                         n_seen.data_ptr<int32_t>(), min_others, red ? u32(*red) : nullptr, current_stream()), "gslic_covis_row_counts");
+        return n_seen;
+    }
 };
 
 // The per-pixel LiDAR range image of one camera, built by the library (gslic_lidar_zbuffer_add / _resolve, include/gslic_hip.h) — the Python host's
@@ -681,6 +775,21 @@ public:
     {
         gstats_ = stats;
         if (gstats_) fit_rows(gstats_->rows());
+    }
+    // From here on prune() / extend() / densify() / resort() carry *cv's rows with the map's (created zero-filled, grown to the map's capacity), and
+    // record_covisibility(frame) replaces column `frame` by radii > 0 of the last step()'s forward — trainer.Covisibility.record(frame, radii).  The
+    // object must outlive the step or be taken off with nullptr.
+    void set_covisibility(Covisibility* cv)
+    {
+        covis_ = cv;
+        if (covis_) fit_rows(covis_->rows());
+    }
+    void record_covisibility(int frame)
+    {
+        TORCH_CHECK(covis_, "record_covisibility: no Covisibility is attached (set_covisibility)");
+        TORCH_CHECK(radii_.defined() && radii_.size(0) == size(), "record_covisibility: no step has run on the rows as they are");
+        fit_rows(covis_->rows());
+        covis_->record(size(), frame, radii_);
     }
     // From here on step() and pose_gradient() take the loss of the exposure-compensated image: E = exposure->matrix(view) applied into a scratch
     // image (gslic_exposure_apply), the loss calls unchanged on that image, then gslic_exposure_backward, which hands the rasteriser's backward
@@ -1450,6 +1559,7 @@ private:
         std::vector<std::vector<StatRow>> lists;
         if (stats && stats->defined()) lists.push_back(stats->rows());
         if (gstats_) lists.push_back(gstats_->rows());
+        if (covis_) lists.push_back(covis_->rows());
         return lists;
     }
     // fit to capacity: every array created zero-filled, or zero-extended, to capacity() rows; a lazy array that does not exist only when it is `wanted`
@@ -1459,7 +1569,7 @@ private:
         for (const StatRow& r : rows) {
             torch::Tensor& t = *r.array;
             if (t.defined() ? t.size(0) >= cap : (r.lazy && std::find(wanted.begin(), wanted.end(), r.array) == wanted.end())) continue;
-            torch::Tensor n = torch::zeros({cap}, prm_[0].options().requires_grad(false).dtype(r.type));
+            torch::Tensor n = torch::zeros(r.cols ? std::vector<int64_t>{cap, r.cols} : std::vector<int64_t>{cap}, prm_[0].options().requires_grad(false).dtype(r.type));
             if (t.defined()) n.narrow(0, 0, t.size(0)).copy_(t);
             t = n;
         }
@@ -1473,7 +1583,9 @@ private:
         for (const StatRow& r : rows) {
             if (!r.array->defined()) continue;
             old.push_back(*r.array);   // (alive until the launch is issued)
-            *r.array = torch::zeros({capacity()}, old.back().options());
+            std::vector<int64_t> shape = old.back().sizes().vec();
+            shape[0] = capacity();
+            *r.array = torch::zeros(shape, old.back().options());
             list.push_back({old.back().data_ptr(), r.array->data_ptr(), r.width});
         }
         if (count > 0 && !list.empty())
@@ -1566,6 +1678,7 @@ private:
     int64_t sorted_P_ = 0, n_resorts_ = 0;                          // rows [0, sorted_P_) are in Morton order; resort() calls so far
     torch::Tensor last_perm_;                                       // the last resort()'s permutation
     GradientStats* gstats_ = nullptr;                               // set_gradient_stats: accumulated by step(), carried by the row changes
+    Covisibility* covis_ = nullptr;                                 // set_covisibility: recorded by record_covisibility(), carried by the row changes
     Exposure* exposure_ = nullptr;                                  // set_exposure: applied and updated by step(), applied by pose_gradient()
     int exposure_view_ = 0;
     torch::Tensor ex_image_, ex_dL_, ex_partials_;                  // exposure: the compensated image, the loss's gradient w.r.t. it, the partial sums

@@ -1131,6 +1131,208 @@ def _grad_stats_for_step(grad_stats, model):
     return grad_stats
 
 
+COVIS_MAX_FRAMES = 1024        # GSLIC_COVIS_MAX_FRAMES
+COVIS_MAX_PAIR_FRAMES = 128    # GSLIC_COVIS_MAX_PAIR_FRAMES
+
+
+class Covisibility(_RowStatistics):
+    """Covisibility sets: which keyframes see which Gaussians, on the device (the rule: include/gslic_hip.h, gslic_covis_*).  One bit per (row,
+    frame) in int32 [capacity, Wd] rows, Wd = ceil(n_frames / 32): bit f of a row says "frame f, when it was last recorded, had radii > 0 on this
+    row".  record() REPLACES a frame's column, so the state is a function of each frame's last record.  GraphedStep(keyframes=, covis=) records
+    the trained slot's column behind its backward; a host without a store calls record(frame, gs.visible) or record(frame, radii).
+
+    Signals only: which keyframe to give up (redundant), which window to train (frame_counts / overlap) and which rows to protect
+    (seen_by_fewer_than) stay the host's policy.
+
+    Like the other statistics the object owns its device array (sized to the model's capacity, zero-filled) and ATTACHES itself to the model:
+    prune() gathers it, extend() / densify() give new rows and split parents zeros, resort() permutes it — the bits are one more row array of
+    run-time width, carried by the same row kernels; detach() ends that and a detached object raises once the rows have changed.  Single GPU."""
+
+    def __init__(self, model, n_frames):
+        if _dist_on():
+            raise NotImplementedError("Covisibility is single-GPU only: the records of the ranks' views are not merged across ranks")
+        F = int(n_frames)
+        if not 1 <= F <= COVIS_MAX_FRAMES:
+            raise ValueError(f"Covisibility: n_frames = {n_frames} is outside 1 .. {COVIS_MAX_FRAMES}")
+        self.n_frames, self.words = F, (F + 31) // 32
+        self._word = torch.zeros(1, dtype=torch.int32, device=model.device)   # the frame word of the calls that name their frame by a host int
+        super().__init__(model)
+
+    def _alloc(self, cap):
+        self._bits = torch.zeros(cap, self.words, dtype=torch.int32, device=self.model.device)   # uint32 [cap, Wd]
+
+    def _arrays(self):
+        return [(self._bits, self.words)]
+
+    def _index(self, frame):
+        f = int(frame)
+        if not 0 <= f < self.n_frames:
+            raise IndexError(f"Covisibility: frame {frame} is outside [0, {self.n_frames})")
+        return f
+
+    def _frame_word(self, frame):
+        """The device int32 [1] a call reads its frame from: a device word as it is (a value outside [0, n_frames) makes record() a no-op and the
+        queries return zeros), a host int validated and written into the object's own word (stream-ordered in front of the launch)."""
+        if torch.is_tensor(frame):
+            if frame.dtype != torch.int32 or frame.numel() != 1 or frame.device != self._bits.device:
+                raise ValueError(f"Covisibility: a frame word must be one int32 on {self._bits.device}, got {frame.dtype} {tuple(frame.shape)} on {frame.device}")
+            return frame
+        self._word.fill_(self._index(frame))
+        return self._word
+
+    def _record(self, word, radii=None, visible=None, skip=None, rows=None):
+        """One gslic_covis_record on the rows as they are (no checks of the tensors: record() and GraphedStep make them)."""
+        from . import _lib
+        P = self.model.P
+        if P == 0:
+            return
+        b, e = (0, -1) if rows is None else (int(rows[0]), int(rows[1]))
+        _lib.check(_lib.lib().gslic_covis_record(P, self.n_frames, self._bits.data_ptr(), _lib.ptr(radii), _lib.ptr(visible), _lib.ptr(word), _lib.ptr(skip),
+                                                 b, e, _lib.current_stream_ptr()))
+
+    @torch.no_grad()
+    def record(self, frame, seen, rows=None):
+        """Replaces column `frame` (an int, or a device int32 word) by `seen`: radii (int32 [P]: seen where > 0) or a visibility mask (bool / uint8
+        [P]), of THIS model's rows; None clears the column.  rows = (begin, end): only those rows.  One launch, no read-back."""
+        self._check()
+        word = self._frame_word(frame)
+        if seen is None:
+            return self._record(word, rows=rows)
+        P = self.model.P
+        if not torch.is_tensor(seen) or tuple(seen.shape) != (P,) or seen.dtype not in (torch.int32, torch.bool, torch.uint8) or seen.device != self._bits.device:
+            raise ValueError(f"Covisibility.record: seen must be radii (int32) or a visibility mask (bool / uint8) of {P} rows on {self._bits.device}, got "
+                             f"{getattr(seen, 'dtype', type(seen))} {tuple(getattr(seen, 'shape', ()))}")
+        seen = seen.contiguous()
+        if seen.dtype == torch.int32:
+            return self._record(word, radii=seen, rows=rows)
+        self._record(word, visible=seen.view(torch.uint8) if seen.dtype == torch.bool else seen, rows=rows)
+
+    def clear(self, frame):
+        """Clears column `frame` (what a replaced keyframe slot needs before its first record)."""
+        self.record(frame, None)
+
+    def reset(self):
+        self._check()
+        self._bits.zero_()
+
+    # --- queries
+    def bits(self):
+        """int32 [P, Wd]: the rows' words as stored (bit f of a row: bit f & 31 of word f >> 5)."""
+        self._check()
+        return self._bits[:self.model.P]
+
+    @torch.no_grad()
+    def pair_counts(self):
+        """int64 [F, F]: [f, g] = the number of rows both f and g see (symmetric; the diagonal is each frame's visible count).  n_frames <= 128."""
+        from . import _lib
+        self._check()
+        F = self.n_frames
+        if F > COVIS_MAX_PAIR_FRAMES:
+            raise ValueError(f"Covisibility.pair_counts: n_frames = {F} is above {COVIS_MAX_PAIR_FRAMES} (use frame_counts per frame)")
+        out = torch.zeros(F, F, dtype=torch.int32, device=self._bits.device)
+        if self.model.P:
+            _lib.check(_lib.lib().gslic_covis_pair_counts(self.model.P, F, self._bits.data_ptr(), _lib.ptr(out), _lib.current_stream_ptr()))
+        return out.long()
+
+    @torch.no_grad()
+    def frame_counts(self, frame):
+        """int64 [F]: [g] = the number of rows that `frame` (an int or a device word) and g both see: the window query around one keyframe."""
+        from . import _lib
+        self._check()
+        word = self._frame_word(frame)
+        out = torch.zeros(self.n_frames, dtype=torch.int32, device=self._bits.device)
+        if self.model.P:
+            _lib.check(_lib.lib().gslic_covis_frame_counts(self.model.P, self.n_frames, self._bits.data_ptr(), _lib.ptr(word), _lib.ptr(out),
+                                                           _lib.current_stream_ptr()))
+        return out.long()
+
+    def _mask_words(self, frames):
+        """frames: None (every frame), a bool [F] tensor / array, or frame indices -> the int32 [Wd] device mask (or None)."""
+        if frames is None:
+            return None
+        import numpy as np
+        f = frames.detach().cpu().numpy() if torch.is_tensor(frames) else np.asarray(list(frames) if not isinstance(frames, np.ndarray) else frames)
+        if f.dtype == np.bool_:
+            if f.shape != (self.n_frames,):
+                raise ValueError(f"Covisibility: a frame mask must have {self.n_frames} entries, got {f.shape}")
+            idx = np.flatnonzero(f)
+        else:
+            idx = np.asarray([self._index(i) for i in f.reshape(-1)], dtype=np.int64)
+        words = np.zeros(self.words, dtype=np.uint32)
+        np.bitwise_or.at(words, idx >> 5, np.uint32(1) << (idx & 31).astype(np.uint32))
+        return torch.from_numpy(words.view(np.int32)).to(self._bits.device)
+
+    def _row_counts(self, frames, min_others, with_redundant):
+        from . import _lib
+        self._check()
+        P, dev = self.model.P, self._bits.device
+        n_seen = torch.zeros(P, dtype=torch.int32, device=dev)
+        red = torch.zeros(self.n_frames, dtype=torch.int32, device=dev) if with_redundant else None
+        if int(min_others) < 0:
+            raise ValueError(f"Covisibility: min_others = {min_others} is negative")
+        if P:
+            mask = self._mask_words(frames)
+            _lib.check(_lib.lib().gslic_covis_row_counts(P, self.n_frames, self._bits.data_ptr(), _lib.ptr(mask), _lib.ptr(n_seen), int(min_others),
+                                                         _lib.ptr(red), _lib.current_stream_ptr()))
+        return n_seen, red
+
+    @torch.no_grad()
+    def seen_count(self, frames=None):
+        """int32 [P]: how many of `frames` (None: all; a bool [F] mask or frame indices) see each row."""
+        return self._row_counts(frames, 0, False)[0]
+
+    @torch.no_grad()
+    def redundant(self, min_others, frames=None):
+        """int64 [F]: [f] = the number of rows f sees that at least 1 + min_others of `frames` (None: all) see — with f among them, "f and at least
+        min_others others".  redundant(n) / pair_counts()[f, f] near 1 is the usual criterion for giving keyframe f up."""
+        return self._row_counts(frames, min_others, True)[1].long()
+
+    def rows_of(self, frame):
+        """bool [P]: the rows frame `frame` (a host int) saw when it was last recorded."""
+        self._check()
+        f = self._index(frame)
+        return ((self._bits[:self.model.P, f >> 5] >> (f & 31)) & 1).bool()
+
+    def seen_by_fewer_than(self, n, frames=None):
+        """bool [P]: rows fewer than n of `frames` see — a mask for prune(protect= / drop=) (n = 2: rows only one keyframe ever saw, or none)."""
+        return self.seen_count(frames) < int(n)
+
+    def overlap(self, frame):
+        """float32 [F]: frame_counts(frame) / the frame's own visible count — the share of what `frame` sees that g sees too; 0 where it sees nothing."""
+        fc = self.frame_counts(frame).to(torch.float32)
+        own = fc[self._index(frame)] if not torch.is_tensor(frame) else fc.gather(0, frame.long().clamp(0, self.n_frames - 1))
+        return torch.where(own > 0, fc / own.clamp_min(1.0), torch.zeros_like(fc))
+
+    def state_dict(self):
+        self._check()
+        return dict(n_frames=self.n_frames, bits=self._bits[:self.model.P].clone())
+
+    def load_state_dict(self, state):
+        self._check()
+        P = self.model.P
+        bits = torch.as_tensor(state["bits"])
+        if int(state["n_frames"]) != self.n_frames or tuple(bits.shape) != (P, self.words) or bits.dtype != torch.int32:
+            raise ValueError(f"Covisibility.load_state_dict: expected n_frames = {self.n_frames} and int32 bits [{P}, {self.words}], got "
+                             f"n_frames = {state['n_frames']} and {bits.dtype} {tuple(bits.shape)}")
+        self._bits[:P].copy_(bits)
+        self._bits[P:].zero_()
+
+
+def _covis_for_step(covis, model, keyframes):
+    """The checks GraphedStep makes on its covis= argument (None passes): this model's object, its rows current, a store whose slots fit its columns."""
+    if covis is None:
+        return None
+    if not isinstance(covis, Covisibility) or covis.model is not model:
+        raise ValueError("covis must be a Covisibility of the model that is trained")
+    if keyframes is None:
+        raise ValueError("GraphedStep: covis given without keyframes (the recorded column is the store's slot; a host without a store calls "
+                         "covis.record(frame, step.visible) itself)")
+    if covis.n_frames < keyframes.capacity:
+        raise ValueError(f"GraphedStep: covis has {covis.n_frames} frames, the keyframe store {keyframes.capacity} slots (column = slot)")
+    covis._check()
+    return covis
+
+
 def exchange_mode():
     """How the N > 1 step exchanges gradients: "rank1" (default: 11 floats all-reduced + the 3-float colour gradient all-gathered,
     exchange_rank1), "dense" (the whole [P x 59] slab all-reduced in three pipelined segments), "sparse" (only the rows some view sees).
@@ -2565,11 +2767,20 @@ class GraphedStep:
     shared_grad) is saved and restored around the warm-up and capture passes with the rest.  On a set without shared=True it raises ValueError, with
     grad_stats NotImplementedError, as True does.  train_pose=False: the step does
     not train the pose — pose steps are then issued between graphed steps through pose_gradient(..., poses=, do_step=True) or
-    training_step_with_pose(poses=) — and is the step as it was, launch for launch."""
+    training_step_with_pose(poses=) — and is the step as it was, launch for launch.
+
+    covis (a trainer.Covisibility of this model, with keyframes): ONE gslic_covis_record launch behind the backward (behind the pose step under
+    train_pose; it is independent of the camera kernel) replaces the column of the slot the step trained on — column = slot, so covis.n_frames must
+    be at least the store's capacity — by radii > 0 of the step's own forward, read from the capacity buffers; the column is named by the store's
+    frame word, so step(frame=j) changes target and recorded column together, eager and captured.  Its skip word is the forward's status word: a
+    step that did not fit records nothing, and check() repeats it with its frame.  The warm-up and capture passes record too, so the one word per
+    row that holds the loaded slot's column is saved and restored around them: building or re-capturing a step leaves no record behind.  covis
+    without keyframes raises ValueError (a host without a store calls covis.record(frame, step.visible)); covis=None is the step as it was,
+    launch for launch."""
 
     def __init__(self, model, camera, gt_image, bg, headroom=1.25, check_every=16, cap_R=None, cap_B=None, use_graph=False, gt_depth=None,
                  lambda_depth=0.0, weight=None, grad_stats=None, depth_weight=None, depth_huber=0.0, exposure=None, view=0, keyframes=None,
-                 frame=None, level=0, poses=None, train_pose=False):
+                 frame=None, level=0, poses=None, train_pose=False, covis=None):
         """use_graph=False (default since round 5): the capacity-mode step (caller-owned scratch, no host round trip, overflow checks and repeats as
         below) issued as eager launches; use_graph=True: captured in a hipGraph and replayed with one launch per step.  The two are equally fast at
         2M Gaussians (bench.py: `capacity_eager` / `graphed`; the host runs ahead of the device either way), and the eager form has no hazard:
@@ -2586,6 +2797,8 @@ class GraphedStep:
         self.keyframes, self.level = keyframes, int(level)
         # a store with depths under lambda_depth != 0: the depth target (and the store's depth weight) is decoded inside the step as well
         self._kf_depth = isinstance(keyframes, KeyframeStore) and keyframes.has_depths and lambda_depth != 0.0
+        # covis (a Covisibility of this model, with keyframes): every step that fits records radii > 0 into the column of the slot it trained on
+        self.covis = _covis_for_step(covis, model, keyframes if isinstance(keyframes, KeyframeStore) else None)
         if keyframes is None:
             if frame is not None or self.level != 0:
                 raise ValueError("GraphedStep: frame / level given without keyframes (pass a trainer.KeyframeStore)")
@@ -2708,8 +2921,10 @@ class GraphedStep:
             cam = rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad, camera_grads=True, cam_out=self._cam_grads)
             step_word = self.poses._step_shared_word if self._pose_shared else self.poses._step_word
             step_word(self._pose_word, cam, self.bufs.status[2:3])   # (skip: the forward's overflow word, as the exposure's)
-            return
-        rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad, grad_stats=self._gstat)
+        else:
+            rr.backward(dL_dimage, dL_ddepth, adam=self._adam, xyz_grad=self._xyz_grad, grad_stats=self._gstat)
+        if self.covis is not None:   # column = the slot the frame word names; a step that did not fit records nothing (skip: the same status word)
+            self.covis._record(self._kf_word, radii=self.bufs.radii, skip=self.bufs.status[2:3])
 
     def _capture(self):
         from . import rasterizer as rz
@@ -2731,6 +2946,9 @@ class GraphedStep:
         saved_ps = None if ps is None else [(a, a.clone()) for a in (ps.view, ps.proj, ps.campos, ps.m, ps.v, ps.steps, ps.grad)]
         if self._pose_shared:
             saved_ps += [(a, a.clone()) for a in (ps.sm, ps.sv, ps.ssteps, ps.X, ps.tau, ps.shared_grad)]
+        cv = self.covis   # the two passes record into the loaded slot's column: the one word per row that holds it is saved and restored
+        self._cv_addr = None if cv is None else cv._bits.data_ptr()
+        saved_cv = None if cv is None else cv._bits[:, self._kf_host >> 5].clone()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s), torch.no_grad():
@@ -2749,6 +2967,8 @@ class GraphedStep:
             a.copy_(keep)
         for a, keep in (saved_ex or []) + (saved_ps or []):
             a.copy_(keep)
+        if cv is not None:
+            cv._bits[:, self._kf_host >> 5].copy_(saved_cv)
         self.bufs.status.zero_()
         self.graph = g
         self.steps_issued = 0
@@ -2854,6 +3074,11 @@ class GraphedStep:
             if self.grad_stats._addresses() != self._gstat_addr:
                 raise RuntimeError("GraphedStep: the arrays of the GradientStats were reallocated since this step was built; the step holds the old "
                                    "addresses — build a new GraphedStep")
+        if self.covis is not None:
+            self.covis._check()
+            if self.covis._bits.data_ptr() != self._cv_addr:
+                raise RuntimeError("GraphedStep: the array of the Covisibility was reallocated since this step was built; the step holds the old "
+                                   "address — build a new GraphedStep")
         if self.graph is not None:
             self.graph.replay()
         else:

@@ -1348,6 +1348,56 @@ int gslic_densify_emit(
     uint32_t* tie_rank /*[>= P + count] or NULL*/, float scaling_raw_split, uint32_t seed, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * gslic_covis_* — covisibility sets: which keyframes see which Gaussians (no reference counterpart: its optimize() draws 100 keyframes at
+ * random, gaussian.cpp:644-662, and keeps no relation between keyframes and rows).  Signals only: which keyframe to give up, which window to
+ * train and which rows to protect stay the host's policy.
+ *
+ * THE DATA AND ITS RULE.  bits: uint32 [capacity, Wd], row-major, DEVICE, caller-owned, in STORAGE row order, with Wd = ceil(F / 32) dwords
+ * per row and F = n_frames in 1 .. GSLIC_COVIS_MAX_FRAMES.  Bit f of row r is bit (f & 31) of word r * Wd + (f >> 5), and means "frame f, when
+ * it was last recorded, had radii[r] > 0".  Bits f >= F of a row's last word are never set by the library and are ignored by the queries.  The
+ * state is per row and Wd dwords wide, so gslic_gather_rows / gslic_permute_rows and the zero segments of gslic_densify_emit's launch carry
+ * it through every map edit as one more row array of run-time width.  16 bytes per row at F = 128.  Every call below sees rows [0, P) only.
+ *
+ * gslic_covis_record — one launch, one thread per row of [row_begin, row_end) (row_end < 0: P).  With f = *frame_word:
+ *      seen(r) = radii[r] > 0          (radii given: int32 [P])
+ *              = visible[r] != 0       (visible given: uint8 [P])
+ *              = false                 (both NULL: the column is cleared — what a replaced keyframe slot needs)
+ *      word r * Wd + (f >> 5)  <-  (word & ~(1 << (f & 31))) | (seen(r) << (f & 31))
+ *  by one plain load and one plain store of that single word; the other words of the row are neither read nor written.  The call REPLACES
+ *  and does not OR: recording a frame again overwrites its column, so the state is a function of each frame's last record, whatever the order.
+ *  frame_word is a required DEVICE int32; a value outside [0, F) touches nothing.  skip is an optional DEVICE int32 [1]: nonzero touches
+ *  nothing (a training step passes its forward's status word, status[2]: a step that did not fit its buffers records nothing).  No
+ *  allocation, no read-back, no synchronisation, no atomics: the call can be captured in a graph, and a captured graph changes column through
+ *  the word.  Refused with GSLIC_ERR_INVALID_ARG before any device work: P < 0, F outside 1 .. GSLIC_COVIS_MAX_FRAMES, bits or frame_word
+ *  NULL, radii and visible both given, a row range outside 0 <= row_begin <= row_end <= P, bits ([P, Wd] x 4 bytes) overlapping radii,
+ *  visible, frame_word or skip.  An empty range returns at once.
+ *
+ * The three queries read bits and zero their outputs themselves (a memset node on the stream in front of the launch); every count is an
+ * unsigned integer sum, so the results are the same on every run whatever the order of the adds.  Rows are expected to be sparse in set bits:
+ * a thread owns a row and walks its set bits; counters live in the workgroup's LDS and are added to the output by integer atomics once per
+ * workgroup.  P == 0 gives zeros.
+ * gslic_covis_pair_counts  — pair[f * F + g] = number of rows r < P with bit f AND bit g.  Symmetric; the diagonal is each frame's visible
+ *      count.  F <= GSLIC_COVIS_MAX_PAIR_FRAMES (the upper triangle of 128 x 128 counters is 33 KB of LDS); a larger F is refused.
+ * gslic_covis_frame_counts — out[g] = number of rows with bit f AND bit g, f = *frame_word (DEVICE int32): the window query around one
+ *      keyframe, any F.  f outside [0, F) gives zeros.
+ * gslic_covis_row_counts   — n_seen[r] = popcount(row r AND frame_mask), frame_mask uint32 [Wd] on the DEVICE or NULL = every frame.  With
+ *      redundant given: redundant[f] = number of rows with bit f (of the row as stored, masked or not) and n_seen[r] >= 1 + min_others —
+ *      "f sees the row and so do at least min_others others" when f is in the mask.  min_others >= 0.
+ *  Refused before any device work: P < 0, F out of range, a NULL bits / output / frame_word, min_others < 0, an output overlapping bits, an
+ *  input or another output.
+ */
+#define GSLIC_COVIS_MAX_FRAMES 1024
+#define GSLIC_COVIS_MAX_PAIR_FRAMES 128
+int gslic_covis_record(
+    int32_t P, int32_t F, uint32_t* bits /*[P,Wd]*/, const int32_t* radii /*[P] or NULL*/, const uint8_t* visible /*[P] or NULL*/,
+    const int32_t* frame_word /*[1] device*/, const int32_t* skip /*[1] device or NULL*/, int32_t row_begin, int32_t row_end, void* stream);
+int gslic_covis_pair_counts(int32_t P, int32_t F, const uint32_t* bits, uint32_t* pair /*[F*F]*/, void* stream);
+int gslic_covis_frame_counts(int32_t P, int32_t F, const uint32_t* bits, const int32_t* frame_word /*[1] device*/, uint32_t* out /*[F]*/, void* stream);
+int gslic_covis_row_counts(
+    int32_t P, int32_t F, const uint32_t* bits, const uint32_t* frame_mask /*[Wd] or NULL*/, int32_t* n_seen /*[P]*/, int32_t min_others,
+    uint32_t* redundant /*[F] or NULL*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Introspection / measurement (no reference counterpart; used by bench.py and the tests).
  */
 int gslic_abi_version(void);
